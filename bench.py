@@ -10,6 +10,12 @@ region gather) over one batch of synthetic frames already resident in HBM.  One 
 GPU; frames shard across ranks with no data-path collective (weak scaling: --batch frames per
 GPU); the only collective is the broadcast of the weight blobs at init (RCCL over xGMI).
 Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times --steps steps and prints the headline (value, ms_per_step, the
+kernel configuration and the VALU / whole-pass figures computed from the step time).  --full adds
+what takes extra work: per-layer hipEvents in the timed steps with the roofline objects built on
+them, the CPU baseline and its bit comparison, and the sub-records of other sizes and precisions.
+--dump-outputs DIR writes what the last timed step computed, for comparing two builds.
 """
 import argparse
 import ctypes
@@ -225,6 +231,32 @@ def rccl_record(ctx, B, steps, dt_rank, dev):
 
 print_record = None                # set by main(): writes the one JSON line to the original stdout
 MFMA_PEAK_TFLOPS = 2500.0      # MI355X_MICROARCH.md: ~2.5 PF dense fp16/bf16
+DUMP_BUDGET_BYTES = 64_000_000     # --dump-outputs writes at most this much in all (every rank together)
+DUMP_SAMPLE_SEED = 0
+
+
+def dump_outputs(out_dir, arrays, rank, world):
+    """--dump-outputs: what the timed path handed its caller in the last timed step, one DIR/<name>.npy per array (float64 for scalars,
+    float32 otherwise: int16 and fp32 values convert exactly), for output-for-output comparison of two builds on the same seeded inputs.
+    With several ranks every rank writes its own shard as <name>_rank<r>.npy.  An array larger than what is left of this rank's share of
+    DUMP_BUDGET_BYTES is cut to a fixed seeded sample of its leading (frame) axis, and the frame indices go to <name>_frames.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    left = DUMP_BUDGET_BYTES // world - 4096 * len(arrays)          # minus room for the .npy headers
+    sfx = f"_rank{rank}" if world > 1 else ""
+    wrote = []
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = a.astype(np.float64 if a.ndim <= 1 else np.float32)
+        if a.nbytes > left and a.ndim > 1:
+            k = max(1, (left - 8 * a.shape[0]) // a[0].nbytes)
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(a.shape[0], k, replace=False))
+            a = a[idx]
+            np.save(os.path.join(out_dir, f"{name}_frames{sfx}.npy"), idx.astype(np.float64))
+            left -= idx.size * 8
+        np.save(os.path.join(out_dir, f"{name}{sfx}.npy"), a)
+        left -= a.nbytes
+        wrote.append(f"{name}{sfx}.npy {tuple(a.shape)}")
+    print(f"bench.py[rank {rank}]: outputs of the last timed step in {out_dir}: {', '.join(wrote)}", file=sys.stderr, flush=True)
 
 
 def fp16_solo_layer_ms(ctx, frames, region, Bl, stream, dev, steps=5):
@@ -309,6 +341,24 @@ def fp16_traffic(kernel, Bl):
     return e["hbm_bytes_per_launch"], e["algorithmic_bytes_per_launch"], F16_TRAFFIC_FILE
 
 
+def fp16_headline(ctx, B, steps, dt, world=1, lanes=None):
+    """What the fp16 line reports from the timed steps alone: `dt` seconds for `steps` passes over B frames per GPU -> the rate, the
+    step time, the launch table and the chip-level `whole_pass` object (no per-layer times, no run of its own)."""
+    lanes = ctx.num_lanes_fp16() if lanes is None else lanes
+    Bl = B // lanes
+    kern = ctx.fp16_layer_kernels()
+    chip_ach = 2.0 * net.macs_per_frame() * B / (dt / steps) / 1e12
+    return {
+        "value": world * B * steps / dt, "unit": "frames/s", "ms_per_step": dt / steps * 1e3, "steps": steps, "dtype": "f16",
+        "config": {"workload": f"YOLOv2 fp16 416x416 batch={B} per GPU, MFMA implicit-GEMM conv (fp32 accumulate)",
+                   "batch_per_gpu": B, "global_batch": B * world, "lanes": lanes, "frames_per_launch": Bl,
+                   "kernels": {str(i): k for i, k in sorted(kern.items())}},
+        # chip level, independent of how the lanes' launches overlap: all conv FLOPs of the step / wall time of the step
+        "whole_pass": {"scope": "all conv FLOPs of one step (both lanes) / ms_per_step", "achieved": chip_ach, "unit": "TFLOP/s",
+                       "frac": chip_ach / MFMA_PEAK_TFLOPS},
+    }
+
+
 def fp16_record(ctx, B, steps, dt, layer_ms, world=1, solo_ms=None):
     """Roofline objects of the fp16 MFMA path from one timed run: `dt` seconds for `steps` passes over B frames per GPU,
     layer_ms = the library's per-layer hipEvent times of lane 0 (overlapped with the other lane's launches), solo_ms = the same
@@ -326,13 +376,10 @@ def fp16_record(ctx, B, steps, dt, layer_ms, world=1, solo_ms=None):
     halo_launch_ach = halo_ach
     if solo_ms is None:                                          # (multi-GPU line: no solo pass; lane 0's overlapped launches x lanes, upper bound)
         halo_ach = halo_launch_ach * lanes
-    chip_ach = 2.0 * net.macs_per_frame() * B / (dt / steps) / 1e12
+    head = fp16_headline(ctx, B, steps, dt, world, lanes)
     traffic, traffic_alg, traffic_src = fp16_traffic("k_conv_f16_halo<256,2,16>", Bl)
     return {
-        "value": world * B * steps / dt, "unit": "frames/s", "ms_per_step": dt / steps * 1e3, "steps": steps, "dtype": "f16",
-        "config": {"workload": f"YOLOv2 fp16 416x416 batch={B} per GPU, MFMA implicit-GEMM conv (fp32 accumulate)",
-                   "batch_per_gpu": B, "global_batch": B * world, "lanes": lanes, "frames_per_launch": Bl,
-                   "kernels": {str(i): k for i, k in sorted(kern.items())}},
+        **{k: head[k] for k in ("value", "unit", "ms_per_step", "steps", "dtype", "config")},
         # dominant kernel: k_conv_f16_halo (3x3 layers at <= 52x52 with >= 128 output channels, as the launch table reports them)
         # - its layers' FLOPs / their hipEvent time; whole_pass = all conv layers (incl. fused pools and fused 1x1 layers)
         "roofline": {"bound": "mfma", "kernel": "k_conv_f16_halo", "launches_per_step": len(halo), "layers": [l.idx for l in halo],
@@ -346,9 +393,7 @@ def fp16_record(ctx, B, steps, dt, layer_ms, world=1, solo_ms=None):
                               "lane's share, hipEvents inside the library); the step itself runs two such launches side by side: whole_pass")
                              if solo_ms is not None else
                              "achieved = lanes x (FLOPs of lane 0's launch / its duration while the other lane's launches run beside it): an upper bound"},
-        # chip level, independent of how the lanes' launches overlap: all conv FLOPs of the step / wall time of the step
-        "whole_pass": {"scope": "all conv FLOPs of one step (both lanes) / ms_per_step", "achieved": chip_ach, "unit": "TFLOP/s",
-                       "frac": chip_ach / MFMA_PEAK_TFLOPS},
+        "whole_pass": head["whole_pass"],
         "mfma_busy": fp16_mfma_busy(),
         "layer_ms": [round(float(x), 4) for x in layer_ms], "conv_ms_per_step": conv_ms,
     }
@@ -416,7 +461,8 @@ def bench_fp16(args, world, rank, local_rank, dev):
 
     for _ in range(args.warmup):
         step()
-    ctx.set_profiling(True)
+    if args.full:
+        ctx.set_profiling(True)
     fence()
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -428,23 +474,31 @@ def bench_fp16(args, world, rank, local_rank, dev):
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    layer_ms = ctx.layer_times_ms()
-    ctx.set_profiling(False)
-    solo = None
-    if world == 1 and ctx.num_lanes_fp16() > 1:      # the per-kernel object from launches that have the chip to themselves
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"region": region.cpu().numpy()}, rank, world)
+    layer_ms, solo = None, None
+    if args.full:
+        layer_ms = ctx.layer_times_ms()
+        ctx.set_profiling(False)
+    if args.full and world == 1 and ctx.num_lanes_fp16() > 1:      # the per-kernel object from launches that have the chip to themselves
         lanes = ctx.num_lanes_fp16()
         region0 = region[0].clone()
         solo = (fp16_solo_layer_ms(ctx, frames, region, B // lanes, stream, dev), B // lanes)
         region[0].copy_(region0)
     if rank == 0:
-        rec = fp16_record(ctx, B, args.steps, dt, layer_ms, world, solo_ms=solo)
+        if args.full:
+            rec = fp16_record(ctx, B, args.steps, dt, layer_ms, world, solo_ms=solo)
+            keys = ("config", "roofline", "whole_pass", "mfma_busy", "layer_ms", "conv_ms_per_step")
+        else:
+            rec = fp16_headline(ctx, B, args.steps, dt, world)
+            keys = ("config", "whole_pass")
         result = {"metric": "YOLOv2 fp16 416x416 frames/sec", "value": rec["value"], "unit": "frames/s", "n_gpus": world,
                   "steps": args.steps, "warmup": args.warmup, "ms_per_step": rec["ms_per_step"],
                   "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f16", "data": "synthetic"}
-        result.update({k: rec[k] for k in ("config", "roofline", "whole_pass", "mfma_busy", "layer_ms", "conv_ms_per_step")})
+        result.update({k: rec[k] for k in keys})
         if rccl is not None:
             result["rccl"], result["per_rank"] = rccl, per_rank
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             import orclib
             orclib.oracle().orc_set_threads(1)
             t0c = time.perf_counter()
@@ -833,14 +887,23 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=64, help="frames per GPU per step (configs[2]: 64)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: per-layer hipEvent times of the timed steps and the roofline objects built on "
+                         "them, cpu_baseline with its bit comparison, the sub-records (c5_b256_per_gpu, latency_b1, e2e_u8_b64, fp16_b256, "
+                         "fp32tol_b128, fp32_exact_b32) and, for --precision fp16, the solo-lane pass")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed (the region tensor; int16: and its final Q) as "
+                         "DIR/<name>.npy in float32 / float64, at most 64 MB in all")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out cpu_baseline")
     ap.add_argument("--no-sub-records", action="store_true",
-                    help="skip the latency_b1 (configs[1]) and fp16_b256 (configs[3]) sub-records of the default line")
+                    help="with --full: leave out the sub-records of the default line")
     ap.add_argument("--dry-launch", action="store_true",
                     help="rehearse the --gpus N launcher without a GPU: the ranks only report the environment they were started with")
     ap.add_argument("--precision", choices=["int16", "fp16"], default="int16",
                     help="int16 = the headline bit-exact path; fp16 = MFMA implicit-GEMM path (configs[3], use --batch 256)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # ---- which process is this?  (a) a rank: RANK / LOCAL_RANK / WORLD_SIZE are in the environment (torch.distributed.run, or
     # the launcher below);  (b) `python bench.py --gpus N` typed plainly with N > 1: the launcher - it starts N fresh rank
@@ -909,7 +972,8 @@ def main():
 
     for _ in range(args.warmup):
         step()
-    ctx.set_profiling(True)      # hipEvent pairs around every layer launch, on `stream`
+    if args.full:
+        ctx.set_profiling(True)      # hipEvent pairs around every layer launch, on `stream`
     fence()
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -921,31 +985,19 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    layer_ms = ctx.layer_times_ms()
-    ctx.set_profiling(False)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"final_q": [ctx.final_q], "region": region.cpu().numpy()}, rank, world)
+    layer_ms = None
+    if args.full:
+        layer_ms = ctx.layer_times_ms()
+        ctx.set_profiling(False)
 
     if rank == 0:
         fps = world * B * args.steps / dt
         paths = ctx.layer_paths()
         lanes = ctx.num_lanes()          # every layer is `lanes` concurrent part-batch launches (3 at batch 64: 21 + 21 + 22)
         Bl = B // lanes                  # frames per launch of lane 0, the one the per-layer hipEvents time (the remainder goes to the last lanes)
-        # dominant kernel = the conv kernel instantiation with the largest total time
-        groups = {}
         fused = ctx.pool_fused_layers()      # convs that run as k_conv_i16_pool (conv + leaky + 2x2 pool in one kernel)
-        for l in net.CONVS:
-            info = ctx.conv_launch_info(l.ord)
-            key = (l.size, "pool" if l.idx in fused else info["pixels_per_lane"], paths[l.ord])
-            g = groups.setdefault(key, {"ms": 0.0, "launches": 0, "bytes": 0.0, "steps": 0, "layers": []})
-            g["ms"] += float(layer_ms[l.idx])
-            g["launches"] += 1
-            g["bytes"] += conv_layer_bytes(l, Bl)
-            g["steps"] += l.size * l.size * ((l.c + 3) // 4) * l.n * l.out_h * l.out_w * Bl
-            g["layers"].append(l.idx)
-        key, g = max(groups.items(), key=lambda kv: kv[1]["ms"])
-        avg_ms = g["ms"] / g["launches"]
-        ach = (g["bytes"] / g["launches"]) / (avg_ms * 1e-3) / 1e9
-        kname = f"k_conv_i16_pool<MODE={key[2]}>" if key[1] == "pool" else f"k_conv_i16<KS={key[0]},P={key[1]},MODE={key[2]}>"
-        conv_ms = float(sum(layer_ms[l.idx] for l in net.CONVS))
         # VALU issue roofline over the whole step (chip level, independent of how launches overlap):
         # SIMD issue cycles the conv steps of one batch need at the measured instruction costs
         # / cycles available in ms_per_step on 1024 SIMDs at the 2.4 GHz maximum clock
@@ -970,9 +1022,6 @@ def main():
                             "scalar loads and LDS reads compiled out - a pure VALU loop over the step sequence - runs at the same rate "
                             "(profiles/r03_i16_ablation_b256.txt), and a register-only loop of the sequence costs 13.5 of these cycles per "
                             "step, not 12 (profiles/r03_ubench_step.txt)"}
-        traffic, traffic_src = hbm_traffic_per_launch(key[0], B)
-        fam = [l for l in net.CONVS if l.size == key[0] and l.idx not in fused]     # the scope of `traffic`: all k_conv_i16 launches of this kernel size
-        fam_alg = sum(conv_layer_bytes(l, Bl) for l in fam) / len(fam)
         result = {
             "metric": "YOLOv2 INT16 416x416 frames/sec", "value": fps, "unit": "frames/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -984,35 +1033,57 @@ def main():
                        "lanes": lanes, "frames_per_launch": Bl, "conv_pool_fused_layers": fused,
                        "conv_plans": {l.idx: ctx.conv_plan(l.ord) for l in net.CONVS}, "conv_plan_source": ctx.plan_source(),
                        "options": ctx.options()},
-            "roofline": {"bound": "hbm", "kernel": kname, "launches_per_step": g["launches"], "layers": g["layers"],
-                         "avg_launch_ms": avg_ms, "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": ach / HBM_PEAK_GBS, "traffic": traffic, "traffic_unit": "bytes per launch", "traffic_source": traffic_src,
-                         "traffic_scope": f"mean over the {len(fam)} conv{key[0]}x{key[0]} launches per lane and step (k_conv_i16 and k_conv_i16_w16 "
-                                          "instantiations of that kernel size); L2-to-fabric bytes, Infinity Cache hits included",
-                         "algorithmic_bytes_per_launch_same_scope": fam_alg,
-                         "algorithmic_bytes_per_launch": g["bytes"] / g["launches"],
-                         "binds": False,
-                         "note": "BASELINE.json asks for the HBM fraction of the int16 path; by construction it is a few per cent "
-                                 "(SURVEY.md 8d): the path is integer-VALU-issue bound, see binding_roofline"},
-            "binding_roofline": "valu_roofline",
-            "valu_roofline": valu,
-            "layer_ms": [round(float(x), 4) for x in layer_ms],
-            "conv_ms_per_step": conv_ms,
         }
+        if args.full:
+            # dominant kernel = the conv kernel instantiation with the largest total time (per-layer hipEvents of the timed steps)
+            groups = {}
+            for l in net.CONVS:
+                info = ctx.conv_launch_info(l.ord)
+                key = (l.size, "pool" if l.idx in fused else info["pixels_per_lane"], paths[l.ord])
+                g = groups.setdefault(key, {"ms": 0.0, "launches": 0, "bytes": 0.0, "steps": 0, "layers": []})
+                g["ms"] += float(layer_ms[l.idx])
+                g["launches"] += 1
+                g["bytes"] += conv_layer_bytes(l, Bl)
+                g["steps"] += l.size * l.size * ((l.c + 3) // 4) * l.n * l.out_h * l.out_w * Bl
+                g["layers"].append(l.idx)
+            key, g = max(groups.items(), key=lambda kv: kv[1]["ms"])
+            avg_ms = g["ms"] / g["launches"]
+            ach = (g["bytes"] / g["launches"]) / (avg_ms * 1e-3) / 1e9
+            kname = f"k_conv_i16_pool<MODE={key[2]}>" if key[1] == "pool" else f"k_conv_i16<KS={key[0]},P={key[1]},MODE={key[2]}>"
+            traffic, traffic_src = hbm_traffic_per_launch(key[0], B)
+            fam = [l for l in net.CONVS if l.size == key[0] and l.idx not in fused]     # the scope of `traffic`: all k_conv_i16 launches of this kernel size
+            fam_alg = sum(conv_layer_bytes(l, Bl) for l in fam) / len(fam)
+            result["roofline"] = {
+                "bound": "hbm", "kernel": kname, "launches_per_step": g["launches"], "layers": g["layers"],
+                "avg_launch_ms": avg_ms, "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": ach / HBM_PEAK_GBS, "traffic": traffic, "traffic_unit": "bytes per launch", "traffic_source": traffic_src,
+                "traffic_scope": f"mean over the {len(fam)} conv{key[0]}x{key[0]} launches per lane and step (k_conv_i16 and k_conv_i16_w16 "
+                                 "instantiations of that kernel size); L2-to-fabric bytes, Infinity Cache hits included",
+                "algorithmic_bytes_per_launch_same_scope": fam_alg,
+                "algorithmic_bytes_per_launch": g["bytes"] / g["launches"],
+                "binds": False,
+                "note": "BASELINE.json asks for the HBM fraction of the int16 path; by construction it is a few per cent "
+                        "(SURVEY.md 8d): the path is integer-VALU-issue bound, see binding_roofline"}
+        result["binding_roofline"] = "valu_roofline"
+        result["valu_roofline"] = valu
+        if args.full:
+            result["layer_ms"] = [round(float(x), 4) for x in layer_ms]
+            result["conv_ms_per_step"] = float(sum(layer_ms[l.idx] for l in net.CONVS))
         if rccl is not None:
             result["rccl"], result["per_rank"] = rccl, per_rank
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             idx = [0, B - 1]    # first frame of the first lane, last frame of the last
             result["cpu_baseline"] = cpu_baseline(model, [frames[i].cpu().numpy() for i in idx],
                                                   [region[i].cpu().numpy() for i in idx])
-    r0 = region[0].clone()
-    if not args.no_sub_records:
+    sub_records = args.full and not args.no_sub_records
+    if sub_records:
+        r0 = region[0].clone()
         # configs[4] at its own shard size (256 frames per GPU), on EVERY rank count incl. 1: a collective sub-record
         c5 = sub_c5_b256(ctx, rank, world, dev)
         if rank == 0:
             result["c5_b256_per_gpu"] = c5
     if rank == 0:
-        if world == 1 and not args.no_sub_records:
+        if world == 1 and sub_records:
             # configs[1] and configs[3] under the same clock as the headline: ~10 s together
             result["latency_b1"] = sub_latency_b1(ctx, frames, region, dev)
             result["latency_b1"]["matches_batched_result_bit_exact"] = bool(torch.equal(region[0], r0))

@@ -112,9 +112,9 @@ def test_own_weight_gen_matches_reference_tool_and_python(tmp_path):
         assert r.returncode == 0, r.stderr
         assert open(out, "rb").read() == open(tmp_path / "weights" / ours, "rb").read(), prec
         ref_tool = os.path.join(orclib.REF_DIR, "yolov2_weight_gen")
-        if os.path.exists(ref_tool) and os.path.exists("/root/reference/config/yolov2.cfg"):
+        if os.path.exists(ref_tool):
             ref_out = tmp_path / f"ref_{prec}.bin"
-            subprocess.run([ref_tool, "--cfg", "/root/reference/config/yolov2.cfg", "--weights", str(tmp_path / "weights" / src),
+            subprocess.run([ref_tool, "--cfg", orclib.REF_CFG, "--weights", str(tmp_path / "weights" / src),
                             "--out", str(ref_out), "--precision", prec], check=True, capture_output=True, cwd=str(tmp_path))
             assert open(out, "rb").read() == open(ref_out, "rb").read(), prec
     r = subprocess.run([os.path.join(PKG, "yolov2_weight_gen"), "--weights", "/nonexistent.bin", "--cfg", cfg], capture_output=True, text=True)

@@ -9,10 +9,10 @@ TAG=$1; shift
 export TMPDIR=/tmp
 OUT=$PWD/gpurun_out/clock_$TAG
 rm -rf "$OUT"; mkdir -p "$OUT"
-rocprofv3 --kernel-trace --pmc GRBM_GUI_ACTIVE --output-format csv -d "$OUT" -- python3 bench.py --no-cpu-baseline --no-sub-records "$@" > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -20 "$OUT/bench.err"; exit 1; }
+rocprofv3 --kernel-trace --pmc GRBM_GUI_ACTIVE --output-format csv -d "$OUT" -- python3 bench.py --full --no-cpu-baseline --no-sub-records "$@" > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -20 "$OUT/bench.err"; exit 1; }
 CSV=$(find "$OUT" -name "*counter_collection.csv" | head -1)
 {
-echo "# rocprofv3 --kernel-trace --pmc GRBM_GUI_ACTIVE -- python3 bench.py --no-cpu-baseline --no-sub-records $*"
+echo "# rocprofv3 --kernel-trace --pmc GRBM_GUI_ACTIVE -- python3 bench.py --full --no-cpu-baseline --no-sub-records $*"
 echo "# effective clock per dispatch = GRBM_GUI_ACTIVE / 8 / duration; dispatches of >= 0.3 ms only; dispatches are serialised under counter collection"
 python3 - "$CSV" <<'PY'
 import csv, sys, collections, statistics

@@ -12,7 +12,7 @@ OUT=$PWD/gpurun_out/f16_traffic_$TAG
 rm -rf "$OUT"; mkdir -p "$OUT"
 for CNT in FETCH_SIZE WRITE_SIZE; do
   D="$OUT/$CNT"; mkdir -p "$D"
-  rocprofv3 --kernel-trace --pmc $CNT --output-format csv -d "$D" -- python3 bench.py --no-cpu-baseline --no-sub-records --precision fp16 --batch 256 --steps 3 --warmup 1 > "$D/bench.json" 2> "$D/bench.err" || { tail -20 "$D/bench.err"; exit 1; }
+  rocprofv3 --kernel-trace --pmc $CNT --output-format csv -d "$D" -- python3 bench.py --full --no-cpu-baseline --no-sub-records --precision fp16 --batch 256 --steps 3 --warmup 1 > "$D/bench.json" 2> "$D/bench.err" || { tail -20 "$D/bench.err"; exit 1; }
   echo "pass $CNT done"
 done
 python3 tools/f16_traffic.py "$OUT" "$PWD/gpurun_out/f16_traffic_$TAG.json" | tee "$PWD/gpurun_out/f16_traffic_${TAG}_summary.txt"

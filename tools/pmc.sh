@@ -7,7 +7,7 @@ TAG=$1; CNT=$2; shift; shift
 export TMPDIR=/tmp
 OUT=$PWD/gpurun_out/pmc_$TAG
 rm -rf "$OUT"; mkdir -p "$OUT"
-rocprofv3 --kernel-trace --pmc $CNT --output-format csv -d "$OUT" -- python3 bench.py --no-cpu-baseline "$@" > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -20 "$OUT/bench.err"; exit 1; }
+rocprofv3 --kernel-trace --pmc $CNT --output-format csv -d "$OUT" -- python3 bench.py --full --no-cpu-baseline "$@" > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -20 "$OUT/bench.err"; exit 1; }
 CSV=$(find "$OUT" -name "*counter_collection.csv" | head -1)
 python3 - "$CSV" <<'PY' | tee "$PWD/gpurun_out/pmc_${TAG}_summary.txt"
 import csv, sys, collections

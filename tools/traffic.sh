@@ -15,14 +15,14 @@ rm -rf "$OUT"; mkdir -p "$OUT"
 for CNT in FETCH_SIZE WRITE_SIZE; do
   for N in 2 6; do
     D="$OUT/${CNT}_$N"; mkdir -p "$D"
-    rocprofv3 --kernel-trace --pmc $CNT --output-format csv -d "$D" -- python3 bench.py --no-cpu-baseline --no-sub-records --warmup 0 --steps $N "$@" > "$D/bench.json" 2> "$D/bench.err" || { tail -20 "$D/bench.err"; exit 1; }
+    rocprofv3 --kernel-trace --pmc $CNT --output-format csv -d "$D" -- python3 bench.py --full --no-cpu-baseline --no-sub-records --warmup 0 --steps $N "$@" > "$D/bench.json" 2> "$D/bench.err" || { tail -20 "$D/bench.err"; exit 1; }
     echo "pass $CNT steps=$N done"
   done
 done
 export YOLO2_NO_POOLFUSE=1
 for N in 2 6; do
   D="$OUT/CAL_FETCH_SIZE_$N"; mkdir -p "$D"
-  rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d "$D" -- python3 bench.py --no-cpu-baseline --no-sub-records --warmup 0 --steps $N "$@" > "$D/bench.json" 2> "$D/bench.err" || { tail -20 "$D/bench.err"; exit 1; }
+  rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d "$D" -- python3 bench.py --full --no-cpu-baseline --no-sub-records --warmup 0 --steps $N "$@" > "$D/bench.json" 2> "$D/bench.err" || { tail -20 "$D/bench.err"; exit 1; }
   echo "calibration pass steps=$N done"
 done
 unset YOLO2_NO_POOLFUSE
