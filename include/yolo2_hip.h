@@ -90,6 +90,8 @@ int yolo2_execute_maxpool_layer(uint64_t input_addr, uint64_t output_addr, int c
  * -1 = the generic one-thread-per-output kernel for shapes the tiled kernel does not cover).  The
  * per-layer calls prove the form for the whole layer from the weights and Q values of that call. */
 int yolo2_hip_last_layer_path(void);
+/* 1 if the last int16 conv of the driver tier ran edge-class pixel tiles (yolo2_hip_i16_edge_map), else 0. */
+int yolo2_hip_last_layer_edge(void);
 
 /* fp32 twin of the conv call (host-sim form YOLO2_FPGA without INT16_MODE,
  * hls/models/yolov2/yolo2_accel.hpp:10-17): float tensors, Q arguments absent. */
@@ -342,6 +344,12 @@ int yolo2_hip_i16_plan_check(int splits, int cg_out, int npix, size_t cap_bytes)
 /* Bytes of that scratch the context holds for its current batch: the largest splits x items x pixels x 24 among the plans that were
  * accepted - 0 when no layer runs the K-split kernel (round 3 held 66 MB per frame for every context of <= 4 frames). */
 size_t yolo2_hip_ks_scratch_bytes(yolo2_hip_ctx *ctx);
+/* Edge-class pixel tiles of the int16 3x3 conv (forms C / D, one pixel per lane): the partition of B frames of H x W pixels that the
+ * kernel decodes, on plain numbers (no GPU).  Returns the number of tiles (0: the geometry keeps raster tiles); with non-null
+ * arrays of room for `cap` tiles it also fills tile_cls[t] (0 top row, 1 bottom row, 2 left column, 3 right column, 4 interior,
+ * 5 mixed), tile_mask[t] (the taps the tile runs, bit 3i + j for tap row i and column j) and pix[64 t + lane] (the pixel's raster
+ * index (b H + y) W + x, or -1 for a padding lane), and *steps = the pixel x tap visits of the grid. */
+int yolo2_hip_i16_edge_map(int B, int H, int W, int cap, int *tile_cls, int *tile_mask, int *pix, long long *steps);
 
 /* fp32 whole network in the reference's own arithmetic (what yolov2_hls_ps does at Precision::FP32,
  * hls/models/yolov2/yolo2_model.cpp:229-449: compute() fp32 branch core_compute.cpp:121-172 in its

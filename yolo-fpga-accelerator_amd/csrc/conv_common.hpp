@@ -39,6 +39,14 @@ struct ConvArgs {
     // and leaves the clamp-affine triples of its sub-chains in ks_trip[z][channel item][pixel][2 pairs][a, l, h]
     int ks_S, ks_Q, ks_mb;     // splits, groups per split, blocks in this launch (grid.y / ks_S)
     int *ks_trip;
+    // edge-class pixel tiles (k_conv_i16<3, 1, 3|4, NST, 1, true>; set by edge_tiles_plan, see there)
+    int edge;                  // 1: grid.x counts edge-class tiles instead of raster tiles
+    int e_nt, e_nb;            // tiles in all, band tiles among them
+    int e_band[4];             // cumulative full-tile counts of the band classes: top, + bottom, + left, + right
+    int e_int;                 // full interior tiles (the mixed tiles follow them)
+    int e_n[5];                // pixels per class: top, bottom, left, right, interior
+    int e_rem[6];              // cumulative class remainders n % 64: the mixed pixels of class c are [e_rem[c], e_rem[c + 1])
+    unsigned mH2, sH2, mW2, sW2, mI2, sI2;   // division by H - 2, W - 2, (H - 2)(W - 2)
 };
 
 inline void set_conv_div(ConvArgs &a)
@@ -77,6 +85,151 @@ __device__ __forceinline__ int flat_of(const ConvArgs &a, int q)
     const int y = div_c(r, a.mW, a.sW);
     const int x = r - y * a.W;
     return b * a.PL + (y + 1) * a.Wp + x;
+}
+
+// ---- edge-class pixel tiles (3x3 'same' convs, H, W >= 3) ---------------------------------------------------------------------
+//
+// A tap outside the image reads a stored zero and its step leaves the accumulator as it was (sat16(acc + 0) = acc in every form),
+// but a raster tile's 64 pixels span several rows, so no tap is out of the image for all of them.  Edge-class tiles group the real
+// pixels by the set of taps that can be in the image:
+//   top row (corners included, taps of rows 0, +1), bottom row (rows -1, 0), left column of rows 1 .. H-2 (columns 0, +1),
+//   right column of rows 1 .. H-2 (columns -1, 0): 6 taps each; interior: 9 taps.
+// Each class is ordered (b, y, x); its full 64-pixel tiles run only the class's taps.  The remainders of all five classes (< 64
+// each) are concatenated into "mixed" tiles that run all 9.  Grid order: the band tiles are interleaved evenly among interior +
+// mixed tiles (Bresenham), so that every XCD's contiguous tile range and every CU get the same share of 6-tap work.
+// Host and device share these functions: the host partition check (yolo2_hip_i16_edge_map) runs exactly the kernel's decode.
+enum { kEdgeTop = 0, kEdgeBottom = 1, kEdgeLeft = 2, kEdgeRight = 3, kEdgeInterior = 4, kEdgeMixed = 5 };
+
+// taps (i, j) = (row 0..2, column 0..2) as bit 3i + j
+__host__ __device__ constexpr int edge_class_mask(int cls)
+{
+    return cls == kEdgeTop ? 0x1f8 : cls == kEdgeBottom ? 0x03f : cls == kEdgeLeft ? 0x1b6 : cls == kEdgeRight ? 0x0db : 0x1ff;
+}
+
+__host__ __device__ inline unsigned edge_div(unsigned n, unsigned m, unsigned s)   // fast_div, also on the host; s = 32: divisor 1
+{
+    if (s >= 32) return n;
+    const unsigned t = (unsigned)(((unsigned long long)m * n) >> 32);
+    return (t + ((n - t) >> 1)) >> s;
+}
+
+// tile (logical index, after the XCD numbering) -> class and index of the tile within its class
+__host__ __device__ inline int edge_tile_class(const ConvArgs &a, int tile, int &ct)
+{
+    const unsigned nb = (unsigned)a.e_nb, nt = (unsigned)a.e_nt;   // (the host keeps nt * nb < 2^32)
+    const int c0 = (int)((unsigned)tile * nb / nt), c1 = (int)((unsigned)(tile + 1) * nb / nt);
+    if (c1 > c0) {
+        int c = 0;
+        while (c < 3 && c0 >= a.e_band[c]) ++c;
+        ct = c0 - (c ? a.e_band[c - 1] : 0);
+        return c;
+    }
+    const int o = tile - c0;
+    if (o < a.e_int) { ct = o; return kEdgeInterior; }
+    ct = o - a.e_int;
+    return kEdgeMixed;
+}
+
+// pixel `lane` of tile ct of class cls -> (b, y, x); false for the padding lanes of the last mixed tile (which get its last pixel)
+__host__ __device__ inline bool edge_lane_pixel(const ConvArgs &a, int cls, int ct, int lane, int &b, int &y, int &x)
+{
+    int i = ct * 64 + lane;
+    bool valid = true;
+    if (cls == kEdgeMixed) {
+        const int nm = a.e_rem[5];
+        valid = i < nm;
+        if (!valid) i = nm - 1;
+        int c = 0;
+        while (c < 4 && i >= a.e_rem[c + 1]) ++c;
+        i = a.e_n[c] - (a.e_rem[c + 1] - a.e_rem[c]) + (i - a.e_rem[c]);
+        cls = c;
+    }
+    if (cls == kEdgeTop || cls == kEdgeBottom) {
+        b = (int)edge_div((unsigned)i, a.mW, a.sW);
+        x = i - b * a.W;
+        y = cls == kEdgeTop ? 0 : a.H - 1;
+    } else if (cls == kEdgeLeft || cls == kEdgeRight) {
+        b = (int)edge_div((unsigned)i, a.mH2, a.sH2);
+        y = 1 + i - b * (a.H - 2);
+        x = cls == kEdgeLeft ? 0 : a.W - 1;
+    } else {
+        b = (int)edge_div((unsigned)i, a.mI2, a.sI2);
+        const int r = i - b * ((a.H - 2) * (a.W - 2));
+        const int yy = (int)edge_div((unsigned)r, a.mW2, a.sW2);
+        y = 1 + yy;
+        x = 1 + r - yy * (a.W - 2);
+    }
+    return valid;
+}
+
+// LDS items of a gathered (mixed) tile: [tap row i][lane][tap column j], 9 slots per lane
+constexpr int kEdgeGatherItems = 3 * 64 * 3;
+
+// The per-frame patch a band tile stages (items of frame b start at flat b PL + org; Lf items per frame; LDS row pitch):
+//   top / bottom: image rows {0, 1} / {H-2, H-1} from column -1 to column W, i.e. 2 Wp + 1 consecutive items, pitch Wp;
+//   left / right: columns {0, 1} / {W-2, W-1} of image rows 0 .. H-1, 2 items per row, pitch 2.
+__host__ __device__ inline void edge_band_patch(const ConvArgs &a, int cls, int &org, int &Lf, int &pitch)
+{
+    const bool rows = cls == kEdgeTop || cls == kEdgeBottom;
+    Lf = rows ? 2 * a.Wp + 1 : 2 * a.H;
+    pitch = rows ? a.Wp : 2;
+    org = cls == kEdgeTop ? a.Wp - 1 : cls == kEdgeBottom ? (a.H - 1) * a.Wp - 1 : cls == kEdgeLeft ? a.Wp : a.Wp + a.W - 2;
+}
+
+// The partition of a's geometry (B, H, W, Wp, PL and the set_conv_div fields already set) into edge-class tiles: fills the e_*
+// fields and returns the LDS tile the launch needs (items: the gathered layout or the longest interior run, whichever is
+// larger), or 0 if the geometry is not eligible (H or W < 3, or too many tiles for the 32-bit interleave).
+inline int edge_tiles_plan(ConvArgs &a)
+{
+    a.edge = 0;
+    if (a.H < 3 || a.W < 3) return 0;
+    const long B = a.B, H = a.H, W = a.W;
+    const long n[5] = {B * W, B * W, B * (H - 2), B * (H - 2), B * (H - 2) * (W - 2)};
+    if (n[4] + 2 * n[0] + 2 * n[2] >= (1L << 30)) return 0;
+    a.e_rem[0] = 0;
+    int nb = 0;
+    for (int c = 0; c < 5; ++c) {
+        a.e_n[c] = (int)n[c];
+        a.e_rem[c + 1] = a.e_rem[c] + (int)(n[c] % 64);
+        if (c < 4) { nb += (int)(n[c] / 64); a.e_band[c] = nb; }
+    }
+    a.e_int = (int)(n[4] / 64);
+    a.e_nb = nb;
+    a.e_nt = nb + a.e_int + (a.e_rem[5] + 63) / 64;
+    if ((unsigned long long)a.e_nt * (unsigned long long)(a.e_nb + 1) >= (1ULL << 32)) return 0;
+    auto magic = [](unsigned d, unsigned &m, unsigned &s) { if (d < 2) { m = 0; s = 32; } else fast_div_magic(d, m, s); };
+    magic((unsigned)(H - 2), a.mH2, a.sH2);
+    magic((unsigned)(W - 2), a.mW2, a.sW2);
+    magic((unsigned)((H - 2) * (W - 2)), a.mI2, a.sI2);
+    // interior tiles stage one contiguous run (first pixel - halo .. last pixel + halo), band tiles one patch per frame they
+    // touch, mixed tiles the gathered layout: the longest of them
+    int lt = kEdgeGatherItems;
+    for (int c = kEdgeTop; c <= kEdgeRight; ++c) {
+        int org, Lf, pitch;
+        edge_band_patch(a, c, org, Lf, pitch);
+        for (int t = 0; t < a.e_band[c] - (c ? a.e_band[c - 1] : 0); ++t) {
+            int b0, b1, y, x;
+            edge_lane_pixel(a, c, t, 0, b0, y, x);
+            edge_lane_pixel(a, c, t, 63, b1, y, x);
+            lt = lt > (b1 - b0 + 1) * Lf ? lt : (b1 - b0 + 1) * Lf;
+        }
+    }
+    for (int t = 0; t < a.e_int; ++t) {
+        int b0, y0, x0, b1, y1, x1;
+        edge_lane_pixel(a, kEdgeInterior, t, 0, b0, y0, x0);
+        edge_lane_pixel(a, kEdgeInterior, t, 63, b1, y1, x1);
+        const int f0 = b0 * a.PL + (y0 + 1) * a.Wp + x0, f1 = b1 * a.PL + (y1 + 1) * a.Wp + x1;
+        lt = lt > f1 - f0 + 1 + 2 * (a.Wp + 1) ? lt : f1 - f0 + 1 + 2 * (a.Wp + 1);
+    }
+    a.edge = 1;
+    return lt;
+}
+
+// Steps (pixel x tap visits, per output channel and input group) of the edge-class grid: 6 taps per full band tile, 9 per
+// interior or mixed tile (padding lanes included, as the kernel issues them).
+inline long edge_tiles_steps(const ConvArgs &a)
+{
+    return 64L * (6L * a.e_nb + 9L * (a.e_nt - a.e_nb));
 }
 
 // Workgroups are dealt to the 8 XCDs round-robin in linear launch order (x fastest) and every XCD

@@ -217,11 +217,16 @@ __device__ __forceinline__ long step64(long acc, int2 x, int2 w, const ConvArgs 
                        // 8 = weights loaded once per workgroup (no scalar loads in the loop), 16 = one input item per lane (no LDS reads in the loop).
                        // Results are wrong with any of them; only the timing is of interest.
 #endif
-template <int KS, int P, int MODE, int NST, int GRP = 1>
+// EDGE: the grid is edge-class tiles (conv_common.hpp, edge_tile_class): a workgroup runs only the taps its class can find
+//      inside the image.  Interior tiles stage one contiguous run, band tiles one small patch per frame (edge_band_patch), mixed
+//      tiles each lane's 9 taps gathered ([tap row][lane][tap column]); the step loop reads all three through rowaddr exactly
+//      like a run.  Forms C / D, P = 1, 3x3 only.
+template <int KS, int P, int MODE, int NST, int GRP = 1, bool EDGE = false>
 __global__ __launch_bounds__(256, 2) void k_conv_i16(const int2 *__restrict__ in, int2 *__restrict__ out,
                                                    const int2 *__restrict__ wpk,
                                                    const short *__restrict__ bias, const ConvArgs a)
 {
+    static_assert(!EDGE || (KS == 3 && P == 1 && GRP == 1 && (MODE == 3 || MODE == 4)), "edge-class tiles: forms C / D, P = 1, 3x3");
     extern __shared__ int2 lds[];
     constexpr bool X64 = MODE == 2;
     typedef typename std::conditional<X64, long, int>::type acc_t;
@@ -236,26 +241,72 @@ __global__ __launch_bounds__(256, 2) void k_conv_i16(const int2 *__restrict__ in
     int tile = blockIdx.x, yb = blockIdx.y;
     if (a.xcd_remap) xcd_partition(a.xcd_remap - 1, tile, yb);
     const int mb = a.mb_list ? a.mb_list[yb] : yb;
-    const int q0 = tile * T;
-    const int qlast = min(q0 + T, a.npix) - 1;
     const int halo = (KS == 3) ? a.Wp + 1 : 0;
-    const int fmin = flat_of(a, q0);
-    const int fmax = flat_of(a, qlast);
-    const int tile_start = fmin - halo;
-    const int Lt = min(fmax - fmin + 1 + 2 * halo, a.lt_max);
-
     int fo[P];        // flat item offset of each owned pixel (also its output address)
     int rowaddr[P][KS];  // LDS byte address of (row i-1, col -1) relative tap origin per pixel
     bool valid[P];
+    int tile_start, Lt;
+    int ecls = kEdgeInterior;
+    int soff[NST], loff[NST];   // EDGE: source item (from in + kLead) and LDS item of each staged item
+    if (EDGE) {
+        int ct, b, y, x;
+        ecls = edge_tile_class(a, tile, ct);
+        valid[0] = edge_lane_pixel(a, ecls, ct, lane, b, y, x);
+        fo[0] = b * a.PL + (y + 1) * a.Wp + x;
+        if (ecls == kEdgeInterior) {   // full tile, flat offsets increase with the lane
+            const int fmin = __builtin_amdgcn_readfirstlane(fo[0]), fmax = __builtin_amdgcn_readlane(fo[0], 63);
+            tile_start = fmin - halo;
+            Lt = min(fmax - fmin + 1 + 2 * halo, a.lt_max);
+            const int lo = fo[0] - tile_start;
 #pragma unroll
-    for (int p = 0; p < P; ++p) {
-        const int q = q0 + p * 64 + lane;
-        valid[p] = q <= qlast;
-        fo[p] = flat_of(a, min(q, qlast));
-        const int lo = fo[p] - tile_start;
+            for (int i = 0; i < KS; ++i) rowaddr[0][i] = (lo + (i - 1) * a.Wp - 1) * 8;
 #pragma unroll
-        for (int i = 0; i < KS; ++i)
-            rowaddr[p][i] = (KS == 3) ? (lo + (i - 1) * a.Wp - 1) * 8 : lo * 8;
+            for (int k = 0; k < NST; ++k) { soff[k] = tile_start + tid + k * 256; loff[k] = tid + k * 256; }
+        } else if (ecls != kEdgeMixed) {   // band tile (full): one patch per frame it touches, edge_band_patch
+            const int b0 = __builtin_amdgcn_readfirstlane(b), b1 = __builtin_amdgcn_readlane(b, 63);
+            const bool rows = ecls == kEdgeTop || ecls == kEdgeBottom;
+            int org, Lf, pitch;
+            edge_band_patch(a, ecls, org, Lf, pitch);
+            tile_start = 0;
+            Lt = min((b1 - b0 + 1) * Lf, a.lt_max);
+            const int lo = (b - b0) * Lf + (rows ? fo[0] - b * a.PL - org : 2 * y + (ecls == kEdgeRight));
+#pragma unroll
+            for (int i = 0; i < KS; ++i) rowaddr[0][i] = (lo + (i - 1) * pitch - 1) * 8;
+#pragma unroll
+            for (int k = 0; k < NST; ++k) {   // staged item s: frame b0 + s / Lf, item r = s % Lf of its patch
+                const int s_ = tid + k * 256, fr = s_ / Lf, r_ = s_ - fr * Lf;
+                soff[k] = (b0 + fr) * a.PL + org + (rows ? r_ : (r_ >> 1) * a.Wp + (r_ & 1));
+                loff[k] = s_;
+            }
+        } else {   // mixed tile: pixels from the ends of all classes, each lane's 9 taps gathered
+            tile_start = 0;
+            Lt = kEdgeGatherItems;
+#pragma unroll
+            for (int i = 0; i < KS; ++i) rowaddr[0][i] = (i * 64 + lane) * 3 * 8;
+#pragma unroll
+            for (int k = 0; k < NST; ++k) {   // staged item tid + 256 k: this lane's tap t = wave + 4 k
+                const int t = wave + 4 * k, ti = t / 3, tj = t - 3 * ti;
+                soff[k] = fo[0] + (ti - 1) * a.Wp + (tj - 1);
+                loff[k] = (ti * 64 + lane) * 3 + tj;
+            }
+        }
+    } else {
+        const int q0 = tile * T;
+        const int qlast = min(q0 + T, a.npix) - 1;
+        const int fmin = flat_of(a, q0);
+        const int fmax = flat_of(a, qlast);
+        tile_start = fmin - halo;
+        Lt = min(fmax - fmin + 1 + 2 * halo, a.lt_max);
+#pragma unroll
+        for (int p = 0; p < P; ++p) {
+            const int q = q0 + p * 64 + lane;
+            valid[p] = q <= qlast;
+            fo[p] = flat_of(a, min(q, qlast));
+            const int lo = fo[p] - tile_start;
+#pragma unroll
+            for (int i = 0; i < KS; ++i)
+                rowaddr[p][i] = (KS == 3) ? (lo + (i - 1) * a.Wp - 1) * 8 : lo * 8;
+        }
     }
 
     // bias moved to the Qa_out domain, not saturated (core_compute.cpp:86-97)
@@ -301,7 +352,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_i16(const int2 *__restrict__ in
     int r_vgpr = r;
     if (MODE != 2) asm volatile("" : "+v"(r_vgpr));
     const char *lds_b = reinterpret_cast<const char *>(lds);
-    const int2 *src = in + kLead + tile_start;
+    const int2 *src = in + kLead + (EDGE ? 0 : tile_start);
     const int2 *wq = wpk + ((long)mb * a.CGin * KT * 32 + wave * 8);   // [mb][cg][tap][32]: KT taps per group
 
     // Input tiles are double-buffered in LDS: the global loads of group cg+1 are issued before the
@@ -316,12 +367,12 @@ __global__ __launch_bounds__(256, 2) void k_conv_i16(const int2 *__restrict__ in
 #pragma unroll
     for (int k = 0; k < NST; ++k) {
         const int i = tid + k * 256;
-        if (i < LtG) stage[k] = src[src_off(i)];
+        if (i < LtG) stage[k] = src[EDGE ? soff[k] : src_off(i)];
     }
 #pragma unroll
     for (int k = 0; k < NST; ++k) {
         const int i = tid + k * 256;
-        if (i < LtG) lds[lds_off(i)] = stage[k];
+        if (i < LtG) lds[EDGE ? loff[k] : lds_off(i)] = stage[k];
     }
     __syncthreads();
 
@@ -335,6 +386,9 @@ __global__ __launch_bounds__(256, 2) void k_conv_i16(const int2 *__restrict__ in
     int2 abl_x = lds[tid & 63];
 #endif
     const int niter = a.CGin / GRP;   // the host only selects GRP > 1 when it divides CGin
+    // The channel-group loop for one constant tap set (bit 3i + j: tap (i, j)); EDGE instantiates it once per class.
+    auto group_loop = [&](auto mask_c) __attribute__((always_inline)) {
+    constexpr int MASK = decltype(mask_c)::value;
     for (int cg = 0; cg < niter; ++cg) {
         // branch-free: the last group re-fetches its own tile instead of testing `cg + 1 < niter`
         src += (cg + 1 < niter) ? a.in_cg_stride * GRP : 0;
@@ -342,7 +396,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_i16(const int2 *__restrict__ in
 #pragma unroll
         for (int k = 0; k < NST; ++k) {
             const int i = tid + k * 256;
-            if (i < LtG) stage[k] = src[src_off(i)];
+            if (i < LtG) stage[k] = src[EDGE ? soff[k] : src_off(i)];
         }
 #endif
         const char *tile = lds_b + (cg & 1) * buf_items * 8;
@@ -360,10 +414,11 @@ __global__ __launch_bounds__(256, 2) void k_conv_i16(const int2 *__restrict__ in
 #pragma unroll
             for (int tt = 0; tt < KT * PFG; ++tt)
 #pragma unroll
-                for (int p = 0; p < P; ++p) xv[tt][p] = *xaddr(gb * KT * PFG + tt, p);
+                for (int p = 0; p < P; ++p) if ((MASK >> (tt % KT)) & 1) xv[tt][p] = *xaddr(gb * KT * PFG + tt, p);
         }
 #pragma unroll
         for (int tt = 0; tt < KT * PFG; ++tt) {
+            if (!((MASK >> (tt % KT)) & 1)) continue;   // a tap outside the image for every pixel of the tile: its step is acc = acc
             const int tap = gb * KT * PFG + tt;
             int2 w[8];
 #if (Y2_I16_ABL & 8)
@@ -423,7 +478,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_i16(const int2 *__restrict__ in
 #pragma unroll
             for (int k = 0; k < NST; ++k) {
                 const int i = tid + k * 256;
-                if (i < LtG) nxt[lds_off(i)] = stage[k];
+                if (i < LtG) nxt[EDGE ? loff[k] : lds_off(i)] = stage[k];
             }
         }
 #endif
@@ -435,6 +490,18 @@ __global__ __launch_bounds__(256, 2) void k_conv_i16(const int2 *__restrict__ in
 #if !(Y2_I16_ABL & 4)
         __syncthreads();
 #endif
+    }
+    };
+    if (!EDGE) {
+        group_loop(std::integral_constant<int, 0x1ff>());
+    } else {
+        switch (ecls) {   // wave-uniform (from blockIdx)
+        case kEdgeTop: group_loop(std::integral_constant<int, edge_class_mask(kEdgeTop)>()); break;
+        case kEdgeBottom: group_loop(std::integral_constant<int, edge_class_mask(kEdgeBottom)>()); break;
+        case kEdgeLeft: group_loop(std::integral_constant<int, edge_class_mask(kEdgeLeft)>()); break;
+        case kEdgeRight: group_loop(std::integral_constant<int, edge_class_mask(kEdgeRight)>()); break;
+        default: group_loop(std::integral_constant<int, 0x1ff>()); break;
+        }
     }
 
     // write-back with integer leaky (core_compute.cpp:175-264): 2 items (8 channels) per pixel

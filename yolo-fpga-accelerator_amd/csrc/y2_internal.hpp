@@ -62,7 +62,8 @@ struct Y2Options {
     // (b)
     int splitk = -1;              // -1 tuned; 0 no K-split of either kind; 1 the lane-split kernel wherever legal
     int poolfuse = -1;            // 1: conv + pool fused wherever legal
-    bool no_poolfuse = false, no_hiacc = false, no_ks = false, no_w16 = false, no_grp = false, grp16 = false, no_xcd_remap = false, splitk_no_pack = false;
+    bool no_poolfuse = false, no_hiacc = false, no_ks = false, no_w16 = false, no_grp = false, grp16 = false, no_xcd_remap = false, splitk_no_pack = false,
+         no_edge_tiles = false;   // (no_edge_tiles: raster tiles for the 3x3 form C / D launches, A/B - it changes no plan field)
     int f16_lanes = 2;
     bool f16_no_lanes = false, f16_no_mfma0 = false, f16_no_glds = false, f16_no_poolfuse = false, f16_no_halo = false, f16_no_persist = false,
          f16_persist_all = false, f16_ring_all = false, f16_no_ring = false, f16_no_c32 = false, f16_m16 = false, f16_w8 = false, f16_no_wide = false,

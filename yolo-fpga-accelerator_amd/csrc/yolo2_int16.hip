@@ -136,6 +136,19 @@ static void plan_conv(ConvPlan &p, const ActGeom &gin, long out_cg_stride, long 
     p.grid = dim3((npix + T - 1) / T, p.mb_count ? p.mb_count : (p.N + 31) / 32, 1);
     a.ks_S = p.ks; a.ks_Q = p.ks ? gin.CG / p.ks : 0; a.ks_mb = (int)p.grid.y;
     if (p.ks) { p.grid.y *= p.ks; p.lds_pad = 0; }
+    // Edge-class pixel tiles (conv_common.hpp): the one-pixel-per-lane form C / D 3x3 launches skip the taps that lie outside the
+    // image for all 64 pixels of a tile (6.4 % of the network's steps).  Same plan fields; option no_edge_tiles keeps raster tiles.
+    a.edge = 0;
+    if (!opt.no_edge_tiles && p.K == 3 && p.P == 1 && p.grp == 1 && (p.path == 3 || p.path == 4) && !p.hiacc && !p.w16 && !p.splitk && !p.ks) {
+        ConvArgs e = a;
+        const int lt = edge_tiles_plan(e);
+        if (lt > 0 && lt <= kMaxTileItems) {
+            a = e;
+            a.lt_max = lt;
+            p.lds_bytes = std::max(lt * 8 * 2, p.lds_pad);
+            p.grid.x = a.e_nt;
+        }
+    }
     // XCD grid over (tiles, blocks): bytes crossing the fabric = input x Xm + weights x Xt x G, where
     // G > 1 only if the blocks one XCD owns do not keep their weights in its 4 MiB L2 (then every
     // generation of co-resident tiles fetches them again).  See xcd_partition in kernels_int16.hpp.
@@ -175,6 +188,7 @@ static bool plan_conv_pool(ConvPlan &p, const ActGeom &gin, const ActGeom &gpool
     if (lt > 12 * 256) return false;
     ConvArgs &a = p.args;
     p.splitk = 0; p.splitk_pp = 1; p.grp = 1; p.P = 4; p.lds_pad = 0; p.w16 = 0; p.hiacc = 0; p.ks = 0;   // the fused kernel has one shape
+    a.edge = 0;
     p.pool_fused = full ? 2 : 1;
     a.lt_max = lt;
     a.nwin = gin.B * (gin.H / 2) * (gin.W / 2);
@@ -219,6 +233,14 @@ static void launch_conv_n(const ConvPlan &p, const int2 *in, int2 *out, const in
     if (nst <= 2) hipLaunchKernelGGL((k_conv_i16<KS, P, MODE, 2>), p.grid, dim3(256), p.lds_bytes, st, in, out, wpk, bias, p.args);
     else if (nst <= 4) hipLaunchKernelGGL((k_conv_i16<KS, P, MODE, 4>), p.grid, dim3(256), p.lds_bytes, st, in, out, wpk, bias, p.args);
     else hipLaunchKernelGGL((k_conv_i16<KS, P, MODE, 8>), p.grid, dim3(256), p.lds_bytes, st, in, out, wpk, bias, p.args);
+}
+
+template <int MODE>
+static void launch_conv_edge(const ConvPlan &p, const int2 *in, int2 *out, const int2 *wpk, const short *bias, hipStream_t st)
+{
+    const int nst = (p.args.lt_max + 255) / 256;   // 3: the gathered 9-tap layout (576 items) and every interior run up to 768
+    if (nst <= 3) hipLaunchKernelGGL((k_conv_i16<3, 1, MODE, 3, 1, true>), p.grid, dim3(256), p.lds_bytes, st, in, out, wpk, bias, p.args);
+    else hipLaunchKernelGGL((k_conv_i16<3, 1, MODE, 8, 1, true>), p.grid, dim3(256), p.lds_bytes, st, in, out, wpk, bias, p.args);
 }
 
 template <int KS, int MODE>
@@ -294,7 +316,9 @@ static int launch_conv(const ConvPlan &p, const int2 *in, int2 *out, const int2 
         return YOLO2_SUCCESS;
     }
     if (p.K == 3) {
-        if (p.path == 2) launch_conv_p<3, 2>(p, in, out, wpk, bias, st);
+        if (p.args.edge && p.path == 4) launch_conv_edge<4>(p, in, out, wpk, bias, st);
+        else if (p.args.edge && p.path == 3) launch_conv_edge<3>(p, in, out, wpk, bias, st);
+        else if (p.path == 2) launch_conv_p<3, 2>(p, in, out, wpk, bias, st);
         else if (p.path == 4 && p.hiacc) launch_conv_p<3, 5>(p, in, out, wpk, bias, st);
         else if (p.path == 4) launch_conv_p<3, 4>(p, in, out, wpk, bias, st);
         else if (p.path == 3) launch_conv_p<3, 3>(p, in, out, wpk, bias, st);
@@ -1210,7 +1234,8 @@ extern "C" int yolo2_hip_conv_launch_info(yolo2_hip_ctx *c, int ord, int *grid_x
     return fail(YOLO2_ERROR, "bad conv ordinal %d", ord);
 }
 
-// The launch plan of conv layer `ord` as text (lane 0's with lanes): "P=1 pad=0 w16=0 hiacc=1 ks=0 splitk=0 pp=1 grp=1 fused=0 form=4".
+// The launch plan of conv layer `ord` as text (lane 0's with lanes): "P=1 pad=0 w16=0 hiacc=1 ks=0 splitk=0 pp=1 grp=1 fused=0 form=4 extra=0 edge=0"
+// (edge=1: edge-class pixel tiles; launch-level, not a plan-table field).
 // What bench.py discloses as the plan it ran (the plan table makes it the same in every process).
 extern "C" int yolo2_hip_conv_plan_string(yolo2_hip_ctx *c, int ord, char *buf, int cap)
 {
@@ -1222,8 +1247,8 @@ extern "C" int yolo2_hip_conv_plan_string(yolo2_hip_ctx *c, int ord, char *buf, 
         if (kNet[i].type == L_CONV) {
             if (o == ord) {
                 const ConvPlan &pl = c->fuse_pool[i] ? c->fplan[i] : c->plan[i];
-                snprintf(buf, (size_t)cap, "P=%d pad=%d w16=%d hiacc=%d ks=%d splitk=%d pp=%d grp=%d fused=%d form=%d extra=%zu", pl.P, pl.lds_pad, pl.w16, pl.hiacc,
-                         pl.ks, pl.splitk, pl.splitk_pp, pl.grp, pl.pool_fused, pl.path, c->extra[i].size());
+                snprintf(buf, (size_t)cap, "P=%d pad=%d w16=%d hiacc=%d ks=%d splitk=%d pp=%d grp=%d fused=%d form=%d extra=%zu edge=%d", pl.P, pl.lds_pad, pl.w16,
+                         pl.hiacc, pl.ks, pl.splitk, pl.splitk_pp, pl.grp, pl.pool_fused, pl.path, c->extra[i].size(), pl.args.edge);
                 return YOLO2_SUCCESS;
             }
             o++;
@@ -1417,11 +1442,15 @@ static int max_abs_i16_dev(const short *dev, int n, int *out)
     return YOLO2_SUCCESS;
 }
 
+static int g_last_edge = 0;   // the last driver-tier int16 conv ran edge-class tiles (yolo2_hip_last_layer_edge)
+extern "C" int yolo2_hip_last_layer_edge(void) { return g_last_edge; }
+
 int y2_drv_conv_i16(const short *in, short *out, const short *w, const short *beta, int ifm_num, int ofm_num, int ksize, int kstride,
                     int input_w, int input_h, int output_w, int output_h, int padding, int is_nl, int qw, int qa_in, int qa_out, int qb,
                     int *path_out)
 {
     hipStream_t st = nullptr;
+    g_last_edge = 0;
     const int so = qa_in + qw - qa_out, sb = qb - qa_out;
     if (!g_scr.bound) HIP_TRY(hipMalloc((void **)&g_scr.bound, 4 * sizeof(int)), YOLO2_MMAP_ERROR);
     bool tiled = kstride == 1 && ((ksize == 3 && padding == 1) || (ksize == 1 && padding == 0));
@@ -1477,6 +1506,7 @@ int y2_drv_conv_i16(const short *in, short *out, const short *w, const short *be
     }
     plan_conv(p, gi, go.cg_stride, kLead, go.CG, popt);
     *path_out = p.path;
+    g_last_edge = p.args.edge;
     if ((rc = launch_conv(p, (const int2 *)g_scr.in_items, (int2 *)g_scr.out_items, (const int2 *)g_scr.wpk, (const short *)g_scr.bias_pk, st))) return rc;
     hipLaunchKernelGGL(k_items_to_ref, dim3(blocks_for((long)ofm_num * output_h * output_w, 256)), dim3(256), 0, st,
                        (const short *)g_scr.out_items, out, ofm_num, output_h, output_w, (output_w + 7) & ~7, go.Wp, go.PL,

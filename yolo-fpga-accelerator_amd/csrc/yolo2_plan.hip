@@ -26,7 +26,7 @@ const FlagOpt kFlags[] = {
     {"no_lanes", &Y2Options::no_lanes}, {"verbose", &Y2Options::verbose}, {"no_plan_cache", &Y2Options::no_plan_cache},
     {"no_poolfuse", &Y2Options::no_poolfuse}, {"no_hiacc", &Y2Options::no_hiacc}, {"no_ks", &Y2Options::no_ks},
     {"no_w16", &Y2Options::no_w16}, {"no_grp", &Y2Options::no_grp}, {"grp16", &Y2Options::grp16}, {"no_xcd_remap", &Y2Options::no_xcd_remap},
-    {"splitk_no_pack", &Y2Options::splitk_no_pack}, {"force_w16", &Y2Options::force_w16}, {"force_hiacc", &Y2Options::force_hiacc},
+    {"no_edge_tiles", &Y2Options::no_edge_tiles}, {"splitk_no_pack", &Y2Options::splitk_no_pack}, {"force_w16", &Y2Options::force_w16}, {"force_hiacc", &Y2Options::force_hiacc},
     {"f16_no_lanes", &Y2Options::f16_no_lanes}, {"f16_no_mfma0", &Y2Options::f16_no_mfma0}, {"f16_no_glds", &Y2Options::f16_no_glds},
     {"f16_no_poolfuse", &Y2Options::f16_no_poolfuse}, {"f16_no_halo", &Y2Options::f16_no_halo}, {"f16_no_persist", &Y2Options::f16_no_persist},
     {"f16_persist_all", &Y2Options::f16_persist_all}, {"f16_ring_all", &Y2Options::f16_ring_all}, {"f16_no_ring", &Y2Options::f16_no_ring},
@@ -155,6 +155,34 @@ extern "C" int yolo2_hip_i16_plan_check(int splits, int cg_out, int npix, size_t
         return fail(YOLO2_ERROR, "K-split: %d splits x %d items x %d pixels x 24 B = %zu bytes of triples do not fit the %zu-byte scratch", splits, cg_out,
                     npix, y2_ks_bytes(splits, cg_out, npix), cap_bytes);
     return YOLO2_SUCCESS;
+}
+
+// The edge-class partition on plain numbers: edge_tiles_plan + the kernel's own decode (conv_common.hpp), run on the host.
+extern "C" int yolo2_hip_i16_edge_map(int B, int H, int W, int cap, int *tile_cls, int *tile_mask, int *pix, long long *steps)
+{
+    if (B <= 0 || H <= 0 || W <= 0) return fail(YOLO2_ERROR, "edge tiles: empty geometry %d x %d x %d", B, H, W);
+    const y2::ActGeom g = y2::make_geom(4, H, W, B);
+    y2::ConvArgs a{};
+    a.B = B; a.H = H; a.W = W; a.Wp = g.Wp; a.PL = g.PL;
+    a.npix = B * H * W;
+    y2::set_conv_div(a);
+    if (!y2::edge_tiles_plan(a)) return 0;
+    if (steps) *steps = y2::edge_tiles_steps(a);
+    if (tile_cls && tile_mask && pix) {
+        if (cap < a.e_nt) return fail(YOLO2_ERROR, "edge tiles: %d tiles, room for %d", a.e_nt, cap);
+        for (int t = 0; t < a.e_nt; ++t) {
+            int ct;
+            const int cls = y2::edge_tile_class(a, t, ct);
+            tile_cls[t] = cls;
+            tile_mask[t] = y2::edge_class_mask(cls);
+            for (int lane = 0; lane < 64; ++lane) {
+                int b, y, x;
+                const bool ok = y2::edge_lane_pixel(a, cls, ct, lane, b, y, x);
+                pix[64L * t + lane] = ok ? (b * H + y) * W + x : -1;
+            }
+        }
+    }
+    return a.e_nt;
 }
 
 // ---------------------------------------------------------------------------- plan lines and the committed table

@@ -44,7 +44,7 @@ EXPORTS = [
     "yolo2_hip_fp16_layer_kernel", "yolo2_hip_f16_store_check",
     "yolo2_hip_run_images_u8_dets", "yolo2_hip_multi_run_images_u8_dets", "yolo2_hip_set_fp16_lanes", "yolo2_hip_conv_plan_string", "yolo2_hip_plan_source",
     "yolo2_hip_set_option", "yolo2_hip_options_string", "yolo2_hip_set_plan_cache", "yolo2_hip_plan_cache_info", "yolo2_hip_plan_cache_check",
-    "yolo2_hip_i16_plan_check", "yolo2_hip_ks_scratch_bytes",
+    "yolo2_hip_i16_plan_check", "yolo2_hip_ks_scratch_bytes", "yolo2_hip_i16_edge_map", "yolo2_hip_last_layer_edge",
     "yolo2_hip_run_batch_f32tol", "yolo2_hip_run_batch_f32tol_host", "yolo2_hip_f32tol_layer_kernel", "yolo2_hip_num_lanes_f32tol",
 ]
 
@@ -147,6 +147,8 @@ def lib():
     sig("yolo2_hip_plan_cache_info", [vp, C.POINTER(u64), pi32, pi32, pi32])
     sig("yolo2_hip_plan_cache_check", [C.c_char_p, u64, pi32])
     sig("yolo2_hip_i16_plan_check", [i32, i32, i32, C.c_size_t])
+    sig("yolo2_hip_i16_edge_map", [i32, i32, i32, i32, vp, vp, vp, vp])
+    sig("yolo2_hip_last_layer_edge", [], i32)
     sig("yolo2_hip_run_batch_f32tol", [vp, u64, i32, u64, vp])
     sig("yolo2_hip_run_batch_f32tol_host", [vp, vp, i32, vp])
     sig("yolo2_hip_f32tol_layer_kernel", [vp, i32], C.c_char_p)
