@@ -245,6 +245,15 @@ int yolo2_hip_f16_store_check(int store, int pool, int B, int H, int W, int Cp_o
 int yolo2_hip_debug_layer_output(yolo2_hip_ctx *ctx, int layer_idx, int frame, int16_t *out,
                                  size_t capacity_elems, size_t *out_elems);
 
+/* fp16 / split-fp16 parity hook: the RAW items (uint16 halves) of one frame's plane of layer `layer_idx`'s tensor from the last
+ * yolo2_hip_run_batch_fp16 (split = 0) or yolo2_hip_run_batch_f32tol (split = 1), lane-aware.  which: 0 = the frame's (H+1)(W+1)
+ * items, 1 = the lead items before plane 0, 2 = the tail items after the last plane (of the lane that holds the frame).
+ * geom[8] = {C, Cp, H, W, Wp, items, part stride, channel offset}: items of Cp halves; split items hold [hi | lo | hi] parts of
+ * `part stride` channels; layers 24 and 27 are channels 256.. / 0.. of the concat tensor.  out == NULL returns the geometry only.
+ * YOLO2_ERROR for a tensor no step of the current launch table writes (fused intermediates, layer 30 = the region tensor). */
+int yolo2_hip_debug_f16_tensor(yolo2_hip_ctx *ctx, int split, int layer_idx, int frame, int which, uint16_t *out,
+                               size_t capacity_halves, int *geom);
+
 /* Per-layer device time: enabling records hipEvent pairs around every layer kernel of
  * subsequent runs, on the stream they are launched on (the analogue of the per-layer latency
  * report in linux_app/src/yolo2_inference.c:75-142).  layer_times_ms returns the mean over the

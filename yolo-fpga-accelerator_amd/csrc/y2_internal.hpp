@@ -275,6 +275,8 @@ struct yolo2_hip_ctx {
     ConvPlan fp32_plan[32];
     long wh_off[YOLO2_N_CONV], biasf_off[YOLO2_N_CONV];
     int f16_batch = 0;
+    int f16_last_batch = 0;            // batch of the last yolo2_hip_run_batch_fp16 on this context (yolo2_hip_debug_f16_tensor)
+    bool f16_last_laned = false;       // ... and whether it ran as lanes (f16_lanes hold the tensors then)
     HalfTensor h_in, h_out[32], h_cat;
     // per-layer device timing: a ring of event sets, one per profiled run (hipEvents on the
     // stream the kernels are launched on); the analogue of yolo2_inference.c:75-142

@@ -765,11 +765,13 @@ extern "C" int yolo2_hip_run_batch_fp16(yolo2_hip_ctx *c, uint64_t frames_dev, i
         }
         for (int i = 0; i < want_lanes; ++i)
             if (c->f16_lanes[i]->lane_stream) HIP_TRY(hipStreamWaitEvent(st, c->f16_lanes[i]->ev_join, 0), YOLO2_ERROR);
+        c->f16_last_batch = batch; c->f16_last_laned = true;
         return YOLO2_SUCCESS;
     }
     int rc = ensure_f16_batch(c, batch);
     if (rc) return rc;
     if (c->f16_plan->batch != batch && (rc = build_f16_plan(c, batch))) return rc;
+    c->f16_last_batch = batch; c->f16_last_laned = false;
     if (c->prof && (rc = y2_ensure_prof_events(c))) return rc;
     hipEvent_t *ev = c->prof ? c->ev[c->prof_runs % yolo2_hip_ctx::kProfSlots] : nullptr;
     // the table walk: hipEvent slot i opens layer i, slot i+1 closes it (layers 0+1 are one launch, booked to layer 0)
@@ -851,6 +853,55 @@ extern "C" int yolo2_hip_run_batch_f32tol_host(yolo2_hip_ctx *c, const float *fr
 // Kernel the split-mode table runs for layer `layer_idx` (after the first yolo2_hip_run_batch_f32tol at this batch); "" if none.
 extern "C" const char *yolo2_hip_f32tol_layer_kernel(yolo2_hip_ctx *c, int layer_idx) { return c && c->tol ? yolo2_hip_fp16_layer_kernel(c->tol, layer_idx) : ""; }
 extern "C" int yolo2_hip_num_lanes_f32tol(yolo2_hip_ctx *c) { return c && c->tol && !c->tol->f16_lanes.empty() ? (int)c->tol->f16_lanes.size() : 1; }
+
+// Test hook: the raw items of one frame's plane of layer `layer_idx`'s tensor from the last run of the fp16 pass (split = 0) or of the
+// split-fp16 twin (split = 1).  which = 0: the frame's PL = (H+1)(W+1) items; 1: the kLead items before plane 0; 2: the kTail items after
+// the last plane (of the lane that holds the frame).  geom[8] = C, Cp, H, W, Wp, items copied, part stride (split items: [hi | lo | hi]
+// parts of that many channels; plain items: Cp), channel offset of the layer inside the items (layer 24: 256 of the concat tensor).
+// out == NULL: geometry only.  Only tensors that a step of the current table writes can be read: the others are never stored.
+extern "C" int yolo2_hip_debug_f16_tensor(yolo2_hip_ctx *c, int split, int layer_idx, int frame, int which, uint16_t *out, size_t cap,
+                                          int *geom)
+{
+    if (!c || !geom) return fail(YOLO2_ERROR, "null argument");
+    if (split) {
+        if (!c->tol) return fail(YOLO2_ERROR, "no split-fp16 run yet (yolo2_hip_run_batch_f32tol)");
+        c = c->tol;
+    }
+    if (!c->f16_last_batch) return fail(YOLO2_ERROR, "no fp16 run yet");
+    if (frame < 0 || frame >= c->f16_last_batch) return fail(YOLO2_ERROR, "frame %d outside the last batch of %d", frame, c->f16_last_batch);
+    if (which < 0 || which > 2) return fail(YOLO2_ERROR, "bad item range %d", which);
+    if (c->f16_last_laned) {   // frame -> lane exactly as yolo2_hip_run_batch_fp16 splits the batch
+        if (c->f16_lanes.empty()) return fail(YOLO2_ERROR, "the lanes of the last fp16 run are gone (yolo2_hip_set_fp16_lanes)");
+        const int half = c->f16_last_batch / (int)c->f16_lanes.size();
+        yolo2_hip_ctx *l = c->f16_lanes[frame / half];
+        if (l->f16_last_batch != half || l->f16_last_laned) return fail(YOLO2_ERROR, "fp16 lane state does not match the last run");
+        return yolo2_hip_debug_f16_tensor(l, 0, layer_idx, frame % half, which, out, cap, geom);
+    }
+    if (layer_idx < 0 || layer_idx > 30) return fail(YOLO2_ERROR, "bad layer %d", layer_idx);
+    if (layer_idx == 30) return fail(YOLO2_ERROR, "layer 30's output is the region tensor the run returns");
+    const LayerDesc &l = kNet[layer_idx];
+    if (l.type == L_ROUTE) return fail(YOLO2_ERROR, "route layer %d has no tensor of its own", layer_idx);
+    if (!c->f16_plan || c->f16_plan->batch != c->f16_last_batch) return fail(YOLO2_ERROR, "no launch table for the last run");
+    const bool cat = layer_idx == 24 || layer_idx == 27;
+    const yolo2_hip_ctx::HalfTensor &t = cat ? c->h_cat : c->h_out[layer_idx];
+    bool written = false;   // from the table itself: some step stores into this tensor (layer 24 / 27: the step of that layer)
+    for (const F16Step &s : c->f16_plan->steps)
+        if (t.d && s.out == t.d && (!cat || s.layer == layer_idx)) written = true;
+    if (!written)
+        return fail(YOLO2_ERROR, "layer %d's tensor is not written by the current fp16 plan (its launch is fused or it has none)", layer_idx);
+    const int C = l.type == L_MAX ? l.c : (l.type == L_REORG ? 4 * l.c : l.n);
+    const int ps = c->split ? part_stride(cat ? 1280 : C) : t.Cp;
+    const int g[8] = {C, t.Cp, t.H, t.W, t.Wp, which == 0 ? t.PL : (which == 1 ? kLead : kTail), ps, layer_idx == 24 ? 256 : 0};
+    memcpy(geom, g, sizeof(g));
+    if (!out) return YOLO2_SUCCESS;
+    const size_t n = (size_t)g[5] * t.Cp;
+    if (cap < n) return fail(YOLO2_ERROR, "output buffer too small (%zu < %zu halves)", cap, n);
+    const size_t first = which == 0 ? (size_t)kLead + (size_t)frame * t.PL : (which == 1 ? 0 : (size_t)kLead + (size_t)t.B * t.PL);
+    HIP_TRY(hipSetDevice(c->device), YOLO2_INIT_ERROR);
+    HIP_TRY(hipDeviceSynchronize(), YOLO2_ERROR);   // (lanes run on streams of their own)
+    HIP_TRY(hipMemcpy(out, t.d + first * t.Cp, n * 2, hipMemcpyDeviceToHost), YOLO2_DMA_ERROR);
+    return YOLO2_SUCCESS;
+}
 
 #ifdef Y2_STAMPS
 // diagnostic build only: the halo kernel's workgroup timeline of the launch selected by YOLO2_STAMP_LAYER

@@ -46,6 +46,7 @@ EXPORTS = [
     "yolo2_hip_set_option", "yolo2_hip_options_string", "yolo2_hip_set_plan_cache", "yolo2_hip_plan_cache_info", "yolo2_hip_plan_cache_check",
     "yolo2_hip_i16_plan_check", "yolo2_hip_ks_scratch_bytes", "yolo2_hip_i16_edge_map", "yolo2_hip_last_layer_edge",
     "yolo2_hip_run_batch_f32tol", "yolo2_hip_run_batch_f32tol_host", "yolo2_hip_f32tol_layer_kernel", "yolo2_hip_num_lanes_f32tol",
+    "yolo2_hip_debug_f16_tensor",
 ]
 
 
@@ -154,6 +155,7 @@ def lib():
     sig("yolo2_hip_f32tol_layer_kernel", [vp, i32], C.c_char_p)
     sig("yolo2_hip_num_lanes_f32tol", [vp])
     sig("yolo2_hip_ks_scratch_bytes", [vp], C.c_size_t)
+    sig("yolo2_hip_debug_f16_tensor", [vp, i32, i32, i32, i32, vp, C.c_size_t, pi32])
     L.yolo2_hip_multi_create.argtypes = [vp, i32, C.POINTER(vp)]
     L.yolo2_hip_multi_destroy.argtypes = [vp]
     L.yolo2_hip_multi_num_devices.argtypes = [vp]
@@ -472,6 +474,19 @@ class Yolo2Hip:
 
     def num_lanes_f32tol(self) -> int:
         return int(lib().yolo2_hip_num_lanes_f32tol(self._h))
+
+    F16_GEOM = ("C", "Cp", "H", "W", "Wp", "items", "part_stride", "ch_off")
+
+    def debug_f16_tensor(self, layer_idx: int, frame: int = 0, split: bool = False, which: int = 0):
+        """Raw items of layer `layer_idx`'s fp16 (split=False) or split-fp16 tensor from the last run: (uint16 [items][Cp], geometry
+        dict).  which: 0 the frame's (H+1)(W+1) items, 1 the lead items, 2 the tail items of the lane holding the frame."""
+        g = (C.c_int * 8)()
+        check(lib().yolo2_hip_debug_f16_tensor(self._h, int(split), layer_idx, frame, which, None, 0, g), "yolo2_hip_debug_f16_tensor")
+        geom = dict(zip(self.F16_GEOM, list(g)))
+        out = np.empty((geom["items"], geom["Cp"]), dtype=np.uint16)
+        check(lib().yolo2_hip_debug_f16_tensor(self._h, int(split), layer_idx, frame, which, out.ctypes.data_as(C.c_void_p), out.size, g),
+              "yolo2_hip_debug_f16_tensor")
+        return out, geom
 
     def set_fp16_lanes(self, lanes: int):
         check(lib().yolo2_hip_set_fp16_lanes(self._h, lanes), "yolo2_hip_set_fp16_lanes")
