@@ -436,6 +436,20 @@ int yolo2_hip_run_images_u8_dets(yolo2_hip_ctx *ctx, const uint8_t *const *image
                                  int channels, int n, int batch, float thresh, float nms, int flags, yolo2_hip_det *dets,
                                  int cap_per_frame, int *counts, int *final_q);
 
+/* The same two entries on the matrix-core passes (needs yolo2_hip_load_weights_fp32): split = 0 the fp16 pass, 1 the fp32-tolerance
+ * (split-fp16) pass, as in yolo2_hip_debug_f16_tensor.  Same chunks, staging, stream overlap, ragged last chunk and record layout as
+ * the int16 entries; the region tensor is fp32 [n][425][13][13] and the records equal yolo2_hip_postprocess_f32's on it.  Layers 0+1
+ * read the chunk's image bytes themselves (k_conv0_pool_mfma_u8): the result is bit-identical to letterboxing every image
+ * (yolo2_hip_letterbox_u8) and running yolo2_hip_run_batch_fp16 / _f32tol on those frames in the same chunks. */
+int yolo2_hip_run_images_u8_f16_host(yolo2_hip_ctx *ctx, int split, const uint8_t *const *images, const int *widths,
+                                     const int *heights, int channels, int n, int batch, float *region_host);
+int yolo2_hip_run_images_u8_dets_f16(yolo2_hip_ctx *ctx, int split, const uint8_t *const *images, const int *widths,
+                                     const int *heights, int channels, int n, int batch, float thresh, float nms, int flags,
+                                     yolo2_hip_det *dets, int cap_per_frame, int *counts);
+/* what the last of those calls ran for layers 0+1 at that `split` ("" before the first): the fused kernel, or under the option
+ * f16_no_mfma0 "k_letterbox_u8_batch + " and the frame path's layer-0 kernel */
+const char *yolo2_hip_images_layer0_kernel(yolo2_hip_ctx *ctx, int split);
+
 /* ------------------------------------------------------- multi-GPU: frame sharding, one weight broadcast
  *
  * SURVEY.md 8(b) "init(device_list) ... load_weights (H2D on rank 0, RCCL broadcast to the rest)", 8(e): frames are
@@ -474,6 +488,10 @@ int  yolo2_hip_multi_run_images_u8_host(yolo2_hip_multi *m, const uint8_t *const
 int  yolo2_hip_multi_run_images_u8_dets(yolo2_hip_multi *m, const uint8_t *const *images, const int *widths, const int *heights,
                                         int channels, int n, int batch_per_device, float thresh, float nms, int flags,
                                         yolo2_hip_det *dets, int cap_per_frame, int *counts, int *final_q);
+/* the same on the fp16 (split = 0) / fp32-tolerance (split = 1) pass; see yolo2_hip_run_images_u8_dets_f16 */
+int  yolo2_hip_multi_run_images_u8_dets_f16(yolo2_hip_multi *m, int split, const uint8_t *const *images, const int *widths,
+                                            const int *heights, int channels, int n, int batch_per_device, float thresh, float nms,
+                                            int flags, yolo2_hip_det *dets, int cap_per_frame, int *counts);
 
 /* (b) one process per device (torchrun / MPI style; what bench.py --gpus N runs): rank 0 makes the 128-byte id
  * (ncclGetUniqueId), the launcher hands it to every rank, each rank joins with its context (ncclCommInitRank), then

@@ -28,6 +28,7 @@
 #include <cstdint>
 
 #include "layout.hpp"
+#include "letterbox.hpp"   // k_conv0_pool_mfma_u8: LetterboxItem, lb_value_at
 
 namespace y2 {
 
@@ -2747,10 +2748,15 @@ __global__ void k_pack_weights_f16(const float *__restrict__ src, _Float16 *__re
 // B fragments -, every product as three MFMAs (hi hi + lo hi + hi lo) into the same fp32 accumulators, the pooled fp32 value split again
 // into the layer-1 item's [hi | lo | hi] parts of 32 channels (items of 128 halves).  Replaces the fp32-VALU form k_conv0_pool_f16<true>
 // there (0.59 ms per 64 frames, 9 % of that pass).
-template <bool SPLIT = false>
-__global__ __launch_bounds__(256) void k_conv0_pool_mfma(const float *__restrict__ frames, const float *__restrict__ w0,
-                                                          const float *__restrict__ bias0, _Float16 *__restrict__ out, int H,
-                                                          int W, int oWp, int oPL, int n_tile_total)
+// U8 (k_conv0_pool_mfma_u8, the images entries): the patch is built from the chunk's image BYTES instead of from fp32 frames -
+// `lb` is the chunk's staging buffer (a LetterboxItem table, then the images: kernels_pre.hpp), tile frame b is table item
+// lb_first + b, and every patch value is lb_value_at()'s fp32 value of that canvas element (0 outside the 416 x 416 canvas, as the
+// frame path's masks make it), i.e. exactly the float k_letterbox_u8_batch stores there.  Conversion, MFMAs, pool and stores are
+// the frame form's, so the output is bit-identical to k_letterbox_u8_batch followed by k_conv0_pool_mfma.
+template <bool SPLIT, bool U8>
+__device__ __forceinline__ void conv0_pool_mfma_tiles(const float *__restrict__ frames, const uint8_t *__restrict__ lb, int lb_first,
+                                                      const float *__restrict__ w0, const float *__restrict__ bias0,
+                                                      _Float16 *__restrict__ out, int H, int W, int oWp, int oPL, int n_tile_total)
 {
     // Patch = rows ty0-1 .. ty0+16, image columns tx0-4 .. tx0+35 (the tile's 34 plus three on either side so that every piece is
     // a 16-byte aligned float4 in the frame: tx0 is a multiple of 32): column tx0-1+p is stored at index p + PSH of its row.
@@ -2800,12 +2806,38 @@ __global__ __launch_bounds__(256) void k_conv0_pool_mfma(const float *__restrict
     // Two tiles' pieces in flight: the set a tile is converted from was requested TWO tiles earlier (one tile ahead left ~0.05 of
     // 0.19 ms per 128 frames waiting for loads: Y2_C0_ABL = 2).
     float4 pvA[NIT], pvB[NIT];
+    // U8: v / 255.f of every byte value (bit-identical to the division; lb_part needs four per patch value)
+    __shared__ float lbt[U8 ? 256 : 1];
+    if constexpr (U8) {
+        lbt[tid] = __fdiv_rn((float)tid, 255.f);
+        __syncthreads();
+    }
     auto request = [&](int tile, float4 (&pv)[NIT]) {   // clamped addresses (always inside the plane), masked when written
 #if (Y2_C0_ABL & 2)
         tile = (int)blockIdx.x;          // diagnostic: every request re-reads the workgroup's first (cache-hot) patch
 #endif
         const int b = tile / (tiles_x * tiles_y), tr = tile % (tiles_x * tiles_y);
         const int ty0 = (tr / tiles_x) * TR, tx0 = (tr % tiles_x) * TC;
+        if constexpr (U8) {   // the patch's values from the image bytes; the pieces' canvas positions as in the float form below
+            const LetterboxItem *item = reinterpret_cast<const LetterboxItem *>(lb) + lb_first + b;
+            const LetterboxArgs a = item->a;
+            const uint8_t *img = lb + item->off;
+            const LbTable q{lbt};
+            // a patch wholly inside a letterbox band (wave-uniform): 0.5 on the canvas, no byte loads
+            const bool band = tx0 + TC + 3 < a.off_x || tx0 - 4 >= a.off_x + a.new_w || ty0 + TR < a.off_y || ty0 - 1 >= a.off_y + a.new_h;
+#pragma unroll
+            for (int it = 0; it < NIT; ++it) {
+                const int k = pel_pk[it] >> 16, y = ty0 + (pel_pk[it] & 255) - 1, x0 = tx0 - 4 + 4 * ((pel_pk[it] >> 8) & 255);
+                float v[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const bool canvas = y >= 0 && y < H && x0 + e >= 0 && x0 + e < W;   // outside: the conv's zero padding
+                    v[e] = !canvas ? 0.f : (band ? .5f : lb_value_at(img, a, k, y, x0 + e, q));
+                }
+                pv[it] = make_float4(v[0], v[1], v[2], v[3]);
+            }
+            return;
+        }
         const float *fb = frames + (size_t)b * 3 * H * W;
         if (ty0 > 0 && ty0 + TR < H && tx0 > 0 && tx0 + TC < W) {      // an interior tile (wave-uniform): the whole patch is inside the plane, no clamps
             const float *tb = fb + (size_t)(ty0 - 1) * W + (tx0 - 4);
@@ -2933,6 +2965,23 @@ __global__ __launch_bounds__(256) void k_conv0_pool_mfma(const float *__restrict
         do_tile(tile, pvA);
         if (tile + G < n_tile_total) do_tile(tile + G, pvB);
     }
+}
+
+template <bool SPLIT = false>
+__global__ __launch_bounds__(256) void k_conv0_pool_mfma(const float *__restrict__ frames, const float *__restrict__ w0,
+                                                          const float *__restrict__ bias0, _Float16 *__restrict__ out, int H,
+                                                          int W, int oWp, int oPL, int n_tile_total)
+{
+    conv0_pool_mfma_tiles<SPLIT, false>(frames, nullptr, 0, w0, bias0, out, H, W, oWp, oPL, n_tile_total);
+}
+
+// layers 0+1 straight from image bytes (see U8 above); H = W = 416 = the letterbox canvas
+template <bool SPLIT = false>
+__global__ __launch_bounds__(256) void k_conv0_pool_mfma_u8(const uint8_t *__restrict__ lb, int lb_first, const float *__restrict__ w0,
+                                                             const float *__restrict__ bias0, _Float16 *__restrict__ out, int oWp, int oPL,
+                                                             int n_tile_total)
+{
+    conv0_pool_mfma_tiles<SPLIT, true>(nullptr, lb, lb_first, w0, bias0, out, 416, 416, oWp, oPL, n_tile_total);
 }
 
 // (Round 4 also built a second form with the im2col expansion on the B side - an MFMA row = four adjacent conv pixels, K = (channel,

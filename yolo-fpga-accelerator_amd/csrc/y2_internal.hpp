@@ -204,6 +204,10 @@ struct PipeBufs {
     uint8_t *hgeom[2] = {nullptr, nullptr};
     yolo2_hip_det *hdets[2] = {nullptr, nullptr};
     int *hcounts[2] = {nullptr, nullptr};
+    // the fp16 / split-fp16 images entries: fp32 region tensors [batch][425][13][13] per buffer set (device; pinned mirrors for the
+    // entry that returns them)
+    int regf_batch = 0;
+    float *dregf[2] = {nullptr, nullptr}, *hregf[2] = {nullptr, nullptr};
 };
 
 struct F16Plan;   // yolo2_fp16.hip: the per-context launch table of the fp16 path
@@ -263,6 +267,7 @@ struct yolo2_hip_ctx {
     float *w0f = nullptr;  // layer 0: [27][32] fp32 weights + [32] bias for the fused conv0+pool kernel
     float *wf32 = nullptr, *bf32 = nullptr;   // the fp32 blobs as loaded (reference stream order), for the exact fp32 pass
     F16Plan *f16_plan = nullptr;              // launch table of the fp16 pass (built once per (weights, batch); owned)
+    std::string images_l0[2];                 // what the last fp16 (0) / split (1) images call ran for layers 0+1 (yolo2_hip_images_layer0_kernel)
     // ---- tiled exact fp32 path (kernels_f32.hpp): packed weights [mb][cg][tap][32][4] floats, items of 4 floats
     float *wpkf = nullptr, *biasf32_pk = nullptr;
     long wpkf_off[YOLO2_N_CONV], biasf32_off[YOLO2_N_CONV];
@@ -307,6 +312,14 @@ int y2_ensure(void **p, size_t *cap, size_t need);   // grow-only device scratch
 
 // yolo2_fp16.hip
 void y2_f16_plan_free(yolo2_hip_ctx *c);
+// The fp16 images entries (yolo2_hip.hip).  y2_f16_images_ctx: the context whose pass they run - c itself (split 0) or its split twin
+// (split 1, made here) - or YOLO2_ERROR without fp32 weights.  y2_f16_images_fused: that pass has the layer-0 step from bytes (not under
+// f16_no_mfma0: the entries then letterbox into frames and run the frame path).  y2_f16_run_images: the pass on a chunk of `batch`
+// frames whose staging buffer (LetterboxItem table + images) is at lb, enqueued on st; y2_f16_images_kernel names its layer-0 kernel.
+int y2_f16_images_ctx(yolo2_hip_ctx *c, int split, yolo2_hip_ctx **run);
+bool y2_f16_images_fused(const yolo2_hip_ctx *run);
+int y2_f16_run_images(yolo2_hip_ctx *run, const uint8_t *lb, int batch, float *region_dev, hipStream_t st);
+const char *y2_f16_images_kernel(const yolo2_hip_ctx *run);
 
 // The per-layer driver calls' device work (yolo2_driver.hip validates, latches the register file, takes the lock, binds the
 // device, and synchronises with the reference's timeout semantics afterwards; these only enqueue on the null stream).
@@ -328,4 +341,8 @@ int y2_post_fill_geom(void *geom_host, const int *im_w, const int *im_h, int n);
 // b->geom must hold the frames' records (copied on `st` in front of this call).  Enqueues on st, returns without synchronising.
 int y2_post_enqueue_int16(int device, const int16_t *region_dev, int batch, int final_q, float thresh, float nms, int cap, int best_only,
                           Y2PostBufs *b, hipStream_t st);
+// the same on an fp32 region tensor (the fp16 / split / fp32 passes; yolo2_hip_postprocess_f32 is this plus its synchronous copies).
+// proc_dev (optional): the activated region tensor; final_rows (optional): the rows the records were compacted from.
+int y2_post_enqueue_f32(const float *region_dev, int batch, float thresh, float nms, int cap, int best_only, Y2PostBufs *b, hipStream_t st,
+                        float *proc_dev = nullptr, float **final_rows = nullptr);
 

@@ -74,10 +74,16 @@ struct F16Step {
     int iCp = 0, iWp = 0, iPL = 0, oCp = 0, oWp = 0, oPL = 0, OH = 0, OW = 0, iPS = 0, oPS = 0;
 };
 
+typedef void (*F16LaunchU8)(const F16Step &, const uint8_t *lb, int lb_first, hipStream_t);
+
 struct F16Plan {
     F16Switches sw;
     int batch = 0;               // the batch the table below was built for (0 = none)
     std::vector<F16Step> steps;
+    // the images entries' layer-0 step "from bytes" (layers 0+1 from a chunk's staging buffer), used instead of steps[0]; every
+    // other step is the table's.  Not set (launch_u8 == nullptr) under f16_no_mfma0: those entries letterbox into frames first.
+    F16Step u8;
+    F16LaunchU8 launch_u8 = nullptr;
 };
 
 void y2_f16_plan_free(yolo2_hip_ctx *c)
@@ -301,6 +307,11 @@ static int ensure_f16_batch(yolo2_hip_ctx *c, int B)
         __VA_ARGS__;                                                                                   \
     }
 template <bool SP = false> Y2_LAUNCHER(L_conv0_mfma, hipLaunchKernelGGL(k_conv0_pool_mfma<SP>, s.grid, s.block, 0, st, frames, s.w0, s.bias, s.out, 416, 416, s.oWp, s.oPL, s.T))
+template <bool SP>
+static void L_conv0_mfma_u8(const F16Step &s, const uint8_t *lb, int lb_first, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_conv0_pool_mfma_u8<SP>, s.grid, s.block, 0, st, lb, lb_first, s.w0, s.bias, s.out, s.oWp, s.oPL, s.T);
+}
 template <bool SP> Y2_LAUNCHER(L_conv0_valu, hipLaunchKernelGGL(k_conv0_pool_f16<SP>, s.grid, s.block, 0, st, frames, s.w0, s.bias, s.out, s.B, 416, 416, s.oWp, s.oPL))
 template <int BN> Y2_LAUNCHER(L_ring, hipLaunchKernelGGL((k_gemm1_f16_p<256, BN, 3>), s.grid, s.block, s.lds, st, s.in, s.w, s.bias, s.out,
                                                             s.store == FS_REGION ? region : (float *)nullptr, s.a, s.T))
@@ -333,6 +344,7 @@ static int build_f16_plan(yolo2_hip_ctx *c, int B)
     const F16Switches &sw = P.sw;
     P.steps.clear();
     P.batch = 0;
+    P.launch_u8 = nullptr;
     typedef yolo2_hip_ctx::HalfTensor HT;
     const bool split = c->split;     // "fp32tol" mode: items of three parts [hi | lo | hi], SPLIT kernel instantiations
     auto checked_push = [&](F16Step &s, const HT &dst) -> int {
@@ -365,6 +377,11 @@ static int build_f16_plan(yolo2_hip_ctx *c, int B)
         }
         if (g.B != B || g.H != 208 || g.W != 208 || g.Cp != (split ? 128 : 32)) return fail(YOLO2_ERROR, "fp16 plan: layer-1 tensor has the wrong geometry");
         P.steps.push_back(s);
+        if (!sw.no_mfma0) {   // the same tiles, grid and output from image bytes (the images entries)
+            P.u8 = s;
+            P.u8.kernel = split ? "k_conv0_pool_mfma_u8<split>" : "k_conv0_pool_mfma_u8";
+            P.launch_u8 = split ? L_conv0_mfma_u8<true> : L_conv0_mfma_u8<false>;
+        }
     }
     int ord = 1, skip_pool = -1, fused_conv = -1;
     const HT *cur = &c->h_out[1];
@@ -734,11 +751,13 @@ static int make_f16_lanes(yolo2_hip_ctx *c, int want_lanes)
     return YOLO2_SUCCESS;
 }
 
-extern "C" int yolo2_hip_run_batch_fp16(yolo2_hip_ctx *c, uint64_t frames_dev, int batch, uint64_t region_dev, void *stream)
+// The pass.  lb == nullptr: layer 0 reads the float frames at frames_dev (the table as it is).  lb != nullptr (the images entries):
+// layer 0 reads frames lb_first .. lb_first + batch - 1 of the chunk staging buffer lb through the table's step "from bytes".
+static int run_f16(yolo2_hip_ctx *c, uint64_t frames_dev, const uint8_t *lb, int lb_first, int batch, uint64_t region_dev, void *stream)
 {
     if (!c) return fail(YOLO2_ERROR, "null ctx");
     if (!c->f16_loaded || !c->f16_plan) return fail(YOLO2_ERROR, "fp32 weights not loaded (yolo2_hip_load_weights_fp32)");
-    if (!frames_dev || !region_dev) return fail(YOLO2_ERROR, "null buffer address");
+    if ((!lb && !frames_dev) || !region_dev) return fail(YOLO2_ERROR, "null buffer address");
     if (batch <= 0 || batch > 4096) return fail(YOLO2_ERROR, "batch %d out of range", batch);
     HIP_TRY(hipSetDevice(c->device), YOLO2_INIT_ERROR);
     hipStream_t st = (hipStream_t)stream;
@@ -758,8 +777,8 @@ extern "C" int yolo2_hip_run_batch_fp16(yolo2_hip_ctx *c, uint64_t frames_dev, i
             yolo2_hip_ctx *l = c->f16_lanes[i];
             hipStream_t ls = l->lane_stream ? l->lane_stream : st;
             if (l->lane_stream) HIP_TRY(hipStreamWaitEvent(ls, c->ev_fork, 0), YOLO2_ERROR);
-            const int rc = yolo2_hip_run_batch_fp16(l, frames_dev + (uint64_t)i * half * YOLO2_FRAME_ELEMS * sizeof(float), half,
-                                                    region_dev + (uint64_t)i * half * YOLO2_REGION_ELEMS * sizeof(float), ls);
+            const int rc = run_f16(l, lb ? 0 : frames_dev + (uint64_t)i * half * YOLO2_FRAME_ELEMS * sizeof(float), lb, lb_first + i * half, half,
+                                   region_dev + (uint64_t)i * half * YOLO2_REGION_ELEMS * sizeof(float), ls);
             if (rc) return rc;
             if (l->lane_stream) HIP_TRY(hipEventRecord(l->ev_join, ls), YOLO2_ERROR);
         }
@@ -778,15 +797,25 @@ extern "C" int yolo2_hip_run_batch_fp16(yolo2_hip_ctx *c, uint64_t frames_dev, i
     const float *frames = (const float *)(uintptr_t)frames_dev;
     float *region = (float *)(uintptr_t)region_dev;
     int next_ev = 0;
-    for (const F16Step &s : c->f16_plan->steps) {
+    const F16Plan &P = *c->f16_plan;
+    if (lb && !P.launch_u8) return fail(YOLO2_ERROR, "fp16 plan has no layer-0 step from bytes");
+    for (const F16Step &s : P.steps) {
         if (ev) for (; next_ev <= s.layer; ++next_ev) (void)hipEventRecord(ev[next_ev], st);   // layers without a launch of their own
-        s.launch(s, frames, region, st);
+        if (lb && s.layer == 0)
+            P.launch_u8(P.u8, lb, lb_first, st);
+        else
+            s.launch(s, frames, region, st);
         if (ev) { (void)hipEventRecord(ev[s.layer + 1], st); next_ev = s.layer + 2; }
     }
     if (ev) for (; next_ev <= 32; ++next_ev) (void)hipEventRecord(ev[next_ev], st);
     HIP_TRY(hipGetLastError(), YOLO2_ERROR);
     if (ev) c->prof_runs++;
     return YOLO2_SUCCESS;
+}
+
+extern "C" int yolo2_hip_run_batch_fp16(yolo2_hip_ctx *c, uint64_t frames_dev, int batch, uint64_t region_dev, void *stream)
+{
+    return run_f16(c, frames_dev, nullptr, 0, batch, region_dev, stream);
 }
 
 // ---------------------------------------------------------------------------- split-fp16: the MFMA path inside the fp32 tolerance
@@ -928,4 +957,33 @@ extern "C" int yolo2_hip_run_batch_fp16_host(yolo2_hip_ctx *c, const float *fram
     (void)hipFree(fd);
     (void)hipFree(rd);
     return rc;
+}
+
+// ---------------------------------------------------------------------------- the images entries' pass (yolo2_hip.hip)
+
+int y2_f16_images_ctx(yolo2_hip_ctx *c, int split, yolo2_hip_ctx **run)
+{
+    if (split != 0 && split != 1) return fail(YOLO2_ERROR, "split must be 0 (fp16) or 1 (fp32 tolerance), not %d", split);
+    if (!c->f16_loaded || !c->f16_plan || !c->wf32) return fail(YOLO2_ERROR, "fp32 weights not loaded (yolo2_hip_load_weights_fp32)");
+    if (split) {
+        HIP_TRY(hipSetDevice(c->device), YOLO2_INIT_ERROR);
+        const int rc = ensure_tol_twin(c);
+        if (rc) return rc;
+    }
+    *run = split ? c->tol : c;
+    return YOLO2_SUCCESS;
+}
+
+bool y2_f16_images_fused(const yolo2_hip_ctx *run) { return !run->f16_plan->sw.no_mfma0; }
+
+int y2_f16_run_images(yolo2_hip_ctx *run, const uint8_t *lb, int batch, float *region_dev, hipStream_t st)
+{
+    if (!lb) return fail(YOLO2_ERROR, "null buffer address");
+    return run_f16(run, 0, lb, 0, batch, (uint64_t)(uintptr_t)region_dev, st);
+}
+
+const char *y2_f16_images_kernel(const yolo2_hip_ctx *run)
+{
+    if (!run->f16_lanes.empty() && run->f16_last_laned) run = run->f16_lanes[0];
+    return run->f16_plan && run->f16_plan->launch_u8 ? run->f16_plan->u8.kernel : "";
 }

@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <thread>
 #include <vector>
 
 #include "y2_internal.hpp"
@@ -204,6 +205,8 @@ static void pipe_free(PipeBufs &p)
         if (p.hcounts[k]) (void)hipHostFree(p.hcounts[k]);
         if (p.hin[k]) (void)hipHostFree(p.hin[k]);
         if (p.hout[k]) (void)hipHostFree(p.hout[k]);
+        if (p.hregf[k]) (void)hipHostFree(p.hregf[k]);
+        (void)hipFree(p.dregf[k]);
         (void)hipFree(p.dbytes[k]); (void)hipFree(p.din[k]); (void)hipFree(p.dout[k]);
         if (p.e_in[k]) (void)hipEventDestroy(p.e_in[k]);
         if (p.e_run[k]) (void)hipEventDestroy(p.e_run[k]);
@@ -641,6 +644,187 @@ extern "C" int yolo2_hip_run_images_u8_dets(yolo2_hip_ctx *c, const uint8_t *con
     cleanup();
 #undef Y2_TRY
     return rc;
+}
+
+// ---------------------------------------------------------------------------- the fp16 / split-fp16 images entries
+//
+// yolo2_hip_run_images_u8_host / _dets on the matrix-core passes: the same chunks, staging format and three-stream overlap, but
+// layers 0+1 read the chunk's bytes themselves (k_conv0_pool_mfma_u8: no letterboxed frame is written or read back), the region
+// tensor is fp32 and the tail is y2_post_enqueue_f32.  Under f16_no_mfma0 the chunk is letterboxed into frames first and the frame
+// path's table runs (the reference route the tests compare with).
+
+static int pipe_ensure_regf(PipeBufs &p, int batch, bool need_host)
+{
+    if (p.regf_batch >= batch && (!need_host || p.hregf[0])) return YOLO2_SUCCESS;
+    need_host = need_host || p.hregf[0] != nullptr;
+    batch = std::max(batch, p.regf_batch);
+    const size_t rbytes = (size_t)batch * YOLO2_REGION_ELEMS * sizeof(float);
+    for (int k = 0; k < 2; ++k) {
+        if (p.hregf[k]) (void)hipHostFree(p.hregf[k]);
+        (void)hipFree(p.dregf[k]);
+        p.hregf[k] = nullptr; p.dregf[k] = nullptr;
+    }
+    p.regf_batch = 0;
+    for (int k = 0; k < 2; ++k)
+        if (hipMalloc((void **)&p.dregf[k], rbytes) != hipSuccess ||
+            (need_host && hipHostMalloc((void **)&p.hregf[k], rbytes, hipHostMallocDefault) != hipSuccess)) {
+            (void)hipGetLastError();
+            return fail(YOLO2_MMAP_ERROR, "fp32 region buffers for %d frames could not be allocated", batch);
+        }
+    p.regf_batch = batch;
+    return YOLO2_SUCCESS;
+}
+
+// The staging copy (pageable images -> the pinned chunk buffer) on up to kStageThreads threads: at the fp16 pass's rate one
+// thread's memcpy would be the slowest stage of the pipeline.
+static constexpr int kStageThreads = 4;
+
+static void stage_images(uint8_t *dst, const uint8_t *const *images, const size_t *offs, const size_t *bytes, int nf)
+{
+    size_t total = 0;
+    for (int i = 0; i < nf; ++i) total += bytes[i];
+    const int nt = (int)std::min<size_t>(kStageThreads, std::max<size_t>(1, total >> 22));   // a thread per 4 MiB at most
+    auto part = [&](int t) {   // an even share of the bytes; images are cut where the shares end
+        const size_t lo = total * t / nt, hi = total * (t + 1) / nt;
+        size_t at = 0;
+        for (int i = 0; i < nf; ++i) {
+            const size_t a = std::max(lo, at), b = std::min(hi, at + bytes[i]);
+            if (a < b) memcpy(dst + offs[i] + (a - at), images[i] + (a - at), b - a);
+            at += bytes[i];
+        }
+    };
+    std::vector<std::thread> th;
+    for (int t = 1; t < nt; ++t) th.emplace_back(part, t);
+    part(0);
+    for (auto &t : th) t.join();
+}
+
+// dets == nullptr: region tensors to region_host; otherwise the records (the int16 dets entry's contract)
+static int run_images_f16(yolo2_hip_ctx *c, int split, const uint8_t *const *images, const int *widths, const int *heights, int channels,
+                          int n, int batch, float *region_host, float thresh, float nms, int flags, yolo2_hip_det *dets, int cap,
+                          int *counts)
+{
+    const bool want_dets = dets != nullptr;
+    if (n <= 0 || batch <= 0 || (want_dets && cap <= 0))
+        return fail(YOLO2_ERROR, "bad image count %d / batch %d / capacity %d", n, batch, want_dets ? cap : 1);
+    if (want_dets && thresh < 0.f) return fail(YOLO2_ERROR, "negative threshold");
+    yolo2_hip_ctx *run = nullptr;
+    int rc = y2_f16_images_ctx(c, split, &run);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device), YOLO2_INIT_ERROR);
+    batch = std::min(batch, n);
+    const int chunks = (n + batch - 1) / batch, best_only = (flags & YOLO2_DETS_BEST_CLASS) ? 1 : 0;
+    auto in_chunk = [&](int k) { return std::min(batch, n - k * batch); };
+    auto padded = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t table_bytes = padded((size_t)batch * sizeof(LetterboxItem));   // the chunk's letterbox table leads its staging buffer
+    size_t cap_bytes = 0;   // bytes of the largest chunk
+    for (int k = 0; k < chunks; ++k) {
+        size_t sum = table_bytes;
+        for (int i = k * batch; i < k * batch + in_chunk(k); ++i) {
+            LetterboxArgs a;
+            if (!images[i]) return fail(YOLO2_ERROR, "null image %d", i);
+            if ((rc = letterbox_args(widths[i], heights[i], channels, 416, 416, a))) return rc;
+            sum += padded((size_t)widths[i] * heights[i] * channels);
+        }
+        cap_bytes = std::max(cap_bytes, sum);
+    }
+    const bool fused = y2_f16_images_fused(run);
+    if ((rc = pipe_ensure(c->pipe, cap_bytes, cap_bytes, batch, false))) return rc;      // (din: the frames of the f16_no_mfma0 route)
+    if ((rc = pipe_ensure_regf(c->pipe, batch, !want_dets))) return rc;
+    if (want_dets && (rc = pipe_ensure_post(c, batch, cap))) return rc;
+    PipeBufs &P = c->pipe;
+    const size_t gbytes = y2_post_geom_bytes(), rbytes = (size_t)batch * YOLO2_REGION_ELEMS * sizeof(float);
+    auto cleanup = [&]() { (void)hipDeviceSynchronize(); };
+#define Y2_TRY(expr, code) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { rc = fail(code, "%s failed: %s", #expr, hipGetErrorString(e_)); cleanup(); return rc; } } while (0)
+    auto drain = [&](int k) {
+        const int b = k & 1, nf = in_chunk(k);
+        (void)hipEventSynchronize(P.e_out[b]);
+        if (!want_dets) {
+            memcpy(region_host + (size_t)k * batch * YOLO2_REGION_ELEMS, P.hregf[b], (size_t)nf * YOLO2_REGION_ELEMS * sizeof(float));
+            return;
+        }
+        memcpy(counts + (size_t)k * batch, P.hcounts[b], (size_t)nf * sizeof(int));
+        for (int f = 0; f < nf; ++f) {   // frame numbers are global in the caller's records
+            const int cnt = std::min(P.hcounts[b][f], cap);
+            yolo2_hip_det *dst = dets + ((size_t)k * batch + f) * cap;
+            memcpy(dst, P.hdets[b] + (size_t)f * cap, (size_t)cnt * sizeof(yolo2_hip_det));
+            for (int r = 0; r < cnt; ++r) dst[r].frame = k * batch + f;
+        }
+    };
+    std::vector<size_t> offs((size_t)batch), sizes((size_t)batch);
+    std::vector<int> cw((size_t)batch), chh((size_t)batch);
+    for (int k = 0; k < chunks && rc == YOLO2_SUCCESS; ++k) {
+        const int b = k & 1, nf = in_chunk(k), first = k * batch;
+        if (k >= 2) drain(k - 2);   // buffer set b is free again once chunk k-2 has left it
+        size_t off = table_bytes;
+        for (int i = 0; i < nf; ++i) {
+            sizes[(size_t)i] = (size_t)widths[first + i] * heights[first + i] * channels;
+            offs[(size_t)i] = off;
+            off += padded(sizes[(size_t)i]);
+        }
+        stage_images(P.hin[b], images + first, offs.data(), sizes.data(), nf);
+        LetterboxItem *items = reinterpret_cast<LetterboxItem *>(P.hin[b]);
+        for (int f = 0; f < batch; ++f) {   // a partial last chunk repeats its last image
+            const int i = std::min(f, nf - 1);
+            cw[(size_t)f] = widths[first + i]; chh[(size_t)f] = heights[first + i];
+            items[f].off = offs[(size_t)i];
+            if ((rc = letterbox_args(widths[first + i], heights[first + i], channels, 416, 416, items[f].a))) break;
+        }
+        if (rc) break;
+        if (want_dets && (rc = y2_post_fill_geom(P.hgeom[b], cw.data(), chh.data(), batch))) break;
+        Y2_TRY(hipMemcpyAsync(P.dbytes[b], P.hin[b], off, hipMemcpyHostToDevice, P.s_in), YOLO2_DMA_ERROR);
+        if (want_dets) Y2_TRY(hipMemcpyAsync(P.post[b].geom, P.hgeom[b], (size_t)batch * gbytes, hipMemcpyHostToDevice, P.s_in), YOLO2_DMA_ERROR);
+        Y2_TRY(hipEventRecord(P.e_in[b], P.s_in), YOLO2_ERROR);
+        Y2_TRY(hipStreamWaitEvent(P.s_run, P.e_in[b], 0), YOLO2_ERROR);
+        if (fused) {
+            rc = y2_f16_run_images(run, P.dbytes[b], batch, P.dregf[b], P.s_run);
+        } else {
+            hipLaunchKernelGGL(k_letterbox_u8_batch, dim3(blocks_for((long)YOLO2_FRAME_ELEMS, 256), batch), dim3(256), 0, P.s_run, P.dbytes[b],
+                               P.din[b], (int)YOLO2_FRAME_ELEMS);
+            Y2_TRY(hipGetLastError(), YOLO2_ERROR);
+            rc = yolo2_hip_run_batch_fp16(run, (uint64_t)(uintptr_t)P.din[b], batch, (uint64_t)(uintptr_t)P.dregf[b], P.s_run);
+        }
+        if (rc) break;
+        Y2_TRY(hipEventRecord(P.e_run[b], P.s_run), YOLO2_ERROR);
+        Y2_TRY(hipStreamWaitEvent(P.s_out, P.e_run[b], 0), YOLO2_ERROR);
+        if (want_dets) {   // the tail on the download stream, straight from HBM (see yolo2_hip_run_images_u8_dets)
+            if ((rc = y2_post_enqueue_f32(P.dregf[b], batch, thresh, nms, cap, best_only, &P.post[b], P.s_out))) break;
+            Y2_TRY(hipMemcpyAsync(P.hcounts[b], P.post[b].counts, (size_t)batch * sizeof(int), hipMemcpyDeviceToHost, P.s_out), YOLO2_DMA_ERROR);
+            Y2_TRY(hipMemcpyAsync(P.hdets[b], P.post[b].dets, (size_t)batch * cap * sizeof(yolo2_hip_det), hipMemcpyDeviceToHost, P.s_out),
+                   YOLO2_DMA_ERROR);
+        } else {
+            Y2_TRY(hipMemcpyAsync(P.hregf[b], P.dregf[b], rbytes, hipMemcpyDeviceToHost, P.s_out), YOLO2_DMA_ERROR);
+        }
+        Y2_TRY(hipEventRecord(P.e_out[b], P.s_out), YOLO2_ERROR);
+    }
+    if (rc == YOLO2_SUCCESS) {
+        for (int k = std::max(0, chunks - 2); k < chunks; ++k) drain(k);
+        c->images_l0[split] = fused ? std::string(y2_f16_images_kernel(run))
+                                    : std::string("k_letterbox_u8_batch + ") + yolo2_hip_fp16_layer_kernel(run, 0);
+    }
+    cleanup();
+#undef Y2_TRY
+    return rc;
+}
+
+extern "C" int yolo2_hip_run_images_u8_f16_host(yolo2_hip_ctx *c, int split, const uint8_t *const *images, const int *widths,
+                                                const int *heights, int channels, int n, int batch, float *region_host)
+{
+    if (!c || !images || !widths || !heights || !region_host) return fail(YOLO2_ERROR, "null argument");
+    return run_images_f16(c, split, images, widths, heights, channels, n, batch, region_host, 0.f, 0.f, 0, nullptr, 0, nullptr);
+}
+
+extern "C" int yolo2_hip_run_images_u8_dets_f16(yolo2_hip_ctx *c, int split, const uint8_t *const *images, const int *widths,
+                                                const int *heights, int channels, int n, int batch, float thresh, float nms, int flags,
+                                                yolo2_hip_det *dets, int cap_per_frame, int *counts)
+{
+    if (!c || !images || !widths || !heights || !dets || !counts) return fail(YOLO2_ERROR, "null argument");
+    return run_images_f16(c, split, images, widths, heights, channels, n, batch, nullptr, thresh, nms, flags, dets, cap_per_frame, counts);
+}
+
+extern "C" const char *yolo2_hip_images_layer0_kernel(yolo2_hip_ctx *c, int split)
+{
+    return c && (split == 0 || split == 1) ? c->images_l0[split].c_str() : "";
 }
 
 extern "C" int yolo2_hip_run_frames_int16(yolo2_hip_ctx *c, const float *frames, int n_frames, int batch, int16_t *region,

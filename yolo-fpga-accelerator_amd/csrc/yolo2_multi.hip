@@ -609,3 +609,20 @@ extern "C" int yolo2_hip_multi_run_images_u8_dets(yolo2_hip_multi *m, const uint
     return rc;
 }
 
+
+extern "C" int yolo2_hip_multi_run_images_u8_dets_f16(yolo2_hip_multi *m, int split, const uint8_t *const *images, const int *widths,
+                                                      const int *heights, int channels, int n, int batch_per_device, float thresh, float nms,
+                                                      int flags, yolo2_hip_det *dets, int cap_per_frame, int *counts)
+{
+    if (!m || !images || !widths || !heights || !dets || !counts) return mfail(YOLO2_ERROR, "null argument");
+    if (n <= 0 || batch_per_device <= 0 || cap_per_frame <= 0) return mfail(YOLO2_ERROR, "bad image count / batch / capacity");
+    return multi_run(m, n, [&](yolo2_hip_ctx *c, int lo, int hi) {
+        const int r = yolo2_hip_run_images_u8_dets_f16(c, split, images + lo, widths + lo, heights + lo, channels, hi - lo,
+                                                       std::min(batch_per_device, hi - lo), thresh, nms, flags, dets + (size_t)lo * cap_per_frame,
+                                                       cap_per_frame, counts + lo);
+        if (r == YOLO2_SUCCESS)   // records carry global frame indices
+            for (int f = lo; f < hi; ++f)
+                for (int k = 0, cnt = std::min(counts[f], cap_per_frame); k < cnt; ++k) dets[(size_t)f * cap_per_frame + k].frame = f;
+        return r;
+    });
+}

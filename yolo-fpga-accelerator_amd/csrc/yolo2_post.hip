@@ -483,8 +483,16 @@ int postprocess(yolo2_hip_ctx *ctx, uint64_t region_dev, int batch, int final_q,
     float *proc_dev = nullptr;
     if (proc_host) HIPP_TRY(hipMalloc((void **)&proc_dev, (size_t)batch * YOLO2_REGION_ELEMS * sizeof(float)), YOLO2_MMAP_ERROR);
     float *final_rows = nullptr;
-    enqueue<T>((const T *)(uintptr_t)region_dev, l, final_q, batch, thresh, nms, dets ? cap : 0, 0, *s, proc_dev, st, &final_rows);
-    hipError_t e = hipGetLastError();
+    hipError_t e = hipSuccess;
+    if constexpr (std::is_same<T, float>::value) {
+        if ((rc = y2_post_enqueue_f32((const float *)(uintptr_t)region_dev, batch, thresh, nms, dets ? cap : 0, 0, s, st, proc_dev, &final_rows))) {
+            if (proc_dev) (void)hipFree(proc_dev);
+            return rc;
+        }
+    } else {
+        enqueue<T>((const T *)(uintptr_t)region_dev, l, final_q, batch, thresh, nms, dets ? cap : 0, 0, *s, proc_dev, st, &final_rows);
+        e = hipGetLastError();
+    }
     if (e == hipSuccess && dets) e = hipMemcpyAsync(counts, s->counts, (size_t)batch * sizeof(int), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess && dets) e = hipMemcpyAsync(dets, s->dets, (size_t)batch * cap * sizeof(DetRec), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess && rows_host) e = hipMemcpyAsync(rows_host, final_rows, (size_t)batch * kDets * kEntries * sizeof(float), hipMemcpyDeviceToHost, st);
@@ -551,3 +559,12 @@ int y2_post_enqueue_int16(int device, const int16_t *region_dev, int batch, int 
     return YOLO2_SUCCESS;
 }
 
+
+int y2_post_enqueue_f32(const float *region_dev, int batch, float thresh, float nms, int cap, int best_only, Y2PostBufs *b, hipStream_t st,
+                        float *proc_dev, float **final_rows)
+{
+    if (batch > b->cap_frames || (size_t)batch * (size_t)cap > b->cap_dets) return pfail(YOLO2_ERROR, "post-processing buffers too small for %d frames x %d records", batch, cap);
+    enqueue<float>(region_dev, Luts(), 0, batch, thresh, nms, cap, best_only, *b, proc_dev, st, final_rows);
+    HIPP_TRY(hipGetLastError(), YOLO2_ERROR);
+    return YOLO2_SUCCESS;
+}

@@ -106,7 +106,9 @@ void print_usage(const char *prog)
         "  --strict              Stop at the first input that cannot be read or decoded (default: log it, skip the frame, go on)\n"
         "  --no-plan-cache       int16: do not read / write <weights>/weights_reorg_int16.bin.y2plan (the weight set's bounds, forms and\n"
         "                        timed conv plans; with it a weight set is timed once and every later run uses the same kernels)\n"
-        "  --post <gpu|host>     Where region + boxes + NMS run (default gpu)\n",
+        "  --post <gpu|host>     Where region + boxes + NMS run (default gpu; host: int16 only)\n"
+        "  --precision int16 | fp16 | fp32fast   also when streaming: fp16 / fp32fast read weights_reorg.bin + bias.bin and run layers 0+1\n"
+        "                        straight from the image bytes on the matrix cores (yolo2_hip_run_images_u8_dets_f16)\n",
         prog);
 }
 
@@ -452,12 +454,30 @@ class DecodePool {
 // order).  Round 3 drove all devices from one call per chunk (every chunk was split over all devices and joined): a chunk was as
 // slow as its slowest device and the reader fed them in lock step.  Now a chunk belongs to ONE device, devices take chunks as
 // they become free (work-conserving, no join across devices), and the writer restores the order by chunk number.
+// a float blob of at least `want` elements (weights_reorg.bin / bias.bin)
+std::vector<float> read_floats(const std::string &path, size_t want)
+{
+    std::ifstream f(path, std::ios::binary | std::ios::ate);
+    if (!f) throw std::runtime_error("Cannot open " + path);
+    const size_t n = (size_t)f.tellg() / sizeof(float);
+    if (n < want) throw std::runtime_error(path + " is too small (" + std::to_string(n) + " floats, need " + std::to_string(want) + ")");
+    std::vector<float> v(n);
+    f.seekg(0);
+    f.read(reinterpret_cast<char *>(v.data()), (std::streamsize)(n * sizeof(float)));
+    return v;
+}
+
 void run_stream(AppConfig cfg)
 {
     namespace fs = std::filesystem;
     static char outbuf[1 << 16];
     std::setvbuf(stdout, outbuf, _IOFBF, sizeof(outbuf));    // thousands of frames a second: no write() per line
-    if (cfg.precision != "int16") throw std::runtime_error("the streaming frontend runs the int16 path");
+    // fp16 / fp32fast: the matrix-core passes from image bytes (yolo2_hip_run_images_u8_dets_f16), split = 0 / 1
+    const bool f16 = cfg.precision == "fp16" || cfg.precision == "fp32fast";
+    const int split = cfg.precision == "fp32fast" ? 1 : 0;
+    if (cfg.precision != "int16" && !f16) throw std::runtime_error("the streaming frontend runs the int16, fp16 and fp32fast paths");
+    if (f16 && cfg.post == "host")
+        throw std::runtime_error("--post host runs the int16 region tensor only; --precision " + cfg.precision + " needs --post gpu");
     if (cfg.devices.empty()) cfg.devices.push_back(cfg.device);
     if (cfg.batch <= 0) throw std::runtime_error("--batch must be positive");
     const y2h::Network net = y2h::parse_cfg(cfg.cfg_path);
@@ -473,7 +493,11 @@ void run_stream(AppConfig cfg)
     yolo2_hip_multi *m = nullptr;
     if (yolo2_hip_multi_create(cfg.devices.data(), ndev, &m) != YOLO2_SUCCESS) throw std::runtime_error(yolo2_hip_last_error());
     struct Guard { yolo2_hip_multi *m; ~Guard() { yolo2_hip_multi_destroy(m); } } guard{m};
-    {
+    if (f16) {
+        const std::vector<float> w = read_floats(cfg.weights_dir + "/weights_reorg.bin", (size_t)YOLO2_N_WEIGHTS);
+        const std::vector<float> b = read_floats(cfg.weights_dir + "/bias.bin", (size_t)YOLO2_N_BIAS);
+        if (yolo2_hip_multi_load_weights_fp32(m, w.data(), w.size(), b.data(), b.size()) != YOLO2_SUCCESS) throw std::runtime_error(yolo2_hip_last_error());
+    } else {
         // the weight-side cache (include/yolo2_hip.h): beside the interchange file, one per weight set, shared by every device
         if (cfg.plan_cache)
             for (int i = 0; i < yolo2_hip_multi_num_devices(m); ++i)
@@ -605,9 +629,12 @@ void run_stream(AppConfig cfg)
     auto lane = [&](int slot) {
         try {
             yolo2_hip_ctx *ctx = yolo2_hip_multi_ctx(m, slot);
-            // while the reader decodes its first chunk: plan the batch (activation tensors, lanes) on this device
-            if (yolo2_hip_set_batch(ctx, cfg.batch) != YOLO2_SUCCESS) throw std::runtime_error(yolo2_hip_last_error());
-            if (slot == 0) std::printf("  conv plans: %s\n", plan_source_name(yolo2_hip_plan_source(ctx)));
+            // while the reader decodes its first chunk: plan the batch (activation tensors, lanes) on this device (int16; the fp16
+            // passes build their launch table at the first chunk)
+            if (!f16) {
+                if (yolo2_hip_set_batch(ctx, cfg.batch) != YOLO2_SUCCESS) throw std::runtime_error(yolo2_hip_last_error());
+                if (slot == 0) std::printf("  conv plans: %s\n", plan_source_name(yolo2_hip_plan_source(ctx)));
+            }
             std::unique_ptr<Chunk> ck;
             std::vector<int16_t> region;
             std::vector<yolo2_hip_det> recs;
@@ -627,9 +654,11 @@ void run_stream(AppConfig cfg)
                         const int cap = 845;
                         recs.resize((size_t)n * cap);
                         std::vector<int> counts((size_t)n);
-                        if (yolo2_hip_run_images_u8_dets(ctx, ptrs.data(), ws.data(), hs.data(), 3, n, cfg.batch, cfg.thresh, cfg.nms, YOLO2_DETS_BEST_CLASS,
-                                                         recs.data(), cap, counts.data(), &q) != YOLO2_SUCCESS)
-                            throw std::runtime_error(yolo2_hip_last_error());
+                        const int rc = f16 ? yolo2_hip_run_images_u8_dets_f16(ctx, split, ptrs.data(), ws.data(), hs.data(), 3, n, cfg.batch, cfg.thresh,
+                                                                              cfg.nms, YOLO2_DETS_BEST_CLASS, recs.data(), cap, counts.data())
+                                           : yolo2_hip_run_images_u8_dets(ctx, ptrs.data(), ws.data(), hs.data(), 3, n, cfg.batch, cfg.thresh, cfg.nms,
+                                                                          YOLO2_DETS_BEST_CLASS, recs.data(), cap, counts.data(), &q);
+                        if (rc != YOLO2_SUCCESS) throw std::runtime_error(yolo2_hip_last_error());
                         for (int f = 0; f < n; ++f) {
                             if (counts[(size_t)f] > cap) throw std::runtime_error("detection records truncated");   // cannot happen in best-class mode
                             for (int k = 0; k < counts[(size_t)f]; ++k) {
@@ -701,16 +730,6 @@ void run_detector(AppConfig cfg)
     int frames_run = cfg.batch;
     if (cfg.precision == "fp32" || cfg.precision == "fp16" || cfg.precision == "fp32fast") {
         // weights/weights_reorg.bin + weights/bias.bin, the files load_weights() reads at Precision::FP32 (yolo2_model.cpp:171-183)
-        auto read_floats = [](const std::string &path, size_t want) {
-            std::ifstream f(path, std::ios::binary | std::ios::ate);
-            if (!f) throw std::runtime_error("Cannot open " + path);
-            const size_t n = (size_t)f.tellg() / sizeof(float);
-            if (n < want) throw std::runtime_error(path + " is too small (" + std::to_string(n) + " floats, need " + std::to_string(want) + ")");
-            std::vector<float> v(n);
-            f.seekg(0);
-            f.read(reinterpret_cast<char *>(v.data()), (std::streamsize)(n * sizeof(float)));
-            return v;
-        };
         const std::vector<float> w = read_floats(cfg.weights_dir + "/weights_reorg.bin", (size_t)YOLO2_N_WEIGHTS);
         const std::vector<float> b = read_floats(cfg.weights_dir + "/bias.bin", (size_t)YOLO2_N_BIAS);
         if (yolo2_hip_load_weights_fp32(ctx, w.data(), w.size(), b.data(), b.size()) != YOLO2_SUCCESS) throw std::runtime_error(yolo2_hip_last_error());

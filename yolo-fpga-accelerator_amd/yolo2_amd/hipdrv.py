@@ -47,6 +47,8 @@ EXPORTS = [
     "yolo2_hip_i16_plan_check", "yolo2_hip_ks_scratch_bytes", "yolo2_hip_i16_edge_map", "yolo2_hip_last_layer_edge",
     "yolo2_hip_run_batch_f32tol", "yolo2_hip_run_batch_f32tol_host", "yolo2_hip_f32tol_layer_kernel", "yolo2_hip_num_lanes_f32tol",
     "yolo2_hip_debug_f16_tensor",
+    "yolo2_hip_run_images_u8_f16_host", "yolo2_hip_run_images_u8_dets_f16", "yolo2_hip_multi_run_images_u8_dets_f16",
+    "yolo2_hip_images_layer0_kernel",
 ]
 
 
@@ -156,6 +158,10 @@ def lib():
     sig("yolo2_hip_num_lanes_f32tol", [vp])
     sig("yolo2_hip_ks_scratch_bytes", [vp], C.c_size_t)
     sig("yolo2_hip_debug_f16_tensor", [vp, i32, i32, i32, i32, vp, C.c_size_t, pi32])
+    sig("yolo2_hip_run_images_u8_f16_host", [vp, i32, vp, vp, vp, i32, i32, i32, vp])
+    sig("yolo2_hip_run_images_u8_dets_f16", [vp, i32, vp, vp, vp, i32, i32, i32, C.c_float, C.c_float, i32, vp, i32, vp])
+    sig("yolo2_hip_multi_run_images_u8_dets_f16", [vp, i32, vp, vp, vp, i32, i32, i32, C.c_float, C.c_float, i32, vp, i32, vp])
+    sig("yolo2_hip_images_layer0_kernel", [vp, i32], C.c_char_p)
     L.yolo2_hip_multi_create.argtypes = [vp, i32, C.POINTER(vp)]
     L.yolo2_hip_multi_destroy.argtypes = [vp]
     L.yolo2_hip_multi_num_devices.argtypes = [vp]
@@ -466,6 +472,19 @@ class Yolo2Hip:
               "yolo2_hip_run_batch_f32tol_host")
         return region
 
+    def run_images_f16_host(self, images, batch: int, split: bool = False) -> np.ndarray:
+        """images (uint8 [h][w][3] or [h][w] grey, any sizes) -> float32 region tensors [n][425][13][13] through the fp16 pass
+        (split=True: the fp32-tolerance pass); layers 0+1 read the image bytes on the GPU (yolo2_hip_run_images_u8_f16_host)."""
+        n, ptrs, ws, hs, ch, _keep = _image_args(images)
+        region = np.empty((n, 425, 13, 13), dtype=np.float32)
+        check(lib().yolo2_hip_run_images_u8_f16_host(self._h, int(bool(split)), ptrs, ws, hs, ch, n, batch,
+                                                     region.ctypes.data_as(C.c_void_p)), "yolo2_hip_run_images_u8_f16_host")
+        return region
+
+    def images_layer0_kernel(self, split: bool = False) -> str:
+        """What the last images call of the fp16 (split=False) / fp32-tolerance pass ran for layers 0+1 ("" before the first)."""
+        return lib().yolo2_hip_images_layer0_kernel(self._h, int(bool(split))).decode()
+
     def run_batch_f32tol_ptr(self, frames_ptr: int, batch: int, region_ptr: int, stream: int = 0):
         check(lib().yolo2_hip_run_batch_f32tol(self._h, frames_ptr, batch, region_ptr, C.c_void_p(stream)), "yolo2_hip_run_batch_f32tol")
 
@@ -563,17 +582,37 @@ def postprocess(ctx, region_ptr: int, batch: int, im_w, im_h, thresh: float, nms
 DETS_BEST_CLASS = 1
 
 
-def run_images_dets(handle, images, batch: int, thresh: float, nms: float, cap: int = 845, best_class: bool = True, multi: bool = False):
-    """yolo2_hip_run_images_u8_dets / yolo2_hip_multi_run_images_u8_dets: host images (uint8 [h][w][3]) -> per-frame detection
-    records; letterbox, network and the tail run on the device(s), the region tensor never leaves HBM."""
+def _image_args(images):
+    """(n, pointer array, widths, heights, channels, the contiguous arrays the pointers point into)"""
     imgs = [np.ascontiguousarray(im, dtype=np.uint8) for im in images]
     n = len(imgs)
     ch = 1 if imgs[0].ndim == 2 else imgs[0].shape[2]
     ptrs = (C.c_void_p * n)(*[im.ctypes.data for im in imgs])
     ws = (C.c_int * n)(*[im.shape[1] for im in imgs])
     hs = (C.c_int * n)(*[im.shape[0] for im in imgs])
+    return n, ptrs, ws, hs, ch, imgs
+
+
+PRECISIONS = ("int16", "fp16", "fp32fast")
+
+
+def run_images_dets(handle, images, batch: int, thresh: float, nms: float, cap: int = 845, best_class: bool = True, multi: bool = False,
+                    precision: str = "int16"):
+    """yolo2_hip_run_images_u8_dets / yolo2_hip_multi_run_images_u8_dets: host images (uint8 [h][w][3]) -> per-frame detection
+    records; letterbox, network and the tail run on the device(s), the region tensor never leaves HBM.  precision "fp16" /
+    "fp32fast" (the split-fp16 pass) run the _dets_f16 entries instead (fp32 weights loaded); their final_q is None."""
+    if precision not in PRECISIONS:
+        raise ValueError(f"precision must be one of {PRECISIONS}, not {precision!r}")
+    n, ptrs, ws, hs, ch, _keep = _image_args(images)
     dets = np.zeros((n, cap), dtype=DET_DTYPE)
     counts = np.zeros(n, dtype=np.int32)
+    flags = DETS_BEST_CLASS if best_class else 0
+    if precision != "int16":
+        split = int(precision == "fp32fast")
+        fn = lib().yolo2_hip_multi_run_images_u8_dets_f16 if multi else lib().yolo2_hip_run_images_u8_dets_f16
+        check(fn(handle, split, ptrs, ws, hs, ch, n, batch, thresh, nms, flags, dets.ctypes.data_as(C.c_void_p), cap,
+                 counts.ctypes.data_as(C.c_void_p)), "yolo2_hip_run_images_u8_dets_f16")
+        return {"dets": [dets[f, :min(int(counts[f]), cap)] for f in range(n)], "counts": counts, "final_q": None}
     q = C.c_int(0)
     fn = lib().yolo2_hip_multi_run_images_u8_dets if multi else lib().yolo2_hip_run_images_u8_dets
     check(fn(handle, ptrs, ws, hs, ch, n, batch, thresh, nms, DETS_BEST_CLASS if best_class else 0, dets.ctypes.data_as(C.c_void_p), cap,
@@ -690,6 +729,13 @@ class Yolo2HipMulti:
         vp = lambda a: a.ctypes.data_as(C.c_void_p)
         check(lib().yolo2_hip_multi_load_weights_int16(self._m, vp(w), w.size, vp(b), b.size, vp(wq), wq.size, vp(bq), bq.size,
                                                        vp(aq), aq.size), "yolo2_hip_multi_load_weights_int16")
+
+    def load_model_fp32(self, model):
+        """fp32 weights on every device (the fp16 / split-fp16 passes)"""
+        w = np.ascontiguousarray(model.weights_f32(), dtype=np.float32)
+        b = np.ascontiguousarray(model.bias_f32(), dtype=np.float32)
+        check(lib().yolo2_hip_multi_load_weights_fp32(self._m, w.ctypes.data_as(C.c_void_p), w.size, b.ctypes.data_as(C.c_void_p), b.size),
+              "yolo2_hip_multi_load_weights_fp32")
 
     def run_frames(self, frames: np.ndarray, batch_per_device: int):
         frames = np.ascontiguousarray(frames, dtype=np.float32)
