@@ -450,6 +450,38 @@ int yolo2_hip_run_images_u8_dets_f16(yolo2_hip_ctx *ctx, int split, const uint8_
  * f16_no_mfma0 "k_letterbox_u8_batch + " and the frame path's layer-0 kernel */
 const char *yolo2_hip_images_layer0_kernel(yolo2_hip_ctx *ctx, int split);
 
+/* ------------------------------------------------------- camera pixel formats: the same entries with a pixel format
+ *
+ * The reference's camera loop (linux_app/src/main.c:942-984) takes MJPEG and YUYV from V4L2 and turns both into RGB24 on the host
+ * before rgb24_to_chw_float, letterbox and inference.  These entries are the letterbox / images entries above with `int pixfmt`
+ * where those have `int channels`:
+ *   YOLO2_PIX_GREY8, YOLO2_PIX_RGB24   exactly the u8 entries with channels 1 / 3 (same code path, same kernels)
+ *   YOLO2_PIX_YUYV                     packed YUYV 4:2:2, 2 bytes per pixel (V4L2 'YUYV' = ffmpeg yuyv422: Y0 U Y1 V per pixel
+ *                                      pair), width even.  The GPU reads the YUYV bytes itself - 2 bytes per pixel cross PCIe
+ *                                      and no host thread converts them - and every result is bit-identical to the RGB24
+ *                                      entries on the output of the reference's yolo2_yuyv_to_rgb24
+ *                                      (linux_app/src/yolo2_v4l2.c:328-374; y2h_yuyv_to_rgb24 in libyolo2_host.so restates it):
+ *                                        c = Y - 16, d = U - 128, e = V - 128, arithmetic >> 8, each clamped to 0..255
+ *                                        R = (298 c + 409 e + 128) >> 8
+ *                                        G = (298 c - 100 d - 208 e + 128) >> 8
+ *                                        B = (298 c + 516 d + 128) >> 8
+ * A call is one format.  An odd YUYV width or an unknown pixfmt is YOLO2_ERROR (yolo2_hip_last_error names it) before anything is
+ * launched; yolo2_hip_letterbox_pix also wants a YUYV image_dev on a 4-byte boundary.  After a YUYV call
+ * yolo2_hip_images_layer0_kernel reports k_conv0_pool_mfma_yuyv[<split>], or under f16_no_mfma0 "k_letterbox_yuyv_batch + " and
+ * the frame path's layer-0 kernel. */
+enum { YOLO2_PIX_GREY8 = 1, YOLO2_PIX_RGB24 = 3, YOLO2_PIX_YUYV = 0x56595559 /* V4L2 fourcc 'YUYV' */ };
+int yolo2_hip_letterbox_pix(uint64_t image_dev, int w, int h, int pixfmt, uint64_t frame_dev, int net_w, int net_h, void *stream);
+int yolo2_hip_run_images_pix_host(yolo2_hip_ctx *ctx, const uint8_t *const *images, const int *widths, const int *heights,
+                                  int pixfmt, int n, int batch, int16_t *region_host, int *final_q);
+int yolo2_hip_run_images_pix_dets(yolo2_hip_ctx *ctx, const uint8_t *const *images, const int *widths, const int *heights,
+                                  int pixfmt, int n, int batch, float thresh, float nms, int flags, yolo2_hip_det *dets,
+                                  int cap_per_frame, int *counts, int *final_q);
+int yolo2_hip_run_images_pix_f16_host(yolo2_hip_ctx *ctx, int split, const uint8_t *const *images, const int *widths,
+                                      const int *heights, int pixfmt, int n, int batch, float *region_host);
+int yolo2_hip_run_images_pix_dets_f16(yolo2_hip_ctx *ctx, int split, const uint8_t *const *images, const int *widths,
+                                      const int *heights, int pixfmt, int n, int batch, float thresh, float nms, int flags,
+                                      yolo2_hip_det *dets, int cap_per_frame, int *counts);
+
 /* ------------------------------------------------------- multi-GPU: frame sharding, one weight broadcast
  *
  * SURVEY.md 8(b) "init(device_list) ... load_weights (H2D on rank 0, RCCL broadcast to the rest)", 8(e): frames are
@@ -492,6 +524,16 @@ int  yolo2_hip_multi_run_images_u8_dets(yolo2_hip_multi *m, const uint8_t *const
 int  yolo2_hip_multi_run_images_u8_dets_f16(yolo2_hip_multi *m, int split, const uint8_t *const *images, const int *widths,
                                             const int *heights, int channels, int n, int batch_per_device, float thresh, float nms,
                                             int flags, yolo2_hip_det *dets, int cap_per_frame, int *counts);
+/* the three with a pixel format (see yolo2_hip_run_images_pix_host) */
+int  yolo2_hip_multi_run_images_pix_host(yolo2_hip_multi *m, const uint8_t *const *images, const int *widths,
+                                         const int *heights, int pixfmt, int n, int batch_per_device,
+                                         int16_t *region_host, int *final_q);
+int  yolo2_hip_multi_run_images_pix_dets(yolo2_hip_multi *m, const uint8_t *const *images, const int *widths, const int *heights,
+                                         int pixfmt, int n, int batch_per_device, float thresh, float nms, int flags,
+                                         yolo2_hip_det *dets, int cap_per_frame, int *counts, int *final_q);
+int  yolo2_hip_multi_run_images_pix_dets_f16(yolo2_hip_multi *m, int split, const uint8_t *const *images, const int *widths,
+                                             const int *heights, int pixfmt, int n, int batch_per_device, float thresh, float nms,
+                                             int flags, yolo2_hip_det *dets, int cap_per_frame, int *counts);
 
 /* (b) one process per device (torchrun / MPI style; what bench.py --gpus N runs): rank 0 makes the 128-byte id
  * (ncclGetUniqueId), the launcher hands it to every rank, each rank joins with its context (ncclCommInitRank), then

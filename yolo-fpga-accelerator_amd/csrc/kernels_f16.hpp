@@ -28,7 +28,7 @@
 #include <cstdint>
 
 #include "layout.hpp"
-#include "letterbox.hpp"   // k_conv0_pool_mfma_u8: LetterboxItem, lb_value_at
+#include "letterbox.hpp"   // k_conv0_pool_mfma_u8 / _yuyv: LetterboxItem, lb_value_at
 
 namespace y2 {
 
@@ -2753,7 +2753,10 @@ __global__ void k_pack_weights_f16(const float *__restrict__ src, _Float16 *__re
 // lb_first + b, and every patch value is lb_value_at()'s fp32 value of that canvas element (0 outside the 416 x 416 canvas, as the
 // frame path's masks make it), i.e. exactly the float k_letterbox_u8_batch stores there.  Conversion, MFMAs, pool and stores are
 // the frame form's, so the output is bit-identical to k_letterbox_u8_batch followed by k_conv0_pool_mfma.
-template <bool SPLIT, bool U8>
+// PIX is the pixel fetch of the byte form (letterbox.hpp): LbInterleaved for k_conv0_pool_mfma_u8, LbYuyv for k_conv0_pool_mfma_yuyv,
+// whose chunks hold packed YUYV 4:2:2 frames (table items with ch == 2) - a second instantiation, so that the RGB / grey kernel
+// does not pay for a format it is not reading; bit-identical to k_letterbox_yuyv_batch followed by k_conv0_pool_mfma.
+template <bool SPLIT, bool U8, class PIX = LbInterleaved>
 __device__ __forceinline__ void conv0_pool_mfma_tiles(const float *__restrict__ frames, const uint8_t *__restrict__ lb, int lb_first,
                                                       const float *__restrict__ w0, const float *__restrict__ bias0,
                                                       _Float16 *__restrict__ out, int H, int W, int oWp, int oPL, int n_tile_total)
@@ -2832,7 +2835,7 @@ __device__ __forceinline__ void conv0_pool_mfma_tiles(const float *__restrict__ 
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const bool canvas = y >= 0 && y < H && x0 + e >= 0 && x0 + e < W;   // outside: the conv's zero padding
-                    v[e] = !canvas ? 0.f : (band ? .5f : lb_value_at(img, a, k, y, x0 + e, q));
+                    v[e] = !canvas ? 0.f : (band ? .5f : lb_value_at<LbTable, PIX>(img, a, k, y, x0 + e, q));
                 }
                 pv[it] = make_float4(v[0], v[1], v[2], v[3]);
             }
@@ -2982,6 +2985,15 @@ __global__ __launch_bounds__(256) void k_conv0_pool_mfma_u8(const uint8_t *__res
                                                              int n_tile_total)
 {
     conv0_pool_mfma_tiles<SPLIT, true>(nullptr, lb, lb_first, w0, bias0, out, 416, 416, oWp, oPL, n_tile_total);
+}
+
+// the same from a chunk of packed YUYV 4:2:2 frames (see PIX above)
+template <bool SPLIT = false>
+__global__ __launch_bounds__(256) void k_conv0_pool_mfma_yuyv(const uint8_t *__restrict__ lb, int lb_first, const float *__restrict__ w0,
+                                                               const float *__restrict__ bias0, _Float16 *__restrict__ out, int oWp, int oPL,
+                                                               int n_tile_total)
+{
+    conv0_pool_mfma_tiles<SPLIT, true, LbYuyv>(nullptr, lb, lb_first, w0, bias0, out, 416, 416, oWp, oPL, n_tile_total);
 }
 
 // (Round 4 also built a second form with the im2col expansion on the B side - an MFMA row = four adjacent conv pixels, K = (channel,

@@ -4,12 +4,19 @@
 // is.  This header restates its two structs token for token (tests/test_images_f16_abi.py compares them) and its lb_part / lb_value
 // with the byte -> v / 255 step as a parameter, so that the fused kernel can take it from a table in LDS.  Every float operation
 // is lb_part / lb_value's, in their order: the values are bit-identical (tests/test_gpu_images_f16.py).
+// The pixel fetch is a parameter too: LbInterleaved reads kernels_pre.hpp's 1 or 3 interleaved byte channels, LbYuyv turns a packed
+// YUYV 4:2:2 pixel into the R, G or B byte first (kernels_pix.hpp, k_conv0_pool_mfma_yuyv).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 namespace y2 {
 
+// (kernels_pix.hpp sets Y2_LETTERBOX_STRUCTS_FROM_PRE: in the one translation unit that includes kernels_pre.hpp the two structs
+//  are kernels_pre.hpp's own)
+#ifndef Y2_LETTERBOX_STRUCTS_FROM_PRE
 struct LetterboxArgs {
     int w, h, ch;          // source image: w x h, ch interleaved byte channels (1 or 3)
     int net_w, net_h;      // canvas (416 x 416)
@@ -17,6 +24,7 @@ struct LetterboxArgs {
     int off_x, off_y;      // where the fitted image sits on the canvas
     float w_scale, h_scale;
 };
+#endif
 
 // byte -> v / 255.f as load_image_stb computes it
 struct LbDiv255 {
@@ -28,23 +36,55 @@ struct LbTable {
     __device__ float operator()(uint8_t v) const { return t[v]; }
 };
 
+// The pixel fetch, a type parameter of lb_part_q: which bytes of image row r are byte k of pixel x.
+// kernels_pre.hpp's: a.ch interleaved byte channels, a grey image gives its one channel three times (lb_part_q's own lines)
+struct LbInterleaved {};
+// Packed YUYV 4:2:2 (V4L2 'YUYV', a.ch == 2 bytes per pixel, a.w even): pixels 2p and 2p + 1 are the bytes Y0 U Y1 V at 4p, and
+// the byte is the reference camera loop's conversion (yolo2_yuyv_to_rgb24, linux_app/src/yolo2_v4l2.c:328-374): integer BT.601
+// with an arithmetic shift and a clamp to 0..255.  The pair is one aligned dword (rows are 2 a.w bytes, the image starts on a
+// 4-byte boundary), loaded once per pixel.
+struct LbYuyv {
+    const uint32_t *row;
+    int cu, cv;   // channel k's U and V coefficients
+    __device__ LbYuyv(const uint8_t *__restrict__ img, const LetterboxArgs &a, int r, int k)
+        : row(reinterpret_cast<const uint32_t *>(img + ((size_t)r * a.w) * 2)), cu(k == 0 ? 0 : (k == 1 ? -100 : 516)),
+          cv(k == 0 ? 409 : (k == 1 ? -208 : 0)) {}
+    __device__ uint8_t operator()(int x) const
+    {
+        const uint32_t p = row[x >> 1];
+        const int c = (int)((p >> ((x & 1) * 16)) & 255u) - 16, d = (int)((p >> 8) & 255u) - 128, e = (int)(p >> 24) - 128;
+        return (uint8_t)min(max((298 * c + cu * d + cv * e + 128) >> 8, 0), 255);
+    }
+};
+
 // kernels_pre.hpp's lb_part: the horizontally interpolated value part(c, r, k) of resize_image's first pass
-template <class Q = LbDiv255>
+template <class Q = LbDiv255, class F = LbInterleaved>
 __device__ inline float lb_part_q(const uint8_t *__restrict__ img, const LetterboxArgs &a, int c, int r, int k, Q q = Q())
 {
-    const int kk = a.ch == 3 ? k : 0;
-    const uint8_t *row = img + ((size_t)r * a.w) * a.ch + kk;
-    if (c == a.new_w - 1 || a.w == 1) return q(row[(size_t)(a.w - 1) * a.ch]);
-    const float sx = __fmul_rn((float)c, a.w_scale);
-    const int ix = (int)sx;
-    const float dx = __fsub_rn(sx, (float)ix);
-    const float p0 = q(row[(size_t)min(ix, a.w - 1) * a.ch]);
-    const float p1 = q(row[(size_t)min(ix + 1, a.w - 1) * a.ch]);   // (clamp: memory safety only)
-    return __fadd_rn(__fmul_rn(__fsub_rn(1.f, dx), p0), __fmul_rn(dx, p1));
+    if constexpr (std::is_same<F, LbYuyv>::value) {   // the same operations on the converted bytes
+        const LbYuyv px(img, a, r, k);
+        if (c == a.new_w - 1 || a.w == 1) return q(px(a.w - 1));
+        const float sx = __fmul_rn((float)c, a.w_scale);
+        const int ix = (int)sx;
+        const float dx = __fsub_rn(sx, (float)ix);
+        const float p0 = q(px(min(ix, a.w - 1)));
+        const float p1 = q(px(min(ix + 1, a.w - 1)));
+        return __fadd_rn(__fmul_rn(__fsub_rn(1.f, dx), p0), __fmul_rn(dx, p1));
+    } else {
+        const int kk = a.ch == 3 ? k : 0;
+        const uint8_t *row = img + ((size_t)r * a.w) * a.ch + kk;
+        if (c == a.new_w - 1 || a.w == 1) return q(row[(size_t)(a.w - 1) * a.ch]);
+        const float sx = __fmul_rn((float)c, a.w_scale);
+        const int ix = (int)sx;
+        const float dx = __fsub_rn(sx, (float)ix);
+        const float p0 = q(row[(size_t)min(ix, a.w - 1) * a.ch]);
+        const float p1 = q(row[(size_t)min(ix + 1, a.w - 1) * a.ch]);   // (clamp: memory safety only)
+        return __fadd_rn(__fmul_rn(__fsub_rn(1.f, dx), p0), __fmul_rn(dx, p1));
+    }
 }
 
 // kernels_pre.hpp's lb_value for canvas element (k, y, x): 0.5 outside the fitted image, resize_image's second pass inside it
-template <class Q = LbDiv255>
+template <class Q = LbDiv255, class F = LbInterleaved>
 __device__ inline float lb_value_at(const uint8_t *__restrict__ img, const LetterboxArgs &a, int k, int y, int x, Q q = Q())
 {
     const int c = x - a.off_x, r = y - a.off_y;
@@ -53,16 +93,18 @@ __device__ inline float lb_value_at(const uint8_t *__restrict__ img, const Lette
         const float sy = __fmul_rn((float)r, a.h_scale);
         const int iy = (int)sy;
         const float dy = __fsub_rn(sy, (float)iy);
-        v = __fmul_rn(__fsub_rn(1.f, dy), lb_part_q(img, a, c, min(iy, a.h - 1), k, q));
-        if (!(r == a.new_h - 1 || a.h == 1)) v = __fadd_rn(v, __fmul_rn(dy, lb_part_q(img, a, c, min(iy + 1, a.h - 1), k, q)));
+        v = __fmul_rn(__fsub_rn(1.f, dy), lb_part_q<Q, F>(img, a, c, min(iy, a.h - 1), k, q));
+        if (!(r == a.new_h - 1 || a.h == 1)) v = __fadd_rn(v, __fmul_rn(dy, lb_part_q<Q, F>(img, a, c, min(iy + 1, a.h - 1), k, q)));
     }
     return v;
 }
 
 // one frame of a chunk's staging buffer: where the image's bytes start (relative to the buffer) and its geometry
+#ifndef Y2_LETTERBOX_STRUCTS_FROM_PRE
 struct LetterboxItem {
     unsigned long long off;
     LetterboxArgs a;
 };
+#endif
 
 }  // namespace y2

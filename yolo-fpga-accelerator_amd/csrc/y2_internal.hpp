@@ -316,10 +316,11 @@ void y2_f16_plan_free(yolo2_hip_ctx *c);
 // (split 1, made here) - or YOLO2_ERROR without fp32 weights.  y2_f16_images_fused: that pass has the layer-0 step from bytes (not under
 // f16_no_mfma0: the entries then letterbox into frames and run the frame path).  y2_f16_run_images: the pass on a chunk of `batch`
 // frames whose staging buffer (LetterboxItem table + images) is at lb, enqueued on st; y2_f16_images_kernel names its layer-0 kernel.
+// yuyv: the chunk's images are packed YUYV 4:2:2 frames (table items with ch == 2) instead of interleaved bytes.
 int y2_f16_images_ctx(yolo2_hip_ctx *c, int split, yolo2_hip_ctx **run);
 bool y2_f16_images_fused(const yolo2_hip_ctx *run);
-int y2_f16_run_images(yolo2_hip_ctx *run, const uint8_t *lb, int batch, float *region_dev, hipStream_t st);
-const char *y2_f16_images_kernel(const yolo2_hip_ctx *run);
+int y2_f16_run_images(yolo2_hip_ctx *run, const uint8_t *lb, bool yuyv, int batch, float *region_dev, hipStream_t st);
+const char *y2_f16_images_kernel(const yolo2_hip_ctx *run, bool yuyv);
 
 // The per-layer driver calls' device work (yolo2_driver.hip validates, latches the register file, takes the lock, binds the
 // device, and synchronises with the reference's timeout semantics afterwards; these only enqueue on the null stream).

@@ -82,8 +82,10 @@ struct F16Plan {
     std::vector<F16Step> steps;
     // the images entries' layer-0 step "from bytes" (layers 0+1 from a chunk's staging buffer), used instead of steps[0]; every
     // other step is the table's.  Not set (launch_u8 == nullptr) under f16_no_mfma0: those entries letterbox into frames first.
+    // launch_yuyv / yuyv_kernel: the same step "from YUYV bytes" (a chunk of packed YUYV 4:2:2 frames: k_conv0_pool_mfma_yuyv).
     F16Step u8;
-    F16LaunchU8 launch_u8 = nullptr;
+    F16LaunchU8 launch_u8 = nullptr, launch_yuyv = nullptr;
+    const char *yuyv_kernel = "";
 };
 
 void y2_f16_plan_free(yolo2_hip_ctx *c)
@@ -312,6 +314,11 @@ static void L_conv0_mfma_u8(const F16Step &s, const uint8_t *lb, int lb_first, h
 {
     hipLaunchKernelGGL(k_conv0_pool_mfma_u8<SP>, s.grid, s.block, 0, st, lb, lb_first, s.w0, s.bias, s.out, s.oWp, s.oPL, s.T);
 }
+template <bool SP>
+static void L_conv0_mfma_yuyv(const F16Step &s, const uint8_t *lb, int lb_first, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_conv0_pool_mfma_yuyv<SP>, s.grid, s.block, 0, st, lb, lb_first, s.w0, s.bias, s.out, s.oWp, s.oPL, s.T);
+}
 template <bool SP> Y2_LAUNCHER(L_conv0_valu, hipLaunchKernelGGL(k_conv0_pool_f16<SP>, s.grid, s.block, 0, st, frames, s.w0, s.bias, s.out, s.B, 416, 416, s.oWp, s.oPL))
 template <int BN> Y2_LAUNCHER(L_ring, hipLaunchKernelGGL((k_gemm1_f16_p<256, BN, 3>), s.grid, s.block, s.lds, st, s.in, s.w, s.bias, s.out,
                                                             s.store == FS_REGION ? region : (float *)nullptr, s.a, s.T))
@@ -344,7 +351,7 @@ static int build_f16_plan(yolo2_hip_ctx *c, int B)
     const F16Switches &sw = P.sw;
     P.steps.clear();
     P.batch = 0;
-    P.launch_u8 = nullptr;
+    P.launch_u8 = P.launch_yuyv = nullptr;
     typedef yolo2_hip_ctx::HalfTensor HT;
     const bool split = c->split;     // "fp32tol" mode: items of three parts [hi | lo | hi], SPLIT kernel instantiations
     auto checked_push = [&](F16Step &s, const HT &dst) -> int {
@@ -381,6 +388,8 @@ static int build_f16_plan(yolo2_hip_ctx *c, int B)
             P.u8 = s;
             P.u8.kernel = split ? "k_conv0_pool_mfma_u8<split>" : "k_conv0_pool_mfma_u8";
             P.launch_u8 = split ? L_conv0_mfma_u8<true> : L_conv0_mfma_u8<false>;
+            P.yuyv_kernel = split ? "k_conv0_pool_mfma_yuyv<split>" : "k_conv0_pool_mfma_yuyv";
+            P.launch_yuyv = split ? L_conv0_mfma_yuyv<true> : L_conv0_mfma_yuyv<false>;
         }
     }
     int ord = 1, skip_pool = -1, fused_conv = -1;
@@ -752,8 +761,10 @@ static int make_f16_lanes(yolo2_hip_ctx *c, int want_lanes)
 }
 
 // The pass.  lb == nullptr: layer 0 reads the float frames at frames_dev (the table as it is).  lb != nullptr (the images entries):
-// layer 0 reads frames lb_first .. lb_first + batch - 1 of the chunk staging buffer lb through the table's step "from bytes".
-static int run_f16(yolo2_hip_ctx *c, uint64_t frames_dev, const uint8_t *lb, int lb_first, int batch, uint64_t region_dev, void *stream)
+// layer 0 reads frames lb_first .. lb_first + batch - 1 of the chunk staging buffer lb through the table's step "from bytes", or,
+// for a chunk of YUYV frames (yuyv), "from YUYV bytes".
+static int run_f16(yolo2_hip_ctx *c, uint64_t frames_dev, const uint8_t *lb, int lb_first, bool yuyv, int batch, uint64_t region_dev,
+                   void *stream)
 {
     if (!c) return fail(YOLO2_ERROR, "null ctx");
     if (!c->f16_loaded || !c->f16_plan) return fail(YOLO2_ERROR, "fp32 weights not loaded (yolo2_hip_load_weights_fp32)");
@@ -777,7 +788,7 @@ static int run_f16(yolo2_hip_ctx *c, uint64_t frames_dev, const uint8_t *lb, int
             yolo2_hip_ctx *l = c->f16_lanes[i];
             hipStream_t ls = l->lane_stream ? l->lane_stream : st;
             if (l->lane_stream) HIP_TRY(hipStreamWaitEvent(ls, c->ev_fork, 0), YOLO2_ERROR);
-            const int rc = run_f16(l, lb ? 0 : frames_dev + (uint64_t)i * half * YOLO2_FRAME_ELEMS * sizeof(float), lb, lb_first + i * half, half,
+            const int rc = run_f16(l, lb ? 0 : frames_dev + (uint64_t)i * half * YOLO2_FRAME_ELEMS * sizeof(float), lb, lb_first + i * half, yuyv, half,
                                    region_dev + (uint64_t)i * half * YOLO2_REGION_ELEMS * sizeof(float), ls);
             if (rc) return rc;
             if (l->lane_stream) HIP_TRY(hipEventRecord(l->ev_join, ls), YOLO2_ERROR);
@@ -799,10 +810,11 @@ static int run_f16(yolo2_hip_ctx *c, uint64_t frames_dev, const uint8_t *lb, int
     int next_ev = 0;
     const F16Plan &P = *c->f16_plan;
     if (lb && !P.launch_u8) return fail(YOLO2_ERROR, "fp16 plan has no layer-0 step from bytes");
+    const F16LaunchU8 from_bytes = yuyv ? P.launch_yuyv : P.launch_u8;
     for (const F16Step &s : P.steps) {
         if (ev) for (; next_ev <= s.layer; ++next_ev) (void)hipEventRecord(ev[next_ev], st);   // layers without a launch of their own
         if (lb && s.layer == 0)
-            P.launch_u8(P.u8, lb, lb_first, st);
+            from_bytes(P.u8, lb, lb_first, st);
         else
             s.launch(s, frames, region, st);
         if (ev) { (void)hipEventRecord(ev[s.layer + 1], st); next_ev = s.layer + 2; }
@@ -815,7 +827,7 @@ static int run_f16(yolo2_hip_ctx *c, uint64_t frames_dev, const uint8_t *lb, int
 
 extern "C" int yolo2_hip_run_batch_fp16(yolo2_hip_ctx *c, uint64_t frames_dev, int batch, uint64_t region_dev, void *stream)
 {
-    return run_f16(c, frames_dev, nullptr, 0, batch, region_dev, stream);
+    return run_f16(c, frames_dev, nullptr, 0, false, batch, region_dev, stream);
 }
 
 // ---------------------------------------------------------------------------- split-fp16: the MFMA path inside the fp32 tolerance
@@ -976,14 +988,15 @@ int y2_f16_images_ctx(yolo2_hip_ctx *c, int split, yolo2_hip_ctx **run)
 
 bool y2_f16_images_fused(const yolo2_hip_ctx *run) { return !run->f16_plan->sw.no_mfma0; }
 
-int y2_f16_run_images(yolo2_hip_ctx *run, const uint8_t *lb, int batch, float *region_dev, hipStream_t st)
+int y2_f16_run_images(yolo2_hip_ctx *run, const uint8_t *lb, bool yuyv, int batch, float *region_dev, hipStream_t st)
 {
     if (!lb) return fail(YOLO2_ERROR, "null buffer address");
-    return run_f16(run, 0, lb, 0, batch, (uint64_t)(uintptr_t)region_dev, st);
+    return run_f16(run, 0, lb, 0, yuyv, batch, (uint64_t)(uintptr_t)region_dev, st);
 }
 
-const char *y2_f16_images_kernel(const yolo2_hip_ctx *run)
+const char *y2_f16_images_kernel(const yolo2_hip_ctx *run, bool yuyv)
 {
     if (!run->f16_lanes.empty() && run->f16_last_laned) run = run->f16_lanes[0];
-    return run->f16_plan && run->f16_plan->launch_u8 ? run->f16_plan->u8.kernel : "";
+    if (!run->f16_plan || !run->f16_plan->launch_u8) return "";
+    return yuyv ? run->f16_plan->yuyv_kernel : run->f16_plan->u8.kernel;
 }

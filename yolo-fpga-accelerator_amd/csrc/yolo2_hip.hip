@@ -13,6 +13,7 @@
 
 #include "y2_internal.hpp"
 #include "kernels_pre.hpp"
+#include "kernels_pix.hpp"   // after kernels_pre.hpp: uses its structs
 
 using namespace y2;
 
@@ -369,10 +370,13 @@ extern "C" int yolo2_hip_layer_times_ms(yolo2_hip_ctx *c, float *ms32)
 
 // ---------------------------------------------------------------------------- pre-processing
 
-static int letterbox_args(int w, int h, int channels, int net_w, int net_h, LetterboxArgs &a)
+// channels: bytes per pixel = LetterboxArgs::ch.  1 and 3 are interleaved byte channels; 2 marks a packed YUYV 4:2:2 frame and is
+// accepted from the _pix entries only (yuyv_ok): on the u8 entries, whose callers pass a channel count, it stays an error.
+static int letterbox_args(int w, int h, int channels, int net_w, int net_h, LetterboxArgs &a, bool yuyv_ok = false)
 {
-    if (w <= 0 || h <= 0 || net_w <= 1 || net_h <= 1 || (channels != 1 && channels != 3))
+    if (w <= 0 || h <= 0 || net_w <= 1 || net_h <= 1 || (channels != 1 && channels != 3 && !(channels == 2 && yuyv_ok)))
         return fail(YOLO2_ERROR, "letterbox: bad image geometry %dx%dx%d -> %dx%d", w, h, channels, net_w, net_h);
+    if (channels == 2 && (w & 1)) return fail(YOLO2_ERROR, "letterbox: YUYV frames have an even width, not %d", w);
     if ((long)w * h > (1L << 28)) return fail(YOLO2_ERROR, "letterbox: image too large");
     a.w = w; a.h = h; a.ch = channels; a.net_w = net_w; a.net_h = net_h;
     // letterbox_image, src/core/yolo_image.cpp:148-165
@@ -401,13 +405,48 @@ extern "C" int yolo2_hip_letterbox_u8(uint64_t image_dev, int w, int h, int chan
     return YOLO2_SUCCESS;
 }
 
+// pixfmt -> bytes per pixel (LetterboxArgs::ch) for the _pix entries; 0 and an error for anything else
+static int pix_channels(int pixfmt)
+{
+    if (pixfmt == YOLO2_PIX_GREY8) return 1;
+    if (pixfmt == YOLO2_PIX_RGB24) return 3;
+    if (pixfmt == YOLO2_PIX_YUYV) return 2;
+    (void)fail(YOLO2_ERROR, "unknown pixel format 0x%x (YOLO2_PIX_GREY8, YOLO2_PIX_RGB24 or YOLO2_PIX_YUYV)", (unsigned)pixfmt);
+    return 0;
+}
+
+extern "C" int yolo2_hip_letterbox_pix(uint64_t image_dev, int w, int h, int pixfmt, uint64_t frame_dev, int net_w, int net_h,
+                                       void *stream)
+{
+    const int ch = pix_channels(pixfmt);
+    if (!ch) return YOLO2_ERROR;
+    if (ch != 2) return yolo2_hip_letterbox_u8(image_dev, w, h, ch, frame_dev, net_w, net_h, stream);
+    if (!image_dev || !frame_dev) return fail(YOLO2_ERROR, "null buffer address");
+    if (image_dev & 3) return fail(YOLO2_ERROR, "letterbox: a YUYV frame starts on a 4-byte boundary");   // (LbYuyv loads pixel pairs)
+    LetterboxArgs a;
+    int rc = letterbox_args(w, h, ch, net_w, net_h, a, true);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_letterbox_yuyv, dim3(blocks_for((long)3 * net_w * net_h, 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const uint8_t *)(uintptr_t)image_dev, (float *)(uintptr_t)frame_dev, a);
+    HIP_TRY(hipGetLastError(), YOLO2_ERROR);
+    return YOLO2_SUCCESS;
+}
+
+// the chunk letterbox of either kind of staging buffer (pix: YUYV frames, table items with ch == 2)
+static void launch_letterbox_batch(bool yuyv, const uint8_t *dbytes, float *din, int batch, hipStream_t st)
+{
+    const dim3 grid(blocks_for((long)YOLO2_FRAME_ELEMS, 256), batch);
+    if (yuyv) hipLaunchKernelGGL(k_letterbox_yuyv_batch, grid, dim3(256), 0, st, dbytes, din, (int)YOLO2_FRAME_ELEMS);
+    else hipLaunchKernelGGL(k_letterbox_u8_batch, grid, dim3(256), 0, st, dbytes, din, (int)YOLO2_FRAME_ELEMS);   // the whole chunk in one launch
+}
+
 // Camera-style entry: n images of arbitrary sizes as host bytes -> region tensors, in chunks of
 // `batch` images.  The bytes (not the 4x larger float frames) cross PCIe; letterboxing runs on the
 // GPU into the chunk's frame buffer.  Same three-stream pipeline as yolo2_hip_run_frames_int16:
 // upload of chunk k+1 (CPU staging copy + DMA) overlaps the kernels of chunk k and the download of k-1.
-extern "C" int yolo2_hip_run_images_u8_host(yolo2_hip_ctx *c, const uint8_t *const *images, const int *widths,
-                                            const int *heights, int channels, int n, int batch, int16_t *region,
-                                            int *final_q)
+// (channels: bytes per pixel; pix: called from the _pix entry, where 2 = YUYV is a format)
+static int run_images_i16_host(yolo2_hip_ctx *c, const uint8_t *const *images, const int *widths, const int *heights, int channels, bool pix,
+                               int n, int batch, int16_t *region, int *final_q)
 {
     if (!c || !images || !widths || !heights || !region) return fail(YOLO2_ERROR, "null argument");
     if (n <= 0 || batch <= 0) return fail(YOLO2_ERROR, "bad image count %d / batch %d", n, batch);
@@ -424,7 +463,7 @@ extern "C" int yolo2_hip_run_images_u8_host(yolo2_hip_ctx *c, const uint8_t *con
         for (int i = k * batch; i < k * batch + in_chunk(k); ++i) {
             LetterboxArgs a;
             if (!images[i]) return fail(YOLO2_ERROR, "null image %d", i);
-            const int rc = letterbox_args(widths[i], heights[i], channels, 416, 416, a);
+            const int rc = letterbox_args(widths[i], heights[i], channels, 416, 416, a, pix);
             if (rc) return rc;
             sum += padded((size_t)widths[i] * heights[i] * channels);
         }
@@ -467,14 +506,13 @@ extern "C" int yolo2_hip_run_images_u8_host(yolo2_hip_ctx *c, const uint8_t *con
         for (int f = 0; f < batch && rc == YOLO2_SUCCESS; ++f) {   // a partial last chunk repeats its last image
             const int i = std::min(f, nf - 1);
             items[f].off = offs[(size_t)i];
-            rc = letterbox_args(widths[first + i], heights[first + i], channels, 416, 416, items[f].a);
+            rc = letterbox_args(widths[first + i], heights[first + i], channels, 416, 416, items[f].a, pix);
         }
         if (rc) break;
         Y2_TRY(hipMemcpyAsync(dbytes[b], hin[b], off, hipMemcpyHostToDevice, s_in), YOLO2_DMA_ERROR);
         Y2_TRY(hipEventRecord(e_in[b], s_in), YOLO2_ERROR);
         Y2_TRY(hipStreamWaitEvent(s_run, e_in[b], 0), YOLO2_ERROR);
-        hipLaunchKernelGGL(k_letterbox_u8_batch, dim3(blocks_for((long)YOLO2_FRAME_ELEMS, 256), batch), dim3(256), 0, s_run, dbytes[b], din[b],
-                           (int)YOLO2_FRAME_ELEMS);   // the whole chunk in one launch
+        launch_letterbox_batch(channels == 2, dbytes[b], din[b], batch, s_run);
         Y2_TRY(hipGetLastError(), YOLO2_ERROR);
         rc = yolo2_hip_run_batch_int16(c, (uint64_t)(uintptr_t)din[b], batch, (uint64_t)(uintptr_t)dout[b], &q, s_run);
         if (rc) break;
@@ -490,6 +528,20 @@ extern "C" int yolo2_hip_run_images_u8_host(yolo2_hip_ctx *c, const uint8_t *con
     cleanup();
 #undef Y2_TRY
     return rc;
+}
+
+extern "C" int yolo2_hip_run_images_u8_host(yolo2_hip_ctx *c, const uint8_t *const *images, const int *widths,
+                                            const int *heights, int channels, int n, int batch, int16_t *region,
+                                            int *final_q)
+{
+    return run_images_i16_host(c, images, widths, heights, channels, false, n, batch, region, final_q);
+}
+
+extern "C" int yolo2_hip_run_images_pix_host(yolo2_hip_ctx *c, const uint8_t *const *images, const int *widths, const int *heights,
+                                             int pixfmt, int n, int batch, int16_t *region, int *final_q)
+{
+    const int ch = pix_channels(pixfmt);
+    return ch ? run_images_i16_host(c, images, widths, heights, ch, true, n, batch, region, final_q) : YOLO2_ERROR;
 }
 
 // ---------------------------------------------------------------------------- streaming host entry
@@ -525,9 +577,9 @@ static int pipe_ensure_post(yolo2_hip_ctx *c, int batch, int cap)
     return YOLO2_SUCCESS;
 }
 
-extern "C" int yolo2_hip_run_images_u8_dets(yolo2_hip_ctx *c, const uint8_t *const *images, const int *widths, const int *heights,
-                                            int channels, int n, int batch, float thresh, float nms, int flags, yolo2_hip_det *dets,
-                                            int cap_per_frame, int *counts, int *final_q)
+static int run_images_i16_dets(yolo2_hip_ctx *c, const uint8_t *const *images, const int *widths, const int *heights, int channels, bool pix,
+                               int n, int batch, float thresh, float nms, int flags, yolo2_hip_det *dets, int cap_per_frame, int *counts,
+                               int *final_q)
 {
     if (!c || !images || !widths || !heights || !dets || !counts) return fail(YOLO2_ERROR, "null argument");
     if (n <= 0 || batch <= 0 || cap_per_frame <= 0) return fail(YOLO2_ERROR, "bad image count %d / batch %d / capacity %d", n, batch, cap_per_frame);
@@ -545,7 +597,7 @@ extern "C" int yolo2_hip_run_images_u8_dets(yolo2_hip_ctx *c, const uint8_t *con
         for (int i = k * batch; i < k * batch + in_chunk(k); ++i) {
             LetterboxArgs a;
             if (!images[i]) return fail(YOLO2_ERROR, "null image %d", i);
-            const int rc = letterbox_args(widths[i], heights[i], channels, 416, 416, a);
+            const int rc = letterbox_args(widths[i], heights[i], channels, 416, 416, a, pix);
             if (rc) return rc;
             sum += padded((size_t)widths[i] * heights[i] * channels);
         }
@@ -591,7 +643,7 @@ extern "C" int yolo2_hip_run_images_u8_dets(yolo2_hip_ctx *c, const uint8_t *con
             const int i = std::min(f, nf - 1);
             cw[(size_t)f] = widths[first + i]; chh[(size_t)f] = heights[first + i];
             items[f].off = offs[(size_t)i];
-            if ((rc = letterbox_args(widths[first + i], heights[first + i], channels, 416, 416, items[f].a))) break;
+            if ((rc = letterbox_args(widths[first + i], heights[first + i], channels, 416, 416, items[f].a, pix))) break;
         }
         if (rc) break;
         if ((rc = y2_post_fill_geom(P.hgeom[b], cw.data(), chh.data(), batch))) break;
@@ -599,8 +651,7 @@ extern "C" int yolo2_hip_run_images_u8_dets(yolo2_hip_ctx *c, const uint8_t *con
         Y2_TRY(hipMemcpyAsync(P.post[b].geom, P.hgeom[b], (size_t)batch * gbytes, hipMemcpyHostToDevice, P.s_in), YOLO2_DMA_ERROR);
         Y2_TRY(hipEventRecord(P.e_in[b], P.s_in), YOLO2_ERROR);
         Y2_TRY(hipStreamWaitEvent(P.s_run, P.e_in[b], 0), YOLO2_ERROR);
-        hipLaunchKernelGGL(k_letterbox_u8_batch, dim3(blocks_for((long)YOLO2_FRAME_ELEMS, 256), batch), dim3(256), 0, P.s_run, P.dbytes[b], P.din[b],
-                           (int)YOLO2_FRAME_ELEMS);
+        launch_letterbox_batch(channels == 2, P.dbytes[b], P.din[b], batch, P.s_run);
         Y2_TRY(hipGetLastError(), YOLO2_ERROR);
         // The network.  A chunk's lanes are NOT joined back into one stream here: consecutive chunks are independent, every lane
         // owns its activations and its stream keeps its chunks in order, so lane i starts chunk k + 1 the moment it has finished
@@ -644,6 +695,22 @@ extern "C" int yolo2_hip_run_images_u8_dets(yolo2_hip_ctx *c, const uint8_t *con
     cleanup();
 #undef Y2_TRY
     return rc;
+}
+
+extern "C" int yolo2_hip_run_images_u8_dets(yolo2_hip_ctx *c, const uint8_t *const *images, const int *widths, const int *heights,
+                                            int channels, int n, int batch, float thresh, float nms, int flags, yolo2_hip_det *dets,
+                                            int cap_per_frame, int *counts, int *final_q)
+{
+    return run_images_i16_dets(c, images, widths, heights, channels, false, n, batch, thresh, nms, flags, dets, cap_per_frame, counts, final_q);
+}
+
+extern "C" int yolo2_hip_run_images_pix_dets(yolo2_hip_ctx *c, const uint8_t *const *images, const int *widths, const int *heights,
+                                             int pixfmt, int n, int batch, float thresh, float nms, int flags, yolo2_hip_det *dets,
+                                             int cap_per_frame, int *counts, int *final_q)
+{
+    const int ch = pix_channels(pixfmt);
+    return ch ? run_images_i16_dets(c, images, widths, heights, ch, true, n, batch, thresh, nms, flags, dets, cap_per_frame, counts, final_q)
+              : YOLO2_ERROR;
 }
 
 // ---------------------------------------------------------------------------- the fp16 / split-fp16 images entries
@@ -701,10 +768,10 @@ static void stage_images(uint8_t *dst, const uint8_t *const *images, const size_
 
 // dets == nullptr: region tensors to region_host; otherwise the records (the int16 dets entry's contract)
 static int run_images_f16(yolo2_hip_ctx *c, int split, const uint8_t *const *images, const int *widths, const int *heights, int channels,
-                          int n, int batch, float *region_host, float thresh, float nms, int flags, yolo2_hip_det *dets, int cap,
+                          bool pix, int n, int batch, float *region_host, float thresh, float nms, int flags, yolo2_hip_det *dets, int cap,
                           int *counts)
 {
-    const bool want_dets = dets != nullptr;
+    const bool want_dets = dets != nullptr, yuyv = channels == 2;
     if (n <= 0 || batch <= 0 || (want_dets && cap <= 0))
         return fail(YOLO2_ERROR, "bad image count %d / batch %d / capacity %d", n, batch, want_dets ? cap : 1);
     if (want_dets && thresh < 0.f) return fail(YOLO2_ERROR, "negative threshold");
@@ -723,7 +790,7 @@ static int run_images_f16(yolo2_hip_ctx *c, int split, const uint8_t *const *ima
         for (int i = k * batch; i < k * batch + in_chunk(k); ++i) {
             LetterboxArgs a;
             if (!images[i]) return fail(YOLO2_ERROR, "null image %d", i);
-            if ((rc = letterbox_args(widths[i], heights[i], channels, 416, 416, a))) return rc;
+            if ((rc = letterbox_args(widths[i], heights[i], channels, 416, 416, a, pix))) return rc;
             sum += padded((size_t)widths[i] * heights[i] * channels);
         }
         cap_bytes = std::max(cap_bytes, sum);
@@ -768,7 +835,7 @@ static int run_images_f16(yolo2_hip_ctx *c, int split, const uint8_t *const *ima
             const int i = std::min(f, nf - 1);
             cw[(size_t)f] = widths[first + i]; chh[(size_t)f] = heights[first + i];
             items[f].off = offs[(size_t)i];
-            if ((rc = letterbox_args(widths[first + i], heights[first + i], channels, 416, 416, items[f].a))) break;
+            if ((rc = letterbox_args(widths[first + i], heights[first + i], channels, 416, 416, items[f].a, pix))) break;
         }
         if (rc) break;
         if (want_dets && (rc = y2_post_fill_geom(P.hgeom[b], cw.data(), chh.data(), batch))) break;
@@ -777,10 +844,9 @@ static int run_images_f16(yolo2_hip_ctx *c, int split, const uint8_t *const *ima
         Y2_TRY(hipEventRecord(P.e_in[b], P.s_in), YOLO2_ERROR);
         Y2_TRY(hipStreamWaitEvent(P.s_run, P.e_in[b], 0), YOLO2_ERROR);
         if (fused) {
-            rc = y2_f16_run_images(run, P.dbytes[b], batch, P.dregf[b], P.s_run);
+            rc = y2_f16_run_images(run, P.dbytes[b], yuyv, batch, P.dregf[b], P.s_run);
         } else {
-            hipLaunchKernelGGL(k_letterbox_u8_batch, dim3(blocks_for((long)YOLO2_FRAME_ELEMS, 256), batch), dim3(256), 0, P.s_run, P.dbytes[b],
-                               P.din[b], (int)YOLO2_FRAME_ELEMS);
+            launch_letterbox_batch(yuyv, P.dbytes[b], P.din[b], batch, P.s_run);
             Y2_TRY(hipGetLastError(), YOLO2_ERROR);
             rc = yolo2_hip_run_batch_fp16(run, (uint64_t)(uintptr_t)P.din[b], batch, (uint64_t)(uintptr_t)P.dregf[b], P.s_run);
         }
@@ -799,8 +865,8 @@ static int run_images_f16(yolo2_hip_ctx *c, int split, const uint8_t *const *ima
     }
     if (rc == YOLO2_SUCCESS) {
         for (int k = std::max(0, chunks - 2); k < chunks; ++k) drain(k);
-        c->images_l0[split] = fused ? std::string(y2_f16_images_kernel(run))
-                                    : std::string("k_letterbox_u8_batch + ") + yolo2_hip_fp16_layer_kernel(run, 0);
+        c->images_l0[split] = fused ? std::string(y2_f16_images_kernel(run, yuyv))
+                                    : std::string(yuyv ? "k_letterbox_yuyv_batch + " : "k_letterbox_u8_batch + ") + yolo2_hip_fp16_layer_kernel(run, 0);
     }
     cleanup();
 #undef Y2_TRY
@@ -811,7 +877,15 @@ extern "C" int yolo2_hip_run_images_u8_f16_host(yolo2_hip_ctx *c, int split, con
                                                 const int *heights, int channels, int n, int batch, float *region_host)
 {
     if (!c || !images || !widths || !heights || !region_host) return fail(YOLO2_ERROR, "null argument");
-    return run_images_f16(c, split, images, widths, heights, channels, n, batch, region_host, 0.f, 0.f, 0, nullptr, 0, nullptr);
+    return run_images_f16(c, split, images, widths, heights, channels, false, n, batch, region_host, 0.f, 0.f, 0, nullptr, 0, nullptr);
+}
+
+extern "C" int yolo2_hip_run_images_pix_f16_host(yolo2_hip_ctx *c, int split, const uint8_t *const *images, const int *widths,
+                                                 const int *heights, int pixfmt, int n, int batch, float *region_host)
+{
+    if (!c || !images || !widths || !heights || !region_host) return fail(YOLO2_ERROR, "null argument");
+    const int ch = pix_channels(pixfmt);
+    return ch ? run_images_f16(c, split, images, widths, heights, ch, true, n, batch, region_host, 0.f, 0.f, 0, nullptr, 0, nullptr) : YOLO2_ERROR;
 }
 
 extern "C" int yolo2_hip_run_images_u8_dets_f16(yolo2_hip_ctx *c, int split, const uint8_t *const *images, const int *widths,
@@ -819,7 +893,17 @@ extern "C" int yolo2_hip_run_images_u8_dets_f16(yolo2_hip_ctx *c, int split, con
                                                 yolo2_hip_det *dets, int cap_per_frame, int *counts)
 {
     if (!c || !images || !widths || !heights || !dets || !counts) return fail(YOLO2_ERROR, "null argument");
-    return run_images_f16(c, split, images, widths, heights, channels, n, batch, nullptr, thresh, nms, flags, dets, cap_per_frame, counts);
+    return run_images_f16(c, split, images, widths, heights, channels, false, n, batch, nullptr, thresh, nms, flags, dets, cap_per_frame, counts);
+}
+
+extern "C" int yolo2_hip_run_images_pix_dets_f16(yolo2_hip_ctx *c, int split, const uint8_t *const *images, const int *widths,
+                                                 const int *heights, int pixfmt, int n, int batch, float thresh, float nms, int flags,
+                                                 yolo2_hip_det *dets, int cap_per_frame, int *counts)
+{
+    if (!c || !images || !widths || !heights || !dets || !counts) return fail(YOLO2_ERROR, "null argument");
+    const int ch = pix_channels(pixfmt);
+    return ch ? run_images_f16(c, split, images, widths, heights, ch, true, n, batch, nullptr, thresh, nms, flags, dets, cap_per_frame, counts)
+              : YOLO2_ERROR;
 }
 
 extern "C" const char *yolo2_hip_images_layer0_kernel(yolo2_hip_ctx *c, int split)

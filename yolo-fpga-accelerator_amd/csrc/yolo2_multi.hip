@@ -568,15 +568,16 @@ extern "C" int yolo2_hip_multi_run_frames_int16(yolo2_hip_multi *m, const float 
     return rc;
 }
 
-extern "C" int yolo2_hip_multi_run_images_u8_host(yolo2_hip_multi *m, const uint8_t *const *images, const int *widths, const int *heights,
-                                                  int channels, int n, int batch_per_device, int16_t *region, int *final_q)
+// The images entries, u8 (`fmt` = channels) and pix (`fmt` = pixfmt) alike: `run` is the single-device entry every shard goes through.
+static int multi_images_host(decltype(&yolo2_hip_run_images_u8_host) run, yolo2_hip_multi *m, const uint8_t *const *images, const int *widths,
+                             const int *heights, int fmt, int n, int batch_per_device, int16_t *region, int *final_q)
 {
     if (!m || !images || !widths || !heights || !region) return mfail(YOLO2_ERROR, "null argument");
     if (n <= 0 || batch_per_device <= 0) return mfail(YOLO2_ERROR, "bad image count / batch");
     std::vector<int> q(m->ctx.size(), 0);
     const int rc = multi_run(m, n, [&](yolo2_hip_ctx *c, int lo, int hi) {
         int qq = 0;
-        const int r = yolo2_hip_run_images_u8_host(c, images + lo, widths + lo, heights + lo, channels, hi - lo, std::min(batch_per_device, hi - lo),
+        const int r = run(c, images + lo, widths + lo, heights + lo, fmt, hi - lo, std::min(batch_per_device, hi - lo),
                                                    region + (size_t)lo * YOLO2_REGION_ELEMS, &qq);
         for (size_t i = 0; i < m->ctx.size(); ++i)
             if (m->ctx[i] == c) q[i] = qq;
@@ -586,9 +587,21 @@ extern "C" int yolo2_hip_multi_run_images_u8_host(yolo2_hip_multi *m, const uint
     return rc;
 }
 
-extern "C" int yolo2_hip_multi_run_images_u8_dets(yolo2_hip_multi *m, const uint8_t *const *images, const int *widths, const int *heights,
-                                                  int channels, int n, int batch_per_device, float thresh, float nms, int flags,
-                                                  yolo2_hip_det *dets, int cap_per_frame, int *counts, int *final_q)
+extern "C" int yolo2_hip_multi_run_images_u8_host(yolo2_hip_multi *m, const uint8_t *const *images, const int *widths, const int *heights,
+                                                  int channels, int n, int batch_per_device, int16_t *region, int *final_q)
+{
+    return multi_images_host(yolo2_hip_run_images_u8_host, m, images, widths, heights, channels, n, batch_per_device, region, final_q);
+}
+
+extern "C" int yolo2_hip_multi_run_images_pix_host(yolo2_hip_multi *m, const uint8_t *const *images, const int *widths, const int *heights,
+                                                   int pixfmt, int n, int batch_per_device, int16_t *region, int *final_q)
+{
+    return multi_images_host(yolo2_hip_run_images_pix_host, m, images, widths, heights, pixfmt, n, batch_per_device, region, final_q);
+}
+
+static int multi_images_dets(decltype(&yolo2_hip_run_images_u8_dets) run, yolo2_hip_multi *m, const uint8_t *const *images, const int *widths,
+                             const int *heights, int fmt, int n, int batch_per_device, float thresh, float nms, int flags,
+                             yolo2_hip_det *dets, int cap_per_frame, int *counts, int *final_q)
 {
     if (!m || !images || !widths || !heights || !dets || !counts) return mfail(YOLO2_ERROR, "null argument");
     if (n <= 0 || batch_per_device <= 0 || cap_per_frame <= 0) return mfail(YOLO2_ERROR, "bad image count / batch / capacity");
@@ -596,7 +609,7 @@ extern "C" int yolo2_hip_multi_run_images_u8_dets(yolo2_hip_multi *m, const uint
     const int rc = multi_run(m, n, [&](yolo2_hip_ctx *c, int lo, int hi) {
         int qq = 0;
         // shard [lo, hi): its own device runs the network AND the tail; records are renumbered to global frame indices below
-        const int r = yolo2_hip_run_images_u8_dets(c, images + lo, widths + lo, heights + lo, channels, hi - lo, std::min(batch_per_device, hi - lo),
+        const int r = run(c, images + lo, widths + lo, heights + lo, fmt, hi - lo, std::min(batch_per_device, hi - lo),
                                                    thresh, nms, flags, dets + (size_t)lo * cap_per_frame, cap_per_frame, counts + lo, &qq);
         if (r == YOLO2_SUCCESS)
             for (int f = lo; f < hi; ++f)
@@ -609,15 +622,30 @@ extern "C" int yolo2_hip_multi_run_images_u8_dets(yolo2_hip_multi *m, const uint
     return rc;
 }
 
+extern "C" int yolo2_hip_multi_run_images_u8_dets(yolo2_hip_multi *m, const uint8_t *const *images, const int *widths, const int *heights,
+                                                  int channels, int n, int batch_per_device, float thresh, float nms, int flags,
+                                                  yolo2_hip_det *dets, int cap_per_frame, int *counts, int *final_q)
+{
+    return multi_images_dets(yolo2_hip_run_images_u8_dets, m, images, widths, heights, channels, n, batch_per_device, thresh, nms, flags, dets,
+                             cap_per_frame, counts, final_q);
+}
 
-extern "C" int yolo2_hip_multi_run_images_u8_dets_f16(yolo2_hip_multi *m, int split, const uint8_t *const *images, const int *widths,
-                                                      const int *heights, int channels, int n, int batch_per_device, float thresh, float nms,
-                                                      int flags, yolo2_hip_det *dets, int cap_per_frame, int *counts)
+extern "C" int yolo2_hip_multi_run_images_pix_dets(yolo2_hip_multi *m, const uint8_t *const *images, const int *widths, const int *heights,
+                                                   int pixfmt, int n, int batch_per_device, float thresh, float nms, int flags,
+                                                   yolo2_hip_det *dets, int cap_per_frame, int *counts, int *final_q)
+{
+    return multi_images_dets(yolo2_hip_run_images_pix_dets, m, images, widths, heights, pixfmt, n, batch_per_device, thresh, nms, flags, dets,
+                             cap_per_frame, counts, final_q);
+}
+
+static int multi_images_dets_f16(decltype(&yolo2_hip_run_images_u8_dets_f16) run, yolo2_hip_multi *m, int split, const uint8_t *const *images,
+                                 const int *widths, const int *heights, int fmt, int n, int batch_per_device, float thresh, float nms,
+                                 int flags, yolo2_hip_det *dets, int cap_per_frame, int *counts)
 {
     if (!m || !images || !widths || !heights || !dets || !counts) return mfail(YOLO2_ERROR, "null argument");
     if (n <= 0 || batch_per_device <= 0 || cap_per_frame <= 0) return mfail(YOLO2_ERROR, "bad image count / batch / capacity");
     return multi_run(m, n, [&](yolo2_hip_ctx *c, int lo, int hi) {
-        const int r = yolo2_hip_run_images_u8_dets_f16(c, split, images + lo, widths + lo, heights + lo, channels, hi - lo,
+        const int r = run(c, split, images + lo, widths + lo, heights + lo, fmt, hi - lo,
                                                        std::min(batch_per_device, hi - lo), thresh, nms, flags, dets + (size_t)lo * cap_per_frame,
                                                        cap_per_frame, counts + lo);
         if (r == YOLO2_SUCCESS)   // records carry global frame indices
@@ -625,4 +653,20 @@ extern "C" int yolo2_hip_multi_run_images_u8_dets_f16(yolo2_hip_multi *m, int sp
                 for (int k = 0, cnt = std::min(counts[f], cap_per_frame); k < cnt; ++k) dets[(size_t)f * cap_per_frame + k].frame = f;
         return r;
     });
+}
+
+extern "C" int yolo2_hip_multi_run_images_u8_dets_f16(yolo2_hip_multi *m, int split, const uint8_t *const *images, const int *widths,
+                                                      const int *heights, int channels, int n, int batch_per_device, float thresh, float nms,
+                                                      int flags, yolo2_hip_det *dets, int cap_per_frame, int *counts)
+{
+    return multi_images_dets_f16(yolo2_hip_run_images_u8_dets_f16, m, split, images, widths, heights, channels, n, batch_per_device, thresh, nms,
+                                 flags, dets, cap_per_frame, counts);
+}
+
+extern "C" int yolo2_hip_multi_run_images_pix_dets_f16(yolo2_hip_multi *m, int split, const uint8_t *const *images, const int *widths,
+                                                       const int *heights, int pixfmt, int n, int batch_per_device, float thresh, float nms,
+                                                       int flags, yolo2_hip_det *dets, int cap_per_frame, int *counts)
+{
+    return multi_images_dets_f16(yolo2_hip_run_images_pix_dets_f16, m, split, images, widths, heights, pixfmt, n, batch_per_device, thresh, nms,
+                                 flags, dets, cap_per_frame, counts);
 }

@@ -271,6 +271,25 @@ Image resize_image(const Image &im, int w, int h)
     return resized;
 }
 
+// yolo2_yuyv_to_rgb24, linux_app/src/yolo2_v4l2.c:328-374
+bool yuyv_to_rgb24(const uint8_t *yuyv, uint8_t *rgb, int w, int h)
+{
+    if (!yuyv || !rgb || w <= 0 || h <= 0 || (w & 1)) return false;
+    static const int kU[3] = {0, -100, 516}, kV[3] = {409, -208, 0};   // R, G, B
+    for (size_t p = 0, pairs = (size_t)w * h / 2; p < pairs; ++p) {
+        const uint8_t *s = yuyv + 4 * p;
+        const int d = s[1] - 128, e = s[3] - 128;
+        for (int half = 0; half < 2; ++half) {
+            const int luma = 298 * (s[2 * half] - 16) + 128;
+            for (int k = 0; k < 3; ++k) {
+                const int v = (luma + kU[k] * d + kV[k] * e) >> 8;   // arithmetic shift of a negative sum, as the reference's int >> 8
+                rgb[6 * p + 3 * half + k] = (uint8_t)std::min(std::max(v, 0), 255);
+            }
+        }
+    }
+    return true;
+}
+
 // letterbox_image, yolo_image.cpp:148-165
 Image letterbox_image(const Image &im, int w, int h)
 {

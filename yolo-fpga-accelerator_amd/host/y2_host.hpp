@@ -54,6 +54,11 @@ Image load_image(const std::string &path);                // load_image_stb(path
 void save_ppm(const Image &im, const std::string &path);
 Image resize_image(const Image &im, int w, int h);        // yolo_image.cpp:84-126 (two-pass bilinear)
 Image letterbox_image(const Image &im, int w, int h);     // yolo_image.cpp:148-165 (grey 0.5 bars)
+// A packed YUYV 4:2:2 camera frame (V4L2 'YUYV': bytes Y0 U Y1 V per pixel pair, 2 w bytes per row) -> RGB24 [h][w][3], the
+// conversion of the reference's camera loop (yolo2_yuyv_to_rgb24, linux_app/src/yolo2_v4l2.c:328-374): integer BT.601, arithmetic
+// shift, clamp to 0..255.  The GPU entries compute the same byte per fetched pixel (csrc/letterbox.hpp, LbYuyv).  False for an odd
+// or non-positive width / height (the reference converts pairs over the flat stream and leaves an odd frame's last pixel unwritten).
+bool yuyv_to_rgb24(const uint8_t *yuyv, uint8_t *rgb, int w, int h);
 void draw_box(Image &im, int x1, int y1, int x2, int y2, int thick, float r, float g, float b);
 
 // ---------------------------------------------------------------- weights (yolo2_model.cpp:158-227)

@@ -92,6 +92,14 @@ int y2h_load_pnm(const char *path, int *whc, float *out, long capacity)
     } catch (const std::exception &e) { g_err = e.what(); return -1; }
 }
 
+// yuyv_to_rgb24: 0, or -1 (y2h_last_error) for a null pointer, a non-positive size or an odd width
+int y2h_yuyv_to_rgb24(const uint8_t *yuyv, uint8_t *rgb, int w, int h)
+{
+    if (yuyv_to_rgb24(yuyv, rgb, w, h)) return 0;
+    g_err = "yuyv_to_rgb24: bad frame " + std::to_string(w) + "x" + std::to_string(h) + " (YUYV frames have an even width)";
+    return -1;
+}
+
 // decode_image (y2_codec.cpp): JPEG / PNG bytes -> RGB bytes [h][w][3]; returns w*h*3, or -1 (y2h_last_error) / -2 (capacity)
 long y2h_decode_image(const unsigned char *data, long n, int *w, int *h, unsigned char *rgb, long cap)
 {

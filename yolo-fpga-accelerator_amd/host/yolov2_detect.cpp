@@ -12,7 +12,7 @@
 // `--batch N` runs the same frame N times through one batched call to show the batched entry.
 //
 // Streaming frontend (the role of the reference's yolo2_linux --video/--camera loop, linux_app/src/main.c:878-1288):
-//   --input-list <file> | --input-dir <dir> | --video-raw <file|-> --video-width W --video-height H
+//   --input-list <file> | --input-dir <dir> | --video-raw <file|-> --video-width W --video-height H [--video-pix-fmt rgb24|yuyv422]
 // Frames are taken in chunks of --batch per device, go to the GPU as BYTES (letterbox on the GPU), through the
 // int16 network on --devices a,b,... (contiguous frame shards, weights broadcast once by the library) and through the
 // region + boxes + NMS tail (--post gpu: yolo2_hip_postprocess_int16; --post host: the threaded host code).  Per frame it
@@ -62,6 +62,7 @@ struct AppConfig {
     std::vector<int> devices;          // --devices a,b,...: frame shards over several GPUs
     std::string input_list, input_dir, video_raw, jsonl_path, save_dir;
     int video_w = 640, video_h = 480;
+    int video_pixfmt = YOLO2_PIX_RGB24; // --video-pix-fmt: what a --video-raw frame holds (RGB24, or packed YUYV 4:2:2 read by the GPU as it is)
     int max_frames = 0;                // 0 = all
     int infer_every = 1;
     std::string post = "gpu";          // region + boxes + NMS: gpu | host
@@ -97,6 +98,9 @@ void print_usage(const char *prog)
         "  --input-dir <dir>     Every *.jpg / *.jpeg / *.png / *.ppm / *.pgm of a directory, sorted by name\n"
         "  --video-raw <file|->  Raw RGB24 frames (e.g. from `ffmpeg -f rawvideo -pix_fmt rgb24 -`), with\n"
         "  --video-width <w> --video-height <h>   frame size (default 640x480)\n"
+        "  --video-pix-fmt <rgb24|yuyv422>   what --video-raw holds (default rgb24).  yuyv422 (also: yuyv): packed YUYV 4:2:2, a V4L2 camera's\n"
+        "                        native frames (`ffmpeg -f v4l2 -pix_fmt yuyv422 ... -f rawvideo -`), 2 bytes per pixel, even width; they go to\n"
+        "                        the GPU as they are and are converted where they are read (every --precision, --devices)\n"
         "  --max-frames <n>      Stop after n inference frames (default: all)\n"
         "  --infer-every <n>     Run inference on every n-th frame (default 1)\n"
         "  --jsonl <path>        One JSON record per frame (fields of the reference's --output-json)\n"
@@ -108,7 +112,7 @@ void print_usage(const char *prog)
         "                        timed conv plans; with it a weight set is timed once and every later run uses the same kernels)\n"
         "  --post <gpu|host>     Where region + boxes + NMS run (default gpu; host: int16 only)\n"
         "  --precision int16 | fp16 | fp32fast   also when streaming: fp16 / fp32fast read weights_reorg.bin + bias.bin and run layers 0+1\n"
-        "                        straight from the image bytes on the matrix cores (yolo2_hip_run_images_u8_dets_f16)\n",
+        "                        straight from the image bytes on the matrix cores (yolo2_hip_run_images_pix_dets_f16)\n",
         prog);
 }
 
@@ -146,6 +150,12 @@ AppConfig parse_args(int argc, char **argv)
         else if (arg == "--video-raw" && need("")) cfg.video_raw = argv[++i];
         else if (arg == "--video-width" && need("")) cfg.video_w = std::atoi(argv[++i]);
         else if (arg == "--video-height" && need("")) cfg.video_h = std::atoi(argv[++i]);
+        else if (arg == "--video-pix-fmt" && need("")) {
+            const std::string v = argv[++i];
+            if (v == "rgb24") cfg.video_pixfmt = YOLO2_PIX_RGB24;
+            else if (v == "yuyv422" || v == "yuyv") cfg.video_pixfmt = YOLO2_PIX_YUYV;
+            else { std::fprintf(stderr, "Unsupported --video-pix-fmt %s (rgb24 | yuyv422)\n", v.c_str()); std::exit(1); }
+        }
         else if (arg == "--max-frames" && need("")) cfg.max_frames = std::atoi(argv[++i]);
         else if (arg == "--infer-every" && need("")) cfg.infer_every = std::max(1, std::atoi(argv[++i]));
         else if ((arg == "--jsonl" || arg == "--output-json") && need("")) cfg.jsonl_path = argv[++i];
@@ -180,6 +190,10 @@ AppConfig parse_args(int argc, char **argv)
             print_usage(argv[0]);
             std::exit(1);
         } else cfg.input_path = arg;
+    }
+    if (cfg.video_pixfmt == YOLO2_PIX_YUYV && !cfg.video_raw.empty() && (cfg.video_w & 1)) {
+        std::fprintf(stderr, "--video-pix-fmt yuyv422 needs an even --video-width, not %d\n", cfg.video_w);
+        std::exit(1);
     }
     return cfg;
 }
@@ -273,7 +287,7 @@ std::vector<OutDet> best_class_dets(const std::vector<y2h::Detection> &dets, int
 struct SrcFrame {
     std::string source;
     int frame_index = 0;    // 1-based position in the stream
-    y2h::ImageU8 img;
+    y2h::ImageU8 img;       // (a --video-pix-fmt yuyv422 frame: img.rgb holds its 2 w h YUYV bytes, as they were read)
 };
 
 // Frame source: a list of image files, a directory, or a raw RGB24 stream.  next_ref() enumerates the frames selected for
@@ -318,7 +332,7 @@ class FrameSource {
             SrcFrame f;
             if (mode_ == "video") {
                 f.img.w = cfg_.video_w; f.img.h = cfg_.video_h;
-                f.img.rgb.resize((size_t)cfg_.video_w * cfg_.video_h * 3);
+                f.img.rgb.resize((size_t)cfg_.video_w * cfg_.video_h * (cfg_.video_pixfmt == YOLO2_PIX_YUYV ? 2 : 3));
                 const size_t rd = std::fread(f.img.rgb.data(), 1, f.img.rgb.size(), raw_);
                 if (rd != f.img.rgb.size()) return false;    // EOF (a trailing partial frame is dropped like the reference's reader)
                 f.source = cfg_.video_raw;
@@ -472,9 +486,11 @@ void run_stream(AppConfig cfg)
     namespace fs = std::filesystem;
     static char outbuf[1 << 16];
     std::setvbuf(stdout, outbuf, _IOFBF, sizeof(outbuf));    // thousands of frames a second: no write() per line
-    // fp16 / fp32fast: the matrix-core passes from image bytes (yolo2_hip_run_images_u8_dets_f16), split = 0 / 1
+    // fp16 / fp32fast: the matrix-core passes from image bytes (yolo2_hip_run_images_pix_dets_f16), split = 0 / 1
     const bool f16 = cfg.precision == "fp16" || cfg.precision == "fp32fast";
     const int split = cfg.precision == "fp32fast" ? 1 : 0;
+    // what the frames' bytes are: decoded image files are RGB24, a raw video stream is what --video-pix-fmt says
+    const int pixfmt = cfg.input_list.empty() && cfg.input_dir.empty() ? cfg.video_pixfmt : YOLO2_PIX_RGB24;
     if (cfg.precision != "int16" && !f16) throw std::runtime_error("the streaming frontend runs the int16, fp16 and fp32fast paths");
     if (f16 && cfg.post == "host")
         throw std::runtime_error("--post host runs the int16 region tensor only; --precision " + cfg.precision + " needs --post gpu");
@@ -596,9 +612,15 @@ void run_stream(AppConfig cfg)
                     if (jf) write_jsonl(jf, src.mode(), fr.source, fr.frame_index, infer_idx, fr.img.w, fr.img.h, c.dets[(size_t)f], names);
                     if (!cfg.save_dir.empty()) {
                         y2h::Image im = y2h::make_image(fr.img.w, fr.img.h, 3);
+                        std::vector<uint8_t> conv;   // the annotated frame needs RGB pixels: a YUYV frame is converted here, on the host
+                        if (pixfmt == YOLO2_PIX_YUYV) {
+                            conv.resize((size_t)im.w * im.h * 3);
+                            if (!y2h::yuyv_to_rgb24(fr.img.rgb.data(), conv.data(), im.w, im.h)) throw std::runtime_error("bad YUYV frame");
+                        }
+                        const uint8_t *rgb = conv.empty() ? fr.img.rgb.data() : conv.data();
                         for (int k = 0; k < 3; ++k)
                             for (int y = 0; y < im.h; ++y)
-                                for (int x = 0; x < im.w; ++x) im.at(x, y, k) = (float)fr.img.rgb[((size_t)y * im.w + x) * 3 + k] / 255.f;
+                                for (int x = 0; x < im.w; ++x) im.at(x, y, k) = (float)rgb[((size_t)y * im.w + x) * 3 + k] / 255.f;
                         for (const OutDet &d : c.dets[(size_t)f]) {
                             const y2h::Box &b = d.box;
                             const float hue = (float)((d.class_id * 123457) % last.classes) / last.classes;
@@ -654,10 +676,10 @@ void run_stream(AppConfig cfg)
                         const int cap = 845;
                         recs.resize((size_t)n * cap);
                         std::vector<int> counts((size_t)n);
-                        const int rc = f16 ? yolo2_hip_run_images_u8_dets_f16(ctx, split, ptrs.data(), ws.data(), hs.data(), 3, n, cfg.batch, cfg.thresh,
-                                                                              cfg.nms, YOLO2_DETS_BEST_CLASS, recs.data(), cap, counts.data())
-                                           : yolo2_hip_run_images_u8_dets(ctx, ptrs.data(), ws.data(), hs.data(), 3, n, cfg.batch, cfg.thresh, cfg.nms,
-                                                                          YOLO2_DETS_BEST_CLASS, recs.data(), cap, counts.data(), &q);
+                        const int rc = f16 ? yolo2_hip_run_images_pix_dets_f16(ctx, split, ptrs.data(), ws.data(), hs.data(), pixfmt, n, cfg.batch, cfg.thresh,
+                                                                               cfg.nms, YOLO2_DETS_BEST_CLASS, recs.data(), cap, counts.data())
+                                           : yolo2_hip_run_images_pix_dets(ctx, ptrs.data(), ws.data(), hs.data(), pixfmt, n, cfg.batch, cfg.thresh, cfg.nms,
+                                                                           YOLO2_DETS_BEST_CLASS, recs.data(), cap, counts.data(), &q);
                         if (rc != YOLO2_SUCCESS) throw std::runtime_error(yolo2_hip_last_error());
                         for (int f = 0; f < n; ++f) {
                             if (counts[(size_t)f] > cap) throw std::runtime_error("detection records truncated");   // cannot happen in best-class mode
@@ -668,7 +690,7 @@ void run_stream(AppConfig cfg)
                         }
                     } else {
                         region.resize((size_t)n * YOLO2_REGION_ELEMS);
-                        if (yolo2_hip_run_images_u8_host(ctx, ptrs.data(), ws.data(), hs.data(), 3, n, cfg.batch, region.data(), &q) != YOLO2_SUCCESS)
+                        if (yolo2_hip_run_images_pix_host(ctx, ptrs.data(), ws.data(), hs.data(), pixfmt, n, cfg.batch, region.data(), &q) != YOLO2_SUCCESS)
                             throw std::runtime_error(yolo2_hip_last_error());
                         auto all = y2h::postprocess_batch(region.data(), n, q, ws.data(), hs.data(), cfg.thresh, cfg.nms, post_threads);
                         for (int f = 0; f < n; ++f) ck->dets[(size_t)f] = best_class_dets(all[(size_t)f], (int)all[(size_t)f].size(), last.classes, cfg.thresh);

@@ -49,13 +49,37 @@ EXPORTS = [
     "yolo2_hip_debug_f16_tensor",
     "yolo2_hip_run_images_u8_f16_host", "yolo2_hip_run_images_u8_dets_f16", "yolo2_hip_multi_run_images_u8_dets_f16",
     "yolo2_hip_images_layer0_kernel",
+    "yolo2_hip_letterbox_pix", "yolo2_hip_run_images_pix_host", "yolo2_hip_run_images_pix_dets", "yolo2_hip_run_images_pix_f16_host",
+    "yolo2_hip_run_images_pix_dets_f16", "yolo2_hip_multi_run_images_pix_host", "yolo2_hip_multi_run_images_pix_dets",
+    "yolo2_hip_multi_run_images_pix_dets_f16",
 ]
 
+# include/yolo2_hip.h YOLO2_PIX_*: the pixfmt argument of the _pix entries ("yuyv": packed YUYV 4:2:2, arrays uint8 [h][w][2])
+PIXFMTS = {"grey8": 1, "rgb24": 3, "yuyv": 0x56595559}
 
-def letterbox_u8(image_hwc: np.ndarray, net_w: int = 416, net_h: int = 416) -> np.ndarray:
+
+def _pix_code(pixfmt, imgs) -> int:
+    """the entries' pixfmt argument for a list of contiguous uint8 arrays, whose shapes must be that format's"""
+    if pixfmt not in PIXFMTS:
+        raise ValueError(f"pixfmt must be None or one of {tuple(PIXFMTS)}, not {pixfmt!r}")
+    last = {"grey8": None, "rgb24": 3, "yuyv": 2}[pixfmt]
+    for im in imgs:
+        if (im.ndim != 2 if last is None else im.ndim != 3 or im.shape[2] != last):
+            raise ValueError(f"a {pixfmt} image is uint8 [h][w]{'' if last is None else f'[{last}]'}, not {im.shape}")
+    return PIXFMTS[pixfmt]
+
+
+def letterbox_pix(image: np.ndarray, pixfmt: str, net_w: int = 416, net_h: int = 416) -> np.ndarray:
+    """letterbox_u8 with a pixel format (yolo2_hip_letterbox_pix): "grey8" [h][w], "rgb24" [h][w][3] or "yuyv" [h][w][2] (packed
+    YUYV 4:2:2, converted per fetched pixel on the GPU) -> float [3][net_h][net_w] frame."""
+    return letterbox_u8(image, net_w, net_h, pixfmt=pixfmt)
+
+
+def letterbox_u8(image_hwc: np.ndarray, net_w: int = 416, net_h: int = 416, pixfmt=None) -> np.ndarray:
     """uint8 [h][w][3] (or [h][w]) host image -> float [3][net_h][net_w] frame, letterboxed on the GPU."""
     im = np.ascontiguousarray(image_hwc, dtype=np.uint8)
     ch = 1 if im.ndim == 2 else im.shape[2]
+    code = None if pixfmt is None else _pix_code(pixfmt, [im])
     L = lib()
     src, dst = C.c_uint64(0), C.c_uint64(0)
     out = np.empty((3, net_h, net_w), dtype=np.float32)
@@ -63,7 +87,10 @@ def letterbox_u8(image_hwc: np.ndarray, net_w: int = 416, net_h: int = 416) -> n
     check(L.yolo2_hip_alloc(out.nbytes, C.byref(dst)), "alloc")
     try:
         check(L.yolo2_hip_memcpy_h2d(src, im.ctypes.data_as(C.c_void_p), im.nbytes), "h2d")
-        check(L.yolo2_hip_letterbox_u8(src, im.shape[1], im.shape[0], ch, dst, net_w, net_h, None), "yolo2_hip_letterbox_u8")
+        if code is None:
+            check(L.yolo2_hip_letterbox_u8(src, im.shape[1], im.shape[0], ch, dst, net_w, net_h, None), "yolo2_hip_letterbox_u8")
+        else:
+            check(L.yolo2_hip_letterbox_pix(src, im.shape[1], im.shape[0], code, dst, net_w, net_h, None), "yolo2_hip_letterbox_pix")
         check(L.yolo2_hip_memcpy_d2h(out.ctypes.data_as(C.c_void_p), dst, out.nbytes), "d2h")
     finally:
         L.yolo2_hip_free(src)
@@ -202,6 +229,15 @@ def lib():
     L.dma_buffer_sync_for_device.argtypes = [vp, C.c_size_t, C.c_size_t]
     L.dma_buffer_sync_for_cpu.argtypes = [vp, C.c_size_t, C.c_size_t]
     L.memory_get_phys_addr.argtypes = [vp]
+    # the images entries with a pixel format: the u8 entries' argument lists, pixfmt in place of channels
+    sig("yolo2_hip_letterbox_pix", L.yolo2_hip_letterbox_u8.argtypes)
+    for name in ("run_images_pix_host", "multi_run_images_pix_host"):
+        sig("yolo2_hip_" + name, L.yolo2_hip_run_images_u8_host.argtypes)
+    for name in ("run_images_pix_dets", "multi_run_images_pix_dets"):
+        sig("yolo2_hip_" + name, L.yolo2_hip_run_images_u8_dets.argtypes)
+    sig("yolo2_hip_run_images_pix_f16_host", L.yolo2_hip_run_images_u8_f16_host.argtypes)
+    for name in ("run_images_pix_dets_f16", "multi_run_images_pix_dets_f16"):
+        sig("yolo2_hip_" + name, L.yolo2_hip_run_images_u8_dets_f16.argtypes)
     _lib = L
     return L
 
@@ -370,19 +406,16 @@ class Yolo2Hip:
         self.final_q = q.value
         return region, q.value
 
-    def run_images_host(self, images, batch: int = 64):
+    def run_images_host(self, images, batch: int = 64, pixfmt=None):
         """images: list of uint8 arrays [h][w][3] (or [h][w] grey) of arbitrary sizes -> region tensors.
-        Bytes cross PCIe, letterboxing runs on the GPU (yolo2_hip_run_images_u8_host)."""
-        imgs = [np.ascontiguousarray(im, dtype=np.uint8) for im in images]
-        n = len(imgs)
-        ch = 1 if imgs[0].ndim == 2 else imgs[0].shape[2]
-        ptrs = (C.c_void_p * n)(*[im.ctypes.data for im in imgs])
-        ws = (C.c_int * n)(*[im.shape[1] for im in imgs])
-        hs = (C.c_int * n)(*[im.shape[0] for im in imgs])
+        Bytes cross PCIe, letterboxing runs on the GPU (yolo2_hip_run_images_u8_host).  pixfmt "grey8" / "rgb24" / "yuyv" (arrays
+        [h][w][2]) names the format instead (yolo2_hip_run_images_pix_host); None infers grey / RGB from the shape."""
+        n, ptrs, ws, hs, fmt, _keep = _image_args(images, pixfmt)
         region = np.empty((n, 425, 13, 13), dtype=np.int16)
         q = C.c_int(0)
-        check(lib().yolo2_hip_run_images_u8_host(self._h, ptrs, ws, hs, ch, n, batch, region.ctypes.data_as(C.c_void_p), C.byref(q)),
-              "yolo2_hip_run_images_u8_host")
+        fn = lib().yolo2_hip_run_images_u8_host if pixfmt is None else lib().yolo2_hip_run_images_pix_host
+        check(fn(self._h, ptrs, ws, hs, fmt, n, batch, region.ctypes.data_as(C.c_void_p), C.byref(q)),
+              "yolo2_hip_run_images_u8_host" if pixfmt is None else "yolo2_hip_run_images_pix_host")
         self.final_q = q.value
         return region, q.value
 
@@ -472,13 +505,15 @@ class Yolo2Hip:
               "yolo2_hip_run_batch_f32tol_host")
         return region
 
-    def run_images_f16_host(self, images, batch: int, split: bool = False) -> np.ndarray:
+    def run_images_f16_host(self, images, batch: int, split: bool = False, pixfmt=None) -> np.ndarray:
         """images (uint8 [h][w][3] or [h][w] grey, any sizes) -> float32 region tensors [n][425][13][13] through the fp16 pass
-        (split=True: the fp32-tolerance pass); layers 0+1 read the image bytes on the GPU (yolo2_hip_run_images_u8_f16_host)."""
-        n, ptrs, ws, hs, ch, _keep = _image_args(images)
+        (split=True: the fp32-tolerance pass); layers 0+1 read the image bytes on the GPU (yolo2_hip_run_images_u8_f16_host).
+        pixfmt as in run_images_host (yolo2_hip_run_images_pix_f16_host)."""
+        n, ptrs, ws, hs, fmt, _keep = _image_args(images, pixfmt)
         region = np.empty((n, 425, 13, 13), dtype=np.float32)
-        check(lib().yolo2_hip_run_images_u8_f16_host(self._h, int(bool(split)), ptrs, ws, hs, ch, n, batch,
-                                                     region.ctypes.data_as(C.c_void_p)), "yolo2_hip_run_images_u8_f16_host")
+        fn = lib().yolo2_hip_run_images_u8_f16_host if pixfmt is None else lib().yolo2_hip_run_images_pix_f16_host
+        check(fn(self._h, int(bool(split)), ptrs, ws, hs, fmt, n, batch, region.ctypes.data_as(C.c_void_p)),
+              "yolo2_hip_run_images_u8_f16_host" if pixfmt is None else "yolo2_hip_run_images_pix_f16_host")
         return region
 
     def images_layer0_kernel(self, split: bool = False) -> str:
@@ -582,11 +617,12 @@ def postprocess(ctx, region_ptr: int, batch: int, im_w, im_h, thresh: float, nms
 DETS_BEST_CLASS = 1
 
 
-def _image_args(images):
-    """(n, pointer array, widths, heights, channels, the contiguous arrays the pointers point into)"""
+def _image_args(images, pixfmt=None):
+    """(n, pointer array, widths, heights, channels - or, with a pixfmt, its YOLO2_PIX_* code -, the contiguous arrays the pointers
+    point into)"""
     imgs = [np.ascontiguousarray(im, dtype=np.uint8) for im in images]
     n = len(imgs)
-    ch = 1 if imgs[0].ndim == 2 else imgs[0].shape[2]
+    ch = (1 if imgs[0].ndim == 2 else imgs[0].shape[2]) if pixfmt is None else _pix_code(pixfmt, imgs)
     ptrs = (C.c_void_p * n)(*[im.ctypes.data for im in imgs])
     ws = (C.c_int * n)(*[im.shape[1] for im in imgs])
     hs = (C.c_int * n)(*[im.shape[0] for im in imgs])
@@ -597,26 +633,28 @@ PRECISIONS = ("int16", "fp16", "fp32fast")
 
 
 def run_images_dets(handle, images, batch: int, thresh: float, nms: float, cap: int = 845, best_class: bool = True, multi: bool = False,
-                    precision: str = "int16"):
+                    precision: str = "int16", pixfmt=None):
     """yolo2_hip_run_images_u8_dets / yolo2_hip_multi_run_images_u8_dets: host images (uint8 [h][w][3]) -> per-frame detection
     records; letterbox, network and the tail run on the device(s), the region tensor never leaves HBM.  precision "fp16" /
-    "fp32fast" (the split-fp16 pass) run the _dets_f16 entries instead (fp32 weights loaded); their final_q is None."""
+    "fp32fast" (the split-fp16 pass) run the _dets_f16 entries instead (fp32 weights loaded); their final_q is None.
+    pixfmt "grey8" / "rgb24" / "yuyv" (arrays [h][w][2]): the _pix_dets entries with that format; None infers grey / RGB."""
     if precision not in PRECISIONS:
         raise ValueError(f"precision must be one of {PRECISIONS}, not {precision!r}")
-    n, ptrs, ws, hs, ch, _keep = _image_args(images)
+    n, ptrs, ws, hs, ch, _keep = _image_args(images, pixfmt)
+    kind = "u8" if pixfmt is None else "pix"
     dets = np.zeros((n, cap), dtype=DET_DTYPE)
     counts = np.zeros(n, dtype=np.int32)
     flags = DETS_BEST_CLASS if best_class else 0
     if precision != "int16":
         split = int(precision == "fp32fast")
-        fn = lib().yolo2_hip_multi_run_images_u8_dets_f16 if multi else lib().yolo2_hip_run_images_u8_dets_f16
-        check(fn(handle, split, ptrs, ws, hs, ch, n, batch, thresh, nms, flags, dets.ctypes.data_as(C.c_void_p), cap,
-                 counts.ctypes.data_as(C.c_void_p)), "yolo2_hip_run_images_u8_dets_f16")
+        name = f"yolo2_hip_{'multi_' if multi else ''}run_images_{kind}_dets_f16"
+        check(getattr(lib(), name)(handle, split, ptrs, ws, hs, ch, n, batch, thresh, nms, flags, dets.ctypes.data_as(C.c_void_p), cap,
+                                   counts.ctypes.data_as(C.c_void_p)), name)
         return {"dets": [dets[f, :min(int(counts[f]), cap)] for f in range(n)], "counts": counts, "final_q": None}
     q = C.c_int(0)
-    fn = lib().yolo2_hip_multi_run_images_u8_dets if multi else lib().yolo2_hip_run_images_u8_dets
-    check(fn(handle, ptrs, ws, hs, ch, n, batch, thresh, nms, DETS_BEST_CLASS if best_class else 0, dets.ctypes.data_as(C.c_void_p), cap,
-             counts.ctypes.data_as(C.c_void_p), C.byref(q)), "yolo2_hip_run_images_u8_dets")
+    name = f"yolo2_hip_{'multi_' if multi else ''}run_images_{kind}_dets"
+    check(getattr(lib(), name)(handle, ptrs, ws, hs, ch, n, batch, thresh, nms, flags, dets.ctypes.data_as(C.c_void_p), cap,
+                               counts.ctypes.data_as(C.c_void_p), C.byref(q)), name)
     return {"dets": [dets[f, :min(int(counts[f]), cap)] for f in range(n)], "counts": counts, "final_q": q.value}
 
 
@@ -746,15 +784,11 @@ class Yolo2HipMulti:
                                                      region.ctypes.data_as(C.c_void_p), C.byref(q)), "yolo2_hip_multi_run_frames_int16")
         return region, q.value
 
-    def run_images(self, images, batch_per_device: int):
-        imgs = [np.ascontiguousarray(im, dtype=np.uint8) for im in images]
-        n = len(imgs)
-        ch = 1 if imgs[0].ndim == 2 else imgs[0].shape[2]
-        ptrs = (C.c_void_p * n)(*[im.ctypes.data for im in imgs])
-        ws = (C.c_int * n)(*[im.shape[1] for im in imgs])
-        hs = (C.c_int * n)(*[im.shape[0] for im in imgs])
+    def run_images(self, images, batch_per_device: int, pixfmt=None):
+        n, ptrs, ws, hs, fmt, _keep = _image_args(images, pixfmt)
         region = np.empty((n, 425, 13, 13), dtype=np.int16)
         q = C.c_int(0)
-        check(lib().yolo2_hip_multi_run_images_u8_host(self._m, ptrs, ws, hs, ch, n, batch_per_device, region.ctypes.data_as(C.c_void_p),
-                                                       C.byref(q)), "yolo2_hip_multi_run_images_u8_host")
+        fn = lib().yolo2_hip_multi_run_images_u8_host if pixfmt is None else lib().yolo2_hip_multi_run_images_pix_host
+        check(fn(self._m, ptrs, ws, hs, fmt, n, batch_per_device, region.ctypes.data_as(C.c_void_p), C.byref(q)),
+              "yolo2_hip_multi_run_images_u8_host" if pixfmt is None else "yolo2_hip_multi_run_images_pix_host")
         return region, q.value
