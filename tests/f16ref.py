@@ -259,7 +259,7 @@ def step_ref(path, kernel, layers, x, W, mutate=None):
     input (layer 0: the float frame [3][416][416] as v); W: Weights.  Returns dict(ref, bound, unit, kind) with kind f16 / split /
     f32 (the unit's meaning: see the module doc) or exact (pool / reorg: bit-exact steps).
     mutate: a deliberate error (tests only), e.g. ("drop_channel", c), ("drop_border_tap", tap), ("shift_tile", t0), ("no_bias_block",
-    blk), ("leaky", slope), ("pool_offset",), ("no_lo",), ("rtz",)."""
+    blk), ("leaky", slope), ("pool_offset",), ("no_lo",), ("no_wlo",), ("rtz",)."""
     exact = path == "exact"
     rm = dict(op="conv", x="f32", w="f32") if exact and layers[0] == 0 else \
         (dict(op=net.LAYERS[layers[0]].type) if exact else rounding_of(kernel, path))
@@ -294,6 +294,8 @@ def step_ref(path, kernel, layers, x, W, mutate=None):
                     xh, xl = split_pair(xv)
                     wh, wl = split_pair(w)
                     xp, wp = [xh, xl, xh], [wh, wh, wl]
+                    if mutate and mutate[0] == "no_wlo":
+                        xp, wp = [xh, xl], [wh, wh]
                 else:
                     wp = [fl16(w)] if wm == "f16" else [w]
             elif exact:
@@ -302,6 +304,8 @@ def step_ref(path, kernel, layers, x, W, mutate=None):
                 wh, wl = split_pair(w)
                 if mutate and mutate[0] == "no_lo":
                     xp, wp = [x["hi"], x["hi"]], [wh, wl]
+                elif mutate and mutate[0] == "no_wlo":             # only a_hi w_lo dropped: the tail part of the packed weights
+                    xp, wp = [x["hi"], x["lo"]], [wh, wh]
                 else:
                     xp, wp = [x["hi"], x["lo"], x["hi"]], [wh, wh, wl]
             else:
