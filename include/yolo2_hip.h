@@ -254,6 +254,12 @@ int yolo2_hip_debug_layer_output(yolo2_hip_ctx *ctx, int layer_idx, int frame, i
 int yolo2_hip_debug_f16_tensor(yolo2_hip_ctx *ctx, int split, int layer_idx, int frame, int which, uint16_t *out,
                                size_t capacity_halves, int *geom);
 
+/* Test hook: the bytes of device (hipMalloc) and pinned (hipHostMalloc) memory the library's contexts and calls hold right now,
+ * process-wide.  Not counted: what yolo2_hip_alloc / the driver tier hand to the caller, and the process-lifetime tables and
+ * scratch of the driver tier and the int16 post-processing; the per-device scratch of the synchronous yolo2_hip_postprocess_*
+ * entries is counted and stays until the process ends.  (0, 0) before the first context exists. */
+int yolo2_hip_debug_live_bytes(size_t *device_bytes, size_t *pinned_bytes);
+
 /* Per-layer device time: enabling records hipEvent pairs around every layer kernel of
  * subsequent runs, on the stream they are launched on (the analogue of the per-layer latency
  * report in linux_app/src/yolo2_inference.c:75-142).  layer_times_ms returns the mean over the

@@ -38,6 +38,20 @@ def test_integration_doc_indexes_every_entry_point():
     assert not missing, missing
 
 
+def test_live_bytes_hook_reports_zero_before_any_context():
+    """yolo2_hip_debug_live_bytes: exported, and (0, 0) in a process that has loaded the library and made no context (a fresh
+    process: this one may hold contexts of earlier tests)."""
+    import subprocess
+    code = ("import ctypes as C; L = C.CDLL(%r); d = C.c_size_t(7); p = C.c_size_t(7); "
+            "L.yolo2_hip_debug_live_bytes.argtypes = [C.POINTER(C.c_size_t)] * 2; "
+            "print(L.yolo2_hip_debug_live_bytes(C.byref(d), C.byref(p)), d.value, p.value, L.yolo2_hip_debug_live_bytes(None, None))"
+            % hipdrv.LIB_PATH)
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    assert r.stdout.split() == ["0", "0", "0", str(hipdrv.YOLO2_ERROR)], r.stdout
+    assert hipdrv.live_bytes() is not None   # the wrapper the GPU tests read the counters through
+
+
 def test_no_gpu_means_loud_failure_not_fallback():
     L = hipdrv.lib()
     if L.yolo2_hip_device_count() > 0:

@@ -26,6 +26,7 @@
 #include "../../include/yolo2_hip.h"
 #include "conv_common.hpp"
 #include "layout.hpp"
+#include "y2_mem.hpp"
 
 // ---------------------------------------------------------------------------- errors (yolo2_hip.hip)
 
@@ -171,19 +172,22 @@ struct ConvPlan {
 
 // ---------------------------------------------------------------------------- the context
 
+// An activation tensor: geometry, the address kernels and launch tables use, and - in the struct that allocated it - the owner.
+// An alias (slots 24 and 27 of every family are the concat tensor) carries geometry and address only: y2_view_of.
 struct Tensor {
     y2::ActGeom g;
     int2 *d = nullptr;
+    Y2DevBuf<int2> own;
 };
 
 // Device buffers of one post-processing call in flight (yolo2_post.hip)
 struct Y2PostBufs {
     int cap_frames = 0;
     size_t cap_dets = 0;
-    float *rows = nullptr, *rows2 = nullptr;
-    int *totals = nullptr, *counts = nullptr;
-    void *geom = nullptr;            // [cap_frames] letterbox-correction records (y2_post_geom_bytes() each)
-    yolo2_hip_det *dets = nullptr;   // [cap_frames][cap]
+    Y2DevBuf<float> rows, rows2;
+    Y2DevBuf<int> totals, counts;
+    Y2DevBuf<uint8_t> geom;          // [cap_frames] letterbox-correction records (y2_post_geom_bytes() each)
+    Y2DevBuf<yolo2_hip_det> dets;    // [cap_frames][cap]
 };
 
 // Staging for the host-buffer entries (run_frames / run_images): two buffer sets and three streams
@@ -192,22 +196,25 @@ struct Y2PostBufs {
 struct PipeBufs {
     size_t host_in = 0, dev_in = 0;   // capacities in bytes (dev_in: raw image bytes, 0 for float frames)
     int batch = 0;
-    uint8_t *hin[2] = {nullptr, nullptr}, *dbytes[2] = {nullptr, nullptr};
-    float *din[2] = {nullptr, nullptr};
-    int16_t *hout[2] = {nullptr, nullptr}, *dout[2] = {nullptr, nullptr};
+    Y2PinBuf<uint8_t> hin[2];
+    Y2DevBuf<uint8_t> dbytes[2];
+    Y2DevBuf<float> din[2];
+    Y2PinBuf<int16_t> hout[2];
+    Y2DevBuf<int16_t> dout[2];
     hipStream_t s_in = nullptr, s_run = nullptr, s_out = nullptr;
     hipEvent_t e_in[2] = {nullptr, nullptr}, e_run[2] = {nullptr, nullptr}, e_out[2] = {nullptr, nullptr};
     hipEvent_t e_lane[2][8] = {};      // images -> detections entry: lane i has finished its part of the chunk in buffer set b (created on demand)
     // the tail as a pipeline stage (yolo2_hip_run_images_u8_dets): per buffer set its device buffers and pinned host mirrors
     int post_batch = 0, post_cap = 0;
     Y2PostBufs post[2];
-    uint8_t *hgeom[2] = {nullptr, nullptr};
-    yolo2_hip_det *hdets[2] = {nullptr, nullptr};
-    int *hcounts[2] = {nullptr, nullptr};
+    Y2PinBuf<uint8_t> hgeom[2];
+    Y2PinBuf<yolo2_hip_det> hdets[2];
+    Y2PinBuf<int> hcounts[2];
     // the fp16 / split-fp16 images entries: fp32 region tensors [batch][425][13][13] per buffer set (device; pinned mirrors for the
     // entry that returns them)
     int regf_batch = 0;
-    float *dregf[2] = {nullptr, nullptr}, *hregf[2] = {nullptr, nullptr};
+    Y2DevBuf<float> dregf[2];
+    Y2PinBuf<float> hregf[2];
 };
 
 struct F16Plan;   // yolo2_fp16.hip: the per-context launch table of the fp16 path
@@ -218,8 +225,12 @@ struct yolo2_hip_ctx {
     Y2Options opt;                     // parsed once at creation (environment), changed only by yolo2_hip_set_option; lanes copy it
     std::shared_ptr<Y2PlanCache> plan_cache;   // weight-side cache bound by yolo2_hip_set_plan_cache (lanes share the parent's)
     bool weights_loaded = false;
+    // Weight buffers are an owner plus the view every user reads: the context that allocated a buffer fills both, a lane or the split
+    // twin fills only the view of what it borrows from its parent (which outlives it: yolo2_hip_destroy, and every reload destroys
+    // the borrowers before it replaces a buffer).
     short *wpk = nullptr;      // all layers, packed
     short *bias_pk = nullptr;  // all layers, padded to 32
+    Y2DevBuf<short> wpk_own, bias_pk_own;
     long wpk_off[YOLO2_N_CONV], bias_off[YOLO2_N_CONV];
     int maxsum[YOLO2_N_CONV], maxbias[YOLO2_N_CONV];
     std::vector<int> weight_q, bias_q, act_q;
@@ -229,8 +240,10 @@ struct yolo2_hip_ctx {
     std::vector<signed char> wscale_mb[YOLO2_N_CONV];   // log2 of the factor each block's packed weights currently carry (form D)
     std::vector<signed char> form_mb[YOLO2_N_CONV];     // arithmetic form resolve_q chose per block of 32 output channels
     int *mb_lists = nullptr;           // device: block index lists of all split layers
+    Y2DevBuf<int> mb_lists_own;
     int plan_source = 0;               // how set_batch planned the conv launches: 1 plan table, 2 timed (autotune), 3 static defaults, 4 forced, 5 weight cache
     int *ks_trip = nullptr;            // device scratch of the K-split-across-workgroups kernel (triples of every split): sized from the accepted plans
+    Y2DevBuf<int> ks_trip_own;
     size_t ks_trip_bytes = 0;
     // Lanes: a batch is run as part-batches on internal streams (forked from / joined to the
     // caller's stream with events).  Every layer is then several concurrent launches, and the idle tail of
@@ -250,30 +263,36 @@ struct yolo2_hip_ctx {
     int batch = 0;
     Tensor t_in, t_out[32], t_cat;
     // ---- fp16 MFMA path
-    struct HalfTensor {
+    struct HalfGeom {
         int C = 0, Cp = 0, H = 0, W = 0, Wp = 0, PL = 0, B = 0;
         size_t items = 0;
+    };
+    struct HalfTensor : HalfGeom {
         _Float16 *d = nullptr;
+        Y2DevBuf<_Float16> own;
     };
     bool f16_loaded = false;
     // split-fp16 ("fp32tol") mode: a twin context that runs the fp16 launch table on items of three parts [hi | lo | hi] with
     // weights packed [w_hi | w_hi | w_lo] (kernels_f16.hpp, SPLIT instantiations).  The twin owns its packed weights (wh / biasf), its
-    // tensors, table and lanes; it borrows the fp32 blobs and w0f from this context.
+    // tensors, table and lanes; it borrows the fp32 blobs and w0f from this context (views without owners).
     bool split = false;                // this context IS such a twin (or a lane of one)
-    bool borrows_f32 = false;          // w0f / wf32 / bf32 belong to the parent
     yolo2_hip_ctx *tol = nullptr;      // the parent's twin, made at the first yolo2_hip_run_batch_f32tol
     _Float16 *wh = nullptr;
     float *biasf = nullptr;
     float *w0f = nullptr;  // layer 0: [27][32] fp32 weights + [32] bias for the fused conv0+pool kernel
     float *wf32 = nullptr, *bf32 = nullptr;   // the fp32 blobs as loaded (reference stream order), for the exact fp32 pass
+    Y2DevBuf<_Float16> wh_own;
+    Y2DevBuf<float> biasf_own, w0f_own, wf32_own, bf32_own;
     F16Plan *f16_plan = nullptr;              // launch table of the fp16 pass (built once per (weights, batch); owned)
     std::string images_l0[2];                 // what the last fp16 (0) / split (1) images call ran for layers 0+1 (yolo2_hip_images_layer0_kernel)
     // ---- tiled exact fp32 path (kernels_f32.hpp): packed weights [mb][cg][tap][32][4] floats, items of 4 floats
     float *wpkf = nullptr, *biasf32_pk = nullptr;
+    Y2DevBuf<float> wpkf_own, biasf32_pk_own;
     long wpkf_off[YOLO2_N_CONV], biasf32_off[YOLO2_N_CONV];
     struct FTensor {
         y2::ActGeom g;
         float4 *d = nullptr;
+        Y2DevBuf<float4> own;
     };
     int f32_batch = 0;
     FTensor f_in, f_out[32], f_cat;
@@ -295,9 +314,15 @@ struct yolo2_hip_ctx {
 // ---------------------------------------------------------------------------- helpers that cross translation units
 
 // yolo2_hip.hip
-void y2_free_activations(yolo2_hip_ctx *c);
-void y2_free_f16_activations(yolo2_hip_ctx *c);
-void y2_free_f32_activations(yolo2_hip_ctx *c);
+// drops the tensors of one family (owners and views) and its batch: c->t_* / batch, c->h_* / f16_batch, c->f_* / f32_batch
+template <typename TensorT>
+void y2_free_tensors(TensorT &in, TensorT (&out)[32], TensorT &cat, int &batch)
+{
+    for (TensorT *t : {&in, &cat}) { t->own.reset(); t->d = nullptr; }
+    for (TensorT &t : out) { t.own.reset(); t.d = nullptr; }
+    batch = 0;
+}
+void y2_free_activations(yolo2_hip_ctx *c);       // the int16 family and its K-split scratch
 void y2_destroy_lanes(yolo2_hip_ctx *c);
 // Streams of the lanes (yolo2_hip.hip): created at the device's HIGHEST stream priority.  HIP multiplexes the streams of a process
 // onto a few hardware queues PER PRIORITY LEVEL (4 by default); at the default priority the lanes share that pool with every other
@@ -308,7 +333,49 @@ void y2_destroy_lanes(yolo2_hip_ctx *c);
 int y2_lane_stream_create(hipStream_t *s);
 bool y2_lane0_own_stream();
 int y2_ensure_prof_events(yolo2_hip_ctx *c);
-int y2_ensure(void **p, size_t *cap, size_t need);   // grow-only device scratch
+
+// allocates `count` elements into `own` and points the view `d` at them (nullptr if the allocation fails)
+template <typename T>
+int y2_alloc_owned(Y2DevBuf<T> &own, T *&d, size_t count, const char *file = __builtin_FILE(), int line = __builtin_LINE())
+{
+    d = nullptr;
+    const int rc = own.alloc(count, file, line);
+    d = own.get();
+    return rc;
+}
+// `v` becomes an alias of `of`: its geometry and address, owning nothing
+template <typename TensorT>
+void y2_view_of(TensorT &v, const TensorT &of)
+{
+    v.own.reset();
+    v.g = of.g;
+    v.d = of.d;
+}
+inline void y2_view_of(yolo2_hip_ctx::HalfTensor &v, const yolo2_hip_ctx::HalfTensor &of)
+{
+    v.own.reset();
+    static_cast<yolo2_hip_ctx::HalfGeom &>(v) = of;
+    v.d = of.d;
+}
+// frames on the host -> device, `run(frames_dev, region_dev)` on the null stream, the region tensor (elements of R) back: the four
+// yolo2_hip_run_batch_*_host entries
+template <typename R, typename Run>
+int y2_run_batch_host(yolo2_hip_ctx *c, const float *frames, int batch, R *region, Run run)
+{
+    if (!c || !frames || !region) return fail(YOLO2_ERROR, "null argument");
+    HIP_TRY(hipSetDevice(c->device), YOLO2_INIT_ERROR);
+    Y2DevBuf<float> fd;
+    Y2DevBuf<R> rd;
+    int rc;
+    if ((rc = fd.alloc((size_t)batch * YOLO2_FRAME_ELEMS)) || (rc = rd.alloc((size_t)batch * YOLO2_REGION_ELEMS))) return rc;
+    HIP_TRY(hipMemcpy(fd.get(), frames, (size_t)batch * YOLO2_FRAME_ELEMS * sizeof(float), hipMemcpyHostToDevice), YOLO2_DMA_ERROR);
+    rc = run((uint64_t)(uintptr_t)fd.get(), (uint64_t)(uintptr_t)rd.get());
+    if (rc == YOLO2_SUCCESS) {
+        const hipError_t e = hipMemcpy(region, rd.get(), (size_t)batch * YOLO2_REGION_ELEMS * sizeof(R), hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = fail(YOLO2_DMA_ERROR, "D2H of region tensor failed: %s", hipGetErrorString(e));
+    }
+    return rc;
+}
 
 // yolo2_fp16.hip
 void y2_f16_plan_free(yolo2_hip_ctx *c);
@@ -335,7 +402,6 @@ void y2_drv_conv_f32(const float *in, float *out, const float *w, const float *b
 
 // yolo2_post.hip: the tail (region + boxes + NMS + record compaction) as a stage of a pipeline - caller-owned buffers, enqueue only.
 int y2_post_alloc(int device, int batch, int cap, Y2PostBufs *b);
-void y2_post_free(Y2PostBufs *b);
 size_t y2_post_geom_bytes(void);
 int y2_post_fill_geom(void *geom_host, const int *im_w, const int *im_h, int n);   // host side: correct_region_boxes' per-frame constants
 // region tensor [batch][425][13][13] int16 on `device` -> b->dets / b->counts (cap records per frame; best_only: one per detection);

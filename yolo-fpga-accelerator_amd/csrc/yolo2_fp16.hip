@@ -181,12 +181,12 @@ static int pack_half_weights(yolo2_hip_ctx *c, const float *wd, const float *bd)
     c->f16_plan = new (std::nothrow) F16Plan();
     if (!c->f16_plan) return fail(YOLO2_ERROR, "out of host memory");
     c->f16_plan->sw = F16Switches::from_options(c->opt);   // the ONLY place the fp16 path reads its switches
-    if (c->wh) (void)hipFree(c->wh);
-    if (c->biasf) (void)hipFree(c->biasf);
+    int rc;
+    c->wh_own.reset();
+    c->biasf_own.reset();
     c->wh = nullptr;
     c->biasf = nullptr;
-    HIP_TRY(hipMalloc((void **)&c->wh, (size_t)wtot * 2), YOLO2_MMAP_ERROR);
-    HIP_TRY(hipMalloc((void **)&c->biasf, (size_t)btot * 4), YOLO2_MMAP_ERROR);
+    if ((rc = y2_alloc_owned(c->wh_own, c->wh, (size_t)wtot)) || (rc = y2_alloc_owned(c->biasf_own, c->biasf, (size_t)btot))) return rc;
     long woff = 0, boff = 0;
     ord = 0;
     for (int i = 0; i < 32; ++i) {
@@ -219,15 +219,13 @@ static int load_fp32_common(yolo2_hip_ctx *c, const void *weights_reorg, size_t 
     if (n_bias < YOLO2_N_BIAS) return fail(YOLO2_ERROR, "bias file too small");
     HIP_TRY(hipSetDevice(c->device), YOLO2_INIT_ERROR);
     if (c->tol) { yolo2_hip_destroy(c->tol); c->tol = nullptr; }   // the split-mode twin packs from the blobs that are about to be replaced
-    float *wd = nullptr, *bd = nullptr;
-    HIP_TRY(hipMalloc((void **)&wd, (size_t)YOLO2_N_WEIGHTS * 4), YOLO2_MMAP_ERROR);
-    HIP_TRY(hipMalloc((void **)&bd, (size_t)YOLO2_N_BIAS * 4), YOLO2_MMAP_ERROR);
+    Y2DevBuf<float> wd_own, bd_own;
+    int rc;
+    if ((rc = wd_own.alloc(YOLO2_N_WEIGHTS)) || (rc = bd_own.alloc(YOLO2_N_BIAS))) return rc;
+    float *const wd = wd_own.get(), *const bd = bd_own.get();
     HIP_TRY(hipMemcpy(wd, weights_reorg, (size_t)YOLO2_N_WEIGHTS * 4, kind), YOLO2_DMA_ERROR);
     HIP_TRY(hipMemcpy(bd, bias, (size_t)YOLO2_N_BIAS * 4, kind), YOLO2_DMA_ERROR);
-    {
-        const int prc = pack_half_weights(c, wd, bd);
-        if (prc) return prc;
-    }
+    if ((rc = pack_half_weights(c, wd, bd))) return rc;
     // the halo-tile kernels use up to the whole 160 KiB of LDS: raise their dynamic-LDS limit on THIS device
     HIP_TRY(hipFuncSetAttribute((const void *)k_conv_f16_halo<128, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), YOLO2_ERROR);
     HIP_TRY(hipFuncSetAttribute((const void *)k_conv_f16_halo<256, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), YOLO2_ERROR);
@@ -252,16 +250,16 @@ static int load_fp32_common(yolo2_hip_ctx *c, const void *weights_reorg, size_t 
     HIP_TRY(hipFuncSetAttribute((const void *)k_gemm1_f16_p<256, 128, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), YOLO2_ERROR);
     HIP_TRY(hipFuncSetAttribute((const void *)k_gemm1_f16_p<128, 256, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), YOLO2_ERROR);
     HIP_TRY(hipFuncSetAttribute((const void *)k_gemm1_f16_p<256, 256, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), YOLO2_ERROR);
-    if (!c->w0f) HIP_TRY(hipMalloc((void **)&c->w0f, (27 * 32 + 32) * sizeof(float)), YOLO2_MMAP_ERROR);
+    if (!c->w0f && (rc = y2_alloc_owned(c->w0f_own, c->w0f, 27 * 32 + 32))) return rc;
     hipLaunchKernelGGL(k_pack_w0_f32, dim3(4), dim3(256), 0, nullptr, wd, bd, c->w0f, c->w0f + 27 * 32);
     HIP_TRY(hipGetLastError(), YOLO2_ERROR);
     HIP_TRY(hipDeviceSynchronize(), YOLO2_ERROR);
     // the fp32 blobs stay resident (204 MB of 288 GB): yolo2_hip_run_frame_fp32_host consumes them as they are
-    if (c->wpkf) (void)hipFree(c->wpkf);         // the tiled fp32 path re-packs from the new blobs at its next run
-    if (c->biasf32_pk) (void)hipFree(c->biasf32_pk);
+    c->wpkf_own.reset();         // the tiled fp32 path re-packs from the new blobs at its next run
+    c->biasf32_pk_own.reset();
     c->wpkf = c->biasf32_pk = nullptr;
-    if (c->wf32) (void)hipFree(c->wf32);
-    if (c->bf32) (void)hipFree(c->bf32);
+    c->wf32_own = std::move(wd_own);
+    c->bf32_own = std::move(bd_own);
     c->wf32 = wd;
     c->bf32 = bd;
     c->f16_loaded = true;
@@ -272,7 +270,8 @@ static int alloc_half(yolo2_hip_ctx::HalfTensor &t, int C, int Cp, int H, int W,
 {
     t.C = C; t.Cp = Cp; t.H = H; t.W = W; t.Wp = W + 1; t.PL = (H + 1) * t.Wp; t.B = B;
     t.items = (size_t)kLead + (size_t)B * t.PL + kTail;
-    HIP_TRY(hipMalloc((void **)&t.d, t.items * Cp * 2), YOLO2_MMAP_ERROR);
+    const int rc = y2_alloc_owned(t.own, t.d, t.items * Cp);
+    if (rc) return rc;
     HIP_TRY(hipMemset(t.d, 0, t.items * Cp * 2), YOLO2_DMA_ERROR);  // zeros = conv padding and channel padding
     return YOLO2_SUCCESS;
 }
@@ -280,7 +279,7 @@ static int alloc_half(yolo2_hip_ctx::HalfTensor &t, int C, int Cp, int H, int W,
 static int ensure_f16_batch(yolo2_hip_ctx *c, int B)
 {
     if (c->f16_batch == B) return YOLO2_SUCCESS;
-    y2_free_f16_activations(c);
+    y2_free_tensors(c->h_in, c->h_out, c->h_cat, c->f16_batch);
     if (c->f16_plan) { c->f16_plan->batch = 0; c->f16_plan->steps.clear(); }   // the table points into the tensors just freed
     int rc;
     if ((rc = alloc_half(c->h_cat, 1280, item_halves(1280, c->split), 13, 13, B))) return rc;
@@ -292,8 +291,8 @@ static int ensure_f16_batch(yolo2_hip_ctx *c, int B)
             if ((rc = alloc_half(c->h_out[i], l.c, item_halves(l.c, c->split), l.h / 2, l.w / 2, B))) return rc;
         }
     }
-    c->h_out[24] = c->h_cat;
-    c->h_out[27] = c->h_cat;
+    y2_view_of(c->h_out[24], c->h_cat);
+    y2_view_of(c->h_out[27], c->h_cat);
     c->f16_batch = B;
     // the zero fills above run on the null stream; the pass may be enqueued on a non-blocking stream (the lanes'
     // are), which does not order itself behind it
@@ -850,7 +849,6 @@ static int ensure_tol_twin(yolo2_hip_ctx *c)
     t->device = c->device;
     t->opt = c->opt;
     t->split = true;
-    t->borrows_f32 = true;
     t->w0f = c->w0f; t->wf32 = c->wf32; t->bf32 = c->bf32;
     int rc = pack_half_weights(t, c->wf32, c->bf32);
     if (rc == YOLO2_SUCCESS && hipDeviceSynchronize() != hipSuccess) rc = fail(YOLO2_ERROR, "split weight packing failed");
@@ -875,20 +873,7 @@ extern "C" int yolo2_hip_run_batch_f32tol(yolo2_hip_ctx *c, uint64_t frames_dev,
 
 extern "C" int yolo2_hip_run_batch_f32tol_host(yolo2_hip_ctx *c, const float *frames, int batch, float *region)
 {
-    if (!c || !frames || !region) return fail(YOLO2_ERROR, "null argument");
-    HIP_TRY(hipSetDevice(c->device), YOLO2_INIT_ERROR);
-    float *fd = nullptr, *rd = nullptr;
-    HIP_TRY(hipMalloc((void **)&fd, (size_t)batch * YOLO2_FRAME_ELEMS * 4), YOLO2_MMAP_ERROR);
-    HIP_TRY(hipMalloc((void **)&rd, (size_t)batch * YOLO2_REGION_ELEMS * 4), YOLO2_MMAP_ERROR);
-    HIP_TRY(hipMemcpy(fd, frames, (size_t)batch * YOLO2_FRAME_ELEMS * 4, hipMemcpyHostToDevice), YOLO2_DMA_ERROR);
-    int rc = yolo2_hip_run_batch_f32tol(c, (uint64_t)(uintptr_t)fd, batch, (uint64_t)(uintptr_t)rd, nullptr);
-    if (rc == YOLO2_SUCCESS) {
-        hipError_t e = hipMemcpy(region, rd, (size_t)batch * YOLO2_REGION_ELEMS * 4, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = fail(YOLO2_DMA_ERROR, "D2H of region tensor failed: %s", hipGetErrorString(e));
-    }
-    (void)hipFree(fd);
-    (void)hipFree(rd);
-    return rc;
+    return y2_run_batch_host(c, frames, batch, region, [&](uint64_t fd, uint64_t rd) { return yolo2_hip_run_batch_f32tol(c, fd, batch, rd, nullptr); });
 }
 
 // Kernel the split-mode table runs for layer `layer_idx` (after the first yolo2_hip_run_batch_f32tol at this batch); "" if none.
@@ -955,20 +940,7 @@ extern "C" int yolo2_hip_debug_stamps(unsigned long long *dst, int n_wg)
 
 extern "C" int yolo2_hip_run_batch_fp16_host(yolo2_hip_ctx *c, const float *frames, int batch, float *region)
 {
-    if (!c || !frames || !region) return fail(YOLO2_ERROR, "null argument");
-    HIP_TRY(hipSetDevice(c->device), YOLO2_INIT_ERROR);
-    float *fd = nullptr, *rd = nullptr;
-    HIP_TRY(hipMalloc((void **)&fd, (size_t)batch * YOLO2_FRAME_ELEMS * 4), YOLO2_MMAP_ERROR);
-    HIP_TRY(hipMalloc((void **)&rd, (size_t)batch * YOLO2_REGION_ELEMS * 4), YOLO2_MMAP_ERROR);
-    HIP_TRY(hipMemcpy(fd, frames, (size_t)batch * YOLO2_FRAME_ELEMS * 4, hipMemcpyHostToDevice), YOLO2_DMA_ERROR);
-    int rc = yolo2_hip_run_batch_fp16(c, (uint64_t)(uintptr_t)fd, batch, (uint64_t)(uintptr_t)rd, nullptr);
-    if (rc == YOLO2_SUCCESS) {
-        hipError_t e = hipMemcpy(region, rd, (size_t)batch * YOLO2_REGION_ELEMS * 4, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = fail(YOLO2_DMA_ERROR, "D2H of region tensor failed: %s", hipGetErrorString(e));
-    }
-    (void)hipFree(fd);
-    (void)hipFree(rd);
-    return rc;
+    return y2_run_batch_host(c, frames, batch, region, [&](uint64_t fd, uint64_t rd) { return yolo2_hip_run_batch_fp16(c, fd, batch, rd, nullptr); });
 }
 
 // ---------------------------------------------------------------------------- the images entries' pass (yolo2_hip.hip)

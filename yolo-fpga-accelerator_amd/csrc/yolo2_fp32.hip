@@ -34,23 +34,19 @@ extern "C" int yolo2_hip_run_frame_fp32_host(yolo2_hip_ctx *c, const float *fram
     if (!c->f16_loaded || !c->wf32) return fail(YOLO2_ERROR, "fp32 weights not loaded (yolo2_hip_load_weights_fp32)");
     HIP_TRY(hipSetDevice(c->device), YOLO2_INIT_ERROR);
     auto w8 = [](int w) { return (w + 7) & ~7; };
+    Y2DevBuf<float> own[32], in0_own, cat_own;   // own[i]: layer i's tensor where it has one of its own (24 and 27 live in cat)
     float *bufs[32] = {nullptr};
-    float *in0 = nullptr, *cat = nullptr;
     int rc = YOLO2_SUCCESS;
-    auto release = [&]() {
-        (void)hipDeviceSynchronize();
-        for (int i = 0; i < 32; ++i)
-            if (bufs[i] && i != 24 && i != 27) (void)hipFree(bufs[i]);
-        (void)hipFree(in0); (void)hipFree(cat);
-    };
-    auto dalloc = [&](float **p, size_t elems) -> bool {
-        if (hipMalloc((void **)p, elems * sizeof(float)) != hipSuccess || hipMemsetAsync(*p, 0, elems * sizeof(float), nullptr) != hipSuccess) {
+    auto release = [&]() { (void)hipDeviceSynchronize(); };   // before the owners free the buffers the kernels use
+    auto dalloc = [&](Y2DevBuf<float> &o, size_t elems) -> float * {
+        if (o.alloc(elems) || hipMemsetAsync(o.get(), 0, elems * sizeof(float), nullptr) != hipSuccess) {
             rc = fail(YOLO2_MMAP_ERROR, "fp32 pass: activation buffer allocation failed");
-            return false;
+            return nullptr;
         }
-        return true;
+        return o.get();
     };
-    if (!dalloc(&in0, (size_t)3 * 416 * 416) || !dalloc(&cat, (size_t)1280 * 13 * 16)) { release(); return rc; }
+    float *const in0 = dalloc(in0_own, (size_t)3 * 416 * 416), *const cat = in0 ? dalloc(cat_own, (size_t)1280 * 13 * 16) : nullptr;
+    if (!in0 || !cat) { release(); return rc; }
     if (hipMemcpyAsync(in0, frame, (size_t)3 * 416 * 416 * sizeof(float), hipMemcpyHostToDevice, nullptr) != hipSuccess) {
         release();
         return fail(YOLO2_DMA_ERROR, "H2D of the frame failed");
@@ -67,7 +63,7 @@ extern "C" int yolo2_hip_run_frame_fp32_host(yolo2_hip_ctx *c, const float *fram
             const float *src = i == 26 ? bufs[16] : (i == 29 ? cat : cur);
             float *dst = nullptr;
             if (i == 24) dst = cat + (size_t)256 * 13 * 16;
-            else if (!dalloc(&dst, (size_t)l.n * oh * w8(ow))) break;
+            else if (!(dst = dalloc(own[i], (size_t)l.n * oh * w8(ow)))) break;
             hipLaunchKernelGGL(k_conv_ref_f32, dim3(blocks_for((long)l.n * oh * ow, 256)), dim3(256), 0, nullptr, src, dst,
                                (const float *)(c->wf32 + woff), (const float *)(c->bf32 + boff), l.c, l.n, l.size, 1, l.w, l.h, ow, oh,
                                pad, l.leaky);
@@ -79,8 +75,8 @@ extern "C" int yolo2_hip_run_frame_fp32_host(yolo2_hip_ctx *c, const float *fram
             break;
         }
         case L_MAX: {
-            float *dst = nullptr;
-            if (!dalloc(&dst, (size_t)l.c * oh * w8(ow))) break;
+            float *const dst = dalloc(own[i], (size_t)l.c * oh * w8(ow));
+            if (!dst) break;
             hipLaunchKernelGGL((k_pool_ref<float>), dim3(blocks_for((long)l.c * oh * ow, 256)), dim3(256), 0, nullptr, cur, dst, l.c, 2, 2,
                                l.w, l.h, ow, oh, -1024.f * 1024.f);   // pad value of core_compute.cpp:291, core_io.cpp:101
             bufs[i] = dst;
@@ -113,7 +109,8 @@ extern "C" int yolo2_hip_run_frame_fp32_host(yolo2_hip_ctx *c, const float *fram
 static int alloc_ftensor(yolo2_hip_ctx::FTensor &t, int C, int H, int W, int B)
 {
     t.g = make_geom(C, H, W, B);
-    HIP_TRY(hipMalloc((void **)&t.d, (size_t)t.g.items * 16), YOLO2_MMAP_ERROR);
+    const int rc = y2_alloc_owned(t.own, t.d, (size_t)t.g.items);
+    if (rc) return rc;
     HIP_TRY(hipMemset(t.d, 0, (size_t)t.g.items * 16), YOLO2_DMA_ERROR);   // +0.0f: the conv padding and the 4th lane of the input
     return YOLO2_SUCCESS;
 }
@@ -189,8 +186,8 @@ static int ensure_f32_path(yolo2_hip_ctx *c, int B)
                 btot += (long)((kNet[i].n + 31) / 32) * 32;
                 ord++;
             }
-        HIP_TRY(hipMalloc((void **)&c->wpkf, (size_t)wtot * 4), YOLO2_MMAP_ERROR);
-        HIP_TRY(hipMalloc((void **)&c->biasf32_pk, (size_t)btot * 4), YOLO2_MMAP_ERROR);
+        int arc;
+        if ((arc = y2_alloc_owned(c->wpkf_own, c->wpkf, (size_t)wtot)) || (arc = y2_alloc_owned(c->biasf32_pk_own, c->biasf32_pk, (size_t)btot))) return arc;
         HIP_TRY(hipMemset(c->biasf32_pk, 0, (size_t)btot * 4), YOLO2_DMA_ERROR);
         long woff = 0, boff = 0;
         ord = 0;
@@ -210,7 +207,7 @@ static int ensure_f32_path(yolo2_hip_ctx *c, int B)
         HIP_TRY(hipDeviceSynchronize(), YOLO2_ERROR);
     }
     if (c->f32_batch == B) return YOLO2_SUCCESS;
-    y2_free_f32_activations(c);
+    y2_free_tensors(c->f_in, c->f_out, c->f_cat, c->f32_batch);
     int rc;
     if ((rc = alloc_ftensor(c->f_in, 3, 416, 416, B))) return rc;
     if ((rc = alloc_ftensor(c->f_cat, 1280, 13, 13, B))) return rc;
@@ -222,8 +219,8 @@ static int ensure_f32_path(yolo2_hip_ctx *c, int B)
             if ((rc = alloc_ftensor(c->f_out[i], l.c, l.h / 2, l.w / 2, B))) return rc;
         }
     }
-    c->f_out[24] = c->f_cat;
-    c->f_out[27] = c->f_cat;
+    y2_view_of(c->f_out[24], c->f_cat);
+    y2_view_of(c->f_out[27], c->f_cat);
     c->f32_batch = B;
     // pixels per lane: timed once per layer (the arithmetic does not depend on it)
     const int fp = c->opt.f32_p;   // test hook: 1 / 2 / 4 for every layer (0: timed)
@@ -321,18 +318,5 @@ extern "C" int yolo2_hip_run_batch_fp32(yolo2_hip_ctx *c, uint64_t frames_dev, i
 
 extern "C" int yolo2_hip_run_batch_fp32_host(yolo2_hip_ctx *c, const float *frames, int batch, float *region)
 {
-    if (!c || !frames || !region) return fail(YOLO2_ERROR, "null argument");
-    HIP_TRY(hipSetDevice(c->device), YOLO2_INIT_ERROR);
-    float *fd = nullptr, *rd = nullptr;
-    HIP_TRY(hipMalloc((void **)&fd, (size_t)batch * YOLO2_FRAME_ELEMS * 4), YOLO2_MMAP_ERROR);
-    HIP_TRY(hipMalloc((void **)&rd, (size_t)batch * YOLO2_REGION_ELEMS * 4), YOLO2_MMAP_ERROR);
-    HIP_TRY(hipMemcpy(fd, frames, (size_t)batch * YOLO2_FRAME_ELEMS * 4, hipMemcpyHostToDevice), YOLO2_DMA_ERROR);
-    int rc = yolo2_hip_run_batch_fp32(c, (uint64_t)(uintptr_t)fd, batch, (uint64_t)(uintptr_t)rd, nullptr);
-    if (rc == YOLO2_SUCCESS) {
-        hipError_t e = hipMemcpy(region, rd, (size_t)batch * YOLO2_REGION_ELEMS * 4, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = fail(YOLO2_DMA_ERROR, "D2H of region tensor failed: %s", hipGetErrorString(e));
-    }
-    (void)hipFree(fd);
-    (void)hipFree(rd);
-    return rc;
+    return y2_run_batch_host(c, frames, batch, region, [&](uint64_t fd, uint64_t rd) { return yolo2_hip_run_batch_fp32(c, fd, batch, rd, nullptr); });
 }

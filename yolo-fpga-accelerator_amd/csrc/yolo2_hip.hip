@@ -90,14 +90,13 @@ extern "C" int yolo2_hip_layer_desc(int i, int desc[9])
 
 // ---------------------------------------------------------------------------- HBM helpers
 
-int y2_ensure(void **p, size_t *cap, size_t need)
+std::atomic<size_t> y2_live_bytes[2];
+
+extern "C" int yolo2_hip_debug_live_bytes(size_t *device_bytes, size_t *pinned_bytes)
 {
-    if (*cap >= need) return YOLO2_SUCCESS;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    HIP_TRY(hipMalloc(p, need), YOLO2_MMAP_ERROR);
-    *cap = need;
+    if (!device_bytes || !pinned_bytes) return fail(YOLO2_ERROR, "null argument");
+    *device_bytes = y2_live_bytes[0];
+    *pinned_bytes = y2_live_bytes[1];
     return YOLO2_SUCCESS;
 }
 
@@ -151,42 +150,10 @@ extern "C" int yolo2_hip_ctx_device(yolo2_hip_ctx *c) { return c ? c->device : -
 
 void y2_free_activations(yolo2_hip_ctx *c)
 {
-    if (c->ks_trip) (void)hipFree(c->ks_trip);
+    c->ks_trip_own.reset();
     c->ks_trip = nullptr;
     c->ks_trip_bytes = 0;
-    if (c->t_in.d) (void)hipFree(c->t_in.d);
-    c->t_in.d = nullptr;
-    if (c->t_cat.d) (void)hipFree(c->t_cat.d);
-    c->t_cat.d = nullptr;
-    for (int i = 0; i < 32; ++i) {
-        if (c->t_out[i].d && i != 24 && i != 27) (void)hipFree(c->t_out[i].d);
-        c->t_out[i].d = nullptr;
-    }
-    c->batch = 0;
-}
-
-void y2_free_f16_activations(yolo2_hip_ctx *c)
-{
-    if (c->h_in.d) (void)hipFree(c->h_in.d);
-    if (c->h_cat.d) (void)hipFree(c->h_cat.d);
-    c->h_in.d = c->h_cat.d = nullptr;
-    for (int i = 0; i < 32; ++i) {
-        if (c->h_out[i].d && i != 24 && i != 27) (void)hipFree(c->h_out[i].d);
-        c->h_out[i].d = nullptr;
-    }
-    c->f16_batch = 0;
-}
-
-void y2_free_f32_activations(yolo2_hip_ctx *c)
-{
-    if (c->f_in.d) (void)hipFree(c->f_in.d);
-    if (c->f_cat.d) (void)hipFree(c->f_cat.d);
-    c->f_in.d = c->f_cat.d = nullptr;
-    for (int i = 0; i < 32; ++i) {
-        if (c->f_out[i].d && i != 24 && i != 27) (void)hipFree(c->f_out[i].d);
-        c->f_out[i].d = nullptr;
-    }
-    c->f32_batch = 0;
+    y2_free_tensors(c->t_in, c->t_out, c->t_cat, c->batch);
 }
 
 void y2_destroy_lanes(yolo2_hip_ctx *c)
@@ -200,15 +167,6 @@ void y2_destroy_lanes(yolo2_hip_ctx *c)
 static void pipe_free(PipeBufs &p)
 {
     for (int k = 0; k < 2; ++k) {
-        y2_post_free(&p.post[k]);
-        if (p.hgeom[k]) (void)hipHostFree(p.hgeom[k]);
-        if (p.hdets[k]) (void)hipHostFree(p.hdets[k]);
-        if (p.hcounts[k]) (void)hipHostFree(p.hcounts[k]);
-        if (p.hin[k]) (void)hipHostFree(p.hin[k]);
-        if (p.hout[k]) (void)hipHostFree(p.hout[k]);
-        if (p.hregf[k]) (void)hipHostFree(p.hregf[k]);
-        (void)hipFree(p.dregf[k]);
-        (void)hipFree(p.dbytes[k]); (void)hipFree(p.din[k]); (void)hipFree(p.dout[k]);
         if (p.e_in[k]) (void)hipEventDestroy(p.e_in[k]);
         if (p.e_run[k]) (void)hipEventDestroy(p.e_run[k]);
         if (p.e_out[k]) (void)hipEventDestroy(p.e_out[k]);
@@ -217,7 +175,7 @@ static void pipe_free(PipeBufs &p)
     if (p.s_in) (void)hipStreamDestroy(p.s_in);
     if (p.s_run) (void)hipStreamDestroy(p.s_run);
     if (p.s_out) (void)hipStreamDestroy(p.s_out);
-    p = PipeBufs();
+    p = PipeBufs();   // (its owners free the buffers)
 }
 
 // need_hout: the pinned mirror of the region tensor (the entries that return region tensors; the images -> detections entry
@@ -225,18 +183,16 @@ static void pipe_free(PipeBufs &p)
 static int pipe_ensure(PipeBufs &p, size_t host_in, size_t dev_in, int batch, bool need_hout = true)
 {
     if (p.s_in && p.host_in >= host_in && p.dev_in >= dev_in && p.batch >= batch && (!need_hout || p.hout[0])) return YOLO2_SUCCESS;
-    need_hout = need_hout || p.hout[0] != nullptr;
+    need_hout = need_hout || p.hout[0];
     host_in = std::max(host_in, p.host_in);
     dev_in = std::max(dev_in, p.dev_in);
     batch = std::max(batch, p.batch);
     pipe_free(p);
-    const size_t fbytes = (size_t)batch * YOLO2_FRAME_ELEMS * sizeof(float), rbytes = (size_t)batch * YOLO2_REGION_ELEMS * sizeof(int16_t);
+    const size_t felems = (size_t)batch * YOLO2_FRAME_ELEMS, relems = (size_t)batch * YOLO2_REGION_ELEMS;
     bool ok = true;
     for (int k = 0; k < 2 && ok; ++k) {
-        ok = hipHostMalloc((void **)&p.hin[k], host_in, hipHostMallocDefault) == hipSuccess &&
-             (!need_hout || hipHostMalloc((void **)&p.hout[k], rbytes, hipHostMallocDefault) == hipSuccess) &&
-             (dev_in == 0 || hipMalloc((void **)&p.dbytes[k], dev_in) == hipSuccess) &&
-             hipMalloc((void **)&p.din[k], fbytes) == hipSuccess && hipMalloc((void **)&p.dout[k], rbytes) == hipSuccess &&
+        ok = p.hin[k].alloc(host_in) == YOLO2_SUCCESS && (!need_hout || p.hout[k].alloc(relems) == YOLO2_SUCCESS) &&
+             p.dbytes[k].alloc(dev_in) == YOLO2_SUCCESS && p.din[k].alloc(felems) == YOLO2_SUCCESS && p.dout[k].alloc(relems) == YOLO2_SUCCESS &&
              hipEventCreateWithFlags(&p.e_in[k], hipEventDisableTiming) == hipSuccess &&
              hipEventCreateWithFlags(&p.e_run[k], hipEventDisableTiming) == hipSuccess &&
              hipEventCreateWithFlags(&p.e_out[k], hipEventDisableTiming) == hipSuccess;
@@ -289,28 +245,10 @@ extern "C" void yolo2_hip_destroy(yolo2_hip_ctx *c)
     c->f16_lanes.clear();
     if (c->tol) yolo2_hip_destroy(c->tol);
     c->tol = nullptr;
-    if (c->is_lane) {   // packed weights and biases belong to the parent
-        c->wpk = nullptr;
-        c->bias_pk = nullptr;
-        c->wh = nullptr; c->biasf = nullptr; c->w0f = nullptr; c->wf32 = nullptr; c->bf32 = nullptr;
-    }
-    if (c->borrows_f32) { c->w0f = nullptr; c->wf32 = nullptr; c->bf32 = nullptr; }   // the split-mode twin: its wh / biasf are its own
-    y2_free_f16_activations(c);
-    y2_free_f32_activations(c);
-    if (c->wpkf) (void)hipFree(c->wpkf);
-    if (c->biasf32_pk) (void)hipFree(c->biasf32_pk);
-    if (c->wh) (void)hipFree(c->wh);
-    if (c->biasf) (void)hipFree(c->biasf);
-    if (c->w0f) (void)hipFree(c->w0f);
-    if (c->wf32) (void)hipFree(c->wf32);
-    if (c->bf32) (void)hipFree(c->bf32);
-    if (c->wpk) (void)hipFree(c->wpk);
-    if (c->bias_pk) (void)hipFree(c->bias_pk);
-    if (c->mb_lists) (void)hipFree(c->mb_lists);
     if (c->ev_made)
         for (auto &slot : c->ev)
             for (auto &e : slot) (void)hipEventDestroy(e);
-    delete c;
+    delete c;   // the owners free what this context allocated; what it borrowed (a lane's, the twin's views) stays with the parent
 }
 
 // ---------------------------------------------------------------------------- lanes / profiling accessors
@@ -477,9 +415,9 @@ static int run_images_i16_host(yolo2_hip_ctx *c, const uint8_t *const *images, c
     int rc = pipe_ensure(c->pipe, cap, cap, batch);
     if (rc) return rc;
     PipeBufs &P = c->pipe;
-    uint8_t **hin = P.hin, **dbytes = P.dbytes;
-    float **din = P.din;
-    int16_t **hout = P.hout, **dout = P.dout;
+    uint8_t *hin[2] = {P.hin[0].get(), P.hin[1].get()}, *dbytes[2] = {P.dbytes[0].get(), P.dbytes[1].get()};
+    float *din[2] = {P.din[0].get(), P.din[1].get()};
+    int16_t *hout[2] = {P.hout[0].get(), P.hout[1].get()}, *dout[2] = {P.dout[0].get(), P.dout[1].get()};
     hipStream_t s_in = P.s_in, s_run = P.s_run, s_out = P.s_out;
     hipEvent_t *e_in = P.e_in, *e_run = P.e_run, *e_out = P.e_out;
     auto cleanup = [&]() { (void)hipDeviceSynchronize(); };
@@ -559,16 +497,11 @@ static int pipe_ensure_post(yolo2_hip_ctx *c, int batch, int cap)
     batch = std::max(batch, p.post_batch);
     cap = std::max(cap, p.post_cap);
     for (int k = 0; k < 2; ++k) {
-        if (p.hgeom[k]) (void)hipHostFree(p.hgeom[k]);
-        if (p.hdets[k]) (void)hipHostFree(p.hdets[k]);
-        if (p.hcounts[k]) (void)hipHostFree(p.hcounts[k]);
-        p.hgeom[k] = nullptr; p.hdets[k] = nullptr; p.hcounts[k] = nullptr;
+        p.hgeom[k].reset(); p.hdets[k].reset(); p.hcounts[k].reset();
         p.post_batch = p.post_cap = 0;
         const int rc = y2_post_alloc(c->device, batch, cap, &p.post[k]);
         if (rc) return rc;
-        if (hipHostMalloc((void **)&p.hgeom[k], (size_t)batch * y2_post_geom_bytes(), hipHostMallocDefault) != hipSuccess ||
-            hipHostMalloc((void **)&p.hdets[k], (size_t)batch * cap * sizeof(yolo2_hip_det), hipHostMallocDefault) != hipSuccess ||
-            hipHostMalloc((void **)&p.hcounts[k], (size_t)batch * sizeof(int), hipHostMallocDefault) != hipSuccess) {
+        if (p.hgeom[k].alloc((size_t)batch * y2_post_geom_bytes()) || p.hdets[k].alloc((size_t)batch * cap) || p.hcounts[k].alloc((size_t)batch)) {
             (void)hipGetLastError();
             return fail(YOLO2_MMAP_ERROR, "pinned buffers for %d frames x %d detection records could not be allocated", batch, cap);
         }
@@ -617,11 +550,11 @@ static int run_images_i16_dets(yolo2_hip_ctx *c, const uint8_t *const *images, c
     auto drain = [&](int k) {
         const int b = k & 1, nf = in_chunk(k);
         (void)hipEventSynchronize(P.e_out[b]);
-        memcpy(counts + (size_t)k * batch, P.hcounts[b], (size_t)nf * sizeof(int));
+        memcpy(counts + (size_t)k * batch, P.hcounts[b].get(), (size_t)nf * sizeof(int));
         for (int f = 0; f < nf; ++f) {   // frame numbers are global in the caller's records
-            const int cnt = std::min(P.hcounts[b][f], cap);
+            const int cnt = std::min(P.hcounts[b].get()[f], cap);
             yolo2_hip_det *dst = dets + ((size_t)k * batch + f) * cap;
-            memcpy(dst, P.hdets[b] + (size_t)f * cap, (size_t)cnt * sizeof(yolo2_hip_det));
+            memcpy(dst, P.hdets[b].get() + (size_t)f * cap, (size_t)cnt * sizeof(yolo2_hip_det));
             for (int r = 0; r < cnt; ++r) dst[r].frame = k * batch + f;
         }
     };
@@ -634,11 +567,11 @@ static int run_images_i16_dets(yolo2_hip_ctx *c, const uint8_t *const *images, c
         size_t off = table_bytes;
         for (int i = 0; i < nf; ++i) {
             const size_t bytes = (size_t)widths[first + i] * heights[first + i] * channels;
-            memcpy(P.hin[b] + off, images[first + i], bytes);
+            memcpy(P.hin[b].get() + off, images[first + i], bytes);
             offs[(size_t)i] = off;
             off += padded(bytes);
         }
-        LetterboxItem *items = reinterpret_cast<LetterboxItem *>(P.hin[b]);
+        LetterboxItem *items = reinterpret_cast<LetterboxItem *>(P.hin[b].get());
         for (int f = 0; f < batch; ++f) {   // a partial last chunk repeats its last image
             const int i = std::min(f, nf - 1);
             cw[(size_t)f] = widths[first + i]; chh[(size_t)f] = heights[first + i];
@@ -646,12 +579,12 @@ static int run_images_i16_dets(yolo2_hip_ctx *c, const uint8_t *const *images, c
             if ((rc = letterbox_args(widths[first + i], heights[first + i], channels, 416, 416, items[f].a, pix))) break;
         }
         if (rc) break;
-        if ((rc = y2_post_fill_geom(P.hgeom[b], cw.data(), chh.data(), batch))) break;
-        Y2_TRY(hipMemcpyAsync(P.dbytes[b], P.hin[b], off, hipMemcpyHostToDevice, P.s_in), YOLO2_DMA_ERROR);
-        Y2_TRY(hipMemcpyAsync(P.post[b].geom, P.hgeom[b], (size_t)batch * gbytes, hipMemcpyHostToDevice, P.s_in), YOLO2_DMA_ERROR);
+        if ((rc = y2_post_fill_geom(P.hgeom[b].get(), cw.data(), chh.data(), batch))) break;
+        Y2_TRY(hipMemcpyAsync(P.dbytes[b].get(), P.hin[b].get(), off, hipMemcpyHostToDevice, P.s_in), YOLO2_DMA_ERROR);
+        Y2_TRY(hipMemcpyAsync(P.post[b].geom.get(), P.hgeom[b].get(), (size_t)batch * gbytes, hipMemcpyHostToDevice, P.s_in), YOLO2_DMA_ERROR);
         Y2_TRY(hipEventRecord(P.e_in[b], P.s_in), YOLO2_ERROR);
         Y2_TRY(hipStreamWaitEvent(P.s_run, P.e_in[b], 0), YOLO2_ERROR);
-        launch_letterbox_batch(channels == 2, P.dbytes[b], P.din[b], batch, P.s_run);
+        launch_letterbox_batch(channels == 2, P.dbytes[b].get(), P.din[b].get(), batch, P.s_run);
         Y2_TRY(hipGetLastError(), YOLO2_ERROR);
         // The network.  A chunk's lanes are NOT joined back into one stream here: consecutive chunks are independent, every lane
         // owns its activations and its stream keeps its chunks in order, so lane i starts chunk k + 1 the moment it has finished
@@ -667,14 +600,14 @@ static int run_images_i16_dets(yolo2_hip_ctx *c, const uint8_t *const *images, c
                 const uint64_t first = (uint64_t)c->lane_first[i];
                 if (!P.e_lane[b][i]) Y2_TRY(hipEventCreateWithFlags(&P.e_lane[b][i], hipEventDisableTiming), YOLO2_ERROR);
                 Y2_TRY(hipStreamWaitEvent(l->lane_stream, P.e_run[b], 0), YOLO2_ERROR);
-                rc = yolo2_hip_run_batch_int16(l, (uint64_t)(uintptr_t)(P.din[b] + first * YOLO2_FRAME_ELEMS), l->batch,
-                                               (uint64_t)(uintptr_t)(P.dout[b] + first * YOLO2_REGION_ELEMS), &q, l->lane_stream);
+                rc = yolo2_hip_run_batch_int16(l, (uint64_t)(uintptr_t)(P.din[b].get() + first * YOLO2_FRAME_ELEMS), l->batch,
+                                               (uint64_t)(uintptr_t)(P.dout[b].get() + first * YOLO2_REGION_ELEMS), &q, l->lane_stream);
                 if (rc) break;
                 Y2_TRY(hipEventRecord(P.e_lane[b][i], l->lane_stream), YOLO2_ERROR);
                 Y2_TRY(hipStreamWaitEvent(P.s_out, P.e_lane[b][i], 0), YOLO2_ERROR);
             }
         } else {
-            rc = yolo2_hip_run_batch_int16(c, (uint64_t)(uintptr_t)P.din[b], batch, (uint64_t)(uintptr_t)P.dout[b], &q, P.s_run);
+            rc = yolo2_hip_run_batch_int16(c, (uint64_t)(uintptr_t)P.din[b].get(), batch, (uint64_t)(uintptr_t)P.dout[b].get(), &q, P.s_run);
             if (rc) break;
             Y2_TRY(hipEventRecord(P.e_run[b], P.s_run), YOLO2_ERROR);
             Y2_TRY(hipStreamWaitEvent(P.s_out, P.e_run[b], 0), YOLO2_ERROR);
@@ -682,10 +615,10 @@ static int run_images_i16_dets(yolo2_hip_ctx *c, const uint8_t *const *images, c
         if (rc) break;
         // the step after the path, on the device that produced the tensor, straight from HBM - on the download stream, so that the
         // next chunk's letterbox and network need not wait for it (the tail is 64 workgroups for 0.7 ms: latency, not work)
-        rc = y2_post_enqueue_int16(c->device, P.dout[b], batch, q, thresh, nms, cap, best_only, &P.post[b], P.s_out);
+        rc = y2_post_enqueue_int16(c->device, P.dout[b].get(), batch, q, thresh, nms, cap, best_only, &P.post[b], P.s_out);
         if (rc) break;
-        Y2_TRY(hipMemcpyAsync(P.hcounts[b], P.post[b].counts, (size_t)batch * sizeof(int), hipMemcpyDeviceToHost, P.s_out), YOLO2_DMA_ERROR);
-        Y2_TRY(hipMemcpyAsync(P.hdets[b], P.post[b].dets, (size_t)batch * cap * sizeof(yolo2_hip_det), hipMemcpyDeviceToHost, P.s_out), YOLO2_DMA_ERROR);
+        Y2_TRY(hipMemcpyAsync(P.hcounts[b].get(), P.post[b].counts.get(), (size_t)batch * sizeof(int), hipMemcpyDeviceToHost, P.s_out), YOLO2_DMA_ERROR);
+        Y2_TRY(hipMemcpyAsync(P.hdets[b].get(), P.post[b].dets.get(), (size_t)batch * cap * sizeof(yolo2_hip_det), hipMemcpyDeviceToHost, P.s_out), YOLO2_DMA_ERROR);
         Y2_TRY(hipEventRecord(P.e_out[b], P.s_out), YOLO2_ERROR);
     }
     if (rc == YOLO2_SUCCESS) {
@@ -723,18 +656,13 @@ extern "C" int yolo2_hip_run_images_pix_dets(yolo2_hip_ctx *c, const uint8_t *co
 static int pipe_ensure_regf(PipeBufs &p, int batch, bool need_host)
 {
     if (p.regf_batch >= batch && (!need_host || p.hregf[0])) return YOLO2_SUCCESS;
-    need_host = need_host || p.hregf[0] != nullptr;
+    need_host = need_host || p.hregf[0];
     batch = std::max(batch, p.regf_batch);
-    const size_t rbytes = (size_t)batch * YOLO2_REGION_ELEMS * sizeof(float);
-    for (int k = 0; k < 2; ++k) {
-        if (p.hregf[k]) (void)hipHostFree(p.hregf[k]);
-        (void)hipFree(p.dregf[k]);
-        p.hregf[k] = nullptr; p.dregf[k] = nullptr;
-    }
+    const size_t relems = (size_t)batch * YOLO2_REGION_ELEMS;
+    for (int k = 0; k < 2; ++k) { p.hregf[k].reset(); p.dregf[k].reset(); }
     p.regf_batch = 0;
     for (int k = 0; k < 2; ++k)
-        if (hipMalloc((void **)&p.dregf[k], rbytes) != hipSuccess ||
-            (need_host && hipHostMalloc((void **)&p.hregf[k], rbytes, hipHostMallocDefault) != hipSuccess)) {
+        if (p.dregf[k].alloc(relems) || (need_host && p.hregf[k].alloc(relems))) {
             (void)hipGetLastError();
             return fail(YOLO2_MMAP_ERROR, "fp32 region buffers for %d frames could not be allocated", batch);
         }
@@ -807,14 +735,14 @@ static int run_images_f16(yolo2_hip_ctx *c, int split, const uint8_t *const *ima
         const int b = k & 1, nf = in_chunk(k);
         (void)hipEventSynchronize(P.e_out[b]);
         if (!want_dets) {
-            memcpy(region_host + (size_t)k * batch * YOLO2_REGION_ELEMS, P.hregf[b], (size_t)nf * YOLO2_REGION_ELEMS * sizeof(float));
+            memcpy(region_host + (size_t)k * batch * YOLO2_REGION_ELEMS, P.hregf[b].get(), (size_t)nf * YOLO2_REGION_ELEMS * sizeof(float));
             return;
         }
-        memcpy(counts + (size_t)k * batch, P.hcounts[b], (size_t)nf * sizeof(int));
+        memcpy(counts + (size_t)k * batch, P.hcounts[b].get(), (size_t)nf * sizeof(int));
         for (int f = 0; f < nf; ++f) {   // frame numbers are global in the caller's records
-            const int cnt = std::min(P.hcounts[b][f], cap);
+            const int cnt = std::min(P.hcounts[b].get()[f], cap);
             yolo2_hip_det *dst = dets + ((size_t)k * batch + f) * cap;
-            memcpy(dst, P.hdets[b] + (size_t)f * cap, (size_t)cnt * sizeof(yolo2_hip_det));
+            memcpy(dst, P.hdets[b].get() + (size_t)f * cap, (size_t)cnt * sizeof(yolo2_hip_det));
             for (int r = 0; r < cnt; ++r) dst[r].frame = k * batch + f;
         }
     };
@@ -829,8 +757,8 @@ static int run_images_f16(yolo2_hip_ctx *c, int split, const uint8_t *const *ima
             offs[(size_t)i] = off;
             off += padded(sizes[(size_t)i]);
         }
-        stage_images(P.hin[b], images + first, offs.data(), sizes.data(), nf);
-        LetterboxItem *items = reinterpret_cast<LetterboxItem *>(P.hin[b]);
+        stage_images(P.hin[b].get(), images + first, offs.data(), sizes.data(), nf);
+        LetterboxItem *items = reinterpret_cast<LetterboxItem *>(P.hin[b].get());
         for (int f = 0; f < batch; ++f) {   // a partial last chunk repeats its last image
             const int i = std::min(f, nf - 1);
             cw[(size_t)f] = widths[first + i]; chh[(size_t)f] = heights[first + i];
@@ -838,28 +766,28 @@ static int run_images_f16(yolo2_hip_ctx *c, int split, const uint8_t *const *ima
             if ((rc = letterbox_args(widths[first + i], heights[first + i], channels, 416, 416, items[f].a, pix))) break;
         }
         if (rc) break;
-        if (want_dets && (rc = y2_post_fill_geom(P.hgeom[b], cw.data(), chh.data(), batch))) break;
-        Y2_TRY(hipMemcpyAsync(P.dbytes[b], P.hin[b], off, hipMemcpyHostToDevice, P.s_in), YOLO2_DMA_ERROR);
-        if (want_dets) Y2_TRY(hipMemcpyAsync(P.post[b].geom, P.hgeom[b], (size_t)batch * gbytes, hipMemcpyHostToDevice, P.s_in), YOLO2_DMA_ERROR);
+        if (want_dets && (rc = y2_post_fill_geom(P.hgeom[b].get(), cw.data(), chh.data(), batch))) break;
+        Y2_TRY(hipMemcpyAsync(P.dbytes[b].get(), P.hin[b].get(), off, hipMemcpyHostToDevice, P.s_in), YOLO2_DMA_ERROR);
+        if (want_dets) Y2_TRY(hipMemcpyAsync(P.post[b].geom.get(), P.hgeom[b].get(), (size_t)batch * gbytes, hipMemcpyHostToDevice, P.s_in), YOLO2_DMA_ERROR);
         Y2_TRY(hipEventRecord(P.e_in[b], P.s_in), YOLO2_ERROR);
         Y2_TRY(hipStreamWaitEvent(P.s_run, P.e_in[b], 0), YOLO2_ERROR);
         if (fused) {
-            rc = y2_f16_run_images(run, P.dbytes[b], yuyv, batch, P.dregf[b], P.s_run);
+            rc = y2_f16_run_images(run, P.dbytes[b].get(), yuyv, batch, P.dregf[b].get(), P.s_run);
         } else {
-            launch_letterbox_batch(yuyv, P.dbytes[b], P.din[b], batch, P.s_run);
+            launch_letterbox_batch(yuyv, P.dbytes[b].get(), P.din[b].get(), batch, P.s_run);
             Y2_TRY(hipGetLastError(), YOLO2_ERROR);
-            rc = yolo2_hip_run_batch_fp16(run, (uint64_t)(uintptr_t)P.din[b], batch, (uint64_t)(uintptr_t)P.dregf[b], P.s_run);
+            rc = yolo2_hip_run_batch_fp16(run, (uint64_t)(uintptr_t)P.din[b].get(), batch, (uint64_t)(uintptr_t)P.dregf[b].get(), P.s_run);
         }
         if (rc) break;
         Y2_TRY(hipEventRecord(P.e_run[b], P.s_run), YOLO2_ERROR);
         Y2_TRY(hipStreamWaitEvent(P.s_out, P.e_run[b], 0), YOLO2_ERROR);
         if (want_dets) {   // the tail on the download stream, straight from HBM (see yolo2_hip_run_images_u8_dets)
-            if ((rc = y2_post_enqueue_f32(P.dregf[b], batch, thresh, nms, cap, best_only, &P.post[b], P.s_out))) break;
-            Y2_TRY(hipMemcpyAsync(P.hcounts[b], P.post[b].counts, (size_t)batch * sizeof(int), hipMemcpyDeviceToHost, P.s_out), YOLO2_DMA_ERROR);
-            Y2_TRY(hipMemcpyAsync(P.hdets[b], P.post[b].dets, (size_t)batch * cap * sizeof(yolo2_hip_det), hipMemcpyDeviceToHost, P.s_out),
+            if ((rc = y2_post_enqueue_f32(P.dregf[b].get(), batch, thresh, nms, cap, best_only, &P.post[b], P.s_out))) break;
+            Y2_TRY(hipMemcpyAsync(P.hcounts[b].get(), P.post[b].counts.get(), (size_t)batch * sizeof(int), hipMemcpyDeviceToHost, P.s_out), YOLO2_DMA_ERROR);
+            Y2_TRY(hipMemcpyAsync(P.hdets[b].get(), P.post[b].dets.get(), (size_t)batch * cap * sizeof(yolo2_hip_det), hipMemcpyDeviceToHost, P.s_out),
                    YOLO2_DMA_ERROR);
         } else {
-            Y2_TRY(hipMemcpyAsync(P.hregf[b], P.dregf[b], rbytes, hipMemcpyDeviceToHost, P.s_out), YOLO2_DMA_ERROR);
+            Y2_TRY(hipMemcpyAsync(P.hregf[b].get(), P.dregf[b].get(), rbytes, hipMemcpyDeviceToHost, P.s_out), YOLO2_DMA_ERROR);
         }
         Y2_TRY(hipEventRecord(P.e_out[b], P.s_out), YOLO2_ERROR);
     }
@@ -925,9 +853,8 @@ extern "C" int yolo2_hip_run_frames_int16(yolo2_hip_ctx *c, const float *frames,
     int rc = pipe_ensure(c->pipe, fbytes, 0, batch);
     if (rc) return rc;
     PipeBufs &P = c->pipe;
-    float *hin[2] = {(float *)P.hin[0], (float *)P.hin[1]};
-    float **din = P.din;
-    int16_t **hout = P.hout, **dout = P.dout;
+    float *hin[2] = {(float *)P.hin[0].get(), (float *)P.hin[1].get()}, *din[2] = {P.din[0].get(), P.din[1].get()};
+    int16_t *hout[2] = {P.hout[0].get(), P.hout[1].get()}, *dout[2] = {P.dout[0].get(), P.dout[1].get()};
     hipStream_t s_in = P.s_in, s_run = P.s_run, s_out = P.s_out;
     hipEvent_t *e_in = P.e_in, *e_run = P.e_run, *e_out = P.e_out;
     auto cleanup = [&]() { (void)hipDeviceSynchronize(); };

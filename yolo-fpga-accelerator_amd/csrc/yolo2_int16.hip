@@ -373,14 +373,14 @@ static int resolve_q(yolo2_hip_ctx *c)
                 c->wscale_mb[ord][(size_t)mb] = (signed char)want;
             }
             if (rescale && !c->is_lane) {   // lanes share the parent's packed weights (and reach the same decisions)
-                signed char *dd = nullptr;
-                HIP_TRY(hipMalloc((void **)&dd, (size_t)MB), YOLO2_MMAP_ERROR);
-                HIP_TRY(hipMemcpy(dd, delta.data(), (size_t)MB, hipMemcpyHostToDevice), YOLO2_DMA_ERROR);
+                Y2DevBuf<signed char> dd;
+                int arc;
+                if ((arc = dd.alloc((size_t)MB))) return arc;
+                HIP_TRY(hipMemcpy(dd.get(), delta.data(), (size_t)MB, hipMemcpyHostToDevice), YOLO2_DMA_ERROR);
                 const long per_mb = packed_weight_elems(l.c, l.n, l.size) / MB;
                 hipLaunchKernelGGL(k_scale_weight_blocks, dim3(std::min<unsigned>(blocks_for(per_mb, 256), 64), MB), dim3(256), 0,
-                                   nullptr, c->wpk + c->wpk_off[ord], per_mb, dd);
+                                   nullptr, c->wpk + c->wpk_off[ord], per_mb, dd.get());
                 HIP_TRY(hipDeviceSynchronize(), YOLO2_ERROR);
-                (void)hipFree(dd);
             }
             int dom = 0;
             for (int k = 0; k < 5; ++k) {
@@ -425,10 +425,9 @@ static int resolve_q(yolo2_hip_ctx *c)
         }
     }
     c->final_q = current_Qa;
-    if (c->mb_lists) (void)hipFree(c->mb_lists);
-    c->mb_lists = nullptr;
+    const int lrc = y2_alloc_owned(c->mb_lists_own, c->mb_lists, lists.size());
+    if (lrc) return lrc;
     if (!lists.empty()) {
-        HIP_TRY(hipMalloc((void **)&c->mb_lists, lists.size() * sizeof(int)), YOLO2_MMAP_ERROR);
         HIP_TRY(hipMemcpy(c->mb_lists, lists.data(), lists.size() * sizeof(int), hipMemcpyHostToDevice), YOLO2_DMA_ERROR);
         for (int i = 0; i < 32; ++i) {
             if (kNet[i].type != L_CONV || !c->plan[i].mb_count) continue;
@@ -458,12 +457,13 @@ static int weight_set_hash(const short *w_dev, const std::vector<short> &bias_ho
 {
     *out = 0;
     if ((uintptr_t)w_dev & 7) return YOLO2_SUCCESS;     // (a caller-owned device blob that is not 8-byte aligned: no hash, no cache)
-    unsigned long long *acc = nullptr, h = 0;
-    HIP_TRY(hipMalloc((void **)&acc, sizeof(*acc)), YOLO2_MMAP_ERROR);
-    HIP_TRY(hipMemsetAsync(acc, 0, sizeof(*acc), nullptr), YOLO2_DMA_ERROR);
-    hipLaunchKernelGGL(k_hash_words, dim3(2048), dim3(256), 0, nullptr, (const unsigned long long *)w_dev, (long)YOLO2_N_WEIGHTS / 4, acc);
-    HIP_TRY(hipMemcpy(&h, acc, sizeof(h), hipMemcpyDeviceToHost), YOLO2_DMA_ERROR);
-    (void)hipFree(acc);
+    Y2DevBuf<unsigned long long> acc;
+    unsigned long long h = 0;
+    const int arc = acc.alloc(1);
+    if (arc) return arc;
+    HIP_TRY(hipMemsetAsync(acc.get(), 0, sizeof(h), nullptr), YOLO2_DMA_ERROR);
+    hipLaunchKernelGGL(k_hash_words, dim3(2048), dim3(256), 0, nullptr, (const unsigned long long *)w_dev, (long)YOLO2_N_WEIGHTS / 4, acc.get());
+    HIP_TRY(hipMemcpy(&h, acc.get(), sizeof(h), hipMemcpyDeviceToHost), YOLO2_DMA_ERROR);
     uint64_t x = y2_hash_bytes(h ? h : 1, bias_host.data(), bias_host.size() * sizeof(short));
     const int sizes[3] = {(int)wq.size(), (int)bq.size(), (int)aq.size()};
     x = y2_hash_bytes(x, sizes, sizeof(sizes));
@@ -496,19 +496,18 @@ static int load_common(yolo2_hip_ctx *c, const short *w_dev, size_t n_weights, c
             btot += (long)((kNet[i].n + 31) / 32) * 32;
             ord++;
         }
-    if (c->wpk) (void)hipFree(c->wpk);
-    if (c->bias_pk) (void)hipFree(c->bias_pk);
+    int rc;
+    c->wpk_own.reset();
+    c->bias_pk_own.reset();
     c->wpk = c->bias_pk = nullptr;
-    HIP_TRY(hipMalloc((void **)&c->wpk, (size_t)wtot * 2), YOLO2_MMAP_ERROR);
-    HIP_TRY(hipMalloc((void **)&c->bias_pk, (size_t)btot * 2), YOLO2_MMAP_ERROR);
+    if ((rc = y2_alloc_owned(c->wpk_own, c->wpk, (size_t)wtot)) || (rc = y2_alloc_owned(c->bias_pk_own, c->bias_pk, (size_t)btot))) return rc;
     HIP_TRY(hipMemset(c->bias_pk, 0, (size_t)btot * 2), YOLO2_DMA_ERROR);
-    int *bound = nullptr, *bound_mb = nullptr, *bound_abs = nullptr;
+    Y2DevBuf<int> bound_own, bound_mb_own, bound_abs_own;
     int mb_total = 0;
     for (int i = 0; i < 32; ++i)
         if (kNet[i].type == L_CONV) mb_total += (kNet[i].n + 31) / 32;
-    HIP_TRY(hipMalloc((void **)&bound, sizeof(int) * YOLO2_N_CONV), YOLO2_MMAP_ERROR);
-    HIP_TRY(hipMalloc((void **)&bound_mb, sizeof(int) * mb_total), YOLO2_MMAP_ERROR);
-    HIP_TRY(hipMalloc((void **)&bound_abs, sizeof(int) * mb_total), YOLO2_MMAP_ERROR);
+    if ((rc = bound_own.alloc(YOLO2_N_CONV)) || (rc = bound_mb_own.alloc((size_t)mb_total)) || (rc = bound_abs_own.alloc((size_t)mb_total))) return rc;
+    int *const bound = bound_own.get(), *const bound_mb = bound_mb_own.get(), *const bound_abs = bound_abs_own.get();
     HIP_TRY(hipMemset(bound, 0, sizeof(int) * YOLO2_N_CONV), YOLO2_DMA_ERROR);
     int mb_off = 0;
     std::vector<int> mb_offs;
@@ -571,10 +570,8 @@ static int load_common(yolo2_hip_ctx *c, const short *w_dev, size_t n_weights, c
             // the bias bounds were recomputed from the blob above (host side, free): they must agree with the file
             if (pc->bounds[o].maxbias != c->maxbias[o] || pc->bounds[o].bias_mb != c->maxbias_mb[o]) bounds_cached = false;
         }
-        if (!bounds_cached) {   // same hash, other bounds: do not trust the file
-            (void)hipFree(bound); (void)hipFree(bound_mb); (void)hipFree(bound_abs);
+        if (!bounds_cached)   // same hash, other bounds: do not trust the file
             return load_common(c, w_dev, n_weights, b_dev, n_bias, weight_q, n_wq, bias_q, n_bq, act_q, n_aq, false);
-        }
     } else {
     HIP_TRY(hipMemcpy(c->maxsum, bound, sizeof(int) * YOLO2_N_CONV, hipMemcpyDeviceToHost), YOLO2_DMA_ERROR);
     {
@@ -591,13 +588,7 @@ static int load_common(yolo2_hip_ctx *c, const short *w_dev, size_t n_weights, c
             }
     }
     }
-    (void)hipFree(bound);
-    (void)hipFree(bound_mb);
-    (void)hipFree(bound_abs);
-    {
-        const int rq = resolve_q(c);
-        if (rq) return rq;
-    }
+    if ((rc = resolve_q(c))) return rc;
     if (pc) {
         std::lock_guard<std::mutex> lk(pc->mu);
         if (bounds_cached) {
@@ -651,15 +642,13 @@ extern "C" int yolo2_hip_load_weights_int16(yolo2_hip_ctx *c, const int16_t *wei
     if (n_weights < YOLO2_N_WEIGHTS) return fail(YOLO2_ERROR, "weights file too small");
     if (n_bias < YOLO2_N_BIAS) return fail(YOLO2_ERROR, "bias file too small");
     HIP_TRY(hipSetDevice(c->device), YOLO2_INIT_ERROR);
-    short *wd = nullptr, *bd = nullptr;
-    HIP_TRY(hipMalloc((void **)&wd, (size_t)YOLO2_N_WEIGHTS * 2), YOLO2_MMAP_ERROR);
-    HIP_TRY(hipMalloc((void **)&bd, (size_t)YOLO2_N_BIAS * 2), YOLO2_MMAP_ERROR);
-    HIP_TRY(hipMemcpy(wd, weights_reorg, (size_t)YOLO2_N_WEIGHTS * 2, hipMemcpyHostToDevice), YOLO2_DMA_ERROR);
-    HIP_TRY(hipMemcpy(bd, bias, (size_t)YOLO2_N_BIAS * 2, hipMemcpyHostToDevice), YOLO2_DMA_ERROR);
-    const int rc = load_common(c, wd, YOLO2_N_WEIGHTS, bd, YOLO2_N_BIAS, weight_q, n_weight_q, bias_q, n_bias_q, act_q, n_act_q);
-    (void)hipDeviceSynchronize();
-    (void)hipFree(wd);
-    (void)hipFree(bd);
+    Y2DevBuf<short> wd, bd;
+    int rc;
+    if ((rc = wd.alloc(YOLO2_N_WEIGHTS)) || (rc = bd.alloc(YOLO2_N_BIAS))) return rc;
+    HIP_TRY(hipMemcpy(wd.get(), weights_reorg, (size_t)YOLO2_N_WEIGHTS * 2, hipMemcpyHostToDevice), YOLO2_DMA_ERROR);
+    HIP_TRY(hipMemcpy(bd.get(), bias, (size_t)YOLO2_N_BIAS * 2, hipMemcpyHostToDevice), YOLO2_DMA_ERROR);
+    rc = load_common(c, wd.get(), YOLO2_N_WEIGHTS, bd.get(), YOLO2_N_BIAS, weight_q, n_weight_q, bias_q, n_bias_q, act_q, n_act_q);
+    (void)hipDeviceSynchronize();   // before the uploaded blobs are dropped
     return rc;
 }
 
@@ -685,7 +674,8 @@ extern "C" int yolo2_hip_layer_path_counts(yolo2_hip_ctx *c, int ord, int counts
 static int alloc_tensor(Tensor &t, int C, int H, int W, int B)
 {
     t.g = make_geom(C, H, W, B);
-    HIP_TRY(hipMalloc((void **)&t.d, (size_t)t.g.items * 8), YOLO2_MMAP_ERROR);
+    const int rc = y2_alloc_owned(t.own, t.d, (size_t)t.g.items);
+    if (rc) return rc;
     HIP_TRY(hipMemset(t.d, 0, (size_t)t.g.items * 8), YOLO2_DMA_ERROR);  // the zeros ARE the conv padding
     return YOLO2_SUCCESS;
 }
@@ -704,8 +694,10 @@ static int autotune(yolo2_hip_ctx *c)
     // repeated launch finds its weights in L2 and, at small batch, the latency of the per-tap
     // scalar weight loads - exactly what the split-K kernel avoids - is not seen.
     const size_t flush_bytes = (size_t)64 << 20;
-    void *flush = nullptr;
-    HIP_TRY(hipMalloc(&flush, flush_bytes), YOLO2_MMAP_ERROR);
+    Y2DevBuf<uint8_t> flush_own;
+    const int frc = flush_own.alloc(flush_bytes);
+    if (frc) return frc;
+    void *const flush = flush_own.get();
     int ord = 0;
     for (int i = 0; i < 32; ++i) {
         if (kNet[i].type != L_CONV) continue;
@@ -788,7 +780,6 @@ static int autotune(yolo2_hip_ctx *c)
     }
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
-    (void)hipFree(flush);
     HIP_TRY(hipGetLastError(), YOLO2_ERROR);
     return YOLO2_SUCCESS;
 }
@@ -831,13 +822,10 @@ static int ensure_ks_scratch(yolo2_hip_ctx *c, size_t bytes)
 {
     if (c->ks_trip_bytes == bytes) return YOLO2_SUCCESS;
     HIP_TRY(hipDeviceSynchronize(), YOLO2_ERROR);
-    if (c->ks_trip) (void)hipFree(c->ks_trip);
-    c->ks_trip = nullptr;
     c->ks_trip_bytes = 0;
-    if (bytes) {
-        HIP_TRY(hipMalloc((void **)&c->ks_trip, bytes), YOLO2_MMAP_ERROR);
-        c->ks_trip_bytes = bytes;
-    }
+    const int rc = y2_alloc_owned(c->ks_trip_own, c->ks_trip, bytes / sizeof(int));   // (bytes: a multiple of the 24-byte triples)
+    if (rc) return rc;
+    c->ks_trip_bytes = bytes;
     return YOLO2_SUCCESS;
 }
 
@@ -949,13 +937,15 @@ static int setup_pool_fusion(yolo2_hip_ctx *c, bool timed, bool default_on)
     const bool force = c->opt.poolfuse == 1;
     if (!default_on && !force) return YOLO2_SUCCESS;
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    void *flush = nullptr;
+    Y2DevBuf<uint8_t> flush_own;
     const size_t flush_bytes = (size_t)64 << 20;
     if (timed && !force) {
         HIP_TRY(hipEventCreate(&e0), YOLO2_ERROR);
         HIP_TRY(hipEventCreate(&e1), YOLO2_ERROR);
-        HIP_TRY(hipMalloc(&flush, flush_bytes), YOLO2_MMAP_ERROR);
+        const int frc = flush_own.alloc(flush_bytes);
+        if (frc) return frc;
     }
+    void *const flush = flush_own.get();
     int ord = 0;
     for (int i = 0; i < 31; ++i) {
         if (kNet[i].type != L_CONV) continue;
@@ -1008,7 +998,6 @@ static int setup_pool_fusion(yolo2_hip_ctx *c, bool timed, bool default_on)
     }
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
-    if (flush) (void)hipFree(flush);
     HIP_TRY(hipGetLastError(), YOLO2_ERROR);
     return YOLO2_SUCCESS;
 }
@@ -1109,8 +1098,8 @@ static int set_batch_single(yolo2_hip_ctx *c, int batch)
                 if ((rc = alloc_tensor(c->t_out[i], l.c, l.h / 2, l.w / 2, batch))) return rc;
             }
         }
-        c->t_out[24] = c->t_cat;  // conv-24 output and the reorg output live in the concat tensor
-        c->t_out[27] = c->t_cat;  // (yolo2_model.cpp:97-104 does the same by arena placement)
+        y2_view_of(c->t_out[24], c->t_cat);  // conv-24 output and the reorg output live in the concat tensor
+        y2_view_of(c->t_out[27], c->t_cat);  // (yolo2_model.cpp:97-104 does the same by arena placement)
         c->batch = batch;
     }
     const Y2Options &o = c->opt;
@@ -1362,21 +1351,7 @@ extern "C" int yolo2_hip_run_batch_int16(yolo2_hip_ctx *c, uint64_t frames_dev, 
 extern "C" int yolo2_hip_run_batch_int16_host(yolo2_hip_ctx *c, const float *frames, int batch, int16_t *region,
                                               int *final_q)
 {
-    if (!c || !frames || !region) return fail(YOLO2_ERROR, "null argument");
-    HIP_TRY(hipSetDevice(c->device), YOLO2_INIT_ERROR);
-    float *fd = nullptr;
-    short *rd = nullptr;
-    HIP_TRY(hipMalloc((void **)&fd, (size_t)batch * YOLO2_FRAME_ELEMS * 4), YOLO2_MMAP_ERROR);
-    HIP_TRY(hipMalloc((void **)&rd, (size_t)batch * YOLO2_REGION_ELEMS * 2), YOLO2_MMAP_ERROR);
-    HIP_TRY(hipMemcpy(fd, frames, (size_t)batch * YOLO2_FRAME_ELEMS * 4, hipMemcpyHostToDevice), YOLO2_DMA_ERROR);
-    int rc = yolo2_hip_run_batch_int16(c, (uint64_t)(uintptr_t)fd, batch, (uint64_t)(uintptr_t)rd, final_q, nullptr);
-    if (rc == YOLO2_SUCCESS) {
-        hipError_t e = hipMemcpy(region, rd, (size_t)batch * YOLO2_REGION_ELEMS * 2, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = fail(YOLO2_DMA_ERROR, "D2H of region tensor failed: %s", hipGetErrorString(e));
-    }
-    (void)hipFree(fd);
-    (void)hipFree(rd);
-    return rc;
+    return y2_run_batch_host(c, frames, batch, region, [&](uint64_t fd, uint64_t rd) { return yolo2_hip_run_batch_int16(c, fd, batch, rd, final_q, nullptr); });
 }
 
 extern "C" int yolo2_hip_debug_layer_output(yolo2_hip_ctx *c, int layer_idx, int frame, int16_t *out, size_t cap,
@@ -1403,13 +1378,14 @@ extern "C" int yolo2_hip_debug_layer_output(yolo2_hip_ctx *c, int layer_idx, int
     if (out_elems) *out_elems = n;
     if (cap < n) return fail(YOLO2_ERROR, "output buffer too small (%zu < %zu)", cap, n);
     HIP_TRY(hipSetDevice(c->device), YOLO2_INIT_ERROR);
-    short *tmp = nullptr;
-    HIP_TRY(hipMalloc((void **)&tmp, n * 2), YOLO2_MMAP_ERROR);
+    Y2DevBuf<short> tmp_own;
+    const int arc = tmp_own.alloc(n);
+    if (arc) return arc;
+    short *const tmp = tmp_own.get();
     HIP_TRY(hipMemset(tmp, 0, n * 2), YOLO2_DMA_ERROR);
     hipLaunchKernelGGL(k_items_to_ref, dim3(blocks_for((long)C * H * W, 256)), dim3(256), 0, nullptr, base, tmp, C, H, W, W8,
                        t.g.Wp, t.g.PL, t.g.cg_stride, frame);
     hipError_t e = hipMemcpy(out, tmp, n * 2, hipMemcpyDeviceToHost);
-    (void)hipFree(tmp);
     if (e != hipSuccess) return fail(YOLO2_DMA_ERROR, "D2H failed: %s", hipGetErrorString(e));
     return YOLO2_SUCCESS;
 }
@@ -1418,6 +1394,8 @@ extern "C" int yolo2_hip_debug_layer_output(yolo2_hip_ctx *c, int layer_idx, int
 // (yolo2_driver.hip holds the lock, has bound the device and synchronises afterwards; everything here goes to the null stream)
 
 namespace {
+// Static storage: raw pointers with an explicit release (y2_drv_release_i16), not owners - a destructor at process exit may run
+// after the HIP runtime is gone.
 struct DrvScratch {   // grow-only
     void *in_items = nullptr, *out_items = nullptr, *wpk = nullptr, *bias_pk = nullptr;
     size_t in_cap = 0, out_cap = 0, wpk_cap = 0, bias_cap = 0;
@@ -1430,6 +1408,17 @@ void y2_drv_release_i16(void)
     for (void *p : {g_scr.in_items, g_scr.out_items, g_scr.wpk, g_scr.bias_pk, (void *)g_scr.bound})
         if (p) (void)hipFree(p);
     g_scr = DrvScratch();
+}
+
+static int drv_ensure(void **p, size_t *cap, size_t need)   // grow-only
+{
+    if (*cap >= need) return YOLO2_SUCCESS;
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+    *cap = 0;
+    HIP_TRY(hipMalloc(p, need), YOLO2_MMAP_ERROR);
+    *cap = need;
+    return YOLO2_SUCCESS;
 }
 
 static int max_abs_i16_dev(const short *dev, int n, int *out)
@@ -1471,10 +1460,10 @@ int y2_drv_conv_i16(const short *in, short *out, const short *w, const short *be
     const long wpk_elems = packed_weight_elems(ifm_num, ofm_num, ksize);
     const int MB = (ofm_num + 31) / 32;
     int rc;
-    if ((rc = y2_ensure(&g_scr.in_items, &g_scr.in_cap, (size_t)gi.items * 8))) return rc;
-    if ((rc = y2_ensure(&g_scr.out_items, &g_scr.out_cap, (size_t)go.items * 8))) return rc;
-    if ((rc = y2_ensure(&g_scr.wpk, &g_scr.wpk_cap, (size_t)wpk_elems * 2))) return rc;
-    if ((rc = y2_ensure(&g_scr.bias_pk, &g_scr.bias_cap, (size_t)MB * 32 * 2))) return rc;
+    if ((rc = drv_ensure(&g_scr.in_items, &g_scr.in_cap, (size_t)gi.items * 8))) return rc;
+    if ((rc = drv_ensure(&g_scr.out_items, &g_scr.out_cap, (size_t)go.items * 8))) return rc;
+    if ((rc = drv_ensure(&g_scr.wpk, &g_scr.wpk_cap, (size_t)wpk_elems * 2))) return rc;
+    if ((rc = drv_ensure(&g_scr.bias_pk, &g_scr.bias_cap, (size_t)MB * 32 * 2))) return rc;
     HIP_TRY(hipMemsetAsync(g_scr.in_items, 0, (size_t)gi.items * 8, st), YOLO2_DMA_ERROR);
     HIP_TRY(hipMemsetAsync(g_scr.bias_pk, 0, (size_t)MB * 32 * 2, st), YOLO2_DMA_ERROR);
     HIP_TRY(hipMemsetAsync(g_scr.bound, 0, sizeof(int), st), YOLO2_DMA_ERROR);

@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "../../include/yolo2_hip.h"
+#include "y2_mem.hpp"
 
 extern "C" int yolo2_hip_set_error(int code, const char *msg);   // yolo2_hip.hip: stores the message for yolo2_hip_last_error()
 
@@ -306,21 +307,22 @@ static int load_bcast(yolo2_hip_ctx *ctx, const T *weights, size_t n_weights, co
     if (root < 0 || root >= st->nranks) return mfail(YOLO2_ERROR, "bad root rank %d", root);
     const bool is_root = st->rank == root;
     HIPM_TRY(hipSetDevice(st->device), YOLO2_INIT_ERROR);
-    void *wd = nullptr, *bd = nullptr, *qd = nullptr;
-    int *word = nullptr;
+    Y2DevBuf<T> wd_own, bd_own;
+    Y2DevBuf<int32_t> qd_own;
+    Y2DevBuf<int> word_own;
     const size_t wbytes = (size_t)YOLO2_N_WEIGHTS * sizeof(T), bbytes = (size_t)YOLO2_N_BIAS * sizeof(T), qbytes = kQRec * sizeof(int32_t);
-    auto release = [&]() { (void)hipFree(wd); (void)hipFree(bd); (void)hipFree(qd); (void)hipFree(word); };
     // the status word first: without it this rank cannot take part in the agreement at all
-    if (hipMalloc((void **)&word, sizeof(int)) != hipSuccess) return mfail(YOLO2_MMAP_ERROR, "device word for the status agreement could not be allocated");
+    if (word_own.alloc(1)) return mfail(YOLO2_MMAP_ERROR, "device word for the status agreement could not be allocated");
+    int *const word = word_own.get();
     // ---- local part; errors are recorded, not returned
     int local = local_rc;
     std::string local_msg = local ? yolo2_hip_last_error() : "";
     auto note = [&](int code, const char *msg) { if (local == YOLO2_SUCCESS) { local = code; local_msg = msg; } };
     if (is_root && (!weights || !bias)) note(YOLO2_ERROR, "the root rank must pass the weight blobs");
     else if (is_root && (n_weights < YOLO2_N_WEIGHTS || n_bias < YOLO2_N_BIAS)) note(YOLO2_ERROR, "weight blobs too small");
-    if (local == YOLO2_SUCCESS &&
-        (hipMalloc(&wd, wbytes) != hipSuccess || hipMalloc(&bd, bbytes) != hipSuccess || hipMalloc(&qd, qbytes) != hipSuccess))
+    if (local == YOLO2_SUCCESS && (wd_own.alloc(YOLO2_N_WEIGHTS) || bd_own.alloc(YOLO2_N_BIAS) || qd_own.alloc(kQRec)))
         note(YOLO2_MMAP_ERROR, "device buffers for the weight broadcast could not be allocated");
+    void *const wd = wd_own.get(), *const bd = bd_own.get(), *const qd = qd_own.get();
     if (local == YOLO2_SUCCESS && is_root &&
         (hipMemcpy(wd, weights, wbytes, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(bd, bias, bbytes, hipMemcpyHostToDevice) != hipSuccess ||
          hipMemcpy(qd, qrec, qbytes, hipMemcpyHostToDevice) != hipSuccess))
@@ -332,7 +334,7 @@ static int load_bcast(yolo2_hip_ctx *ctx, const T *weights, size_t n_weights, co
     if (rc == YOLO2_SUCCESS && agreed != YOLO2_SUCCESS)
         rc = local ? mfail(local, "%s", local_msg.c_str())
                    : mfail(agreed, "another rank could not prepare the weight broadcast (status %d): no rank loads", agreed);
-    if (rc) { release(); return rc; }
+    if (rc) return rc;
     // ---- the broadcast
     std::vector<Member> me(1);
     me[0].device = st->device; me[0].comm = st->comm; me[0].stream = st->stream;
@@ -348,7 +350,6 @@ static int load_bcast(yolo2_hip_ctx *ctx, const T *weights, size_t n_weights, co
     rc = agree_status(R, st->device, st->comm, st->stream, word, local, &agreed);
     if (rc == YOLO2_SUCCESS && agreed != YOLO2_SUCCESS)
         rc = local ? mfail(local, "%s", local_msg.c_str()) : mfail(agreed, "another rank failed to load the broadcast weights (status %d)", agreed);
-    release();
     return rc;
 }
 
@@ -471,15 +472,15 @@ static int multi_load(yolo2_hip_multi *m, const T *weights, size_t n_weights, co
     const size_t wbytes = (size_t)YOLO2_N_WEIGHTS * sizeof(T), bbytes = (size_t)YOLO2_N_BIAS * sizeof(T);
     const int n = (int)m->ctx.size();
     std::vector<Member> mem((size_t)n);
+    std::vector<Y2DevBuf<T>> wd((size_t)n), bd((size_t)n);
     int rc = YOLO2_SUCCESS;
     for (int i = 0; i < n && rc == YOLO2_SUCCESS; ++i) {
         mem[(size_t)i].device = m->devices[(size_t)i];
         mem[(size_t)i].stream = m->streams[(size_t)i];
         mem[(size_t)i].comm = m->comms.empty() ? nullptr : m->comms[(size_t)i];
-        void *wd = nullptr, *bd = nullptr;
-        if (hipSetDevice(m->devices[(size_t)i]) != hipSuccess || hipMalloc(&wd, wbytes) != hipSuccess || hipMalloc(&bd, bbytes) != hipSuccess)
+        if (hipSetDevice(m->devices[(size_t)i]) != hipSuccess || wd[(size_t)i].alloc(YOLO2_N_WEIGHTS) || bd[(size_t)i].alloc(YOLO2_N_BIAS))
             rc = mfail(YOLO2_MMAP_ERROR, "device buffers for the weight blobs could not be allocated on device %d", m->devices[(size_t)i]);
-        mem[(size_t)i].bufs = {wd, bd};
+        mem[(size_t)i].bufs = {wd[(size_t)i].get(), bd[(size_t)i].get()};
     }
     if (rc == YOLO2_SUCCESS) {
         (void)hipSetDevice(m->devices[0]);
@@ -502,7 +503,8 @@ static int multi_load(yolo2_hip_multi *m, const T *weights, size_t n_weights, co
     for (int i = 0; i < n; ++i) {
         (void)hipSetDevice(m->devices[(size_t)i]);
         (void)hipDeviceSynchronize();
-        for (void *p : mem[(size_t)i].bufs) (void)hipFree(p);
+        wd[(size_t)i].reset();
+        bd[(size_t)i].reset();
     }
     return rc;
 }

@@ -385,30 +385,30 @@ FrameGeom frame_geom(int w, int h)
 }
 
 // Device buffers of one post-processing call in flight.  The public synchronous entries keep one set per device (g_scratch, one call
-// at a time per device); the streaming entries (yolo2_hip.hip) own one set per pipeline stage (y2_post_alloc / y2_post_free).
+// at a time per device); the streaming entries (yolo2_hip.hip) own one set per pipeline stage (y2_post_alloc; PipeBufs frees them).
 int alloc_bufs(Y2PostBufs &s, int batch, int cap)
 {
+    int rc;
     if (s.cap_frames < batch) {
-        for (void *p : {(void *)s.rows, (void *)s.rows2, (void *)s.totals, (void *)s.counts, (void *)s.geom}) (void)hipFree(p);
-        s.rows = s.rows2 = nullptr; s.totals = s.counts = nullptr; s.geom = nullptr; s.cap_frames = 0;
-        const size_t rb = (size_t)batch * kDets * kEntries * sizeof(float);
-        HIPP_TRY(hipMalloc((void **)&s.rows, rb), YOLO2_MMAP_ERROR);
-        HIPP_TRY(hipMalloc((void **)&s.rows2, rb), YOLO2_MMAP_ERROR);
-        HIPP_TRY(hipMalloc((void **)&s.totals, (size_t)batch * sizeof(int)), YOLO2_MMAP_ERROR);
-        HIPP_TRY(hipMalloc((void **)&s.counts, (size_t)batch * sizeof(int)), YOLO2_MMAP_ERROR);
-        HIPP_TRY(hipMalloc((void **)&s.geom, (size_t)batch * sizeof(FrameGeom)), YOLO2_MMAP_ERROR);
+        s.rows.reset(); s.rows2.reset(); s.totals.reset(); s.counts.reset(); s.geom.reset();
+        s.cap_frames = 0;
+        const size_t rows = (size_t)batch * kDets * kEntries;
+        if ((rc = s.rows.alloc(rows)) || (rc = s.rows2.alloc(rows)) || (rc = s.totals.alloc((size_t)batch)) || (rc = s.counts.alloc((size_t)batch)) ||
+            (rc = s.geom.alloc((size_t)batch * sizeof(FrameGeom))))
+            return rc;
         s.cap_frames = batch;
     }
     const size_t need = (size_t)batch * (size_t)cap;
     if (s.cap_dets < need) {
-        (void)hipFree(s.dets);
-        s.dets = nullptr; s.cap_dets = 0;
-        HIPP_TRY(hipMalloc((void **)&s.dets, need * sizeof(DetRec)), YOLO2_MMAP_ERROR);
+        s.cap_dets = 0;
+        if ((rc = s.dets.alloc(need))) return rc;
         s.cap_dets = need;
     }
     return YOLO2_SUCCESS;
 }
-std::map<int, Y2PostBufs> g_scratch;
+// kept for the life of the process and never destroyed (a static map's destructor would call hipFree at process exit, when the HIP
+// runtime may be gone): the one set of owners that yolo2_hip_debug_live_bytes keeps counting after every context is closed
+std::map<int, Y2PostBufs> &g_scratch = *new std::map<int, Y2PostBufs>();
 std::map<int, std::mutex> g_dev_mu;   // one synchronous call at a time PER DEVICE (the shared scratch set); devices do not wait for each other
 
 // The three kernels, enqueued on `st`; nothing is synchronised.  geom_dev: `batch` FrameGeom records already on the device (or on
@@ -418,13 +418,13 @@ void enqueue(const T *region, const Luts &l, int final_q, int batch, float thres
              float *proc_dev, hipStream_t st, float **final_rows)
 {
     In<T> in{region, l.logistic, l.softexp, l.expf_, std::ldexp(1.0f, -final_q)};
-    hipLaunchKernelGGL((k_region_rows<T>), dim3(batch), dim3(256), 0, st, in, batch, (const FrameGeom *)s.geom, thresh, s.rows, s.totals, proc_dev);
-    float *fr = s.rows;
+    hipLaunchKernelGGL((k_region_rows<T>), dim3(batch), dim3(256), 0, st, in, batch, (const FrameGeom *)s.geom.get(), thresh, s.rows.get(), s.totals.get(), proc_dev);
+    float *fr = s.rows.get();
     if (nms > 0.f) {
-        hipLaunchKernelGGL(k_nms_rows, dim3(batch), dim3(256), 0, st, s.rows, s.totals, nms, s.rows2);
-        fr = s.rows2;
+        hipLaunchKernelGGL(k_nms_rows, dim3(batch), dim3(256), 0, st, s.rows.get(), s.totals.get(), nms, s.rows2.get());
+        fr = s.rows2.get();
     }
-    if (cap > 0) hipLaunchKernelGGL(k_compact_dets, dim3(batch), dim3(256), 0, st, fr, s.totals, cap, (DetRec *)s.dets, s.counts, best_only);
+    if (cap > 0) hipLaunchKernelGGL(k_compact_dets, dim3(batch), dim3(256), 0, st, fr, s.totals.get(), cap, (DetRec *)s.dets.get(), s.counts.get(), best_only);
     if (final_rows) *final_rows = fr;
 }
 
@@ -478,28 +478,26 @@ int postprocess(yolo2_hip_ctx *ctx, uint64_t region_dev, int batch, int final_q,
         if (im_w[f] <= 0 || im_h[f] <= 0) return pfail(YOLO2_ERROR, "bad image size for frame %d", f);
         g[(size_t)f] = frame_geom(im_w[f], im_h[f]);
     }
-    HIPP_TRY(hipMemcpyAsync(s->geom, g.data(), (size_t)batch * sizeof(FrameGeom), hipMemcpyHostToDevice, st), YOLO2_DMA_ERROR);
+    HIPP_TRY(hipMemcpyAsync(s->geom.get(), g.data(), (size_t)batch * sizeof(FrameGeom), hipMemcpyHostToDevice, st), YOLO2_DMA_ERROR);
     HIPP_TRY(hipStreamSynchronize(st), YOLO2_DMA_ERROR);      // g is a local
-    float *proc_dev = nullptr;
-    if (proc_host) HIPP_TRY(hipMalloc((void **)&proc_dev, (size_t)batch * YOLO2_REGION_ELEMS * sizeof(float)), YOLO2_MMAP_ERROR);
+    Y2DevBuf<float> proc;
+    if (proc_host && (rc = proc.alloc((size_t)batch * YOLO2_REGION_ELEMS))) return rc;
+    float *const proc_dev = proc.get();
     float *final_rows = nullptr;
     hipError_t e = hipSuccess;
     if constexpr (std::is_same<T, float>::value) {
-        if ((rc = y2_post_enqueue_f32((const float *)(uintptr_t)region_dev, batch, thresh, nms, dets ? cap : 0, 0, s, st, proc_dev, &final_rows))) {
-            if (proc_dev) (void)hipFree(proc_dev);
+        if ((rc = y2_post_enqueue_f32((const float *)(uintptr_t)region_dev, batch, thresh, nms, dets ? cap : 0, 0, s, st, proc_dev, &final_rows)))
             return rc;
-        }
     } else {
         enqueue<T>((const T *)(uintptr_t)region_dev, l, final_q, batch, thresh, nms, dets ? cap : 0, 0, *s, proc_dev, st, &final_rows);
         e = hipGetLastError();
     }
-    if (e == hipSuccess && dets) e = hipMemcpyAsync(counts, s->counts, (size_t)batch * sizeof(int), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && dets) e = hipMemcpyAsync(dets, s->dets, (size_t)batch * cap * sizeof(DetRec), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && dets) e = hipMemcpyAsync(counts, s->counts.get(), (size_t)batch * sizeof(int), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && dets) e = hipMemcpyAsync(dets, s->dets.get(), (size_t)batch * cap * sizeof(DetRec), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess && rows_host) e = hipMemcpyAsync(rows_host, final_rows, (size_t)batch * kDets * kEntries * sizeof(float), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && totals_host) e = hipMemcpyAsync(totals_host, s->totals, (size_t)batch * sizeof(int), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && totals_host) e = hipMemcpyAsync(totals_host, s->totals.get(), (size_t)batch * sizeof(int), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess && proc_host) e = hipMemcpyAsync(proc_host, proc_dev, (size_t)batch * YOLO2_REGION_ELEMS * sizeof(float), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (proc_dev) (void)hipFree(proc_dev);
     if (e != hipSuccess) return pfail(YOLO2_ERROR, "post-processing failed: %s", hipGetErrorString(e));
     return YOLO2_SUCCESS;
 }
@@ -526,12 +524,6 @@ int y2_post_alloc(int device, int batch, int cap, Y2PostBufs *b)
 {
     HIPP_TRY(hipSetDevice(device), YOLO2_INIT_ERROR);
     return alloc_bufs(*b, batch, cap);
-}
-
-void y2_post_free(Y2PostBufs *b)
-{
-    for (void *p : {(void *)b->rows, (void *)b->rows2, (void *)b->totals, (void *)b->counts, (void *)b->geom, (void *)b->dets}) (void)hipFree(p);
-    *b = Y2PostBufs();
 }
 
 size_t y2_post_geom_bytes(void) { return sizeof(FrameGeom); }

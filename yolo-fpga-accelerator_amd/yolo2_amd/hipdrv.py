@@ -46,7 +46,7 @@ EXPORTS = [
     "yolo2_hip_set_option", "yolo2_hip_options_string", "yolo2_hip_set_plan_cache", "yolo2_hip_plan_cache_info", "yolo2_hip_plan_cache_check",
     "yolo2_hip_i16_plan_check", "yolo2_hip_ks_scratch_bytes", "yolo2_hip_i16_edge_map", "yolo2_hip_last_layer_edge",
     "yolo2_hip_run_batch_f32tol", "yolo2_hip_run_batch_f32tol_host", "yolo2_hip_f32tol_layer_kernel", "yolo2_hip_num_lanes_f32tol",
-    "yolo2_hip_debug_f16_tensor",
+    "yolo2_hip_debug_f16_tensor", "yolo2_hip_debug_live_bytes",
     "yolo2_hip_run_images_u8_f16_host", "yolo2_hip_run_images_u8_dets_f16", "yolo2_hip_multi_run_images_u8_dets_f16",
     "yolo2_hip_images_layer0_kernel",
     "yolo2_hip_letterbox_pix", "yolo2_hip_run_images_pix_host", "yolo2_hip_run_images_pix_dets", "yolo2_hip_run_images_pix_f16_host",
@@ -185,6 +185,7 @@ def lib():
     sig("yolo2_hip_num_lanes_f32tol", [vp])
     sig("yolo2_hip_ks_scratch_bytes", [vp], C.c_size_t)
     sig("yolo2_hip_debug_f16_tensor", [vp, i32, i32, i32, i32, vp, C.c_size_t, pi32])
+    sig("yolo2_hip_debug_live_bytes", [C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)])
     sig("yolo2_hip_run_images_u8_f16_host", [vp, i32, vp, vp, vp, i32, i32, i32, vp])
     sig("yolo2_hip_run_images_u8_dets_f16", [vp, i32, vp, vp, vp, i32, i32, i32, C.c_float, C.c_float, i32, vp, i32, vp])
     sig("yolo2_hip_multi_run_images_u8_dets_f16", [vp, i32, vp, vp, vp, i32, i32, i32, C.c_float, C.c_float, i32, vp, i32, vp])
@@ -612,6 +613,13 @@ def postprocess(ctx, region_ptr: int, batch: int, im_w, im_h, thresh: float, nms
                                              vp(rows), vp(totals), vp(proc), C.c_void_p(stream))
     check(rc, "yolo2_hip_postprocess")
     return {"dets": [dets[f, :min(int(counts[f]), cap)] for f in range(batch)], "counts": counts, "rows": rows, "totals": totals, "proc": proc}
+
+
+def live_bytes():
+    """(device bytes, pinned bytes) the library's contexts and calls hold right now (yolo2_hip_debug_live_bytes, a test hook)."""
+    d, p = C.c_size_t(0), C.c_size_t(0)
+    check(lib().yolo2_hip_debug_live_bytes(C.byref(d), C.byref(p)), "yolo2_hip_debug_live_bytes")
+    return d.value, p.value
 
 
 DETS_BEST_CLASS = 1
