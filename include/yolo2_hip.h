@@ -488,6 +488,52 @@ int yolo2_hip_run_images_pix_dets_f16(yolo2_hip_ctx *ctx, int split, const uint8
                                       const int *heights, int pixfmt, int n, int batch, float thresh, float nms, int flags,
                                       yolo2_hip_det *dets, int cap_per_frame, int *counts);
 
+/* ------------------------------------------------------- calibration: fp32 weights + frames -> int16 weights and Q tables
+ *
+ * The reference makes its int16 weight set with a separate tool (weights/README.md step 2b: "activation-calibrated"
+ * weight_int16.bin, bias_int16.bin, weight_int16_Q.bin, bias_int16_Q.bin, iofm_Q.bin).  These entries are that step on the GPU, from what
+ * yolo2_hip_load_weights_fp32 left resident: the exact fp32 pass (bit-identical to the reference's fp32) runs the calibration frames
+ * and one abs-max reduction per tensor gives the range of the input and of every conv layer's unpooled output.
+ *
+ * Q rule: q(m, h) = the largest integer q in 0..15 at which h * m still quantises to at most 32767, i.e. h * m * 2^q < 32767.5
+ * (rounding is half away from zero), in double; m = 0 gives 15; no such q is YOLO2_ERROR naming the tensor.  So 1.0 -> 14,
+ * 3.9999 -> 13 (32767.18 rounds to 32767), 4.0 -> 12, 32767 -> 0, 32768 -> error.  weight_q[ord] = q(max |w_ord|, 1), bias_q[ord] = q(max |b_ord|, 1), act_q[0] = q(max |input|, 1) (frames in
+ * [0, 1] give 14), act_q[ord + 1] = q(max |out_ord|, headroom) with the caller's headroom >= 1.  One fix-up: the layer loop
+ * (yolo2_model.cpp:379-399) only shifts the reorg half of the concat tensor DOWN to layer 24's Q, so if layer 24's output Q came out
+ * above layer 26's it is lowered to layer 26's.
+ *
+ * Every entry refuses bad arguments before anything is launched; yolo2_hip_last_error names the cause. */
+
+/* max |x| over n floats in HBM (any 4-byte-aligned address), and the number of Inf / NaN among them - counted, and left out of the
+ * maximum (the count saturates: exact below 2^20 per workgroup of the reduction).  On the calling thread's current device;
+ * synchronises `stream`.  nonfinite may be NULL. */
+int yolo2_hip_absmax_f32(uint64_t data_dev, size_t n, float *absmax, uint32_t *nonfinite, void *stream);
+/* Clears the context's statistics (they accumulate over calls).  Call it after loading another weight set. */
+int yolo2_hip_calib_reset(yolo2_hip_ctx *ctx);
+/* One exact fp32 pass over frames_dev (float [batch][3][416][416], device) and the 24 reductions, accumulated.  Needs
+ * yolo2_hip_load_weights_fp32; batch limits are yolo2_hip_run_batch_fp32's.  The frames are looked at first: a NaN or Inf among them
+ * is YOLO2_ERROR with nothing accumulated.  Enqueues on `stream` and synchronises it. */
+int yolo2_hip_calib_frames(yolo2_hip_ctx *ctx, uint64_t frames_dev, int batch, void *stream);
+/* The same from n images as HOST bytes, letterboxed on the GPU in chunks of `batch` (pixfmt: YOLO2_PIX_*). */
+int yolo2_hip_calib_images_pix_host(yolo2_hip_ctx *ctx, const uint8_t *const *images, const int *widths, const int *heights,
+                                    int pixfmt, int n, int batch);
+/* act_absmax[24]: the network input, then the output of conv ordinal 0..22; weight_absmax[23] / bias_absmax[23]: the resident fp32
+ * blobs per conv ordinal; *frames_seen: frames accumulated since the last reset.  Any of the four may be NULL. */
+int yolo2_hip_calib_stats(yolo2_hip_ctx *ctx, float *act_absmax, float *weight_absmax, float *bias_absmax, long *frames_seen);
+/* The Q rule above on the context's statistics -> weight_q[23], bias_q[23], act_q[24].  YOLO2_ERROR if no frame was seen or a
+ * non-finite value was counted in any tensor. */
+int yolo2_hip_calib_q_tables(yolo2_hip_ctx *ctx, float headroom, int32_t *weight_q, int32_t *bias_q, int32_t *act_q);
+/* The Q rule on explicit maxima (host arithmetic only, no GPU): act_absmax[24], weight_absmax[23], bias_absmax[23] as above. */
+int yolo2_hip_calib_q_from_stats(const float *act_absmax, const float *weight_absmax, const float *bias_absmax, float headroom,
+                                 int32_t *weight_q, int32_t *bias_q, int32_t *act_q);
+/* int16 = round(x * 2^Q) of the resident fp32 blobs, on the GPU, into host buffers of at least YOLO2_N_WEIGHTS / YOLO2_N_BIAS
+ * elements, in the order yolo2_hip_load_weights_int16 takes (on this or another context).  The rule is the network input's
+ * (yolo2_model.cpp:257-273): product in fp32, clamped, rounded half away from zero - clamped symmetrically to +-32767.  Any tables
+ * with Q in 0..30 may be passed, not only calibrated ones; *clamped (may be NULL) = the values whose rounded product lay outside
+ * +-32767 (|x * 2^Q| >= 32767.5; a NaN counts and becomes 0). */
+int yolo2_hip_quantize_weights_int16(yolo2_hip_ctx *ctx, const int32_t *weight_q, const int32_t *bias_q, int16_t *weights_reorg_out,
+                                     size_t n_weights, int16_t *bias_out, size_t n_bias, long *clamped);
+
 /* ------------------------------------------------------- multi-GPU: frame sharding, one weight broadcast
  *
  * SURVEY.md 8(b) "init(device_list) ... load_weights (H2D on rank 0, RCCL broadcast to the rest)", 8(e): frames are

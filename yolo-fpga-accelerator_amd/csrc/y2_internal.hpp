@@ -6,6 +6,7 @@
 //   yolo2_int16.hip   the int16 path: weight loading / arithmetic-form proofs, launch planning, autotune, run_batch_int16
 //   yolo2_fp16.hip    the fp16 MFMA path: weight packing, per-context launch table, run_batch_fp16
 //   yolo2_fp32.hip    the exact fp32 path (tiled and one-thread-per-output)
+//   yolo2_calib.hip   fp32 weights + calibration frames -> Q tables and int16 weights (statistics of the exact fp32 pass)
 //   yolo2_post.hip    region layer + boxes + NMS;   yolo2_multi.hip  frame sharding + the RCCL weight broadcast
 // Every non-template kernel is launched from exactly one of them (its kernels_*.hpp is included there only).
 #pragma once
@@ -297,6 +298,10 @@ struct yolo2_hip_ctx {
     int f32_batch = 0;
     FTensor f_in, f_out[32], f_cat;
     ConvPlan fp32_plan[32];
+    // ---- calibration (yolo2_calib.hip): abs-max statistics of the exact fp32 pass's tensors, accumulated over yolo2_hip_calib_frames
+    // calls.  Pairs of uint32 {max |x| as fp32 bits, saturating count of non-finite values}; allocated at the first calibration call.
+    Y2DevBuf<unsigned> calib_stats;
+    long calib_frames_seen = 0;
     long wh_off[YOLO2_N_CONV], biasf_off[YOLO2_N_CONV];
     int f16_batch = 0;
     int f16_last_batch = 0;            // batch of the last yolo2_hip_run_batch_fp16 on this context (yolo2_hip_debug_f16_tensor)
@@ -399,6 +404,10 @@ void y2_drv_release_i16(void);   // frees the grow-only scratch of y2_drv_conv_i
 // yolo2_fp32.hip:
 void y2_drv_conv_f32(const float *in, float *out, const float *w, const float *beta, int ifm, int ofm, int ksize, int kstride, int iw,
                      int ih, int ow, int oh, int pad, int is_nl);
+
+// yolo2_calib.hip: one exact fp32 pass over `batch` device frames + the abs-max reductions, accumulated into c->calib_stats; `counted`
+// of the frames are new ones (the images entry pads a short last chunk by repeating its last image).  Synchronises st.
+int y2_calib_frames(yolo2_hip_ctx *c, uint64_t frames_dev, int batch, int counted, hipStream_t st);
 
 // yolo2_post.hip: the tail (region + boxes + NMS + record compaction) as a stage of a pipeline - caller-owned buffers, enqueue only.
 int y2_post_alloc(int device, int batch, int cap, Y2PostBufs *b);

@@ -482,6 +482,63 @@ extern "C" int yolo2_hip_run_images_pix_host(yolo2_hip_ctx *c, const uint8_t *co
     return ch ? run_images_i16_host(c, images, widths, heights, ch, true, n, batch, region, final_q) : YOLO2_ERROR;
 }
 
+// Calibration from image bytes (yolo2_calib.hip has the statistics): the chunks and staging of the entry above - letterbox table +
+// bytes H2D, one k_letterbox_*_batch launch - with y2_calib_frames in place of the int16 pass.  Chunk after chunk, no overlap:
+// calibration runs once per weight set.  A short last chunk repeats its last image, which moves no maximum and is not counted.
+extern "C" int yolo2_hip_calib_images_pix_host(yolo2_hip_ctx *c, const uint8_t *const *images, const int *widths, const int *heights,
+                                               int pixfmt, int n, int batch)
+{
+    if (!c || !images || !widths || !heights) return fail(YOLO2_ERROR, "null argument");
+    const int channels = pix_channels(pixfmt);
+    if (!channels) return YOLO2_ERROR;
+    if (n <= 0 || batch <= 0 || batch > 1024) return fail(YOLO2_ERROR, "bad image count %d / batch %d", n, batch);
+    if (!c->f16_loaded || !c->wf32) return fail(YOLO2_ERROR, "fp32 weights not loaded (yolo2_hip_load_weights_fp32)");
+    batch = std::min(batch, n);
+    const int chunks = (n + batch - 1) / batch;
+    auto in_chunk = [&](int k) { return std::min(batch, n - k * batch); };
+    auto padded = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t table_bytes = padded((size_t)batch * sizeof(LetterboxItem));
+    size_t cap = 0;
+    for (int k = 0; k < chunks; ++k) {
+        size_t sum = table_bytes;
+        for (int i = k * batch; i < k * batch + in_chunk(k); ++i) {
+            LetterboxArgs a;
+            if (!images[i]) return fail(YOLO2_ERROR, "null image %d", i);
+            const int rc = letterbox_args(widths[i], heights[i], channels, 416, 416, a, true);
+            if (rc) return rc;
+            sum += padded((size_t)widths[i] * heights[i] * channels);
+        }
+        cap = std::max(cap, sum);
+    }
+    HIP_TRY(hipSetDevice(c->device), YOLO2_INIT_ERROR);
+    int rc = pipe_ensure(c->pipe, cap, cap, batch, false);
+    if (rc) return rc;
+    PipeBufs &P = c->pipe;
+    uint8_t *const hin = P.hin[0].get(), *const dbytes = P.dbytes[0].get();
+    std::vector<size_t> offs((size_t)batch);
+    for (int k = 0; k < chunks; ++k) {
+        const int nf = in_chunk(k), first = k * batch;
+        size_t off = table_bytes;
+        for (int i = 0; i < nf; ++i) {
+            const size_t bytes = (size_t)widths[first + i] * heights[first + i] * channels;
+            memcpy(hin + off, images[first + i], bytes);
+            offs[(size_t)i] = off;
+            off += padded(bytes);
+        }
+        LetterboxItem *items = reinterpret_cast<LetterboxItem *>(hin);
+        for (int f = 0; f < batch; ++f) {
+            const int i = std::min(f, nf - 1);
+            items[f].off = offs[(size_t)i];
+            if ((rc = letterbox_args(widths[first + i], heights[first + i], channels, 416, 416, items[f].a, true))) return rc;
+        }
+        HIP_TRY(hipMemcpyAsync(dbytes, hin, off, hipMemcpyHostToDevice, P.s_run), YOLO2_DMA_ERROR);
+        launch_letterbox_batch(channels == 2, dbytes, P.din[0].get(), batch, P.s_run);
+        HIP_TRY(hipGetLastError(), YOLO2_ERROR);
+        if ((rc = y2_calib_frames(c, (uint64_t)(uintptr_t)P.din[0].get(), batch, nf, P.s_run))) return rc;   // (synchronises: hin is free again)
+    }
+    return YOLO2_SUCCESS;
+}
+
 // ---------------------------------------------------------------------------- streaming host entry
 
 // Camera-to-detections entry (the whole path incl. the step after it, at the path's rate): n images as host bytes -> detection

@@ -1,0 +1,186 @@
+// yolov2_calibrate -- fp32 weight files + calibration images -> the int16 weight set yolov2_detect --precision int16 runs.
+//
+// The reference makes this set with a separate tool (weights/README.md step 2b); here it is the calibration tier of the HIP library
+// behind its C ABI (include/yolo2_hip.h, "calibration"): the exact fp32 pass runs the images, one abs-max per tensor gives the
+// ranges, the Q rule turns them into the three tables and the GPU quantises the resident fp32 streams.  Plain C++ host, like
+// yolov2_detect: it decodes the images (y2_codec.cpp), hands bytes over, and writes the five files in the reference's layout
+// (one pad element after every odd-length layer, yolo2_model.cpp:198-224).
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <filesystem>
+#include <fstream>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include "../../include/yolo2_hip.h"
+#include "y2_host.hpp"
+
+namespace {
+
+struct Config {
+    std::string weights_dir = "weights", out_dir, input_dir, input_list;
+    int batch = 8, device = 0;
+    float headroom = 1.0f;
+};
+
+void print_usage(const char *prog)
+{
+    std::printf(
+        "Usage: %s --weights <dir> (--input-dir <dir> | --input-list <file>) --out <dir> [options]\n"
+        "  --weights <dir>       Directory with weights_reorg.bin and bias.bin (fp32; default: weights)\n"
+        "  --input-dir <dir>     Calibration images: every *.jpg / *.jpeg / *.png / *.ppm / *.pgm of a directory, sorted by name\n"
+        "  --input-list <file>   Calibration images, one path per line\n"
+        "  --out <dir>           Where weights_reorg_int16.bin, bias_int16.bin, weight_int16_Q.bin, bias_int16_Q.bin and iofm_Q.bin go\n"
+        "  --batch <n>           Images per pass of the exact fp32 network (default 8)\n"
+        "  --headroom <float>    Factor >= 1 kept free above every conv output's measured maximum (default 1)\n"
+        "  --device <n>          HIP device (default 0)\n"
+        "Q rule: the largest Q in 0..15 with headroom * max|x| * 2^Q < 32767.5 (it still rounds to at most 32767), per tensor.\n",
+        prog);
+}
+
+Config parse_args(int argc, char **argv)
+{
+    Config cfg;
+    for (int i = 1; i < argc; ++i) {
+        const std::string arg = argv[i];
+        auto need = [&]() {
+            if (i + 1 >= argc) { std::fprintf(stderr, "%s needs a value\n", arg.c_str()); std::exit(1); }
+            return true;
+        };
+        if (arg == "--help" || arg == "-h") { print_usage(argv[0]); std::exit(0); }
+        else if (arg == "--weights" && need()) cfg.weights_dir = argv[++i];
+        else if (arg == "--input-dir" && need()) cfg.input_dir = argv[++i];
+        else if (arg == "--input-list" && need()) cfg.input_list = argv[++i];
+        else if (arg == "--out" && need()) cfg.out_dir = argv[++i];
+        else if (arg == "--batch" && need()) cfg.batch = std::atoi(argv[++i]);
+        else if (arg == "--headroom" && need()) cfg.headroom = (float)std::atof(argv[++i]);
+        else if (arg == "--device" && need()) cfg.device = std::atoi(argv[++i]);
+        else { std::fprintf(stderr, "Unknown argument: %s\n", arg.c_str()); print_usage(argv[0]); std::exit(1); }
+    }
+    if (cfg.out_dir.empty() || (cfg.input_dir.empty() == cfg.input_list.empty())) {
+        std::fprintf(stderr, "--out and exactly one of --input-dir / --input-list are required\n");
+        print_usage(argv[0]);
+        std::exit(1);
+    }
+    if (cfg.batch < 1 || cfg.batch > 1024) { std::fprintf(stderr, "--batch must be 1..1024\n"); std::exit(1); }
+    if (!(cfg.headroom >= 1.0f)) { std::fprintf(stderr, "--headroom must be >= 1\n"); std::exit(1); }
+    return cfg;
+}
+
+std::vector<std::string> list_inputs(const Config &cfg)
+{
+    namespace fs = std::filesystem;
+    std::vector<std::string> files;
+    if (!cfg.input_list.empty()) {
+        std::ifstream in(cfg.input_list);
+        if (!in) throw std::runtime_error("Cannot open " + cfg.input_list);
+        std::string line;
+        while (std::getline(in, line)) {
+            while (!line.empty() && (line.back() == '\r' || line.back() == ' ')) line.pop_back();
+            if (!line.empty()) files.push_back(line);
+        }
+    } else {
+        for (const auto &e : fs::directory_iterator(cfg.input_dir)) {
+            const std::string ext = e.path().extension().string();
+            if (ext == ".ppm" || ext == ".pgm" || ext == ".jpg" || ext == ".jpeg" || ext == ".png") files.push_back(e.path().string());
+        }
+        std::sort(files.begin(), files.end());
+    }
+    if (files.empty()) throw std::runtime_error("no calibration images");
+    return files;
+}
+
+std::vector<float> read_floats(const std::string &path, size_t want)
+{
+    std::ifstream in(path, std::ios::binary);
+    if (!in) throw std::runtime_error("Cannot open " + path);
+    std::vector<float> v(want);
+    in.read(reinterpret_cast<char *>(v.data()), (std::streamsize)(want * sizeof(float)));
+    if ((size_t)in.gcount() != want * sizeof(float)) throw std::runtime_error(path + " is short of " + std::to_string(want) + " floats");
+    return v;
+}
+
+template <typename T>
+void write_blob(const std::string &path, const std::vector<T> &v)
+{
+    std::ofstream out(path, std::ios::binary);
+    out.write(reinterpret_cast<const char *>(v.data()), (std::streamsize)(v.size() * sizeof(T)));
+    if (!out) throw std::runtime_error("Cannot write " + path);
+}
+
+// the stream with one zero element after every odd-length layer (yolo2_model.cpp:198-224; yolo2_strip_int16_layer_pad undoes it)
+std::vector<int16_t> with_layer_pad(const std::vector<int16_t> &flat, const int *len)
+{
+    std::vector<int16_t> out;
+    size_t off = 0;
+    for (int o = 0; o < YOLO2_N_CONV; ++o) {
+        out.insert(out.end(), flat.begin() + (long)off, flat.begin() + (long)(off + (size_t)len[o]));
+        if (len[o] & 1) out.push_back(0);
+        off += (size_t)len[o];
+    }
+    return out;
+}
+
+void check(int rc)
+{
+    if (rc != YOLO2_SUCCESS) throw std::runtime_error(yolo2_hip_last_error());
+}
+
+int run(const Config &cfg)
+{
+    const std::vector<std::string> files = list_inputs(cfg);
+    const std::vector<float> w = read_floats(cfg.weights_dir + "/weights_reorg.bin", (size_t)YOLO2_N_WEIGHTS);
+    const std::vector<float> b = read_floats(cfg.weights_dir + "/bias.bin", (size_t)YOLO2_N_BIAS);
+    std::vector<y2h::ImageU8> images;
+    for (const std::string &f : files) images.push_back(y2h::load_image_u8(f));
+    std::vector<const uint8_t *> ptrs;
+    std::vector<int> ws, hs;
+    for (const y2h::ImageU8 &im : images) { ptrs.push_back(im.rgb.data()); ws.push_back(im.w); hs.push_back(im.h); }
+
+    yolo2_hip_ctx *ctx = nullptr;
+    check(yolo2_hip_create(cfg.device, &ctx));
+    struct Guard { yolo2_hip_ctx *c; ~Guard() { yolo2_hip_destroy(c); } } guard{ctx};
+    check(yolo2_hip_load_weights_fp32(ctx, w.data(), w.size(), b.data(), b.size()));
+    check(yolo2_hip_calib_images_pix_host(ctx, ptrs.data(), ws.data(), hs.data(), YOLO2_PIX_RGB24, (int)images.size(), cfg.batch));
+    float act_max[YOLO2_N_CONV + 1], w_max[YOLO2_N_CONV], b_max[YOLO2_N_CONV];
+    long seen = 0;
+    check(yolo2_hip_calib_stats(ctx, act_max, w_max, b_max, &seen));
+    std::vector<int32_t> wq(YOLO2_N_CONV), bq(YOLO2_N_CONV), aq(YOLO2_N_CONV + 1);
+    check(yolo2_hip_calib_q_tables(ctx, cfg.headroom, wq.data(), bq.data(), aq.data()));
+    std::vector<int16_t> wi((size_t)YOLO2_N_WEIGHTS), bi((size_t)YOLO2_N_BIAS);
+    long clamped = 0;
+    check(yolo2_hip_quantize_weights_int16(ctx, wq.data(), bq.data(), wi.data(), wi.size(), bi.data(), bi.size(), &clamped));
+
+    std::printf("calibrated on %ld images (batch %d, headroom %g)\n", seen, cfg.batch, (double)cfg.headroom);
+    std::printf("input        max|x| %-12.6g act_q %d\n", (double)act_max[0], aq[0]);
+    std::printf("%-5s %-14s %-8s %-14s %-6s %-14s %s\n", "conv", "max|w|", "weight_q", "max|b|", "bias_q", "max|out|", "act_q");
+    for (int o = 0; o < YOLO2_N_CONV; ++o)
+        std::printf("%-5d %-14.6g %-8d %-14.6g %-6d %-14.6g %d\n", o, (double)w_max[o], wq[(size_t)o], (double)b_max[o], bq[(size_t)o],
+                    (double)act_max[o + 1], aq[(size_t)o + 1]);
+    std::printf("values clamped to +-32767: %ld\n", clamped);
+
+    std::filesystem::create_directories(cfg.out_dir);
+    write_blob(cfg.out_dir + "/weights_reorg_int16.bin", with_layer_pad(wi, yolo2_weight_len));
+    write_blob(cfg.out_dir + "/bias_int16.bin", with_layer_pad(bi, yolo2_bias_len));
+    write_blob(cfg.out_dir + "/weight_int16_Q.bin", wq);
+    write_blob(cfg.out_dir + "/bias_int16_Q.bin", bq);
+    write_blob(cfg.out_dir + "/iofm_Q.bin", aq);
+    std::printf("wrote weights_reorg_int16.bin, bias_int16.bin, weight_int16_Q.bin, bias_int16_Q.bin, iofm_Q.bin to %s\n", cfg.out_dir.c_str());
+    return 0;
+}
+
+}  // namespace
+
+int main(int argc, char **argv)
+{
+    const Config cfg = parse_args(argc, argv);
+    try {
+        return run(cfg);
+    } catch (const std::exception &e) {
+        std::fprintf(stderr, "yolov2_calibrate: %s\n", e.what());
+        return 1;
+    }
+}

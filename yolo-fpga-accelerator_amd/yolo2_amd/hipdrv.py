@@ -52,6 +52,8 @@ EXPORTS = [
     "yolo2_hip_letterbox_pix", "yolo2_hip_run_images_pix_host", "yolo2_hip_run_images_pix_dets", "yolo2_hip_run_images_pix_f16_host",
     "yolo2_hip_run_images_pix_dets_f16", "yolo2_hip_multi_run_images_pix_host", "yolo2_hip_multi_run_images_pix_dets",
     "yolo2_hip_multi_run_images_pix_dets_f16",
+    "yolo2_hip_absmax_f32", "yolo2_hip_calib_reset", "yolo2_hip_calib_frames", "yolo2_hip_calib_images_pix_host", "yolo2_hip_calib_stats",
+    "yolo2_hip_calib_q_tables", "yolo2_hip_calib_q_from_stats", "yolo2_hip_quantize_weights_int16",
 ]
 
 # include/yolo2_hip.h YOLO2_PIX_*: the pixfmt argument of the _pix entries ("yuyv": packed YUYV 4:2:2, arrays uint8 [h][w][2])
@@ -239,6 +241,15 @@ def lib():
     sig("yolo2_hip_run_images_pix_f16_host", L.yolo2_hip_run_images_u8_f16_host.argtypes)
     for name in ("run_images_pix_dets_f16", "multi_run_images_pix_dets_f16"):
         sig("yolo2_hip_" + name, L.yolo2_hip_run_images_u8_dets_f16.argtypes)
+    # calibration (include/yolo2_hip.h "calibration")
+    sig("yolo2_hip_absmax_f32", [u64, C.c_size_t, C.POINTER(C.c_float), C.POINTER(u32), vp])
+    sig("yolo2_hip_calib_reset", [vp])
+    sig("yolo2_hip_calib_frames", [vp, u64, i32, vp])
+    sig("yolo2_hip_calib_images_pix_host", [vp, vp, vp, vp, i32, i32, i32])
+    sig("yolo2_hip_calib_stats", [vp, vp, vp, vp, C.POINTER(C.c_long)])
+    sig("yolo2_hip_calib_q_tables", [vp, C.c_float, vp, vp, vp])
+    sig("yolo2_hip_calib_q_from_stats", [vp, vp, vp, C.c_float, vp, vp, vp])
+    sig("yolo2_hip_quantize_weights_int16", [vp, vp, vp, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_long)])
     _lib = L
     return L
 
@@ -584,6 +595,161 @@ class Yolo2Hip:
         v = [C.c_int(0) for _ in range(5)]
         check(lib().yolo2_hip_conv_launch_info(self._h, ord_, *[C.byref(x) for x in v]), "conv_launch_info")
         return dict(zip(("grid_x", "grid_y", "block", "lds_bytes", "pixels_per_lane"), (x.value for x in v)))
+
+    # ---- calibration: fp32 weights + frames -> int16 weights and Q tables (CalibratedModel below)
+    def calib_reset(self):
+        check(lib().yolo2_hip_calib_reset(self._h), "yolo2_hip_calib_reset")
+
+    def calib_frames(self, frames: np.ndarray):
+        """One exact fp32 pass over host frames [B][3][416][416] + the abs-max reductions, accumulated (yolo2_hip_calib_frames)."""
+        buf = DevBuf(np.ascontiguousarray(frames, dtype=np.float32).reshape(-1, 3, 416, 416))
+        try:
+            check(lib().yolo2_hip_calib_frames(self._h, buf.addr, buf.nbytes // (4 * 3 * 416 * 416), None), "yolo2_hip_calib_frames")
+        finally:
+            buf.free()
+
+    def calib_images(self, images, batch: int, pixfmt=None):
+        """The same from host images (uint8 arrays as run_images_host takes them), letterboxed on the GPU in chunks of `batch`."""
+        imgs = [np.ascontiguousarray(im, dtype=np.uint8) for im in images]
+        if pixfmt is None:
+            pixfmt = "grey8" if imgs[0].ndim == 2 else "rgb24"
+        n, ptrs, ws, hs, fmt, _keep = _image_args(imgs, pixfmt)
+        check(lib().yolo2_hip_calib_images_pix_host(self._h, ptrs, ws, hs, fmt, n, batch), "yolo2_hip_calib_images_pix_host")
+
+    def calib_stats(self):
+        """dict(act_absmax [24], weight_absmax [23], bias_absmax [23], frames_seen) of the statistics accumulated so far"""
+        nconv = len(net.CONVS)
+        a, w, b = np.zeros(nconv + 1, np.float32), np.zeros(nconv, np.float32), np.zeros(nconv, np.float32)
+        seen = C.c_long(0)
+        vp = lambda v: v.ctypes.data_as(C.c_void_p)
+        check(lib().yolo2_hip_calib_stats(self._h, vp(a), vp(w), vp(b), C.byref(seen)), "yolo2_hip_calib_stats")
+        return {"act_absmax": a, "weight_absmax": w, "bias_absmax": b, "frames_seen": seen.value}
+
+    def calib_q_tables(self, headroom: float = 1.0):
+        nconv = len(net.CONVS)
+        wq, bq, aq = np.zeros(nconv, np.int32), np.zeros(nconv, np.int32), np.zeros(nconv + 1, np.int32)
+        vp = lambda v: v.ctypes.data_as(C.c_void_p)
+        check(lib().yolo2_hip_calib_q_tables(self._h, headroom, vp(wq), vp(bq), vp(aq)), "yolo2_hip_calib_q_tables")
+        return wq, bq, aq
+
+    def quantize_weights(self, weight_q, bias_q):
+        """The resident fp32 blobs as int16 = round(x * 2^Q) with the given tables, quantised on the GPU -> (weights, bias, clamped)."""
+        wq, bq = (np.ascontiguousarray(q, dtype=np.int32) for q in (weight_q, bias_q))
+        if wq.shape != (len(net.CONVS),) or bq.shape != wq.shape:
+            raise ValueError(f"Q tables hold {len(net.CONVS)} entries each")
+        w, b = np.empty(N_WEIGHTS, np.int16), np.empty(N_BIAS, np.int16)
+        clamped = C.c_long(0)
+        vp = lambda v: v.ctypes.data_as(C.c_void_p)
+        check(lib().yolo2_hip_quantize_weights_int16(self._h, vp(wq), vp(bq), vp(w), w.size, vp(b), b.size, C.byref(clamped)),
+              "yolo2_hip_quantize_weights_int16")
+        return w, b, clamped.value
+
+    def calibrate(self, frames=None, images=None, batch: int = 8, headroom: float = 1.0, pixfmt=None) -> "CalibratedModel":
+        """fp32 weights (load_weights_fp32) + calibration frames (float [n][3][416][416]) or images -> a CalibratedModel: statistics of
+        the exact fp32 pass in chunks of `batch`, the Q rule with `headroom`, the weights quantised on the GPU.  Starts from cleared
+        statistics."""
+        if (frames is None) == (images is None):
+            raise ValueError("calibrate takes frames=... or images=..., not both")
+        if batch < 1:
+            raise ValueError("batch must be positive")
+        self.calib_reset()
+        if frames is not None:
+            frames = np.ascontiguousarray(frames, dtype=np.float32).reshape(-1, 3, 416, 416)
+            for i in range(0, frames.shape[0], batch):
+                self.calib_frames(frames[i:i + batch])
+        else:
+            self.calib_images(images, batch, pixfmt)
+        st = self.calib_stats()
+        wq, bq, aq = self.calib_q_tables(headroom)
+        w, b, clamped = self.quantize_weights(wq, bq)
+        return CalibratedModel(w, b, wq, bq, aq, clamped, st["act_absmax"], st["weight_absmax"], st["bias_absmax"], st["frames_seen"])
+
+
+# ------------------------------------------------------------------ calibration: fp32 weights + frames -> an int16 weight set
+
+N_WEIGHTS, N_BIAS = net.N_WEIGHTS, net.N_BIAS   # include/yolo2_hip.h YOLO2_N_WEIGHTS / YOLO2_N_BIAS
+
+
+def absmax_f32(dev_addr: int, n: int, stream: int = 0):
+    """(max |x|, count of Inf / NaN) of n floats in HBM (yolo2_hip_absmax_f32); non-finite values are left out of the maximum."""
+    m, bad = C.c_float(0), C.c_uint32(0)
+    check(lib().yolo2_hip_absmax_f32(dev_addr, n, C.byref(m), C.byref(bad), C.c_void_p(stream)), "yolo2_hip_absmax_f32")
+    return np.float32(m.value), int(bad.value)
+
+
+def q_tables_from_stats(act_absmax, weight_absmax, bias_absmax, headroom: float = 1.0):
+    """The Q rule on explicit maxima (yolo2_hip_calib_q_from_stats; host arithmetic, no GPU): q = the largest integer in 0..15 with
+    headroom * max * 2^q < 32767.5, i.e. still rounding to at most 32767 (headroom on the conv outputs only), then the concat
+    fix-up.  -> (weight_q, bias_q, act_q)."""
+    nconv = len(net.CONVS)
+    a, w, b = (np.ascontiguousarray(v, dtype=np.float32) for v in (act_absmax, weight_absmax, bias_absmax))
+    if a.shape != (nconv + 1,) or w.shape != (nconv,) or b.shape != (nconv,):
+        raise ValueError(f"maxima are [{nconv + 1}] activations, [{nconv}] weights, [{nconv}] biases")
+    wq, bq, aq = np.zeros(nconv, np.int32), np.zeros(nconv, np.int32), np.zeros(nconv + 1, np.int32)
+    vp = lambda v: v.ctypes.data_as(C.c_void_p)
+    check(lib().yolo2_hip_calib_q_from_stats(vp(a), vp(w), vp(b), headroom, vp(wq), vp(bq), vp(aq)), "yolo2_hip_calib_q_from_stats")
+    return wq, bq, aq
+
+
+class CalibratedModel:
+    """An int16 weight set made by Yolo2Hip.calibrate / quantize_weights: what load_model, orclib.forward_i16 and the other users of
+    a synth.SynthModel read (weights_i16(), bias_i16(), the three Q tables), and the reference's five files."""
+
+    FILES = ("weights_reorg_int16.bin", "bias_int16.bin", "weight_int16_Q.bin", "bias_int16_Q.bin", "iofm_Q.bin")
+
+    def __init__(self, weights_i16, bias_i16, weight_q, bias_q, act_q, clamped=0, act_absmax=None, weight_absmax=None,
+                 bias_absmax=None, frames_seen=0):
+        self._w = np.ascontiguousarray(weights_i16, dtype=np.int16)
+        self._b = np.ascontiguousarray(bias_i16, dtype=np.int16)
+        self.weight_q, self.bias_q, self.act_q = (np.array(q, dtype=np.int32) for q in (weight_q, bias_q, act_q))
+        nconv = len(net.CONVS)
+        if self._w.shape != (N_WEIGHTS,) or self._b.shape != (N_BIAS,) or self.weight_q.shape != (nconv,) or \
+                self.bias_q.shape != (nconv,) or self.act_q.shape != (nconv + 1,):
+            raise ValueError("not a YOLOv2 int16 weight set")
+        self.clamped, self.frames_seen = int(clamped), int(frames_seen)
+        self.act_absmax, self.weight_absmax, self.bias_absmax = act_absmax, weight_absmax, bias_absmax
+
+    def weights_i16(self) -> np.ndarray:
+        return self._w
+
+    def bias_i16(self) -> np.ndarray:
+        return self._b
+
+    @staticmethod
+    def _with_layer_pad(flat, lens):
+        """the stream with one zero element after every odd-length layer (synth.SynthModel.write_files; yolo2_model.cpp:198-224)"""
+        out, off = [], 0
+        for n in lens:
+            out.append(flat[off:off + n])
+            if n & 1:
+                out.append(np.zeros(1, dtype=flat.dtype))
+            off += n
+        return np.concatenate(out)
+
+    def write_files(self, weights_dir: str):
+        os.makedirs(weights_dir, exist_ok=True)
+        arrays = (self._with_layer_pad(self._w, net.WEIGHT_LEN),
+                  self._with_layer_pad(self._b, net.BIAS_LEN), self.weight_q, self.bias_q, self.act_q)
+        paths = {}
+        for name, arr in zip(self.FILES, arrays):
+            paths[name] = os.path.join(weights_dir, name)
+            arr.tofile(paths[name])
+        return paths
+
+    @classmethod
+    def read_files(cls, weights_dir: str):
+        """the five files back (per-layer pads stripped)"""
+        def strip(flat, lens):
+            out, off = [], 0
+            for n in lens:
+                out.append(flat[off:off + n])
+                off += n + (n & 1)
+            if off != flat.size:
+                raise ValueError(f"{flat.size} elements on file, the layer table wants {off}")
+            return np.concatenate(out)
+        rd = lambda name, dt: np.fromfile(os.path.join(weights_dir, name), dtype=dt)
+        return cls(strip(rd(cls.FILES[0], np.int16), net.WEIGHT_LEN), strip(rd(cls.FILES[1], np.int16), net.BIAS_LEN),
+                   rd(cls.FILES[2], np.int32), rd(cls.FILES[3], np.int32), rd(cls.FILES[4], np.int32))
 
 
 # ------------------------------------------------------------------ post-processing on the GPU
