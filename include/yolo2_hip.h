@@ -488,6 +488,36 @@ int yolo2_hip_run_images_pix_dets_f16(yolo2_hip_ctx *ctx, int split, const uint8
                                       const int *heights, int pixfmt, int n, int batch, float thresh, float nms, int flags,
                                       yolo2_hip_det *dets, int cap_per_frame, int *counts);
 
+/* ------------------------------------------------------- annotated frames: the records painted into the frames they came from
+ *
+ * The reference's camera / video loop ends every frame with yolo2_draw_detections_rgb24 (linux_app/src/yolo2_draw.c:276-369, called at
+ * linux_app/src/main.c:1079-1091) and hands the RGB24 frame to --save-annotated-dir or the MJPEG streamer.  These entries make that
+ * frame on the GPU, bit-identical, from the frame in its camera format (YOLO2_PIX_*: RGB24 copied, GREY8 replicated, YUYV converted
+ * as above) and records of the YOLO2_DETS_BEST_CLASS form (one per detection), whichever pass produced them; no weights are needed.
+ *   which records   in array order, those with prob > thresh (and cls >= 0); later records paint over earlier ones
+ *   box             corners (int)((x -+ w * 0.5f) * width) etc. in fp32, NaN / out-of-int-range products -> INT_MIN, each clamped to
+ *                   the image; 2 pixels thick, every ring clamped again (yolo2_draw_rect_rgb24, :94-111); colour palette[cls % 8]
+ *   tag             "<label> <prob %.2f>", at most 127 characters, label = labels[cls] or "class<cls>" (labels NULL, cls >= n_labels, labels[cls] NULL);
+ *                   5x7 font at scale 2 (a-z, A-Z as lower case, digits, '.'; anything else a blank that still takes its cell),
+ *                   black text on a bright tag (r + g + b > 382), white otherwise; the tag's top is y0 - 18, or y0 + 1 if that is
+ *                   negative; rectangle and glyph pixels are cut at the image's edges
+ * y2h_draw_detections_rgb24 (libyolo2_host.so) is the same on the host.  Bad arguments - a null pointer, an odd YUYV width, an
+ * unknown pixfmt, thresh < 0, a non-positive size, a non-finite prob among the records to be used - are YOLO2_ERROR
+ * (yolo2_hip_last_error names the cause) before anything is launched. */
+
+/* One image already on the calling thread's device (the analogue of yolo2_hip_letterbox_pix): image_dev in `pixfmt` (YUYV on a
+ * 4-byte boundary) -> rgb_out_dev, w * h * 3 bytes.  dets are n_dets HOST records (NULL if n_dets is 0), labels may be NULL, *drawn
+ * (may be NULL) = the records drawn.  Enqueues on `stream` and synchronises it. */
+int yolo2_hip_annotate_pix(uint64_t image_dev, int w, int h, int pixfmt, const yolo2_hip_det *dets, int n_dets, float thresh,
+                           const char *const *labels, int n_labels, uint64_t rgb_out_dev, int *drawn, void *stream);
+/* n images as HOST bytes with the records a yolo2_hip_run_images_*_dets* call returned for them: images / widths / heights / pixfmt
+ * and dets [n][cap_per_frame] / counts [n] exactly as that call took and filled them; frame f uses min(counts[f], cap_per_frame)
+ * records.  annotated[f] receives w * h * 3 bytes; drawn [n] may be NULL.  Chunks of `batch` (at most 1024); upload, kernel and
+ * download of consecutive chunks overlap on three streams through pinned staging the context keeps.  Synchronous. */
+int yolo2_hip_annotate_images_pix_host(yolo2_hip_ctx *ctx, const uint8_t *const *images, const int *widths, const int *heights,
+                                       int pixfmt, int n, int batch, const yolo2_hip_det *dets, int cap_per_frame, const int *counts,
+                                       float thresh, const char *const *labels, int n_labels, uint8_t *const *annotated, int *drawn);
+
 /* ------------------------------------------------------- calibration: fp32 weights + frames -> int16 weights and Q tables
  *
  * The reference makes its int16 weight set with a separate tool (weights/README.md step 2b: "activation-calibrated"
@@ -586,6 +616,12 @@ int  yolo2_hip_multi_run_images_pix_dets(yolo2_hip_multi *m, const uint8_t *cons
 int  yolo2_hip_multi_run_images_pix_dets_f16(yolo2_hip_multi *m, int split, const uint8_t *const *images, const int *widths,
                                              const int *heights, int pixfmt, int n, int batch_per_device, float thresh, float nms,
                                              int flags, yolo2_hip_det *dets, int cap_per_frame, int *counts);
+
+/* annotated frames (see yolo2_hip_annotate_images_pix_host), shard i painted by device i */
+int  yolo2_hip_multi_annotate_images_pix_host(yolo2_hip_multi *m, const uint8_t *const *images, const int *widths, const int *heights,
+                                              int pixfmt, int n, int batch_per_device, const yolo2_hip_det *dets, int cap_per_frame,
+                                              const int *counts, float thresh, const char *const *labels, int n_labels,
+                                              uint8_t *const *annotated, int *drawn);
 
 /* (b) one process per device (torchrun / MPI style; what bench.py --gpus N runs): rank 0 makes the 128-byte id
  * (ncclGetUniqueId), the launcher hands it to every rank, each rank joins with its context (ncclCommInitRank), then

@@ -13,7 +13,8 @@ FLAGS="-O3 -std=c++17 --offload-arch=gfx950 -fPIC -Wno-unused-function -ffp-cont
 [ "$TU" = yolo2_fp16 ] && FLAGS="$FLAGS -mllvm -amdgpu-mfma-vgpr-form"     # (the Makefile's TUFLAGS_yolo2_fp16)
 /opt/rocm/bin/hipcc $FLAGS "$@" -c -o "$P/build/${TU}_$NAME.o" "$P/csrc/$TU.hip"
 OBJS=""
-for t in yolo2_hip yolo2_driver yolo2_plan yolo2_int16 yolo2_fp16 yolo2_fp32 yolo2_multi yolo2_post; do
+TUS=$(sed -n 's/^HIP_TUS *:= *//p' "$P/Makefile")     # the Makefile's list of translation units: every object of the library
+for t in $TUS; do
   if [ "$t" = "$TU" ]; then OBJS="$OBJS $P/build/${TU}_$NAME.o"; else OBJS="$OBJS $P/build/$t.o"; fi
 done
 /opt/rocm/bin/hipcc $FLAGS -shared -o "$P/build/lib_$NAME.so" $OBJS -ldl

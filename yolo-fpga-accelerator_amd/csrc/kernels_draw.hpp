@@ -1,0 +1,216 @@
+// kernels_draw.hpp -- the annotated frame on the GPU: source pixels in their camera format -> packed RGB24 with the boxes and tags of
+// the reference's yolo2_draw_detections_rgb24 (linux_app/src/yolo2_draw.c:276-369) painted in, one read and one write per pixel.
+//
+// The reference paints record after record into the frame, later records over earlier ones, per record the border, the tag's
+// rectangle, the glyphs.  Here every output pixel asks the frame's draw list (draw_list.hpp: one DrawItem per drawn record, made on
+// the host) from its LAST item back to its first and takes the first item that covers it - within an item the tag (glyph bit: text
+// colour, else the tag's colour) before the two border rings.  That is the painter's result without a write race: a pixel is
+// stored once.  Glyph pixels need no test of their own outside the tag: every glyph pixel inside the image lies inside the clamped
+// tag rectangle (the text sits 2 pixels inside the unclamped one, and the clamp only cuts at the image's edges).
+//
+// Work split: a frame's pixels are one flat run (packed RGB24 has no row padding); a workgroup takes a strip of kAnnoStripPx
+// consecutive pixels, a lane kAnnoGroups runs of 4 pixels = 12 bytes = 3 dwords of it.  A run is loaded and stored as dwords where
+// the frame's base is 4-byte aligned and the run is whole, and byte by byte otherwise (a frame's last, short run; a caller's odd
+// address).  A workgroup stages in LDS the items whose extent (box united with tag) meets the rows of its strip, kAnnoPiece items
+// of the list at a time, in list order from the back.  A frame without items is a pure convert / copy.
+//
+// Launched from yolo2_draw.hip only.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "draw_list.hpp"
+#include "letterbox.hpp"
+
+namespace y2 {
+
+using y2d::DrawItem;
+
+// The table that leads a chunk's staging buffer (LetterboxItem leads the letterbox chunk the same way): header, one AnnoFrame per
+// frame, the draw items of all frames.
+struct AnnoHeader {
+    uint64_t font[y2d::kDrawGlyphs];   // y2d::kDrawFont
+    unsigned long long items_off;      // where the DrawItem array starts, in bytes from the table
+};
+struct AnnoFrame {
+    unsigned long long src_off, out_off;   // the frame's source bytes / its RGB24 output, in bytes from the two base addresses
+    int w, h, ch;                          // ch: source bytes per pixel - 1 grey, 3 RGB24, 2 packed YUYV 4:2:2 (w even, 4-byte aligned)
+    int item0, n_items;                    // its items in the array, in record order
+    int strips;                            // workgroups that have work on it: ceil(w * h / kAnnoStripPx)
+};
+
+constexpr int kAnnoThreads = 256, kAnnoGroups = 4, kAnnoStripPx = kAnnoThreads * kAnnoGroups * 4, kAnnoPiece = 128;
+constexpr int kAnnoItemDwords = (int)(sizeof(DrawItem) / 4);
+static_assert(sizeof(DrawItem) % 4 == 0 && kAnnoPiece <= kAnnoThreads, "items are copied dword by dword, one lane tests one item");
+
+// One pixel of a loaded YUYV pair (bytes Y0 U Y1 V) -> R | G << 8 | B << 16: the conversion of the YUYV entries (letterbox.hpp, LbYuyv
+// - its arithmetic on a dword that is loaded once per pair; tests/test_gpu_draw.py holds the two together)
+__device__ inline uint32_t anno_yuyv_px(uint32_t pair, int odd)
+{
+    const int c = 298 * ((int)((pair >> (odd * 16)) & 255u) - 16) + 128, d = (int)((pair >> 8) & 255u) - 128, e = (int)(pair >> 24) - 128;
+    const int r = min(max((c + 409 * e) >> 8, 0), 255), g = min(max((c - 100 * d - 208 * e) >> 8, 0), 255), b = min(max((c + 516 * d) >> 8, 0), 255);
+    return (uint32_t)r | ((uint32_t)g << 8) | ((uint32_t)b << 16);
+}
+
+// source pixel p of a frame -> R | G << 8 | B << 16
+__device__ inline uint32_t anno_load_px(const uint8_t *__restrict__ src, int ch, int p)
+{
+    if (ch == 3) return (uint32_t)src[(size_t)p * 3] | ((uint32_t)src[(size_t)p * 3 + 1] << 8) | ((uint32_t)src[(size_t)p * 3 + 2] << 16);
+    if (ch == 1) return (uint32_t)src[p] * 0x010101u;
+    return anno_yuyv_px(reinterpret_cast<const uint32_t *>(src)[p >> 1], p & 1);   // (the frame as one row of pairs)
+}
+
+// does `it` paint pixel (x, y)?  c: the colour it leaves there
+__device__ inline bool anno_hit(const DrawItem &it, const uint64_t *font, int x, int y, uint32_t &c)
+{
+    if (x < it.ext[0] || x > it.ext[2] || y < it.ext[1] || y > it.ext[3]) return false;
+    if (x >= it.tag[0] && x <= it.tag[2] && y >= it.tag[1] && y <= it.tag[3]) {
+        c = it.box_rgb;
+        const int dx = x - it.gx, dy = y - it.gy;
+        if (dx >= 0 && dy >= 0 && dy < y2d::kDrawGlyphH && dx < it.nchar * y2d::kDrawCell) {
+            const int k = dx / y2d::kDrawCell, cx = (dx - k * y2d::kDrawCell) / y2d::kDrawScale;
+            if (cx < 5 && ((font[it.text[k]] >> (5 * (dy / y2d::kDrawScale) + cx)) & 1)) c = it.text_rgb;
+        }
+        return true;
+    }
+#pragma unroll
+    for (int t = 0; t < y2d::kDrawThick; ++t) {
+        const int *r = it.ring[t];
+        if (((y == r[1] || y == r[3]) && x >= r[0] && x <= r[2]) || ((x == r[0] || x == r[2]) && y >= r[1] && y <= r[3])) {
+            c = it.box_rgb;
+            return true;
+        }
+    }
+    return false;
+}
+
+// grid (max strips of the chunk's frames, frames); table: AnnoHeader, AnnoFrame[frames], DrawItem[]
+__global__ __launch_bounds__(kAnnoThreads) void k_annotate_batch(const uint8_t *__restrict__ table, const uint8_t *__restrict__ src_base,
+                                                                 uint8_t *__restrict__ out_base)
+{
+    __shared__ uint64_t s_font[y2d::kDrawGlyphs];
+    __shared__ DrawItem s_items[kAnnoPiece];
+    __shared__ int s_sel[kAnnoPiece];
+    __shared__ int s_wave[kAnnoThreads / 64];
+
+    const AnnoHeader *hd = reinterpret_cast<const AnnoHeader *>(table);
+    const AnnoFrame fr = reinterpret_cast<const AnnoFrame *>(table + sizeof(AnnoHeader))[blockIdx.y];
+    if ((int)blockIdx.x >= fr.strips) return;   // (the whole workgroup)
+    const DrawItem *items = reinterpret_cast<const DrawItem *>(table + hd->items_off) + fr.item0;
+    const int tid = threadIdx.x;
+    if (tid < y2d::kDrawGlyphs) s_font[tid] = hd->font[tid];
+
+    const int npx = fr.w * fr.h;
+    const int p_lo = (int)blockIdx.x * kAnnoStripPx, p_hi = min(npx, p_lo + kAnnoStripPx);
+    const int ya = p_lo / fr.w, yb = (p_hi - 1) / fr.w;   // the rows this strip touches
+    const uint8_t *src = src_base + fr.src_off;
+    uint8_t *out = out_base + fr.out_off;
+    const bool src_al = ((uintptr_t)src & 3) == 0, out_al = ((uintptr_t)out & 3) == 0;
+
+    // ---- this lane's pixels: run j starts at pixel p_lo + (j * 256 + tid) * 4
+    uint32_t col[kAnnoGroups * 4];
+    int px[kAnnoGroups * 4], py[kAnnoGroups * 4];
+    unsigned todo = 0;   // bit k: pixel k exists and no item has painted it yet
+#pragma unroll
+    for (int j = 0; j < kAnnoGroups; ++j) {
+        const int p = p_lo + (j * kAnnoThreads + tid) * 4;
+        if (p >= p_hi) continue;
+        const bool whole = p + 4 <= p_hi;
+        if (whole && src_al && fr.ch == 3) {
+            const uint32_t *s = reinterpret_cast<const uint32_t *>(src + (size_t)p * 3);
+            const uint32_t d0 = s[0], d1 = s[1], d2 = s[2];
+            col[4 * j] = d0 & 0xffffffu;
+            col[4 * j + 1] = (d0 >> 24) | ((d1 & 0xffffu) << 8);
+            col[4 * j + 2] = (d1 >> 16) | ((d2 & 0xffu) << 16);
+            col[4 * j + 3] = d2 >> 8;
+        } else if (whole && fr.ch == 2) {   // (a YUYV frame starts on a 4-byte boundary: the entries refuse any other)
+            const uint32_t *s = reinterpret_cast<const uint32_t *>(src + (size_t)p * 2);
+            const uint32_t d0 = s[0], d1 = s[1];
+            col[4 * j] = anno_yuyv_px(d0, 0);
+            col[4 * j + 1] = anno_yuyv_px(d0, 1);
+            col[4 * j + 2] = anno_yuyv_px(d1, 0);
+            col[4 * j + 3] = anno_yuyv_px(d1, 1);
+        } else if (whole && src_al && fr.ch == 1) {
+            const uint32_t d = *reinterpret_cast<const uint32_t *>(src + p);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) col[4 * j + i] = ((d >> (8 * i)) & 255u) * 0x010101u;
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) col[4 * j + i] = p + i < p_hi ? anno_load_px(src, fr.ch, p + i) : 0u;
+        }
+        const int y0 = p / fr.w;
+        int x = p - y0 * fr.w, y = y0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            px[4 * j + i] = x;
+            py[4 * j + i] = y;
+            if (p + i < p_hi) todo |= 1u << (4 * j + i);
+            if (++x == fr.w) { x = 0; ++y; }
+        }
+    }
+
+    // ---- the draw list from the back, kAnnoPiece items at a time
+    for (int hi = fr.n_items; hi > 0; hi -= kAnnoPiece) {
+        const int cnt = min(kAnnoPiece, hi);
+        __syncthreads();   // the piece before this one has been read by everybody (first time round: s_font is written)
+        // lane t looks at item hi - 1 - t; the items that meet the strip keep that order in s_sel
+        bool meets = false;
+        if (tid < cnt) {
+            const DrawItem &g = items[hi - 1 - tid];
+            meets = g.ext[1] <= yb && g.ext[3] >= ya;
+        }
+        const unsigned long long m = __ballot(meets);
+        const int wave = tid >> 6, lane = tid & 63;
+        if (lane == 0) s_wave[wave] = __popcll(m);
+        __syncthreads();
+        int before = 0, nsel = 0;
+#pragma unroll
+        for (int v = 0; v < kAnnoThreads / 64; ++v) {
+            if (v < wave) before += s_wave[v];
+            nsel += s_wave[v];
+        }
+        if (meets) s_sel[before + __popcll(m & ((1ull << lane) - 1ull))] = hi - 1 - tid;
+        __syncthreads();
+        for (int e = tid; e < nsel * kAnnoItemDwords; e += kAnnoThreads) {
+            const int s = e / kAnnoItemDwords, d = e - s * kAnnoItemDwords;
+            reinterpret_cast<uint32_t *>(s_items)[e] = reinterpret_cast<const uint32_t *>(items + s_sel[s])[d];
+        }
+        __syncthreads();
+        for (int s = 0; s < nsel && todo; ++s) {
+            const DrawItem &it = s_items[s];
+#pragma unroll
+            for (int k = 0; k < kAnnoGroups * 4; ++k) {
+                uint32_t c;
+                if (((todo >> k) & 1u) && anno_hit(it, s_font, px[k], py[k], c)) {
+                    col[k] = c;
+                    todo &= ~(1u << k);
+                }
+            }
+        }
+    }
+
+    // ---- packed RGB24 out
+#pragma unroll
+    for (int j = 0; j < kAnnoGroups; ++j) {
+        const int p = p_lo + (j * kAnnoThreads + tid) * 4;
+        if (p >= p_hi) continue;
+        if (p + 4 <= p_hi && out_al) {
+            uint32_t *o = reinterpret_cast<uint32_t *>(out + (size_t)p * 3);
+            const uint32_t c0 = col[4 * j] & 0xffffffu, c1 = col[4 * j + 1] & 0xffffffu, c2 = col[4 * j + 2] & 0xffffffu, c3 = col[4 * j + 3] & 0xffffffu;
+            o[0] = c0 | (c1 << 24);
+            o[1] = (c1 >> 8) | (c2 << 16);
+            o[2] = (c2 >> 16) | (c3 << 8);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                if (p + i >= p_hi) break;
+                uint8_t *o = out + (size_t)(p + i) * 3;
+                o[0] = (uint8_t)col[4 * j + i];
+                o[1] = (uint8_t)(col[4 * j + i] >> 8);
+                o[2] = (uint8_t)(col[4 * j + i] >> 16);
+            }
+        }
+    }
+}
+
+}  // namespace y2

@@ -1,0 +1,11 @@
+// y2_draw.hpp -- what yolo2_draw.hip offers the other translation units beside the C ABI (yolo2_multi.hip uses the C ABI only and
+// does not include y2_internal.hpp).
+#pragma once
+#include <cstdint>
+
+#include "../../include/yolo2_hip.h"
+
+// Everything the batched annotate entries refuse, looked at before anything is allocated or launched (the multi entry asks for the
+// whole call before it starts a shard).  YOLO2_SUCCESS, or YOLO2_ERROR with the cause in yolo2_hip_last_error.
+int y2_annotate_check(const uint8_t *const *images, const int *widths, const int *heights, int pixfmt, int n, int batch, const yolo2_hip_det *dets,
+                      int cap_per_frame, const int *counts, float thresh, int n_labels, uint8_t *const *annotated);

@@ -8,6 +8,7 @@
 //   yolo2_fp32.hip    the exact fp32 path (tiled and one-thread-per-output)
 //   yolo2_calib.hip   fp32 weights + calibration frames -> Q tables and int16 weights (statistics of the exact fp32 pass)
 //   yolo2_post.hip    region layer + boxes + NMS;   yolo2_multi.hip  frame sharding + the RCCL weight broadcast
+//   yolo2_draw.hip    annotated frames: records + frames -> RGB24 with the reference's boxes and tags
 // Every non-template kernel is launched from exactly one of them (its kernels_*.hpp is included there only).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -218,10 +219,21 @@ struct PipeBufs {
     Y2PinBuf<float> hregf[2];
 };
 
+// Staging of yolo2_hip_annotate_images_pix_host (yolo2_draw.hip): two buffer sets - pinned and device staging for a chunk's table,
+// draw items and frame bytes, device and pinned RGB24 output - and three streams, grown on demand and kept with the context.
+struct Y2AnnoBufs {
+    size_t cap_in = 0, cap_out = 0;
+    Y2PinBuf<uint8_t> hin[2], hout[2];
+    Y2DevBuf<uint8_t> din[2], dout[2];
+    hipStream_t s_in = nullptr, s_run = nullptr, s_out = nullptr;
+    hipEvent_t e_in[2] = {nullptr, nullptr}, e_run[2] = {nullptr, nullptr}, e_out[2] = {nullptr, nullptr};
+};
+
 struct F16Plan;   // yolo2_fp16.hip: the per-context launch table of the fp16 path
 
 struct yolo2_hip_ctx {
     PipeBufs pipe;
+    Y2AnnoBufs anno;
     int device = 0;
     Y2Options opt;                     // parsed once at creation (environment), changed only by yolo2_hip_set_option; lanes copy it
     std::shared_ptr<Y2PlanCache> plan_cache;   // weight-side cache bound by yolo2_hip_set_plan_cache (lanes share the parent's)
@@ -404,6 +416,9 @@ void y2_drv_release_i16(void);   // frees the grow-only scratch of y2_drv_conv_i
 // yolo2_fp32.hip:
 void y2_drv_conv_f32(const float *in, float *out, const float *w, const float *beta, int ifm, int ofm, int ksize, int kstride, int iw,
                      int ih, int ow, int oh, int pad, int is_nl);
+
+// yolo2_draw.hip: the streams, events and buffers of c->anno (yolo2_hip_destroy)
+void y2_anno_free(yolo2_hip_ctx *c);
 
 // yolo2_calib.hip: one exact fp32 pass over `batch` device frames + the abs-max reductions, accumulated into c->calib_stats; `counted`
 // of the frames are new ones (the images entry pads a short last chunk by repeating its last image).  Synchronises st.

@@ -1,0 +1,271 @@
+// yolo2_draw.hip -- annotated frames (include/yolo2_hip.h, "annotated frames"): detection records + the frames they came from ->
+// RGB24 frames with the boxes and tags of the reference's yolo2_draw_detections_rgb24 painted in, bit-identical.
+//
+// The host turns records into draw items (draw_list.hpp: corner casts, "%s %.2f" through the host's snprintf, glyph indices), the
+// items travel with the frame bytes, and k_annotate_batch (kernels_draw.hpp) converts and paints in one pass per pixel.  One entry
+// serves the records of every precision: it needs the frames and the records, no weights.
+#include "y2_internal.hpp"
+#include "kernels_draw.hpp"
+#include "y2_draw.hpp"
+
+#include <cmath>
+
+using namespace y2;
+using y2d::DrawDet;
+
+static_assert(sizeof(DrawDet) == sizeof(yolo2_hip_det), "draw_list.hpp restates yolo2_hip_det");
+
+namespace {
+
+size_t padded(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// pixfmt -> source bytes per pixel (AnnoFrame::ch); 0 and the error for anything else
+int anno_channels(int pixfmt)
+{
+    if (pixfmt == YOLO2_PIX_GREY8) return 1;
+    if (pixfmt == YOLO2_PIX_RGB24) return 3;
+    if (pixfmt == YOLO2_PIX_YUYV) return 2;
+    (void)fail(YOLO2_ERROR, "annotate: unknown pixel format 0x%x (YOLO2_PIX_GREY8, YOLO2_PIX_RGB24 or YOLO2_PIX_YUYV)", (unsigned)pixfmt);
+    return 0;
+}
+
+int check_geometry(int w, int h, int ch, int frame)
+{
+    if (w <= 0 || h <= 0) return fail(YOLO2_ERROR, "annotate: bad frame size %dx%d (frame %d)", w, h, frame);
+    if ((long)w * h > (1L << 28)) return fail(YOLO2_ERROR, "annotate: frame %d too large (%dx%d)", frame, w, h);
+    if (ch == 2 && (w & 1)) return fail(YOLO2_ERROR, "annotate: YUYV frames have an even width, not %d (frame %d)", w, frame);
+    return YOLO2_SUCCESS;
+}
+
+int check_records(const yolo2_hip_det *dets, int n, int frame)
+{
+    for (int i = 0; i < n; ++i)
+        if (!std::isfinite(dets[i].prob)) return fail(YOLO2_ERROR, "annotate: record %d of frame %d has a non-finite prob", i, frame);
+    return YOLO2_SUCCESS;
+}
+
+int check_common(float thresh, int n_labels)
+{
+    if (!(thresh >= 0.f)) return fail(YOLO2_ERROR, "annotate: thresh %g is negative or not a number", (double)thresh);
+    if (n_labels < 0) return fail(YOLO2_ERROR, "annotate: negative label count %d", n_labels);
+    return YOLO2_SUCCESS;
+}
+
+// the records of one frame that are drawn (draw_make_item's rule), without making the items
+int count_drawn(const yolo2_hip_det *dets, int n, float thresh)
+{
+    int k = 0;
+    for (int i = 0; i < n; ++i) k += dets[i].prob > thresh && dets[i].cls >= 0;
+    return k;
+}
+
+// One chunk's table at `tbl` (table_bytes(nf, items) bytes): header, frames, items.  src_off / out_off / geometry of each frame
+// come from the caller; this fills the items and their ranges.  drawn (optional) [nf].
+struct FrameIn {
+    int w, h, ch;
+    size_t src_off, out_off;
+    const yolo2_hip_det *dets;
+    int n_dets;
+};
+size_t table_bytes(int nf, size_t items)
+{
+    return padded(sizeof(AnnoHeader) + (size_t)nf * sizeof(AnnoFrame)) + padded(items * sizeof(DrawItem));
+}
+int fill_table(uint8_t *tbl, const FrameIn *fr, int nf, float thresh, const char *const *labels, int n_labels, int *drawn)
+{
+    AnnoHeader *hd = reinterpret_cast<AnnoHeader *>(tbl);
+    for (int i = 0; i < y2d::kDrawGlyphs; ++i) hd->font[i] = y2d::kDrawFont[i];
+    hd->items_off = padded(sizeof(AnnoHeader) + (size_t)nf * sizeof(AnnoFrame));
+    AnnoFrame *af = reinterpret_cast<AnnoFrame *>(tbl + sizeof(AnnoHeader));
+    DrawItem *items = reinterpret_cast<DrawItem *>(tbl + hd->items_off);
+    int at = 0, max_strips = 0;
+    for (int f = 0; f < nf; ++f) {
+        af[f].src_off = fr[f].src_off;
+        af[f].out_off = fr[f].out_off;
+        af[f].w = fr[f].w; af[f].h = fr[f].h; af[f].ch = fr[f].ch;
+        af[f].item0 = at;
+        for (int i = 0; i < fr[f].n_dets; ++i) {
+            DrawDet d;
+            memcpy(&d, &fr[f].dets[i], sizeof(d));
+            if (y2d::draw_make_item(d, fr[f].w, fr[f].h, thresh, labels, n_labels, &items[at])) ++at;
+        }
+        af[f].n_items = at - af[f].item0;
+        af[f].strips = (int)(((long)fr[f].w * fr[f].h + kAnnoStripPx - 1) / kAnnoStripPx);
+        max_strips = std::max(max_strips, af[f].strips);
+        if (drawn) drawn[f] = af[f].n_items;
+    }
+    return max_strips;
+}
+
+void launch_annotate(const uint8_t *table_dev, const uint8_t *src_base, uint8_t *out_base, int max_strips, int nf, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_annotate_batch, dim3((unsigned)max_strips, (unsigned)nf), dim3(kAnnoThreads), 0, st, table_dev, src_base, out_base);
+}
+
+}  // namespace
+
+// ---------------------------------------------------------------------------- one image already on the device
+
+extern "C" int yolo2_hip_annotate_pix(uint64_t image_dev, int w, int h, int pixfmt, const yolo2_hip_det *dets, int n_dets, float thresh,
+                                      const char *const *labels, int n_labels, uint64_t rgb_out_dev, int *drawn, void *stream)
+{
+    if (!image_dev || !rgb_out_dev) return fail(YOLO2_ERROR, "annotate: null buffer address");
+    if (n_dets < 0 || (n_dets > 0 && !dets)) return fail(YOLO2_ERROR, "annotate: null records (n_dets %d)", n_dets);
+    const int ch = anno_channels(pixfmt);
+    if (!ch) return YOLO2_ERROR;
+    int rc;
+    if ((rc = check_geometry(w, h, ch, 0)) || (rc = check_common(thresh, n_labels)) || (rc = check_records(dets, n_dets, 0))) return rc;
+    if (ch == 2 && (image_dev & 3)) return fail(YOLO2_ERROR, "annotate: a YUYV frame starts on a 4-byte boundary");
+    const FrameIn fr = {w, h, ch, 0, 0, dets, n_dets};
+    const size_t bytes = table_bytes(1, (size_t)count_drawn(dets, n_dets, thresh));
+    std::vector<uint8_t> tbl(bytes);
+    int n_drawn = 0;
+    const int max_strips = fill_table(tbl.data(), &fr, 1, thresh, labels, n_labels, &n_drawn);
+    Y2DevBuf<uint8_t> dtbl;
+    if ((rc = dtbl.alloc(bytes))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(hipMemcpyAsync(dtbl.get(), tbl.data(), bytes, hipMemcpyHostToDevice, st), YOLO2_DMA_ERROR);
+    launch_annotate(dtbl.get(), (const uint8_t *)(uintptr_t)image_dev, (uint8_t *)(uintptr_t)rgb_out_dev, max_strips, 1, st);
+    HIP_TRY(hipGetLastError(), YOLO2_ERROR);
+    HIP_TRY(hipStreamSynchronize(st), YOLO2_ERROR);
+    if (drawn) *drawn = n_drawn;
+    return YOLO2_SUCCESS;
+}
+
+// ---------------------------------------------------------------------------- n host images, chunks of `batch`
+
+void y2_anno_free(yolo2_hip_ctx *c)
+{
+    Y2AnnoBufs &a = c->anno;
+    for (int k = 0; k < 2; ++k)
+        for (hipEvent_t *e : {&a.e_in[k], &a.e_run[k], &a.e_out[k]})
+            if (*e) { (void)hipEventDestroy(*e); *e = nullptr; }
+    for (hipStream_t *s : {&a.s_in, &a.s_run, &a.s_out})
+        if (*s) { (void)hipStreamDestroy(*s); *s = nullptr; }
+    for (int k = 0; k < 2; ++k) { a.hin[k].reset(); a.hout[k].reset(); a.din[k].reset(); a.dout[k].reset(); }
+    a.cap_in = a.cap_out = 0;
+}
+
+// two buffer sets of at least cap_in staging bytes (table + items + frames) and cap_out output bytes; three streams.  Grown on demand
+// and kept with the context, like PipeBufs.
+static int anno_ensure(yolo2_hip_ctx *c, size_t cap_in, size_t cap_out)
+{
+    Y2AnnoBufs &a = c->anno;
+    if (a.s_in && a.cap_in >= cap_in && a.cap_out >= cap_out) return YOLO2_SUCCESS;
+    cap_in = std::max(cap_in, a.cap_in);
+    cap_out = std::max(cap_out, a.cap_out);
+    y2_anno_free(c);
+    bool ok = true;
+    for (int k = 0; k < 2 && ok; ++k)
+        ok = a.hin[k].alloc(cap_in) == YOLO2_SUCCESS && a.din[k].alloc(cap_in) == YOLO2_SUCCESS && a.hout[k].alloc(cap_out) == YOLO2_SUCCESS &&
+             a.dout[k].alloc(cap_out) == YOLO2_SUCCESS && hipEventCreateWithFlags(&a.e_in[k], hipEventDisableTiming) == hipSuccess &&
+             hipEventCreateWithFlags(&a.e_run[k], hipEventDisableTiming) == hipSuccess &&
+             hipEventCreateWithFlags(&a.e_out[k], hipEventDisableTiming) == hipSuccess;
+    ok = ok && hipStreamCreateWithFlags(&a.s_in, hipStreamNonBlocking) == hipSuccess &&
+         hipStreamCreateWithFlags(&a.s_run, hipStreamNonBlocking) == hipSuccess &&
+         hipStreamCreateWithFlags(&a.s_out, hipStreamNonBlocking) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        y2_anno_free(c);
+        return fail(YOLO2_MMAP_ERROR, "annotate: staging buffers (%zu + %zu bytes, twice) could not be allocated", cap_in, cap_out);
+    }
+    a.cap_in = cap_in;
+    a.cap_out = cap_out;
+    return YOLO2_SUCCESS;
+}
+
+// (y2_draw.hpp)
+int y2_annotate_check(const uint8_t *const *images, const int *widths, const int *heights, int pixfmt, int n, int batch, const yolo2_hip_det *dets,
+                      int cap_per_frame, const int *counts, float thresh, int n_labels, uint8_t *const *annotated)
+{
+    if (!images || !widths || !heights || !dets || !counts || !annotated) return fail(YOLO2_ERROR, "annotate: null argument");
+    const int ch = anno_channels(pixfmt);
+    if (!ch) return YOLO2_ERROR;
+    if (n <= 0 || batch <= 0 || batch > 1024 || cap_per_frame <= 0)
+        return fail(YOLO2_ERROR, "annotate: bad image count %d / batch %d (1..1024) / capacity %d", n, batch, cap_per_frame);
+    int rc;
+    if ((rc = check_common(thresh, n_labels))) return rc;
+    for (int f = 0; f < n; ++f) {
+        if (!images[f] || !annotated[f]) return fail(YOLO2_ERROR, "annotate: null image or output %d", f);
+        if (counts[f] < 0) return fail(YOLO2_ERROR, "annotate: negative record count %d of frame %d", counts[f], f);
+        if ((rc = check_geometry(widths[f], heights[f], ch, f)) ||
+            (rc = check_records(dets + (size_t)f * cap_per_frame, std::min(counts[f], cap_per_frame), f)))
+            return rc;
+    }
+    return YOLO2_SUCCESS;
+}
+
+// Upload of chunk k + 1 (host staging copy, item making, DMA) overlaps the kernel of chunk k and the download of chunk k - 1: the
+// three-stream pipeline of the images entries (yolo2_hip.hip), with the RGB24 frames as the product that comes back.
+extern "C" int yolo2_hip_annotate_images_pix_host(yolo2_hip_ctx *c, const uint8_t *const *images, const int *widths, const int *heights,
+                                                  int pixfmt, int n, int batch, const yolo2_hip_det *dets, int cap_per_frame,
+                                                  const int *counts, float thresh, const char *const *labels, int n_labels,
+                                                  uint8_t *const *annotated, int *drawn)
+{
+    if (!c) return fail(YOLO2_ERROR, "annotate: null argument");
+    int rc;
+    if ((rc = y2_annotate_check(images, widths, heights, pixfmt, n, batch, dets, cap_per_frame, counts, thresh, n_labels, annotated))) return rc;
+    const int ch = anno_channels(pixfmt);
+    batch = std::min(batch, n);
+    const int chunks = (n + batch - 1) / batch;
+    auto in_chunk = [&](int k) { return std::min(batch, n - k * batch); };
+    auto used = [&](int f) { return std::min(counts[f], cap_per_frame); };
+    size_t cap_in = 0, cap_out = 0;
+    for (int k = 0; k < chunks; ++k) {
+        size_t items = 0, in = 0, out = 0;
+        for (int f = k * batch; f < k * batch + in_chunk(k); ++f) {
+            items += (size_t)count_drawn(dets + (size_t)f * cap_per_frame, used(f), thresh);
+            in += padded((size_t)widths[f] * heights[f] * ch);
+            out += padded((size_t)widths[f] * heights[f] * 3);
+        }
+        cap_in = std::max(cap_in, table_bytes(in_chunk(k), items) + in);
+        cap_out = std::max(cap_out, out);
+    }
+    HIP_TRY(hipSetDevice(c->device), YOLO2_INIT_ERROR);
+    if ((rc = anno_ensure(c, cap_in, cap_out))) return rc;
+    Y2AnnoBufs &A = c->anno;
+    auto cleanup = [&]() { (void)hipDeviceSynchronize(); };
+#define Y2_TRY(expr, code) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { rc = fail(code, "%s failed: %s", #expr, hipGetErrorString(e_)); cleanup(); return rc; } } while (0)
+
+    std::vector<FrameIn> fr((size_t)batch);
+    auto drain = [&](int k) {
+        const int b = k & 1;
+        (void)hipEventSynchronize(A.e_out[b]);
+        size_t off = 0;
+        for (int f = k * batch; f < k * batch + in_chunk(k); ++f) {
+            const size_t bytes = (size_t)widths[f] * heights[f] * 3;
+            memcpy(annotated[f], A.hout[b].get() + off, bytes);
+            off += padded(bytes);
+        }
+    };
+    for (int k = 0; k < chunks; ++k) {
+        const int b = k & 1, nf = in_chunk(k), first = k * batch;
+        if (k >= 2) drain(k - 2);   // buffer set b is free again once chunk k-2 has left it
+        size_t items = 0;
+        for (int i = 0; i < nf; ++i) items += (size_t)count_drawn(dets + (size_t)(first + i) * cap_per_frame, used(first + i), thresh);
+        uint8_t *hin = A.hin[b].get();
+        size_t off = table_bytes(nf, items), out_off = 0;
+        for (int i = 0; i < nf; ++i) {
+            const int f = first + i;
+            const size_t bytes = (size_t)widths[f] * heights[f] * ch;
+            memcpy(hin + off, images[f], bytes);
+            fr[(size_t)i] = {widths[f], heights[f], ch, off, out_off, dets + (size_t)f * cap_per_frame, used(f)};
+            off += padded(bytes);
+            out_off += padded((size_t)widths[f] * heights[f] * 3);
+        }
+        const int max_strips = fill_table(hin, fr.data(), nf, thresh, labels, n_labels, drawn ? drawn + first : nullptr);
+        Y2_TRY(hipMemcpyAsync(A.din[b].get(), hin, off, hipMemcpyHostToDevice, A.s_in), YOLO2_DMA_ERROR);
+        Y2_TRY(hipEventRecord(A.e_in[b], A.s_in), YOLO2_ERROR);
+        Y2_TRY(hipStreamWaitEvent(A.s_run, A.e_in[b], 0), YOLO2_ERROR);
+        launch_annotate(A.din[b].get(), A.din[b].get(), A.dout[b].get(), max_strips, nf, A.s_run);
+        Y2_TRY(hipGetLastError(), YOLO2_ERROR);
+        Y2_TRY(hipEventRecord(A.e_run[b], A.s_run), YOLO2_ERROR);
+        Y2_TRY(hipStreamWaitEvent(A.s_out, A.e_run[b], 0), YOLO2_ERROR);
+        Y2_TRY(hipMemcpyAsync(A.hout[b].get(), A.dout[b].get(), out_off, hipMemcpyDeviceToHost, A.s_out), YOLO2_DMA_ERROR);
+        Y2_TRY(hipEventRecord(A.e_out[b], A.s_out), YOLO2_ERROR);
+    }
+    for (int k = std::max(0, chunks - 2); k < chunks; ++k) drain(k);
+#undef Y2_TRY
+    HIP_TRY(hipDeviceSynchronize(), YOLO2_ERROR);
+    return YOLO2_SUCCESS;
+}

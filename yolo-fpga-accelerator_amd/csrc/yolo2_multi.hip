@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "../../include/yolo2_hip.h"
+#include "y2_draw.hpp"
 #include "y2_mem.hpp"
 
 extern "C" int yolo2_hip_set_error(int code, const char *msg);   // yolo2_hip.hip: stores the message for yolo2_hip_last_error()
@@ -671,4 +672,21 @@ extern "C" int yolo2_hip_multi_run_images_pix_dets_f16(yolo2_hip_multi *m, int s
 {
     return multi_images_dets_f16(yolo2_hip_run_images_pix_dets_f16, m, split, images, widths, heights, pixfmt, n, batch_per_device, thresh, nms,
                                  flags, dets, cap_per_frame, counts);
+}
+
+// annotated frames, shard i painted by device i (yolo2_hip_annotate_images_pix_host on its own host thread)
+extern "C" int yolo2_hip_multi_annotate_images_pix_host(yolo2_hip_multi *m, const uint8_t *const *images, const int *widths,
+                                                        const int *heights, int pixfmt, int n, int batch_per_device,
+                                                        const yolo2_hip_det *dets, int cap_per_frame, const int *counts, float thresh,
+                                                        const char *const *labels, int n_labels, uint8_t *const *annotated, int *drawn)
+{
+    if (!m) return mfail(YOLO2_ERROR, "annotate: null argument");
+    // the whole call is looked at before any shard starts: a refusal leaves every frame untouched
+    const int rc = y2_annotate_check(images, widths, heights, pixfmt, n, batch_per_device, dets, cap_per_frame, counts, thresh, n_labels, annotated);
+    if (rc) return rc;
+    return multi_run(m, n, [&](yolo2_hip_ctx *c, int lo, int hi) {
+        return yolo2_hip_annotate_images_pix_host(c, images + lo, widths + lo, heights + lo, pixfmt, hi - lo, std::min(batch_per_device, hi - lo),
+                                                  dets + (size_t)lo * cap_per_frame, cap_per_frame, counts + lo, thresh, labels, n_labels,
+                                                  annotated + lo, drawn ? drawn + lo : nullptr);
+    });
 }

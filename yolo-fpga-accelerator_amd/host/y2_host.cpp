@@ -2,6 +2,8 @@
 // reproduces are cited per function (paths relative to the reference repository).
 #include "y2_host.hpp"
 
+#include "../csrc/draw_list.hpp"
+
 #include <algorithm>
 #include <thread>
 #include <atomic>
@@ -323,6 +325,72 @@ void draw_box(Image &im, int x1, int y1, int x2, int y2, int thick, float r, flo
             for (int y = b1; y <= b2; ++y) { im.at(a1, y, k) = col[k]; im.at(a2, y, k) = col[k]; }
         }
     }
+}
+
+// yolo2_draw_detections_rgb24 (linux_app/src/yolo2_draw.c:276-369): records in array order, later ones over earlier ones; per record
+// the two border rings (yolo2_draw_rect_rgb24, :94-111), the tag's filled rectangle, then the glyphs, each glyph pixel bounds-checked.
+// What a record paints is y2d::draw_make_item's (csrc/draw_list.hpp); this paints it the painter's way.
+int draw_detections_rgb24(uint8_t *rgb, int w, int h, const DrawRecord *dets, int n, float thresh, const char *const *labels, int n_labels)
+{
+    static_assert(sizeof(DrawRecord) == sizeof(y2d::DrawDet), "one record layout");
+    if (!rgb || w <= 0 || h <= 0 || !dets || n <= 0) return 0;
+    auto put = [&](int x, int y, uint32_t c) {
+        if (x < 0 || x >= w || y < 0 || y >= h) return;
+        uint8_t *p = rgb + ((size_t)y * w + x) * 3;
+        p[0] = (uint8_t)c; p[1] = (uint8_t)(c >> 8); p[2] = (uint8_t)(c >> 16);
+    };
+    int drawn = 0;
+    y2d::DrawItem it;
+    for (int i = 0; i < n; ++i) {
+        y2d::DrawDet d;
+        memcpy(&d, &dets[i], sizeof(d));
+        if (!y2d::draw_make_item(d, w, h, thresh, labels, n_labels, &it)) continue;
+        for (int t = 0; t < y2d::kDrawThick; ++t) {
+            const int *r = it.ring[t];
+            for (int x = r[0]; x <= r[2]; ++x) { put(x, r[1], it.box_rgb); put(x, r[3], it.box_rgb); }
+            for (int y = r[1]; y <= r[3]; ++y) { put(r[0], y, it.box_rgb); put(r[2], y, it.box_rgb); }
+        }
+        for (int y = it.tag[1]; y <= it.tag[3]; ++y)
+            for (int x = it.tag[0]; x <= it.tag[2]; ++x) put(x, y, it.box_rgb);
+        for (int k = 0; k < it.nchar; ++k) {
+            const uint64_t g = y2d::kDrawFont[it.text[k]];
+            for (int b = 0; b < 35; ++b) {
+                if (!((g >> b) & 1)) continue;
+                const int px = it.gx + k * y2d::kDrawCell + (b % 5) * y2d::kDrawScale, py = it.gy + (b / 5) * y2d::kDrawScale;
+                for (int yy = 0; yy < y2d::kDrawScale; ++yy)
+                    for (int xx = 0; xx < y2d::kDrawScale; ++xx) put(px + xx, py + yy, it.text_rgb);
+            }
+        }
+        ++drawn;
+    }
+    return drawn;
+}
+
+Image plain_box_frame(const uint8_t *bytes, int w, int h, bool yuyv, const DrawRecord *recs, int n, int classes)
+{
+    Image im = make_image(w, h, 3);
+    std::vector<uint8_t> conv;   // the frame needs RGB pixels: a YUYV frame is converted here, on the host
+    if (yuyv) {
+        conv.resize((size_t)im.w * im.h * 3);
+        if (!yuyv_to_rgb24(bytes, conv.data(), im.w, im.h)) throw std::runtime_error("bad YUYV frame");
+    }
+    const uint8_t *rgb = conv.empty() ? bytes : conv.data();
+    for (int k = 0; k < 3; ++k)
+        for (int y = 0; y < im.h; ++y)
+            for (int x = 0; x < im.w; ++x) im.at(x, y, k) = (float)rgb[((size_t)y * im.w + x) * 3 + k] / 255.f;
+    for (int i = 0; i < n; ++i) {
+        const DrawRecord &b = recs[i];
+        const float hue = (float)((b.cls * 123457) % classes) / classes;
+        draw_box(im, (int)((b.x - b.w / 2.) * im.w), (int)((b.y - b.h / 2.) * im.h), (int)((b.x + b.w / 2.) * im.w),
+                 (int)((b.y + b.h / 2.) * im.h), std::max(1, (int)(im.h * .006)), hue, 1.f - hue, 0.5f);
+    }
+    return im;
+}
+
+int draw_font(char *chars, uint64_t *words)
+{
+    for (int i = 0; i < y2d::kDrawGlyphs; ++i) { chars[i] = y2d::kDrawFontChars[i]; words[i] = y2d::kDrawFont[i]; }
+    return y2d::kDrawGlyphs;
 }
 
 // -------------------------------------------------------------------------------------- weights

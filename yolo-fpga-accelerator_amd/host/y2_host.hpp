@@ -60,6 +60,21 @@ Image letterbox_image(const Image &im, int w, int h);     // yolo_image.cpp:148-
 // or non-positive width / height (the reference converts pairs over the flat stream and leaves an odd frame's last pixel unwritten).
 bool yuyv_to_rgb24(const uint8_t *yuyv, uint8_t *rgb, int w, int h);
 void draw_box(Image &im, int x1, int y1, int x2, int y2, int thick, float r, float g, float b);
+// The annotated frame of the reference's camera / video loop: yolo2_draw_detections_rgb24 (linux_app/src/yolo2_draw.c:276-369, called
+// at linux_app/src/main.c:1079-1091) on records of the library's yolo2_hip_det layout in the YOLO2_DETS_BEST_CLASS form (one per
+// detection).  Per record with prob > thresh, in array order: a 2-pixel box in palette[cls % 8], a tag "<label> <prob %.2f>" above
+// the box (below its top edge when fewer than 18 rows are free) in the same colour with black or white 5x7 text at scale 2; labels
+// may be NULL ("class<N>", also for cls >= n_labels).  Bit-identical to the reference (tests/golden/draw.npz).  Returns the records drawn.
+struct DrawRecord {
+    int frame, det, cls;
+    float prob, x, y, w, h;
+};
+int draw_detections_rgb24(uint8_t *rgb, int w, int h, const DrawRecord *dets, int n, float thresh, const char *const *labels, int n_labels);
+// The streaming CLI's own annotated frame (without --annotate-gpu): the frame's bytes (RGB24, or with yuyv a packed YUYV frame through
+// yuyv_to_rgb24) as a float image, one draw_box per record in a hue colour of its class, thickness max(1, h * .006).  No labels.
+// Throws std::runtime_error for a bad YUYV frame.
+Image plain_box_frame(const uint8_t *bytes, int w, int h, bool yuyv, const DrawRecord *recs, int n, int classes);
+int draw_font(char *chars, uint64_t *words);   // the packed font: 38 characters and their 35-bit glyph words (bit 5 * row + column)
 
 // ---------------------------------------------------------------- weights (yolo2_model.cpp:158-227)
 struct WeightsI16 {

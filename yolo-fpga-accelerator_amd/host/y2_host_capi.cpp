@@ -100,6 +100,31 @@ int y2h_yuyv_to_rgb24(const uint8_t *yuyv, uint8_t *rgb, int w, int h)
     return -1;
 }
 
+// draw_detections_rgb24: dets are yolo2_hip_det records; returns the records drawn, or -1 (y2h_last_error) for a null frame or a
+// non-positive size
+int y2h_draw_detections_rgb24(uint8_t *rgb, int w, int h, const void *dets, int n, float thresh, const char *const *labels, int n_labels)
+{
+    if (!rgb || w <= 0 || h <= 0 || (n > 0 && !dets)) {
+        g_err = "draw_detections_rgb24: null buffer or bad frame " + std::to_string(w) + "x" + std::to_string(h);
+        return -1;
+    }
+    return draw_detections_rgb24(rgb, w, h, static_cast<const DrawRecord *>(dets), n, thresh, labels, n_labels);
+}
+
+// plain_box_frame, the CLI writer's own frame, for tools/annotate_report.py to time; returns the sum of the image, or -1
+// (y2h_last_error) for a bad YUYV frame
+double y2h_plain_box_frame(const uint8_t *bytes, int w, int h, int yuyv, const void *dets, int n, int classes)
+{
+    try {
+        const Image im = plain_box_frame(bytes, w, h, yuyv != 0, static_cast<const DrawRecord *>(dets), n, classes);
+        double sum = 0;
+        for (float v : im.data) sum += v;
+        return sum;
+    } catch (const std::exception &e) { g_err = e.what(); return -1; }
+}
+
+int y2h_draw_font(char *chars, uint64_t *words) { return draw_font(chars, words); }
+
 // decode_image (y2_codec.cpp): JPEG / PNG bytes -> RGB bytes [h][w][3]; returns w*h*3, or -1 (y2h_last_error) / -2 (capacity)
 long y2h_decode_image(const unsigned char *data, long n, int *w, int *h, unsigned char *rgb, long cap)
 {

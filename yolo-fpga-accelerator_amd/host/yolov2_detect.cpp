@@ -61,6 +61,7 @@ struct AppConfig {
     // streaming frontend
     std::vector<int> devices;          // --devices a,b,...: frame shards over several GPUs
     std::string input_list, input_dir, video_raw, jsonl_path, save_dir;
+    bool annotate_gpu = false;   // --annotate-gpu: annotated frames come from yolo2_hip_annotate_images_pix_host, in the reference's look
     int video_w = 640, video_h = 480;
     int video_pixfmt = YOLO2_PIX_RGB24; // --video-pix-fmt: what a --video-raw frame holds (RGB24, or packed YUYV 4:2:2 read by the GPU as it is)
     int max_frames = 0;                // 0 = all
@@ -105,6 +106,9 @@ void print_usage(const char *prog)
         "  --infer-every <n>     Run inference on every n-th frame (default 1)\n"
         "  --jsonl <path>        One JSON record per frame (fields of the reference's --output-json)\n"
         "  --save-annotated-dir <dir>   Write annotated frames as PPM\n"
+        "  --annotate-gpu        with --save-annotated-dir: the frames are painted on the GPU right behind the detections, in the\n"
+        "                        reference's look (boxes and \"<label> <prob>\" tags, labels from --names; yolo2_hip_annotate_images_pix_host);\n"
+        "                        needs --post gpu\n"
         "  --chunk-batches <n>   Batches per device and accelerator call (default 4)\n"
         "  --decode-threads <n>  Host threads decoding images ahead of the accelerators (default: all cores; one pool feeds every device)\n"
         "  --strict              Stop at the first input that cannot be read or decoded (default: log it, skip the frame, go on)\n"
@@ -160,6 +164,7 @@ AppConfig parse_args(int argc, char **argv)
         else if (arg == "--infer-every" && need("")) cfg.infer_every = std::max(1, std::atoi(argv[++i]));
         else if ((arg == "--jsonl" || arg == "--output-json") && need("")) cfg.jsonl_path = argv[++i];
         else if (arg == "--save-annotated-dir" && need("")) cfg.save_dir = argv[++i];
+        else if (arg == "--annotate-gpu") cfg.annotate_gpu = true;
         else if (arg == "--chunk-batches" && need("")) cfg.chunk_batches = std::max(1, std::atoi(argv[++i]));
         else if (arg == "--decode-threads" && need("")) cfg.decode_threads = std::atoi(argv[++i]);
         else if (arg == "--strict") cfg.strict = true;
@@ -404,6 +409,7 @@ struct Chunk {
     std::vector<SrcFrame> frames;            // frames whose image could not be decoded are dropped before the accelerator (see skipped)
     std::vector<std::pair<int, std::string>> skipped;   // (frame_index, reason)
     std::vector<std::vector<OutDet>> dets;   // filled by the accelerator stage
+    std::vector<std::vector<uint8_t>> annotated;   // --annotate-gpu: the frames as RGB24 with boxes and tags, from the accelerator stage
     double seconds = 0;                      // wall time of the accelerator call for this chunk
 };
 
@@ -496,10 +502,14 @@ void run_stream(AppConfig cfg)
         throw std::runtime_error("--post host runs the int16 region tensor only; --precision " + cfg.precision + " needs --post gpu");
     if (cfg.devices.empty()) cfg.devices.push_back(cfg.device);
     if (cfg.batch <= 0) throw std::runtime_error("--batch must be positive");
+    const bool annotate_gpu = cfg.annotate_gpu && !cfg.save_dir.empty();
+    if (annotate_gpu && cfg.post != "gpu") throw std::runtime_error("--annotate-gpu paints the records of --post gpu");
     const y2h::Network net = y2h::parse_cfg(cfg.cfg_path);
     check_topology(net);
     const std::vector<std::string> names = y2h::load_names(cfg.names_path);
     const y2h::Layer &last = net.layers.back();
+    std::vector<const char *> labels;
+    for (const std::string &s : names) labels.push_back(s.c_str());
     FrameSource src(cfg);
     const int ndev = (int)cfg.devices.size();
     std::printf("YOLOv2 Object Detection - streaming (%s)\n  devices:", src.mode());
@@ -610,23 +620,20 @@ void run_stream(AppConfig cfg)
                         std::printf("  %s: %.0f%%  (x=%.4f y=%.4f w=%.4f h=%.4f)\n", d.class_id < (int)names.size() ? names[(size_t)d.class_id].c_str() : "?",
                                     d.prob * 100, d.box.x, d.box.y, d.box.w, d.box.h);
                     if (jf) write_jsonl(jf, src.mode(), fr.source, fr.frame_index, infer_idx, fr.img.w, fr.img.h, c.dets[(size_t)f], names);
-                    if (!cfg.save_dir.empty()) {
-                        y2h::Image im = y2h::make_image(fr.img.w, fr.img.h, 3);
-                        std::vector<uint8_t> conv;   // the annotated frame needs RGB pixels: a YUYV frame is converted here, on the host
-                        if (pixfmt == YOLO2_PIX_YUYV) {
-                            conv.resize((size_t)im.w * im.h * 3);
-                            if (!y2h::yuyv_to_rgb24(fr.img.rgb.data(), conv.data(), im.w, im.h)) throw std::runtime_error("bad YUYV frame");
-                        }
-                        const uint8_t *rgb = conv.empty() ? fr.img.rgb.data() : conv.data();
-                        for (int k = 0; k < 3; ++k)
-                            for (int y = 0; y < im.h; ++y)
-                                for (int x = 0; x < im.w; ++x) im.at(x, y, k) = (float)rgb[((size_t)y * im.w + x) * 3 + k] / 255.f;
-                        for (const OutDet &d : c.dets[(size_t)f]) {
-                            const y2h::Box &b = d.box;
-                            const float hue = (float)((d.class_id * 123457) % last.classes) / last.classes;
-                            y2h::draw_box(im, (int)((b.x - b.w / 2.) * im.w), (int)((b.y - b.h / 2.) * im.h), (int)((b.x + b.w / 2.) * im.w),
-                                          (int)((b.y + b.h / 2.) * im.h), std::max(1, (int)(im.h * .006)), hue, 1.f - hue, 0.5f);
-                        }
+                    if (annotate_gpu) {
+                        char name[64];
+                        std::snprintf(name, sizeof(name), "frame_%06d.ppm", infer_idx);
+                        const std::string path = (fs::path(cfg.save_dir) / name).string();
+                        FILE *pf = std::fopen(path.c_str(), "wb");
+                        if (!pf) throw std::runtime_error("Cannot write " + path);
+                        std::fprintf(pf, "P6\n%d %d\n255\n", fr.img.w, fr.img.h);
+                        std::fwrite(c.annotated[(size_t)f].data(), 1, c.annotated[(size_t)f].size(), pf);
+                        std::fclose(pf);
+                    } else if (!cfg.save_dir.empty()) {
+                        std::vector<y2h::DrawRecord> recs;
+                        for (const OutDet &d : c.dets[(size_t)f]) recs.push_back({0, 0, d.class_id, d.prob, d.box.x, d.box.y, d.box.w, d.box.h});
+                        const y2h::Image im = y2h::plain_box_frame(fr.img.rgb.data(), fr.img.w, fr.img.h, pixfmt == YOLO2_PIX_YUYV, recs.data(),
+                                                                   (int)recs.size(), last.classes);
                         char name[64];
                         std::snprintf(name, sizeof(name), "frame_%06d.ppm", infer_idx);
                         y2h::save_ppm(im, (fs::path(cfg.save_dir) / name).string());
@@ -671,6 +678,7 @@ void run_stream(AppConfig cfg)
                     for (int i = 0; i < n; ++i) { ptrs[(size_t)i] = ck->frames[(size_t)i].img.rgb.data(); ws[(size_t)i] = ck->frames[(size_t)i].img.w; hs[(size_t)i] = ck->frames[(size_t)i].img.h; }
                     int q = 0;
                     const auto t0 = std::chrono::steady_clock::now();
+                    double t_annotate = 0;     // --annotate-gpu: upload, painting and download of the annotated frames, kept out of the inference time
                     if (cfg.post == "gpu") {
                         // one record per detection (its best class, main.c:1040-1052): at most 845 per frame, never truncated
                         const int cap = 845;
@@ -681,6 +689,19 @@ void run_stream(AppConfig cfg)
                                            : yolo2_hip_run_images_pix_dets(ctx, ptrs.data(), ws.data(), hs.data(), pixfmt, n, cfg.batch, cfg.thresh, cfg.nms,
                                                                            YOLO2_DETS_BEST_CLASS, recs.data(), cap, counts.data(), &q);
                         if (rc != YOLO2_SUCCESS) throw std::runtime_error(yolo2_hip_last_error());
+                        const auto t_dets = std::chrono::steady_clock::now();
+                        if (annotate_gpu) {     // the chunk's frames with these records painted in, while both are at hand
+                            ck->annotated.resize((size_t)n);
+                            std::vector<uint8_t *> outs((size_t)n);
+                            for (int f = 0; f < n; ++f) {
+                                ck->annotated[(size_t)f].resize((size_t)ws[(size_t)f] * hs[(size_t)f] * 3);
+                                outs[(size_t)f] = ck->annotated[(size_t)f].data();
+                            }
+                            if (yolo2_hip_annotate_images_pix_host(ctx, ptrs.data(), ws.data(), hs.data(), pixfmt, n, cfg.batch, recs.data(), cap, counts.data(),
+                                                                   cfg.thresh, labels.data(), (int)labels.size(), outs.data(), nullptr) != YOLO2_SUCCESS)
+                                throw std::runtime_error(yolo2_hip_last_error());
+                        }
+                        t_annotate = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_dets).count();
                         for (int f = 0; f < n; ++f) {
                             if (counts[(size_t)f] > cap) throw std::runtime_error("detection records truncated");   // cannot happen in best-class mode
                             for (int k = 0; k < counts[(size_t)f]; ++k) {
@@ -695,7 +716,7 @@ void run_stream(AppConfig cfg)
                         auto all = y2h::postprocess_batch(region.data(), n, q, ws.data(), hs.data(), cfg.thresh, cfg.nms, post_threads);
                         for (int f = 0; f < n; ++f) ck->dets[(size_t)f] = best_class_dets(all[(size_t)f], (int)all[(size_t)f].size(), last.classes, cfg.thresh);
                     }
-                    ck->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+                    ck->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() - t_annotate;
                     accel_s[(size_t)slot] += ck->seconds;
                 }
                 to_write.push(std::move(ck));

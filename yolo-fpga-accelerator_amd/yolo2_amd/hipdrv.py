@@ -54,6 +54,7 @@ EXPORTS = [
     "yolo2_hip_multi_run_images_pix_dets_f16",
     "yolo2_hip_absmax_f32", "yolo2_hip_calib_reset", "yolo2_hip_calib_frames", "yolo2_hip_calib_images_pix_host", "yolo2_hip_calib_stats",
     "yolo2_hip_calib_q_tables", "yolo2_hip_calib_q_from_stats", "yolo2_hip_quantize_weights_int16",
+    "yolo2_hip_annotate_pix", "yolo2_hip_annotate_images_pix_host", "yolo2_hip_multi_annotate_images_pix_host",
 ]
 
 # include/yolo2_hip.h YOLO2_PIX_*: the pixfmt argument of the _pix entries ("yuyv": packed YUYV 4:2:2, arrays uint8 [h][w][2])
@@ -250,6 +251,10 @@ def lib():
     sig("yolo2_hip_calib_q_tables", [vp, C.c_float, vp, vp, vp])
     sig("yolo2_hip_calib_q_from_stats", [vp, vp, vp, C.c_float, vp, vp, vp])
     sig("yolo2_hip_quantize_weights_int16", [vp, vp, vp, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_long)])
+    # annotated frames (include/yolo2_hip.h "annotated frames")
+    sig("yolo2_hip_annotate_pix", [u64, i32, i32, i32, vp, i32, C.c_float, vp, i32, u64, C.POINTER(i32), vp])
+    for name in ("annotate_images_pix_host", "multi_annotate_images_pix_host"):
+        sig("yolo2_hip_" + name, [vp, vp, vp, vp, i32, i32, i32, vp, i32, vp, C.c_float, vp, i32, vp, vp])
     _lib = L
     return L
 
@@ -430,6 +435,10 @@ class Yolo2Hip:
               "yolo2_hip_run_images_u8_host" if pixfmt is None else "yolo2_hip_run_images_pix_host")
         self.final_q = q.value
         return region, q.value
+
+    def annotate_images(self, images, dets, counts, batch: int, thresh: float, labels=None, pixfmt=None):
+        """the images with their detection records painted in, as the reference's camera loop does (module-level annotate_images)"""
+        return annotate_images(self._h, images, dets, counts, batch, thresh, labels=labels, pixfmt=pixfmt)
 
     # ---- fp16 MFMA path
     def load_weights_fp32(self, weights_f32, bias_f32):
@@ -832,6 +841,69 @@ def run_images_dets(handle, images, batch: int, thresh: float, nms: float, cap: 
     return {"dets": [dets[f, :min(int(counts[f]), cap)] for f in range(n)], "counts": counts, "final_q": q.value}
 
 
+# ------------------------------------------------------------------ annotated frames
+
+def _label_args(labels):
+    """(char ** or None, n_labels, what keeps the strings alive)"""
+    if labels is None:
+        return None, 0, None
+    enc = [s.encode() if isinstance(s, str) else bytes(s) for s in labels]
+    arr = (C.c_char_p * max(len(enc), 1))(*enc)
+    return arr, len(enc), enc
+
+
+def annotate_pix(image: np.ndarray, dets, pixfmt=None, thresh: float = 0.24, labels=None):
+    """yolo2_hip_annotate_pix: one image ("grey8" [h][w], "rgb24" [h][w][3], "yuyv" [h][w][2]; None infers grey / RGB) and its
+    records (DET_DTYPE, one per detection) -> (uint8 [h][w][3] with the reference's boxes and tags painted in, records drawn)."""
+    im = np.ascontiguousarray(image, dtype=np.uint8)
+    code = _pix_code(pixfmt if pixfmt is not None else ("grey8" if im.ndim == 2 else "rgb24"), [im])
+    d = np.ascontiguousarray(dets, dtype=DET_DTYPE).reshape(-1)
+    lab, n_labels, _keep = _label_args(labels)
+    L = lib()
+    src, dst = C.c_uint64(0), C.c_uint64(0)
+    out = np.empty((im.shape[0], im.shape[1], 3), dtype=np.uint8)
+    drawn = C.c_int(0)
+    try:
+        check(L.yolo2_hip_alloc(max(im.nbytes, 16), C.byref(src)), "alloc")
+        check(L.yolo2_hip_alloc(max(out.nbytes, 16), C.byref(dst)), "alloc")
+        check(L.yolo2_hip_memcpy_h2d(src, im.ctypes.data_as(C.c_void_p), im.nbytes), "h2d")
+        check(L.yolo2_hip_annotate_pix(src, im.shape[1], im.shape[0], code, d.ctypes.data_as(C.c_void_p) if d.size else None, d.size,
+                                       thresh, lab, n_labels, dst, C.byref(drawn), None), "yolo2_hip_annotate_pix")
+        check(L.yolo2_hip_memcpy_d2h(out.ctypes.data_as(C.c_void_p), dst, out.nbytes), "d2h")
+    finally:
+        for buf in (src, dst):
+            if buf.value:
+                L.yolo2_hip_free(buf)
+    return out, drawn.value
+
+
+def annotate_images(handle, images, dets, counts, batch: int, thresh: float, labels=None, pixfmt=None, multi: bool = False):
+    """yolo2_hip_annotate_images_pix_host / yolo2_hip_multi_annotate_images_pix_host: host images and the records a run_images_dets call
+    returned for them -> (list of uint8 [h][w][3] annotated frames, records drawn per frame).  dets: DET_DTYPE [n][cap] with counts [n]
+    (frame f uses min(counts[f], cap) records), or - counts None - a list of per-frame record arrays (run_images_dets()["dets"])."""
+    imgs0 = [np.ascontiguousarray(im, dtype=np.uint8) for im in images]
+    fmt = pixfmt if pixfmt is not None else ("grey8" if imgs0[0].ndim == 2 else "rgb24")
+    n, ptrs, ws, hs, code, imgs = _image_args(imgs0, fmt)
+    if counts is None:
+        cap = max([len(d) for d in dets] + [1])
+        packed = np.zeros((n, cap), dtype=DET_DTYPE)
+        for f, d in enumerate(dets):
+            packed[f, :len(d)] = d
+        dets, counts = packed, [len(d) for d in dets]
+    d = np.ascontiguousarray(dets, dtype=DET_DTYPE)
+    if d.ndim != 2 or d.shape[0] != n:
+        raise ValueError(f"dets is [n][cap] records for {n} images, not {d.shape}")
+    cnt = np.ascontiguousarray(counts, dtype=np.int32)
+    lab, n_labels, _keep = _label_args(labels)
+    outs = [np.empty((im.shape[0], im.shape[1], 3), dtype=np.uint8) for im in imgs]
+    optrs = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
+    drawn = np.zeros(n, dtype=np.int32)
+    name = f"yolo2_hip_{'multi_' if multi else ''}annotate_images_pix_host"
+    check(getattr(lib(), name)(handle, ptrs, ws, hs, code, n, batch, d.ctypes.data_as(C.c_void_p), d.shape[1], cnt.ctypes.data_as(C.c_void_p),
+                               thresh, lab, n_labels, optrs, drawn.ctypes.data_as(C.c_void_p)), name)
+    return outs, drawn
+
+
 # ------------------------------------------------------------------ more than one GPU
 
 def shard_range(total: int, rank: int, world: int):
@@ -966,3 +1038,7 @@ class Yolo2HipMulti:
         check(fn(self._m, ptrs, ws, hs, fmt, n, batch_per_device, region.ctypes.data_as(C.c_void_p), C.byref(q)),
               "yolo2_hip_multi_run_images_u8_host" if pixfmt is None else "yolo2_hip_multi_run_images_pix_host")
         return region, q.value
+
+    def annotate_images(self, images, dets, counts, batch_per_device: int, thresh: float, labels=None, pixfmt=None):
+        """annotated frames, shard i painted by device i (module-level annotate_images)"""
+        return annotate_images(self._m, images, dets, counts, batch_per_device, thresh, labels=labels, pixfmt=pixfmt, multi=True)
