@@ -518,6 +518,33 @@ int yolo2_hip_annotate_images_pix_host(yolo2_hip_ctx *ctx, const uint8_t *const 
                                        int pixfmt, int n, int batch, const yolo2_hip_det *dets, int cap_per_frame, const int *counts,
                                        float thresh, const char *const *labels, int n_labels, uint8_t *const *annotated, int *drawn);
 
+/* ------------------------------------------------------- annotated frames as JPEG: the stream of the reference's MJPEG streamer
+ *
+ * The reference's camera loop hands the annotated frame to its MJPEG streamer, which encodes it with stb_image_write v1.09
+ * (stbi_write_jpg_to_func with 3 components, linux_app/src/yolo2_mjpeg_server.c:221-238; quality clamped to 1..100, default 80,
+ * main.c:80).  These entries make that stream on the GPU, byte for byte, from RGB24 frames that stay in device memory: baseline JPEG,
+ * Y / Cb / Cr without subsampling (one 8x8 block each per MCU, edge pixels repeated), float AAN transform, the typical Huffman
+ * tables, no restart markers, a 607-byte header.  Eight launches (csrc/kernels_jpeg.hpp): transform; bit lengths and a two-level
+ * scan; code words; 0xFF counts, their scan, and the stuffed stream.  y2h_write_jpg_rgb24 (libyolo2_host.so) is the same encoder
+ * on the host.  Width and height are 1..65535, and a frame's bound stays below 2^31 bytes; anything else is YOLO2_ERROR. */
+
+/* The most bytes the stream of a w x h frame can take (607 + twice the scan's bound of 1660 bits per block + 2); 0 for a size these
+ * entries refuse (outside 1..65535, or a bound of 2^31 bytes or more). */
+size_t yolo2_hip_jpeg_bound(int w, int h);
+/* One RGB24 frame already on the calling thread's device -> its stream at jpeg_out_dev; neither address needs any alignment.
+ * *size = the stream's length.  If it exceeds cap, nothing at or beyond cap is written and the call returns YOLO2_ERROR ("too
+ * small"; *size is still set, jpeg_out_dev may be 0 if cap is 0).  Enqueues on `stream` and synchronises it. */
+int yolo2_hip_jpeg_encode_rgb24(uint64_t rgb_dev, int w, int h, int quality, uint64_t jpeg_out_dev, size_t cap, size_t *size, void *stream);
+/* yolo2_hip_annotate_images_pix_host with JPEG streams out: the painter writes RGB24 into device memory, the encoder follows on the
+ * same stream, and the frame never visits the host.  jpeg[f] has room for caps[f] bytes and receives min(sizes[f], caps[f]); the
+ * download copies the sizes first and then only the bytes in use.  A frame whose stream exceeds its capacity gets its sizes[f]
+ * and nothing past the capacity, the other frames are complete, and the call returns YOLO2_ERROR ("too small").  A frame without
+ * records in YOLO2_PIX_RGB24 is a pure encode.  drawn [n] may be NULL.  Synchronous. */
+int yolo2_hip_annotate_images_pix_jpeg_host(yolo2_hip_ctx *ctx, const uint8_t *const *images, const int *widths, const int *heights,
+                                            int pixfmt, int n, int batch, const yolo2_hip_det *dets, int cap_per_frame, const int *counts,
+                                            float thresh, const char *const *labels, int n_labels, int quality, uint8_t *const *jpeg,
+                                            const size_t *caps, size_t *sizes, int *drawn);
+
 /* ------------------------------------------------------- calibration: fp32 weights + frames -> int16 weights and Q tables
  *
  * The reference makes its int16 weight set with a separate tool (weights/README.md step 2b: "activation-calibrated"
@@ -622,6 +649,12 @@ int  yolo2_hip_multi_annotate_images_pix_host(yolo2_hip_multi *m, const uint8_t 
                                               int pixfmt, int n, int batch_per_device, const yolo2_hip_det *dets, int cap_per_frame,
                                               const int *counts, float thresh, const char *const *labels, int n_labels,
                                               uint8_t *const *annotated, int *drawn);
+
+/* annotated frames as JPEG streams (see yolo2_hip_annotate_images_pix_jpeg_host), shard i painted and encoded by device i */
+int  yolo2_hip_multi_annotate_images_pix_jpeg_host(yolo2_hip_multi *m, const uint8_t *const *images, const int *widths, const int *heights,
+                                                   int pixfmt, int n, int batch_per_device, const yolo2_hip_det *dets, int cap_per_frame,
+                                                   const int *counts, float thresh, const char *const *labels, int n_labels, int quality,
+                                                   uint8_t *const *jpeg, const size_t *caps, size_t *sizes, int *drawn);
 
 /* (b) one process per device (torchrun / MPI style; what bench.py --gpus N runs): rank 0 makes the 128-byte id
  * (ncclGetUniqueId), the launcher hands it to every rank, each rank joins with its context (ncclCommInitRank), then

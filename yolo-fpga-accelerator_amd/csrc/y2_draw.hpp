@@ -9,3 +9,7 @@
 // whole call before it starts a shard).  YOLO2_SUCCESS, or YOLO2_ERROR with the cause in yolo2_hip_last_error.
 int y2_annotate_check(const uint8_t *const *images, const int *widths, const int *heights, int pixfmt, int n, int batch, const yolo2_hip_det *dets,
                       int cap_per_frame, const int *counts, float thresh, int n_labels, uint8_t *const *annotated);
+// The same for the JPEG entries: the checks above (the streams' pointers in place of the frames') and what the encoder refuses.
+int y2_annotate_jpeg_check(const uint8_t *const *images, const int *widths, const int *heights, int pixfmt, int n, int batch,
+                           const yolo2_hip_det *dets, int cap_per_frame, const int *counts, float thresh, int n_labels, uint8_t *const *jpeg,
+                           const size_t *caps, size_t *sizes);

@@ -9,6 +9,7 @@
 //   yolo2_calib.hip   fp32 weights + calibration frames -> Q tables and int16 weights (statistics of the exact fp32 pass)
 //   yolo2_post.hip    region layer + boxes + NMS;   yolo2_multi.hip  frame sharding + the RCCL weight broadcast
 //   yolo2_draw.hip    annotated frames: records + frames -> RGB24 with the reference's boxes and tags
+//   yolo2_jpeg.hip    RGB24 frames in device memory -> the reference's JPEG streams
 // Every non-template kernel is launched from exactly one of them (its kernels_*.hpp is included there only).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -229,11 +230,23 @@ struct Y2AnnoBufs {
     hipEvent_t e_in[2] = {nullptr, nullptr}, e_run[2] = {nullptr, nullptr}, e_out[2] = {nullptr, nullptr};
 };
 
+// What yolo2_hip_annotate_images_pix_jpeg_host (yolo2_draw.hip) keeps beside Y2AnnoBufs' upload side and streams: the painted RGB24
+// frames and the encoder's work area (touched by kernels of one stream only, so one of each), two sets of packed device and pinned
+// output with the pinned per-frame sizes, grown on demand.
+struct Y2JpegBufs {
+    size_t cap_rgb = 0, cap_work = 0, cap_out = 0, cap_frames = 0;
+    Y2DevBuf<uint8_t> rgb, work, dout[2];
+    Y2PinBuf<uint8_t> hout[2];
+    Y2PinBuf<unsigned long long> hsizes[2];
+    hipEvent_t e_sizes[2] = {nullptr, nullptr};
+};
+
 struct F16Plan;   // yolo2_fp16.hip: the per-context launch table of the fp16 path
 
 struct yolo2_hip_ctx {
     PipeBufs pipe;
     Y2AnnoBufs anno;
+    Y2JpegBufs jpeg;
     int device = 0;
     Y2Options opt;                     // parsed once at creation (environment), changed only by yolo2_hip_set_option; lanes copy it
     std::shared_ptr<Y2PlanCache> plan_cache;   // weight-side cache bound by yolo2_hip_set_plan_cache (lanes share the parent's)
@@ -419,6 +432,7 @@ void y2_drv_conv_f32(const float *in, float *out, const float *w, const float *b
 
 // yolo2_draw.hip: the streams, events and buffers of c->anno (yolo2_hip_destroy)
 void y2_anno_free(yolo2_hip_ctx *c);
+void y2_anno_jpeg_free(yolo2_hip_ctx *c);   // c->jpeg
 
 // yolo2_calib.hip: one exact fp32 pass over `batch` device frames + the abs-max reductions, accumulated into c->calib_stats; `counted`
 // of the frames are new ones (the images entry pads a short last chunk by repeating its last image).  Synchronises st.

@@ -7,6 +7,7 @@
 #include "y2_internal.hpp"
 #include "kernels_draw.hpp"
 #include "y2_draw.hpp"
+#include "y2_jpeg.hpp"
 
 #include <cmath>
 
@@ -267,5 +268,174 @@ extern "C" int yolo2_hip_annotate_images_pix_host(yolo2_hip_ctx *c, const uint8_
     for (int k = std::max(0, chunks - 2); k < chunks; ++k) drain(k);
 #undef Y2_TRY
     HIP_TRY(hipDeviceSynchronize(), YOLO2_ERROR);
+    return YOLO2_SUCCESS;
+}
+
+// ---------------------------------------------------------------------------- n host images -> annotated frames as JPEG streams
+
+void y2_anno_jpeg_free(yolo2_hip_ctx *c)
+{
+    Y2JpegBufs &j = c->jpeg;
+    for (int k = 0; k < 2; ++k) {
+        if (j.e_sizes[k]) { (void)hipEventDestroy(j.e_sizes[k]); j.e_sizes[k] = nullptr; }
+        j.dout[k].reset(); j.hout[k].reset(); j.hsizes[k].reset();
+    }
+    j.rgb.reset();
+    j.work.reset();
+    j.cap_rgb = j.cap_work = j.cap_out = j.cap_frames = 0;
+}
+
+static int anno_jpeg_ensure(yolo2_hip_ctx *c, size_t cap_rgb, size_t cap_work, size_t cap_out, size_t frames)
+{
+    Y2JpegBufs &j = c->jpeg;
+    if (j.e_sizes[0] && j.cap_rgb >= cap_rgb && j.cap_work >= cap_work && j.cap_out >= cap_out && j.cap_frames >= frames) return YOLO2_SUCCESS;
+    cap_rgb = std::max(cap_rgb, j.cap_rgb);
+    cap_work = std::max(cap_work, j.cap_work);
+    cap_out = std::max(cap_out, j.cap_out);
+    frames = std::max(frames, j.cap_frames);
+    y2_anno_jpeg_free(c);
+    bool ok = j.rgb.alloc(cap_rgb) == YOLO2_SUCCESS && j.work.alloc(cap_work) == YOLO2_SUCCESS;
+    for (int k = 0; k < 2 && ok; ++k)
+        ok = j.dout[k].alloc(cap_out) == YOLO2_SUCCESS && j.hout[k].alloc(cap_out) == YOLO2_SUCCESS && j.hsizes[k].alloc(frames) == YOLO2_SUCCESS &&
+             hipEventCreateWithFlags(&j.e_sizes[k], hipEventDisableTiming) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        y2_anno_jpeg_free(c);
+        return fail(YOLO2_MMAP_ERROR, "annotate: JPEG buffers (%zu + %zu bytes, and %zu twice) could not be allocated", cap_rgb, cap_work, cap_out);
+    }
+    j.cap_rgb = cap_rgb; j.cap_work = cap_work; j.cap_out = cap_out; j.cap_frames = frames;
+    return YOLO2_SUCCESS;
+}
+
+// (y2_draw.hpp)
+int y2_annotate_jpeg_check(const uint8_t *const *images, const int *widths, const int *heights, int pixfmt, int n, int batch,
+                           const yolo2_hip_det *dets, int cap_per_frame, const int *counts, float thresh, int n_labels, uint8_t *const *jpeg,
+                           const size_t *caps, size_t *sizes)
+{
+    if (!caps || !sizes) return fail(YOLO2_ERROR, "annotate: null argument");
+    int rc;
+    if ((rc = y2_annotate_check(images, widths, heights, pixfmt, n, batch, dets, cap_per_frame, counts, thresh, n_labels, jpeg))) return rc;
+    for (int f = 0; f < n; ++f)
+        if ((rc = y2_jpeg_check_frame(widths[f], heights[f], f))) return rc;
+    return YOLO2_SUCCESS;
+}
+
+// The painter's pipeline with the encoder behind it on the run stream: chunk k's frames are painted into device memory
+// (k_annotate_batch), encoded there (stages A - D of kernels_jpeg.hpp) and only the streams come back - first the sizes, then one copy
+// of the bytes in use.  While the GPU paints and encodes chunk k, the output stream downloads chunk k - 1's bytes and the host copies
+// them out of pinned memory: the byte copy of chunk k - 1 is queued on the output stream BEFORE that stream is made to wait for chunk
+// k's kernels (for chunk k's sizes copy).
+extern "C" int yolo2_hip_annotate_images_pix_jpeg_host(yolo2_hip_ctx *c, const uint8_t *const *images, const int *widths, const int *heights,
+                                                       int pixfmt, int n, int batch, const yolo2_hip_det *dets, int cap_per_frame,
+                                                       const int *counts, float thresh, const char *const *labels, int n_labels, int quality,
+                                                       uint8_t *const *jpeg, const size_t *caps, size_t *sizes, int *drawn)
+{
+    if (!c) return fail(YOLO2_ERROR, "annotate: null argument");
+    int rc;
+    if ((rc = y2_annotate_jpeg_check(images, widths, heights, pixfmt, n, batch, dets, cap_per_frame, counts, thresh, n_labels, jpeg, caps, sizes)))
+        return rc;
+    const int ch = anno_channels(pixfmt);
+    batch = std::min(batch, n);
+    const int chunks = (n + batch - 1) / batch;
+    auto in_chunk = [&](int k) { return std::min(batch, n - k * batch); };
+    auto used = [&](int f) { return std::min(counts[f], cap_per_frame); };
+    // per chunk: the painter's item count and the encoder's plan, made once; an upload holds the painter's table, the frames, then
+    // the encoder's table
+    std::vector<Y2JpegFrameIn> jf((size_t)batch);
+    std::vector<Y2JpegPlan> plans((size_t)chunks);
+    std::vector<size_t> items((size_t)chunks, 0);
+    size_t cap_in = 0, cap_rgb = 0, cap_work = 0, cap_out = 0;
+    for (int k = 0; k < chunks; ++k) {
+        size_t in = 0, out = 0;
+        for (int i = 0; i < in_chunk(k); ++i) {
+            const int f = k * batch + i;
+            items[(size_t)k] += (size_t)count_drawn(dets + (size_t)f * cap_per_frame, used(f), thresh);
+            in += padded((size_t)widths[f] * heights[f] * ch);
+            jf[(size_t)i] = {widths[f], heights[f], out, caps[f]};
+            out += padded((size_t)widths[f] * heights[f] * 3);
+        }
+        if ((rc = y2_jpeg_plan(jf.data(), in_chunk(k), &plans[(size_t)k]))) return rc;
+        cap_in = std::max(cap_in, table_bytes(in_chunk(k), items[(size_t)k]) + in + plans[(size_t)k].table_bytes);
+        cap_rgb = std::max(cap_rgb, out);
+        cap_work = std::max(cap_work, plans[(size_t)k].work_bytes);
+        cap_out = std::max(cap_out, plans[(size_t)k].out_bytes);
+    }
+    HIP_TRY(hipSetDevice(c->device), YOLO2_INIT_ERROR);
+    if ((rc = anno_ensure(c, cap_in, 0)) || (rc = anno_jpeg_ensure(c, cap_rgb, cap_work, std::max(cap_out, (size_t)1), (size_t)batch))) return rc;
+    Y2AnnoBufs &A = c->anno;
+    Y2JpegBufs &J = c->jpeg;
+    auto cleanup = [&]() { (void)hipDeviceSynchronize(); };
+#define Y2_TRY(expr, code) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { rc = fail(code, "%s failed: %s", #expr, hipGetErrorString(e_)); cleanup(); return rc; } } while (0)
+
+    std::vector<FrameIn> fr((size_t)batch);
+    int short_frame = -1;
+    // The sizes first, then only the bytes in use: frame f's stream starts where the frames before it end, each cut at its capacity.
+    // fetch(k): wait for chunk k's sizes, queue one D2H of the bytes in use.  deliver(k): wait for it, hand the streams out.
+    auto fetch = [&](int k) -> int {
+        const int b = k & 1, nf = in_chunk(k), first = k * batch;
+        Y2_TRY(hipEventSynchronize(J.e_sizes[b]), YOLO2_ERROR);
+        const unsigned long long *hs = J.hsizes[b].get();
+        size_t total = 0;
+        for (int i = 0; i < nf; ++i) total += std::min((size_t)hs[i], caps[first + i]);
+        if (total) Y2_TRY(hipMemcpyAsync(J.hout[b].get(), J.dout[b].get(), total, hipMemcpyDeviceToHost, A.s_out), YOLO2_DMA_ERROR);
+        Y2_TRY(hipEventRecord(A.e_out[b], A.s_out), YOLO2_ERROR);
+        return YOLO2_SUCCESS;
+    };
+    auto deliver = [&](int k) -> int {
+        const int b = k & 1, nf = in_chunk(k), first = k * batch;
+        Y2_TRY(hipEventSynchronize(A.e_out[b]), YOLO2_ERROR);
+        const unsigned long long *hs = J.hsizes[b].get();
+        size_t off = 0;
+        for (int i = 0; i < nf; ++i) {
+            const int f = first + i;
+            const size_t bytes = std::min((size_t)hs[i], caps[f]);
+            if (bytes) memcpy(jpeg[f], J.hout[b].get() + off, bytes);
+            off += bytes;
+            sizes[f] = (size_t)hs[i];
+            if (sizes[f] > caps[f] && short_frame < 0) short_frame = f;
+        }
+        return YOLO2_SUCCESS;
+    };
+    for (int k = 0; k < chunks; ++k) {
+        const int b = k & 1, nf = in_chunk(k), first = k * batch;
+        const Y2JpegPlan &plan = plans[(size_t)k];
+        // (buffer set b is free: chunk k - 2 was delivered in the round before)
+        uint8_t *hin = A.hin[b].get();
+        size_t off = table_bytes(nf, items[(size_t)k]), out_off = 0;
+        for (int i = 0; i < nf; ++i) {
+            const int f = first + i;
+            const size_t bytes = (size_t)widths[f] * heights[f] * ch;
+            memcpy(hin + off, images[f], bytes);
+            fr[(size_t)i] = {widths[f], heights[f], ch, off, out_off, dets + (size_t)f * cap_per_frame, used(f)};
+            jf[(size_t)i] = {widths[f], heights[f], out_off, caps[f]};
+            off += padded(bytes);
+            out_off += padded((size_t)widths[f] * heights[f] * 3);
+        }
+        const int max_strips = fill_table(hin, fr.data(), nf, thresh, labels, n_labels, drawn ? drawn + first : nullptr);
+        const size_t jtab = off;
+        y2_jpeg_write_table(jf.data(), nf, quality, hin + jtab);
+        off += plan.table_bytes;
+        Y2_TRY(hipMemcpyAsync(A.din[b].get(), hin, off, hipMemcpyHostToDevice, A.s_in), YOLO2_DMA_ERROR);
+        Y2_TRY(hipEventRecord(A.e_in[b], A.s_in), YOLO2_ERROR);
+        Y2_TRY(hipStreamWaitEvent(A.s_run, A.e_in[b], 0), YOLO2_ERROR);
+        // (the work area holds the sizes of the chunk before until they have been copied out)
+        if (k >= 1) Y2_TRY(hipStreamWaitEvent(A.s_run, J.e_sizes[b ^ 1], 0), YOLO2_ERROR);
+        launch_annotate(A.din[b].get(), A.din[b].get(), J.rgb.get(), max_strips, nf, A.s_run);
+        Y2_TRY(hipGetLastError(), YOLO2_ERROR);
+        if ((rc = y2_jpeg_enqueue(plan, A.din[b].get() + jtab, J.rgb.get(), J.work.get(), J.dout[b].get(), A.s_run))) { cleanup(); return rc; }
+        Y2_TRY(hipEventRecord(A.e_run[b], A.s_run), YOLO2_ERROR);
+        // chunk k - 1's bytes go onto the output stream ahead of the wait for chunk k's kernels, so they come down while those run
+        if (k >= 1 && (rc = fetch(k - 1))) return rc;
+        Y2_TRY(hipStreamWaitEvent(A.s_out, A.e_run[b], 0), YOLO2_ERROR);
+        Y2_TRY(hipMemcpyAsync(J.hsizes[b].get(), J.work.get() + plan.sizes, (size_t)nf * sizeof(unsigned long long), hipMemcpyDeviceToHost, A.s_out),
+               YOLO2_DMA_ERROR);
+        Y2_TRY(hipEventRecord(J.e_sizes[b], A.s_out), YOLO2_ERROR);
+        if (k >= 1 && (rc = deliver(k - 1))) return rc;
+    }
+    if ((rc = fetch(chunks - 1)) || (rc = deliver(chunks - 1))) return rc;
+#undef Y2_TRY
+    HIP_TRY(hipDeviceSynchronize(), YOLO2_ERROR);
+    if (short_frame >= 0)
+        return fail(YOLO2_ERROR, "annotate: output buffer too small for frame %d (%zu < %zu bytes)", short_frame, caps[short_frame], sizes[short_frame]);
     return YOLO2_SUCCESS;
 }

@@ -236,6 +236,7 @@ extern "C" void yolo2_hip_destroy(yolo2_hip_ctx *c)
     (void)hipDeviceSynchronize();
     pipe_free(c->pipe);
     y2_anno_free(c);
+    y2_anno_jpeg_free(c);
     y2_f16_plan_free(c);
     y2_destroy_lanes(c);
     y2_free_activations(c);

@@ -690,3 +690,22 @@ extern "C" int yolo2_hip_multi_annotate_images_pix_host(yolo2_hip_multi *m, cons
                                                   annotated + lo, drawn ? drawn + lo : nullptr);
     });
 }
+
+// annotated frames as JPEG streams, shard i painted and encoded by device i
+extern "C" int yolo2_hip_multi_annotate_images_pix_jpeg_host(yolo2_hip_multi *m, const uint8_t *const *images, const int *widths,
+                                                             const int *heights, int pixfmt, int n, int batch_per_device,
+                                                             const yolo2_hip_det *dets, int cap_per_frame, const int *counts, float thresh,
+                                                             const char *const *labels, int n_labels, int quality, uint8_t *const *jpeg,
+                                                             const size_t *caps, size_t *sizes, int *drawn)
+{
+    if (!m) return mfail(YOLO2_ERROR, "annotate: null argument");
+    // the whole call is looked at before any shard starts: a refusal leaves every stream untouched
+    const int rc = y2_annotate_jpeg_check(images, widths, heights, pixfmt, n, batch_per_device, dets, cap_per_frame, counts, thresh, n_labels, jpeg,
+                                          caps, sizes);
+    if (rc) return rc;
+    return multi_run(m, n, [&](yolo2_hip_ctx *c, int lo, int hi) {
+        return yolo2_hip_annotate_images_pix_jpeg_host(c, images + lo, widths + lo, heights + lo, pixfmt, hi - lo, std::min(batch_per_device, hi - lo),
+                                                       dets + (size_t)lo * cap_per_frame, cap_per_frame, counts + lo, thresh, labels, n_labels,
+                                                       quality, jpeg + lo, caps + lo, sizes + lo, drawn ? drawn + lo : nullptr);
+    });
+}

@@ -75,6 +75,12 @@ int draw_detections_rgb24(uint8_t *rgb, int w, int h, const DrawRecord *dets, in
 // Throws std::runtime_error for a bad YUYV frame.
 Image plain_box_frame(const uint8_t *bytes, int w, int h, bool yuyv, const DrawRecord *recs, int n, int classes);
 int draw_font(char *chars, uint64_t *words);   // the packed font: 38 characters and their 35-bit glyph words (bit 5 * row + column)
+// The annotated frame as the JPEG stream the reference's MJPEG streamer sends (stb_image_write v1.09's stbi_write_jpg_to_func with 3
+// components, linux_app/src/yolo2_mjpeg_server.c:221-238), byte for byte (y2_jpeg.cpp; tests/golden/jpeg.npz): baseline, no
+// subsampling, quality clamped to 1..100.  Returns the stream's length and stores the bytes below `cap` (out may be NULL if cap is
+// 0); -1 for a null frame or a width / height outside 1..65535.  jpg_rgb24_bound: the most bytes a w x h frame can take (0: bad size).
+long write_jpg_rgb24(const uint8_t *rgb, int w, int h, int quality, uint8_t *out, size_t cap);
+size_t jpg_rgb24_bound(int w, int h);
 
 // ---------------------------------------------------------------- weights (yolo2_model.cpp:158-227)
 struct WeightsI16 {

@@ -125,6 +125,15 @@ double y2h_plain_box_frame(const uint8_t *bytes, int w, int h, int yuyv, const v
 
 int y2h_draw_font(char *chars, uint64_t *words) { return draw_font(chars, words); }
 
+// write_jpg_rgb24 (y2_jpeg.cpp): returns the stream's length (bytes below cap are stored), or -1 (y2h_last_error)
+long y2h_write_jpg_rgb24(const uint8_t *rgb, int w, int h, int quality, uint8_t *out, size_t cap)
+{
+    const long n = write_jpg_rgb24(rgb, w, h, quality, out, cap);
+    if (n < 0) g_err = "write_jpg_rgb24: null buffer or bad frame " + std::to_string(w) + "x" + std::to_string(h) + " (1..65535)";
+    return n;
+}
+size_t y2h_jpg_rgb24_bound(int w, int h) { return jpg_rgb24_bound(w, h); }
+
 // decode_image (y2_codec.cpp): JPEG / PNG bytes -> RGB bytes [h][w][3]; returns w*h*3, or -1 (y2h_last_error) / -2 (capacity)
 long y2h_decode_image(const unsigned char *data, long n, int *w, int *h, unsigned char *rgb, long cap)
 {

@@ -62,6 +62,8 @@ struct AppConfig {
     std::vector<int> devices;          // --devices a,b,...: frame shards over several GPUs
     std::string input_list, input_dir, video_raw, jsonl_path, save_dir;
     bool annotate_gpu = false;   // --annotate-gpu: annotated frames come from yolo2_hip_annotate_images_pix_host, in the reference's look
+    std::string annotated_format;   // --annotated-format jpg: they are encoded on the GPU too (yolo2_hip_annotate_images_pix_jpeg_host); "" / ppm: PPM
+    int jpeg_quality = 80;          // --jpeg-quality, the reference streamer's default
     int video_w = 640, video_h = 480;
     int video_pixfmt = YOLO2_PIX_RGB24; // --video-pix-fmt: what a --video-raw frame holds (RGB24, or packed YUYV 4:2:2 read by the GPU as it is)
     int max_frames = 0;                // 0 = all
@@ -109,6 +111,9 @@ void print_usage(const char *prog)
         "  --annotate-gpu        with --save-annotated-dir: the frames are painted on the GPU right behind the detections, in the\n"
         "                        reference's look (boxes and \"<label> <prob>\" tags, labels from --names; yolo2_hip_annotate_images_pix_host);\n"
         "                        needs --post gpu\n"
+        "  --annotated-format <ppm|jpg>  with --annotate-gpu: jpg writes frame_NNNNNN.jpg, the reference's MJPEG stream of the frame,\n"
+        "                        encoded on the GPU (yolo2_hip_annotate_images_pix_jpeg_host); default ppm\n"
+        "  --jpeg-quality <1..100>  quality of --annotated-format jpg (default 80)\n"
         "  --chunk-batches <n>   Batches per device and accelerator call (default 4)\n"
         "  --decode-threads <n>  Host threads decoding images ahead of the accelerators (default: all cores; one pool feeds every device)\n"
         "  --strict              Stop at the first input that cannot be read or decoded (default: log it, skip the frame, go on)\n"
@@ -165,6 +170,8 @@ AppConfig parse_args(int argc, char **argv)
         else if ((arg == "--jsonl" || arg == "--output-json") && need("")) cfg.jsonl_path = argv[++i];
         else if (arg == "--save-annotated-dir" && need("")) cfg.save_dir = argv[++i];
         else if (arg == "--annotate-gpu") cfg.annotate_gpu = true;
+        else if (arg == "--annotated-format" && need("")) cfg.annotated_format = argv[++i];
+        else if (arg == "--jpeg-quality" && need("")) cfg.jpeg_quality = std::atoi(argv[++i]);
         else if (arg == "--chunk-batches" && need("")) cfg.chunk_batches = std::max(1, std::atoi(argv[++i]));
         else if (arg == "--decode-threads" && need("")) cfg.decode_threads = std::atoi(argv[++i]);
         else if (arg == "--strict") cfg.strict = true;
@@ -504,6 +511,10 @@ void run_stream(AppConfig cfg)
     if (cfg.batch <= 0) throw std::runtime_error("--batch must be positive");
     const bool annotate_gpu = cfg.annotate_gpu && !cfg.save_dir.empty();
     if (annotate_gpu && cfg.post != "gpu") throw std::runtime_error("--annotate-gpu paints the records of --post gpu");
+    if (!cfg.annotated_format.empty() && cfg.annotated_format != "ppm" && cfg.annotated_format != "jpg")
+        throw std::runtime_error("--annotated-format is ppm or jpg, not " + cfg.annotated_format);
+    const bool annotate_jpg = cfg.annotated_format == "jpg";
+    if (annotate_jpg && !annotate_gpu) throw std::runtime_error("--annotated-format jpg encodes the frames of --annotate-gpu --save-annotated-dir");
     const y2h::Network net = y2h::parse_cfg(cfg.cfg_path);
     check_topology(net);
     const std::vector<std::string> names = y2h::load_names(cfg.names_path);
@@ -622,11 +633,11 @@ void run_stream(AppConfig cfg)
                     if (jf) write_jsonl(jf, src.mode(), fr.source, fr.frame_index, infer_idx, fr.img.w, fr.img.h, c.dets[(size_t)f], names);
                     if (annotate_gpu) {
                         char name[64];
-                        std::snprintf(name, sizeof(name), "frame_%06d.ppm", infer_idx);
+                        std::snprintf(name, sizeof(name), "frame_%06d.%s", infer_idx, annotate_jpg ? "jpg" : "ppm");
                         const std::string path = (fs::path(cfg.save_dir) / name).string();
                         FILE *pf = std::fopen(path.c_str(), "wb");
                         if (!pf) throw std::runtime_error("Cannot write " + path);
-                        std::fprintf(pf, "P6\n%d %d\n255\n", fr.img.w, fr.img.h);
+                        if (!annotate_jpg) std::fprintf(pf, "P6\n%d %d\n255\n", fr.img.w, fr.img.h);
                         std::fwrite(c.annotated[(size_t)f].data(), 1, c.annotated[(size_t)f].size(), pf);
                         std::fclose(pf);
                     } else if (!cfg.save_dir.empty()) {
@@ -690,7 +701,33 @@ void run_stream(AppConfig cfg)
                                                                            YOLO2_DETS_BEST_CLASS, recs.data(), cap, counts.data(), &q);
                         if (rc != YOLO2_SUCCESS) throw std::runtime_error(yolo2_hip_last_error());
                         const auto t_dets = std::chrono::steady_clock::now();
-                        if (annotate_gpu) {     // the chunk's frames with these records painted in, while both are at hand
+                        if (annotate_gpu && annotate_jpg) {     // painted and encoded on the GPU: only the streams come back
+                            ck->annotated.resize((size_t)n);
+                            std::vector<uint8_t *> outs((size_t)n);
+                            std::vector<size_t> caps((size_t)n), sizes((size_t)n);
+                            // room for the raw frame's size; a frame that compresses to more than that (noise at quality 100) gets a
+                            // second call with the encoder's bound
+                            for (int attempt = 0; attempt < 2; ++attempt) {
+                                for (int f = 0; f < n; ++f) {
+                                    const size_t bound = yolo2_hip_jpeg_bound(ws[(size_t)f], hs[(size_t)f]);
+                                    caps[(size_t)f] = attempt ? bound : std::min(bound, (size_t)ws[(size_t)f] * hs[(size_t)f] * 3 + 4096);
+                                    ck->annotated[(size_t)f].resize(caps[(size_t)f]);
+                                    outs[(size_t)f] = ck->annotated[(size_t)f].data();
+                                    sizes[(size_t)f] = 0;
+                                }
+                                const int rc = yolo2_hip_annotate_images_pix_jpeg_host(ctx, ptrs.data(), ws.data(), hs.data(), pixfmt, n, cfg.batch, recs.data(),
+                                                                                       cap, counts.data(), cfg.thresh, labels.data(), (int)labels.size(),
+                                                                                       cfg.jpeg_quality, outs.data(), caps.data(), sizes.data(), nullptr);
+                                if (rc == YOLO2_SUCCESS) break;
+                                bool too_small = false;
+                                for (int f = 0; f < n; ++f) too_small = too_small || sizes[(size_t)f] > caps[(size_t)f];
+                                if (attempt || !too_small) throw std::runtime_error(yolo2_hip_last_error());
+                            }
+                            for (int f = 0; f < n; ++f) {
+                                ck->annotated[(size_t)f].resize(sizes[(size_t)f]);
+                                ck->annotated[(size_t)f].shrink_to_fit();
+                            }
+                        } else if (annotate_gpu) {     // the chunk's frames with these records painted in, while both are at hand
                             ck->annotated.resize((size_t)n);
                             std::vector<uint8_t *> outs((size_t)n);
                             for (int f = 0; f < n; ++f) {

@@ -15,6 +15,7 @@ from . import net
 PKG_DIR = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # YOLO2_HIP_LIB: another build of the same library (A/B runs of compile-time kernel variants, tools/ab.sh)
 LIB_PATH = os.environ.get("YOLO2_HIP_LIB") or os.path.join(PKG_DIR, "libyolo2_hip.so")
+HOST_LIB_PATH = os.path.join(PKG_DIR, "libyolo2_host.so")   # the host restatements (no GPU code)
 
 YOLO2_SUCCESS, YOLO2_ERROR, YOLO2_TIMEOUT, YOLO2_INIT_ERROR, YOLO2_MMAP_ERROR, YOLO2_DMA_ERROR = 0, -1, -2, -3, -4, -5
 
@@ -55,6 +56,8 @@ EXPORTS = [
     "yolo2_hip_absmax_f32", "yolo2_hip_calib_reset", "yolo2_hip_calib_frames", "yolo2_hip_calib_images_pix_host", "yolo2_hip_calib_stats",
     "yolo2_hip_calib_q_tables", "yolo2_hip_calib_q_from_stats", "yolo2_hip_quantize_weights_int16",
     "yolo2_hip_annotate_pix", "yolo2_hip_annotate_images_pix_host", "yolo2_hip_multi_annotate_images_pix_host",
+    "yolo2_hip_jpeg_bound", "yolo2_hip_jpeg_encode_rgb24", "yolo2_hip_annotate_images_pix_jpeg_host",
+    "yolo2_hip_multi_annotate_images_pix_jpeg_host",
 ]
 
 # include/yolo2_hip.h YOLO2_PIX_*: the pixfmt argument of the _pix entries ("yuyv": packed YUYV 4:2:2, arrays uint8 [h][w][2])
@@ -255,6 +258,11 @@ def lib():
     sig("yolo2_hip_annotate_pix", [u64, i32, i32, i32, vp, i32, C.c_float, vp, i32, u64, C.POINTER(i32), vp])
     for name in ("annotate_images_pix_host", "multi_annotate_images_pix_host"):
         sig("yolo2_hip_" + name, [vp, vp, vp, vp, i32, i32, i32, vp, i32, vp, C.c_float, vp, i32, vp, vp])
+    # annotated frames as JPEG (include/yolo2_hip.h "annotated frames as JPEG")
+    sig("yolo2_hip_jpeg_bound", [i32, i32], C.c_size_t)
+    sig("yolo2_hip_jpeg_encode_rgb24", [u64, i32, i32, i32, u64, C.c_size_t, C.POINTER(C.c_size_t), vp])
+    for name in ("annotate_images_pix_jpeg_host", "multi_annotate_images_pix_jpeg_host"):
+        sig("yolo2_hip_" + name, [vp, vp, vp, vp, i32, i32, i32, vp, i32, vp, C.c_float, vp, i32, i32, vp, vp, vp, vp])
     _lib = L
     return L
 
@@ -436,9 +444,10 @@ class Yolo2Hip:
         self.final_q = q.value
         return region, q.value
 
-    def annotate_images(self, images, dets, counts, batch: int, thresh: float, labels=None, pixfmt=None):
-        """the images with their detection records painted in, as the reference's camera loop does (module-level annotate_images)"""
-        return annotate_images(self._h, images, dets, counts, batch, thresh, labels=labels, pixfmt=pixfmt)
+    def annotate_images(self, images, dets, counts, batch: int, thresh: float, labels=None, pixfmt=None, jpeg_quality=None):
+        """the images with their detection records painted in, as the reference's camera loop does (module-level annotate_images);
+        with jpeg_quality, as the JPEG streams its MJPEG streamer sends (a list of bytes)"""
+        return annotate_images(self._h, images, dets, counts, batch, thresh, labels=labels, pixfmt=pixfmt, jpeg_quality=jpeg_quality)
 
     # ---- fp16 MFMA path
     def load_weights_fp32(self, weights_f32, bias_f32):
@@ -877,10 +886,13 @@ def annotate_pix(image: np.ndarray, dets, pixfmt=None, thresh: float = 0.24, lab
     return out, drawn.value
 
 
-def annotate_images(handle, images, dets, counts, batch: int, thresh: float, labels=None, pixfmt=None, multi: bool = False):
+def annotate_images(handle, images, dets, counts, batch: int, thresh: float, labels=None, pixfmt=None, multi: bool = False, jpeg_quality=None):
     """yolo2_hip_annotate_images_pix_host / yolo2_hip_multi_annotate_images_pix_host: host images and the records a run_images_dets call
     returned for them -> (list of uint8 [h][w][3] annotated frames, records drawn per frame).  dets: DET_DTYPE [n][cap] with counts [n]
-    (frame f uses min(counts[f], cap) records), or - counts None - a list of per-frame record arrays (run_images_dets()["dets"])."""
+    (frame f uses min(counts[f], cap) records), or - counts None - a list of per-frame record arrays (run_images_dets()["dets"]).
+    jpeg_quality (1..100): the _jpeg_host entries instead - the frames come back as the reference's JPEG streams, a list of bytes."""
+    if jpeg_quality is not None:
+        return annotate_images_jpeg(handle, images, dets, counts, batch, thresh, int(jpeg_quality), labels=labels, pixfmt=pixfmt, multi=multi)
     imgs0 = [np.ascontiguousarray(im, dtype=np.uint8) for im in images]
     fmt = pixfmt if pixfmt is not None else ("grey8" if imgs0[0].ndim == 2 else "rgb24")
     n, ptrs, ws, hs, code, imgs = _image_args(imgs0, fmt)
@@ -902,6 +914,121 @@ def annotate_images(handle, images, dets, counts, batch: int, thresh: float, lab
     check(getattr(lib(), name)(handle, ptrs, ws, hs, code, n, batch, d.ctypes.data_as(C.c_void_p), d.shape[1], cnt.ctypes.data_as(C.c_void_p),
                                thresh, lab, n_labels, optrs, drawn.ctypes.data_as(C.c_void_p)), name)
     return outs, drawn
+
+
+# ------------------------------------------------------------------ annotated frames as JPEG
+
+_host_lib = None
+
+
+def host_lib():
+    """libyolo2_host.so: the host restatements the GPU entries are checked against"""
+    global _host_lib
+    if _host_lib is None:
+        H = C.CDLL(HOST_LIB_PATH)
+        H.y2h_write_jpg_rgb24.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
+        H.y2h_write_jpg_rgb24.restype = C.c_long
+        H.y2h_jpg_rgb24_bound.argtypes = [C.c_int, C.c_int]
+        H.y2h_jpg_rgb24_bound.restype = C.c_size_t
+        _host_lib = H
+    return _host_lib
+
+
+def _rgb24(rgb):
+    im = np.ascontiguousarray(rgb, dtype=np.uint8)
+    if im.ndim != 3 or im.shape[2] != 3:
+        raise ValueError(f"an RGB24 frame is uint8 [h][w][3], not {im.shape}")
+    return im
+
+
+def write_jpg_host(rgb, quality: int = 80) -> bytes:
+    """y2h_write_jpg_rgb24: an RGB24 frame as the JPEG stream of the reference's MJPEG streamer, encoded on the host"""
+    im = _rgb24(rgb)
+    H = host_lib()
+    cap = H.y2h_jpg_rgb24_bound(im.shape[1], im.shape[0])
+    out = np.empty(max(cap, 1), dtype=np.uint8)
+    n = H.y2h_write_jpg_rgb24(im.ctypes.data, im.shape[1], im.shape[0], quality, out.ctypes.data, cap)
+    if n < 0 or n > cap:
+        raise ValueError(f"y2h_write_jpg_rgb24 refused a {im.shape[1]}x{im.shape[0]} frame")
+    return out[:n].tobytes()
+
+
+def jpeg_bound(w: int, h: int) -> int:
+    """yolo2_hip_jpeg_bound: the most bytes the stream of a w x h frame can take"""
+    return int(lib().yolo2_hip_jpeg_bound(w, h))
+
+
+def jpeg_encode(rgb, quality: int = 80) -> bytes:
+    """yolo2_hip_jpeg_encode_rgb24: the same stream as write_jpg_host, encoded on the GPU"""
+    im = _rgb24(rgb)
+    L = lib()
+    h, w = im.shape[:2]
+    cap = jpeg_bound(w, h)
+    if not cap:
+        raise ValueError(f"width and height are 1..65535, not {w}x{h}")
+    src, dst = C.c_uint64(0), C.c_uint64(0)
+    size = C.c_size_t(0)
+    try:
+        check(L.yolo2_hip_alloc(max(im.nbytes, 16), C.byref(src)), "alloc")
+        check(L.yolo2_hip_alloc(cap, C.byref(dst)), "alloc")
+        check(L.yolo2_hip_memcpy_h2d(src, im.ctypes.data_as(C.c_void_p), im.nbytes), "h2d")
+        check(L.yolo2_hip_jpeg_encode_rgb24(src, w, h, quality, dst, cap, C.byref(size), None), "yolo2_hip_jpeg_encode_rgb24")
+        out = np.empty(size.value, dtype=np.uint8)
+        check(L.yolo2_hip_memcpy_d2h(out.ctypes.data_as(C.c_void_p), dst, out.nbytes), "d2h")
+    finally:
+        for buf in (src, dst):
+            if buf.value:
+                L.yolo2_hip_free(buf)
+    return out.tobytes()
+
+
+def annotate_images_jpeg_raw(handle, images, dets, counts, batch: int, thresh: float, quality: int, caps, labels=None, pixfmt=None,
+                             multi: bool = False, guard: int = 0):
+    """The _jpeg_host entries as they are: caps [n] bytes of room per frame -> (return code, list of uint8 [caps[f] + guard] buffers -
+    with a guard, every byte of them 0xA5 before the call -, sizes [n], records drawn [n])."""
+    imgs0 = [np.ascontiguousarray(im, dtype=np.uint8) for im in images]
+    fmt = pixfmt if pixfmt is not None else ("grey8" if imgs0[0].ndim == 2 else "rgb24")
+    n, ptrs, ws, hs, code, imgs = _image_args(imgs0, fmt)
+    if counts is None:
+        cap = max([len(d) for d in dets] + [1])
+        packed = np.zeros((n, cap), dtype=DET_DTYPE)
+        for f, d in enumerate(dets):
+            packed[f, :len(d)] = d
+        dets, counts = packed, [len(d) for d in dets]
+    d = np.ascontiguousarray(dets, dtype=DET_DTYPE)
+    if d.ndim != 2 or d.shape[0] != n:
+        raise ValueError(f"dets is [n][cap] records for {n} images, not {d.shape}")
+    cnt = np.ascontiguousarray(counts, dtype=np.int32)
+    lab, n_labels, _keep = _label_args(labels)
+    caps = np.ascontiguousarray(caps, dtype=np.uint64)
+    if guard:
+        outs = [np.full(int(caps[f]) + guard, 0xA5, dtype=np.uint8) for f in range(n)]
+    else:       # (untouched pages: filling them would cost what the RGB24 entry's copy of the frames costs)
+        outs = [np.empty(int(caps[f]), dtype=np.uint8) for f in range(n)]
+    optrs = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
+    sizes = np.zeros(n, dtype=np.uint64)
+    drawn = np.zeros(n, dtype=np.int32)
+    name = f"yolo2_hip_{'multi_' if multi else ''}annotate_images_pix_jpeg_host"
+    rc = getattr(lib(), name)(handle, ptrs, ws, hs, code, n, batch, d.ctypes.data_as(C.c_void_p), d.shape[1], cnt.ctypes.data_as(C.c_void_p),
+                              thresh, lab, n_labels, quality, optrs, caps.ctypes.data_as(C.c_void_p), sizes.ctypes.data_as(C.c_void_p),
+                              drawn.ctypes.data_as(C.c_void_p))
+    return rc, outs, sizes, drawn
+
+
+def annotate_images_jpeg(handle, images, dets, counts, batch: int, thresh: float, quality: int = 80, labels=None, pixfmt=None, multi: bool = False):
+    """yolo2_hip_annotate_images_pix_jpeg_host / its multi form: annotate_images, with the frames back as JPEG streams ->
+    (list of bytes, records drawn per frame).  Room per frame: the raw frame's size, and - for the rare frame that compresses to
+    more than that - a second call with the encoder's bound."""
+    shapes = [np.asarray(im).shape for im in images]
+    caps = [min(jpeg_bound(s[1], s[0]), s[0] * s[1] * 3 + 4096) for s in shapes]
+    for attempt in range(2):
+        rc, outs, sizes, drawn = annotate_images_jpeg_raw(handle, images, dets, counts, batch, thresh, quality, caps, labels=labels, pixfmt=pixfmt,
+                                                          multi=multi)
+        if rc == YOLO2_SUCCESS or attempt or not any(int(sizes[f]) > caps[f] for f in range(len(caps))):
+            break
+        caps = [jpeg_bound(s[1], s[0]) for s in shapes]
+    check(rc, "yolo2_hip_annotate_images_pix_jpeg_host")
+    return [outs[f][:int(sizes[f])].tobytes() for f in range(len(outs))], drawn
 
 
 # ------------------------------------------------------------------ more than one GPU
@@ -1039,6 +1166,7 @@ class Yolo2HipMulti:
               "yolo2_hip_multi_run_images_u8_host" if pixfmt is None else "yolo2_hip_multi_run_images_pix_host")
         return region, q.value
 
-    def annotate_images(self, images, dets, counts, batch_per_device: int, thresh: float, labels=None, pixfmt=None):
+    def annotate_images(self, images, dets, counts, batch_per_device: int, thresh: float, labels=None, pixfmt=None, jpeg_quality=None):
         """annotated frames, shard i painted by device i (module-level annotate_images)"""
-        return annotate_images(self._m, images, dets, counts, batch_per_device, thresh, labels=labels, pixfmt=pixfmt, multi=True)
+        return annotate_images(self._m, images, dets, counts, batch_per_device, thresh, labels=labels, pixfmt=pixfmt, multi=True,
+                               jpeg_quality=jpeg_quality)
