@@ -237,6 +237,14 @@ const char *yolo2_hip_fp16_layer_kernel(yolo2_hip_ctx *ctx, int layer_idx);
  * YOLO2_SUCCESS, or YOLO2_ERROR with yolo2_hip_last_error() naming the mismatch. */
 int yolo2_hip_f16_store_check(int store, int pool, int B, int H, int W, int Cp_out, int out_ch_off, int n_store, int dst_B,
                               int dst_H, int dst_W, int dst_Cp);
+/* The launch table the selection makes for a plan batch, as text, without a GPU: one line per step with every field but the
+ * addresses - "L<layer> <kernel> store= grid= block= lds= lt_rows= T= B= in= out= w= w2= a=<the ConvF16Args scalars> pr=<pool / reorg
+ * geometry>" (tensors by the layer whose output they hold, "cat" the concat tensor; weights by conv ordinal) - then, where the images
+ * entries have a layer-0 step from bytes, "u8 <kernel>" and "yuyv <kernel>".  `options` is a space-separated list of name=value
+ * applied to a default option set (NULL or "": the defaults); split = 1: the fp32-tolerance pass.  Returns the length of the text
+ * (buf, if not NULL, receives at most cap - 1 characters of it and a NUL), or YOLO2_ERROR for an unknown option, a value out of
+ * range or a batch outside 1..4096.  A context at that batch runs this table (lanes: each at its part of the batch). */
+int yolo2_hip_f16_plan_describe(const char *options, int split, int batch, char *buf, int cap);
 
 /* Copies layer `layer_idx`'s output of frame `frame` from the last run into the reference's
  * [C][H][W8] int16 layout (pad columns zero) -- the yolov2_region_*_hw.txt style parity hook

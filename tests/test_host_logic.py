@@ -243,6 +243,58 @@ def test_fp16_plan_store_check_rejects_the_layer6_mismatch():
     assert ok(7, 0, B, 13, 13, 1024, 0, 1024, B, 13, 13, 1024) == hipdrv.YOLO2_ERROR            # unknown store kind
 
 
+def _plan_cases():
+    """tests/golden/f16_plan.txt.gz: the commit the tables were recorded from, then per case a '# split= batch= options=' header
+    and the table text."""
+    import gzip
+    with gzip.open(os.path.join(ROOT, "tests", "golden", "f16_plan.txt.gz"), "rt") as f:
+        head, *cases = re.split(r"^# ", f.read(), flags=re.M)
+    assert re.fullmatch(r"[0-9a-f]{40}\n", head), head
+    for case in cases:
+        header, body = case.split("\n", 1)
+        m = re.fullmatch(r"split=([01]) batch=(\d+) options=(.*)", header)
+        yield m[3], int(m[1]), int(m[2]), body
+
+
+def test_fp16_selection_reproduces_the_recorded_tables():
+    """The fp16 launch table is selected from (options, split mode, batch) alone (select_f16_table, csrc/yolo2_fp16.hip); the fixture
+    holds the tables the commit before that split built on an MI355X - every field of every step but the addresses - for both modes,
+    plan batches 1 / 32 / 128 (128: what each of the two lanes builds for a call of 256), the defaults, every f16_* switch alone,
+    f16_lanes=1, stamp_layer=6, f16_skip=63 and six pairs.  No GPU needed."""
+    cases = list(_plan_cases())
+    assert len(cases) == 2 * 3 * 29 and len({c[:3] for c in cases}) == len(cases)
+    singles = {c[0] for c in cases if " " not in c[0]}
+    src = open(os.path.join(ROOT, "yolo-fpga-accelerator_amd", "csrc", "yolo2_plan.hip")).read()
+    flags = set(re.findall(r'\{"(f16_[a-z0-9_]+)", &Y2Options::', src)) - {"f16_lanes", "f16_skip"}
+    assert len(flags) == 19 and {f + "=1" for f in flags} | {"", "f16_lanes=1", "stamp_layer=6", "f16_skip=63"} == singles
+    for options, split, batch, want in cases:
+        assert hipdrv.f16_plan_describe(options, split, batch) == want, (options, split, batch)
+    L = hipdrv.lib()
+    for options, batch, msg in ((b"f16_no_such_switch=1", 2, b"f16_no_such_switch"), (b"f16_lanes=9", 2, b"f16_lanes=9"), (b"", 0, b"batch 0")):
+        assert L.yolo2_hip_f16_plan_describe(options, 0, batch, None, 0) == hipdrv.YOLO2_ERROR and msg in L.yolo2_hip_last_error()
+    assert L.yolo2_hip_f16_plan_describe(None, 1, 2, None, 0) == len(hipdrv.f16_plan_describe("", 1, 2))    # NULL: the defaults
+
+
+def test_fp16_selection_past_the_32bit_offset_guards():
+    """Plan batches nobody should allocate on a shared machine, on the CPU: the guards of the kernels that address their input with
+    signed 32-bit byte offsets ((kLead + B PL + kTail) x item bytes < 2^31), read off the conditions of the selection:
+    k_conv_f16_rwc (layer 2: PL = 209^2, 64-byte items) holds up to batch 768, k_conv_f16_rw / rwb (layers 4 and 6: PL = 105^2,
+    128-byte items) up to batch 1521.  At 1024 layer 2 falls back to k_conv_f16_c32_pool (32-bit UNSIGNED offsets, < 2^32 up to
+    batch 1536) while layers 4 / 6 keep k_conv_f16_rwb; at 2048 layer 2 runs the plain GEMM, layer 4 too (the persistent halo kernel
+    is past its own 2^32 guard, the halo kernel's arena does not fit 104-pixel rows) with layer 5 a launch of its own again, and
+    layer 6 the GEMM with its pool fused.  describe returns the table only if every step passed the store check."""
+    def names(batch):
+        return {int(ln.split()[0][1:]): ln.split()[1] for ln in hipdrv.f16_plan_describe("", 0, batch).splitlines() if ln[0] == "L"}
+    assert (64 + 768 * 209 ** 2 + 1024) * 64 < 2 ** 31 <= (64 + 769 * 209 ** 2 + 1024) * 64
+    assert (64 + 1521 * 105 ** 2 + 1024) * 128 < 2 ** 31 <= (64 + 1522 * 105 ** 2 + 1024) * 128
+    base, b1024, b2048 = names(768), names(1024), names(2048)
+    assert (base[2], base[4], base[6]) == ("k_conv_f16_rwc", "k_conv_f16_rwb<+1x1>", "k_conv_f16_rwb<pool>") and 5 not in base
+    assert {L: k for L, k in b1024.items() if k != base[L]} == {2: "k_conv_f16_c32_pool"}
+    assert {L: k for L, k in b2048.items() if k != base.get(L)} == {2: "k_conv_f16<128,64,32>", 4: "k_conv_f16_glds<128>", 5: "k_conv_f16_glds<64>",
+                                                                     6: "k_conv_f16_glds<128>"}
+    assert not any(k.startswith(("k_conv_f16_rw", "k_conv_f16_halo_p")) for k in b2048.values())
+
+
 def _containment_worker(rank, world, port, q, fail_rank):
     import torch
     import torch.distributed as dist
@@ -299,7 +351,7 @@ def test_no_planning_or_launch_path_reads_the_environment():
         else:
             assert "getenv" not in code, f
     plan = open(os.path.join(csrc, "yolo2_fp16.hip")).read()
-    assert "F16Switches::from_options(c->opt)" in plan
+    assert plan.count("c->f16_plan->opt = c->opt;") == 1    # the fp16 plan's latch at weight load: its own copy of the option set
 
 
 def test_options_are_named_validated_and_parsed_once(monkeypatch):

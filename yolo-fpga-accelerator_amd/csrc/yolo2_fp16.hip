@@ -20,34 +20,13 @@ using namespace y2;
 // Which kernel runs which layer is decided ONCE per (context, batch) and stored as a table of steps; a pass is a walk over
 // that table (no environment look-ups, no selection logic on the launch path).  The A/B switches of the kernel families
 // (options f16_* of the context, from YOLO2_F16_* at context creation or yolo2_hip_set_option: tests and tools/abenv.sh use
-// them) are latched once, when the weights are loaded, into F16Switches.
-
-struct F16Switches {
-    int lanes = 2;            // YOLO2_F16_LANES=n (1..8), YOLO2_F16_NO_LANES -> 1
-    bool no_mfma0 = false, no_glds = false, no_poolfuse = false, no_halo = false, no_persist = false, persist_all = false;
-    bool ring_all = false, no_ring = false, no_c32 = false, m16 = false, w8 = false, no_wide = false;
-    int stamp_layer = -1;     // diagnostic builds (-DY2_STAMPS): the layer whose halo launch records its workgroup timeline
-    bool verbose = false;
-    int skip = 0;             // diagnostic: see Y2Options::f16_skip
-    bool no_fuse1x1 = false, no_rw = false, no_rwb = false, no_rwc = false, ring256 = false, ring_sq = false;
-    static F16Switches from_options(const Y2Options &o)   // the context's option set (y2_internal.hpp), latched at weight load
-    {
-        F16Switches s;
-        s.lanes = o.f16_no_lanes ? 1 : o.f16_lanes;
-        s.no_mfma0 = o.f16_no_mfma0; s.no_glds = o.f16_no_glds; s.no_poolfuse = o.f16_no_poolfuse;
-        s.no_halo = o.f16_no_halo; s.no_persist = o.f16_no_persist; s.persist_all = o.f16_persist_all;
-        s.ring_all = o.f16_ring_all; s.no_ring = o.f16_no_ring; s.no_c32 = o.f16_no_c32;
-        s.m16 = o.f16_m16; s.w8 = o.f16_w8; s.no_wide = o.f16_no_wide;
-        s.no_fuse1x1 = o.f16_no_fuse1x1; s.no_rw = o.f16_no_rw; s.no_rwb = o.f16_no_rwb; s.no_rwc = o.f16_no_rwc; s.ring256 = o.f16_ring256; s.ring_sq = o.f16_ring_sq;
-        s.stamp_layer = o.stamp_layer;
-        s.verbose = o.verbose;
-        s.skip = o.f16_skip;
-        return s;
-    }
-};
+// them) are latched once, when the weights are loaded: the plan keeps its own copy of the context's Y2Options.
+// SELECTION (select_f16_table) is a function of (options, split mode, batch) alone - no HIP call, no device pointer, every field but
+// the addresses (yolo2_hip_f16_plan_describe prints it without a GPU); BINDING (bind_f16_step) fills the addresses from a context.
 
 struct F16Step;
 typedef void (*F16Launch)(const F16Step &, const float *frames, float *region, hipStream_t);
+typedef void (*F16LaunchU8)(const F16Step &, const uint8_t *lb, int lb_first, hipStream_t);
 
 // How a kernel family stores its output (what the extent check below needs to know about it)
 enum F16Store {
@@ -62,22 +41,22 @@ struct F16Step {
     const char *kernel = "";
     F16Launch launch = nullptr;
     F16Store store = FS_FULL;
-    ConvF16Args a;
+    ConvF16Args a = {};
     dim3 grid, block;
     unsigned lds = 0;
     int lt_rows = 0, T = 0;      // extra kernel arguments (halo tile rows, persistent kernels' tile count)
-    const _Float16 *in = nullptr, *w = nullptr, *w2 = nullptr;     // w2 / bias2: the 1x1 layer fused behind a 3x3 (k_conv_f16_rw MODE 2)
-    const float *bias = nullptr, *w0 = nullptr, *bias2 = nullptr;
-    _Float16 *out = nullptr;
     int B = 0;
     // pool / reorg steps: source and destination geometry (iPS / oPS: part strides of split items)
     int iCp = 0, iWp = 0, iPL = 0, oCp = 0, oWp = 0, oPL = 0, OH = 0, OW = 0, iPS = 0, oPS = 0;
+    // What the step reads and writes as selection names it - tensors by the layer whose output they hold (f16_geom; -1: the caller's
+    // frames / region buffer), weights by conv ordinal (-1: none; w2: the 1x1 layer fused behind a 3x3) - and as binding resolves it
+    int t_in = -1, t_out = -1, w_ord = -1, w2_ord = -1;
+    const _Float16 *in = nullptr, *w = nullptr, *w2 = nullptr;
+    const float *bias = nullptr, *w0 = nullptr, *bias2 = nullptr;
+    _Float16 *out = nullptr;
 };
 
-typedef void (*F16LaunchU8)(const F16Step &, const uint8_t *lb, int lb_first, hipStream_t);
-
-struct F16Plan {
-    F16Switches sw;
+struct F16Table {
     int batch = 0;               // the batch the table below was built for (0 = none)
     std::vector<F16Step> steps;
     // the images entries' layer-0 step "from bytes" (layers 0+1 from a chunk's staging buffer), used instead of steps[0]; every
@@ -86,6 +65,10 @@ struct F16Plan {
     F16Step u8;
     F16LaunchU8 launch_u8 = nullptr, launch_yuyv = nullptr;
     const char *yuyv_kernel = "";
+};
+struct F16Plan : F16Table {
+    Y2Options opt;               // the context's option set as it was when the weights were loaded; a lane runs the parent's selection
+    int lanes = 2;               // the only member that changes afterwards (yolo2_hip_set_fp16_lanes): f16_no_lanes ? 1 : f16_lanes
 };
 
 void y2_f16_plan_free(yolo2_hip_ctx *c)
@@ -140,6 +123,7 @@ extern "C" int yolo2_hip_f16_store_check(int store, int pool, int B, int H, int 
 
 
 static int load_fp32_common(yolo2_hip_ctx *c, const void *weights_reorg, size_t n_weights, const void *bias, size_t n_bias, hipMemcpyKind kind);
+static int raise_f16_lds_limits();   // (walks the kernel registry below)
 
 extern "C" int yolo2_hip_load_weights_fp32(yolo2_hip_ctx *c, const float *weights_reorg, size_t n_weights,
                                            const float *bias, size_t n_bias)
@@ -180,7 +164,8 @@ static int pack_half_weights(yolo2_hip_ctx *c, const float *wd, const float *bd)
     y2_f16_plan_free(c);
     c->f16_plan = new (std::nothrow) F16Plan();
     if (!c->f16_plan) return fail(YOLO2_ERROR, "out of host memory");
-    c->f16_plan->sw = F16Switches::from_options(c->opt);   // the ONLY place the fp16 path reads its switches
+    c->f16_plan->opt = c->opt;   // the ONLY place the fp16 path reads the context's switches
+    c->f16_plan->lanes = c->opt.f16_no_lanes ? 1 : c->opt.f16_lanes;
     int rc;
     c->wh_own.reset();
     c->biasf_own.reset();
@@ -227,29 +212,7 @@ static int load_fp32_common(yolo2_hip_ctx *c, const void *weights_reorg, size_t 
     HIP_TRY(hipMemcpy(bd, bias, (size_t)YOLO2_N_BIAS * 4, kind), YOLO2_DMA_ERROR);
     if ((rc = pack_half_weights(c, wd, bd))) return rc;
     // the halo-tile kernels use up to the whole 160 KiB of LDS: raise their dynamic-LDS limit on THIS device
-    HIP_TRY(hipFuncSetAttribute((const void *)k_conv_f16_halo<128, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), YOLO2_ERROR);
-    HIP_TRY(hipFuncSetAttribute((const void *)k_conv_f16_halo<256, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), YOLO2_ERROR);
-    HIP_TRY(hipFuncSetAttribute((const void *)k_conv_f16_halo<256, 2, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), YOLO2_ERROR);
-    HIP_TRY(hipFuncSetAttribute((const void *)k_conv_f16_halo<256, 2, 16, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), YOLO2_ERROR);
-    HIP_TRY(hipFuncSetAttribute((const void *)k_conv_f16_halo_p<256, 16, 32>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), YOLO2_ERROR);
-    HIP_TRY(hipFuncSetAttribute((const void *)k_conv_f16_halo_p<256, 16, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), YOLO2_ERROR);
-    HIP_TRY(hipFuncSetAttribute((const void *)k_conv_f16_halo_p<128, 8, 32>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), YOLO2_ERROR);
-    HIP_TRY(hipFuncSetAttribute((const void *)k_conv_f16_halo_p<128, 8, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), YOLO2_ERROR);
-    HIP_TRY(hipFuncSetAttribute((const void *)k_conv_f16_halo<128, 3, 8, 32, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), YOLO2_ERROR);
-    HIP_TRY(hipFuncSetAttribute((const void *)k_conv_f16_halo<256, 2, 16, 32, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), YOLO2_ERROR);
-    HIP_TRY(hipFuncSetAttribute((const void *)k_conv_f16_halo_p<256, 16, 32, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), YOLO2_ERROR);
-    HIP_TRY(hipFuncSetAttribute((const void *)k_conv_f16_halo_p<128, 8, 32, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), YOLO2_ERROR);
-    HIP_TRY(hipFuncSetAttribute((const void *)k_conv_f16_halo<256, 2, 16, 32, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), YOLO2_ERROR);
-    HIP_TRY(hipFuncSetAttribute((const void *)k_conv_f16_rw<13, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), YOLO2_ERROR);
-    HIP_TRY(hipFuncSetAttribute((const void *)k_conv_f16_rw<13, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), YOLO2_ERROR);
-    HIP_TRY(hipFuncSetAttribute((const void *)k_conv_f16_rw<13, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), YOLO2_ERROR);
-    HIP_TRY(hipFuncSetAttribute((const void *)k_conv_f16_rwb<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), YOLO2_ERROR);
-    HIP_TRY(hipFuncSetAttribute((const void *)k_conv_f16_rwb<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), YOLO2_ERROR);
-    HIP_TRY(hipFuncSetAttribute((const void *)k_conv_f16_rwc, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), YOLO2_ERROR);
-    HIP_TRY(hipFuncSetAttribute((const void *)k_gemm1_f16_p<256, 64, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), YOLO2_ERROR);
-    HIP_TRY(hipFuncSetAttribute((const void *)k_gemm1_f16_p<256, 128, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), YOLO2_ERROR);
-    HIP_TRY(hipFuncSetAttribute((const void *)k_gemm1_f16_p<128, 256, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), YOLO2_ERROR);
-    HIP_TRY(hipFuncSetAttribute((const void *)k_gemm1_f16_p<256, 256, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), YOLO2_ERROR);
+    if ((rc = raise_f16_lds_limits())) return rc;
     if (!c->w0f && (rc = y2_alloc_owned(c->w0f_own, c->w0f, 27 * 32 + 32))) return rc;
     hipLaunchKernelGGL(k_pack_w0_f32, dim3(4), dim3(256), 0, nullptr, wd, bd, c->w0f, c->w0f + 27 * 32);
     HIP_TRY(hipGetLastError(), YOLO2_ERROR);
@@ -266,13 +229,29 @@ static int load_fp32_common(yolo2_hip_ctx *c, const void *weights_reorg, size_t 
     return YOLO2_SUCCESS;
 }
 
-static int alloc_half(yolo2_hip_ctx::HalfTensor &t, int C, int Cp, int H, int W, int B)
+// ---- tensor geometry: follows from kNet, the batch and the split mode; nothing here allocates.  The tensor that holds layer i's
+// output (a pool layer's: the pooled map; 24 and 27: the concat tensor they are placed in).  C == 0: the layer has none - layer 0's
+// 416x416x32 tensor never exists (conv0+pool are fused), a route concatenates by placement, layer 30 writes the region buffer.
+typedef yolo2_hip_ctx::HalfGeom HalfGeom;
+static HalfGeom f16_geom(int i, bool split, int B)
 {
-    t.C = C; t.Cp = Cp; t.H = H; t.W = W; t.Wp = W + 1; t.PL = (H + 1) * t.Wp; t.B = B;
-    t.items = (size_t)kLead + (size_t)B * t.PL + kTail;
-    const int rc = y2_alloc_owned(t.own, t.d, t.items * Cp);
+    HalfGeom g;
+    const LayerDesc &l = kNet[std::max(i, 0)];
+    if (i == 24 || i == 27) { g.C = 1280; g.H = g.W = 13; }
+    else if (i >= 1 && i <= 29 && l.type == L_CONV) { g.C = l.n; g.H = l.h; g.W = l.w; }
+    else if (i >= 1 && i <= 29 && l.type == L_MAX) { g.C = l.c; g.H = l.h / 2; g.W = l.w / 2; }
+    else return g;
+    g.Cp = item_halves(g.C, split); g.Wp = g.W + 1; g.PL = (g.H + 1) * g.Wp; g.B = B;
+    g.items = (size_t)kLead + (size_t)B * g.PL + kTail;
+    return g;
+}
+
+static int alloc_half(yolo2_hip_ctx::HalfTensor &t, const HalfGeom &g)
+{
+    static_cast<HalfGeom &>(t) = g;
+    const int rc = y2_alloc_owned(t.own, t.d, t.items * t.Cp);
     if (rc) return rc;
-    HIP_TRY(hipMemset(t.d, 0, t.items * Cp * 2), YOLO2_DMA_ERROR);  // zeros = conv padding and channel padding
+    HIP_TRY(hipMemset(t.d, 0, t.items * t.Cp * 2), YOLO2_DMA_ERROR);  // zeros = conv padding and channel padding
     return YOLO2_SUCCESS;
 }
 
@@ -282,15 +261,9 @@ static int ensure_f16_batch(yolo2_hip_ctx *c, int B)
     y2_free_tensors(c->h_in, c->h_out, c->h_cat, c->f16_batch);
     if (c->f16_plan) { c->f16_plan->batch = 0; c->f16_plan->steps.clear(); }   // the table points into the tensors just freed
     int rc;
-    if ((rc = alloc_half(c->h_cat, 1280, item_halves(1280, c->split), 13, 13, B))) return rc;
-    for (int i = 1; i < 30; ++i) {   // layer 0's 416x416x32 tensor never exists: conv0+pool are fused
-        const LayerDesc &l = kNet[i];
-        if (l.type == L_CONV && i != 24) {
-            if ((rc = alloc_half(c->h_out[i], l.n, item_halves(l.n, c->split), l.h, l.w, B))) return rc;
-        } else if (l.type == L_MAX) {
-            if ((rc = alloc_half(c->h_out[i], l.c, item_halves(l.c, c->split), l.h / 2, l.w / 2, B))) return rc;
-        }
-    }
+    if ((rc = alloc_half(c->h_cat, f16_geom(24, c->split, B)))) return rc;
+    for (int i = 1; i < 30; ++i)
+        if (i != 24 && i != 27 && f16_geom(i, c->split, B).C && (rc = alloc_half(c->h_out[i], f16_geom(i, c->split, B)))) return rc;
     y2_view_of(c->h_out[24], c->h_cat);
     y2_view_of(c->h_out[27], c->h_cat);
     c->f16_batch = B;
@@ -300,404 +273,430 @@ static int ensure_f16_batch(yolo2_hip_ctx *c, int B)
     return YOLO2_SUCCESS;
 }
 
-// ---- launchers: one per kernel instantiation, all with the table's signature
-#define Y2_LAUNCHER(name, ...)                                                                         \
-    static void name(const F16Step &s, const float *frames, float *region, hipStream_t st)           \
-    {                                                                                                  \
-        (void)frames; (void)region;                                                                    \
-        __VA_ARGS__;                                                                                   \
-    }
-template <bool SP = false> Y2_LAUNCHER(L_conv0_mfma, hipLaunchKernelGGL(k_conv0_pool_mfma<SP>, s.grid, s.block, 0, st, frames, s.w0, s.bias, s.out, 416, 416, s.oWp, s.oPL, s.T))
-template <bool SP>
-static void L_conv0_mfma_u8(const F16Step &s, const uint8_t *lb, int lb_first, hipStream_t st)
-{
-    hipLaunchKernelGGL(k_conv0_pool_mfma_u8<SP>, s.grid, s.block, 0, st, lb, lb_first, s.w0, s.bias, s.out, s.oWp, s.oPL, s.T);
-}
-template <bool SP>
-static void L_conv0_mfma_yuyv(const F16Step &s, const uint8_t *lb, int lb_first, hipStream_t st)
-{
-    hipLaunchKernelGGL(k_conv0_pool_mfma_yuyv<SP>, s.grid, s.block, 0, st, lb, lb_first, s.w0, s.bias, s.out, s.oWp, s.oPL, s.T);
-}
-template <bool SP> Y2_LAUNCHER(L_conv0_valu, hipLaunchKernelGGL(k_conv0_pool_f16<SP>, s.grid, s.block, 0, st, frames, s.w0, s.bias, s.out, s.B, 416, 416, s.oWp, s.oPL))
-template <int BN> Y2_LAUNCHER(L_ring, hipLaunchKernelGGL((k_gemm1_f16_p<256, BN, 3>), s.grid, s.block, s.lds, st, s.in, s.w, s.bias, s.out,
-                                                            s.store == FS_REGION ? region : (float *)nullptr, s.a, s.T))
-Y2_LAUNCHER(L_ring_sq, hipLaunchKernelGGL((k_gemm1_f16_p<256, 256, 2>), s.grid, s.block, s.lds, st, s.in, s.w, s.bias, s.out, (float *)nullptr, s.a, s.T))
-Y2_LAUNCHER(L_ring256, hipLaunchKernelGGL((k_gemm1_f16_p<128, 256, 3>), s.grid, s.block, s.lds, st, s.in, s.w, s.bias, s.out, (float *)nullptr, s.a, s.T))
-Y2_LAUNCHER(L_c32_pool, hipLaunchKernelGGL(k_conv_f16_c32_pool, s.grid, s.block, s.lds, st, s.in, s.w, s.bias, s.out, s.a, s.T))
-Y2_LAUNCHER(L_rwc, hipLaunchKernelGGL(k_conv_f16_rwc, s.grid, s.block, s.lds, st, s.in, s.w, s.bias, s.out, s.a, s.lt_rows, s.T))
-template <int BN, bool SP = false> Y2_LAUNCHER(L_glds, hipLaunchKernelGGL((k_conv_f16_glds<BN, SP>), s.grid, s.block, 0, st, s.in, s.w, s.bias, s.out,
-                                                                            s.store == FS_REGION ? region : (float *)nullptr, s.a))
-template <int BN, int BK> Y2_LAUNCHER(L_reg, hipLaunchKernelGGL((k_conv_f16<128, BN, BK>), s.grid, s.block, 0, st, s.in, s.w, s.bias, s.out,
-                                                                   s.store == FS_REGION ? region : (float *)nullptr, s.a))
-template <int BN, int NW, int TS, bool SP = false> Y2_LAUNCHER(L_halo_p, hipLaunchKernelGGL((k_conv_f16_halo_p<BN, NW, TS, SP>), s.grid, s.block, s.lds, st, s.in, s.w,
-                                                                                            s.bias, s.out, s.a, s.lt_rows, s.T))
-template <int BN, int NB, int NW, int TS, bool SP = false, bool F1 = false>
-Y2_LAUNCHER(L_halo, hipLaunchKernelGGL((k_conv_f16_halo<BN, NB, NW, TS, SP, F1>), s.grid, s.block, s.lds, st, s.in, s.w, s.bias, s.out, s.a, s.lt_rows, s.w2, s.bias2))
-template <int MODE> Y2_LAUNCHER(L_rw, hipLaunchKernelGGL((k_conv_f16_rw<13, MODE>), s.grid, s.block, s.lds, st, s.in, s.w, s.bias, s.out, s.w2, s.bias2, s.a,
-                                                       s.lt_rows, s.T))
-template <int MODE> Y2_LAUNCHER(L_rwb, hipLaunchKernelGGL((k_conv_f16_rwb<MODE>), s.grid, s.block, s.lds, st, s.in, s.w, s.bias, s.out, s.w2, s.bias2, s.a, s.T))
-Y2_LAUNCHER(L_maxpool_split, hipLaunchKernelGGL(k_maxpool2_split, s.grid, s.block, 0, st, s.in, s.out, s.oPS, s.oCp, s.B, s.OH, s.OW, s.iWp, s.iPL, s.oWp, s.oPL))
-Y2_LAUNCHER(L_reorg_split, hipLaunchKernelGGL(k_reorg_split, s.grid, s.block, 0, st, s.in, s.out, s.B, s.iPS, s.iCp, s.iWp, s.iPL, s.oPS, s.oCp, s.oWp, s.oPL))
-Y2_LAUNCHER(L_maxpool, hipLaunchKernelGGL(k_maxpool2_f16, s.grid, s.block, 0, st, s.in, s.out, s.oCp, s.B, s.OH, s.OW, s.iWp, s.iPL, s.oWp, s.oPL))
-Y2_LAUNCHER(L_reorg, hipLaunchKernelGGL(k_reorg_f16, s.grid, s.block, 0, st, s.in, s.out, s.B, s.iCp, s.iWp, s.iPL, s.oCp, s.oWp, s.oPL))
+// ---- launchers: one per kernel signature (K: the instantiation), all with the table's signature
+#define Y2_LAUNCHER(name, ...)                                                                                        \
+    template <auto K> static void name(const F16Step &s, const float *frames, float *region, hipStream_t st)        \
+    { (void)frames; (void)region; hipLaunchKernelGGL(K, s.grid, s.block, s.lds, st, __VA_ARGS__); }
+Y2_LAUNCHER(L_conv0_mfma, frames, s.w0, s.bias, s.out, 416, 416, s.oWp, s.oPL, s.T)
+Y2_LAUNCHER(L_conv0_valu, frames, s.w0, s.bias, s.out, s.B, 416, 416, s.oWp, s.oPL)
+Y2_LAUNCHER(L_gemm, s.in, s.w, s.bias, s.out, s.store == FS_REGION ? region : (float *)nullptr, s.a)         // k_conv_f16_glds, k_conv_f16
+Y2_LAUNCHER(L_ring, s.in, s.w, s.bias, s.out, s.store == FS_REGION ? region : (float *)nullptr, s.a, s.T)    // k_gemm1_f16_p
+Y2_LAUNCHER(L_tiles, s.in, s.w, s.bias, s.out, s.a, s.T)                                                       // k_conv_f16_c32_pool
+Y2_LAUNCHER(L_rows, s.in, s.w, s.bias, s.out, s.a, s.lt_rows, s.T)                                             // k_conv_f16_rwc, k_conv_f16_halo_p
+Y2_LAUNCHER(L_halo, s.in, s.w, s.bias, s.out, s.a, s.lt_rows, s.w2, s.bias2)
+Y2_LAUNCHER(L_rw, s.in, s.w, s.bias, s.out, s.w2, s.bias2, s.a, s.lt_rows, s.T)
+Y2_LAUNCHER(L_rwb, s.in, s.w, s.bias, s.out, s.w2, s.bias2, s.a, s.T)
+Y2_LAUNCHER(L_maxpool_split, s.in, s.out, s.oPS, s.oCp, s.B, s.OH, s.OW, s.iWp, s.iPL, s.oWp, s.oPL)
+Y2_LAUNCHER(L_maxpool, s.in, s.out, s.oCp, s.B, s.OH, s.OW, s.iWp, s.iPL, s.oWp, s.oPL)
+Y2_LAUNCHER(L_reorg_split, s.in, s.out, s.B, s.iPS, s.iCp, s.iWp, s.iPL, s.oPS, s.oCp, s.oWp, s.oPL)
+Y2_LAUNCHER(L_reorg, s.in, s.out, s.B, s.iCp, s.iWp, s.iPL, s.oCp, s.oWp, s.oPL)
 #undef Y2_LAUNCHER
-
-// Builds the table for batch B (the tensors exist: ensure_f16_batch).  The selection rules are those measured in rounds 1-2
-// (DESIGN.md 4.3); every conv step passes f16_store_check against the tensor it is handed before it enters the table.
-static int build_f16_plan(yolo2_hip_ctx *c, int B)
+template <auto K> static void L_conv0_bytes(const F16Step &s, const uint8_t *lb, int lb_first, hipStream_t st)   // the images entries' layer 0
 {
-    F16Plan &P = *c->f16_plan;
-    const F16Switches &sw = P.sw;
-    P.steps.clear();
-    P.batch = 0;
-    P.launch_u8 = P.launch_yuyv = nullptr;
-    typedef yolo2_hip_ctx::HalfTensor HT;
-    const bool split = c->split;     // "fp32tol" mode: items of three parts [hi | lo | hi], SPLIT kernel instantiations
-    auto checked_push = [&](F16Step &s, const HT &dst) -> int {
-        const int rc = f16_store_check(s.kernel, s.store, s.a.pool, B, s.a.H, s.a.W, s.a.Cp_out, s.a.out_ch_off, s.a.n_store, s.a.oWp, s.a.oPL,
-                                       s.a.npix, s.a.npool, dst.B, dst.H, dst.W, dst.Cp, s.store == FS_REGION ? 0 : s.a.split_n);
-        if (rc) return rc;
-        P.steps.push_back(s);
-        return YOLO2_SUCCESS;
-    };
+    hipLaunchKernelGGL(K, s.grid, s.block, 0, st, lb, lb_first, s.w0, s.bias, s.out, s.oWp, s.oPL, s.T);
+}
+
+// ---- the kernel registry: every instantiation the table can name, ONCE - its name string (tools, bench.py, the profiles and the
+// tests key on these), its launcher and kernel, its block size and whether the kernel's dynamic-LDS limit is raised to the whole
+// 160 KiB of a CU at weight load.  XB: the bytes form of layer 0.  A selection site names an entry (use()).
+#define F16_KERNELS(X, XB)                                                                                             \
+    X(FK_C0_MFMA_SP,     "k_conv0_pool_mfma<split>",           L_conv0_mfma, k_conv0_pool_mfma<true>, 256, 0)          \
+    X(FK_C0_MFMA,        "k_conv0_pool_mfma",                  L_conv0_mfma, k_conv0_pool_mfma<false>, 256, 0)         \
+    X(FK_C0_VALU_SP,     "k_conv0_pool_f16<split>",            L_conv0_valu, k_conv0_pool_f16<true>, 256, 0)           \
+    X(FK_C0_VALU,        "k_conv0_pool_f16",                   L_conv0_valu, k_conv0_pool_f16<false>, 256, 0)          \
+    XB(FK_C0_U8_SP,      "k_conv0_pool_mfma_u8<split>",        k_conv0_pool_mfma_u8<true>)                             \
+    XB(FK_C0_U8,         "k_conv0_pool_mfma_u8",               k_conv0_pool_mfma_u8<false>)                            \
+    XB(FK_C0_YUYV_SP,    "k_conv0_pool_mfma_yuyv<split>",      k_conv0_pool_mfma_yuyv<true>)                           \
+    XB(FK_C0_YUYV,       "k_conv0_pool_mfma_yuyv",             k_conv0_pool_mfma_yuyv<false>)                          \
+    X(FK_RW,             "k_conv_f16_rw",                      L_rw, (k_conv_f16_rw<13, 0>), 256, 1)                   \
+    X(FK_RW_POOL,        "k_conv_f16_rw<pool>",                L_rw, (k_conv_f16_rw<13, 1>), 256, 1)                   \
+    X(FK_RW_1X1,         "k_conv_f16_rw<+1x1>",                L_rw, (k_conv_f16_rw<13, 2>), 256, 1)                   \
+    X(FK_RWB_POOL,       "k_conv_f16_rwb<pool>",               L_rwb, k_conv_f16_rwb<1>, 256, 1)                       \
+    X(FK_RWB_1X1,        "k_conv_f16_rwb<+1x1>",               L_rwb, k_conv_f16_rwb<2>, 256, 1)                       \
+    X(FK_RING_SQ,        "k_gemm1_f16_p<256,256,2>",           L_ring, (k_gemm1_f16_p<256, 256, 2>), 1024, 1)          \
+    X(FK_RING256,        "k_gemm1_f16_p<128,256,3>",           L_ring, (k_gemm1_f16_p<128, 256, 3>), 512, 1)           \
+    X(FK_RING_64,        "k_gemm1_f16_p<256,64,3>",            L_ring, (k_gemm1_f16_p<256, 64, 3>), 256, 1)            \
+    X(FK_RING_128,       "k_gemm1_f16_p<256,128,3>",           L_ring, (k_gemm1_f16_p<256, 128, 3>), 512, 1)           \
+    X(FK_RWC,            "k_conv_f16_rwc",                     L_rows, k_conv_f16_rwc, 256, 1)                         \
+    X(FK_C32_POOL,       "k_conv_f16_c32_pool",                L_tiles, k_conv_f16_c32_pool, 256, 0)                   \
+    X(FK_GLDS_64_SP,     "k_conv_f16_glds<64,split>",          L_gemm, (k_conv_f16_glds<64, true>), 256, 0)            \
+    X(FK_GLDS_64,        "k_conv_f16_glds<64>",                L_gemm, (k_conv_f16_glds<64, false>), 256, 0)           \
+    X(FK_REG_64_64,      "k_conv_f16<128,64,64>",              L_gemm, (k_conv_f16<128, 64, 64>), 256, 0)              \
+    X(FK_REG_64_32,      "k_conv_f16<128,64,32>",              L_gemm, (k_conv_f16<128, 64, 32>), 256, 0)              \
+    X(FK_GLDS_128_SP,    "k_conv_f16_glds<128,split>",         L_gemm, (k_conv_f16_glds<128, true>), 256, 0)           \
+    X(FK_GLDS_128,       "k_conv_f16_glds<128>",               L_gemm, (k_conv_f16_glds<128, false>), 256, 0)          \
+    X(FK_REG_128_64,     "k_conv_f16<128,128,64>",             L_gemm, (k_conv_f16<128, 128, 64>), 256, 0)             \
+    X(FK_REG_128_32,     "k_conv_f16<128,128,32>",             L_gemm, (k_conv_f16<128, 128, 32>), 256, 0)             \
+    X(FK_HALO_P_256_SP,  "k_conv_f16_halo_p<256,16,32,split>", L_rows, (k_conv_f16_halo_p<256, 16, 32, true>), 1024, 1) \
+    X(FK_HALO_P_256_M16, "k_conv_f16_halo_p<256,16,16>",       L_rows, (k_conv_f16_halo_p<256, 16, 16, false>), 1024, 1) \
+    X(FK_HALO_P_256,     "k_conv_f16_halo_p<256,16,32>",       L_rows, (k_conv_f16_halo_p<256, 16, 32, false>), 1024, 1) \
+    X(FK_HALO_P_128_SP,  "k_conv_f16_halo_p<128,8,32,split>",  L_rows, (k_conv_f16_halo_p<128, 8, 32, true>), 512, 1)  \
+    X(FK_HALO_P_128_M16, "k_conv_f16_halo_p<128,8,16>",        L_rows, (k_conv_f16_halo_p<128, 8, 16, false>), 512, 1) \
+    X(FK_HALO_P_128,     "k_conv_f16_halo_p<128,8,32>",        L_rows, (k_conv_f16_halo_p<128, 8, 32, false>), 512, 1) \
+    X(FK_HALO_256_1X1,   "k_conv_f16_halo<256,2,16>+1x1",      L_halo, (k_conv_f16_halo<256, 2, 16, 32, false, true>), 1024, 1) \
+    X(FK_HALO_256_SP,    "k_conv_f16_halo<256,2,16,32,split>", L_halo, (k_conv_f16_halo<256, 2, 16, 32, true, false>), 1024, 1) \
+    X(FK_HALO_256_M16,   "k_conv_f16_halo<256,2,16,16>",       L_halo, (k_conv_f16_halo<256, 2, 16, 16, false, false>), 1024, 1) \
+    X(FK_HALO_256,       "k_conv_f16_halo<256,2,16>",          L_halo, (k_conv_f16_halo<256, 2, 16, 32, false, false>), 1024, 1) \
+    X(FK_HALO_256_W8,    "k_conv_f16_halo<256,2>",             L_halo, (k_conv_f16_halo<256, 2, 8, 32, false, false>), 512, 1) \
+    X(FK_HALO_128_SP,    "k_conv_f16_halo<128,3,8,32,split>",  L_halo, (k_conv_f16_halo<128, 3, 8, 32, true, false>), 512, 1) \
+    X(FK_HALO_128,       "k_conv_f16_halo<128,3>",             L_halo, (k_conv_f16_halo<128, 3, 8, 32, false, false>), 512, 1) \
+    X(FK_MAXPOOL_SP,     "k_maxpool2_split",                   L_maxpool_split, k_maxpool2_split, 256, 0)              \
+    X(FK_MAXPOOL,        "k_maxpool2_f16",                     L_maxpool, k_maxpool2_f16, 256, 0)                      \
+    X(FK_REORG_SP,       "k_reorg_split",                      L_reorg_split, k_reorg_split, 256, 0)                   \
+    X(FK_REORG,          "k_reorg_f16",                        L_reorg, k_reorg_f16, 256, 0)
+struct F16Kernel { const char *name; F16Launch launch; F16LaunchU8 launch_u8; unsigned block; const void *raise_lds; };
+#define ID(id, ...) id,
+enum F16Kid { F16_KERNELS(ID, ID) };
+#define X(id, name, form, kernel, block, raise) {name, form<kernel>, nullptr, block, raise ? (const void *)kernel : nullptr},
+#define XB(id, name, kernel) {name, nullptr, L_conv0_bytes<kernel>, 256, nullptr},
+static const F16Kernel kF16Kernels[] = {F16_KERNELS(X, XB)};
+#undef ID
+#undef X
+#undef XB
+
+static int raise_f16_lds_limits()
+{
+    for (const F16Kernel &k : kF16Kernels)
+        if (k.raise_lds) HIP_TRY(hipFuncSetAttribute(k.raise_lds, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), YOLO2_ERROR);
+    return YOLO2_SUCCESS;
+}
+static void use(F16Step &s, F16Kid k) { s.kernel = kF16Kernels[k].name; s.launch = kF16Kernels[k].launch; s.block = dim3(kF16Kernels[k].block); }
+
+// ---- selection: (options, split mode, batch) -> the table without addresses.  The rules are those measured in rounds 1-4 (DESIGN.md
+// 4.3).  One function per kernel family, tried in the order of select_f16_table; each either takes the layer (fills the step, returns
+// true) or declines it and leaves the step as it found it.
+struct F16Conv {              // one conv layer as the family functions see it: none of them needs more than this and the step it fills
+    const Y2Options &o;
+    bool split;               // "fp32tol" mode: items of three parts [hi | lo | hi], SPLIT kernel instantiations
+    int B, i;
+    const LayerDesc &l;
+    bool bk64, glds;          // K-step of 64 channels wherever the item size allows it; LDS-DMA staging wherever the K-step is 64
+    bool pool_next, persist_ok, fuse_pool, in32;   // (in32: 32-bit byte offsets into the input)
+};
+constexpr size_t kLdsCap = 160 * 1024;
+// persistent kernels: every workgroup walks the same number of tiles (`rounds`); a multiple of 8 workgroups, at most one per CU
+static dim3 persistent_grid(int T)
+{
+    const int rounds = (T + 255) / 256;
+    return dim3(std::min(256, std::max(8, round_up((T + rounds - 1) / rounds, 8))));
+}
+// the step stores the pooled tensor of layer i + 1 (which then has no launch of its own)
+static void fuse_pool_into_next(const F16Conv &q, F16Step &s)
+{
+    const HalfGeom tp = f16_geom(q.i + 1, q.split, q.B);
+    s.a.pool = 1; s.a.oWp = tp.Wp; s.a.oPL = tp.PL; s.a.npool = q.B * tp.H * tp.W; s.a.Cp_out = tp.Cp; s.t_out = q.i + 1;
+}
+// the step runs the 1x1 layer i + 1 in its epilogue and stores THAT layer's tensor (the tensor between them is never written)
+static void fuse_1x1_next(const F16Conv &q, F16Step &s)
+{
+    const LayerDesc &nx = kNet[q.i + 1];
+    s.a.Cp_out = f16_geom(q.i + 1, q.split, q.B).Cp; s.a.N = nx.n; s.a.n_store = round_up(nx.n, 32); s.a.out_ch_off = 0;
+    s.t_out = q.i + 1; s.w2_ord = s.w_ord + 1;   // (the NEXT conv's weights)
+}
+// The 64 -> 128 channel 3x3 layers at 104 x 104 (4 and 6): weights resident in registers, two image rows per tile, one barrier
+// per tile (k_conv_f16_rw).  Layer 6 fuses its pool (MODE 1); layer 4 fuses the 1x1 layer 5, its only consumer (MODE 2:
+// the 128-channel tensor between them is never written); MODE 0 stores the plain tensor.
+static bool take_rw(const F16Conv &q, F16Step &s)
+{
+    const LayerDesc &l = q.l, &nx = kNet[q.i + 1]; ConvF16Args &a = s.a;
+    if (q.split || q.o.f16_no_rw || l.size != 3 || a.Cp_in != 64 || l.n != 128 || l.w != 8 * 13 || (l.h & 1) || q.o.f16_no_glds ||
+        ((size_t)kLead + (size_t)q.B * a.PL + kTail) * 128 >= (1ull << 31))   // (signed 32-bit byte offsets into the input)
+        return false;
+    const bool fuse1 = !q.pool_next && !q.o.f16_no_fuse1x1 && nx.type == L_CONV && nx.size == 1 && nx.c == 128 && nx.n == 64 && nx.leaky == l.leaky &&
+                       nx.h == l.h && nx.w == l.w && q.i + 1 != 16 && q.i + 1 != 24;   // (and nothing but layer i + 1 reads layer i: true for every conv of this network except 16)
+    s.T = q.B * (l.h / 2); s.grid = persistent_grid(s.T);
+    const int n_stage = (2 * l.w + 2 * (l.w + 1) + 7) / 8;
+    const bool rwb_ok = !q.o.f16_no_rwb && l.leaky && a.n_store == 128;   // k_conv_f16_rwb: leaky layers, every channel stored
+    s.lt_rows = n_stage * 8;
+    s.lds = (unsigned)(2 * s.lt_rows * 128 + 13 * 1024);   // two input tiles + zero region
+    use(s, FK_RW); s.store = FS_FULL;
+    if (q.pool_next) {
+        fuse_pool_into_next(q, s);
+        s.lds += 2 * (26 * 16 / 4 / 2) * 136 * 2;   // + two pooled tiles
+        use(s, FK_RW_POOL); s.store = FS_POOL_ONLY;
+        // the epilogue inside the MFMA stream (k_conv_f16_rwb)
+        if (rwb_ok) { s.lt_rows = 432; s.lds = (unsigned)(2 * 432 * 128 + 2 * 52 * 136 * 2); use(s, FK_RWB_POOL); }
+    } else if (fuse1) {
+        fuse_1x1_next(q, s);
+        s.lt_rows = std::max(n_stage, ((13 * 16 * 136 * 2 + 127) / 128 + 7) / 8) * 8;   // the 208 x 136-half intermediate tile must fit an input buffer
+        s.lds = (unsigned)(2 * s.lt_rows * 128 + 13 * 1024); use(s, FK_RW_1X1);
+        // (rwb: 2 x 432 x 128 + 208 x 256 = 160 KB: the whole LDS of a CU)
+        if (rwb_ok && nx.leaky && a.Cp_out == 64) { s.lt_rows = 432; s.lds = (unsigned)(2 * 432 * 128 + 208 * 256); use(s, FK_RWB_1X1); }
+    }
+    return true;
+}
+// 1x1 layers: persistent workgroups over a ring of staged K-steps (k_gemm1_f16_p), bm pixels x bn channels per tile
+static void ring_tiles(F16Step &s, int bm, int bn, F16Kid k, unsigned lds)
+{
+    s.a.n_tiles = round_up(s.a.N, bn) / bn;
+    s.T = ((s.a.npix + bm - 1) / bm) * s.a.n_tiles; s.grid = persistent_grid(s.T);
+    use(s, k); s.lds = lds; if (s.store != FS_REGION) s.store = FS_FULL;
+}
+static bool take_ring(const F16Conv &q, F16Step &s)
+{
+    if (q.l.size != 1 || !q.bk64 || !q.in32 || q.o.f16_no_ring) return false;
+    // 1x1 layers whose channel count is a multiple of 256 (13, 15: 256; 19, 21: 512): 128 pixels x 256 channels per tile, so that the
+    // input - the bytes this HBM-bound layer moves - is read once per 256 output channels instead of once per 128
+    // (experiment f16_ring_sq) the same layers on 256 x 256 tiles, sixteen wavefronts, two 64-KB stages: twice the FLOPs per staged byte of the
+    // 128 x 128 tiles (an LDS-DMA'd byte feeds 128 FLOPs instead of 64), at the price of 338 / 170 tiles for 256 CUs
+    const bool n256 = !q.split && q.i != 30 && q.l.n % 256 == 0;
+    if (n256 && q.o.f16_ring_sq) ring_tiles(s, 256, 256, FK_RING_SQ, 2 * (256 + 256) * 128);
+    else if (n256 && q.o.f16_ring256) ring_tiles(s, 128, 256, FK_RING256, 3 * (128 + 256) * 128);
+    else if (q.i != 30 && (!q.o.f16_ring_all || q.split)) return false;
+    else if (q.l.n <= 64) ring_tiles(s, 256, 64, FK_RING_64, 3 * (256 + 64) * 128);
+    else ring_tiles(s, 256, 128, FK_RING_128, 3 * (256 + 128) * 128);
+    return true;
+}
+// the 32-channel layer + its pool with the weights in registers and a ring of image rows in LDS (k_conv_f16_rwc): runs of
+// 52, 26 or 13 consecutive row pairs per workgroup - the longest that still gives every CU a run
+static bool take_rwc(const F16Conv &q, F16Step &s)
+{
+    const LayerDesc &l = q.l; const ConvF16Args &a = s.a;
+    if (q.split || q.o.f16_no_rwc || !q.fuse_pool || a.Cp_in != 32 || l.size != 3 || l.n != 64 || l.w != 208 || l.h != 208 || !l.leaky ||
+        a.Cp_out != 64 || a.n_store != 64 || a.out_ch_off != 0 || ((size_t)kLead + (size_t)q.B * a.PL + kTail) * 64 >= (1ull << 31))
+        return false;
+    int run_len = 52;
+    while (run_len > 13 && q.B * (l.h / 2 / run_len) < 256) run_len /= 2;
+    s.lt_rows = run_len;                       // (the launcher hands it to the kernel)
+    s.T = q.B * (l.h / 2 / run_len);           // runs
+    use(s, FK_RWC); s.store = FS_POOL_ONLY;
+    s.grid = dim3((unsigned)std::min(s.T, 256)); s.lds = (unsigned)(8 * 212 * 64 + 3 * 104 * 72 * 2);
+    return true;
+}
+// the 32-channel layer + its pool: 16 x 16 tiles, patch and all nine taps' weights resident in LDS (k_conv_f16_c32_pool)
+static bool take_c32_pool(const F16Conv &q, F16Step &s)
+{
+    const LayerDesc &l = q.l;
+    if (!q.fuse_pool || s.a.Cp_in != 32 || l.size != 3 || l.n != 64 || l.h % 16 || l.w % 16 || s.a.Cp_out < 64 ||
+        ((size_t)kLead + (size_t)q.B * s.a.PL) * 64 >= (1ull << 32) || q.o.f16_no_c32)
+        return false;
+    s.T = q.B * (l.h / 16) * (l.w / 16);
+    use(s, FK_C32_POOL); s.store = FS_POOL_ONLY;
+    s.grid = dim3((unsigned)std::min(s.T, 512)); s.lds = (9 * 64 + 336) * 64;   // two workgroups per CU, weights staged once each
+    return true;
+}
+// the implicit GEMM on 128-row tiles (32 pool windows where the pool is fused) x bn channels: takes every layer
+// (a 256x128 tile with 8 wavefronts and per-tap A staging was measured 8 % SLOWER than 128x128
+//  with two workgroups per CU: without the halo reuse the bigger tile only adds barrier cost)
+static bool take_gemm(const F16Conv &q, F16Step &s, int bn)
+{
+    static const F16Kid kid[2][4] = {{FK_GLDS_64_SP, FK_GLDS_64, FK_REG_64_64, FK_REG_64_32}, {FK_GLDS_128_SP, FK_GLDS_128, FK_REG_128_64, FK_REG_128_32}};
+    const int m_tiles = s.a.pool ? (s.a.npool + 31) / 32 : (s.a.npix + 127) / 128;
+    s.a.n_tiles = round_up(q.l.n, bn) / bn; s.grid = dim3(m_tiles * s.a.n_tiles);
+    use(s, kid[bn == 128][q.split ? 0 : (q.glds ? 1 : (q.bk64 ? 2 : 3))]);
+    return true;
+}
+// dense halo tile: 256 pixels + W+1 on either side, rounded to 8-row groups, + 8 zero rows (A: two buffers of lt_rows x 128 B)
+static int halo_lt_rows(int w) { return round_up(256 + 2 * (w + 1), 8) + 8; }
+// persistent halo-tile kernel: the workgroup walks its tiles, the next tile's staging overlaps this one's tail
+static bool take_halo_p(const F16Conv &q, F16Step &s)
+{
+    static const F16Kid kid[2][3] = {{FK_HALO_P_128_SP, FK_HALO_P_128_M16, FK_HALO_P_128}, {FK_HALO_P_256_SP, FK_HALO_P_256_M16, FK_HALO_P_256}};
+    const LayerDesc &l = q.l; ConvF16Args &a = s.a;
+    if (!q.glds || l.size != 3 || l.n % kBN || !q.persist_ok || q.fuse_pool) return false;
+    const int lt_rows = halo_lt_rows(l.w);
+    const size_t a_bytes = (size_t)2 * lt_rows * 128;
+    const bool off32 = ((size_t)kLead + (size_t)q.B * a.PL) * std::max(a.Cp_in, a.Cp_out) * 2 < (1ull << 32);
+    const bool wide = l.n % 256 == 0 && a_bytes + (size_t)2 * 256 * 128 <= kLdsCap;
+    const size_t bn = wide ? 256 : 128, lds = a_bytes + 2 * bn * 128;
+    if (!off32 || lds > kLdsCap || lt_rows - 8 > 8 * 8 * 8) return false;
+    a.n_tiles = l.n / (int)bn; s.T = ((a.npix + 255) / 256) * a.n_tiles;
+    // (Launched with one tile per workgroup - the same kernel, only the LDS-free epilogue and the operand order
+    //  differ from k_conv_f16_halo - it measured 2.8 % slower over the pass at batch 256.)
+    s.grid = persistent_grid(s.T);
+    s.lds = (unsigned)lds; s.lt_rows = lt_rows; s.store = FS_FULL;
+    use(s, kid[wide][q.split ? 0 : (q.o.f16_m16 ? 1 : 2)]);
+    return true;
+}
+// 3x3 layers: halo-tile kernel (input tile staged once per 64-channel chunk, nine taps read it
+// shifted) wherever its LDS arena fits: 2 x lt_rows x 128 B (A) + NB x BN x 128 B (B) + fo table
+static bool take_halo(const F16Conv &q, F16Step &s)
+{
+    const LayerDesc &l = q.l, &nx = kNet[q.i + 1]; ConvF16Args &a = s.a;
+    if (!q.glds || l.size != 3 || l.n % kBN || q.o.f16_no_halo || q.fuse_pool) return false;
+    const int lt_rows = halo_lt_rows(l.w);
+    const size_t a_bytes = (size_t)2 * lt_rows * 128, fo_bytes = 256 * sizeof(int);
+    const size_t lds256 = a_bytes + (size_t)2 * 256 * 128 + fo_bytes, lds128 = a_bytes + (size_t)3 * 128 * 128 + fo_bytes;
+    const bool wide = l.n % 256 == 0 && lds256 <= kLdsCap && a_bytes + (size_t)2 * 256 * 128 >= (size_t)256 * 264 * 2 && !q.o.f16_no_wide;
+    // (the two-buffer 256x128 form that would fit the 104x104 layers runs one workgroup per CU and measured
+    //  6 % slower there than the 128x128 kernel with two: only the shapes below are used)
+    if (lt_rows - 8 > 8 * 8 * 8 || a_bytes < (size_t)256 * kCtRow * 2 || !(wide || lds128 <= kLdsCap) || !q.in32) return false;
+    s.lt_rows = lt_rows; s.store = FS_FULL;   // (the kernels' dynamic-LDS limit was raised for this device in load_weights_fp32)
+    a.n_tiles = wide ? l.n / 256 : l.n / kBN;
+    s.grid = dim3(((a.npix + 255) / 256) * a.n_tiles); s.lds = (unsigned)(wide ? lds256 : lds128);   // (without `wide`: the three-buffer 128 form fits)
+    // a 256-channel 3x3 whose only consumer is a 1x1 down to 128 channels (layer 8 -> 9): the 1x1 runs in the epilogue
+    const bool fuse1 = wide && !q.split && !q.o.f16_no_fuse1x1 && !q.o.f16_m16 && !q.o.f16_w8 && l.n == 256 && a.n_tiles == 1 && nx.type == L_CONV &&
+                       nx.size == 1 && nx.c == 256 && nx.n == 128 && nx.leaky == l.leaky && nx.h == l.h && nx.w == l.w && q.i != 16 && q.i != 24;
+    if (fuse1) { fuse_1x1_next(q, s); use(s, FK_HALO_256_1X1); }
+    else if (!wide) use(s, q.split ? FK_HALO_128_SP : FK_HALO_128);
+    else if (q.split) use(s, FK_HALO_256_SP);
+    else if (q.o.f16_m16) use(s, FK_HALO_256_M16);
+    else if (!q.o.f16_w8) use(s, FK_HALO_256);   // 16 wavefronts of 64x64 (4 per SIMD, +4 %) instead of 8 of 128x64
+    else use(s, FK_HALO_256_W8);
+    return true;
+}
+static int select_f16_table(const Y2Options &o, bool split, int B, F16Table &T)
+{
+    T = F16Table();
     {   // layers 0+1 fused: conv 3->32 + leaky + 2x2 pool straight from the float frames
-        const HT &g = c->h_out[1];
+        const HalfGeom g = f16_geom(1, split, B);
         F16Step s;
-        s.layer = 0; s.B = B;   // (booked to layer 0; the pool, layer 1, has no launch of its own)
-        s.w0 = c->w0f; s.bias = c->w0f + 27 * 32; s.out = g.d; s.oWp = g.Wp; s.oPL = g.PL;
-        s.block = dim3(256);
-        if (split && !sw.no_mfma0) {   // the MFMA form on (hi, lo) pairs: three MFMAs per product, (hi, lo) out: 128-halve items
-            s.kernel = "k_conv0_pool_mfma<split>"; s.launch = L_conv0_mfma<true>;
+        s.layer = 0; s.B = B; s.t_out = 1; s.oWp = g.Wp; s.oPL = g.PL;   // (booked to layer 0; the pool, layer 1, has no launch of its own)
+        if (!o.f16_no_mfma0) {   // 416 = 26 x 16 = 13 x 32: the tile grid is exact.  split: the MFMA form on (hi, lo) pairs: three MFMAs per product, (hi, lo) out: 128-halve items
+            use(s, split ? FK_C0_MFMA_SP : FK_C0_MFMA);
             s.T = B * (416 / 16) * (416 / 32);
-            s.grid = dim3((unsigned)std::min(s.T, 256 * 3));   // 161 registers: three workgroups per CU are resident - a fourth would run behind them
-        } else if (split) {   // fp32 VALU form, nothing rounded before the pool (option f16_no_mfma0)
-            s.kernel = "k_conv0_pool_f16<split>"; s.launch = L_conv0_valu<true>;
-            s.grid = dim3(blocks_for((long)B * g.H * g.W, 256), 2);
-        } else if (!sw.no_mfma0) {   // 416 = 26 x 16 = 13 x 32: the tile grid is exact
-            s.kernel = "k_conv0_pool_mfma"; s.launch = L_conv0_mfma<false>;
-            s.T = B * (416 / 16) * (416 / 32);
-            s.grid = dim3((unsigned)std::min(s.T, 256 * Y2_CONV0_WGS));   // persistent workgroups, Y2_CONV0_WGS per CU
-        } else {
-            s.kernel = "k_conv0_pool_f16"; s.launch = L_conv0_valu<false>;
+            // persistent workgroups, Y2_CONV0_WGS per CU; split: 161 registers: three workgroups per CU are resident - a fourth would run behind them
+            s.grid = dim3((unsigned)std::min(s.T, 256 * (split ? 3 : Y2_CONV0_WGS)));
+        } else {   // (option f16_no_mfma0) split: fp32 VALU form, nothing rounded before the pool
+            use(s, split ? FK_C0_VALU_SP : FK_C0_VALU);
             s.grid = dim3(blocks_for((long)B * g.H * g.W, 256), 2);
         }
-        if (g.B != B || g.H != 208 || g.W != 208 || g.Cp != (split ? 128 : 32)) return fail(YOLO2_ERROR, "fp16 plan: layer-1 tensor has the wrong geometry");
-        P.steps.push_back(s);
-        if (!sw.no_mfma0) {   // the same tiles, grid and output from image bytes (the images entries)
-            P.u8 = s;
-            P.u8.kernel = split ? "k_conv0_pool_mfma_u8<split>" : "k_conv0_pool_mfma_u8";
-            P.launch_u8 = split ? L_conv0_mfma_u8<true> : L_conv0_mfma_u8<false>;
-            P.yuyv_kernel = split ? "k_conv0_pool_mfma_yuyv<split>" : "k_conv0_pool_mfma_yuyv";
-            P.launch_yuyv = split ? L_conv0_mfma_yuyv<true> : L_conv0_mfma_yuyv<false>;
+        T.steps.push_back(s);
+        if (!o.f16_no_mfma0) {   // the same tiles, grid and output from image bytes (the images entries)
+            const F16Kernel &u8 = kF16Kernels[split ? FK_C0_U8_SP : FK_C0_U8], &yuyv = kF16Kernels[split ? FK_C0_YUYV_SP : FK_C0_YUYV];
+            T.u8 = s; T.u8.kernel = u8.name; T.launch_u8 = u8.launch_u8;
+            T.yuyv_kernel = yuyv.name; T.launch_yuyv = yuyv.launch_u8;
         }
     }
-    int ord = 1, skip_pool = -1, fused_conv = -1;
-    const HT *cur = &c->h_out[1];
+    int ord = 1, skip_pool = -1, fused_conv = -1, cur = 1;   // (cur: the tensor the next layer reads)
     for (int i = 2; i < 32; ++i) {
         const LayerDesc &l = kNet[i];
         switch (l.type) {
         case L_CONV: {
-            if (i == fused_conv) {   // this 1x1 layer ran inside the launch of the 3x3 before it (k_conv_f16_rw MODE 2): its tensor exists already
-                ord++;
-                cur = &c->h_out[i];
-                break;
-            }
-            const HT *tin = i == 26 ? &c->h_out[16] : (i == 29 ? &c->h_cat : cur);
-            const HT &tout = c->h_out[i];
+            if (i == fused_conv) { ord++; cur = i; break; }   // this 1x1 layer ran inside the launch of the 3x3 before it: its tensor exists already
             F16Step s;
-            s.layer = i; s.B = B;
+            s.layer = i; s.B = B; s.w_ord = ord++;
+            s.t_in = i == 26 ? 16 : (i == 29 ? 27 : cur); s.t_out = i == 30 ? -1 : i;
             ConvF16Args &a = s.a;
-            a.B = B; a.H = l.h; a.W = l.w; a.Wp = l.w + 1; a.PL = (l.h + 1) * (l.w + 1);
-            a.Cp_in = tin->Cp;
-            a.Cp_out = i == 30 ? 0 : tout.Cp;
-            a.N = l.n;
-            a.out_ch_off = i == 24 ? 256 : 0;
-            a.n_store = i == 30 ? l.n : round_up(l.n, 32);
-            a.npix = B * l.h * l.w;
-            a.leaky = l.leaky;
-            a.KS = l.size;
-            a.pool = 0; a.oWp = a.oPL = a.npool = 0;
-            a.n_tiles = 1;
+            a.B = B; a.H = l.h; a.W = l.w; a.Wp = l.w + 1; a.PL = (l.h + 1) * (l.w + 1); a.npix = B * l.h * l.w;
+            a.Cp_in = f16_geom(s.t_in, split, B).Cp; a.Cp_out = i == 30 ? 0 : f16_geom(i, split, B).Cp;
+            a.N = l.n; a.leaky = l.leaky; a.KS = l.size; a.n_tiles = 1; a.stamp = o.stamp_layer == i;
+            a.out_ch_off = i == 24 ? 256 : 0; a.n_store = i == 30 ? l.n : round_up(l.n, 32);
             a.split_n = split && i != 30 ? part_stride(i == 24 ? 1280 : l.n) : 0;
             set_fast_div(a);
-            a.stamp = sw.stamp_layer == i;
-            s.w = (const _Float16 *)(c->wh + c->wh_off[ord]);
-            s.bias = (const float *)(c->biasf + c->biasf_off[ord]);
-            s.in = (const _Float16 *)tin->d;
-            s.out = i == 30 ? (_Float16 *)nullptr : tout.d;
             s.store = i == 30 ? FS_REGION : FS_FULL_OR_POOL;
-            const HT *dst = &tout;
-            ord++;
-            const bool bk64 = a.Cp_in % 64 == 0;   // K-step of 64 channels wherever the item size allows it
-            const bool glds = bk64 && !sw.no_glds;   // LDS-DMA staging wherever the K-step is 64
             // Conv layers whose only consumer is the 2x2 pool after them (2 and 6; 10 runs the halo kernel, 16 also
             // feeds the route) store the pooled tensor directly: MFMA rows ordered by pool window, max in the epilogue.
             // The persistent halo kernel takes the 104x104 layers EXCEPT layer 6: it stores the full-resolution tensor only
             // (FS_FULL), and the pool kernel that then has to follow (0.08 ms at batch 128) costs more than the conv gains.
-            const bool pool_next = kNet[i + 1].type == L_MAX && !sw.no_poolfuse;
-            const bool persist_ok = !sw.no_glds && !sw.no_halo && !sw.no_persist && ((l.w > 52 && !(i == 6 && pool_next)) || sw.persist_all);
-            const bool fuse_pool = (i == 2 || (i == 6 && !persist_ok)) && pool_next;
-            if (fuse_pool) {
-                const HT &tp = c->h_out[i + 1];
-                a.pool = 1; a.oWp = tp.Wp; a.oPL = tp.PL; a.npool = B * tp.H * tp.W;
-                a.Cp_out = tp.Cp;
-                s.out = tp.d;
-                dst = &tp;
-                skip_pool = i + 1;
-            }
-            const bool in32 = ((size_t)kLead + (size_t)B * a.PL) * a.Cp_in * 2 < (1ull << 32);   // 32-bit byte offsets into the input
-            int rc = YOLO2_SUCCESS;
-            bool done = false;
-            // The 64 -> 128 channel 3x3 layers at 104 x 104 (4 and 6): weights resident in registers, two image rows per tile, one barrier
-            // per tile (k_conv_f16_rw).  Layer 6 fuses its pool (MODE 1); layer 4 fuses the 1x1 layer 5, its only consumer (MODE 2:
-            // the 128-channel tensor between them is never written); MODE 0 stores the plain tensor.
-            if (!done && !split && !sw.no_rw && l.size == 3 && a.Cp_in == 64 && l.n == 128 && l.w == 8 * 13 && (l.h & 1) == 0 && !sw.no_glds &&
-                ((size_t)kLead + (size_t)B * a.PL + kTail) * 128 < (1ull << 31)) {   // (signed 32-bit byte offsets into the input)
-                const bool pool_here = kNet[i + 1].type == L_MAX && !sw.no_poolfuse;
-                const LayerDesc &nx = kNet[i + 1];
-                const bool fuse1 = !pool_here && !sw.no_fuse1x1 && nx.type == L_CONV && nx.size == 1 && nx.c == 128 && nx.n == 64 && nx.leaky == l.leaky &&
-                                   nx.h == l.h && nx.w == l.w && i + 1 != 16 && i + 1 != 24;   // (and nothing but layer i + 1 reads layer i: true for every conv of this network except 16)
-                s.T = B * (l.h / 2);
-                const int rounds = (s.T + 255) / 256;
-                s.grid = dim3(std::min(256, std::max(8, round_up((s.T + rounds - 1) / rounds, 8)))); s.block = dim3(256);
-                const int n_stage = (2 * l.w + 2 * (l.w + 1) + 7) / 8;
-                const bool rwb_ok = !sw.no_rwb && l.leaky && a.n_store == 128;   // k_conv_f16_rwb: leaky layers, every channel stored
-                if (pool_here) {
-                    const HT &tp = c->h_out[i + 1];
-                    a.pool = 1; a.oWp = tp.Wp; a.oPL = tp.PL; a.npool = B * tp.H * tp.W;
-                    a.Cp_out = tp.Cp;
-                    s.out = tp.d; dst = &tp; skip_pool = i + 1;
-                    s.lt_rows = n_stage * 8;
-                    s.lds = (unsigned)(2 * s.lt_rows * 128 + 13 * 1024 + 2 * (26 * 16 / 4 / 2) * 136 * 2);   // two input tiles + zero region + two pooled tiles
-                    s.kernel = "k_conv_f16_rw<pool>"; s.launch = L_rw<1>; s.store = FS_POOL_ONLY;
-                    if (rwb_ok) {       // the epilogue inside the MFMA stream (k_conv_f16_rwb)
-                        s.lt_rows = 432;
-                        s.lds = (unsigned)(2 * 432 * 128 + 2 * 52 * 136 * 2);
-                        s.kernel = "k_conv_f16_rwb<pool>"; s.launch = L_rwb<1>;
-                    }
-                } else if (fuse1) {
-                    const HT &t2 = c->h_out[i + 1];
-                    a.Cp_out = t2.Cp; a.N = nx.n; a.n_store = round_up(nx.n, 32); a.out_ch_off = 0;
-                    s.out = t2.d; dst = &t2; fused_conv = i + 1;
-                    s.w2 = (const _Float16 *)(c->wh + c->wh_off[ord]);          // (ord was advanced above: the NEXT conv's weights)
-                    s.bias2 = (const float *)(c->biasf + c->biasf_off[ord]);
-                    s.lt_rows = std::max(n_stage, ((13 * 16 * 136 * 2 + 127) / 128 + 7) / 8) * 8;   // the 208 x 136-half intermediate tile must fit an input buffer
-                    s.lds = (unsigned)(2 * s.lt_rows * 128 + 13 * 1024);
-                    s.kernel = "k_conv_f16_rw<+1x1>"; s.launch = L_rw<2>; s.store = FS_FULL;
-                    if (rwb_ok && nx.leaky && t2.Cp == 64) {
-                        s.lt_rows = 432;
-                        s.lds = (unsigned)(2 * 432 * 128 + 208 * 256);        // = 160 KB: the whole LDS of a CU
-                        s.kernel = "k_conv_f16_rwb<+1x1>"; s.launch = L_rwb<2>;
-                    }
-                } else {
-                    s.lt_rows = n_stage * 8;
-                    s.lds = (unsigned)(2 * s.lt_rows * 128 + 13 * 1024);
-                    s.kernel = "k_conv_f16_rw"; s.launch = L_rw<0>; s.store = FS_FULL;
-                }
-                done = true;
-            }
-            // 1x1 layers: persistent workgroups over a ring of staged K-steps (k_gemm1_f16_p)
+            const bool pool_next = kNet[i + 1].type == L_MAX && !o.f16_no_poolfuse;
+            const bool persist_ok = !o.f16_no_glds && !o.f16_no_halo && !o.f16_no_persist && ((l.w > 52 && !(i == 6 && pool_next)) || o.f16_persist_all);
+            const bool bk64 = a.Cp_in % 64 == 0;
+            const F16Conv q = {o, split, B, i, l, bk64, bk64 && !o.f16_no_glds, pool_next, persist_ok, (i == 2 || (i == 6 && !persist_ok)) && pool_next,
+                               ((size_t)kLead + (size_t)B * a.PL) * a.Cp_in * 2 < (1ull << 32)};
+            if (q.fuse_pool) fuse_pool_into_next(q, s);
             if (split && !bk64) return fail(YOLO2_ERROR, "fp16 plan (split): layer %d has %d-channel items, not a multiple of the 64-channel K-step", i, a.Cp_in);
-            // 1x1 layers whose channel count is a multiple of 256 (13, 15: 256; 19, 21: 512): 128 pixels x 256 channels per tile, so that the
-            // input - the bytes this HBM-bound layer moves - is read once per 256 output channels instead of once per 128
-            // (experiment f16_ring_sq) the same layers on 256 x 256 tiles, sixteen wavefronts, two 64-KB stages: twice the FLOPs per staged byte of the
-            // 128 x 128 tiles (an LDS-DMA'd byte feeds 128 FLOPs instead of 64), at the price of 338 / 170 tiles for 256 CUs
-            if (!done && !split && sw.ring_sq && l.size == 1 && bk64 && i != 30 && l.n % 256 == 0 && in32 && !sw.no_ring) {
-                a.n_tiles = l.n / 256;
-                s.T = ((a.npix + 255) / 256) * a.n_tiles;
-                const int rounds = (s.T + 255) / 256;
-                s.grid = dim3(std::min(256, std::max(8, round_up((s.T + rounds - 1) / rounds, 8))));
-                s.kernel = "k_gemm1_f16_p<256,256,2>"; s.launch = L_ring_sq; s.block = dim3(1024); s.lds = 2 * (256 + 256) * 128;
-                s.store = FS_FULL;
-                done = true;
-            }
-            if (!done && !split && sw.ring256 && l.size == 1 && bk64 && i != 30 && l.n % 256 == 0 && in32 && !sw.no_ring) {
-                a.n_tiles = l.n / 256;
-                s.T = ((a.npix + 127) / 128) * a.n_tiles;
-                const int rounds = (s.T + 255) / 256;
-                s.grid = dim3(std::min(256, std::max(8, round_up((s.T + rounds - 1) / rounds, 8))));
-                s.kernel = "k_gemm1_f16_p<128,256,3>"; s.launch = L_ring256; s.block = dim3(512); s.lds = 3 * (128 + 256) * 128;
-                s.store = FS_FULL;
-                done = true;
-            }
-            if (!done && l.size == 1 && bk64 && (i == 30 || (sw.ring_all && !split)) && in32 && !sw.no_ring) {
-                const int bn = l.n <= 64 ? 64 : 128;
-                a.n_tiles = round_up(l.n, bn) / bn;
-                s.T = ((a.npix + 255) / 256) * a.n_tiles;
-                const int rounds = (s.T + 255) / 256;                                    // tiles per workgroup
-                s.grid = dim3(std::min(256, std::max(8, round_up((s.T + rounds - 1) / rounds, 8))));
-                if (bn == 64) { s.kernel = "k_gemm1_f16_p<256,64,3>"; s.launch = L_ring<64>; s.block = dim3(256); s.lds = 3 * (256 + 64) * 128; }
-                else { s.kernel = "k_gemm1_f16_p<256,128,3>"; s.launch = L_ring<128>; s.block = dim3(512); s.lds = 3 * (256 + 128) * 128; }
-                if (s.store != FS_REGION) s.store = FS_FULL;
-                done = true;
-            }
-            // the 32-channel layer + its pool with the weights in registers and a ring of image rows in LDS (k_conv_f16_rwc): runs of
-            // 52, 26 or 13 consecutive row pairs per workgroup - the longest that still gives every CU a run
-            if (!done && !split && !sw.no_rwc && fuse_pool && a.Cp_in == 32 && l.size == 3 && l.n == 64 && l.w == 208 && l.h == 208 && l.leaky &&
-                a.Cp_out == 64 && a.n_store == 64 && a.out_ch_off == 0 && ((size_t)kLead + (size_t)B * a.PL + kTail) * 64 < (1ull << 31)) {
-                int run_len = 52;
-                while (run_len > 13 && B * (l.h / 2 / run_len) < 256) run_len /= 2;
-                s.lt_rows = run_len;                       // (the launcher hands it to the kernel)
-                s.T = B * (l.h / 2 / run_len);             // runs
-                s.kernel = "k_conv_f16_rwc"; s.launch = L_rwc; s.store = FS_POOL_ONLY;
-                s.grid = dim3((unsigned)std::min(s.T, 256)); s.block = dim3(256);
-                s.lds = (unsigned)(8 * 212 * 64 + 3 * 104 * 72 * 2);
-                done = true;
-            }
-            // the 32-channel layer + its pool: 16 x 16 tiles, patch and all nine taps' weights resident in LDS (k_conv_f16_c32_pool)
-            if (!done && fuse_pool && a.Cp_in == 32 && l.size == 3 && l.n == 64 && l.h % 16 == 0 && l.w % 16 == 0 && a.Cp_out >= 64 &&
-                ((size_t)kLead + (size_t)B * a.PL) * 64 < (1ull << 32) && !sw.no_c32) {
-                s.T = B * (l.h / 16) * (l.w / 16);
-                s.kernel = "k_conv_f16_c32_pool"; s.launch = L_c32_pool; s.store = FS_POOL_ONLY;
-                s.grid = dim3((unsigned)std::min(s.T, 512)); s.block = dim3(256); s.lds = (9 * 64 + 336) * 64;   // two workgroups per CU, weights staged once each
-                done = true;
-            }
-            const int m_tiles = fuse_pool ? (a.npool + 31) / 32 : (a.npix + 127) / 128;   // 128-row tiles (32 pool windows)
-            if (!done && l.n <= 64) {
-                a.n_tiles = round_up(l.n, 64) / 64;
-                s.grid = dim3(m_tiles * a.n_tiles); s.block = dim3(256);
-                if (split) { s.kernel = "k_conv_f16_glds<64,split>"; s.launch = L_glds<64, true>; }
-                else if (glds) { s.kernel = "k_conv_f16_glds<64>"; s.launch = L_glds<64>; }
-                else if (bk64) { s.kernel = "k_conv_f16<128,64,64>"; s.launch = L_reg<64, 64>; }
-                else { s.kernel = "k_conv_f16<128,64,32>"; s.launch = L_reg<64, 32>; }
-                done = true;
-            }
-            if (!done) {
-                a.n_tiles = round_up(l.n, kBN) / kBN;
-                // dense halo tile: 256 pixels + W+1 on either side, rounded to 8-row groups, + 8 zero rows
-                const int lt_rows = round_up(256 + 2 * (l.w + 1), 8) + 8;
-                const size_t a_bytes = (size_t)2 * lt_rows * 128, cap = 160 * 1024;
-                // persistent halo-tile kernel: the workgroup walks its tiles, the next tile's staging overlaps this one's tail
-                if (glds && l.size == 3 && l.n % kBN == 0 && persist_ok && !fuse_pool) {
-                    const bool off32 = ((size_t)kLead + (size_t)B * a.PL) * std::max(a.Cp_in, a.Cp_out) * 2 < (1ull << 32);
-                    const bool wide = l.n % 256 == 0 && a_bytes + (size_t)2 * 256 * 128 <= cap;
-                    const int bn = wide ? 256 : 128;
-                    const size_t lds = a_bytes + (size_t)2 * bn * 128;
-                    if (off32 && lds <= cap && lt_rows - 8 <= 8 * 8 * 8) {
-                        a.n_tiles = l.n / bn;
-                        s.T = ((a.npix + 255) / 256) * a.n_tiles;
-                        const int rounds = (s.T + 255) / 256;
-                        // (Launched with one tile per workgroup - the same kernel, only the LDS-free epilogue and the operand order
-                        //  differ from k_conv_f16_halo - it measured 2.8 % slower over the pass at batch 256.)
-                        s.grid = dim3(std::min(256, std::max(8, round_up((s.T + rounds - 1) / rounds, 8))));
-                        s.lds = (unsigned)lds; s.lt_rows = lt_rows; s.store = FS_FULL;
-                        if (split && wide) { s.kernel = "k_conv_f16_halo_p<256,16,32,split>"; s.launch = L_halo_p<256, 16, 32, true>; s.block = dim3(1024); }
-                        else if (split) { s.kernel = "k_conv_f16_halo_p<128,8,32,split>"; s.launch = L_halo_p<128, 8, 32, true>; s.block = dim3(512); }
-                        else if (wide && sw.m16) { s.kernel = "k_conv_f16_halo_p<256,16,16>"; s.launch = L_halo_p<256, 16, 16>; s.block = dim3(1024); }
-                        else if (wide) { s.kernel = "k_conv_f16_halo_p<256,16,32>"; s.launch = L_halo_p<256, 16, 32>; s.block = dim3(1024); }
-                        else if (sw.m16) { s.kernel = "k_conv_f16_halo_p<128,8,16>"; s.launch = L_halo_p<128, 8, 16>; s.block = dim3(512); }
-                        else { s.kernel = "k_conv_f16_halo_p<128,8,32>"; s.launch = L_halo_p<128, 8, 32>; s.block = dim3(512); }
-                        done = true;
-                    }
-                }
-                // 3x3 layers: halo-tile kernel (input tile staged once per 64-channel chunk, nine taps read it
-                // shifted) wherever its LDS arena fits: 2 x lt_rows x 128 B (A) + NB x BN x 128 B (B) + fo table
-                if (!done && glds && l.size == 3 && l.n % kBN == 0 && !sw.no_halo && !fuse_pool) {
-                    const size_t fo_bytes = 256 * sizeof(int);
-                    const size_t lds256 = a_bytes + (size_t)2 * 256 * 128 + fo_bytes, lds128 = a_bytes + (size_t)3 * 128 * 128 + fo_bytes;
-                    const bool wide = l.n % 256 == 0 && lds256 <= cap && a_bytes + (size_t)2 * 256 * 128 >= (size_t)256 * 264 * 2 && !sw.no_wide;
-                    const bool three = lds128 <= cap;
-                    // (the two-buffer 256x128 form that would fit the 104x104 layers runs one workgroup per CU and measured
-                    //  6 % slower there than the 128x128 kernel with two: only the shapes below are used)
-                    const bool fits = lt_rows - 8 <= 8 * 8 * 8 && a_bytes >= (size_t)256 * kCtRow * 2 && (wide || three) && in32;
-                    if (fits) {   // (the kernels' dynamic-LDS limit was raised for this device in load_weights_fp32)
-                        s.lt_rows = lt_rows; s.store = FS_FULL;
-                        if (wide) {
-                            a.n_tiles = l.n / 256;
-                            s.grid = dim3(((a.npix + 255) / 256) * a.n_tiles); s.lds = (unsigned)lds256;
-                            // a 256-channel 3x3 whose only consumer is a 1x1 down to 128 channels (layer 8 -> 9): the 1x1 runs in the epilogue
-                            const LayerDesc &nx = kNet[i + 1];
-                            const bool fuse1 = !split && !sw.no_fuse1x1 && !sw.m16 && !sw.w8 && l.n == 256 && a.n_tiles == 1 && nx.type == L_CONV && nx.size == 1 &&
-                                               nx.c == 256 && nx.n == 128 && nx.leaky == l.leaky && nx.h == l.h && nx.w == l.w && i != 16 && i != 24;
-                            if (fuse1) {
-                                const HT &t2 = c->h_out[i + 1];
-                                a.Cp_out = t2.Cp; a.N = nx.n; a.n_store = round_up(nx.n, 32); a.out_ch_off = 0;
-                                s.out = t2.d; dst = &t2; fused_conv = i + 1;
-                                s.w2 = (const _Float16 *)(c->wh + c->wh_off[ord]);          // (ord was advanced above: the NEXT conv's weights)
-                                s.bias2 = (const float *)(c->biasf + c->biasf_off[ord]);
-                                s.kernel = "k_conv_f16_halo<256,2,16>+1x1"; s.launch = L_halo<256, 2, 16, 32, false, true>; s.block = dim3(1024);
-                            } else
-                            if (split) { s.kernel = "k_conv_f16_halo<256,2,16,32,split>"; s.launch = L_halo<256, 2, 16, 32, true>; s.block = dim3(1024); }
-                            else if (sw.m16) { s.kernel = "k_conv_f16_halo<256,2,16,16>"; s.launch = L_halo<256, 2, 16, 16>; s.block = dim3(1024); }
-                            else if (!sw.w8) { s.kernel = "k_conv_f16_halo<256,2,16>"; s.launch = L_halo<256, 2, 16, 32>; s.block = dim3(1024); }   // 16 wavefronts of 64x64 (4 per SIMD, +4 %) instead of 8 of 128x64
-                            else { s.kernel = "k_conv_f16_halo<256,2>"; s.launch = L_halo<256, 2, 8, 32>; s.block = dim3(512); }
-                        } else {   // `fits` without `wide` implies `three`
-                            s.grid = dim3(((a.npix + 255) / 256) * a.n_tiles); s.lds = (unsigned)lds128;
-                            if (split) { s.kernel = "k_conv_f16_halo<128,3,8,32,split>"; s.launch = L_halo<128, 3, 8, 32, true>; }
-                            else { s.kernel = "k_conv_f16_halo<128,3>"; s.launch = L_halo<128, 3, 8, 32>; }
-                            s.block = dim3(512);
-                        }
-                        done = true;
-                    }
-                }
-                // (a 256x128 tile with 8 wavefronts and per-tap A staging was measured 8 % SLOWER than 128x128
-                //  with two workgroups per CU: without the halo reuse the bigger tile only adds barrier cost)
-                if (!done) {
-                    s.grid = dim3(m_tiles * a.n_tiles); s.block = dim3(256);
-                    if (split) { s.kernel = "k_conv_f16_glds<128,split>"; s.launch = L_glds<128, true>; }
-                    else if (glds) { s.kernel = "k_conv_f16_glds<128>"; s.launch = L_glds<128>; }
-                    else if (bk64) { s.kernel = "k_conv_f16<128,128,64>"; s.launch = L_reg<128, 64>; }
-                    else { s.kernel = "k_conv_f16<128,128,32>"; s.launch = L_reg<128, 32>; }
-                    done = true;
-                }
-            }
-            if ((rc = checked_push(s, *dst))) return rc;
-            if (i != 30) cur = dst;
+            (void)(take_rw(q, s) || take_ring(q, s) || take_rwc(q, s) || take_c32_pool(q, s) || (l.n <= 64 && take_gemm(q, s, 64)) || take_halo_p(q, s) ||
+                   take_halo(q, s) || take_gemm(q, s, kBN));
+            if (s.a.pool) skip_pool = i + 1;        // the pool after this layer ...
+            if (s.w2_ord >= 0) fused_conv = i + 1;  // ... or the 1x1 after it ran inside this launch
+            const HalfGeom dst = f16_geom(s.t_out, split, B);   // every conv step passes the store check against the tensor it names
+            const int rc = f16_store_check(s.kernel, s.store, a.pool, B, a.H, a.W, a.Cp_out, a.out_ch_off, a.n_store, a.oWp, a.oPL, a.npix, a.npool, dst.B,
+                                           dst.H, dst.W, dst.Cp, s.store == FS_REGION ? 0 : a.split_n);
+            if (rc) return rc;
+            T.steps.push_back(s);
+            if (i != 30) cur = s.t_out;
             break;
         }
         case L_MAX: {
-            if (i == skip_pool) { cur = &c->h_out[i]; break; }   // already produced by the conv before it
-            const HT &gi = *cur, &go = c->h_out[i];
-            if (gi.B != B || go.B != B || gi.H != 2 * go.H || gi.W != 2 * go.W || gi.Cp != go.Cp)
-                return fail(YOLO2_ERROR, "fp16 plan: pool layer %d: %d x %d x %d -> %d x %d x %d does not halve", i, gi.H, gi.W, gi.Cp, go.H, go.W, go.Cp);
+            if (i == skip_pool) { cur = i; break; }   // already produced by the conv before it
+            const HalfGeom gi = f16_geom(cur, split, B), go = f16_geom(i, split, B);
             F16Step s;
-            s.layer = i; s.B = B; s.kernel = "k_maxpool2_f16"; s.launch = L_maxpool;
-            s.in = gi.d; s.out = go.d; s.oCp = go.Cp; s.OH = go.H; s.OW = go.W; s.iWp = gi.Wp; s.iPL = gi.PL; s.oWp = go.Wp; s.oPL = go.PL;
-            s.grid = dim3(blocks_for((long)B * go.H * go.W * (go.Cp / 8), 256)); s.block = dim3(256);
-            if (split) {
-                s.kernel = "k_maxpool2_split"; s.launch = L_maxpool_split; s.oPS = part_stride(go.C);
-                s.grid = dim3(blocks_for((long)B * go.H * go.W * (s.oPS / 8), 256));
-            }
-            P.steps.push_back(s);
-            cur = &c->h_out[i];
+            s.layer = i; s.B = B; s.t_in = cur; s.t_out = cur = i;
+            s.oCp = go.Cp; s.OH = go.H; s.OW = go.W; s.iWp = gi.Wp; s.iPL = gi.PL; s.oWp = go.Wp; s.oPL = go.PL;
+            if (split) s.oPS = part_stride(go.C);
+            use(s, split ? FK_MAXPOOL_SP : FK_MAXPOOL);
+            s.grid = dim3(blocks_for((long)B * go.H * go.W * ((split ? s.oPS : go.Cp) / 8), 256));
+            T.steps.push_back(s);
             break;
         }
         case L_REORG: {
-            const HT &gi = *cur, &go = c->h_cat;
-            if (gi.B != B || go.B != B || gi.H != 26 || gi.W != 26 || gi.Cp < 64 || go.H != 13 || go.W != 13 || go.Cp < 256)
-                return fail(YOLO2_ERROR, "fp16 plan: reorg layer %d has the wrong geometry", i);
+            const HalfGeom gi = f16_geom(cur, split, B), go = f16_geom(i, split, B);
             F16Step s;
-            s.layer = i; s.B = B; s.kernel = "k_reorg_f16"; s.launch = L_reorg;
-            s.in = gi.d; s.out = go.d; s.iCp = gi.Cp; s.iWp = gi.Wp; s.iPL = gi.PL; s.oCp = go.Cp; s.oWp = go.Wp; s.oPL = go.PL;
-            if (split) { s.kernel = "k_reorg_split"; s.launch = L_reorg_split; s.iPS = part_stride(gi.C); s.oPS = part_stride(go.C); }
-            s.grid = dim3(blocks_for((long)B * (split ? 3 * 128 : 128) * 169, 256)); s.block = dim3(256);   // one thread per channel pair (and part)
-            P.steps.push_back(s);
-            cur = &c->h_cat;
+            s.layer = i; s.B = B; s.t_in = cur; s.t_out = cur = i;
+            s.iCp = gi.Cp; s.iWp = gi.Wp; s.iPL = gi.PL; s.oCp = go.Cp; s.oWp = go.Wp; s.oPL = go.PL;
+            if (split) { s.iPS = part_stride(gi.C); s.oPS = part_stride(go.C); }
+            use(s, split ? FK_REORG_SP : FK_REORG);
+            s.grid = dim3(blocks_for((long)B * (split ? 3 * 128 : 128) * 169, 256));   // one thread per channel pair (and part)
+            T.steps.push_back(s);
             break;
         }
-        default:
-            break;  // route: concat by placement; region: the last conv already wrote the dense fp32 tensor
+        default: break;  // route: concat by placement; region: the last conv already wrote the dense fp32 tensor
         }
     }
-    if (sw.skip) {   // diagnostic only: drop launches from the table (wrong results), to price them inside the overlapped step
-        std::vector<F16Step> kept;
-        for (const F16Step &s : P.steps) {
-            const LayerDesc &l = kNet[s.layer];
-            bool drop = false;
-            if ((sw.skip & 1) && (s.layer == 5 || s.layer == 9)) drop = true;
-            if ((sw.skip & 2) && s.layer == 0) drop = true;
-            if ((sw.skip & 4) && (s.layer == 2 || s.layer == 4 || s.layer == 6)) drop = true;
-            if ((sw.skip & 8) && (l.type == L_MAX || l.type == L_REORG)) drop = true;
-            if ((sw.skip & 16) && l.type == L_CONV && l.size == 1 && s.layer != 5 && s.layer != 9) drop = true;
-            if ((sw.skip & 32) && l.type == L_CONV && l.size == 3 && l.w == 13) drop = true;
-            if (!drop) kept.push_back(s);
-        }
-        P.steps = kept;
+    // diagnostic only (f16_skip): drop launches from the table (wrong results), to price them inside the overlapped step
+    T.steps.erase(std::remove_if(T.steps.begin(), T.steps.end(), [&](const F16Step &s) {
+        const LayerDesc &l = kNet[s.layer]; const int k = o.f16_skip;
+        return ((k & 1) && (s.layer == 5 || s.layer == 9)) || ((k & 2) && s.layer == 0) || ((k & 4) && (s.layer == 2 || s.layer == 4 || s.layer == 6)) ||
+               ((k & 8) && (l.type == L_MAX || l.type == L_REORG)) || ((k & 16) && l.type == L_CONV && l.size == 1 && s.layer != 5 && s.layer != 9) ||
+               ((k & 32) && l.type == L_CONV && l.size == 3 && l.w == 13);
+    }), T.steps.end());
+    T.batch = B;
+    return YOLO2_SUCCESS;
+}
+
+// ---- the table as text: one line per step with every field selection sets (yolo2_hip_f16_plan_describe, the `verbose` plan print)
+static std::string f16_table_text(const F16Table &T, const char *prefix)
+{
+    auto tensor = [](int t, const char *none) { return t < 0 ? std::string(none) : (t == 24 || t == 27 ? std::string("cat") : "t" + std::to_string(t)); };
+    std::string out;
+    char buf[960], args[320];
+    for (const F16Step &s : T.steps) {
+        const ConvF16Args &a = s.a;
+        snprintf(args, sizeof(args), "-");
+        if (s.w_ord >= 0)   // a conv step: the ConvF16Args scalars in declaration order
+            snprintf(args, sizeof(args), "%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%u,%u,%u,%u,%d,%d", a.B, a.H, a.W, a.Wp, a.PL, a.Cp_in, a.Cp_out, a.N,
+                     a.out_ch_off, a.n_store, a.npix, a.leaky, a.KS, a.n_tiles, a.pool, a.oWp, a.oPL, a.npool, a.mHW, a.sHW, a.mW, a.sW, a.stamp, a.split_n);
+        snprintf(buf, sizeof(buf), "%sL%d %s store=%d grid=%u,%u block=%u lds=%u lt_rows=%d T=%d B=%d in=%s out=%s w=%d w2=%d a=%s pr=%d,%d,%d,%d,%d,%d,%d,%d,%d,%d\n",
+                 prefix, s.layer, s.kernel, (int)s.store, s.grid.x, s.grid.y, s.block.x, s.lds, s.lt_rows, s.T, s.B, tensor(s.t_in, s.layer == 0 ? "frames" : "-").c_str(),
+                 tensor(s.t_out, s.store == FS_REGION ? "region" : "-").c_str(), s.w_ord, s.w2_ord, args, s.iCp, s.iWp, s.iPL, s.oCp, s.oWp, s.oPL, s.OH, s.OW, s.iPS, s.oPS);
+        out += buf;
     }
-    P.batch = B;
-    if (sw.verbose)   // (plan construction, not the launch path)
-        for (const F16Step &s : P.steps)
-            fprintf(stderr, "[yolo2_hip] fp16 plan B=%d L%-2d %-30s grid %u block %u lds %u\n", B, s.layer, s.kernel, s.grid.x, s.block.x, s.lds);
+    if (T.launch_u8) out += std::string(prefix) + "u8 " + T.u8.kernel + "\n" + prefix + "yuyv " + T.yuyv_kernel + "\n";
+    return out;
+}
+
+// Test hook (no GPU needed): the table selection makes for (options, split, batch), as the text above.
+extern "C" int yolo2_hip_f16_plan_describe(const char *options, int split, int batch, char *buf, int cap)
+{
+    if (split != 0 && split != 1) return fail(YOLO2_ERROR, "split must be 0 (fp16) or 1 (fp32 tolerance), not %d", split);
+    if (batch <= 0 || batch > 4096) return fail(YOLO2_ERROR, "batch %d out of range", batch);
+    Y2Options o;
+    const std::string opts = options ? options : "";
+    for (size_t p = opts.find_first_not_of(' '); p != std::string::npos;) {
+        const size_t e = std::min(opts.find(' ', p), opts.size()), eq = opts.find('=', p);
+        if (eq >= e || o.set(opts.substr(p, eq - p).c_str(), opts.substr(eq + 1, e - eq - 1).c_str()) != 0)
+            return fail(YOLO2_ERROR, "unknown option or value out of range: %s", opts.substr(p, e - p).c_str());
+        p = opts.find_first_not_of(' ', e);
+    }
+    F16Table T;
+    if (const int rc = select_f16_table(o, split != 0, batch, T)) return rc;
+    const std::string text = f16_table_text(T, "");
+    if (buf && cap > 0) snprintf(buf, (size_t)cap, "%s", text.c_str());
+    return (int)text.size();
+}
+
+// ---- binding: the addresses of one step, from the context's tensors (ensure_f16_batch) and weight offsets
+static int bind_f16_step(const yolo2_hip_ctx *c, F16Step &s)
+{
+    if ((s.t_in >= 0 && !c->h_out[s.t_in].d) || (s.t_out >= 0 && !c->h_out[s.t_out].d)) return fail(YOLO2_ERROR, "fp16 plan: layer %d names a tensor that is not allocated", s.layer);
+    if (s.t_in >= 0) s.in = c->h_out[s.t_in].d;
+    if (s.t_out >= 0) s.out = c->h_out[s.t_out].d;
+    if (s.layer == 0) { s.w0 = c->w0f; s.bias = c->w0f + 27 * 32; }
+    if (s.w_ord >= 0) { s.w = c->wh + c->wh_off[s.w_ord]; s.bias = c->biasf + c->biasf_off[s.w_ord]; }
+    if (s.w2_ord >= 0) { s.w2 = c->wh + c->wh_off[s.w2_ord]; s.bias2 = c->biasf + c->biasf_off[s.w2_ord]; }
+    return YOLO2_SUCCESS;
+}
+
+// Builds the table for batch B: selection, then binding to the context's tensors (they exist: ensure_f16_batch).
+static int build_f16_plan(yolo2_hip_ctx *c, int B)
+{
+    F16Plan &P = *c->f16_plan;
+    int rc = select_f16_table(P.opt, c->split, B, P);
+    for (F16Step &s : P.steps) if (!rc) rc = bind_f16_step(c, s);
+    if (!rc && P.launch_u8) rc = bind_f16_step(c, P.u8);
+    if (rc) { P.batch = 0; P.steps.clear(); return rc; }
+    if (P.opt.verbose) fputs(f16_table_text(P, "[yolo2_hip] fp16 plan ").c_str(), stderr);   // (plan construction, not the launch path)
     return YOLO2_SUCCESS;
 }
 
@@ -720,7 +719,7 @@ extern "C" int yolo2_hip_set_fp16_lanes(yolo2_hip_ctx *c, int lanes)
     if (lanes < 1 || lanes > 8) return fail(YOLO2_ERROR, "fp16 lanes: %d out of range (1..8)", lanes);
     HIP_TRY(hipSetDevice(c->device), YOLO2_INIT_ERROR);
     HIP_TRY(hipDeviceSynchronize(), YOLO2_ERROR);
-    c->f16_plan->sw.lanes = lanes;
+    c->f16_plan->lanes = lanes;
     for (yolo2_hip_ctx *l : c->f16_lanes) yolo2_hip_destroy(l);    // rebuilt at the next run if still wanted
     c->f16_lanes.clear();
     return YOLO2_SUCCESS;
@@ -748,7 +747,7 @@ static int make_f16_lanes(yolo2_hip_ctx *c, int want_lanes)
         l->f16_plan = new (std::nothrow) F16Plan();
         ok = l->f16_plan && ((i == 0 && !y2_lane0_own_stream()) || (y2_lane_stream_create(&l->lane_stream) == YOLO2_SUCCESS &&
                                                                      hipEventCreateWithFlags(&l->ev_join, hipEventDisableTiming) == hipSuccess));
-        if (ok) l->f16_plan->sw = c->f16_plan->sw;   // a lane runs the parent's kernel selection
+        if (ok) l->f16_plan->opt = c->f16_plan->opt;   // a lane runs the parent's kernel selection
     }
     if (!ok) {
         for (yolo2_hip_ctx *l : made) yolo2_hip_destroy(l);
@@ -773,7 +772,7 @@ static int run_f16(yolo2_hip_ctx *c, uint64_t frames_dev, const uint8_t *lb, int
     hipStream_t st = (hipStream_t)stream;
     // Two half-batch lanes like the int16 path: the big-tile kernels run one workgroup per CU and a layer is only
     // 2-3 generations of workgroups, so a second stream's launches fill the last, partly empty generation.
-    const int want_lanes = c->f16_plan->sw.lanes;
+    const int want_lanes = c->f16_plan->lanes;
     if (!c->is_lane && batch >= 64 && want_lanes > 1 && batch % want_lanes == 0) {
         if ((int)c->f16_lanes.size() != want_lanes) {
             const int rc = make_f16_lanes(c, want_lanes);
@@ -958,7 +957,7 @@ int y2_f16_images_ctx(yolo2_hip_ctx *c, int split, yolo2_hip_ctx **run)
     return YOLO2_SUCCESS;
 }
 
-bool y2_f16_images_fused(const yolo2_hip_ctx *run) { return !run->f16_plan->sw.no_mfma0; }
+bool y2_f16_images_fused(const yolo2_hip_ctx *run) { return !run->f16_plan->opt.f16_no_mfma0; }
 
 int y2_f16_run_images(yolo2_hip_ctx *run, const uint8_t *lb, bool yuyv, int batch, float *region_dev, hipStream_t st)
 {

@@ -42,7 +42,7 @@ EXPORTS = [
     "yolo2_hip_multi_run_frames_int16", "yolo2_hip_multi_run_images_u8_host", "yolo2_hip_rccl_unique_id",
     "yolo2_hip_rccl_init_rank", "yolo2_hip_rccl_finalize", "yolo2_hip_load_weights_int16_bcast", "yolo2_hip_load_weights_fp32_bcast",
     "yolo2_hip_rccl_info", "yolo2_hip_multi_rccl_info", "yolo2_hip_ctx_device", "yolo2_hip_alloc_on",
-    "yolo2_hip_fp16_layer_kernel", "yolo2_hip_f16_store_check",
+    "yolo2_hip_fp16_layer_kernel", "yolo2_hip_f16_store_check", "yolo2_hip_f16_plan_describe",
     "yolo2_hip_run_images_u8_dets", "yolo2_hip_multi_run_images_u8_dets", "yolo2_hip_set_fp16_lanes", "yolo2_hip_conv_plan_string", "yolo2_hip_plan_source",
     "yolo2_hip_set_option", "yolo2_hip_options_string", "yolo2_hip_set_plan_cache", "yolo2_hip_plan_cache_info", "yolo2_hip_plan_cache_check",
     "yolo2_hip_i16_plan_check", "yolo2_hip_ks_scratch_bytes", "yolo2_hip_i16_edge_map", "yolo2_hip_last_layer_edge",
@@ -183,6 +183,7 @@ def lib():
     sig("yolo2_hip_plan_cache_info", [vp, C.POINTER(u64), pi32, pi32, pi32])
     sig("yolo2_hip_plan_cache_check", [C.c_char_p, u64, pi32])
     sig("yolo2_hip_i16_plan_check", [i32, i32, i32, C.c_size_t])
+    sig("yolo2_hip_f16_plan_describe", [C.c_char_p, i32, i32, C.c_char_p, i32], i32)
     sig("yolo2_hip_i16_edge_map", [i32, i32, i32, i32, vp, vp, vp, vp])
     sig("yolo2_hip_last_layer_edge", [], i32)
     sig("yolo2_hip_run_batch_f32tol", [vp, u64, i32, u64, vp])
@@ -270,6 +271,16 @@ def lib():
 def check(rc: int, what: str = ""):
     if rc != YOLO2_SUCCESS:
         raise Yolo2HipError(f"{what} failed with status {rc}: {lib().yolo2_hip_last_error().decode()}")
+
+
+def f16_plan_describe(options: str, split: int, batch: int) -> str:
+    """The fp16 (split=0) / fp32-tolerance (split=1) launch table for a plan batch as text, one line per step; no GPU needed."""
+    n = lib().yolo2_hip_f16_plan_describe(options.encode(), split, batch, None, 0)
+    if n < 0:
+        check(n, "yolo2_hip_f16_plan_describe")
+    buf = C.create_string_buffer(n + 1)
+    assert lib().yolo2_hip_f16_plan_describe(options.encode(), split, batch, buf, n + 1) == n
+    return buf.value.decode()
 
 
 # ------------------------------------------------------------------ tier 1 helpers (tests)
