@@ -435,6 +435,28 @@ int yolo2_hip_postprocess_f32(yolo2_hip_ctx *ctx, uint64_t region_dev, int batch
                               float thresh, float nms, yolo2_hip_det *dets, int cap_per_frame, int *counts,
                               float *rows, int *totals, float *proc, void *stream);
 
+/* The camera loop's tail.  The reference's streaming app (linux_app/src/main.c:1013-1026, :1184-1197) and its single-image mode
+ * (:827-858) do not run the src/core functions above but linux_app/src/yolo2_postprocess.c, and the two do not compute the same
+ * numbers.  These two entries restate that file; arguments, checks, layouts and synchronisation are those of the entries above.
+ * What differs from the src/core tail:
+ *   sigmoid      1.0f / (1.0f + expf(-x)) in float, x > 10 -> 1 and x < -10 -> 0 (:17-21), not 1. / (1. + exp(-x)) in double
+ *   softmax      expf, the float sum in class order, then *= 1.0f / sum, 1 / n for a sum <= 0 (:30-57), not (float)exp(double) and / sum
+ *   boxes        correct_region_boxes in float throughout, (netw - new_w) / 2.0f / netw (:77-101), not partly in double
+ *   box_iou      fminf / fmaxf and * 0.5f, 0 for an overlap or a union <= 0 (:199-226)
+ *   NMS          yolo2_do_nms_sort (:248-284) runs at EVERY nms, 0 (and below) included (main.c:856-858); the entries above skip
+ *                the sort for nms <= 0.  The per-class sort is the same stable one; thresh < 0 stays refused.
+ *   rows         the array holds only the candidates found (:153-191); the [batch][845][85] layout is kept: the first totals[f] rows
+ *                are dets[] after yolo2_do_nms_sort, element for element and in its order, the rows behind them are zero
+ *   proc         the `output` of yolo2_forward_region_layer
+ * The int16 entry is IDENTICAL to yolo2_postprocess.c on the same tensor, by the same construction: its sigmoid and its two expf
+ * are tables the host's libm filled.  The float entry evaluates expf on the device: within an ulp of the host's per value. */
+int yolo2_hip_postprocess_int16_app(yolo2_hip_ctx *ctx, uint64_t region_dev, int batch, int final_q, const int *im_w,
+                                    const int *im_h, float thresh, float nms, yolo2_hip_det *dets, int cap_per_frame,
+                                    int *counts, float *rows, int *totals, float *proc, void *stream);
+int yolo2_hip_postprocess_f32_app(yolo2_hip_ctx *ctx, uint64_t region_dev, int batch, const int *im_w, const int *im_h,
+                                  float thresh, float nms, yolo2_hip_det *dets, int cap_per_frame, int *counts,
+                                  float *rows, int *totals, float *proc, void *stream);
+
 /* The whole chain for camera-style input at the path's rate: n images of arbitrary sizes as HOST bytes -> detection records, in
  * chunks of `batch` images.  Bytes cross PCIe in, letterboxing and the network run on the GPU, the region tensor STAYS in HBM and
  * the tail (region + boxes + NMS + record compaction) runs on the same device right behind the network; only the records (32 bytes
@@ -443,9 +465,13 @@ int yolo2_hip_postprocess_f32(yolo2_hip_ctx *ctx, uint64_t region_dev, int batch
  * yolo2_forward_region_layer / get_region_detections / do_nms_sort per frame).
  *   flags   YOLO2_DETS_BEST_CLASS: one record per detection - its best class (linux_app/src/main.c:1040-1052); a frame then has at
  *           most 845 records, so cap_per_frame = 845 never truncates.  0: a record per (detection, class) with prob > 0.
+ *           YOLO2_DETS_APP_TAIL: the tail is the camera loop's (yolo2_hip_postprocess_*_app above) instead of the src/core one, in
+ *           every _dets entry, single- and multi-device, int16 and _f16: the records the reference's loop prints, draws and streams.
+ *           Any other bit is ignored.
  *   dets    [n][cap_per_frame]; counts[f] = records frame f produced (if > cap_per_frame the surplus was dropped); dets[].frame is the
  *           image's index in `images`.  Records identical to yolo2_hip_postprocess_int16's on the same tensors.  Synchronous. */
 #define YOLO2_DETS_BEST_CLASS 1
+#define YOLO2_DETS_APP_TAIL 2
 int yolo2_hip_run_images_u8_dets(yolo2_hip_ctx *ctx, const uint8_t *const *images, const int *widths, const int *heights,
                                  int channels, int n, int batch, float thresh, float nms, int flags, yolo2_hip_det *dets,
                                  int cap_per_frame, int *counts, int *final_q);

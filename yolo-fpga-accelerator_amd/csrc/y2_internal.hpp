@@ -444,10 +444,11 @@ size_t y2_post_geom_bytes(void);
 int y2_post_fill_geom(void *geom_host, const int *im_w, const int *im_h, int n);   // host side: correct_region_boxes' per-frame constants
 // region tensor [batch][425][13][13] int16 on `device` -> b->dets / b->counts (cap records per frame; best_only: one per detection);
 // b->geom must hold the frames' records (copied on `st` in front of this call).  Enqueues on st, returns without synchronising.
+// app_tail: the camera loop's tail (linux_app/src/yolo2_postprocess.c, YOLO2_DETS_APP_TAIL) instead of the src/core one.
 int y2_post_enqueue_int16(int device, const int16_t *region_dev, int batch, int final_q, float thresh, float nms, int cap, int best_only,
-                          Y2PostBufs *b, hipStream_t st);
+                          int app_tail, Y2PostBufs *b, hipStream_t st);
 // the same on an fp32 region tensor (the fp16 / split / fp32 passes; yolo2_hip_postprocess_f32 is this plus its synchronous copies).
 // proc_dev (optional): the activated region tensor; final_rows (optional): the rows the records were compacted from.
-int y2_post_enqueue_f32(const float *region_dev, int batch, float thresh, float nms, int cap, int best_only, Y2PostBufs *b, hipStream_t st,
-                        float *proc_dev = nullptr, float **final_rows = nullptr);
+int y2_post_enqueue_f32(const float *region_dev, int batch, float thresh, float nms, int cap, int best_only, int app_tail, Y2PostBufs *b,
+                        hipStream_t st, float *proc_dev = nullptr, float **final_rows = nullptr);
 

@@ -579,7 +579,8 @@ static int run_images_i16_dets(yolo2_hip_ctx *c, const uint8_t *const *images, c
     if (!c->weights_loaded) return fail(YOLO2_ERROR, "weights not loaded");
     HIP_TRY(hipSetDevice(c->device), YOLO2_INIT_ERROR);
     batch = std::min(batch, n);
-    const int chunks = (n + batch - 1) / batch, cap = cap_per_frame, best_only = (flags & YOLO2_DETS_BEST_CLASS) ? 1 : 0;
+    const int chunks = (n + batch - 1) / batch, cap = cap_per_frame, best_only = (flags & YOLO2_DETS_BEST_CLASS) ? 1 : 0,
+              app_tail = (flags & YOLO2_DETS_APP_TAIL) ? 1 : 0;
     auto in_chunk = [&](int k) { return std::min(batch, n - k * batch); };
     auto padded = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const size_t table_bytes = padded((size_t)batch * sizeof(LetterboxItem));   // the chunk's letterbox table leads its staging buffer
@@ -674,7 +675,7 @@ static int run_images_i16_dets(yolo2_hip_ctx *c, const uint8_t *const *images, c
         if (rc) break;
         // the step after the path, on the device that produced the tensor, straight from HBM - on the download stream, so that the
         // next chunk's letterbox and network need not wait for it (the tail is 64 workgroups for 0.7 ms: latency, not work)
-        rc = y2_post_enqueue_int16(c->device, P.dout[b].get(), batch, q, thresh, nms, cap, best_only, &P.post[b], P.s_out);
+        rc = y2_post_enqueue_int16(c->device, P.dout[b].get(), batch, q, thresh, nms, cap, best_only, app_tail, &P.post[b], P.s_out);
         if (rc) break;
         Y2_TRY(hipMemcpyAsync(P.hcounts[b].get(), P.post[b].counts.get(), (size_t)batch * sizeof(int), hipMemcpyDeviceToHost, P.s_out), YOLO2_DMA_ERROR);
         Y2_TRY(hipMemcpyAsync(P.hdets[b].get(), P.post[b].dets.get(), (size_t)batch * cap * sizeof(yolo2_hip_det), hipMemcpyDeviceToHost, P.s_out), YOLO2_DMA_ERROR);
@@ -767,7 +768,8 @@ static int run_images_f16(yolo2_hip_ctx *c, int split, const uint8_t *const *ima
     if (rc) return rc;
     HIP_TRY(hipSetDevice(c->device), YOLO2_INIT_ERROR);
     batch = std::min(batch, n);
-    const int chunks = (n + batch - 1) / batch, best_only = (flags & YOLO2_DETS_BEST_CLASS) ? 1 : 0;
+    const int chunks = (n + batch - 1) / batch, best_only = (flags & YOLO2_DETS_BEST_CLASS) ? 1 : 0,
+              app_tail = (flags & YOLO2_DETS_APP_TAIL) ? 1 : 0;
     auto in_chunk = [&](int k) { return std::min(batch, n - k * batch); };
     auto padded = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const size_t table_bytes = padded((size_t)batch * sizeof(LetterboxItem));   // the chunk's letterbox table leads its staging buffer
@@ -841,7 +843,7 @@ static int run_images_f16(yolo2_hip_ctx *c, int split, const uint8_t *const *ima
         Y2_TRY(hipEventRecord(P.e_run[b], P.s_run), YOLO2_ERROR);
         Y2_TRY(hipStreamWaitEvent(P.s_out, P.e_run[b], 0), YOLO2_ERROR);
         if (want_dets) {   // the tail on the download stream, straight from HBM (see yolo2_hip_run_images_u8_dets)
-            if ((rc = y2_post_enqueue_f32(P.dregf[b].get(), batch, thresh, nms, cap, best_only, &P.post[b], P.s_out))) break;
+            if ((rc = y2_post_enqueue_f32(P.dregf[b].get(), batch, thresh, nms, cap, best_only, app_tail, &P.post[b], P.s_out))) break;
             Y2_TRY(hipMemcpyAsync(P.hcounts[b].get(), P.post[b].counts.get(), (size_t)batch * sizeof(int), hipMemcpyDeviceToHost, P.s_out), YOLO2_DMA_ERROR);
             Y2_TRY(hipMemcpyAsync(P.hdets[b].get(), P.post[b].dets.get(), (size_t)batch * cap * sizeof(yolo2_hip_det), hipMemcpyDeviceToHost, P.s_out),
                    YOLO2_DMA_ERROR);

@@ -17,6 +17,17 @@
 // double in the reference's order (the library is built with -ffp-contract=off; divisions are IEEE).  The float entry
 // (fp16 / fp32 region tensors) evaluates exp on the device instead: same formulas, results within 1 ulp of the host's.
 //
+// The camera loop's tail.  The reference's streaming app (linux_app/src/main.c:1013-1026, :1184-1197, and its single-image mode
+// :827-858) does not run the src/core functions above but linux_app/src/yolo2_postprocess.c, which rounds differently:
+//   yolo2_forward_region_layer   :106-135   sigmoid 1.0f / (1.0f + expf(-x)) with x > 10 -> 1, x < -10 -> 0 (:17-21); softmax with
+//                                           expf, the float sum in class order, then *= 1.0f / sum (1 / n for a sum <= 0, :30-57)
+//   yolo2_get_region_detections  :140-196   the same visiting order and candidate rule; only candidates are in the array
+//   correct_region_boxes         :77-101    float throughout (/ 2.0f)
+//   yolo2_do_nms_sort            :248-284   the same stable sort; box_iou (:199-226) with fminf / fmaxf and * 0.5f, 0 for an overlap
+//                                           or a union <= 0; run at EVERY nms threshold (main.c:856-858), 0 included
+// It is the App = true instantiation of k_region_rows / k_nms_rows; App = false is the src/core tail.  On the int16 path its
+// transcendentals are two more host-filled tables (sigmoid_app, softexp_app), so it is identical to the CPU's by construction too.
+//
 // Kernels (one workgroup per frame, frames are independent):
 //   k_region_rows   activations + candidate compaction (ordered) + box decode + class probabilities -> rows [845][85]
 //   k_nms_rows      the exact sort/suppress sequence over the 80 classes, order kept in LDS
@@ -57,10 +68,13 @@ int pfail(int code, const char *fmt, ...)
         if (e_ != hipSuccess) return pfail(code, "%s failed: %s", #expr, hipGetErrorString(e_));  \
     } while (0)
 
-struct Luts {          // per (device, Q): device pointers to three 65536-entry float tables
+struct Luts {          // per (device, Q): device pointers to 65536-entry float tables
     float *logistic = nullptr;   // [v + 32768] = (float)(1. / (1. + exp(-(double)(v * 2^-Q))))
     float *softexp = nullptr;    // [d]         = (float)exp((double)(-(d * 2^-Q)))        d = largest - value, 0..65535
     float *expf_ = nullptr;      // [v + 32768] = expf(v * 2^-Q)
+    // the camera loop's tail (yolo2_postprocess.c)
+    float *sigmoid_app = nullptr;   // [v + 32768] = x > 10 ? 1 : x < -10 ? 0 : 1.0f / (1.0f + expf(-x)),  x = v * 2^-Q
+    float *softexp_app = nullptr;   // [d]         = expf(-(d * 2^-Q))
 };
 std::mutex g_mu;        // guards the table cache
 std::map<std::pair<int, int>, Luts> g_luts;
@@ -69,12 +83,15 @@ struct FrameGeom {     // per-frame letterbox correction constants (correct_regi
     double off_x, off_y;         // (netw - new_w) / 2. / netw
     float sx, sy;                // (float)new_w / netw
     float mw, mh;                // (float)netw / new_w
+    float foff_x, foff_y;        // (netw - new_w) / 2.0f / netw: the camera loop's tail subtracts in float
 };
 
-template <typename T>
+// App = true: the tables / expressions of yolo2_postprocess.c.  The int16 input is table-driven either way: the variant only
+// decides WHICH tables lg and se point to (enqueue).
+template <typename T, bool App>
 struct In;
-template <>
-struct In<short> {
+template <bool App>
+struct In<short, App> {
     const short *p; const float *lg, *se, *ex; float scale;
     __device__ float raw(int i) const { return (float)p[i] * scale; }                       // yolo2_model.cpp:415-417
     __device__ float logistic(int i) const { return lg[(int)p[i] + 32768]; }
@@ -83,7 +100,7 @@ struct In<short> {
     __device__ float softe(int i, int largest_key, float) const { return se[largest_key - (int)p[i]]; }
 };
 template <>
-struct In<float> {
+struct In<float, false> {
     const float *p; const float *lg, *se, *ex; float scale;
     __device__ float raw(int i) const { return p[i]; }
     __device__ float logistic(int i) const { return (float)(1. / (1. + exp(-(double)p[i]))); }
@@ -91,17 +108,47 @@ struct In<float> {
     __device__ int key(int) const { return 0; }
     __device__ float softe(int i, int, float largest) const { return (float)exp((double)(p[i] / 1.f - largest / 1.f)); }
 };
+template <>
+struct In<float, true> {
+    const float *p; const float *lg, *se, *ex; float scale;
+    __device__ float raw(int i) const { return p[i]; }
+    __device__ float logistic(int i) const                                                     // yolo2_postprocess.c:17-21
+    {
+        const float x = p[i];
+        if (x > 10.0f) return 1.0f;
+        if (x < -10.0f) return 0.0f;
+        return 1.0f / (1.0f + expf(-x));
+    }
+    __device__ float expw(int i) const { return expf(p[i]); }
+    __device__ int key(int) const { return 0; }
+    __device__ float softe(int i, int, float largest) const { return expf(p[i] - largest); }  // :40
+};
 
-// rows: [845][85] = x, y, w, h, objectness, prob[80]; rows at and past `total` are zero (calloc'ed slots of make_network_boxes)
-template <typename T>
-__global__ __launch_bounds__(256) void k_region_rows(In<T> in0, int batch, const FrameGeom *__restrict__ geom, float thresh,
+// e_j and the sequential sum -> the class's softmax output: e / sum (yolo_math.cpp:238-240), or, in the camera loop's tail,
+// e * (1.0f / sum) with 1 / n for a sum <= 0 (yolo2_postprocess.c:45-56)
+template <bool App>
+__device__ __forceinline__ float soft_out(float e, float sum)
+{
+    if constexpr (App) {
+        if (sum <= 0.0f) return 1.0f / (float)kClasses;
+        const float inv_sum = 1.0f / sum;
+        return e * inv_sum;
+    } else {
+        return e / sum;
+    }
+}
+
+// rows: [845][85] = x, y, w, h, objectness, prob[80]; rows at and past `total` are zero (calloc'ed slots of make_network_boxes;
+// the camera loop's array has no such slots, its rows keep the layout and the zeros all the same)
+template <typename T, bool App>
+__global__ __launch_bounds__(256) void k_region_rows(In<T, App> in0, int batch, const FrameGeom *__restrict__ geom, float thresh,
                                                      float *__restrict__ rows, int *__restrict__ totals, float *__restrict__ proc)
 {
     __shared__ int flag[kDets + 3];
     __shared__ int rank[kDets + 3];
     __shared__ int wsum[4];
     const int f = blockIdx.x, tid = threadIdx.x;
-    In<T> in = in0;
+    In<T, App> in = in0;
     in.p += (size_t)f * kEntries * kDets;    // 425 * 169
     float *frows = rows + (size_t)f * kDets * kEntries;
     // candidate d = cell * 5 + anchor (get_region_detections' visiting order); entry e of anchor n at ((n*85 + e)*169 + cell)
@@ -144,8 +191,13 @@ __global__ __launch_bounds__(256) void k_region_rows(In<T> in0, int batch, const
             float by = ((float)row + in.logistic(base + 1 * kWH)) / (float)kH;
             float bw = in.expw(base + 2 * kWH) * c_anchors[2 * n] / (float)kW;
             float bh = in.expw(base + 3 * kWH) * c_anchors[2 * n + 1] / (float)kH;
+            if constexpr (App) {
+                bx = (bx - g.foff_x) / g.sx;                                         // yolo2_postprocess.c:90-91: all float
+                by = (by - g.foff_y) / g.sy;
+            } else {
             bx = (float)(((double)bx - g.off_x) / (double)g.sx);                     // correct_region_boxes, relative = 1
             by = (float)(((double)by - g.off_y) / (double)g.sy);
+            }
             bw *= g.mw;
             bh *= g.mh;
             r[0] = bx; r[1] = by; r[2] = bw; r[3] = bh; r[4] = obj;
@@ -164,10 +216,10 @@ __global__ __launch_bounds__(256) void k_region_rows(In<T> in0, int batch, const
         for (int j = 0; j < 64; ++j) sum += __shfl(e0, j);          // the reference's order: sum += e, j = 0 .. 79
         for (int j = 0; j < kClasses - 64; ++j) sum += __shfl(e1, j);
         {
-            const float p0 = obj * (e0 / sum);
+            const float p0 = obj * soft_out<App>(e0, sum);
             r[5 + lane] = p0 > thresh ? p0 : 0.f;
             if (lane < kClasses - 64) {
-                const float p1 = obj * (e1 / sum);
+                const float p1 = obj * soft_out<App>(e1, sum);
                 r[5 + 64 + lane] = p1 > thresh ? p1 : 0.f;
             }
         }
@@ -190,8 +242,8 @@ __global__ __launch_bounds__(256) void k_region_rows(In<T> in0, int batch, const
             float sum = 0.f;
             for (int j = 0; j < 64; ++j) sum += __shfl(e0, j);
             for (int j = 0; j < kClasses - 64; ++j) sum += __shfl(e1, j);
-            fp[base + (5 + lane) * kWH] = e0 / sum;
-            if (lane < kClasses - 64) fp[base + (5 + 64 + lane) * kWH] = e1 / sum;
+            fp[base + (5 + lane) * kWH] = soft_out<App>(e0, sum);
+            if (lane < kClasses - 64) fp[base + (5 + 64 + lane) * kWH] = soft_out<App>(e1, sum);
         }
     }
 }
@@ -212,9 +264,23 @@ __device__ __forceinline__ float box_iou_dev(const float4 a, const float4 b)    
     return inter / uni;
 }
 
+__device__ __forceinline__ float box_iou_app(const float4 a, const float4 b)        // yolo2_postprocess.c:199-226
+{
+    const float a_left = a.x - a.z * 0.5f, a_right = a.x + a.z * 0.5f, a_top = a.y - a.w * 0.5f, a_bottom = a.y + a.w * 0.5f;
+    const float b_left = b.x - b.z * 0.5f, b_right = b.x + b.z * 0.5f, b_top = b.y - b.w * 0.5f, b_bottom = b.y + b.w * 0.5f;
+    const float ow = fminf(a_right, b_right) - fmaxf(a_left, b_left);
+    const float oh = fminf(a_bottom, b_bottom) - fmaxf(a_top, b_top);
+    if (ow <= 0.0f || oh <= 0.0f) return 0.0f;
+    const float inter = ow * oh;
+    const float uni = a.z * a.w + b.z * b.w - inter;
+    if (uni <= 0.0f) return 0.0f;
+    return inter / uni;
+}
+
 // do_nms_sort for one frame per workgroup.  `order` (LDS) is the permutation the successive stable sorts build up;
 // rows stay where k_region_rows put them and are permuted ONCE at the end (rows_out), so that the output array is the
-// reference's dets[] after the last class, element for element.
+// reference's dets[] after the last class, element for element.  App: yolo2_do_nms_sort, the same sequence with the app's box_iou.
+template <bool App>
 __global__ __launch_bounds__(256) void k_nms_rows(float *__restrict__ rows, const int *__restrict__ totals, float nms,
                                                   float *__restrict__ rows_out)
 {
@@ -264,7 +330,7 @@ __global__ __launch_bounds__(256) void k_nms_rows(float *__restrict__ rows, cons
             if (key[i] == 0.f) continue;                       // uniform: key lives in LDS
             const float4 a = box[order[cur][i]];
             for (int j = i + 1 + tid; j < nnz; j += 256)
-                if (key[j] != 0.f && box_iou_dev(a, box[order[cur][j]]) > nms) {
+                if (key[j] != 0.f && (App ? box_iou_app(a, box[order[cur][j]]) : box_iou_dev(a, box[order[cur][j]])) > nms) {
                     key[j] = 0.f;
                     frows[(size_t)order[cur][j] * kEntries + 5 + k] = 0.f;
                 }
@@ -343,26 +409,32 @@ int get_luts(int device, int q, Luts &out)
     auto it = g_luts.find({device, q});
     if (it != g_luts.end()) { out = it->second; return YOLO2_SUCCESS; }
     // the reference's own expressions, evaluated by the host's libm for every value an int16 x 2^-Q tensor can hold
-    std::vector<float> lg(65536), se(65536), ex(65536);
+    std::vector<float> lg(65536), se(65536), ex(65536), sa(65536), ea(65536);
     const float scale = std::ldexp(1.0f, -q);
     for (int v = -32768; v < 32768; ++v) {
         const float x = (float)v * scale;
         lg[(size_t)(v + 32768)] = (float)(1. / (1. + std::exp(-(double)x)));    // yolo_math.cpp:19
         ex[(size_t)(v + 32768)] = std::exp(x);                                    // std::exp(float): yolo_region.cpp:23-24
+        sa[(size_t)(v + 32768)] = x > 10.0f ? 1.0f : x < -10.0f ? 0.0f : 1.0f / (1.0f + expf(-x));   // yolo2_postprocess.c:17-21
     }
     for (int d = 0; d < 65536; ++d) {
         // input[i]/temp - largest/temp with temp = 1: a float subtraction of two multiples of 2^-Q, exact
         const float diff = -((float)d * scale);
         se[(size_t)d] = (float)std::exp((double)diff);                            // yolo_math.cpp:234
+        ea[(size_t)d] = expf(diff);                                               // yolo2_postprocess.c:40
     }
     Luts l;
     HIPP_TRY(hipSetDevice(device), YOLO2_INIT_ERROR);
     HIPP_TRY(hipMalloc((void **)&l.logistic, 65536 * 4), YOLO2_MMAP_ERROR);
     HIPP_TRY(hipMalloc((void **)&l.softexp, 65536 * 4), YOLO2_MMAP_ERROR);
     HIPP_TRY(hipMalloc((void **)&l.expf_, 65536 * 4), YOLO2_MMAP_ERROR);
+    HIPP_TRY(hipMalloc((void **)&l.sigmoid_app, 65536 * 4), YOLO2_MMAP_ERROR);
+    HIPP_TRY(hipMalloc((void **)&l.softexp_app, 65536 * 4), YOLO2_MMAP_ERROR);
     HIPP_TRY(hipMemcpy(l.logistic, lg.data(), 65536 * 4, hipMemcpyHostToDevice), YOLO2_DMA_ERROR);
     HIPP_TRY(hipMemcpy(l.softexp, se.data(), 65536 * 4, hipMemcpyHostToDevice), YOLO2_DMA_ERROR);
     HIPP_TRY(hipMemcpy(l.expf_, ex.data(), 65536 * 4, hipMemcpyHostToDevice), YOLO2_DMA_ERROR);
+    HIPP_TRY(hipMemcpy(l.sigmoid_app, sa.data(), 65536 * 4, hipMemcpyHostToDevice), YOLO2_DMA_ERROR);
+    HIPP_TRY(hipMemcpy(l.softexp_app, ea.data(), 65536 * 4, hipMemcpyHostToDevice), YOLO2_DMA_ERROR);
     g_luts[{device, q}] = l;
     out = l;
     return YOLO2_SUCCESS;
@@ -381,6 +453,8 @@ FrameGeom frame_geom(int w, int h)
     g.sy = (float)new_h / neth;
     g.mw = (float)netw / new_w;
     g.mh = (float)neth / new_h;
+    g.foff_x = (netw - new_w) / 2.0f / netw;
+    g.foff_y = (neth - new_h) / 2.0f / neth;
     return g;
 }
 
@@ -413,22 +487,23 @@ std::map<int, std::mutex> g_dev_mu;   // one synchronous call at a time PER DEVI
 
 // The three kernels, enqueued on `st`; nothing is synchronised.  geom_dev: `batch` FrameGeom records already on the device (or on
 // their way: copied on `st` in front of this call).  proc_dev optional.
-template <typename T>
+// App: the camera loop's tail, which sorts and suppresses at every nms threshold (main.c:856-858).
+template <typename T, bool App>
 void enqueue(const T *region, const Luts &l, int final_q, int batch, float thresh, float nms, int cap, int best_only, Y2PostBufs &s,
              float *proc_dev, hipStream_t st, float **final_rows)
 {
-    In<T> in{region, l.logistic, l.softexp, l.expf_, std::ldexp(1.0f, -final_q)};
-    hipLaunchKernelGGL((k_region_rows<T>), dim3(batch), dim3(256), 0, st, in, batch, (const FrameGeom *)s.geom.get(), thresh, s.rows.get(), s.totals.get(), proc_dev);
+    In<T, App> in{region, App ? l.sigmoid_app : l.logistic, App ? l.softexp_app : l.softexp, l.expf_, std::ldexp(1.0f, -final_q)};
+    hipLaunchKernelGGL((k_region_rows<T, App>), dim3(batch), dim3(256), 0, st, in, batch, (const FrameGeom *)s.geom.get(), thresh, s.rows.get(), s.totals.get(), proc_dev);
     float *fr = s.rows.get();
-    if (nms > 0.f) {
-        hipLaunchKernelGGL(k_nms_rows, dim3(batch), dim3(256), 0, st, s.rows.get(), s.totals.get(), nms, s.rows2.get());
+    if (App || nms > 0.f) {
+        hipLaunchKernelGGL((k_nms_rows<App>), dim3(batch), dim3(256), 0, st, s.rows.get(), s.totals.get(), nms, s.rows2.get());
         fr = s.rows2.get();
     }
     if (cap > 0) hipLaunchKernelGGL(k_compact_dets, dim3(batch), dim3(256), 0, st, fr, s.totals.get(), cap, (DetRec *)s.dets.get(), s.counts.get(), best_only);
     if (final_rows) *final_rows = fr;
 }
 
-template <typename T>
+template <typename T, bool App = false>
 int postprocess(yolo2_hip_ctx *ctx, uint64_t region_dev, int batch, int final_q, const int *im_w, const int *im_h, float thresh, float nms,
                 yolo2_hip_det *dets, int cap_per_frame, int *counts, float *rows_host, int *totals_host, float *proc_host, void *stream)
 {
@@ -486,10 +561,10 @@ int postprocess(yolo2_hip_ctx *ctx, uint64_t region_dev, int batch, int final_q,
     float *final_rows = nullptr;
     hipError_t e = hipSuccess;
     if constexpr (std::is_same<T, float>::value) {
-        if ((rc = y2_post_enqueue_f32((const float *)(uintptr_t)region_dev, batch, thresh, nms, dets ? cap : 0, 0, s, st, proc_dev, &final_rows)))
+        if ((rc = y2_post_enqueue_f32((const float *)(uintptr_t)region_dev, batch, thresh, nms, dets ? cap : 0, 0, App, s, st, proc_dev, &final_rows)))
             return rc;
     } else {
-        enqueue<T>((const T *)(uintptr_t)region_dev, l, final_q, batch, thresh, nms, dets ? cap : 0, 0, *s, proc_dev, st, &final_rows);
+        enqueue<T, App>((const T *)(uintptr_t)region_dev, l, final_q, batch, thresh, nms, dets ? cap : 0, 0, *s, proc_dev, st, &final_rows);
         e = hipGetLastError();
     }
     if (e == hipSuccess && dets) e = hipMemcpyAsync(counts, s->counts.get(), (size_t)batch * sizeof(int), hipMemcpyDeviceToHost, st);
@@ -518,6 +593,20 @@ extern "C" int yolo2_hip_postprocess_f32(yolo2_hip_ctx *ctx, uint64_t region_dev
     return postprocess<float>(ctx, region_dev, batch, 0, im_w, im_h, thresh, nms, dets, cap_per_frame, counts, rows, totals, proc, stream);
 }
 
+extern "C" int yolo2_hip_postprocess_int16_app(yolo2_hip_ctx *ctx, uint64_t region_dev, int batch, int final_q, const int *im_w, const int *im_h,
+                                               float thresh, float nms, yolo2_hip_det *dets, int cap_per_frame, int *counts, float *rows,
+                                               int *totals, float *proc, void *stream)
+{
+    return postprocess<short, true>(ctx, region_dev, batch, final_q, im_w, im_h, thresh, nms, dets, cap_per_frame, counts, rows, totals, proc, stream);
+}
+
+extern "C" int yolo2_hip_postprocess_f32_app(yolo2_hip_ctx *ctx, uint64_t region_dev, int batch, const int *im_w, const int *im_h, float thresh,
+                                             float nms, yolo2_hip_det *dets, int cap_per_frame, int *counts, float *rows, int *totals,
+                                             float *proc, void *stream)
+{
+    return postprocess<float, true>(ctx, region_dev, batch, 0, im_w, im_h, thresh, nms, dets, cap_per_frame, counts, rows, totals, proc, stream);
+}
+
 // ---------------------------------------------------------------------------- internal: the tail as part of a pipeline (yolo2_hip.hip)
 
 int y2_post_alloc(int device, int batch, int cap, Y2PostBufs *b)
@@ -539,24 +628,26 @@ int y2_post_fill_geom(void *geom_host, const int *im_w, const int *im_h, int n)
 }
 
 int y2_post_enqueue_int16(int device, const int16_t *region_dev, int batch, int final_q, float thresh, float nms, int cap, int best_only,
-                          Y2PostBufs *b, hipStream_t st)
+                          int app_tail, Y2PostBufs *b, hipStream_t st)
 {
     if (final_q < -15 || final_q > 30) return pfail(YOLO2_ERROR, "final Q %d out of range", final_q);
     if (batch > b->cap_frames || (size_t)batch * (size_t)cap > b->cap_dets) return pfail(YOLO2_ERROR, "post-processing buffers too small for %d frames x %d records", batch, cap);
     Luts l;
     const int rc = get_luts(device, final_q, l);
     if (rc) return rc;
-    enqueue<short>(region_dev, l, final_q, batch, thresh, nms, cap, best_only, *b, nullptr, st, nullptr);
+    if (app_tail) enqueue<short, true>(region_dev, l, final_q, batch, thresh, nms, cap, best_only, *b, nullptr, st, nullptr);
+    else enqueue<short, false>(region_dev, l, final_q, batch, thresh, nms, cap, best_only, *b, nullptr, st, nullptr);
     HIPP_TRY(hipGetLastError(), YOLO2_ERROR);
     return YOLO2_SUCCESS;
 }
 
 
-int y2_post_enqueue_f32(const float *region_dev, int batch, float thresh, float nms, int cap, int best_only, Y2PostBufs *b, hipStream_t st,
-                        float *proc_dev, float **final_rows)
+int y2_post_enqueue_f32(const float *region_dev, int batch, float thresh, float nms, int cap, int best_only, int app_tail, Y2PostBufs *b,
+                        hipStream_t st, float *proc_dev, float **final_rows)
 {
     if (batch > b->cap_frames || (size_t)batch * (size_t)cap > b->cap_dets) return pfail(YOLO2_ERROR, "post-processing buffers too small for %d frames x %d records", batch, cap);
-    enqueue<float>(region_dev, Luts(), 0, batch, thresh, nms, cap, best_only, *b, proc_dev, st, final_rows);
+    if (app_tail) enqueue<float, true>(region_dev, Luts(), 0, batch, thresh, nms, cap, best_only, *b, proc_dev, st, final_rows);
+    else enqueue<float, false>(region_dev, Luts(), 0, batch, thresh, nms, cap, best_only, *b, proc_dev, st, final_rows);
     HIPP_TRY(hipGetLastError(), YOLO2_ERROR);
     return YOLO2_SUCCESS;
 }

@@ -583,6 +583,131 @@ int nms_sort(std::vector<Detection> &dets, int classes, float thresh)
     return total;
 }
 
+// --------------------------------------------------------------------------------------- the camera loop's tail (linux_app)
+// The reference's streaming app (linux_app/src/main.c:1013-1026, :1184-1197; single-image mode :827-858) does not use the
+// src/core tail restated above but its own, linux_app/src/yolo2_postprocess.c, which is float throughout and rounds differently.
+
+namespace {
+inline float app_sigmoid(float x)  // yolo2_postprocess.c:17-21
+{
+    if (x > 10.0f) return 1.0f;
+    if (x < -10.0f) return 0.0f;
+    return 1.0f / (1.0f + expf(-x));
+}
+}  // namespace
+
+void app_region_forward(const Layer &l, const float *in, float *out)
+{
+    const int wh = l.w * l.h, total = wh * l.num * (l.coords + l.classes + 1);
+    memcpy(out, in, sizeof(float) * total);  // yolo2_postprocess.c:112
+    for (int n = 0; n < l.num; ++n) {        // :115-121
+        int index = entry_index(l, n * wh, 0);
+        for (int i = 0; i < 2 * wh; ++i) out[index + i] = app_sigmoid(out[index + i]);
+        index = entry_index(l, n * wh, l.coords);
+        for (int i = 0; i < wh; ++i) out[index + i] = app_sigmoid(out[index + i]);
+    }
+    if (!l.softmax) return;
+    for (int n = 0; n < l.num; ++n)
+        for (int loc = 0; loc < wh; ++loc) {  // softmax_stride in place, :30-57
+            float *p = out + entry_index(l, n * wh + loc, l.coords + 1);
+            float largest = -FLT_MAX;
+            for (int i = 0; i < l.classes; ++i)
+                if (p[i * wh] > largest) largest = p[i * wh];
+            float sum = 0.0f;
+            for (int i = 0; i < l.classes; ++i) {
+                const float e = expf(p[i * wh] - largest);
+                sum += e;
+                p[i * wh] = e;
+            }
+            if (sum <= 0.0f) {
+                const float inv = 1.0f / (float)l.classes;
+                for (int i = 0; i < l.classes; ++i) p[i * wh] = inv;
+                continue;
+            }
+            const float inv_sum = 1.0f / sum;
+            for (int i = 0; i < l.classes; ++i) p[i * wh] *= inv_sum;
+        }
+}
+
+std::vector<Detection> app_region_detections(const Layer &l, const float *out, int im_w, int im_h, int net_w, int net_h, float thresh)
+{
+    const int wh = l.w * l.h;
+    std::vector<Detection> dets;  // only the candidates found (yolo2_postprocess.c:153-191): no zeroed slots behind them
+    for (int i = 0; i < wh; ++i) {
+        const int row = i / l.w, col = i % l.w;
+        for (int n = 0; n < l.num; ++n) {
+            const float objectness = out[entry_index(l, n * wh + i, l.coords)];
+            if (objectness <= thresh) continue;
+            const int box_index = entry_index(l, n * wh + i, 0);
+            Detection d;
+            d.bbox.x = (col + out[box_index + 0 * wh]) / l.w;  // get_region_box, :67-74 (expf)
+            d.bbox.y = (row + out[box_index + 1 * wh]) / l.h;
+            d.bbox.w = expf(out[box_index + 2 * wh]) * l.anchors[2 * n] / l.w;
+            d.bbox.h = expf(out[box_index + 3 * wh]) * l.anchors[2 * n + 1] / l.h;
+            d.objectness = objectness;
+            d.prob.assign(l.classes, 0.f);
+            for (int j = 0; j < l.classes; ++j) {
+                const float prob = objectness * out[entry_index(l, n * wh + i, l.coords + 1 + j)];
+                d.prob[j] = prob > thresh ? prob : 0.0f;
+            }
+            dets.push_back(std::move(d));
+        }
+    }
+    // correct_region_boxes, :77-101, relative = 1: float throughout (/ 2.0f)
+    int new_w, new_h;
+    if (((float)net_w / im_w) < ((float)net_h / im_h)) {
+        new_w = net_w;
+        new_h = (im_h * net_w) / im_w;
+    } else {
+        new_h = net_h;
+        new_w = (im_w * net_h) / im_h;
+    }
+    for (Detection &d : dets) {
+        Box &b = d.bbox;
+        b.x = (b.x - (net_w - new_w) / 2.0f / net_w) / ((float)new_w / net_w);
+        b.y = (b.y - (net_h - new_h) / 2.0f / net_h) / ((float)new_h / net_h);
+        b.w *= (float)net_w / new_w;
+        b.h *= (float)net_h / new_h;
+    }
+    return dets;
+}
+
+float app_box_iou(const Box &a, const Box &b)  // yolo2_postprocess.c:199-226
+{
+    const float a_left = a.x - a.w * 0.5f, a_right = a.x + a.w * 0.5f, a_top = a.y - a.h * 0.5f, a_bottom = a.y + a.h * 0.5f;
+    const float b_left = b.x - b.w * 0.5f, b_right = b.x + b.w * 0.5f, b_top = b.y - b.h * 0.5f, b_bottom = b.y + b.h * 0.5f;
+    const float ow = fminf(a_right, b_right) - fmaxf(a_left, b_left);
+    const float oh = fminf(a_bottom, b_bottom) - fmaxf(a_top, b_top);
+    if (ow <= 0.0f || oh <= 0.0f) return 0.0f;
+    const float inter = ow * oh;
+    const float uni = a.w * a.h + b.w * b.h - inter;
+    if (uni <= 0.0f) return 0.0f;
+    return inter / uni;
+}
+
+int app_nms_sort(std::vector<Detection> &dets, int classes, float thresh)
+{
+    // yolo2_do_nms_sort, yolo2_postprocess.c:248-284.  The app calls it whatever the threshold is (main.c:856-858), 0 included.
+    int total = (int)dets.size(), k = total - 1;
+    for (int i = 0; i <= k; ++i)  // :251-262
+        if (dets[i].objectness == 0.0f) {
+            std::swap(dets[i], dets[k]);
+            --k;
+            --i;
+        }
+    total = k + 1;
+    for (int c = 0; c < classes; ++c) {
+        // qsort with nms_comparator (:229-243: the sign of the float difference, descending); glibc's merge sort, so stable
+        std::stable_sort(dets.begin(), dets.begin() + total, [c](const Detection &a, const Detection &b) { return a.prob[c] - b.prob[c] > 0; });
+        for (int i = 0; i < total; ++i) {
+            if (dets[i].prob[c] == 0.0f) continue;
+            for (int j = i + 1; j < total; ++j)
+                if (app_box_iou(dets[i].bbox, dets[j].bbox) > thresh) dets[j].prob[c] = 0.0f;
+        }
+    }
+    return total;
+}
+
 // the region layer of config/yolov2.cfg (13x13, 5 anchors, 80 classes, softmax)
 Layer yolo2_region_layer()
 {
@@ -608,6 +733,33 @@ std::vector<std::vector<Detection>> postprocess_batch(const int16_t *region, int
             region_forward(l, raw.data(), proc.data());
             std::vector<Detection> d = region_boxes(l, proc.data(), im_w[f], im_h[f], 416, 416, thresh);
             if (nms > 0) d.resize((size_t)nms_sort(d, l.classes, nms));
+            out[(size_t)f] = std::move(d);
+        }
+    };
+    threads = std::max(1, std::min(threads, batch));
+    std::vector<std::thread> pool;
+    for (int t = 1; t < threads; ++t) pool.emplace_back(worker);
+    worker();
+    for (auto &t : pool) t.join();
+    return out;
+}
+
+std::vector<std::vector<Detection>> postprocess_batch_app(const int16_t *region, int batch, int final_q, const int *im_w,
+                                                          const int *im_h, float thresh, float nms, int threads)
+{
+    const Layer l = yolo2_region_layer();
+    const size_t elems = (size_t)l.num * (l.coords + 1 + l.classes) * l.h * l.w;
+    std::vector<std::vector<Detection>> out((size_t)std::max(batch, 0));
+    const float scale = std::ldexp(1.0f, -final_q);
+    std::atomic<int> next{0};
+    auto worker = [&]() {
+        std::vector<float> raw(elems), proc(elems);
+        for (int f = next.fetch_add(1); f < batch; f = next.fetch_add(1)) {
+            const int16_t *r = region + (size_t)f * elems;
+            for (size_t t = 0; t < elems; ++t) raw[t] = (float)r[t] * scale;
+            app_region_forward(l, raw.data(), proc.data());
+            std::vector<Detection> d = app_region_detections(l, proc.data(), im_w[f], im_h[f], 416, 416, thresh);
+            if (!d.empty()) d.resize((size_t)app_nms_sort(d, l.classes, nms));   // main.c:856-858
             out[(size_t)f] = std::move(d);
         }
     };

@@ -119,6 +119,25 @@ Layer yolo2_region_layer();
 std::vector<std::vector<Detection>> postprocess_batch(const int16_t *region, int batch, int final_q, const int *im_w,
                                                       const int *im_h, float thresh, float nms, int threads);
 
+// ---------------------------------------------------------------- the camera loop's tail
+// The reference's camera / video loop (linux_app/src/main.c:1013-1026, :1184-1197) and its single-image mode (:827-858) run
+// linux_app/src/yolo2_postprocess.c, not the src/core tail above, and the two round differently.  These restate it bit for bit
+// (tests/golden/apptail.npz):
+// yolo2_forward_region_layer (:106-135): sigmoid 1.0f / (1.0f + expf(-x)) with x > 10 -> 1 and x < -10 -> 0 on x, y, objectness;
+// softmax with expf, a float sum in class order and *= 1.0f / sum (1 / n for a sum <= 0), in place over the raw class entries.
+void app_region_forward(const Layer &l, const float *in, float *out);
+// yolo2_get_region_detections (:140-196) + correct_region_boxes (:77-101, all float), relative = 1.  Returns ONLY the candidates
+// (objectness > thresh), cells in raster order and anchors inner; there are no zeroed slots behind them.
+std::vector<Detection> app_region_detections(const Layer &l, const float *out, int im_w, int im_h, int net_w, int net_h, float thresh);
+// yolo2_do_nms_sort (:248-284) with the app's box_iou (:199-226: fminf / fmaxf, * 0.5f, 0 for an overlap or a union <= 0).  The app
+// runs it at every threshold, 0 included.  Returns the number of detections kept in front.
+int app_nms_sort(std::vector<Detection> &dets, int classes, float thresh);
+float app_box_iou(const Box &a, const Box &b);
+// postprocess_batch with the three functions above: per frame exactly the single-frame calls (app_nms_sort whenever a frame has a
+// candidate, as main.c:856-858 does).
+std::vector<std::vector<Detection>> postprocess_batch_app(const int16_t *region, int batch, int final_q, const int *im_w,
+                                                          const int *im_h, float thresh, float nms, int threads);
+
 std::vector<std::string> load_names(const std::string &path);
 
 }  // namespace y2h

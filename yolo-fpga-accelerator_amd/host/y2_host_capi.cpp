@@ -81,6 +81,28 @@ int y2h_postprocess_batch(const int16_t *region, int batch, int final_q, const i
     } catch (const std::exception &e) { g_err = e.what(); return -1; }
 }
 
+// the camera loop's tail (linux_app/src/yolo2_postprocess.c): same layout as y2h_postprocess_batch
+int y2h_postprocess_app_batch(const int16_t *region, int batch, int final_q, const int *im_w, const int *im_h, float thresh,
+                              float nms, int threads, float *rows_out, int max_rows, int *totals)
+{
+    try {
+        auto all = postprocess_batch_app(region, batch, final_q, im_w, im_h, thresh, nms, threads);
+        for (int f = 0; f < batch; ++f) {
+            const auto &d = all[(size_t)f];
+            totals[f] = (int)d.size();
+            const int rows = std::min((int)d.size(), max_rows);
+            for (int i = 0; i < rows; ++i) {
+                float *r = rows_out + ((size_t)f * max_rows + i) * 85;
+                r[0] = d[i].bbox.x; r[1] = d[i].bbox.y; r[2] = d[i].bbox.w; r[3] = d[i].bbox.h; r[4] = d[i].objectness;
+                memcpy(r + 5, d[i].prob.data(), sizeof(float) * 80);
+            }
+        }
+        return 0;
+    } catch (const std::exception &e) { g_err = e.what(); return -1; }
+}
+
+void y2h_app_region_forward(const float *raw, float *proc) { app_region_forward(yolo2_region_layer(), raw, proc); }
+
 int y2h_load_pnm(const char *path, int *whc, float *out, long capacity)
 {
     try {

@@ -69,6 +69,7 @@ struct AppConfig {
     int max_frames = 0;                // 0 = all
     int infer_every = 1;
     std::string post = "gpu";          // region + boxes + NMS: gpu | host
+    std::string tail = "core";         // whose arithmetic the tail restates: the reference's src/core, or its camera loop's (linux_app)
     int chunk_batches = 4;             // batches per device and accelerator call (streaming)
     int decode_threads = 0;            // image decode pool; 0 = all host cores
     bool strict = false;               // streaming: stop at the first undecodable input instead of skipping the frame
@@ -120,6 +121,8 @@ void print_usage(const char *prog)
         "  --no-plan-cache       int16: do not read / write <weights>/weights_reorg_int16.bin.y2plan (the weight set's bounds, forms and\n"
         "                        timed conv plans; with it a weight set is timed once and every later run uses the same kernels)\n"
         "  --post <gpu|host>     Where region + boxes + NMS run (default gpu; host: int16 only)\n"
+        "  --tail <core|app>     Which of the reference's two detection tails: core = src/core (default), app = its camera loop's\n"
+        "                        linux_app/src/yolo2_postprocess.c (float sigmoid / softmax / boxes, NMS at every --nms)\n"
         "  --precision int16 | fp16 | fp32fast   also when streaming: fp16 / fp32fast read weights_reorg.bin + bias.bin and run layers 0+1\n"
         "                        straight from the image bytes on the matrix cores (yolo2_hip_run_images_pix_dets_f16)\n",
         prog);
@@ -179,6 +182,9 @@ AppConfig parse_args(int argc, char **argv)
         else if (arg == "--post" && need("")) {
             cfg.post = argv[++i];
             if (cfg.post != "gpu" && cfg.post != "host") { std::fprintf(stderr, "Unsupported --post %s (gpu | host)\n", cfg.post.c_str()); std::exit(1); }
+        } else if (arg == "--tail" && need("")) {
+            cfg.tail = argv[++i];
+            if (cfg.tail != "core" && cfg.tail != "app") { std::fprintf(stderr, "Unsupported --tail %s (core | app)\n", cfg.tail.c_str()); std::exit(1); }
         }
         else if (arg == "--backend" && need("")) {
             cfg.backend = argv[++i];
@@ -525,7 +531,7 @@ void run_stream(AppConfig cfg)
     const int ndev = (int)cfg.devices.size();
     std::printf("YOLOv2 Object Detection - streaming (%s)\n  devices:", src.mode());
     for (int d : cfg.devices) std::printf(" %d", d);
-    std::printf("\n  batch per device: %d\n  post-processing: %s\n", cfg.batch, cfg.post.c_str());
+    std::printf("\n  batch per device: %d\n  post-processing: %s (%s tail)\n", cfg.batch, cfg.post.c_str(), cfg.tail.c_str());
 
     yolo2_hip_multi *m = nullptr;
     if (yolo2_hip_multi_create(cfg.devices.data(), ndev, &m) != YOLO2_SUCCESS) throw std::runtime_error(yolo2_hip_last_error());
@@ -679,6 +685,7 @@ void run_stream(AppConfig cfg)
             std::vector<int16_t> region;
             std::vector<yolo2_hip_det> recs;
             const int post_threads = std::max(1, threads / ndev);
+            const int det_flags = YOLO2_DETS_BEST_CLASS | (cfg.tail == "app" ? YOLO2_DETS_APP_TAIL : 0);
             while (to_run.pop(ck)) {
                 const int n = (int)ck->frames.size();
                 ck->device_slot = slot;
@@ -696,9 +703,9 @@ void run_stream(AppConfig cfg)
                         recs.resize((size_t)n * cap);
                         std::vector<int> counts((size_t)n);
                         const int rc = f16 ? yolo2_hip_run_images_pix_dets_f16(ctx, split, ptrs.data(), ws.data(), hs.data(), pixfmt, n, cfg.batch, cfg.thresh,
-                                                                               cfg.nms, YOLO2_DETS_BEST_CLASS, recs.data(), cap, counts.data())
+                                                                               cfg.nms, det_flags, recs.data(), cap, counts.data())
                                            : yolo2_hip_run_images_pix_dets(ctx, ptrs.data(), ws.data(), hs.data(), pixfmt, n, cfg.batch, cfg.thresh, cfg.nms,
-                                                                           YOLO2_DETS_BEST_CLASS, recs.data(), cap, counts.data(), &q);
+                                                                           det_flags, recs.data(), cap, counts.data(), &q);
                         if (rc != YOLO2_SUCCESS) throw std::runtime_error(yolo2_hip_last_error());
                         const auto t_dets = std::chrono::steady_clock::now();
                         if (annotate_gpu && annotate_jpg) {     // painted and encoded on the GPU: only the streams come back
@@ -750,7 +757,8 @@ void run_stream(AppConfig cfg)
                         region.resize((size_t)n * YOLO2_REGION_ELEMS);
                         if (yolo2_hip_run_images_pix_host(ctx, ptrs.data(), ws.data(), hs.data(), pixfmt, n, cfg.batch, region.data(), &q) != YOLO2_SUCCESS)
                             throw std::runtime_error(yolo2_hip_last_error());
-                        auto all = y2h::postprocess_batch(region.data(), n, q, ws.data(), hs.data(), cfg.thresh, cfg.nms, post_threads);
+                        auto all = cfg.tail == "app" ? y2h::postprocess_batch_app(region.data(), n, q, ws.data(), hs.data(), cfg.thresh, cfg.nms, post_threads)
+                                                     : y2h::postprocess_batch(region.data(), n, q, ws.data(), hs.data(), cfg.thresh, cfg.nms, post_threads);
                         for (int f = 0; f < n; ++f) ck->dets[(size_t)f] = best_class_dets(all[(size_t)f], (int)all[(size_t)f].size(), last.classes, cfg.thresh);
                     }
                     ck->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() - t_annotate;
@@ -856,14 +864,18 @@ void run_detector(AppConfig cfg)
     const char *raw_path = std::getenv("YOLO2_DUMP_REGION_RAW");
     if (!raw_path || !raw_path[0]) raw_path = "yolov2_region_raw_hip.txt";
     if (do_dump) dump_floats(raw_path, raw.data(), raw.size());
-    y2h::region_forward(last, raw.data(), proc.data());
+    const bool app_tail = cfg.tail == "app";
+    if (app_tail) y2h::app_region_forward(last, raw.data(), proc.data());
+    else y2h::region_forward(last, raw.data(), proc.data());
     const char *proc_path = std::getenv("YOLO2_DUMP_REGION");
     if (!proc_path || !proc_path[0]) proc_path = "yolov2_region_proc_hip.txt";
     if (do_dump) dump_floats(proc_path, proc.data(), proc.size());
 
-    std::vector<y2h::Detection> dets = y2h::region_boxes(last, proc.data(), im.w, im.h, net.w, net.h, cfg.thresh);
+    std::vector<y2h::Detection> dets = app_tail ? y2h::app_region_detections(last, proc.data(), im.w, im.h, net.w, net.h, cfg.thresh)
+                                                : y2h::region_boxes(last, proc.data(), im.w, im.h, net.w, net.h, cfg.thresh);
     int total = (int)dets.size();
-    if (cfg.nms > 0.0f) total = y2h::nms_sort(dets, last.classes, cfg.nms);
+    if (app_tail) { if (total > 0) total = y2h::app_nms_sort(dets, last.classes, cfg.nms); }   // main.c:856-858: at every nms
+    else if (cfg.nms > 0.0f) total = y2h::nms_sort(dets, last.classes, cfg.nms);
     if ((int)names.size() < last.classes)
         std::fprintf(stderr, "Warning: names file provides %d labels, but network expects %d classes.\n", (int)names.size(), last.classes);
 

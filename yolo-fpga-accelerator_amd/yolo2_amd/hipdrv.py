@@ -37,6 +37,7 @@ EXPORTS = [
     "dma_buffer_init", "dma_buffer_cleanup", "dma_buffer_alloc", "dma_buffer_free", "dma_buffer_sync_for_device",
     "dma_buffer_sync_for_cpu", "dma_buffer_get_phys",
     "yolo2_hip_run_batch_fp32", "yolo2_hip_run_batch_fp32_host", "yolo2_hip_load_weights_fp32_dev", "yolo2_hip_postprocess_int16", "yolo2_hip_postprocess_f32",
+    "yolo2_hip_postprocess_int16_app", "yolo2_hip_postprocess_f32_app",
     "yolo2_hip_shard_range", "yolo2_hip_multi_create", "yolo2_hip_multi_destroy", "yolo2_hip_multi_num_devices",
     "yolo2_hip_multi_uses_rccl", "yolo2_hip_multi_ctx", "yolo2_hip_multi_load_weights_int16", "yolo2_hip_multi_load_weights_fp32",
     "yolo2_hip_multi_run_frames_int16", "yolo2_hip_multi_run_images_u8_host", "yolo2_hip_rccl_unique_id",
@@ -169,6 +170,8 @@ def lib():
     L.yolo2_hip_load_weights_fp32_dev.argtypes = [vp, u64, C.c_size_t, u64, C.c_size_t]
     L.yolo2_hip_postprocess_int16.argtypes = [vp, u64, i32, i32, vp, vp, C.c_float, C.c_float, vp, i32, vp, vp, vp, vp, vp]
     L.yolo2_hip_postprocess_f32.argtypes = [vp, u64, i32, vp, vp, C.c_float, C.c_float, vp, i32, vp, vp, vp, vp, vp]
+    L.yolo2_hip_postprocess_int16_app.argtypes = L.yolo2_hip_postprocess_int16.argtypes
+    L.yolo2_hip_postprocess_f32_app.argtypes = L.yolo2_hip_postprocess_f32.argtypes
     L.yolo2_hip_shard_range.argtypes = [i32, i32, i32, pi32, pi32]
     # (an older build loaded through YOLO2_HIP_LIB for an A/B run may lack the newer entries: their signatures are set when present)
     def sig(name, argtypes, restype=None):
@@ -787,10 +790,21 @@ DET_DTYPE = np.dtype([("frame", np.int32), ("det", np.int32), ("cls", np.int32),
                       ("x", np.float32), ("y", np.float32), ("w", np.float32), ("h", np.float32)])
 
 
+TAILS = ("core", "app")
+
+
+def _check_tail(tail):
+    if tail not in TAILS:
+        raise ValueError(f"tail must be one of {TAILS}, not {tail!r}")
+    return tail == "app"
+
+
 def postprocess(ctx, region_ptr: int, batch: int, im_w, im_h, thresh: float, nms: float, final_q: int = None, cap: int = 256,
-                want_rows: bool = False, want_proc: bool = False, stream: int = 0):
+                want_rows: bool = False, want_proc: bool = False, stream: int = 0, tail: str = "core"):
     """yolo2_hip_postprocess_int16 (final_q given) / _f32 on a DEVICE region tensor.  Returns a dict with
-    dets (structured array of the records kept), counts, and optionally rows [B][845][85], totals, proc."""
+    dets (structured array of the records kept), counts, and optionally rows [B][845][85], totals, proc.
+    tail "core" restates the reference's src/core tail, "app" (the _app entries) its camera loop's yolo2_postprocess.c."""
+    sfx = "_app" if _check_tail(tail) else ""
     iw = np.ascontiguousarray(im_w, dtype=np.int32)
     ih = np.ascontiguousarray(im_h, dtype=np.int32)
     assert iw.size == batch and ih.size == batch
@@ -801,10 +815,10 @@ def postprocess(ctx, region_ptr: int, batch: int, im_w, im_h, thresh: float, nms
     proc = np.zeros((batch, 425 * 169), dtype=np.float32) if want_proc else None
     vp = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
     if final_q is not None:
-        rc = lib().yolo2_hip_postprocess_int16(ctx._h, region_ptr, batch, int(final_q), vp(iw), vp(ih), thresh, nms, vp(dets), cap,
+        rc = getattr(lib(), "yolo2_hip_postprocess_int16" + sfx)(ctx._h, region_ptr, batch, int(final_q), vp(iw), vp(ih), thresh, nms, vp(dets), cap,
                                                vp(counts), vp(rows), vp(totals), vp(proc), C.c_void_p(stream))
     else:
-        rc = lib().yolo2_hip_postprocess_f32(ctx._h, region_ptr, batch, vp(iw), vp(ih), thresh, nms, vp(dets), cap, vp(counts),
+        rc = getattr(lib(), "yolo2_hip_postprocess_f32" + sfx)(ctx._h, region_ptr, batch, vp(iw), vp(ih), thresh, nms, vp(dets), cap, vp(counts),
                                              vp(rows), vp(totals), vp(proc), C.c_void_p(stream))
     check(rc, "yolo2_hip_postprocess")
     return {"dets": [dets[f, :min(int(counts[f]), cap)] for f in range(batch)], "counts": counts, "rows": rows, "totals": totals, "proc": proc}
@@ -818,6 +832,7 @@ def live_bytes():
 
 
 DETS_BEST_CLASS = 1
+DETS_APP_TAIL = 2
 
 
 def _image_args(images, pixfmt=None):
@@ -836,18 +851,20 @@ PRECISIONS = ("int16", "fp16", "fp32fast")
 
 
 def run_images_dets(handle, images, batch: int, thresh: float, nms: float, cap: int = 845, best_class: bool = True, multi: bool = False,
-                    precision: str = "int16", pixfmt=None):
+                    precision: str = "int16", pixfmt=None, tail: str = "core"):
     """yolo2_hip_run_images_u8_dets / yolo2_hip_multi_run_images_u8_dets: host images (uint8 [h][w][3]) -> per-frame detection
     records; letterbox, network and the tail run on the device(s), the region tensor never leaves HBM.  precision "fp16" /
     "fp32fast" (the split-fp16 pass) run the _dets_f16 entries instead (fp32 weights loaded); their final_q is None.
-    pixfmt "grey8" / "rgb24" / "yuyv" (arrays [h][w][2]): the _pix_dets entries with that format; None infers grey / RGB."""
+    pixfmt "grey8" / "rgb24" / "yuyv" (arrays [h][w][2]): the _pix_dets entries with that format; None infers grey / RGB.
+    tail "app" sets YOLO2_DETS_APP_TAIL: the records are those of the reference's camera loop (yolo2_postprocess.c)."""
     if precision not in PRECISIONS:
         raise ValueError(f"precision must be one of {PRECISIONS}, not {precision!r}")
+    app_tail = _check_tail(tail)
     n, ptrs, ws, hs, ch, _keep = _image_args(images, pixfmt)
     kind = "u8" if pixfmt is None else "pix"
     dets = np.zeros((n, cap), dtype=DET_DTYPE)
     counts = np.zeros(n, dtype=np.int32)
-    flags = DETS_BEST_CLASS if best_class else 0
+    flags = (DETS_BEST_CLASS if best_class else 0) | (DETS_APP_TAIL if app_tail else 0)
     if precision != "int16":
         split = int(precision == "fp32fast")
         name = f"yolo2_hip_{'multi_' if multi else ''}run_images_{kind}_dets_f16"
