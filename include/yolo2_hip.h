@@ -316,10 +316,10 @@ int yolo2_hip_layer_pool_fused(yolo2_hip_ctx *ctx, int layer_idx);
 int yolo2_hip_conv_launch_info(yolo2_hip_ctx *ctx, int conv_ordinal, int *grid_x, int *grid_y,
                                int *block, int *lds_bytes, int *pixels_per_lane);
 
-/* The launch plan of conv layer `conv_ordinal` as text, e.g. "P=1 pad=0 w16=0 hiacc=1 ks=0 splitk=0 pp=1 grp=1 fused=0 form=4 extra=0"
+/* The launch plan of conv layer `conv_ordinal` as text, e.g. "P=1 pad=0 w16=0 hiacc=1 ks=0 splitk=0 pp=1 grp=1 fused=0 form=4 extra=0 edge=0 xcd=4 pack=0"
  * (pixels per lane, occupancy cap, 16-channels-per-wavefront kernel, form D without v_perm, K-split over workgroups / over lanes,
- * 1x1 grouping, conv + pool fusion, arithmetic form, extra launches for blocks of another form).  Plans come from the committed plan
- * table (config/plan_gfx950.txt) for the batches it knows - the same in every process - and from timing otherwise. */
+ * 1x1 grouping, conv + pool fusion, arithmetic form, extra launches for blocks of another form, edge-class pixel tiles, XCD grid: 0 = none or 1 + log2 of the XCDs
+ * across the channel blocks, packed triples of the lane-split kernel; new pairs are appended).  Plans come from the committed plan table (config/plan_gfx950.txt) for the batches it knows, else from timing. */
 int yolo2_hip_conv_plan_string(yolo2_hip_ctx *ctx, int conv_ordinal, char *buf, int cap);
 /* Where the current batch's conv plan came from: 1 = the plan table shipped next to the library (config/plan_gfx950.txt: the same
  * kernels in every process), 2 = timed in this process (a batch or a model the table does not hold, or YOLO2_AUTOTUNE=1),

@@ -94,7 +94,9 @@ static void plan_conv(ConvPlan &p, const ActGeom &gin, long out_cg_stride, long 
         const int S = p.splitk, lt = tile_items_bound(gin, 64 / S * p.splitk_pp, halo);
         // (8 splits only for 1x1 layers: on the 3x3 layers the kernel is bound by re-staging the weight slices per
         //  pixel tile, and halving the tile to 8 pixels measured 2x slower)
-        if ((S != 4 && !(S == 8 && p.K == 1)) || gin.CG % S != 0 || gin.CG < 4 * S || S * (lt + p.K * p.K * 32) > kMaxTileItems) p.splitk = 0;
+        // (splitk_ok: the loader's proof that a chain split S ways keeps every increment and partial sum inside int32.  autotune only
+        //  offers the split where it holds; a plan line is held to the same proof here - legality is never taken from a file)
+        if (!p.splitk_ok || (S != 4 && !(S == 8 && p.K == 1)) || gin.CG % S != 0 || gin.CG < 4 * S || S * (lt + p.K * p.K * 32) > kMaxTileItems) p.splitk = 0;
     }
     if (p.ks) {   // K-split across workgroups: form D 3x3 launches, whole groups per split, at least two groups each
         // ... and the triples of all splits (24 bytes per output item and split) must fit the context's scratch: an overflow there
@@ -1224,7 +1226,8 @@ extern "C" int yolo2_hip_conv_launch_info(yolo2_hip_ctx *c, int ord, int *grid_x
 }
 
 // The launch plan of conv layer `ord` as text (lane 0's with lanes): "P=1 pad=0 w16=0 hiacc=1 ks=0 splitk=0 pp=1 grp=1 fused=0 form=4 extra=0 edge=0"
-// (edge=1: edge-class pixel tiles; launch-level, not a plan-table field).
+// (edge=1: edge-class pixel tiles; xcd=0 / 1+lg: no XCD grid / 2^lg XCDs across the blocks; pack=1: the lane-split kernel's packed
+// int16 triples; launch-level, not plan-table fields - new fields are appended at the end).
 // What bench.py discloses as the plan it ran (the plan table makes it the same in every process).
 extern "C" int yolo2_hip_conv_plan_string(yolo2_hip_ctx *c, int ord, char *buf, int cap)
 {
@@ -1236,8 +1239,8 @@ extern "C" int yolo2_hip_conv_plan_string(yolo2_hip_ctx *c, int ord, char *buf, 
         if (kNet[i].type == L_CONV) {
             if (o == ord) {
                 const ConvPlan &pl = c->fuse_pool[i] ? c->fplan[i] : c->plan[i];
-                snprintf(buf, (size_t)cap, "P=%d pad=%d w16=%d hiacc=%d ks=%d splitk=%d pp=%d grp=%d fused=%d form=%d extra=%zu edge=%d", pl.P, pl.lds_pad, pl.w16,
-                         pl.hiacc, pl.ks, pl.splitk, pl.splitk_pp, pl.grp, pl.pool_fused, pl.path, c->extra[i].size(), pl.args.edge);
+                snprintf(buf, (size_t)cap, "P=%d pad=%d w16=%d hiacc=%d ks=%d splitk=%d pp=%d grp=%d fused=%d form=%d extra=%zu edge=%d xcd=%d pack=%d", pl.P, pl.lds_pad, pl.w16,
+                         pl.hiacc, pl.ks, pl.splitk, pl.splitk_pp, pl.grp, pl.pool_fused, pl.path, c->extra[i].size(), pl.args.edge, pl.args.xcd_remap, pl.splitk_pack);
                 return YOLO2_SUCCESS;
             }
             o++;
