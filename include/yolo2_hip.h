@@ -579,6 +579,49 @@ int yolo2_hip_annotate_images_pix_jpeg_host(yolo2_hip_ctx *ctx, const uint8_t *c
                                             float thresh, const char *const *labels, int n_labels, int quality, uint8_t *const *jpeg,
                                             const size_t *caps, size_t *sizes, int *drawn);
 
+/* ------------------------------------------------------- the camera loop as one call
+ *
+ * What yolo2_linux produces per frame (linux_app/src/main.c:942-1091) - the detection records and the annotated frame - from one
+ * upload: per chunk the frames are staged once and go up in one H2D, the network of the chosen precision reads them from the chunk's
+ * device staging buffer (the path of yolo2_hip_run_images_pix_dets[_f16]), the tail leaves its records in HBM, k_draw_items turns them
+ * into the painter's draw items on the device (corner casts, rings, tag and the "%s %.2f" text in integers: csrc/draw_list.hpp),
+ * k_annotate_batch paints from the SAME staging buffer, and with YOLO2_LOOP_OUT_JPEG the encoder follows.  Counts, records and the
+ * frames (or the sizes and only the stream bytes in use) come back.
+ *
+ * dets / counts / final_q (int16 only; may be NULL) are exactly what yolo2_hip_run_images_pix_dets (YOLO2_LOOP_INT16) or
+ * yolo2_hip_run_images_pix_dets_f16 (split 0: YOLO2_LOOP_FP16, split 1: YOLO2_LOOP_F32TOL) return for the same arguments.  flags must
+ * contain YOLO2_DETS_BEST_CLASS (the form the painter draws; YOLO2_DETS_APP_TAIL selects the camera loop's tail); one thresh serves the
+ * records and the painter (main.c:1081).  out[f] (caps[f] bytes of room) and sizes[f]: with YOLO2_LOOP_OUT_RGB24 the bytes
+ * yolo2_hip_annotate_images_pix_host writes for those records, sizes[f] = w * h * 3, and a caps[f] below that is refused up front;
+ * with YOLO2_LOOP_OUT_JPEG (quality 1..100) the semantics of yolo2_hip_annotate_images_pix_jpeg_host.  drawn [n] may be NULL.
+ * A record that would be drawn but whose prob is not finite (or is 2^23 and more) is not drawn; the call then returns YOLO2_ERROR
+ * naming the first such frame, everything else is complete.  Refused before any launch: what the entries it joins refuse.
+ * Synchronous; batch <= 1024, cap_per_frame <= 65536. */
+enum { YOLO2_LOOP_INT16 = 0, YOLO2_LOOP_FP16 = 1, YOLO2_LOOP_F32TOL = 2 };
+enum { YOLO2_LOOP_OUT_RGB24 = 0, YOLO2_LOOP_OUT_JPEG = 1 };
+int yolo2_hip_loop_images_pix(yolo2_hip_ctx *ctx, int precision, const uint8_t *const *images, const int *widths, const int *heights,
+                              int pixfmt, int n, int batch, float thresh, float nms, int flags, yolo2_hip_det *dets, int cap_per_frame,
+                              int *counts, int *final_q, const char *const *labels, int n_labels, int out_format, int quality,
+                              uint8_t *const *out, const size_t *caps, size_t *sizes, int *drawn);
+/* What the last loop call on this context moved and built. */
+typedef struct {
+    int chunks;
+    uint64_t image_bytes_staged;   /* frame bytes copied into pinned staging (each frame once) */
+    uint64_t image_bytes_h2d;      /* bytes of the chunks' uploads: the letterbox and painter tables, then the padded frames */
+    uint64_t out_bytes_d2h;        /* painted frames, or sizes and stream bytes, that came back (records and counts not included) */
+    uint64_t items_built;          /* drawn records, as counted on the device */
+    char items_kernel[32];         /* "k_draw_items" */
+} yolo2_hip_loop_info_t;
+int yolo2_hip_loop_last_info(yolo2_hip_ctx *ctx, yolo2_hip_loop_info_t *info);
+/* Test doorway to k_draw_items: records [n_frames][cap_per_frame] and counts [n_frames] ON THE DEVICE -> the items it makes of them
+ * (frame f's at items + f * cap_per_frame * yolo2_hip_draw_item_size(), n_items[f] of them, in record order), as RGB24 frames of
+ * widths x heights would have them.  unprintable [n_frames] (may be NULL): the drawn records left out for their prob; any such
+ * record makes the call YOLO2_ERROR naming the first such frame, with all outputs complete. */
+size_t yolo2_hip_draw_item_size(void);
+int yolo2_hip_draw_items_dev(yolo2_hip_ctx *ctx, uint64_t dets_dev, uint64_t counts_dev, int n_frames, int cap_per_frame, const int *widths,
+                             const int *heights, float thresh, const char *const *labels, int n_labels, void *items, int *n_items,
+                             int *unprintable);
+
 /* ------------------------------------------------------- calibration: fp32 weights + frames -> int16 weights and Q tables
  *
  * The reference makes its int16 weight set with a separate tool (weights/README.md step 2b: "activation-calibrated"
@@ -689,6 +732,13 @@ int  yolo2_hip_multi_annotate_images_pix_jpeg_host(yolo2_hip_multi *m, const uin
                                                    int pixfmt, int n, int batch_per_device, const yolo2_hip_det *dets, int cap_per_frame,
                                                    const int *counts, float thresh, const char *const *labels, int n_labels, int quality,
                                                    uint8_t *const *jpeg, const size_t *caps, size_t *sizes, int *drawn);
+
+/* the camera loop as one call (see yolo2_hip_loop_images_pix), shard i on device i; yolo2_hip_loop_last_info of a member context
+ * (yolo2_hip_multi_ctx) describes its shard */
+int  yolo2_hip_multi_loop_images_pix(yolo2_hip_multi *m, int precision, const uint8_t *const *images, const int *widths, const int *heights,
+                                     int pixfmt, int n, int batch_per_device, float thresh, float nms, int flags, yolo2_hip_det *dets,
+                                     int cap_per_frame, int *counts, int *final_q, const char *const *labels, int n_labels, int out_format,
+                                     int quality, uint8_t *const *out, const size_t *caps, size_t *sizes, int *drawn);
 
 /* (b) one process per device (torchrun / MPI style; what bench.py --gpus N runs): rank 0 makes the 128-byte id
  * (ncclGetUniqueId), the launcher hands it to every rank, each rank joins with its context (ncclCommInitRank), then

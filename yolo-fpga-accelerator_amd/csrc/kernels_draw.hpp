@@ -84,6 +84,83 @@ __device__ inline bool anno_hit(const DrawItem &it, const uint64_t *font, int x,
     return false;
 }
 
+// The draw list made on the device: a chunk's compact records (k_compact_dets, YOLO2_DETS_BEST_CLASS form: [frames][cap] with the
+// per-frame counts) -> the table k_annotate_batch reads.  One workgroup per frame.  `geom` is the table as the host can know it
+// before the records exist - AnnoHeader (font, items_off) and AnnoFrame[frames] with everything but item0 / n_items - and `table` the
+// complete one: header and frames copied, frame f's items at item0 = f * cap in RECORD order (the order decides which item paints
+// last), made by y2d::draw_item_from_record, the arithmetic the host twin (y2h_draw_item) runs.  The drawn records are compacted in
+// order with an exclusive scan over pieces of 1024 records (4 consecutive records per lane, as k_compact_dets scans its rows).
+// info [2 * frames]: n_items, and the records that would be drawn but whose prob the formatter does not print (not drawn, counted).
+// labels: n_labels entries of y2d::draw_label_entry, or NULL.  Plain vector stores only; frames are independent.
+constexpr int kItemsThreads = 256, kItemsPiece = kItemsThreads * 4;
+__global__ __launch_bounds__(kItemsThreads) void k_draw_items(const y2d::DrawDet *__restrict__ dets, const int *__restrict__ counts, int cap,
+                                                              float thresh, const uint8_t *__restrict__ labels, int n_labels,
+                                                              const uint8_t *__restrict__ geom, uint8_t *__restrict__ table,
+                                                              int *__restrict__ info)
+{
+    __shared__ int s_wave[kItemsThreads / 64], s_bad[kItemsThreads / 64];
+    const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const AnnoHeader *gh = reinterpret_cast<const AnnoHeader *>(geom);
+    const AnnoFrame gf = reinterpret_cast<const AnnoFrame *>(geom + sizeof(AnnoHeader))[f];
+    const unsigned long long items_off = gh->items_off;
+    if (f == 0) {
+        AnnoHeader *th = reinterpret_cast<AnnoHeader *>(table);
+        if (tid < y2d::kDrawGlyphs) th->font[tid] = gh->font[tid];
+        if (tid == 0) th->items_off = items_off;
+    }
+    const int n = min(max(counts[f], 0), cap);
+    const y2d::DrawDet *rec = dets + (size_t)f * cap;
+    DrawItem *items = reinterpret_cast<DrawItem *>(table + items_off) + (size_t)f * cap;
+    int base = 0, bad = 0;
+    for (int p0 = 0; p0 < n; p0 += kItemsPiece) {   // (uniform: n is the frame's)
+        int v[4], s = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int i = p0 + tid * 4 + k;
+            v[k] = 0;
+            if (i < n) {
+                const y2d::DrawDet d = rec[i];
+                if (y2d::draw_is_drawn(d, thresh)) {
+                    if (y2d::draw_prob_printable(d.prob)) v[k] = 1;
+                    else ++bad;
+                }
+            }
+            s += v[k];
+        }
+        int incl = s;
+        for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(incl, o); if (lane >= o) incl += t; }
+        __syncthreads();   // the piece before has read s_wave
+        if (lane == 63) s_wave[wave] = incl;
+        __syncthreads();
+        int before = 0, total = 0;
+#pragma unroll
+        for (int w = 0; w < kItemsThreads / 64; ++w) { if (w < wave) before += s_wave[w]; total += s_wave[w]; }
+        int at = base + before + incl - s;
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (v[k]) {   // at < n <= cap: inside the frame's cap items
+                bool unprintable;
+                (void)y2d::draw_item_from_record(rec[p0 + tid * 4 + k], gf.w, gf.h, thresh, labels, n_labels, &items[at], &unprintable);
+                ++at;
+            }
+        base += total;
+    }
+    for (int o = 32; o > 0; o >>= 1) bad += __shfl_xor(bad, o);
+    __syncthreads();
+    if (lane == 0) s_bad[wave] = bad;
+    __syncthreads();
+    if (tid == 0) {
+        AnnoFrame out = gf;
+        out.item0 = f * cap;
+        out.n_items = base;
+        reinterpret_cast<AnnoFrame *>(table + sizeof(AnnoHeader))[f] = out;
+        info[2 * f] = base;
+        int b = 0;
+        for (int w = 0; w < kItemsThreads / 64; ++w) b += s_bad[w];
+        info[2 * f + 1] = b;
+    }
+}
+
 // grid (max strips of the chunk's frames, frames); table: AnnoHeader, AnnoFrame[frames], DrawItem[]
 __global__ __launch_bounds__(kAnnoThreads) void k_annotate_batch(const uint8_t *__restrict__ table, const uint8_t *__restrict__ src_base,
                                                                  uint8_t *__restrict__ out_base)

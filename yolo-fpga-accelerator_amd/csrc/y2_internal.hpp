@@ -10,6 +10,7 @@
 //   yolo2_post.hip    region layer + boxes + NMS;   yolo2_multi.hip  frame sharding + the RCCL weight broadcast
 //   yolo2_draw.hip    annotated frames: records + frames -> RGB24 with the reference's boxes and tags
 //   yolo2_jpeg.hip    RGB24 frames in device memory -> the reference's JPEG streams
+//   yolo2_loop.hip    the camera loop as one call: frames -> records and annotated frames from one upload (launches nothing itself)
 // Every non-template kernel is launched from exactly one of them (its kernels_*.hpp is included there only).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -241,12 +242,25 @@ struct Y2JpegBufs {
     hipEvent_t e_sizes[2] = {nullptr, nullptr};
 };
 
+// What the loop entry (yolo2_loop.hip) keeps beside PipeBufs and the two above: the draw list k_draw_items makes on the device - the
+// complete painter table (header, frames, cap items per frame) and the per-frame {items, unprintable records}, each written and read
+// on the download stream only, so one of each, with two pinned mirrors of the latter - and the call's label table.
+struct Y2LoopBufs {
+    size_t cap_table = 0, cap_labels = 0;
+    int cap_frames = 0;
+    Y2DevBuf<uint8_t> table, labels;
+    Y2DevBuf<int> info;
+    Y2PinBuf<int> hinfo[2];
+};
+
 struct F16Plan;   // yolo2_fp16.hip: the per-context launch table of the fp16 path
 
 struct yolo2_hip_ctx {
     PipeBufs pipe;
     Y2AnnoBufs anno;
     Y2JpegBufs jpeg;
+    Y2LoopBufs loop;
+    yolo2_hip_loop_info_t loop_info = {};   // of the last loop call (yolo2_hip_loop_last_info)
     int device = 0;
     Y2Options opt;                     // parsed once at creation (environment), changed only by yolo2_hip_set_option; lanes copy it
     std::shared_ptr<Y2PlanCache> plan_cache;   // weight-side cache bound by yolo2_hip_set_plan_cache (lanes share the parent's)
@@ -433,6 +447,34 @@ void y2_drv_conv_f32(const float *in, float *out, const float *w, const float *b
 // yolo2_draw.hip: the streams, events and buffers of c->anno (yolo2_hip_destroy)
 void y2_anno_free(yolo2_hip_ctx *c);
 void y2_anno_jpeg_free(yolo2_hip_ctx *c);   // c->jpeg
+int y2_anno_ensure(yolo2_hip_ctx *c, size_t cap_in, size_t cap_out);
+int y2_anno_jpeg_ensure(yolo2_hip_ctx *c, size_t cap_rgb, size_t cap_work, size_t cap_out, size_t frames);
+// ... and the device draw list of the loop entry (yolo2_loop.hip drives it; k_draw_items and the painter are launched here).
+// geom: the painter's table as the host knows it before the records exist (y2_loop_geom_bytes(nf) bytes; returns the most strips of a
+// frame).  _enqueue_items: k_draw_items on st from the records / counts of one tail, then the D2H of the per-frame
+// {items, unprintable} into c->loop.hinfo[b].  _enqueue_paint: k_annotate_batch over the table _enqueue_items left.
+void y2_loop_free(yolo2_hip_ctx *c);
+size_t y2_loop_geom_bytes(int nf);
+int y2_loop_fill_geom(uint8_t *geom, int nf, const int *widths, const int *heights, int ch, const size_t *src_off, const size_t *out_off);
+int y2_loop_ensure(yolo2_hip_ctx *c, int frames, int cap, const char *const *labels, int n_labels);
+int y2_loop_enqueue_items(yolo2_hip_ctx *c, int b, int nf, int cap, float thresh, const char *const *labels, int n_labels, const uint8_t *geom_dev,
+                          const yolo2_hip_det *dets_dev, const int *counts_dev, hipStream_t st);
+int y2_loop_enqueue_paint(yolo2_hip_ctx *c, int nf, int max_strips, const uint8_t *src_base, uint8_t *out_base, hipStream_t st);
+
+// yolo2_hip.hip: what the images entries and the loop entry share - the letterbox rule, the chunk letterbox launch, PipeBufs' growth
+// (need_hout: the pinned region mirrors; _post: the tail's buffers; _regf: the fp32 region tensors) and the threaded staging copy
+namespace y2 { struct LetterboxArgs; }
+int y2_letterbox_args(int w, int h, int channels, int net_w, int net_h, y2::LetterboxArgs &a, bool yuyv_ok);
+int y2_pix_channels(int pixfmt);
+void y2_launch_letterbox_batch(bool yuyv, const uint8_t *dbytes, float *din, int batch, hipStream_t st);
+int y2_pipe_ensure(PipeBufs &p, size_t host_in, size_t dev_in, int batch, bool need_hout);
+int y2_pipe_ensure_post(yolo2_hip_ctx *c, int batch, int cap);
+int y2_pipe_ensure_regf(PipeBufs &p, int batch, bool need_host);
+void y2_stage_images(uint8_t *dst, const uint8_t *const *images, const size_t *offs, const size_t *bytes, int nf);
+// the network of the chunk in buffer set b (staged, its upload waited for on s_run), enqueued: int16 into dout[b], with the events whoever
+// needs the whole region tensor waits for (the lanes are not joined); fp16 / split into dregf[b], e_run[b] recorded behind it
+int y2_pipe_enqueue_i16(yolo2_hip_ctx *c, int b, bool yuyv, int batch, int *q, std::vector<hipEvent_t> *done);
+int y2_pipe_enqueue_f16(yolo2_hip_ctx *c, yolo2_hip_ctx *run, bool fused, int b, bool yuyv, int batch);
 
 // yolo2_calib.hip: one exact fp32 pass over `batch` device frames + the abs-max reductions, accumulated into c->calib_stats; `counted`
 // of the frames are new ones (the images entry pads a short last chunk by repeating its last image).  Synchronises st.

@@ -3,7 +3,8 @@
 //
 // The host turns records into draw items (draw_list.hpp: corner casts, "%s %.2f" through the host's snprintf, glyph indices), the
 // items travel with the frame bytes, and k_annotate_batch (kernels_draw.hpp) converts and paints in one pass per pixel.  One entry
-// serves the records of every precision: it needs the frames and the records, no weights.
+// serves the records of every precision: it needs the frames and the records, no weights.  For the loop entry (yolo2_loop.hip) the
+// items are made on the device instead, from records that never left it (k_draw_items; the y2_loop_* functions below).
 #include "y2_internal.hpp"
 #include "kernels_draw.hpp"
 #include "y2_draw.hpp"
@@ -149,7 +150,7 @@ void y2_anno_free(yolo2_hip_ctx *c)
 
 // two buffer sets of at least cap_in staging bytes (table + items + frames) and cap_out output bytes; three streams.  Grown on demand
 // and kept with the context, like PipeBufs.
-static int anno_ensure(yolo2_hip_ctx *c, size_t cap_in, size_t cap_out)
+int y2_anno_ensure(yolo2_hip_ctx *c, size_t cap_in, size_t cap_out)
 {
     Y2AnnoBufs &a = c->anno;
     if (a.s_in && a.cap_in >= cap_in && a.cap_out >= cap_out) return YOLO2_SUCCESS;
@@ -223,7 +224,7 @@ extern "C" int yolo2_hip_annotate_images_pix_host(yolo2_hip_ctx *c, const uint8_
         cap_out = std::max(cap_out, out);
     }
     HIP_TRY(hipSetDevice(c->device), YOLO2_INIT_ERROR);
-    if ((rc = anno_ensure(c, cap_in, cap_out))) return rc;
+    if ((rc = y2_anno_ensure(c, cap_in, cap_out))) return rc;
     Y2AnnoBufs &A = c->anno;
     auto cleanup = [&]() { (void)hipDeviceSynchronize(); };
 #define Y2_TRY(expr, code) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { rc = fail(code, "%s failed: %s", #expr, hipGetErrorString(e_)); cleanup(); return rc; } } while (0)
@@ -271,6 +272,135 @@ extern "C" int yolo2_hip_annotate_images_pix_host(yolo2_hip_ctx *c, const uint8_
     return YOLO2_SUCCESS;
 }
 
+// ---------------------------------------------------------------------------- the draw list on the device (the loop entry, yolo2_loop.hip)
+
+void y2_loop_free(yolo2_hip_ctx *c)
+{
+    Y2LoopBufs &l = c->loop;
+    l.table.reset(); l.labels.reset(); l.info.reset();
+    for (int k = 0; k < 2; ++k) l.hinfo[k].reset();
+    l.cap_table = l.cap_labels = l.cap_frames = 0;
+}
+
+size_t y2_loop_geom_bytes(int nf) { return padded(sizeof(AnnoHeader) + (size_t)nf * sizeof(AnnoFrame)); }
+
+int y2_loop_fill_geom(uint8_t *geom, int nf, const int *widths, const int *heights, int ch, const size_t *src_off, const size_t *out_off)
+{
+    AnnoHeader *hd = reinterpret_cast<AnnoHeader *>(geom);
+    for (int i = 0; i < y2d::kDrawGlyphs; ++i) hd->font[i] = y2d::kDrawFont[i];
+    hd->items_off = y2_loop_geom_bytes(nf);
+    AnnoFrame *af = reinterpret_cast<AnnoFrame *>(geom + sizeof(AnnoHeader));
+    int max_strips = 0;
+    for (int f = 0; f < nf; ++f) {
+        af[f].src_off = src_off[f];
+        af[f].out_off = out_off[f];
+        af[f].w = widths[f]; af[f].h = heights[f]; af[f].ch = ch;
+        af[f].item0 = af[f].n_items = 0;   // (k_draw_items fills them in the device's copy)
+        af[f].strips = (int)(((long)widths[f] * heights[f] + kAnnoStripPx - 1) / kAnnoStripPx);
+        max_strips = std::max(max_strips, af[f].strips);
+    }
+    return max_strips;
+}
+
+// The context's scratch for chunks of up to `frames` frames with `cap` records each - the complete table (header, frames, cap items per
+// frame; written and read by kernels of ONE stream, so one of it), the per-frame info and its two pinned mirrors - and the call's
+// label table, uploaded here (synchronous: `labels` is the caller's).
+int y2_loop_ensure(yolo2_hip_ctx *c, int frames, int cap, const char *const *labels, int n_labels)
+{
+    Y2LoopBufs &l = c->loop;
+    int rc;
+    const size_t need = y2_loop_geom_bytes(frames) + padded((size_t)frames * cap * sizeof(DrawItem));
+    if (l.cap_table < need) {
+        l.cap_table = 0;
+        if ((rc = l.table.alloc(need))) return rc;
+        l.cap_table = need;
+    }
+    if (l.cap_frames < frames) {
+        l.cap_frames = 0;
+        if ((rc = l.info.alloc((size_t)frames * 2))) return rc;
+        for (int k = 0; k < 2; ++k)
+            if ((rc = l.hinfo[k].alloc((size_t)frames * 2))) return rc;
+        l.cap_frames = frames;
+    }
+    if (!labels) n_labels = 0;
+    const size_t lbytes = (size_t)n_labels * y2d::kDrawLabelStride;
+    if (lbytes) {
+        if (l.cap_labels < lbytes) {
+            l.cap_labels = 0;
+            if ((rc = l.labels.alloc(lbytes))) return rc;
+            l.cap_labels = lbytes;
+        }
+        std::vector<uint8_t> tbl(lbytes);
+        for (int i = 0; i < n_labels; ++i) y2d::draw_label_entry(labels[i], tbl.data() + (size_t)i * y2d::kDrawLabelStride);
+        HIP_TRY(hipMemcpy(l.labels.get(), tbl.data(), lbytes, hipMemcpyHostToDevice), YOLO2_DMA_ERROR);
+    }
+    return YOLO2_SUCCESS;
+}
+
+int y2_loop_enqueue_items(yolo2_hip_ctx *c, int b, int nf, int cap, float thresh, const char *const *labels, int n_labels, const uint8_t *geom_dev,
+                          const yolo2_hip_det *dets_dev, const int *counts_dev, hipStream_t st)
+{
+    Y2LoopBufs &l = c->loop;
+    if (nf > l.cap_frames || y2_loop_geom_bytes(nf) + (size_t)nf * cap * sizeof(DrawItem) > l.cap_table)
+        return fail(YOLO2_ERROR, "loop: item scratch too small for %d frames x %d records", nf, cap);
+    const bool with_labels = labels && n_labels > 0;
+    hipLaunchKernelGGL(k_draw_items, dim3((unsigned)nf), dim3(kItemsThreads), 0, st, reinterpret_cast<const DrawDet *>(dets_dev), counts_dev, cap,
+                       thresh, with_labels ? l.labels.get() : (const uint8_t *)nullptr, with_labels ? n_labels : 0, geom_dev, l.table.get(), l.info.get());
+    HIP_TRY(hipGetLastError(), YOLO2_ERROR);
+    HIP_TRY(hipMemcpyAsync(l.hinfo[b].get(), l.info.get(), (size_t)nf * 2 * sizeof(int), hipMemcpyDeviceToHost, st), YOLO2_DMA_ERROR);
+    return YOLO2_SUCCESS;
+}
+
+int y2_loop_enqueue_paint(yolo2_hip_ctx *c, int nf, int max_strips, const uint8_t *src_base, uint8_t *out_base, hipStream_t st)
+{
+    launch_annotate(c->loop.table.get(), src_base, out_base, max_strips, nf, st);
+    HIP_TRY(hipGetLastError(), YOLO2_ERROR);
+    return YOLO2_SUCCESS;
+}
+
+// The test doorway: records and counts on the device -> the items k_draw_items makes of them, on the host.
+extern "C" size_t yolo2_hip_draw_item_size(void) { return sizeof(DrawItem); }
+extern "C" int yolo2_hip_draw_items_dev(yolo2_hip_ctx *c, uint64_t dets_dev, uint64_t counts_dev, int n_frames, int cap_per_frame,
+                                        const int *widths, const int *heights, float thresh, const char *const *labels, int n_labels,
+                                        void *items, int *n_items, int *unprintable)
+{
+    if (!c || !dets_dev || !counts_dev || !widths || !heights || !items || !n_items) return fail(YOLO2_ERROR, "draw items: null argument");
+    if (n_frames <= 0 || n_frames > 1024 || cap_per_frame <= 0 || cap_per_frame > 65536)
+        return fail(YOLO2_ERROR, "draw items: bad frame count %d (1..1024) / capacity %d (1..65536)", n_frames, cap_per_frame);
+    int rc;
+    if ((rc = check_common(thresh, n_labels))) return rc;
+    for (int f = 0; f < n_frames; ++f)
+        if ((rc = check_geometry(widths[f], heights[f], 3, f))) return rc;
+    HIP_TRY(hipSetDevice(c->device), YOLO2_INIT_ERROR);
+    if ((rc = y2_loop_ensure(c, n_frames, cap_per_frame, labels, n_labels))) return rc;
+    const size_t gbytes = y2_loop_geom_bytes(n_frames);
+    std::vector<uint8_t> geom(gbytes);
+    std::vector<size_t> zero((size_t)n_frames, 0);
+    (void)y2_loop_fill_geom(geom.data(), n_frames, widths, heights, 3, zero.data(), zero.data());
+    Y2DevBuf<uint8_t> dgeom;
+    if ((rc = dgeom.alloc(gbytes))) return rc;
+    HIP_TRY(hipMemcpy(dgeom.get(), geom.data(), gbytes, hipMemcpyHostToDevice), YOLO2_DMA_ERROR);
+    if ((rc = y2_loop_enqueue_items(c, 0, n_frames, cap_per_frame, thresh, labels, n_labels, dgeom.get(), (const yolo2_hip_det *)(uintptr_t)dets_dev,
+                                    (const int *)(uintptr_t)counts_dev, nullptr)))
+        return rc;
+    HIP_TRY(hipStreamSynchronize(nullptr), YOLO2_ERROR);
+    const int *info = c->loop.hinfo[0].get();
+    int bad_frame = -1;
+    for (int f = 0; f < n_frames; ++f) {
+        n_items[f] = info[2 * f];
+        if (unprintable) unprintable[f] = info[2 * f + 1];
+        if (info[2 * f + 1] && bad_frame < 0) bad_frame = f;
+        if (n_items[f] < 0 || n_items[f] > cap_per_frame) return fail(YOLO2_ERROR, "draw items: frame %d reports %d items", f, n_items[f]);
+        if (n_items[f])
+            HIP_TRY(hipMemcpy(static_cast<uint8_t *>(items) + (size_t)f * cap_per_frame * sizeof(DrawItem),
+                              c->loop.table.get() + gbytes + (size_t)f * cap_per_frame * sizeof(DrawItem), (size_t)n_items[f] * sizeof(DrawItem),
+                              hipMemcpyDeviceToHost),
+                    YOLO2_DMA_ERROR);
+    }
+    if (bad_frame >= 0) return fail(YOLO2_ERROR, "draw items: frame %d has a record with a non-finite (or 2^23 and larger) prob among those to be drawn", bad_frame);
+    return YOLO2_SUCCESS;
+}
+
 // ---------------------------------------------------------------------------- n host images -> annotated frames as JPEG streams
 
 void y2_anno_jpeg_free(yolo2_hip_ctx *c)
@@ -285,7 +415,7 @@ void y2_anno_jpeg_free(yolo2_hip_ctx *c)
     j.cap_rgb = j.cap_work = j.cap_out = j.cap_frames = 0;
 }
 
-static int anno_jpeg_ensure(yolo2_hip_ctx *c, size_t cap_rgb, size_t cap_work, size_t cap_out, size_t frames)
+int y2_anno_jpeg_ensure(yolo2_hip_ctx *c, size_t cap_rgb, size_t cap_work, size_t cap_out, size_t frames)
 {
     Y2JpegBufs &j = c->jpeg;
     if (j.e_sizes[0] && j.cap_rgb >= cap_rgb && j.cap_work >= cap_work && j.cap_out >= cap_out && j.cap_frames >= frames) return YOLO2_SUCCESS;
@@ -361,7 +491,7 @@ extern "C" int yolo2_hip_annotate_images_pix_jpeg_host(yolo2_hip_ctx *c, const u
         cap_out = std::max(cap_out, plans[(size_t)k].out_bytes);
     }
     HIP_TRY(hipSetDevice(c->device), YOLO2_INIT_ERROR);
-    if ((rc = anno_ensure(c, cap_in, 0)) || (rc = anno_jpeg_ensure(c, cap_rgb, cap_work, std::max(cap_out, (size_t)1), (size_t)batch))) return rc;
+    if ((rc = y2_anno_ensure(c, cap_in, 0)) || (rc = y2_anno_jpeg_ensure(c, cap_rgb, cap_work, std::max(cap_out, (size_t)1), (size_t)batch))) return rc;
     Y2AnnoBufs &A = c->anno;
     Y2JpegBufs &J = c->jpeg;
     auto cleanup = [&]() { (void)hipDeviceSynchronize(); };

@@ -180,7 +180,7 @@ static void pipe_free(PipeBufs &p)
 
 // need_hout: the pinned mirror of the region tensor (the entries that return region tensors; the images -> detections entry
 // downloads records instead and skips these 2 x 9 MB of pinned memory, which cost ~10 ms each to allocate)
-static int pipe_ensure(PipeBufs &p, size_t host_in, size_t dev_in, int batch, bool need_hout = true)
+int y2_pipe_ensure(PipeBufs &p, size_t host_in, size_t dev_in, int batch, bool need_hout = true)
 {
     if (p.s_in && p.host_in >= host_in && p.dev_in >= dev_in && p.batch >= batch && (!need_hout || p.hout[0])) return YOLO2_SUCCESS;
     need_hout = need_hout || p.hout[0];
@@ -237,6 +237,7 @@ extern "C" void yolo2_hip_destroy(yolo2_hip_ctx *c)
     pipe_free(c->pipe);
     y2_anno_free(c);
     y2_anno_jpeg_free(c);
+    y2_loop_free(c);
     y2_f16_plan_free(c);
     y2_destroy_lanes(c);
     y2_free_activations(c);
@@ -312,7 +313,7 @@ extern "C" int yolo2_hip_layer_times_ms(yolo2_hip_ctx *c, float *ms32)
 
 // channels: bytes per pixel = LetterboxArgs::ch.  1 and 3 are interleaved byte channels; 2 marks a packed YUYV 4:2:2 frame and is
 // accepted from the _pix entries only (yuyv_ok): on the u8 entries, whose callers pass a channel count, it stays an error.
-static int letterbox_args(int w, int h, int channels, int net_w, int net_h, LetterboxArgs &a, bool yuyv_ok = false)
+int y2_letterbox_args(int w, int h, int channels, int net_w, int net_h, LetterboxArgs &a, bool yuyv_ok = false)
 {
     if (w <= 0 || h <= 0 || net_w <= 1 || net_h <= 1 || (channels != 1 && channels != 3 && !(channels == 2 && yuyv_ok)))
         return fail(YOLO2_ERROR, "letterbox: bad image geometry %dx%dx%d -> %dx%d", w, h, channels, net_w, net_h);
@@ -337,7 +338,7 @@ extern "C" int yolo2_hip_letterbox_u8(uint64_t image_dev, int w, int h, int chan
 {
     if (!image_dev || !frame_dev) return fail(YOLO2_ERROR, "null buffer address");
     LetterboxArgs a;
-    int rc = letterbox_args(w, h, channels, net_w, net_h, a);
+    int rc = y2_letterbox_args(w, h, channels, net_w, net_h, a);
     if (rc) return rc;
     hipLaunchKernelGGL(k_letterbox_u8, dim3(blocks_for((long)3 * net_w * net_h, 256)), dim3(256), 0, (hipStream_t)stream,
                        (const uint8_t *)(uintptr_t)image_dev, (float *)(uintptr_t)frame_dev, a);
@@ -346,7 +347,7 @@ extern "C" int yolo2_hip_letterbox_u8(uint64_t image_dev, int w, int h, int chan
 }
 
 // pixfmt -> bytes per pixel (LetterboxArgs::ch) for the _pix entries; 0 and an error for anything else
-static int pix_channels(int pixfmt)
+int y2_pix_channels(int pixfmt)
 {
     if (pixfmt == YOLO2_PIX_GREY8) return 1;
     if (pixfmt == YOLO2_PIX_RGB24) return 3;
@@ -358,13 +359,13 @@ static int pix_channels(int pixfmt)
 extern "C" int yolo2_hip_letterbox_pix(uint64_t image_dev, int w, int h, int pixfmt, uint64_t frame_dev, int net_w, int net_h,
                                        void *stream)
 {
-    const int ch = pix_channels(pixfmt);
+    const int ch = y2_pix_channels(pixfmt);
     if (!ch) return YOLO2_ERROR;
     if (ch != 2) return yolo2_hip_letterbox_u8(image_dev, w, h, ch, frame_dev, net_w, net_h, stream);
     if (!image_dev || !frame_dev) return fail(YOLO2_ERROR, "null buffer address");
     if (image_dev & 3) return fail(YOLO2_ERROR, "letterbox: a YUYV frame starts on a 4-byte boundary");   // (LbYuyv loads pixel pairs)
     LetterboxArgs a;
-    int rc = letterbox_args(w, h, ch, net_w, net_h, a, true);
+    int rc = y2_letterbox_args(w, h, ch, net_w, net_h, a, true);
     if (rc) return rc;
     hipLaunchKernelGGL(k_letterbox_yuyv, dim3(blocks_for((long)3 * net_w * net_h, 256)), dim3(256), 0, (hipStream_t)stream,
                        (const uint8_t *)(uintptr_t)image_dev, (float *)(uintptr_t)frame_dev, a);
@@ -373,7 +374,7 @@ extern "C" int yolo2_hip_letterbox_pix(uint64_t image_dev, int w, int h, int pix
 }
 
 // the chunk letterbox of either kind of staging buffer (pix: YUYV frames, table items with ch == 2)
-static void launch_letterbox_batch(bool yuyv, const uint8_t *dbytes, float *din, int batch, hipStream_t st)
+void y2_launch_letterbox_batch(bool yuyv, const uint8_t *dbytes, float *din, int batch, hipStream_t st)
 {
     const dim3 grid(blocks_for((long)YOLO2_FRAME_ELEMS, 256), batch);
     if (yuyv) hipLaunchKernelGGL(k_letterbox_yuyv_batch, grid, dim3(256), 0, st, dbytes, din, (int)YOLO2_FRAME_ELEMS);
@@ -403,7 +404,7 @@ static int run_images_i16_host(yolo2_hip_ctx *c, const uint8_t *const *images, c
         for (int i = k * batch; i < k * batch + in_chunk(k); ++i) {
             LetterboxArgs a;
             if (!images[i]) return fail(YOLO2_ERROR, "null image %d", i);
-            const int rc = letterbox_args(widths[i], heights[i], channels, 416, 416, a, pix);
+            const int rc = y2_letterbox_args(widths[i], heights[i], channels, 416, 416, a, pix);
             if (rc) return rc;
             sum += padded((size_t)widths[i] * heights[i] * channels);
         }
@@ -414,7 +415,7 @@ static int run_images_i16_host(yolo2_hip_ctx *c, const uint8_t *const *images, c
         if (rc) return rc;
     }
     const size_t rbytes = (size_t)batch * YOLO2_REGION_ELEMS * sizeof(int16_t);
-    int rc = pipe_ensure(c->pipe, cap, cap, batch);
+    int rc = y2_pipe_ensure(c->pipe, cap, cap, batch);
     if (rc) return rc;
     PipeBufs &P = c->pipe;
     uint8_t *hin[2] = {P.hin[0].get(), P.hin[1].get()}, *dbytes[2] = {P.dbytes[0].get(), P.dbytes[1].get()};
@@ -446,13 +447,13 @@ static int run_images_i16_host(yolo2_hip_ctx *c, const uint8_t *const *images, c
         for (int f = 0; f < batch && rc == YOLO2_SUCCESS; ++f) {   // a partial last chunk repeats its last image
             const int i = std::min(f, nf - 1);
             items[f].off = offs[(size_t)i];
-            rc = letterbox_args(widths[first + i], heights[first + i], channels, 416, 416, items[f].a, pix);
+            rc = y2_letterbox_args(widths[first + i], heights[first + i], channels, 416, 416, items[f].a, pix);
         }
         if (rc) break;
         Y2_TRY(hipMemcpyAsync(dbytes[b], hin[b], off, hipMemcpyHostToDevice, s_in), YOLO2_DMA_ERROR);
         Y2_TRY(hipEventRecord(e_in[b], s_in), YOLO2_ERROR);
         Y2_TRY(hipStreamWaitEvent(s_run, e_in[b], 0), YOLO2_ERROR);
-        launch_letterbox_batch(channels == 2, dbytes[b], din[b], batch, s_run);
+        y2_launch_letterbox_batch(channels == 2, dbytes[b], din[b], batch, s_run);
         Y2_TRY(hipGetLastError(), YOLO2_ERROR);
         rc = yolo2_hip_run_batch_int16(c, (uint64_t)(uintptr_t)din[b], batch, (uint64_t)(uintptr_t)dout[b], &q, s_run);
         if (rc) break;
@@ -480,7 +481,7 @@ extern "C" int yolo2_hip_run_images_u8_host(yolo2_hip_ctx *c, const uint8_t *con
 extern "C" int yolo2_hip_run_images_pix_host(yolo2_hip_ctx *c, const uint8_t *const *images, const int *widths, const int *heights,
                                              int pixfmt, int n, int batch, int16_t *region, int *final_q)
 {
-    const int ch = pix_channels(pixfmt);
+    const int ch = y2_pix_channels(pixfmt);
     return ch ? run_images_i16_host(c, images, widths, heights, ch, true, n, batch, region, final_q) : YOLO2_ERROR;
 }
 
@@ -491,7 +492,7 @@ extern "C" int yolo2_hip_calib_images_pix_host(yolo2_hip_ctx *c, const uint8_t *
                                                int pixfmt, int n, int batch)
 {
     if (!c || !images || !widths || !heights) return fail(YOLO2_ERROR, "null argument");
-    const int channels = pix_channels(pixfmt);
+    const int channels = y2_pix_channels(pixfmt);
     if (!channels) return YOLO2_ERROR;
     if (n <= 0 || batch <= 0 || batch > 1024) return fail(YOLO2_ERROR, "bad image count %d / batch %d", n, batch);
     if (!c->f16_loaded || !c->wf32) return fail(YOLO2_ERROR, "fp32 weights not loaded (yolo2_hip_load_weights_fp32)");
@@ -506,14 +507,14 @@ extern "C" int yolo2_hip_calib_images_pix_host(yolo2_hip_ctx *c, const uint8_t *
         for (int i = k * batch; i < k * batch + in_chunk(k); ++i) {
             LetterboxArgs a;
             if (!images[i]) return fail(YOLO2_ERROR, "null image %d", i);
-            const int rc = letterbox_args(widths[i], heights[i], channels, 416, 416, a, true);
+            const int rc = y2_letterbox_args(widths[i], heights[i], channels, 416, 416, a, true);
             if (rc) return rc;
             sum += padded((size_t)widths[i] * heights[i] * channels);
         }
         cap = std::max(cap, sum);
     }
     HIP_TRY(hipSetDevice(c->device), YOLO2_INIT_ERROR);
-    int rc = pipe_ensure(c->pipe, cap, cap, batch, false);
+    int rc = y2_pipe_ensure(c->pipe, cap, cap, batch, false);
     if (rc) return rc;
     PipeBufs &P = c->pipe;
     uint8_t *const hin = P.hin[0].get(), *const dbytes = P.dbytes[0].get();
@@ -531,10 +532,10 @@ extern "C" int yolo2_hip_calib_images_pix_host(yolo2_hip_ctx *c, const uint8_t *
         for (int f = 0; f < batch; ++f) {
             const int i = std::min(f, nf - 1);
             items[f].off = offs[(size_t)i];
-            if ((rc = letterbox_args(widths[first + i], heights[first + i], channels, 416, 416, items[f].a, true))) return rc;
+            if ((rc = y2_letterbox_args(widths[first + i], heights[first + i], channels, 416, 416, items[f].a, true))) return rc;
         }
         HIP_TRY(hipMemcpyAsync(dbytes, hin, off, hipMemcpyHostToDevice, P.s_run), YOLO2_DMA_ERROR);
-        launch_letterbox_batch(channels == 2, dbytes, P.din[0].get(), batch, P.s_run);
+        y2_launch_letterbox_batch(channels == 2, dbytes, P.din[0].get(), batch, P.s_run);
         HIP_TRY(hipGetLastError(), YOLO2_ERROR);
         if ((rc = y2_calib_frames(c, (uint64_t)(uintptr_t)P.din[0].get(), batch, nf, P.s_run))) return rc;   // (synchronises: hin is free again)
     }
@@ -549,7 +550,7 @@ extern "C" int yolo2_hip_calib_images_pix_host(yolo2_hip_ctx *c, const uint8_t *
 // (32 bytes each) and the per-frame counts come back.  Upload of chunk k+1, kernels of chunk k and download of chunk k-1 overlap on
 // three HIP streams.  Replaces the loop of the reference's streaming app (linux_app/src/main.c:878-1288), which runs
 // yolo2_run_inference and the host post-processing frame by frame.
-static int pipe_ensure_post(yolo2_hip_ctx *c, int batch, int cap)
+int y2_pipe_ensure_post(yolo2_hip_ctx *c, int batch, int cap)
 {
     PipeBufs &p = c->pipe;
     if (p.post_batch >= batch && p.post_cap >= cap) return YOLO2_SUCCESS;
@@ -566,6 +567,42 @@ static int pipe_ensure_post(yolo2_hip_ctx *c, int batch, int cap)
         }
     }
     p.post_batch = batch; p.post_cap = cap;
+    return YOLO2_SUCCESS;
+}
+
+// (y2_internal.hpp) The int16 network of the chunk in buffer set b, for the entries that keep the region tensor in HBM: chunk letterbox
+// on s_run (which already waits for the chunk's upload), then the network.  A chunk's lanes are NOT joined back into one stream here:
+// consecutive chunks are independent, every lane owns its activations and its stream keeps its chunks in order, so lane i starts chunk
+// k + 1 the moment it has finished chunk k (and the chunk's letterbox is done) instead of waiting for the slowest lane - the fork / join
+// per 64 frames and the lanes' end spread (0.3 - 0.7 ms of a 20 ms step in the bench loop) do not exist in a stream of chunks.  Only what
+// needs the whole region tensor waits for all of them: `done` receives the events to wait for.
+int y2_pipe_enqueue_i16(yolo2_hip_ctx *c, int b, bool yuyv, int batch, int *q, std::vector<hipEvent_t> *done)
+{
+    PipeBufs &P = c->pipe;
+    done->clear();
+    y2_launch_letterbox_batch(yuyv, P.dbytes[b].get(), P.din[b].get(), batch, P.s_run);
+    HIP_TRY(hipGetLastError(), YOLO2_ERROR);
+    bool own_streams = c->laned && (int)c->lanes.size() <= 8;
+    if (own_streams) for (yolo2_hip_ctx *l : c->lanes) own_streams = own_streams && l->lane_stream;
+    HIP_TRY(hipEventRecord(P.e_run[b], P.s_run), YOLO2_ERROR);            // (here: the letterboxed frames are ready)
+    if (own_streams) {
+        for (size_t i = 0; i < c->lanes.size(); ++i) {
+            yolo2_hip_ctx *l = c->lanes[i];
+            const uint64_t first = (uint64_t)c->lane_first[i];
+            if (!P.e_lane[b][i]) HIP_TRY(hipEventCreateWithFlags(&P.e_lane[b][i], hipEventDisableTiming), YOLO2_ERROR);
+            HIP_TRY(hipStreamWaitEvent(l->lane_stream, P.e_run[b], 0), YOLO2_ERROR);
+            const int rc = yolo2_hip_run_batch_int16(l, (uint64_t)(uintptr_t)(P.din[b].get() + first * YOLO2_FRAME_ELEMS), l->batch,
+                                                     (uint64_t)(uintptr_t)(P.dout[b].get() + first * YOLO2_REGION_ELEMS), q, l->lane_stream);
+            if (rc) return rc;
+            HIP_TRY(hipEventRecord(P.e_lane[b][i], l->lane_stream), YOLO2_ERROR);
+            done->push_back(P.e_lane[b][i]);
+        }
+    } else {
+        const int rc = yolo2_hip_run_batch_int16(c, (uint64_t)(uintptr_t)P.din[b].get(), batch, (uint64_t)(uintptr_t)P.dout[b].get(), q, P.s_run);
+        if (rc) return rc;
+        HIP_TRY(hipEventRecord(P.e_run[b], P.s_run), YOLO2_ERROR);
+        done->push_back(P.e_run[b]);
+    }
     return YOLO2_SUCCESS;
 }
 
@@ -590,7 +627,7 @@ static int run_images_i16_dets(yolo2_hip_ctx *c, const uint8_t *const *images, c
         for (int i = k * batch; i < k * batch + in_chunk(k); ++i) {
             LetterboxArgs a;
             if (!images[i]) return fail(YOLO2_ERROR, "null image %d", i);
-            const int rc = letterbox_args(widths[i], heights[i], channels, 416, 416, a, pix);
+            const int rc = y2_letterbox_args(widths[i], heights[i], channels, 416, 416, a, pix);
             if (rc) return rc;
             sum += padded((size_t)widths[i] * heights[i] * channels);
         }
@@ -600,8 +637,8 @@ static int run_images_i16_dets(yolo2_hip_ctx *c, const uint8_t *const *images, c
         const int rc = yolo2_hip_set_batch(c, batch);
         if (rc) return rc;
     }
-    int rc = pipe_ensure(c->pipe, cap_bytes, cap_bytes, batch, false);
-    if (rc == YOLO2_SUCCESS) rc = pipe_ensure_post(c, batch, cap);
+    int rc = y2_pipe_ensure(c->pipe, cap_bytes, cap_bytes, batch, false);
+    if (rc == YOLO2_SUCCESS) rc = y2_pipe_ensure_post(c, batch, cap);
     if (rc) return rc;
     PipeBufs &P = c->pipe;
     const size_t gbytes = y2_post_geom_bytes();
@@ -621,6 +658,7 @@ static int run_images_i16_dets(yolo2_hip_ctx *c, const uint8_t *const *images, c
     int q = 0;
     std::vector<size_t> offs((size_t)batch);
     std::vector<int> cw((size_t)batch), chh((size_t)batch);
+    std::vector<hipEvent_t> net_done;
     for (int k = 0; k < chunks && rc == YOLO2_SUCCESS; ++k) {
         const int b = k & 1, nf = in_chunk(k), first = k * batch;
         if (k >= 2) drain(k - 2);   // buffer set b is free again once chunk k-2 has left it
@@ -636,7 +674,7 @@ static int run_images_i16_dets(yolo2_hip_ctx *c, const uint8_t *const *images, c
             const int i = std::min(f, nf - 1);
             cw[(size_t)f] = widths[first + i]; chh[(size_t)f] = heights[first + i];
             items[f].off = offs[(size_t)i];
-            if ((rc = letterbox_args(widths[first + i], heights[first + i], channels, 416, 416, items[f].a, pix))) break;
+            if ((rc = y2_letterbox_args(widths[first + i], heights[first + i], channels, 416, 416, items[f].a, pix))) break;
         }
         if (rc) break;
         if ((rc = y2_post_fill_geom(P.hgeom[b].get(), cw.data(), chh.data(), batch))) break;
@@ -644,35 +682,8 @@ static int run_images_i16_dets(yolo2_hip_ctx *c, const uint8_t *const *images, c
         Y2_TRY(hipMemcpyAsync(P.post[b].geom.get(), P.hgeom[b].get(), (size_t)batch * gbytes, hipMemcpyHostToDevice, P.s_in), YOLO2_DMA_ERROR);
         Y2_TRY(hipEventRecord(P.e_in[b], P.s_in), YOLO2_ERROR);
         Y2_TRY(hipStreamWaitEvent(P.s_run, P.e_in[b], 0), YOLO2_ERROR);
-        launch_letterbox_batch(channels == 2, P.dbytes[b].get(), P.din[b].get(), batch, P.s_run);
-        Y2_TRY(hipGetLastError(), YOLO2_ERROR);
-        // The network.  A chunk's lanes are NOT joined back into one stream here: consecutive chunks are independent, every lane
-        // owns its activations and its stream keeps its chunks in order, so lane i starts chunk k + 1 the moment it has finished
-        // chunk k (and the chunk's letterbox is done) instead of waiting for the slowest lane - the fork / join per 64 frames and the
-        // lanes' end spread (0.3 - 0.7 ms of a 20 ms step in the bench loop) do not exist in a stream of chunks.  Only the tail,
-        // which needs the whole region tensor, waits for all of them, on the download stream.
-        bool own_streams = c->laned && (int)c->lanes.size() <= 8;
-        if (own_streams) for (yolo2_hip_ctx *l : c->lanes) own_streams = own_streams && l->lane_stream;
-        Y2_TRY(hipEventRecord(P.e_run[b], P.s_run), YOLO2_ERROR);            // (here: the letterboxed frames are ready)
-        if (own_streams) {
-            for (size_t i = 0; i < c->lanes.size() && rc == YOLO2_SUCCESS; ++i) {
-                yolo2_hip_ctx *l = c->lanes[i];
-                const uint64_t first = (uint64_t)c->lane_first[i];
-                if (!P.e_lane[b][i]) Y2_TRY(hipEventCreateWithFlags(&P.e_lane[b][i], hipEventDisableTiming), YOLO2_ERROR);
-                Y2_TRY(hipStreamWaitEvent(l->lane_stream, P.e_run[b], 0), YOLO2_ERROR);
-                rc = yolo2_hip_run_batch_int16(l, (uint64_t)(uintptr_t)(P.din[b].get() + first * YOLO2_FRAME_ELEMS), l->batch,
-                                               (uint64_t)(uintptr_t)(P.dout[b].get() + first * YOLO2_REGION_ELEMS), &q, l->lane_stream);
-                if (rc) break;
-                Y2_TRY(hipEventRecord(P.e_lane[b][i], l->lane_stream), YOLO2_ERROR);
-                Y2_TRY(hipStreamWaitEvent(P.s_out, P.e_lane[b][i], 0), YOLO2_ERROR);
-            }
-        } else {
-            rc = yolo2_hip_run_batch_int16(c, (uint64_t)(uintptr_t)P.din[b].get(), batch, (uint64_t)(uintptr_t)P.dout[b].get(), &q, P.s_run);
-            if (rc) break;
-            Y2_TRY(hipEventRecord(P.e_run[b], P.s_run), YOLO2_ERROR);
-            Y2_TRY(hipStreamWaitEvent(P.s_out, P.e_run[b], 0), YOLO2_ERROR);
-        }
-        if (rc) break;
+        if ((rc = y2_pipe_enqueue_i16(c, b, channels == 2, batch, &q, &net_done))) break;     // letterbox + network; lanes are not joined
+        for (hipEvent_t e : net_done) Y2_TRY(hipStreamWaitEvent(P.s_out, e, 0), YOLO2_ERROR);
         // the step after the path, on the device that produced the tensor, straight from HBM - on the download stream, so that the
         // next chunk's letterbox and network need not wait for it (the tail is 64 workgroups for 0.7 ms: latency, not work)
         rc = y2_post_enqueue_int16(c->device, P.dout[b].get(), batch, q, thresh, nms, cap, best_only, app_tail, &P.post[b], P.s_out);
@@ -701,7 +712,7 @@ extern "C" int yolo2_hip_run_images_pix_dets(yolo2_hip_ctx *c, const uint8_t *co
                                              int pixfmt, int n, int batch, float thresh, float nms, int flags, yolo2_hip_det *dets,
                                              int cap_per_frame, int *counts, int *final_q)
 {
-    const int ch = pix_channels(pixfmt);
+    const int ch = y2_pix_channels(pixfmt);
     return ch ? run_images_i16_dets(c, images, widths, heights, ch, true, n, batch, thresh, nms, flags, dets, cap_per_frame, counts, final_q)
               : YOLO2_ERROR;
 }
@@ -713,7 +724,7 @@ extern "C" int yolo2_hip_run_images_pix_dets(yolo2_hip_ctx *c, const uint8_t *co
 // tensor is fp32 and the tail is y2_post_enqueue_f32.  Under f16_no_mfma0 the chunk is letterboxed into frames first and the frame
 // path's table runs (the reference route the tests compare with).
 
-static int pipe_ensure_regf(PipeBufs &p, int batch, bool need_host)
+int y2_pipe_ensure_regf(PipeBufs &p, int batch, bool need_host)
 {
     if (p.regf_batch >= batch && (!need_host || p.hregf[0])) return YOLO2_SUCCESS;
     need_host = need_host || p.hregf[0];
@@ -734,7 +745,7 @@ static int pipe_ensure_regf(PipeBufs &p, int batch, bool need_host)
 // thread's memcpy would be the slowest stage of the pipeline.
 static constexpr int kStageThreads = 4;
 
-static void stage_images(uint8_t *dst, const uint8_t *const *images, const size_t *offs, const size_t *bytes, int nf)
+void y2_stage_images(uint8_t *dst, const uint8_t *const *images, const size_t *offs, const size_t *bytes, int nf)
 {
     size_t total = 0;
     for (int i = 0; i < nf; ++i) total += bytes[i];
@@ -752,6 +763,24 @@ static void stage_images(uint8_t *dst, const uint8_t *const *images, const size_
     for (int t = 1; t < nt; ++t) th.emplace_back(part, t);
     part(0);
     for (auto &t : th) t.join();
+}
+
+// (y2_internal.hpp) The fp16 / split pass of the chunk in buffer set b on s_run, into dregf[b]: layers 0 + 1 from the chunk's bytes where
+// the pass fuses them, else chunk letterbox + the frame path.  Records e_run[b] behind it.
+int y2_pipe_enqueue_f16(yolo2_hip_ctx *c, yolo2_hip_ctx *run, bool fused, int b, bool yuyv, int batch)
+{
+    PipeBufs &P = c->pipe;
+    int rc;
+    if (fused) {
+        rc = y2_f16_run_images(run, P.dbytes[b].get(), yuyv, batch, P.dregf[b].get(), P.s_run);
+    } else {
+        y2_launch_letterbox_batch(yuyv, P.dbytes[b].get(), P.din[b].get(), batch, P.s_run);
+        HIP_TRY(hipGetLastError(), YOLO2_ERROR);
+        rc = yolo2_hip_run_batch_fp16(run, (uint64_t)(uintptr_t)P.din[b].get(), batch, (uint64_t)(uintptr_t)P.dregf[b].get(), P.s_run);
+    }
+    if (rc) return rc;
+    HIP_TRY(hipEventRecord(P.e_run[b], P.s_run), YOLO2_ERROR);
+    return YOLO2_SUCCESS;
 }
 
 // dets == nullptr: region tensors to region_host; otherwise the records (the int16 dets entry's contract)
@@ -779,15 +808,15 @@ static int run_images_f16(yolo2_hip_ctx *c, int split, const uint8_t *const *ima
         for (int i = k * batch; i < k * batch + in_chunk(k); ++i) {
             LetterboxArgs a;
             if (!images[i]) return fail(YOLO2_ERROR, "null image %d", i);
-            if ((rc = letterbox_args(widths[i], heights[i], channels, 416, 416, a, pix))) return rc;
+            if ((rc = y2_letterbox_args(widths[i], heights[i], channels, 416, 416, a, pix))) return rc;
             sum += padded((size_t)widths[i] * heights[i] * channels);
         }
         cap_bytes = std::max(cap_bytes, sum);
     }
     const bool fused = y2_f16_images_fused(run);
-    if ((rc = pipe_ensure(c->pipe, cap_bytes, cap_bytes, batch, false))) return rc;      // (din: the frames of the f16_no_mfma0 route)
-    if ((rc = pipe_ensure_regf(c->pipe, batch, !want_dets))) return rc;
-    if (want_dets && (rc = pipe_ensure_post(c, batch, cap))) return rc;
+    if ((rc = y2_pipe_ensure(c->pipe, cap_bytes, cap_bytes, batch, false))) return rc;      // (din: the frames of the f16_no_mfma0 route)
+    if ((rc = y2_pipe_ensure_regf(c->pipe, batch, !want_dets))) return rc;
+    if (want_dets && (rc = y2_pipe_ensure_post(c, batch, cap))) return rc;
     PipeBufs &P = c->pipe;
     const size_t gbytes = y2_post_geom_bytes(), rbytes = (size_t)batch * YOLO2_REGION_ELEMS * sizeof(float);
     auto cleanup = [&]() { (void)hipDeviceSynchronize(); };
@@ -818,13 +847,13 @@ static int run_images_f16(yolo2_hip_ctx *c, int split, const uint8_t *const *ima
             offs[(size_t)i] = off;
             off += padded(sizes[(size_t)i]);
         }
-        stage_images(P.hin[b].get(), images + first, offs.data(), sizes.data(), nf);
+        y2_stage_images(P.hin[b].get(), images + first, offs.data(), sizes.data(), nf);
         LetterboxItem *items = reinterpret_cast<LetterboxItem *>(P.hin[b].get());
         for (int f = 0; f < batch; ++f) {   // a partial last chunk repeats its last image
             const int i = std::min(f, nf - 1);
             cw[(size_t)f] = widths[first + i]; chh[(size_t)f] = heights[first + i];
             items[f].off = offs[(size_t)i];
-            if ((rc = letterbox_args(widths[first + i], heights[first + i], channels, 416, 416, items[f].a, pix))) break;
+            if ((rc = y2_letterbox_args(widths[first + i], heights[first + i], channels, 416, 416, items[f].a, pix))) break;
         }
         if (rc) break;
         if (want_dets && (rc = y2_post_fill_geom(P.hgeom[b].get(), cw.data(), chh.data(), batch))) break;
@@ -832,15 +861,7 @@ static int run_images_f16(yolo2_hip_ctx *c, int split, const uint8_t *const *ima
         if (want_dets) Y2_TRY(hipMemcpyAsync(P.post[b].geom.get(), P.hgeom[b].get(), (size_t)batch * gbytes, hipMemcpyHostToDevice, P.s_in), YOLO2_DMA_ERROR);
         Y2_TRY(hipEventRecord(P.e_in[b], P.s_in), YOLO2_ERROR);
         Y2_TRY(hipStreamWaitEvent(P.s_run, P.e_in[b], 0), YOLO2_ERROR);
-        if (fused) {
-            rc = y2_f16_run_images(run, P.dbytes[b].get(), yuyv, batch, P.dregf[b].get(), P.s_run);
-        } else {
-            launch_letterbox_batch(yuyv, P.dbytes[b].get(), P.din[b].get(), batch, P.s_run);
-            Y2_TRY(hipGetLastError(), YOLO2_ERROR);
-            rc = yolo2_hip_run_batch_fp16(run, (uint64_t)(uintptr_t)P.din[b].get(), batch, (uint64_t)(uintptr_t)P.dregf[b].get(), P.s_run);
-        }
-        if (rc) break;
-        Y2_TRY(hipEventRecord(P.e_run[b], P.s_run), YOLO2_ERROR);
+        if ((rc = y2_pipe_enqueue_f16(c, run, fused, b, yuyv, batch))) break;
         Y2_TRY(hipStreamWaitEvent(P.s_out, P.e_run[b], 0), YOLO2_ERROR);
         if (want_dets) {   // the tail on the download stream, straight from HBM (see yolo2_hip_run_images_u8_dets)
             if ((rc = y2_post_enqueue_f32(P.dregf[b].get(), batch, thresh, nms, cap, best_only, app_tail, &P.post[b], P.s_out))) break;
@@ -873,7 +894,7 @@ extern "C" int yolo2_hip_run_images_pix_f16_host(yolo2_hip_ctx *c, int split, co
                                                  const int *heights, int pixfmt, int n, int batch, float *region_host)
 {
     if (!c || !images || !widths || !heights || !region_host) return fail(YOLO2_ERROR, "null argument");
-    const int ch = pix_channels(pixfmt);
+    const int ch = y2_pix_channels(pixfmt);
     return ch ? run_images_f16(c, split, images, widths, heights, ch, true, n, batch, region_host, 0.f, 0.f, 0, nullptr, 0, nullptr) : YOLO2_ERROR;
 }
 
@@ -890,7 +911,7 @@ extern "C" int yolo2_hip_run_images_pix_dets_f16(yolo2_hip_ctx *c, int split, co
                                                  yolo2_hip_det *dets, int cap_per_frame, int *counts)
 {
     if (!c || !images || !widths || !heights || !dets || !counts) return fail(YOLO2_ERROR, "null argument");
-    const int ch = pix_channels(pixfmt);
+    const int ch = y2_pix_channels(pixfmt);
     return ch ? run_images_f16(c, split, images, widths, heights, ch, true, n, batch, nullptr, thresh, nms, flags, dets, cap_per_frame, counts)
               : YOLO2_ERROR;
 }
@@ -911,7 +932,7 @@ extern "C" int yolo2_hip_run_frames_int16(yolo2_hip_ctx *c, const float *frames,
         if (rc) return rc;
     }
     const size_t fbytes = (size_t)batch * YOLO2_FRAME_ELEMS * sizeof(float), rbytes = (size_t)batch * YOLO2_REGION_ELEMS * sizeof(int16_t);
-    int rc = pipe_ensure(c->pipe, fbytes, 0, batch);
+    int rc = y2_pipe_ensure(c->pipe, fbytes, 0, batch);
     if (rc) return rc;
     PipeBufs &P = c->pipe;
     float *hin[2] = {(float *)P.hin[0].get(), (float *)P.hin[1].get()}, *din[2] = {P.din[0].get(), P.din[1].get()};

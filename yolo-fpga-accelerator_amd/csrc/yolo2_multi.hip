@@ -691,6 +691,37 @@ extern "C" int yolo2_hip_multi_annotate_images_pix_host(yolo2_hip_multi *m, cons
     });
 }
 
+// the camera loop as one call (yolo2_hip_loop_images_pix), shard i on device i
+extern "C" int yolo2_hip_multi_loop_images_pix(yolo2_hip_multi *m, int precision, const uint8_t *const *images, const int *widths,
+                                               const int *heights, int pixfmt, int n, int batch_per_device, float thresh, float nms, int flags,
+                                               yolo2_hip_det *dets, int cap_per_frame, int *counts, int *final_q, const char *const *labels,
+                                               int n_labels, int out_format, int quality, uint8_t *const *out, const size_t *caps, size_t *sizes,
+                                               int *drawn)
+{
+    if (!m) return mfail(YOLO2_ERROR, "loop: null argument");
+    // the whole call is looked at before any shard starts
+    const int rc = y2_loop_check(precision, images, widths, heights, pixfmt, n, batch_per_device, thresh, flags, dets, cap_per_frame, counts, n_labels,
+                                 out_format, quality, out, caps, sizes);
+    if (rc) return rc;
+    std::vector<int> qs(m->ctx.size(), 0);
+    const int r = multi_run(m, n, [&](yolo2_hip_ctx *c, int lo, int hi) {
+        int qq = 0;
+        for (int f = lo; f < hi; ++f) counts[f] = 0;   // (a shard that is refused leaves no counts behind for the renumbering below)
+        const int r1 = yolo2_hip_loop_images_pix(c, precision, images + lo, widths + lo, heights + lo, pixfmt, hi - lo, std::min(batch_per_device, hi - lo),
+                                                 thresh, nms, flags, dets + (size_t)lo * cap_per_frame, cap_per_frame, counts + lo,
+                                                 &qq, labels, n_labels, out_format, quality, out + lo, caps + lo, sizes + lo,
+                                                 drawn ? drawn + lo : nullptr);
+        // records carry global frame indices (also where a shard returned an error with its frames complete)
+        for (int f = lo; f < hi; ++f)
+            for (int k = 0, cnt = std::min(std::max(counts[f], 0), cap_per_frame); k < cnt; ++k) dets[(size_t)f * cap_per_frame + k].frame = f;
+        for (size_t i = 0; i < m->ctx.size(); ++i)
+            if (m->ctx[i] == c) qs[i] = qq;
+        return r1;
+    });
+    if (final_q && precision == YOLO2_LOOP_INT16) *final_q = qs[0];   // (every device holds the same weights and Q tables; int16 only)
+    return r;
+}
+
 // annotated frames as JPEG streams, shard i painted and encoded by device i
 extern "C" int yolo2_hip_multi_annotate_images_pix_jpeg_host(yolo2_hip_multi *m, const uint8_t *const *images, const int *widths,
                                                              const int *heights, int pixfmt, int n, int batch_per_device,

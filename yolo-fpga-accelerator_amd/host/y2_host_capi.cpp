@@ -5,6 +5,7 @@
 #include <exception>
 #include <string>
 
+#include "../csrc/draw_list.hpp"
 #include "y2_host.hpp"
 
 using namespace y2h;
@@ -146,6 +147,32 @@ double y2h_plain_box_frame(const uint8_t *bytes, int w, int h, int yuyv, const v
 }
 
 int y2h_draw_font(char *chars, uint64_t *words) { return draw_font(chars, words); }
+
+// The shared formatter of csrc/draw_list.hpp (what k_draw_items runs on the device): the glyph indices of
+// snprintf(char[128], "%s %.2f", label, prob); label NULL: "class<cls>".  glyphs [128], zero behind the text.  Returns the length, or
+// -1 for a prob the formatter does not print (not finite, or 2^23 and more).
+int y2h_draw_text(const char *label, int cls, float prob, uint8_t *glyphs)
+{
+    uint8_t entry[y2d::kDrawLabelStride];
+    y2d::draw_label_entry(label, entry);
+    return y2d::draw_text_glyphs(label ? entry + 1 : nullptr, label ? (int)entry[0] : 0, cls, prob, glyphs);
+}
+// One yolo2_hip_det record -> its DrawItem (y2h_draw_item_size() bytes at `item`), by the device's route: a label table made of
+// `labels`, then y2d::draw_item_from_record.  1: drawn; 0: not drawn (item untouched); -1: it would be drawn but its prob is not printable.
+size_t y2h_draw_item_size() { return sizeof(y2d::DrawItem); }
+int y2h_draw_item(const void *det, int w, int h, float thresh, const char *const *labels, int n_labels, void *item)
+{
+    y2d::DrawDet d;
+    memcpy(&d, det, sizeof(d));
+    std::string table((size_t)std::max(n_labels, 0) * y2d::kDrawLabelStride, '\0');
+    for (int i = 0; labels && i < n_labels; ++i) y2d::draw_label_entry(labels[i], reinterpret_cast<uint8_t *>(&table[0]) + (size_t)i * y2d::kDrawLabelStride);
+    y2d::DrawItem it;
+    memset(&it, 0, sizeof(it));
+    bool unprintable = false;
+    const bool drawn = y2d::draw_item_from_record(d, w, h, thresh, labels ? reinterpret_cast<const uint8_t *>(table.data()) : nullptr, n_labels, &it, &unprintable);
+    if (drawn) memcpy(item, &it, sizeof(it));
+    return drawn ? 1 : (unprintable ? -1 : 0);
+}
 
 // write_jpg_rgb24 (y2_jpeg.cpp): returns the stream's length (bytes below cap are stored), or -1 (y2h_last_error)
 long y2h_write_jpg_rgb24(const uint8_t *rgb, int w, int h, int quality, uint8_t *out, size_t cap)

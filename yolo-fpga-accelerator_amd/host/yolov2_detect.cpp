@@ -64,6 +64,7 @@ struct AppConfig {
     bool annotate_gpu = false;   // --annotate-gpu: annotated frames come from yolo2_hip_annotate_images_pix_host, in the reference's look
     std::string annotated_format;   // --annotated-format jpg: they are encoded on the GPU too (yolo2_hip_annotate_images_pix_jpeg_host); "" / ppm: PPM
     int jpeg_quality = 80;          // --jpeg-quality, the reference streamer's default
+    bool loop_gpu = false;          // --loop-gpu: records and annotated frames from ONE accelerator call per chunk (yolo2_hip_loop_images_pix)
     int video_w = 640, video_h = 480;
     int video_pixfmt = YOLO2_PIX_RGB24; // --video-pix-fmt: what a --video-raw frame holds (RGB24, or packed YUYV 4:2:2 read by the GPU as it is)
     int max_frames = 0;                // 0 = all
@@ -115,6 +116,8 @@ void print_usage(const char *prog)
         "  --annotated-format <ppm|jpg>  with --annotate-gpu: jpg writes frame_NNNNNN.jpg, the reference's MJPEG stream of the frame,\n"
         "                        encoded on the GPU (yolo2_hip_annotate_images_pix_jpeg_host); default ppm\n"
         "  --jpeg-quality <1..100>  quality of --annotated-format jpg (default 80)\n"
+        "  --loop-gpu            with --annotate-gpu --save-annotated-dir and --post gpu: one accelerator call per chunk makes the records AND\n"
+        "                        the annotated frames from one upload (yolo2_hip_loop_images_pix); same log, JSONL and files\n"
         "  --chunk-batches <n>   Batches per device and accelerator call (default 4)\n"
         "  --decode-threads <n>  Host threads decoding images ahead of the accelerators (default: all cores; one pool feeds every device)\n"
         "  --strict              Stop at the first input that cannot be read or decoded (default: log it, skip the frame, go on)\n"
@@ -173,6 +176,7 @@ AppConfig parse_args(int argc, char **argv)
         else if ((arg == "--jsonl" || arg == "--output-json") && need("")) cfg.jsonl_path = argv[++i];
         else if (arg == "--save-annotated-dir" && need("")) cfg.save_dir = argv[++i];
         else if (arg == "--annotate-gpu") cfg.annotate_gpu = true;
+        else if (arg == "--loop-gpu") cfg.loop_gpu = true;
         else if (arg == "--annotated-format" && need("")) cfg.annotated_format = argv[++i];
         else if (arg == "--jpeg-quality" && need("")) cfg.jpeg_quality = std::atoi(argv[++i]);
         else if (arg == "--chunk-batches" && need("")) cfg.chunk_batches = std::max(1, std::atoi(argv[++i]));
@@ -208,6 +212,11 @@ AppConfig parse_args(int argc, char **argv)
             print_usage(argv[0]);
             std::exit(1);
         } else cfg.input_path = arg;
+    }
+    if (cfg.loop_gpu && !(cfg.annotate_gpu && !cfg.save_dir.empty() && cfg.post == "gpu" && cfg.streaming())) {
+        std::fprintf(stderr, "--loop-gpu joins the detections and the annotated frames of a streaming run: it needs --annotate-gpu, "
+                             "--save-annotated-dir <dir> and --post gpu\n");
+        std::exit(1);
     }
     if (cfg.video_pixfmt == YOLO2_PIX_YUYV && !cfg.video_raw.empty() && (cfg.video_w & 1)) {
         std::fprintf(stderr, "--video-pix-fmt yuyv422 needs an even --video-width, not %d\n", cfg.video_w);
@@ -702,13 +711,42 @@ void run_stream(AppConfig cfg)
                         const int cap = 845;
                         recs.resize((size_t)n * cap);
                         std::vector<int> counts((size_t)n);
-                        const int rc = f16 ? yolo2_hip_run_images_pix_dets_f16(ctx, split, ptrs.data(), ws.data(), hs.data(), pixfmt, n, cfg.batch, cfg.thresh,
-                                                                               cfg.nms, det_flags, recs.data(), cap, counts.data())
-                                           : yolo2_hip_run_images_pix_dets(ctx, ptrs.data(), ws.data(), hs.data(), pixfmt, n, cfg.batch, cfg.thresh, cfg.nms,
-                                                                           det_flags, recs.data(), cap, counts.data(), &q);
-                        if (rc != YOLO2_SUCCESS) throw std::runtime_error(yolo2_hip_last_error());
+                        if (cfg.loop_gpu) {     // records and annotated frames from one call: the frames go up once
+                            ck->annotated.resize((size_t)n);
+                            std::vector<uint8_t *> outs((size_t)n);
+                            std::vector<size_t> caps((size_t)n), sizes((size_t)n);
+                            for (int attempt = 0; attempt < 2; ++attempt) {     // (JPEG: room as below, a second call with the encoder's bound)
+                                for (int f = 0; f < n; ++f) {
+                                    const size_t raw = (size_t)ws[(size_t)f] * hs[(size_t)f] * 3, bound = yolo2_hip_jpeg_bound(ws[(size_t)f], hs[(size_t)f]);
+                                    caps[(size_t)f] = !annotate_jpg ? raw : attempt ? bound : std::min(bound, raw + 4096);
+                                    ck->annotated[(size_t)f].resize(caps[(size_t)f]);
+                                    outs[(size_t)f] = ck->annotated[(size_t)f].data();
+                                    sizes[(size_t)f] = 0;
+                                }
+                                const int rc = yolo2_hip_loop_images_pix(ctx, f16 ? (split ? YOLO2_LOOP_F32TOL : YOLO2_LOOP_FP16) : YOLO2_LOOP_INT16, ptrs.data(),
+                                                                         ws.data(), hs.data(), pixfmt, n, cfg.batch, cfg.thresh, cfg.nms, det_flags, recs.data(), cap,
+                                                                         counts.data(), &q, labels.data(), (int)labels.size(),
+                                                                         annotate_jpg ? YOLO2_LOOP_OUT_JPEG : YOLO2_LOOP_OUT_RGB24, cfg.jpeg_quality, outs.data(),
+                                                                         caps.data(), sizes.data(), nullptr);
+                                if (rc == YOLO2_SUCCESS) break;
+                                bool too_small = false;
+                                for (int f = 0; f < n; ++f) too_small = too_small || sizes[(size_t)f] > caps[(size_t)f];
+                                if (attempt || !annotate_jpg || !too_small) throw std::runtime_error(yolo2_hip_last_error());
+                            }
+                            for (int f = 0; f < n; ++f) {
+                                ck->annotated[(size_t)f].resize(sizes[(size_t)f]);
+                                ck->annotated[(size_t)f].shrink_to_fit();
+                            }
+                        } else {
+                            const int rc = f16 ? yolo2_hip_run_images_pix_dets_f16(ctx, split, ptrs.data(), ws.data(), hs.data(), pixfmt, n, cfg.batch, cfg.thresh,
+                                                                                   cfg.nms, det_flags, recs.data(), cap, counts.data())
+                                               : yolo2_hip_run_images_pix_dets(ctx, ptrs.data(), ws.data(), hs.data(), pixfmt, n, cfg.batch, cfg.thresh, cfg.nms,
+                                                                               det_flags, recs.data(), cap, counts.data(), &q);
+                            if (rc != YOLO2_SUCCESS) throw std::runtime_error(yolo2_hip_last_error());
+                        }
                         const auto t_dets = std::chrono::steady_clock::now();
-                        if (annotate_gpu && annotate_jpg) {     // painted and encoded on the GPU: only the streams come back
+                        if (cfg.loop_gpu) {     // (the call above made the frames)
+                        } else if (annotate_gpu && annotate_jpg) {     // painted and encoded on the GPU: only the streams come back
                             ck->annotated.resize((size_t)n);
                             std::vector<uint8_t *> outs((size_t)n);
                             std::vector<size_t> caps((size_t)n), sizes((size_t)n);

@@ -59,6 +59,8 @@ EXPORTS = [
     "yolo2_hip_annotate_pix", "yolo2_hip_annotate_images_pix_host", "yolo2_hip_multi_annotate_images_pix_host",
     "yolo2_hip_jpeg_bound", "yolo2_hip_jpeg_encode_rgb24", "yolo2_hip_annotate_images_pix_jpeg_host",
     "yolo2_hip_multi_annotate_images_pix_jpeg_host",
+    "yolo2_hip_loop_images_pix", "yolo2_hip_multi_loop_images_pix", "yolo2_hip_loop_last_info", "yolo2_hip_draw_items_dev",
+    "yolo2_hip_draw_item_size",
 ]
 
 # include/yolo2_hip.h YOLO2_PIX_*: the pixfmt argument of the _pix entries ("yuyv": packed YUYV 4:2:2, arrays uint8 [h][w][2])
@@ -267,6 +269,12 @@ def lib():
     sig("yolo2_hip_jpeg_encode_rgb24", [u64, i32, i32, i32, u64, C.c_size_t, C.POINTER(C.c_size_t), vp])
     for name in ("annotate_images_pix_jpeg_host", "multi_annotate_images_pix_jpeg_host"):
         sig("yolo2_hip_" + name, [vp, vp, vp, vp, i32, i32, i32, vp, i32, vp, C.c_float, vp, i32, i32, vp, vp, vp, vp])
+    # the camera loop as one call (include/yolo2_hip.h "the camera loop as one call")
+    for name in ("loop_images_pix", "multi_loop_images_pix"):
+        sig("yolo2_hip_" + name, [vp, i32, vp, vp, vp, i32, i32, i32, C.c_float, C.c_float, i32, vp, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp])
+    sig("yolo2_hip_loop_last_info", [vp, vp])
+    sig("yolo2_hip_draw_item_size", [], C.c_size_t)
+    sig("yolo2_hip_draw_items_dev", [vp, u64, u64, i32, i32, vp, vp, C.c_float, vp, i32, vp, vp, vp])
     _lib = L
     return L
 
@@ -457,6 +465,15 @@ class Yolo2Hip:
               "yolo2_hip_run_images_u8_host" if pixfmt is None else "yolo2_hip_run_images_pix_host")
         self.final_q = q.value
         return region, q.value
+
+    def loop_images(self, images, pixfmt=None, precision: str = "int16", tail: str = "core", thresh: float = 0.24, nms: float = 0.45,
+                    labels=None, jpeg_quality=None, batch: int = 64, cap: int = 845):
+        """the camera loop as one call: records and annotated frames from one upload (module-level loop_images)"""
+        return loop_images(self._h, images, pixfmt=pixfmt, precision=precision, tail=tail, thresh=thresh, nms=nms, labels=labels,
+                           jpeg_quality=jpeg_quality, batch=batch, cap=cap)
+
+    def loop_last_info(self) -> dict:
+        return loop_last_info(self._h)
 
     def annotate_images(self, images, dets, counts, batch: int, thresh: float, labels=None, pixfmt=None, jpeg_quality=None):
         """the images with their detection records painted in, as the reference's camera loop does (module-level annotate_images);
@@ -884,7 +901,7 @@ def _label_args(labels):
     """(char ** or None, n_labels, what keeps the strings alive)"""
     if labels is None:
         return None, 0, None
-    enc = [s.encode() if isinstance(s, str) else bytes(s) for s in labels]
+    enc = [None if s is None else s.encode() if isinstance(s, str) else bytes(s) for s in labels]      # (None: a null entry, "class<cls>")
     arr = (C.c_char_p * max(len(enc), 1))(*enc)
     return arr, len(enc), enc
 
@@ -1059,6 +1076,105 @@ def annotate_images_jpeg(handle, images, dets, counts, batch: int, thresh: float
     return [outs[f][:int(sizes[f])].tobytes() for f in range(len(outs))], drawn
 
 
+# ------------------------------------------------------------------ the camera loop as one call
+
+LOOP_PRECISIONS = {"int16": 0, "fp16": 1, "fp32fast": 2}
+
+
+class LoopInfo(C.Structure):
+    """yolo2_hip_loop_info_t"""
+    _fields_ = [("chunks", C.c_int), ("image_bytes_staged", C.c_uint64), ("image_bytes_h2d", C.c_uint64), ("out_bytes_d2h", C.c_uint64),
+                ("items_built", C.c_uint64), ("items_kernel", C.c_char * 32)]
+
+    def as_dict(self):
+        return {"chunks": self.chunks, "image_bytes_staged": self.image_bytes_staged, "image_bytes_h2d": self.image_bytes_h2d,
+                "out_bytes_d2h": self.out_bytes_d2h, "items_built": self.items_built, "items_kernel": self.items_kernel.decode()}
+
+
+def loop_last_info(ctx_handle) -> dict:
+    """yolo2_hip_loop_last_info: what the last loop call on this context moved and built"""
+    info = LoopInfo()
+    check(lib().yolo2_hip_loop_last_info(ctx_handle, C.byref(info)), "yolo2_hip_loop_last_info")
+    return info.as_dict()
+
+
+def loop_images_raw(handle, images, pixfmt, precision, flags, thresh, nms, batch, cap, labels, out_format, quality, caps, multi=False, guard=0):
+    """The loop entries as they are: caps [n] bytes of room per frame -> (return code, dets [n][cap], counts, final_q, list of uint8
+    [caps[f] + guard] buffers - with a guard, every byte of them 0xA5 before the call -, sizes [n], records drawn [n])."""
+    imgs0 = [np.ascontiguousarray(im, dtype=np.uint8) for im in images]
+    fmt = pixfmt if pixfmt is not None else ("grey8" if imgs0[0].ndim == 2 else "rgb24")
+    n, ptrs, ws, hs, code, _imgs = _image_args(imgs0, fmt)
+    dets = np.zeros((n, cap), dtype=DET_DTYPE)
+    counts = np.zeros(n, dtype=np.int32)
+    lab, n_labels, _keep = _label_args(labels)
+    caps = np.ascontiguousarray(caps, dtype=np.uint64)
+    outs = [np.full(int(caps[f]) + guard, 0xA5, dtype=np.uint8) if guard else np.empty(int(caps[f]), dtype=np.uint8) for f in range(n)]
+    optrs = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
+    sizes = np.zeros(n, dtype=np.uint64)
+    drawn = np.zeros(n, dtype=np.int32)
+    q = C.c_int(0)
+    name = f"yolo2_hip_{'multi_' if multi else ''}loop_images_pix"
+    rc = getattr(lib(), name)(handle, precision, ptrs, ws, hs, code, n, batch, thresh, nms, flags, dets.ctypes.data_as(C.c_void_p), cap,
+                              counts.ctypes.data_as(C.c_void_p), C.byref(q), lab, n_labels, out_format, quality, optrs,
+                              caps.ctypes.data_as(C.c_void_p), sizes.ctypes.data_as(C.c_void_p), drawn.ctypes.data_as(C.c_void_p))
+    return rc, dets, counts, q.value, outs, sizes, drawn
+
+
+def loop_images(handle, images, pixfmt=None, precision: str = "int16", tail: str = "core", thresh: float = 0.24, nms: float = 0.45,
+                labels=None, jpeg_quality=None, batch: int = 64, cap: int = 845, multi: bool = False):
+    """yolo2_hip_loop_images_pix / its multi form: the camera loop as one call - host images -> {"dets": per-frame record arrays (one
+    per detection, best class), "counts", "final_q" (int16 only, else None), "frames": the annotated frames as uint8 [h][w][3] (or,
+    with jpeg_quality 1..100, as JPEG byte strings), "drawn": records drawn per frame}.  The frames go up once; records, draw items
+    and the painted frames are made on the device."""
+    if precision not in LOOP_PRECISIONS:
+        raise ValueError(f"precision must be one of {tuple(LOOP_PRECISIONS)}, not {precision!r}")
+    flags = DETS_BEST_CLASS | (DETS_APP_TAIL if _check_tail(tail) else 0)
+    shapes = [np.asarray(im).shape for im in images]
+    jpeg = jpeg_quality is not None
+    if jpeg:
+        caps = [min(jpeg_bound(s[1], s[0]), s[0] * s[1] * 3 + 4096) for s in shapes]
+    else:
+        caps = [s[0] * s[1] * 3 for s in shapes]
+    name = f"yolo2_hip_{'multi_' if multi else ''}loop_images_pix"
+    for attempt in range(2):
+        rc, dets, counts, q, outs, sizes, drawn = loop_images_raw(handle, images, pixfmt, LOOP_PRECISIONS[precision], flags, thresh, nms, batch, cap,
+                                                                  labels, int(jpeg), int(jpeg_quality) if jpeg else 0, caps, multi=multi)
+        if rc == YOLO2_SUCCESS or attempt or not jpeg or not any(int(sizes[f]) > caps[f] for f in range(len(caps))):
+            break
+        caps = [jpeg_bound(s[1], s[0]) for s in shapes]   # (the rare frame that compresses to more than its raw size)
+    check(rc, name)
+    if jpeg:
+        frames = [outs[f][:int(sizes[f])].tobytes() for f in range(len(outs))]
+    else:
+        frames = [outs[f].reshape(shapes[f][0], shapes[f][1], 3) for f in range(len(outs))]
+    return {"dets": [dets[f, :min(int(counts[f]), cap)] for f in range(len(outs))], "counts": counts,
+            "final_q": q if precision == "int16" else None, "frames": frames, "drawn": drawn}
+
+
+def draw_items_dev(ctx_handle, dets, counts, widths, heights, thresh: float, labels=None):
+    """yolo2_hip_draw_items_dev, the test doorway to k_draw_items: dets DET_DTYPE [n][cap] and counts [n] are uploaded, the kernel makes
+    the draw items -> (return code, items uint8 [n][cap][item size], n_items [n], unprintable [n])."""
+    L = lib()
+    d = np.ascontiguousarray(dets, dtype=DET_DTYPE)
+    n, cap = d.shape
+    cnt = np.ascontiguousarray(counts, dtype=np.int32)
+    ws = np.ascontiguousarray(widths, dtype=np.int32)
+    hs = np.ascontiguousarray(heights, dtype=np.int32)
+    isz = int(L.yolo2_hip_draw_item_size())
+    items = np.zeros((n, cap, isz), dtype=np.uint8)
+    n_items = np.zeros(n, dtype=np.int32)
+    bad = np.zeros(n, dtype=np.int32)
+    lab, n_labels, _keep = _label_args(labels)
+    dd, dc = DevBuf(d.view(np.uint8).reshape(-1)), DevBuf(cnt)
+    try:
+        rc = L.yolo2_hip_draw_items_dev(ctx_handle, dd.addr, dc.addr, n, cap, ws.ctypes.data_as(C.c_void_p), hs.ctypes.data_as(C.c_void_p), thresh, lab,
+                                        n_labels, items.ctypes.data_as(C.c_void_p), n_items.ctypes.data_as(C.c_void_p), bad.ctypes.data_as(C.c_void_p))
+    finally:
+        dd.free()
+        dc.free()
+    return rc, items, n_items, bad
+
+
 # ------------------------------------------------------------------ more than one GPU
 
 def shard_range(total: int, rank: int, world: int):
@@ -1198,3 +1314,7 @@ class Yolo2HipMulti:
         """annotated frames, shard i painted by device i (module-level annotate_images)"""
         return annotate_images(self._m, images, dets, counts, batch_per_device, thresh, labels=labels, pixfmt=pixfmt, multi=True,
                                jpeg_quality=jpeg_quality)
+
+    def loop_images(self, images, batch_per_device: int = 64, **kw):
+        """the camera loop as one call, shard i on device i (module-level loop_images)"""
+        return loop_images(self._m, images, batch=batch_per_device, multi=True, **kw)
