@@ -668,6 +668,60 @@ int yolo2_hip_calib_q_from_stats(const float *act_absmax, const float *weight_ab
 int yolo2_hip_quantize_weights_int16(yolo2_hip_ctx *ctx, const int32_t *weight_q, const int32_t *bias_q, int16_t *weights_reorg_out,
                                      size_t n_weights, int16_t *bias_out, size_t n_bias, long *clamped);
 
+/* ------------------------------------------------------- int8 pass: calibrate, quantise and run on the i8 matrix cores
+ *
+ * A quantised integer pass of this project's own definition (the reference has no int8 mode): int8 activations and weights, exact
+ * int32 accumulation on v_mfma_i32_32x32x32_i8, one requantisation per output.  It is int8-grade (about 10 % region noise on the
+ * synthetic model), deterministic and bit-exact against tests/i8ref.py; it replaces neither the int16 nor the fp16 pass.
+ *
+ * Q rule: q8(m, h) = the largest integer q in -8..24 with h * m * 2^q < 127.5, in double; m = 0 gives 24; no such q is YOLO2_ERROR
+ * naming the tensor.  Qw[o][m] = q8(max |w| of output channel m of conv o, 1); act_q[0] = q8(max |input|, 1) (frames in [0, 1]
+ * give 6); act_q[o + 1] = q8(max |out_o|, headroom).  Fix-up: act_q[20] (layer 24) and act_q[21] (layer 26) are both set to the
+ * smaller of the two, so the concat tensor layer 29 reads has one Q.  Qin(o), the Q of the tensor conv o reads, is act_q[o], except
+ * act_q[13] for layer 26 (route 25) and act_q[20] for layer 29.
+ * Quantise: w8 = clamp(round_half_away(w * 2^Qw), -127, 127); bias32 = round_half_away(b * 2^(Qin + Qw)) in double;
+ * input x8 = clamp(round_half_away(x * 2^act_q[0]), -128, 127).
+ * Conv: acc = bias32 + sum(w8 * x8) in int32 with zero padding; leaky: acc < 0 -> acc / 10 truncating toward zero;
+ * s = Qin + Qw - act_q[o + 1]; y = (acc + 2^(s-1)) >> s for s > 0, acc << -s (64 bits) otherwise; out = clamp(y, -128, 127).
+ * Pool is a 2x2 max, reorg the legacy Darknet indexing, route is placement.  Layer 30 is not requantised:
+ * region = (float)acc * 2^-(Qin + Qw), round-to-nearest conversion and an exact scaling.
+ * The images, pix, loop and multi-GPU entries have no int8 form. */
+
+/* The int8 Q rule on explicit maxima (host arithmetic only, no GPU): act_absmax[24] as yolo2_hip_calib_stats returns them ->
+ * act_q[24], fix-up applied. */
+int yolo2_hip_calib_q8_from_stats(const float *act_absmax, float headroom, int32_t *act_q);
+/* The same on the context's statistics.  YOLO2_ERROR if no frame was seen or a non-finite value was counted in a tensor. */
+int yolo2_hip_calib_q8_tables(yolo2_hip_ctx *ctx, float headroom, int32_t *act_q);
+/* The resident fp32 blobs quantised on the GPU (k_quantize_i8: per-channel abs-max, then w8, bias32 and Qw) into host buffers:
+ * w8_out, at least YOLO2_N_WEIGHTS int8 in NATURAL [N][C][K][K] order per layer; bias32_out and weight_q_out, at least YOLO2_N_BIAS
+ * each, one entry per output channel.  act_q[24] supplies Qin of every layer.  A channel that no Q holds is YOLO2_ERROR naming it. */
+int yolo2_hip_quantize_weights_int8(yolo2_hip_ctx *ctx, const int32_t *act_q, int8_t *w8_out, size_t n_w, int32_t *bias32_out, size_t n_b,
+                                    int32_t *weight_q_out);
+/* Loads an int8 weight set (host arrays as the quantiser writes them; n_w = YOLO2_N_WEIGHTS, n_b = YOLO2_N_BIAS, weight_q[n_b],
+ * act_q[24]) and packs the weights on the device in the order the conv kernel stages them.  Refused before any launch: wrong
+ * lengths; a Q outside -8..24; act_q[20] != act_q[21]; a shift s outside -7..31; an output channel for which
+ * |bias32| + 128 * sum|w8| + 2^30 < 2^31 does not hold (the proof that neither the accumulator nor its rounding constant can
+ * overflow 32 bits) - the message names the layer and the channel.  Independent of the int16 and fp32 weight sets of the context. */
+int yolo2_hip_load_weights_int8(yolo2_hip_ctx *ctx, const int8_t *w8, size_t n_w, const int32_t *bias32, size_t n_b, const int32_t *weight_q,
+                                const int32_t *act_q);
+/* The int8 pass: frames_dev float [batch][3][416][416] -> region_dev float [batch][425][13][13], both in HBM and laid out as
+ * yolo2_hip_run_batch_fp16 has them; the region tensor feeds yolo2_hip_postprocess_f32 / _f32_app.  One stream, no lanes; enqueues
+ * and returns.  batch 1..1024. */
+int yolo2_hip_run_batch_int8(yolo2_hip_ctx *ctx, uint64_t frames_dev, int batch, uint64_t region_dev, void *stream);
+/* The same with host buffers, blocking. */
+int yolo2_hip_run_batch_int8_host(yolo2_hip_ctx *ctx, const float *frames, int batch, float *region);
+/* Parity hook: the int8 tensor layer `layer_idx` (0..29; -1 = the quantised input) left behind in the last int8 run, frame `frame`,
+ * as dense [C][H][W] into out (cap elements).  geom[4] = {C, H, W, Q}; out may be NULL to ask for the geometry only.  Locates a
+ * wrong layer without another run. */
+int yolo2_hip_debug_i8_tensor(yolo2_hip_ctx *ctx, int layer_idx, int frame, int8_t *out, size_t cap, int *geom);
+/* Driver-tier single layer beside yolo2_execute_conv_layer / _f32: one stride-1 "same" conv of any ifm_num, ofm_num, ksize 1 or 3,
+ * size and batch through the int8 kernel.  Device buffers in natural dense order: input int8 [batch][ifm][H][W], weights int8
+ * [ofm][ifm][k][k], bias32 int32 [ofm], output int8 [batch][ofm][H][W] or - out_float - float of the same shape computed by layer
+ * 30's rule.  weight_q[ofm] is a HOST array.  The loader's refusals (Q ranges, s, the overflow proof) apply.  Blocking. */
+int yolo2_execute_conv_layer_int8(uint64_t input_addr, uint64_t output_addr, uint64_t weight_addr, uint64_t bias_addr,
+                                  const int32_t *weight_q, int ifm_num, int ofm_num, int ksize, int input_w, int input_h, int batch,
+                                  int q_in, int q_out, int is_nl, int out_float, uint32_t timeout_ms);
+
 /* ------------------------------------------------------- multi-GPU: frame sharding, one weight broadcast
  *
  * SURVEY.md 8(b) "init(device_list) ... load_weights (H2D on rank 0, RCCL broadcast to the rest)", 8(e): frames are

@@ -7,6 +7,7 @@
 //   yolo2_fp16.hip    the fp16 MFMA path: weight packing, per-context launch table, run_batch_fp16
 //   yolo2_fp32.hip    the exact fp32 path (tiled and one-thread-per-output)
 //   yolo2_calib.hip   fp32 weights + calibration frames -> Q tables and int16 weights (statistics of the exact fp32 pass)
+//   yolo2_int8.hip    the int8 pass on the i8 matrix cores: quantiser, loader and its proofs, run_batch_int8, the single-layer call
 //   yolo2_post.hip    region layer + boxes + NMS;   yolo2_multi.hip  frame sharding + the RCCL weight broadcast
 //   yolo2_draw.hip    annotated frames: records + frames -> RGB24 with the reference's boxes and tags
 //   yolo2_jpeg.hip    RGB24 frames in device memory -> the reference's JPEG streams
@@ -254,6 +255,7 @@ struct Y2LoopBufs {
 };
 
 struct F16Plan;   // yolo2_fp16.hip: the per-context launch table of the fp16 path
+struct Y2I8;      // yolo2_int8.hip: packed int8 weights, Q tables and activation tensors of the int8 pass
 
 struct yolo2_hip_ctx {
     PipeBufs pipe;
@@ -341,6 +343,7 @@ struct yolo2_hip_ctx {
     // calls.  Pairs of uint32 {max |x| as fp32 bits, saturating count of non-finite values}; allocated at the first calibration call.
     Y2DevBuf<unsigned> calib_stats;
     long calib_frames_seen = 0;
+    Y2I8 *i8 = nullptr;                // the int8 pass (made by yolo2_hip_load_weights_int8; owned: y2_i8_free)
     long wh_off[YOLO2_N_CONV], biasf_off[YOLO2_N_CONV];
     int f16_batch = 0;
     int f16_last_batch = 0;            // batch of the last yolo2_hip_run_batch_fp16 on this context (yolo2_hip_debug_f16_tensor)
@@ -443,6 +446,11 @@ void y2_drv_release_i16(void);   // frees the grow-only scratch of y2_drv_conv_i
 // yolo2_fp32.hip:
 void y2_drv_conv_f32(const float *in, float *out, const float *w, const float *beta, int ifm, int ofm, int ksize, int kstride, int iw,
                      int ih, int ow, int oh, int pad, int is_nl);
+
+// yolo2_int8.hip: the driver tier's int8 conv (buffers in natural dense order; synchronises the null stream), and c->i8's end
+int y2_drv_conv_i8(uint64_t in, uint64_t out, uint64_t w, uint64_t bias, const int32_t *weight_q, int C, int N, int K, int W, int H, int batch,
+                   int q_in, int q_out, int leaky, int out_float);
+void y2_i8_free(yolo2_hip_ctx *c);
 
 // yolo2_draw.hip: the streams, events and buffers of c->anno (yolo2_hip_destroy)
 void y2_anno_free(yolo2_hip_ctx *c);

@@ -255,6 +255,53 @@ extern "C" int yolo2_hip_calib_q_tables(yolo2_hip_ctx *c, float headroom, int32_
     return yolo2_hip_calib_q_from_stats(act, w, b, headroom, weight_q, bias_q, act_q);
 }
 
+// ---- the int8 pass's Q rule (include/yolo2_hip.h "int8 pass"): the rule above with the int8 limit and a range of -8..24
+
+// q8(m, h); INT_MIN-like -100 if no q in -8..24 fits (or m is not a finite non-negative number)
+static int q8_of(double m, double h)
+{
+    if (!(m >= 0.0) || !std::isfinite(m)) return -100;
+    if (m == 0.0) return 24;
+    for (int q = 24; q >= -8; --q)
+        if (h * m * std::ldexp(1.0, q) < 127.5) return q;
+    return -100;
+}
+
+extern "C" int yolo2_hip_calib_q8_from_stats(const float *act_absmax, float headroom, int32_t *act_q)
+{
+    if (!act_absmax || !act_q) return fail(YOLO2_ERROR, "null argument");
+    if (!(headroom >= 1.0f) || !std::isfinite(headroom)) return fail(YOLO2_ERROR, "headroom %g is not a finite number >= 1", (double)headroom);
+    if ((act_q[0] = q8_of(act_absmax[0], 1.0)) == -100)
+        return fail(YOLO2_ERROR, "no Q in -8..24 holds the network input (max = %g)", (double)act_absmax[0]);
+    for (int o = 0; o < YOLO2_N_CONV; ++o)
+        if ((act_q[o + 1] = q8_of(act_absmax[o + 1], headroom)) == -100)
+            return fail(YOLO2_ERROR, "no Q in -8..24 holds the output of conv %d (max = %g, headroom %g)", o, (double)act_absmax[o + 1],
+                        (double)headroom);
+    // layer 24 is conv 19, layer 26 conv 20: both halves of the concat tensor take the smaller Q, nothing is shifted at run time
+    act_q[20] = act_q[21] = std::min(act_q[20], act_q[21]);
+    return YOLO2_SUCCESS;
+}
+
+extern "C" int yolo2_hip_calib_q8_tables(yolo2_hip_ctx *c, float headroom, int32_t *act_q)
+{
+    int rc = need_fp32(c);
+    if (rc) return rc;
+    if (!act_q) return fail(YOLO2_ERROR, "null argument");
+    if (!(headroom >= 1.0f) || !std::isfinite(headroom)) return fail(YOLO2_ERROR, "headroom %g is not a finite number >= 1", (double)headroom);
+    if (c->calib_frames_seen <= 0) return fail(YOLO2_ERROR, "no calibration frame seen (yolo2_hip_calib_frames)");
+    HIP_TRY(hipSetDevice(c->device), YOLO2_INIT_ERROR);
+    unsigned h[kSlots * 2];
+    if ((rc = collect(c, h))) return rc;
+    float act[YOLO2_N_CONV + 1];
+    for (int i = 0; i <= YOLO2_N_CONV; ++i) {
+        if (h[2 * (kActSlot + i) + 1])
+            return fail(YOLO2_ERROR, "%u non-finite values in activation tensor %d (0 = the input, k = the output of conv k-1)",
+                        h[2 * (kActSlot + i) + 1], i);
+        act[i] = bits_float(h[2 * (kActSlot + i)]);
+    }
+    return yolo2_hip_calib_q8_from_stats(act, headroom, act_q);
+}
+
 extern "C" int yolo2_hip_quantize_weights_int16(yolo2_hip_ctx *c, const int32_t *weight_q, const int32_t *bias_q, int16_t *weights_reorg_out,
                                                 size_t n_weights, int16_t *bias_out, size_t n_bias, long *clamped)
 {

@@ -406,3 +406,24 @@ extern "C" int yolo2_execute_conv_layer_f32(uint64_t input_addr, uint64_t output
     HIP_TRY(hipGetLastError(), YOLO2_ERROR);
     return sync_with_timeout(nullptr, timeout_ms);
 }
+
+// int8 twin (this project's own int8 arithmetic, include/yolo2_hip.h "int8 pass"): natural dense buffers, any shape the kernel's
+// flat pixel index holds.  The Q and overflow refusals are the loader's (y2_drv_conv_i8 reads the weights back for them).
+extern "C" int yolo2_execute_conv_layer_int8(uint64_t input_addr, uint64_t output_addr, uint64_t weight_addr, uint64_t bias_addr,
+                                             const int32_t *weight_q, int ifm_num, int ofm_num, int ksize, int input_w, int input_h, int batch,
+                                             int q_in, int q_out, int is_nl, int out_float, uint32_t timeout_ms)
+{
+    std::lock_guard<std::mutex> lk(g_drv.mu);
+    if (!drv_ready_locked()) return fail(YOLO2_INIT_ERROR, "yolo2_accel_init() has not been called");
+    if (!input_addr || !output_addr || !weight_addr || !bias_addr || !weight_q) return fail(YOLO2_ERROR, "null buffer address");
+    if ((bias_addr & 3) || (out_float && (output_addr & 3))) return fail(YOLO2_ERROR, "bias32 and a float output start on a 4-byte boundary");
+    if (ksize != 1 && ksize != 3) return fail(YOLO2_ERROR, "int8 conv: kernel size %d is not 1 or 3", ksize);
+    if (ifm_num < 1 || ifm_num > 4096 || ofm_num < 1 || ofm_num > 4096 || input_w < 1 || input_w > 1024 || input_h < 1 || input_h > 1024 ||
+        batch < 1 || batch > 1024 || (long)batch * input_w * input_h > (1l << 24))
+        return fail(YOLO2_ERROR, "int8 conv: shape outside the entry's limits (channels 1..4096, sides 1..1024, batch 1..1024, 2^24 pixels)");
+    g_drv.calls++;
+    const int rc = y2_drv_conv_i8(input_addr, output_addr, weight_addr, bias_addr, weight_q, ifm_num, ofm_num, ksize, input_w, input_h, batch, q_in,
+                                  q_out, is_nl ? 1 : 0, out_float ? 1 : 0);
+    if (rc) return rc;
+    return sync_with_timeout(nullptr, timeout_ms);
+}

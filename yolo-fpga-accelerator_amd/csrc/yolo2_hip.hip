@@ -239,6 +239,7 @@ extern "C" void yolo2_hip_destroy(yolo2_hip_ctx *c)
     y2_anno_jpeg_free(c);
     y2_loop_free(c);
     y2_f16_plan_free(c);
+    y2_i8_free(c);
     y2_destroy_lanes(c);
     y2_free_activations(c);
     if (c->lane_stream) (void)hipStreamDestroy(c->lane_stream);

@@ -1,4 +1,5 @@
-// yolov2_calibrate -- fp32 weight files + calibration images -> the int16 weight set yolov2_detect --precision int16 runs.
+// yolov2_calibrate -- fp32 weight files + calibration images -> the int16 weight set yolov2_detect --precision int16 runs, or
+// (--format int8) the int8 weight set of --precision int8: the same statistics, the int8 Q rule, per-channel weight Qs.
 //
 // The reference makes this set with a separate tool (weights/README.md step 2b); here it is the calibration tier of the HIP library
 // behind its C ABI (include/yolo2_hip.h, "calibration"): the exact fp32 pass runs the images, one abs-max per tensor gives the
@@ -24,6 +25,7 @@ struct Config {
     std::string weights_dir = "weights", out_dir, input_dir, input_list;
     int batch = 8, device = 0;
     float headroom = 1.0f;
+    std::string format = "int16";
 };
 
 void print_usage(const char *prog)
@@ -37,6 +39,9 @@ void print_usage(const char *prog)
         "  --batch <n>           Images per pass of the exact fp32 network (default 8)\n"
         "  --headroom <float>    Factor >= 1 kept free above every conv output's measured maximum (default 1)\n"
         "  --device <n>          HIP device (default 0)\n"
+        "  --format <int16|int8> int16 (default): the five files above.  int8: weights_int8.bin (natural order), bias_int32.bin,\n"
+        "                        weight_int8_Q.bin (one Q per output channel) and iofm_int8_Q.bin, by the rule\n"
+        "                        'the largest Q in -8..24 with headroom * max|x| * 2^Q < 127.5'\n"
         "Q rule: the largest Q in 0..15 with headroom * max|x| * 2^Q < 32767.5 (it still rounds to at most 32767), per tensor.\n",
         prog);
 }
@@ -58,6 +63,7 @@ Config parse_args(int argc, char **argv)
         else if (arg == "--batch" && need()) cfg.batch = std::atoi(argv[++i]);
         else if (arg == "--headroom" && need()) cfg.headroom = (float)std::atof(argv[++i]);
         else if (arg == "--device" && need()) cfg.device = std::atoi(argv[++i]);
+        else if (arg == "--format" && need()) cfg.format = argv[++i];
         else { std::fprintf(stderr, "Unknown argument: %s\n", arg.c_str()); print_usage(argv[0]); std::exit(1); }
     }
     if (cfg.out_dir.empty() || (cfg.input_dir.empty() == cfg.input_list.empty())) {
@@ -65,6 +71,7 @@ Config parse_args(int argc, char **argv)
         print_usage(argv[0]);
         std::exit(1);
     }
+    if (cfg.format != "int16" && cfg.format != "int8") { std::fprintf(stderr, "--format must be int16 or int8\n"); std::exit(1); }
     if (cfg.batch < 1 || cfg.batch > 1024) { std::fprintf(stderr, "--batch must be 1..1024\n"); std::exit(1); }
     if (!(cfg.headroom >= 1.0f)) { std::fprintf(stderr, "--headroom must be >= 1\n"); std::exit(1); }
     return cfg;
@@ -148,6 +155,28 @@ int run(const Config &cfg)
     float act_max[YOLO2_N_CONV + 1], w_max[YOLO2_N_CONV], b_max[YOLO2_N_CONV];
     long seen = 0;
     check(yolo2_hip_calib_stats(ctx, act_max, w_max, b_max, &seen));
+    if (cfg.format == "int8") {
+        std::vector<int32_t> aq8(YOLO2_N_CONV + 1), wq8((size_t)YOLO2_N_BIAS), b32((size_t)YOLO2_N_BIAS);
+        std::vector<int8_t> w8((size_t)YOLO2_N_WEIGHTS);
+        check(yolo2_hip_calib_q8_tables(ctx, cfg.headroom, aq8.data()));
+        check(yolo2_hip_quantize_weights_int8(ctx, aq8.data(), w8.data(), w8.size(), b32.data(), b32.size(), wq8.data()));
+        std::printf("calibrated on %ld images (batch %d, headroom %g), int8\n", seen, cfg.batch, (double)cfg.headroom);
+        std::printf("input        max|x| %-12.6g act_q %d\n", (double)act_max[0], aq8[0]);
+        std::printf("%-5s %-14s %-12s %-14s %s\n", "conv", "max|w|", "weight_q", "max|out|", "act_q");
+        size_t off = 0;
+        for (int o = 0; o < YOLO2_N_CONV; ++o) {
+            const auto mm = std::minmax_element(wq8.begin() + (long)off, wq8.begin() + (long)(off + (size_t)yolo2_bias_len[o]));
+            std::printf("%-5d %-14.6g %3d..%-7d %-14.6g %d\n", o, (double)w_max[o], *mm.first, *mm.second, (double)act_max[o + 1], aq8[(size_t)o + 1]);
+            off += (size_t)yolo2_bias_len[o];
+        }
+        std::filesystem::create_directories(cfg.out_dir);
+        write_blob(cfg.out_dir + "/weights_int8.bin", w8);
+        write_blob(cfg.out_dir + "/bias_int32.bin", b32);
+        write_blob(cfg.out_dir + "/weight_int8_Q.bin", wq8);
+        write_blob(cfg.out_dir + "/iofm_int8_Q.bin", aq8);
+        std::printf("wrote weights_int8.bin, bias_int32.bin, weight_int8_Q.bin, iofm_int8_Q.bin to %s\n", cfg.out_dir.c_str());
+        return 0;
+    }
     std::vector<int32_t> wq(YOLO2_N_CONV), bq(YOLO2_N_CONV), aq(YOLO2_N_CONV + 1);
     check(yolo2_hip_calib_q_tables(ctx, cfg.headroom, wq.data(), bq.data(), aq.data()));
     std::vector<int16_t> wi((size_t)YOLO2_N_WEIGHTS), bi((size_t)YOLO2_N_BIAS);

@@ -91,9 +91,11 @@ void print_usage(const char *prog)
         "  --nms <float>         NMS IoU threshold (default: 0.45)\n"
         "  --hier <float>        Hierarchical threshold (accepted, unused by region layers)\n"
         "  --backend <hip>       Backend selector (hip = MI355X library; hls/cpu live in the reference build)\n"
-        "  --precision <int16|fp32|fp32fast|fp16>  int16 = the batched fixed-point path; fp32 = the exact fp32 pass (tiled, batched);\n"
+        "  --precision <int16|fp32|fp32fast|fp16|int8>  int16 = the batched fixed-point path; fp32 = the exact fp32 pass (tiled, batched);\n"
         "                            fp32fast = the fp32 weight files on the matrix cores in split-fp16 form (hi + lo halves, three MFMAs per\n"
         "                            product: boxes within 1e-3 of fp32's, ~7x the exact pass's rate); fp16 = fp16 operands, fp32 accumulate (approximate)\n"
+        "                            int8 = the quantised pass on the i8 matrix cores; --weights names a directory written by\n"
+        "                            yolov2_calibrate --format int8 (single image and --batch only, no streaming)\n"
         "  --batch <n>           Frames per accelerator call (default 1)\n"
         "  --device <n>          HIP device (default 0)\n"
         "  --devices <a,b,..>    Several HIP devices: frames shard contiguously, weights are broadcast once (RCCL)\n"
@@ -203,8 +205,9 @@ AppConfig parse_args(int argc, char **argv)
             if (cfg.precision == "i16" || cfg.precision == "fixed") cfg.precision = "int16";
             if (cfg.precision == "half" || cfg.precision == "f16") cfg.precision = "fp16";
             if (cfg.precision == "f32fast" || cfg.precision == "fp32tol") cfg.precision = "fp32fast";
-            if (cfg.precision != "int16" && cfg.precision != "fp32" && cfg.precision != "fp16" && cfg.precision != "fp32fast") {
-                std::fprintf(stderr, "Unsupported precision: %s (the hip backend runs int16, fp32, fp32fast and fp16)\n", cfg.precision.c_str());
+            if (cfg.precision == "i8") cfg.precision = "int8";
+            if (cfg.precision != "int16" && cfg.precision != "fp32" && cfg.precision != "fp16" && cfg.precision != "fp32fast" && cfg.precision != "int8") {
+                std::fprintf(stderr, "Unsupported precision: %s (the hip backend runs int16, fp32, fp32fast, fp16 and int8)\n", cfg.precision.c_str());
                 std::exit(1);
             }
         } else if (arg.rfind("--", 0) == 0) {
@@ -216,6 +219,11 @@ AppConfig parse_args(int argc, char **argv)
     if (cfg.loop_gpu && !(cfg.annotate_gpu && !cfg.save_dir.empty() && cfg.post == "gpu" && cfg.streaming())) {
         std::fprintf(stderr, "--loop-gpu joins the detections and the annotated frames of a streaming run: it needs --annotate-gpu, "
                              "--save-annotated-dir <dir> and --post gpu\n");
+        std::exit(1);
+    }
+    if (cfg.precision == "int8" && cfg.streaming()) {
+        std::fprintf(stderr, "--precision int8 has no streaming form: the images, pix and loop entries run int16, fp16 and fp32fast. "
+                             "Run it on a single image (optionally with --batch).\n");
         std::exit(1);
     }
     if (cfg.video_pixfmt == YOLO2_PIX_YUYV && !cfg.video_raw.empty() && (cfg.video_w & 1)) {
@@ -506,6 +514,18 @@ std::vector<float> read_floats(const std::string &path, size_t want)
     std::vector<float> v(n);
     f.seekg(0);
     f.read(reinterpret_cast<char *>(v.data()), (std::streamsize)(n * sizeof(float)));
+    return v;
+}
+
+template <typename T>
+std::vector<T> read_blob(const std::string &path, size_t want)
+{
+    std::ifstream f(path, std::ios::binary);
+    if (!f) throw std::runtime_error("Cannot open " + path);
+    std::vector<T> v(want);
+    f.read(reinterpret_cast<char *>(v.data()), (std::streamsize)(want * sizeof(T)));
+    if ((size_t)f.gcount() != want * sizeof(T) || f.peek() != std::ifstream::traits_type::eof())
+        throw std::runtime_error(path + " does not hold exactly " + std::to_string(want) + " elements");
     return v;
 }
 
@@ -870,6 +890,20 @@ void run_detector(AppConfig cfg)
         if (rc != YOLO2_SUCCESS) throw std::runtime_error(yolo2_hip_last_error());
         elapsed = std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - t0).count();
         std::memcpy(raw.data(), regions.data(), sizeof(float) * YOLO2_REGION_ELEMS);
+    } else if (cfg.precision == "int8") {
+        // the four files of yolov2_calibrate --format int8: natural-order int8 weights, int32 biases, per-channel weight Qs, 24 tensor Qs
+        const std::vector<int8_t> w = read_blob<int8_t>(cfg.weights_dir + "/weights_int8.bin", (size_t)YOLO2_N_WEIGHTS);
+        const std::vector<int32_t> b = read_blob<int32_t>(cfg.weights_dir + "/bias_int32.bin", (size_t)YOLO2_N_BIAS);
+        const std::vector<int32_t> wq = read_blob<int32_t>(cfg.weights_dir + "/weight_int8_Q.bin", (size_t)YOLO2_N_BIAS);
+        const std::vector<int32_t> aq = read_blob<int32_t>(cfg.weights_dir + "/iofm_int8_Q.bin", (size_t)YOLO2_N_CONV + 1);
+        if (yolo2_hip_load_weights_int8(ctx, w.data(), w.size(), b.data(), b.size(), wq.data(), aq.data()) != YOLO2_SUCCESS)
+            throw std::runtime_error(yolo2_hip_last_error());
+        std::vector<float> frames((size_t)cfg.batch * YOLO2_FRAME_ELEMS), regions((size_t)cfg.batch * YOLO2_REGION_ELEMS);
+        for (int f = 0; f < cfg.batch; ++f) std::memcpy(frames.data() + (size_t)f * YOLO2_FRAME_ELEMS, sized.data.data(), sizeof(float) * YOLO2_FRAME_ELEMS);
+        const auto t0 = std::chrono::high_resolution_clock::now();
+        if (yolo2_hip_run_batch_int8_host(ctx, frames.data(), cfg.batch, regions.data()) != YOLO2_SUCCESS) throw std::runtime_error(yolo2_hip_last_error());
+        elapsed = std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - t0).count();
+        std::memcpy(raw.data(), regions.data(), sizeof(float) * YOLO2_REGION_ELEMS);   // a float region tensor: the float tail below
     } else {
         std::vector<int> wlen(yolo2_weight_len, yolo2_weight_len + YOLO2_N_CONV), blen(yolo2_bias_len, yolo2_bias_len + YOLO2_N_CONV);
         const y2h::WeightsI16 wp = y2h::load_weights_int16(cfg.weights_dir, wlen, blen);

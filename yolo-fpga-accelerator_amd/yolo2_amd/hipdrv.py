@@ -61,6 +61,8 @@ EXPORTS = [
     "yolo2_hip_multi_annotate_images_pix_jpeg_host",
     "yolo2_hip_loop_images_pix", "yolo2_hip_multi_loop_images_pix", "yolo2_hip_loop_last_info", "yolo2_hip_draw_items_dev",
     "yolo2_hip_draw_item_size",
+    "yolo2_hip_calib_q8_from_stats", "yolo2_hip_calib_q8_tables", "yolo2_hip_quantize_weights_int8", "yolo2_hip_load_weights_int8",
+    "yolo2_hip_run_batch_int8", "yolo2_hip_run_batch_int8_host", "yolo2_hip_debug_i8_tensor", "yolo2_execute_conv_layer_int8",
 ]
 
 # include/yolo2_hip.h YOLO2_PIX_*: the pixfmt argument of the _pix entries ("yuyv": packed YUYV 4:2:2, arrays uint8 [h][w][2])
@@ -275,6 +277,15 @@ def lib():
     sig("yolo2_hip_loop_last_info", [vp, vp])
     sig("yolo2_hip_draw_item_size", [], C.c_size_t)
     sig("yolo2_hip_draw_items_dev", [vp, u64, u64, i32, i32, vp, vp, C.c_float, vp, i32, vp, vp, vp])
+    # the int8 pass (include/yolo2_hip.h "int8 pass")
+    sig("yolo2_hip_calib_q8_from_stats", [vp, C.c_float, vp])
+    sig("yolo2_hip_calib_q8_tables", [vp, C.c_float, vp])
+    sig("yolo2_hip_quantize_weights_int8", [vp, vp, vp, C.c_size_t, vp, C.c_size_t, vp])
+    sig("yolo2_hip_load_weights_int8", [vp, vp, C.c_size_t, vp, C.c_size_t, vp, vp])
+    sig("yolo2_hip_run_batch_int8", [vp, u64, i32, u64, vp])
+    sig("yolo2_hip_run_batch_int8_host", [vp, vp, i32, vp])
+    sig("yolo2_hip_debug_i8_tensor", [vp, i32, i32, vp, C.c_size_t, pi32])
+    sig("yolo2_execute_conv_layer_int8", [u64] * 4 + [vp] + [i32] * 10 + [u32])
     _lib = L
     return L
 
@@ -365,6 +376,36 @@ def conv_layer_f32(x, w_reorg, bias, C_, N, K, stride, W, H, pad, leaky):
     return y
 
 
+def conv_layer_i8(x, w8, bias32, weight_q, q_in, q_out, leaky, out_float=False, guard=128):
+    """yolo2_execute_conv_layer_int8: one stride-1 "same" conv through the int8 MFMA kernel.  x int8 [B][C][H][W], w8 int8
+    [N][C][K][K] (K 1 or 3), bias32 int32 [N], weight_q int32 [N] -> int8 [B][N][H][W], or float32 by layer 30's rule (out_float).
+    The output buffer sits between two `guard`-byte regions of 0xA5; they are returned for the caller to look at:
+    (y, guard_before, guard_after)."""
+    x = np.ascontiguousarray(x, dtype=np.int8)
+    w = np.ascontiguousarray(w8, dtype=np.int8)
+    b = np.ascontiguousarray(bias32, dtype=np.int32)
+    qw = np.ascontiguousarray(weight_q, dtype=np.int32)
+    B, C_, H, W = x.shape
+    N, K = w.shape[0], w.shape[2]
+    if w.shape != (N, C_, K, K) or b.shape != (N,) or qw.shape != (N,) or guard % 4:
+        raise ValueError("conv_layer_i8: x [B][C][H][W], w8 [N][C][K][K], bias32 [N], weight_q [N]")
+    dt = np.float32 if out_float else np.int8
+    nbytes = B * N * H * W * np.dtype(dt).itemsize
+    pad = -nbytes % 4
+    bx, bw, bb = DevBuf(x), DevBuf(w), DevBuf(b)
+    by = DevBuf(nbytes=guard + nbytes + pad + guard, fill=0xA5)
+    try:
+        check(lib().yolo2_execute_conv_layer_int8(bx.addr, by.addr + guard, bw.addr, bb.addr, qw.ctypes.data_as(C.c_void_p), C_, N, K, W, H, B,
+                                                  int(q_in), int(q_out), int(bool(leaky)), int(bool(out_float)), 60000),
+              "yolo2_execute_conv_layer_int8")
+        raw = by.get(np.uint8, (guard + nbytes + pad + guard,))
+    finally:
+        for d in (bx, bw, bb, by):
+            d.free()
+    y = raw[guard:guard + nbytes].view(dt).reshape(B, N, H, W).copy()
+    return y, raw[:guard].copy(), raw[guard + nbytes:].copy()
+
+
 def maxpool_layer_i16(x, C_, W, H, K=2, stride=2):
     OW, OH = W // stride, H // stride
     TR = min((27 - K) // stride + 1, 13, OH)
@@ -418,6 +459,8 @@ class Yolo2Hip:
                                                      bq.size, vp(aq), aq.size), "yolo2_hip_load_weights_int16_dev")
 
     def load_model(self, model):
+        if isinstance(model, CalibratedModelI8):
+            return self.load_weights_int8(model.w8, model.bias32, model.weight_q, model.act_q)
         self.load_weights(model.weights_i16(), model.bias_i16(), model.weight_q, model.bias_q, model.act_q)
 
     def layer_paths(self):
@@ -714,6 +757,69 @@ class Yolo2Hip:
         return CalibratedModel(w, b, wq, bq, aq, clamped, st["act_absmax"], st["weight_absmax"], st["bias_absmax"], st["frames_seen"])
 
 
+    # ---- the int8 pass on the i8 matrix cores (include/yolo2_hip.h "int8 pass")
+    def calib_q8_tables(self, headroom: float = 1.0) -> np.ndarray:
+        aq = np.zeros(len(net.CONVS) + 1, np.int32)
+        check(lib().yolo2_hip_calib_q8_tables(self._h, headroom, aq.ctypes.data_as(C.c_void_p)), "yolo2_hip_calib_q8_tables")
+        return aq
+
+    def quantize_weights_int8(self, act_q):
+        """the resident fp32 blobs -> (w8 natural order, bias32 [10761], weight_q [10761]), quantised on the GPU"""
+        aq = np.ascontiguousarray(act_q, dtype=np.int32)
+        if aq.shape != (len(net.CONVS) + 1,):
+            raise ValueError(f"act_q holds {len(net.CONVS) + 1} entries")
+        w, b, q = np.empty(N_WEIGHTS, np.int8), np.empty(N_BIAS, np.int32), np.empty(N_BIAS, np.int32)
+        vp = lambda v: v.ctypes.data_as(C.c_void_p)
+        check(lib().yolo2_hip_quantize_weights_int8(self._h, vp(aq), vp(w), w.size, vp(b), b.size, vp(q)), "yolo2_hip_quantize_weights_int8")
+        return w, b, q
+
+    def calibrate_int8(self, frames=None, images=None, batch: int = 8, headroom: float = 1.0, pixfmt=None) -> "CalibratedModelI8":
+        """fp32 weights (load_weights_fp32) + calibration frames or images -> a CalibratedModelI8: the statistics of calibrate(), the
+        int8 Q rule with `headroom`, per-channel weight Qs, weights and biases quantised on the GPU."""
+        if (frames is None) == (images is None):
+            raise ValueError("calibrate_int8 takes frames=... or images=..., not both")
+        if batch < 1:
+            raise ValueError("batch must be positive")
+        self.calib_reset()
+        if frames is not None:
+            frames = np.ascontiguousarray(frames, dtype=np.float32).reshape(-1, 3, 416, 416)
+            for i in range(0, frames.shape[0], batch):
+                self.calib_frames(frames[i:i + batch])
+        else:
+            self.calib_images(images, batch, pixfmt)
+        st = self.calib_stats()
+        aq = self.calib_q8_tables(headroom)
+        w, b, q = self.quantize_weights_int8(aq)
+        return CalibratedModelI8(w, b, q, aq, st["act_absmax"], st["frames_seen"])
+
+    def load_weights_int8(self, w8, bias32, weight_q, act_q):
+        w = np.ascontiguousarray(w8, dtype=np.int8)
+        b, q, a = (np.ascontiguousarray(v, dtype=np.int32) for v in (bias32, weight_q, act_q))
+        if q.size != b.size or a.size != len(net.CONVS) + 1:
+            raise ValueError(f"weight_q holds one entry per bias ({b.size}), act_q {len(net.CONVS) + 1}")
+        vp = lambda v: v.ctypes.data_as(C.c_void_p)
+        check(lib().yolo2_hip_load_weights_int8(self._h, vp(w), w.size, vp(b), b.size, vp(q), vp(a)), "yolo2_hip_load_weights_int8")
+
+    def run_batch_int8_ptr(self, frames_ptr: int, batch: int, region_ptr: int, stream: int = 0):
+        check(lib().yolo2_hip_run_batch_int8(self._h, frames_ptr, batch, region_ptr, C.c_void_p(stream)), "yolo2_hip_run_batch_int8")
+
+    def run_batch_int8_host(self, frames: np.ndarray) -> np.ndarray:
+        frames = np.ascontiguousarray(frames, dtype=np.float32)
+        B = frames.shape[0]
+        region = np.empty((B, 425, 13, 13), dtype=np.float32)
+        check(lib().yolo2_hip_run_batch_int8_host(self._h, frames.ctypes.data_as(C.c_void_p), B, region.ctypes.data_as(C.c_void_p)),
+              "yolo2_hip_run_batch_int8_host")
+        return region
+
+    def debug_i8_tensor(self, layer_idx: int, frame: int = 0):
+        """(int8 [C][H][W], Q) of layer `layer_idx`'s tensor in the last int8 run; -1 is the quantised input"""
+        g = (C.c_int * 4)()
+        check(lib().yolo2_hip_debug_i8_tensor(self._h, layer_idx, frame, None, 0, g), "yolo2_hip_debug_i8_tensor")
+        out = np.empty((g[0], g[1], g[2]), dtype=np.int8)
+        check(lib().yolo2_hip_debug_i8_tensor(self._h, layer_idx, frame, out.ctypes.data_as(C.c_void_p), out.size, g), "yolo2_hip_debug_i8_tensor")
+        return out, int(g[3])
+
+
 # ------------------------------------------------------------------ calibration: fp32 weights + frames -> an int16 weight set
 
 N_WEIGHTS, N_BIAS = net.N_WEIGHTS, net.N_BIAS   # include/yolo2_hip.h YOLO2_N_WEIGHTS / YOLO2_N_BIAS
@@ -799,6 +905,46 @@ class CalibratedModel:
         rd = lambda name, dt: np.fromfile(os.path.join(weights_dir, name), dtype=dt)
         return cls(strip(rd(cls.FILES[0], np.int16), net.WEIGHT_LEN), strip(rd(cls.FILES[1], np.int16), net.BIAS_LEN),
                    rd(cls.FILES[2], np.int32), rd(cls.FILES[3], np.int32), rd(cls.FILES[4], np.int32))
+
+
+def q8_from_stats(act_absmax, headroom: float = 1.0) -> np.ndarray:
+    """The int8 Q rule on explicit activation maxima [24] (yolo2_hip_calib_q8_from_stats; host arithmetic, no GPU): the largest q in
+    -8..24 with headroom * max * 2^q < 127.5, then the concat fix-up -> act_q [24]."""
+    a = np.ascontiguousarray(act_absmax, dtype=np.float32)
+    if a.shape != (len(net.CONVS) + 1,):
+        raise ValueError(f"maxima are [{len(net.CONVS) + 1}] activations")
+    aq = np.zeros(a.size, np.int32)
+    check(lib().yolo2_hip_calib_q8_from_stats(a.ctypes.data_as(C.c_void_p), headroom, aq.ctypes.data_as(C.c_void_p)),
+          "yolo2_hip_calib_q8_from_stats")
+    return aq
+
+
+class CalibratedModelI8:
+    """An int8 weight set made by Yolo2Hip.calibrate_int8: w8 int8 [50941792] in natural [N][C][K][K] order per layer, bias32 and
+    weight_q int32 [10761] (one per output channel), act_q int32 [24].  load_model takes it."""
+
+    FILES = ("weights_int8.bin", "bias_int32.bin", "weight_int8_Q.bin", "iofm_int8_Q.bin")
+
+    def __init__(self, w8, bias32, weight_q, act_q, act_absmax=None, frames_seen=0):
+        self.w8 = np.ascontiguousarray(w8, dtype=np.int8)
+        self.bias32, self.weight_q, self.act_q = (np.array(v, dtype=np.int32) for v in (bias32, weight_q, act_q))
+        if self.w8.shape != (N_WEIGHTS,) or self.bias32.shape != (N_BIAS,) or self.weight_q.shape != (N_BIAS,) or \
+                self.act_q.shape != (len(net.CONVS) + 1,):
+            raise ValueError("not a YOLOv2 int8 weight set")
+        self.act_absmax, self.frames_seen = act_absmax, int(frames_seen)
+
+    def write_files(self, weights_dir: str):
+        os.makedirs(weights_dir, exist_ok=True)
+        paths = {}
+        for name, arr in zip(self.FILES, (self.w8, self.bias32, self.weight_q, self.act_q)):
+            paths[name] = os.path.join(weights_dir, name)
+            arr.tofile(paths[name])
+        return paths
+
+    @classmethod
+    def read_files(cls, weights_dir: str):
+        rd = lambda name, dt: np.fromfile(os.path.join(weights_dir, name), dtype=dt)
+        return cls(rd(cls.FILES[0], np.int8), rd(cls.FILES[1], np.int32), rd(cls.FILES[2], np.int32), rd(cls.FILES[3], np.int32))
 
 
 # ------------------------------------------------------------------ post-processing on the GPU
