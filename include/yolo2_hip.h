@@ -685,7 +685,8 @@ int yolo2_hip_quantize_weights_int16(yolo2_hip_ctx *ctx, const int32_t *weight_q
  * s = Qin + Qw - act_q[o + 1]; y = (acc + 2^(s-1)) >> s for s > 0, acc << -s (64 bits) otherwise; out = clamp(y, -128, 127).
  * Pool is a 2x2 max, reorg the legacy Darknet indexing, route is placement.  Layer 30 is not requantised:
  * region = (float)acc * 2^-(Qin + Qw), round-to-nearest conversion and an exact scaling.
- * The images, pix, loop and multi-GPU entries have no int8 form. */
+ * Entries: frames in HBM (yolo2_hip_run_batch_int8) and image bytes on the host (yolo2_hip_run_images_pix_int8_host / _dets_int8,
+ * below).  The loop and multi-GPU entries have no int8 form. */
 
 /* The int8 Q rule on explicit maxima (host arithmetic only, no GPU): act_absmax[24] as yolo2_hip_calib_stats returns them ->
  * act_q[24], fix-up applied. */
@@ -710,9 +711,29 @@ int yolo2_hip_load_weights_int8(yolo2_hip_ctx *ctx, const int8_t *w8, size_t n_w
 int yolo2_hip_run_batch_int8(yolo2_hip_ctx *ctx, uint64_t frames_dev, int batch, uint64_t region_dev, void *stream);
 /* The same with host buffers, blocking. */
 int yolo2_hip_run_batch_int8_host(yolo2_hip_ctx *ctx, const float *frames, int batch, float *region);
+/* Image bytes to region tensors / detection records on the int8 pass, single device: the contract of
+ * yolo2_hip_run_images_pix_f16_host / _dets_f16 (chunks of `batch` images, 1..1024, a ragged last chunk repeats its last image;
+ * staging, upload, kernels and download overlap on the context's three streams; region_host float [n][425][13][13]; the records
+ * come from the float tail, flags YOLO2_DETS_BEST_CLASS / YOLO2_DETS_APP_TAIL).  pixfmt YOLO2_PIX_GREY8 / _RGB24 / _YUYV.
+ * One kernel (k_i8_front_u8 / k_i8_front_yuyv) goes from the chunk's bytes to layer 1's tensor: letterbox, the input rule above,
+ * layer 0 with its 27 inputs in one k step of v_mfma_i32_32x32x32_i8, and the 2x2 pool.  The result equals, bit for bit, the chunk
+ * letterboxed (yolo2_hip_letterbox_pix) and run through yolo2_hip_run_batch_int8, which is what the entries do under option
+ * i8_no_front.  The quantised input and layer 0's tensor (2 * batch * 416 * 416 * 32 bytes) are not allocated on this route.
+ * Refused before any launch: int8 weights not loaded, a null pointer or image, n, batch or cap_per_frame <= 0, thresh < 0, an
+ * unknown pixfmt, an odd YUYV width, an image size the letterbox refuses. */
+int yolo2_hip_run_images_pix_int8_host(yolo2_hip_ctx *ctx, const uint8_t *const *images, const int *widths, const int *heights,
+                                       int pixfmt, int n, int batch, float *region_host);
+int yolo2_hip_run_images_pix_dets_int8(yolo2_hip_ctx *ctx, const uint8_t *const *images, const int *widths, const int *heights,
+                                       int pixfmt, int n, int batch, float thresh, float nms, int flags, yolo2_hip_det *dets,
+                                       int cap_per_frame, int *counts);
+/* What the last int8 images call on ctx ran up to layer 1: "k_i8_front_u8" or "k_i8_front_yuyv"; under i8_no_front
+ * "k_letterbox_u8_batch + k_i8_quant_input + k_conv_i8" (or k_letterbox_yuyv_batch ...); "" before the first call. */
+const char *yolo2_hip_images_front_kernel_int8(yolo2_hip_ctx *ctx);
 /* Parity hook: the int8 tensor layer `layer_idx` (0..29; -1 = the quantised input) left behind in the last int8 run, frame `frame`,
  * as dense [C][H][W] into out (cap elements).  geom[4] = {C, H, W, Q}; out may be NULL to ask for the geometry only.  Locates a
- * wrong layer without another run. */
+ * wrong layer without another run.  After an images call it reads the call's last chunk (frame: the index inside that chunk); the
+ * fused front kernel writes neither the quantised input nor layer 0, so layers -1 and 0 are then YOLO2_ERROR ("fused"); under
+ * i8_no_front and after a frames run they are readable. */
 int yolo2_hip_debug_i8_tensor(yolo2_hip_ctx *ctx, int layer_idx, int frame, int8_t *out, size_t cap, int *geom);
 /* Driver-tier single layer beside yolo2_execute_conv_layer / _f32: one stride-1 "same" conv of any ifm_num, ofm_num, ksize 1 or 3,
  * size and batch through the int8 kernel.  Device buffers in natural dense order: input int8 [batch][ifm][H][W], weights int8

@@ -1,4 +1,5 @@
 // kernels_i8.hpp -- the int8 pass on the i8 matrix cores (yolo2_int8.hip launches everything here).
+// (kernels_i8_front.hpp, which includes this file, holds the images entries' kernel from image bytes to layer 1.)
 //
 // Arithmetic (include/yolo2_hip.h "int8 pass"): acc = bias32 + sum(w8 * x8) in int32, leaky = acc / 10 truncating on the accumulator,
 // one rounding shift per output channel down to the int8 output, or - layer 30 - (float)acc scaled by a power of two.  The int32 sum
@@ -172,7 +173,15 @@ __global__ __launch_bounds__(256) void k_conv_i8(const ConvI8Args a)
 
 // ------------------------------------------------------------------ the small kernels of the pass
 
-// x8 = clamp(round_half_away(x * 2^q), -128, 127) of float frames [B][3][HW] -> [B * HW][32], channels 3..31 zero
+// the input rule of the header: x8 = clamp(round_half_away(x * scale), -128, 127), NaN -> 0; scale = 2^act_q[0].  The one definition
+// behind k_i8_quant_input and k_i8_front_pix (kernels_i8_front.hpp).
+__device__ __forceinline__ int i8_quant_input(float x, float scale)
+{
+    const float v = roundf(__fmul_rn(x, scale));
+    return (int)(v != v ? 0.f : fminf(fmaxf(v, -128.f), 127.f));
+}
+
+// x8 = i8_quant_input(x, 2^q) of float frames [B][3][HW] -> [B * HW][32], channels 3..31 zero
 __global__ __launch_bounds__(256) void k_i8_quant_input(const float *__restrict__ frames, signed char *__restrict__ out, int q, int HW, long n)
 {
     const long t = (long)blockIdx.x * 256 + threadIdx.x;
@@ -181,11 +190,7 @@ __global__ __launch_bounds__(256) void k_i8_quant_input(const float *__restrict_
     const float scale = ldexpf(1.0f, q);
     unsigned w = 0;
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        float v = roundf(__fmul_rn(frames[(f * 3 + c) * HW + r], scale));
-        v = v != v ? 0.f : fminf(fmaxf(v, -128.f), 127.f);
-        w |= (unsigned)((int)v & 0xff) << (8 * c);
-    }
+    for (int c = 0; c < 3; ++c) w |= (unsigned)(i8_quant_input(frames[(f * 3 + c) * HW + r], scale) & 0xff) << (8 * c);
     int4 *o = reinterpret_cast<int4 *>(out + t * 32);
     o[0] = make_int4((int)w, 0, 0, 0);
     o[1] = make_int4(0, 0, 0, 0);

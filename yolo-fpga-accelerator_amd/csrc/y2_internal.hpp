@@ -7,7 +7,8 @@
 //   yolo2_fp16.hip    the fp16 MFMA path: weight packing, per-context launch table, run_batch_fp16
 //   yolo2_fp32.hip    the exact fp32 path (tiled and one-thread-per-output)
 //   yolo2_calib.hip   fp32 weights + calibration frames -> Q tables and int16 weights (statistics of the exact fp32 pass)
-//   yolo2_int8.hip    the int8 pass on the i8 matrix cores: quantiser, loader and its proofs, run_batch_int8, the single-layer call
+//   yolo2_int8.hip    the int8 pass on the i8 matrix cores: quantiser, loader and its proofs, run_batch_int8, the pass from a chunk of
+//                     image bytes (k_i8_front_pix + layers 2..30), the single-layer call
 //   yolo2_post.hip    region layer + boxes + NMS;   yolo2_multi.hip  frame sharding + the RCCL weight broadcast
 //   yolo2_draw.hip    annotated frames: records + frames -> RGB24 with the reference's boxes and tags
 //   yolo2_jpeg.hip    RGB24 frames in device memory -> the reference's JPEG streams
@@ -74,6 +75,8 @@ struct Y2Options {
     bool f16_no_lanes = false, f16_no_mfma0 = false, f16_no_glds = false, f16_no_poolfuse = false, f16_no_halo = false, f16_no_persist = false,
          f16_persist_all = false, f16_ring_all = false, f16_no_ring = false, f16_no_c32 = false, f16_m16 = false, f16_w8 = false, f16_no_wide = false,
          f16_no_fuse1x1 = false, f16_no_rw = false, f16_no_rwb = false, f16_no_rwc = false, f16_ring256 = false, f16_ring_sq = false;
+    bool i8_no_front = false;     // the int8 images entries letterbox into float frames and run the frames route (the reference route of
+                                  // k_i8_front_pix's tests and report, as f16_no_mfma0 is for the fp16 entries)
     int stamp_layer = -1;
     int f16_skip = 0;             // DIAGNOSTIC (results wrong by construction): bit mask of fp16 launches left out of the table, to measure
                                   // what a launch costs INSIDE the two-lane step: 1 = 1x1 layers 5 and 9, 2 = layer 0, 4 = layers 2/4/6,
@@ -327,6 +330,7 @@ struct yolo2_hip_ctx {
     Y2DevBuf<float> biasf_own, w0f_own, wf32_own, bf32_own;
     F16Plan *f16_plan = nullptr;              // launch table of the fp16 pass (built once per (weights, batch); owned)
     std::string images_l0[2];                 // what the last fp16 (0) / split (1) images call ran for layers 0+1 (yolo2_hip_images_layer0_kernel)
+    std::string images_front_i8;              // what the last int8 images call ran up to layer 1 (yolo2_hip_images_front_kernel_int8)
     // ---- tiled exact fp32 path (kernels_f32.hpp): packed weights [mb][cg][tap][32][4] floats, items of 4 floats
     float *wpkf = nullptr, *biasf32_pk = nullptr;
     Y2DevBuf<float> wpkf_own, biasf32_pk_own;
@@ -451,6 +455,13 @@ void y2_drv_conv_f32(const float *in, float *out, const float *w, const float *b
 int y2_drv_conv_i8(uint64_t in, uint64_t out, uint64_t w, uint64_t bias, const int32_t *weight_q, int C, int N, int K, int W, int H, int batch,
                    int q_in, int q_out, int leaky, int out_float);
 void y2_i8_free(yolo2_hip_ctx *c);
+// The int8 images entries (yolo2_hip.hip), the siblings of y2_f16_images_fused / y2_f16_run_images / y2_f16_images_kernel:
+// y2_i8_images_fused is false under i8_no_front (the entries then letterbox into frames and call yolo2_hip_run_batch_int8);
+// y2_i8_run_images runs k_i8_front_pix on the chunk's staging buffer at lb into layer 1's tensor and layers 2..30 behind it, on st.
+bool y2_i8_loaded(const yolo2_hip_ctx *c);
+bool y2_i8_images_fused(const yolo2_hip_ctx *c);
+int y2_i8_run_images(yolo2_hip_ctx *c, const uint8_t *lb, bool yuyv, int batch, float *region_dev, hipStream_t st);
+const char *y2_i8_front_kernel(bool yuyv);
 
 // yolo2_draw.hip: the streams, events and buffers of c->anno (yolo2_hip_destroy)
 void y2_anno_free(yolo2_hip_ctx *c);

@@ -784,17 +784,20 @@ int y2_pipe_enqueue_f16(yolo2_hip_ctx *c, yolo2_hip_ctx *run, bool fused, int b,
     return YOLO2_SUCCESS;
 }
 
-// dets == nullptr: region tensors to region_host; otherwise the records (the int16 dets entry's contract)
-static int run_images_f16(yolo2_hip_ctx *c, int split, const uint8_t *const *images, const int *widths, const int *heights, int channels,
-                          bool pix, int n, int batch, float *region_host, float thresh, float nms, int flags, yolo2_hip_det *dets, int cap,
-                          int *counts)
+// The chunk loop of the images entries whose pass leaves an fp32 region tensor (fp16, split-fp16, int8).
+// dets == nullptr: region tensors to region_host; otherwise the records (the int16 dets entry's contract).
+// resolve(): the pass's own refusals (weights not loaded ...), called after the argument checks and before anything is touched;
+// enqueue(b, yuyv, batch): the network of the chunk in buffer set b on s_run into dregf[b], e_run[b] recorded behind it.
+template <class Resolve, class Enqueue>
+static int run_images_regf(yolo2_hip_ctx *c, const uint8_t *const *images, const int *widths, const int *heights, int channels, bool pix, int n,
+                           int batch, float *region_host, float thresh, float nms, int flags, yolo2_hip_det *dets, int cap, int *counts,
+                           Resolve resolve, Enqueue enqueue)
 {
     const bool want_dets = dets != nullptr, yuyv = channels == 2;
     if (n <= 0 || batch <= 0 || (want_dets && cap <= 0))
         return fail(YOLO2_ERROR, "bad image count %d / batch %d / capacity %d", n, batch, want_dets ? cap : 1);
     if (want_dets && thresh < 0.f) return fail(YOLO2_ERROR, "negative threshold");
-    yolo2_hip_ctx *run = nullptr;
-    int rc = y2_f16_images_ctx(c, split, &run);
+    int rc = resolve();
     if (rc) return rc;
     HIP_TRY(hipSetDevice(c->device), YOLO2_INIT_ERROR);
     batch = std::min(batch, n);
@@ -814,8 +817,7 @@ static int run_images_f16(yolo2_hip_ctx *c, int split, const uint8_t *const *ima
         }
         cap_bytes = std::max(cap_bytes, sum);
     }
-    const bool fused = y2_f16_images_fused(run);
-    if ((rc = y2_pipe_ensure(c->pipe, cap_bytes, cap_bytes, batch, false))) return rc;      // (din: the frames of the f16_no_mfma0 route)
+    if ((rc = y2_pipe_ensure(c->pipe, cap_bytes, cap_bytes, batch, false))) return rc;      // (din: the frames of the f16_no_mfma0 / i8_no_front route)
     if ((rc = y2_pipe_ensure_regf(c->pipe, batch, !want_dets))) return rc;
     if (want_dets && (rc = y2_pipe_ensure_post(c, batch, cap))) return rc;
     PipeBufs &P = c->pipe;
@@ -862,7 +864,7 @@ static int run_images_f16(yolo2_hip_ctx *c, int split, const uint8_t *const *ima
         if (want_dets) Y2_TRY(hipMemcpyAsync(P.post[b].geom.get(), P.hgeom[b].get(), (size_t)batch * gbytes, hipMemcpyHostToDevice, P.s_in), YOLO2_DMA_ERROR);
         Y2_TRY(hipEventRecord(P.e_in[b], P.s_in), YOLO2_ERROR);
         Y2_TRY(hipStreamWaitEvent(P.s_run, P.e_in[b], 0), YOLO2_ERROR);
-        if ((rc = y2_pipe_enqueue_f16(c, run, fused, b, yuyv, batch))) break;
+        if ((rc = enqueue(b, yuyv, batch))) break;
         Y2_TRY(hipStreamWaitEvent(P.s_out, P.e_run[b], 0), YOLO2_ERROR);
         if (want_dets) {   // the tail on the download stream, straight from HBM (see yolo2_hip_run_images_u8_dets)
             if ((rc = y2_post_enqueue_f32(P.dregf[b].get(), batch, thresh, nms, cap, best_only, app_tail, &P.post[b], P.s_out))) break;
@@ -874,15 +876,85 @@ static int run_images_f16(yolo2_hip_ctx *c, int split, const uint8_t *const *ima
         }
         Y2_TRY(hipEventRecord(P.e_out[b], P.s_out), YOLO2_ERROR);
     }
-    if (rc == YOLO2_SUCCESS) {
+    if (rc == YOLO2_SUCCESS)
         for (int k = std::max(0, chunks - 2); k < chunks; ++k) drain(k);
-        c->images_l0[split] = fused ? std::string(y2_f16_images_kernel(run, yuyv))
-                                    : std::string(yuyv ? "k_letterbox_yuyv_batch + " : "k_letterbox_u8_batch + ") + yolo2_hip_fp16_layer_kernel(run, 0);
-    }
     cleanup();
 #undef Y2_TRY
     return rc;
 }
+
+static int run_images_f16(yolo2_hip_ctx *c, int split, const uint8_t *const *images, const int *widths, const int *heights, int channels,
+                          bool pix, int n, int batch, float *region_host, float thresh, float nms, int flags, yolo2_hip_det *dets, int cap,
+                          int *counts)
+{
+    yolo2_hip_ctx *run = nullptr;
+    bool fused = false;
+    const int rc = run_images_regf(
+        c, images, widths, heights, channels, pix, n, batch, region_host, thresh, nms, flags, dets, cap, counts,
+        [&]() {
+            const int r = y2_f16_images_ctx(c, split, &run);
+            if (r == YOLO2_SUCCESS) fused = y2_f16_images_fused(run);
+            return r;
+        },
+        [&](int b, bool yuyv, int bt) { return y2_pipe_enqueue_f16(c, run, fused, b, yuyv, bt); });
+    if (rc == YOLO2_SUCCESS)
+        c->images_l0[split] = fused ? std::string(y2_f16_images_kernel(run, channels == 2))
+                                    : std::string(channels == 2 ? "k_letterbox_yuyv_batch + " : "k_letterbox_u8_batch + ") + yolo2_hip_fp16_layer_kernel(run, 0);
+    return rc;
+}
+
+// ... and on the int8 pass (include/yolo2_hip.h "int8 pass"): k_i8_front_pix reads the chunk's bytes and writes layer 1's tensor; under
+// i8_no_front the chunk is letterboxed into frames and the frames route runs (the reference route of the tests and the report).
+static int run_images_i8(yolo2_hip_ctx *c, const uint8_t *const *images, const int *widths, const int *heights, int channels, int n, int batch,
+                         float *region_host, float thresh, float nms, int flags, yolo2_hip_det *dets, int cap, int *counts)
+{
+    bool fused = false;
+    const int rc = run_images_regf(
+        c, images, widths, heights, channels, true, n, batch, region_host, thresh, nms, flags, dets, cap, counts,
+        [&]() {
+            if (!y2_i8_loaded(c)) return fail(YOLO2_ERROR, "int8 weights not loaded (yolo2_hip_load_weights_int8)");
+            if (batch > 1024) return fail(YOLO2_ERROR, "batch %d out of range 1..1024", batch);
+            fused = y2_i8_images_fused(c);
+            return (int)YOLO2_SUCCESS;
+        },
+        [&](int b, bool yuyv, int bt) {
+            PipeBufs &P = c->pipe;
+            int r;
+            if (fused) {
+                r = y2_i8_run_images(c, P.dbytes[b].get(), yuyv, bt, P.dregf[b].get(), P.s_run);
+            } else {
+                y2_launch_letterbox_batch(yuyv, P.dbytes[b].get(), P.din[b].get(), bt, P.s_run);
+                HIP_TRY(hipGetLastError(), YOLO2_ERROR);
+                r = yolo2_hip_run_batch_int8(c, (uint64_t)(uintptr_t)P.din[b].get(), bt, (uint64_t)(uintptr_t)P.dregf[b].get(), P.s_run);
+            }
+            if (r) return r;
+            HIP_TRY(hipEventRecord(P.e_run[b], P.s_run), YOLO2_ERROR);
+            return (int)YOLO2_SUCCESS;
+        });
+    if (rc == YOLO2_SUCCESS)
+        c->images_front_i8 = fused ? std::string(y2_i8_front_kernel(channels == 2))
+                                   : std::string(channels == 2 ? "k_letterbox_yuyv_batch" : "k_letterbox_u8_batch") + " + k_i8_quant_input + k_conv_i8";
+    return rc;
+}
+
+extern "C" int yolo2_hip_run_images_pix_int8_host(yolo2_hip_ctx *c, const uint8_t *const *images, const int *widths, const int *heights,
+                                                  int pixfmt, int n, int batch, float *region_host)
+{
+    if (!c || !images || !widths || !heights || !region_host) return fail(YOLO2_ERROR, "null argument");
+    const int ch = y2_pix_channels(pixfmt);
+    return ch ? run_images_i8(c, images, widths, heights, ch, n, batch, region_host, 0.f, 0.f, 0, nullptr, 0, nullptr) : YOLO2_ERROR;
+}
+
+extern "C" int yolo2_hip_run_images_pix_dets_int8(yolo2_hip_ctx *c, const uint8_t *const *images, const int *widths, const int *heights,
+                                                  int pixfmt, int n, int batch, float thresh, float nms, int flags, yolo2_hip_det *dets,
+                                                  int cap_per_frame, int *counts)
+{
+    if (!c || !images || !widths || !heights || !dets || !counts) return fail(YOLO2_ERROR, "null argument");
+    const int ch = y2_pix_channels(pixfmt);
+    return ch ? run_images_i8(c, images, widths, heights, ch, n, batch, nullptr, thresh, nms, flags, dets, cap_per_frame, counts) : YOLO2_ERROR;
+}
+
+extern "C" const char *yolo2_hip_images_front_kernel_int8(yolo2_hip_ctx *c) { return c ? c->images_front_i8.c_str() : ""; }
 
 extern "C" int yolo2_hip_run_images_u8_f16_host(yolo2_hip_ctx *c, int split, const uint8_t *const *images, const int *widths,
                                                 const int *heights, int channels, int n, int batch, float *region_host)

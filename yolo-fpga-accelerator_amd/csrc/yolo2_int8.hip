@@ -1,6 +1,7 @@
 // yolo2_int8.hip -- the int8 pass (include/yolo2_hip.h "int8 pass"): the weight quantiser, the loader with its
 // refusals and the device-side weight packing, run_batch_int8, the parity hook and the driver tier's single-layer device work.
-// One stream, no lanes; every launch is in this file (kernels_i8.hpp).
+// One stream, no lanes; every launch is in this file (kernels_i8.hpp, kernels_i8_front.hpp).  y2_i8_run_images is the pass from a
+// chunk of image bytes: k_i8_front_pix into layer 1's tensor, then the frames route's layers 2..30.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -9,6 +10,7 @@
 
 #include "y2_internal.hpp"
 #include "kernels_i8.hpp"
+#include "kernels_i8_front.hpp"
 
 using namespace y2;
 
@@ -22,10 +24,13 @@ struct Y2I8 {
     bool loaded = false;
     int act_q[YOLO2_N_CONV + 1] = {};
     Y2DevBuf<signed char> wpk;       // all layers, [tap][chunk][Np][32] each
+    Y2DevBuf<signed char> w0front;   // layer 0 again as k_i8_front_pix's A fragments (front_pack_weights, 1 KB)
     Y2DevBuf<int> bias, sh;          // all layers, padded to Np each
     long wpk_off[YOLO2_N_CONV] = {}, ch_off[YOLO2_N_CONV] = {};
     int Np[YOLO2_N_CONV] = {};
     int batch = 0, last_batch = 0;
+    bool front_tensors = false;      // t_in and t[0] are allocated (the frames route; the images route never touches them)
+    bool last_fused = false;         // the last run wrote t[1] with k_i8_front_pix: t_in and t[0] hold nothing of it
     Y2I8Tensor t_in, t[32];
 };
 
@@ -99,14 +104,29 @@ int need_i8(const yolo2_hip_ctx *c)
     return YOLO2_SUCCESS;
 }
 
-// the activation tensors of the pass for `batch` frames (kept until the batch or the weight set changes)
-int ensure_tensors(Y2I8 *s, int batch)
+// the activation tensors of the pass for `batch` frames (kept until the batch or the weight set changes).  front: with the quantised
+// input and layer 0's tensor (2 * batch * 416 * 416 * 32 bytes), which only the frames route reads and writes: they are allocated at
+// the first frames run at this batch.
+int ensure_tensors(Y2I8 *s, int batch, bool front)
 {
-    if (s->batch == batch) return YOLO2_SUCCESS;
-    s->batch = 0;
     int rc;
+    if (s->batch == batch) {
+        if (front && !s->front_tensors) {
+            for (Y2I8Tensor *t : {&s->t_in, &s->t[0]})
+                if ((rc = y2_alloc_owned(t->own, t->d, (size_t)batch * t->H * t->W * t->cs))) return rc;
+            s->front_tensors = true;
+        }
+        return YOLO2_SUCCESS;
+    }
+    s->batch = 0;
+    s->front_tensors = false;
     auto make = [&](Y2I8Tensor &t, int C, int H, int W, int q) {
         t.C = C; t.cs = round_up(C, kI8Granule); t.H = H; t.W = W; t.q = q;
+        if (!front && (&t == &s->t_in || &t == &s->t[0])) {   // geometry only
+            t.own.reset();
+            t.d = nullptr;
+            return (int)YOLO2_SUCCESS;
+        }
         return y2_alloc_owned(t.own, t.d, (size_t)batch * H * W * t.cs);
     };
     auto view = [&](Y2I8Tensor &t, const Y2I8Tensor &of, int ch0, int C, int q) {
@@ -141,6 +161,50 @@ int ensure_tensors(Y2I8 *s, int batch)
         cur = &t;
     }
     s->batch = batch;
+    s->front_tensors = front;
+    return YOLO2_SUCCESS;
+}
+
+// layers first..30 of the pass on `cur` (the tensor layer `first` reads; `ord` = its conv ordinal), shared by the frames route
+// (first = 0) and the images route (first = 2); ev[i + 1] is recorded behind layer i
+int run_layers(Y2I8 *s, int first, const Y2I8Tensor *cur, int ord, int batch, uint64_t region_dev, hipStream_t st, hipEvent_t *ev)
+{
+    for (int i = first; i < 32; ++i) {
+        const LayerDesc &l = kNet[i];
+        if (l.type == L_CONV) {
+            if (cur->C != l.c || cur->H != l.h || cur->W != l.w) return fail(YOLO2_ERROR, "int8 pass: layer %d does not fit the tensor it reads", i);
+            ConvI8Args a;
+            a.in = cur->d;
+            a.w = s->wpk.get() + s->wpk_off[ord];
+            a.bias = s->bias.get() + s->ch_off[ord];
+            a.sh = s->sh.get() + s->ch_off[ord];
+            a.CC = cur->cs / 32;
+            a.K = l.size; a.H = l.h; a.W = l.w; a.P = batch * l.h * l.w;
+            a.N = l.n; a.Np = s->Np[ord]; a.leaky = l.leaky;
+            if (i == 30) {
+                a.out = (void *)(uintptr_t)region_dev;
+                a.ocs = 0;
+            } else {
+                a.out = s->t[i].d;
+                a.ocs = s->t[i].cs;
+                cur = &s->t[i];
+            }
+            launch_conv(a, i == 30, st);
+            ord++;
+        } else if (l.type == L_MAX) {
+            const long n = (long)batch * (l.h / 2) * (l.w / 2) * (cur->cs / 16);
+            hipLaunchKernelGGL(k_i8_pool, dim3(blocks_for(n, 256)), dim3(256), 0, st, (const signed char *)cur->d, s->t[i].d, l.h, l.w, cur->cs, n);
+            cur = &s->t[i];
+        } else if (l.type == L_ROUTE) {
+            cur = &s->t[i];
+        } else if (l.type == L_REORG) {
+            hipLaunchKernelGGL(k_i8_reorg, dim3(blocks_for((long)batch * 256 * 169, 256)), dim3(256), 0, st, (const signed char *)cur->d, s->t[i].d, batch,
+                               cur->cs, s->t[i].cs);
+            cur = &s->t[i];
+        }
+        if (ev) (void)hipEventRecord(ev[i + 1], st);
+    }
+    HIP_TRY(hipGetLastError(), YOLO2_ERROR);
     return YOLO2_SUCCESS;
 }
 
@@ -237,8 +301,15 @@ extern "C" int yolo2_hip_load_weights_int8(yolo2_hip_ctx *c, const int8_t *w8, s
     s->last_batch = 0;
     int rc;
     Y2DevBuf<signed char> nat;
-    if ((rc = nat.alloc(YOLO2_N_WEIGHTS)) || (rc = s->wpk.alloc(wtot)) || (rc = s->bias.alloc(ctot)) || (rc = s->sh.alloc(ctot))) return rc;
+    if ((rc = nat.alloc(YOLO2_N_WEIGHTS)) || (rc = s->wpk.alloc(wtot)) || (rc = s->w0front.alloc(32 * 32)) || (rc = s->bias.alloc(ctot)) ||
+        (rc = s->sh.alloc(ctot)))
+        return rc;
     HIP_TRY(hipMemcpy(nat.get(), w8, (size_t)YOLO2_N_WEIGHTS, hipMemcpyHostToDevice), YOLO2_DMA_ERROR);
+    {   // layer 0 (the first 32 * 27 of w8) in the front kernel's fragment order, from the same natural-order bytes
+        int8_t front[32 * 32];
+        front_pack_weights(w8, front);
+        HIP_TRY(hipMemcpy(s->w0front.get(), front, sizeof(front), hipMemcpyHostToDevice), YOLO2_DMA_ERROR);
+    }
     std::vector<int> bias_host(ctot, 0);
     {
         long woff = 0, boff = 0;
@@ -277,10 +348,8 @@ extern "C" int yolo2_hip_run_batch_int8(yolo2_hip_ctx *c, uint64_t frames_dev, i
     HIP_TRY(hipSetDevice(c->device), YOLO2_INIT_ERROR);
     Y2I8 *s = c->i8;
     hipStream_t st = (hipStream_t)stream;
-    if (s->batch != batch) {
-        HIP_TRY(hipDeviceSynchronize(), YOLO2_ERROR);   // the tensors of the previous batch may still be read
-        if ((rc = ensure_tensors(s, batch))) return rc;
-    }
+    if (s->batch != batch) HIP_TRY(hipDeviceSynchronize(), YOLO2_ERROR);   // the tensors of the previous batch may still be read
+    if ((rc = ensure_tensors(s, batch, true))) return rc;
     if (c->prof && (rc = y2_ensure_prof_events(c))) return rc;
     hipEvent_t *ev = c->prof ? c->ev[c->prof_runs % yolo2_hip_ctx::kProfSlots] : nullptr;
     {
@@ -289,46 +358,50 @@ extern "C" int yolo2_hip_run_batch_int8(yolo2_hip_ctx *c, uint64_t frames_dev, i
                            s->act_q[0], 416 * 416, n);
     }
     if (ev) HIP_TRY(hipEventRecord(ev[0], st), YOLO2_ERROR);
-    const Y2I8Tensor *cur = &s->t_in;
-    int ord = 0;
-    for (int i = 0; i < 32; ++i) {
-        const LayerDesc &l = kNet[i];
-        if (l.type == L_CONV) {
-            if (cur->C != l.c || cur->H != l.h || cur->W != l.w) return fail(YOLO2_ERROR, "int8 pass: layer %d does not fit the tensor it reads", i);
-            ConvI8Args a;
-            a.in = cur->d;
-            a.w = s->wpk.get() + s->wpk_off[ord];
-            a.bias = s->bias.get() + s->ch_off[ord];
-            a.sh = s->sh.get() + s->ch_off[ord];
-            a.CC = cur->cs / 32;
-            a.K = l.size; a.H = l.h; a.W = l.w; a.P = batch * l.h * l.w;
-            a.N = l.n; a.Np = s->Np[ord]; a.leaky = l.leaky;
-            if (i == 30) {
-                a.out = (void *)(uintptr_t)region_dev;
-                a.ocs = 0;
-            } else {
-                a.out = s->t[i].d;
-                a.ocs = s->t[i].cs;
-                cur = &s->t[i];
-            }
-            launch_conv(a, i == 30, st);
-            ord++;
-        } else if (l.type == L_MAX) {
-            const long n = (long)batch * (l.h / 2) * (l.w / 2) * (cur->cs / 16);
-            hipLaunchKernelGGL(k_i8_pool, dim3(blocks_for(n, 256)), dim3(256), 0, st, (const signed char *)cur->d, s->t[i].d, l.h, l.w, cur->cs, n);
-            cur = &s->t[i];
-        } else if (l.type == L_ROUTE) {
-            cur = &s->t[i];
-        } else if (l.type == L_REORG) {
-            hipLaunchKernelGGL(k_i8_reorg, dim3(blocks_for((long)batch * 256 * 169, 256)), dim3(256), 0, st, (const signed char *)cur->d, s->t[i].d, batch,
-                               cur->cs, s->t[i].cs);
-            cur = &s->t[i];
-        }
-        if (ev) (void)hipEventRecord(ev[i + 1], st);
-    }
-    HIP_TRY(hipGetLastError(), YOLO2_ERROR);
+    if ((rc = run_layers(s, 0, &s->t_in, 0, batch, region_dev, st, ev))) return rc;
     if (ev) c->prof_runs++;
     s->last_batch = batch;
+    s->last_fused = false;
+    return YOLO2_SUCCESS;
+}
+
+// (y2_internal.hpp) The pass on a chunk of `batch` images whose staging buffer is at lb: the front kernel into layer 1's tensor, then
+// layers 2..30.  Profiling: the front's time is layer 1's slot (ev[1] .. ev[2]); layer 0's slot is empty.
+bool y2_i8_loaded(const yolo2_hip_ctx *c) { return c && c->i8 && c->i8->loaded; }
+bool y2_i8_images_fused(const yolo2_hip_ctx *c) { return !c->opt.i8_no_front; }
+const char *y2_i8_front_kernel(bool yuyv) { return yuyv ? "k_i8_front_yuyv" : "k_i8_front_u8"; }
+
+int y2_i8_run_images(yolo2_hip_ctx *c, const uint8_t *lb, bool yuyv, int batch, float *region_dev, hipStream_t st)
+{
+    int rc = need_i8(c);
+    if (rc) return rc;
+    if (!lb || !region_dev) return fail(YOLO2_ERROR, "null buffer address");
+    if (batch <= 0 || batch > 1024) return fail(YOLO2_ERROR, "batch %d out of range 1..1024", batch);
+    Y2I8 *s = c->i8;
+    if (s->batch != batch) HIP_TRY(hipDeviceSynchronize(), YOLO2_ERROR);   // the tensors of the previous batch may still be read
+    if ((rc = ensure_tensors(s, batch, false))) return rc;
+    if (c->prof && (rc = y2_ensure_prof_events(c))) return rc;
+    hipEvent_t *ev = c->prof ? c->ev[c->prof_runs % yolo2_hip_ctx::kProfSlots] : nullptr;
+    if (ev) {
+        HIP_TRY(hipEventRecord(ev[0], st), YOLO2_ERROR);
+        HIP_TRY(hipEventRecord(ev[1], st), YOLO2_ERROR);
+    }
+    FrontI8Args a;
+    a.lb = lb;
+    a.w = s->w0front.get();
+    a.bias = s->bias.get() + s->ch_off[0];
+    a.sh = s->sh.get() + s->ch_off[0];
+    a.out = s->t[1].d;
+    a.q0 = s->act_q[0];
+    a.leaky = kNet[0].leaky;
+    const dim3 grid((unsigned)batch * kFrontTilesPerFrame), block(256);
+    if (yuyv) hipLaunchKernelGGL(k_i8_front_pix<LbYuyv>, grid, block, 0, st, a);
+    else hipLaunchKernelGGL(k_i8_front_pix<LbInterleaved>, grid, block, 0, st, a);
+    if (ev) (void)hipEventRecord(ev[2], st);
+    if ((rc = run_layers(s, 2, &s->t[1], 1, batch, (uint64_t)(uintptr_t)region_dev, st, ev))) return rc;
+    if (ev) c->prof_runs++;
+    s->last_batch = batch;
+    s->last_fused = true;
     return YOLO2_SUCCESS;
 }
 
@@ -349,6 +422,9 @@ extern "C" int yolo2_hip_debug_i8_tensor(yolo2_hip_ctx *c, int layer_idx, int fr
     if (s->last_batch <= 0 || s->batch != s->last_batch) return fail(YOLO2_ERROR, "no int8 run to read (yolo2_hip_run_batch_int8)");
     if (layer_idx < -1 || layer_idx > 29) return fail(YOLO2_ERROR, "layer %d holds no int8 tensor (-1 = the quantised input, 0..29)", layer_idx);
     if (frame < 0 || frame >= s->last_batch) return fail(YOLO2_ERROR, "frame %d outside the last batch of %d", frame, s->last_batch);
+    if (layer_idx < 1 && s->last_fused)
+        return fail(YOLO2_ERROR, "layer %d was not written: the last int8 run was an images call, whose fused front kernel goes from the image bytes to "
+                                 "layer 1 (option i8_no_front runs the frames route)", layer_idx);
     const Y2I8Tensor &t = layer_idx < 0 ? s->t_in : s->t[layer_idx];
     if (!t.d) return fail(YOLO2_ERROR, "layer %d holds no int8 tensor", layer_idx);
     if (geom) { geom[0] = t.C; geom[1] = t.H; geom[2] = t.W; geom[3] = t.q; }

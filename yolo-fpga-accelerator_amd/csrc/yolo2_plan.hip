@@ -22,6 +22,11 @@ struct FlagOpt { const char *name; bool Y2Options::*m; };
 struct IntOpt { const char *name; int Y2Options::*m; int lo, hi; };
 struct StrOpt { const char *name; std::string Y2Options::*m; };
 
+// The int8 pass's switches, a table of their own: kFlags below is audited as the int16 planner's and the fp16 table's switches
+// (tests/test_i16_plans_host.py, tests/test_f16_layer_ref.py), and these steer neither.  Same mechanics: set, environment, describe.
+const FlagOpt kI8Flags[] = {
+    {"i8_no_front", &Y2Options::i8_no_front},
+};
 const FlagOpt kFlags[] = {
     {"no_lanes", &Y2Options::no_lanes}, {"verbose", &Y2Options::verbose}, {"no_plan_cache", &Y2Options::no_plan_cache},
     {"no_poolfuse", &Y2Options::no_poolfuse}, {"no_hiacc", &Y2Options::no_hiacc}, {"no_ks", &Y2Options::no_ks},
@@ -49,11 +54,15 @@ int Y2Options::set(const char *name, const char *value)
     if (!name) return -1;
     const Y2Options dflt;
     const bool clear = !value || !value[0];
+    auto flag = [&](const FlagOpt &f) {   // a flag is on for any value except "0"
+        if (strcmp(name, f.name)) return false;
+        this->*f.m = clear ? dflt.*f.m : strcmp(value, "0") != 0;
+        return true;
+    };
     for (const FlagOpt &f : kFlags)
-        if (!strcmp(name, f.name)) {   // a flag is on for any value except "0"
-            this->*f.m = clear ? dflt.*f.m : strcmp(value, "0") != 0;
-            return 0;
-        }
+        if (flag(f)) return 0;
+    for (const FlagOpt &f : kI8Flags)
+        if (flag(f)) return 0;
     for (const IntOpt &o : kInts)
         if (!strcmp(name, o.name)) {
             if (clear) { this->*o.m = dflt.*o.m; return 0; }
@@ -87,6 +96,7 @@ Y2Options Y2Options::from_env()
             fprintf(stderr, "[yolo2_hip] ignoring %s=%s (out of range)\n", env_name(name).c_str(), v);
     };
     for (const FlagOpt &f : kFlags) take(f.name);
+    for (const FlagOpt &f : kI8Flags) take(f.name);
     for (const IntOpt &i : kInts) take(i.name);
     for (const StrOpt &s : kStrs) take(s.name);
     return o;
@@ -98,6 +108,8 @@ std::string Y2Options::describe() const
     std::string out;
     auto add = [&](const std::string &kv) { out += (out.empty() ? "" : " ") + kv; };
     for (const FlagOpt &f : kFlags)
+        if (this->*f.m != d.*f.m) add(std::string(f.name) + "=" + (this->*f.m ? "1" : "0"));
+    for (const FlagOpt &f : kI8Flags)
         if (this->*f.m != d.*f.m) add(std::string(f.name) + "=" + (this->*f.m ? "1" : "0"));
     for (const IntOpt &i : kInts)
         if (this->*i.m != d.*i.m) add(std::string(i.name) + "=" + std::to_string(this->*i.m));

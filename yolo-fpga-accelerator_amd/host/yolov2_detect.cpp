@@ -95,7 +95,7 @@ void print_usage(const char *prog)
         "                            fp32fast = the fp32 weight files on the matrix cores in split-fp16 form (hi + lo halves, three MFMAs per\n"
         "                            product: boxes within 1e-3 of fp32's, ~7x the exact pass's rate); fp16 = fp16 operands, fp32 accumulate (approximate)\n"
         "                            int8 = the quantised pass on the i8 matrix cores; --weights names a directory written by\n"
-        "                            yolov2_calibrate --format int8 (single image and --batch only, no streaming)\n"
+        "                            yolov2_calibrate --format int8 (a single image, --batch, or streaming on one device: below)\n"
         "  --batch <n>           Frames per accelerator call (default 1)\n"
         "  --device <n>          HIP device (default 0)\n"
         "  --devices <a,b,..>    Several HIP devices: frames shard contiguously, weights are broadcast once (RCCL)\n"
@@ -129,7 +129,11 @@ void print_usage(const char *prog)
         "  --tail <core|app>     Which of the reference's two detection tails: core = src/core (default), app = its camera loop's\n"
         "                        linux_app/src/yolo2_postprocess.c (float sigmoid / softmax / boxes, NMS at every --nms)\n"
         "  --precision int16 | fp16 | fp32fast   also when streaming: fp16 / fp32fast read weights_reorg.bin + bias.bin and run layers 0+1\n"
-        "                        straight from the image bytes on the matrix cores (yolo2_hip_run_images_pix_dets_f16)\n",
+        "                        straight from the image bytes on the matrix cores (yolo2_hip_run_images_pix_dets_f16)\n"
+        "  --precision int8      also when streaming (--input-list, --input-dir, --video-raw with rgb24 or yuyv422), on one device with\n"
+        "                        --post gpu: one kernel goes from the image bytes to layer 1 (yolo2_hip_run_images_pix_dets_int8); --jsonl,\n"
+        "                        --tail app and --annotate-gpu --save-annotated-dir work as for fp16.  Refused: --loop-gpu and more than one\n"
+        "                        device (the loop and multi-GPU entries have no int8 form)\n",
         prog);
 }
 
@@ -221,9 +225,15 @@ AppConfig parse_args(int argc, char **argv)
                              "--save-annotated-dir <dir> and --post gpu\n");
         std::exit(1);
     }
-    if (cfg.precision == "int8" && cfg.streaming()) {
-        std::fprintf(stderr, "--precision int8 has no streaming form: the images, pix and loop entries run int16, fp16 and fp32fast. "
-                             "Run it on a single image (optionally with --batch).\n");
+    if (cfg.precision == "int8" && cfg.streaming() && (cfg.loop_gpu || cfg.devices.size() > 1)) {
+        std::fprintf(stderr, "--precision int8 streams on one device through the images entries only: the loop entries (--loop-gpu) and the "
+                             "multi-GPU entries (--devices with more than one device) have no int8 form.\n");
+        std::exit(1);
+    }
+    if (cfg.precision == "int8" && cfg.streaming() && !std::filesystem::exists(cfg.weights_dir + "/weights_int8.bin")) {
+        // (before a device is opened or a frame is read: the int16 set that --weights usually names is not what this pass loads)
+        std::fprintf(stderr, "--precision int8 when streaming: %s/weights_int8.bin not found; --weights names a directory written by "
+                             "yolov2_calibrate --format int8\n", cfg.weights_dir.c_str());
         std::exit(1);
     }
     if (cfg.video_pixfmt == YOLO2_PIX_YUYV && !cfg.video_raw.empty() && (cfg.video_w & 1)) {
@@ -537,10 +547,12 @@ void run_stream(AppConfig cfg)
     // fp16 / fp32fast: the matrix-core passes from image bytes (yolo2_hip_run_images_pix_dets_f16), split = 0 / 1
     const bool f16 = cfg.precision == "fp16" || cfg.precision == "fp32fast";
     const int split = cfg.precision == "fp32fast" ? 1 : 0;
+    // int8: the quantised pass from image bytes (yolo2_hip_run_images_pix_dets_int8), one device
+    const bool i8 = cfg.precision == "int8";
     // what the frames' bytes are: decoded image files are RGB24, a raw video stream is what --video-pix-fmt says
     const int pixfmt = cfg.input_list.empty() && cfg.input_dir.empty() ? cfg.video_pixfmt : YOLO2_PIX_RGB24;
-    if (cfg.precision != "int16" && !f16) throw std::runtime_error("the streaming frontend runs the int16, fp16 and fp32fast paths");
-    if (f16 && cfg.post == "host")
+    if (cfg.precision != "int16" && !f16 && !i8) throw std::runtime_error("the streaming frontend runs the int16, fp16, fp32fast and int8 paths");
+    if ((f16 || i8) && cfg.post == "host")
         throw std::runtime_error("--post host runs the int16 region tensor only; --precision " + cfg.precision + " needs --post gpu");
     if (cfg.devices.empty()) cfg.devices.push_back(cfg.device);
     if (cfg.batch <= 0) throw std::runtime_error("--batch must be positive");
@@ -565,7 +577,15 @@ void run_stream(AppConfig cfg)
     yolo2_hip_multi *m = nullptr;
     if (yolo2_hip_multi_create(cfg.devices.data(), ndev, &m) != YOLO2_SUCCESS) throw std::runtime_error(yolo2_hip_last_error());
     struct Guard { yolo2_hip_multi *m; ~Guard() { yolo2_hip_multi_destroy(m); } } guard{m};
-    if (f16) {
+    if (i8) {   // the four files of yolov2_calibrate --format int8, on the one device
+        if (ndev != 1 || cfg.loop_gpu) throw std::runtime_error("--precision int8 streams on one device, without --loop-gpu");
+        const std::vector<int8_t> w = read_blob<int8_t>(cfg.weights_dir + "/weights_int8.bin", (size_t)YOLO2_N_WEIGHTS);
+        const std::vector<int32_t> b = read_blob<int32_t>(cfg.weights_dir + "/bias_int32.bin", (size_t)YOLO2_N_BIAS);
+        const std::vector<int32_t> wq = read_blob<int32_t>(cfg.weights_dir + "/weight_int8_Q.bin", (size_t)YOLO2_N_BIAS);
+        const std::vector<int32_t> aq = read_blob<int32_t>(cfg.weights_dir + "/iofm_int8_Q.bin", (size_t)YOLO2_N_CONV + 1);
+        if (yolo2_hip_load_weights_int8(yolo2_hip_multi_ctx(m, 0), w.data(), w.size(), b.data(), b.size(), wq.data(), aq.data()) != YOLO2_SUCCESS)
+            throw std::runtime_error(yolo2_hip_last_error());
+    } else if (f16) {
         const std::vector<float> w = read_floats(cfg.weights_dir + "/weights_reorg.bin", (size_t)YOLO2_N_WEIGHTS);
         const std::vector<float> b = read_floats(cfg.weights_dir + "/bias.bin", (size_t)YOLO2_N_BIAS);
         if (yolo2_hip_multi_load_weights_fp32(m, w.data(), w.size(), b.data(), b.size()) != YOLO2_SUCCESS) throw std::runtime_error(yolo2_hip_last_error());
@@ -706,7 +726,7 @@ void run_stream(AppConfig cfg)
             yolo2_hip_ctx *ctx = yolo2_hip_multi_ctx(m, slot);
             // while the reader decodes its first chunk: plan the batch (activation tensors, lanes) on this device (int16; the fp16
             // passes build their launch table at the first chunk)
-            if (!f16) {
+            if (!f16 && !i8) {
                 if (yolo2_hip_set_batch(ctx, cfg.batch) != YOLO2_SUCCESS) throw std::runtime_error(yolo2_hip_last_error());
                 if (slot == 0) std::printf("  conv plans: %s\n", plan_source_name(yolo2_hip_plan_source(ctx)));
             }
@@ -758,7 +778,9 @@ void run_stream(AppConfig cfg)
                                 ck->annotated[(size_t)f].shrink_to_fit();
                             }
                         } else {
-                            const int rc = f16 ? yolo2_hip_run_images_pix_dets_f16(ctx, split, ptrs.data(), ws.data(), hs.data(), pixfmt, n, cfg.batch, cfg.thresh,
+                            const int rc = i8 ? yolo2_hip_run_images_pix_dets_int8(ctx, ptrs.data(), ws.data(), hs.data(), pixfmt, n, cfg.batch, cfg.thresh, cfg.nms,
+                                                                                   det_flags, recs.data(), cap, counts.data())
+                                           : f16 ? yolo2_hip_run_images_pix_dets_f16(ctx, split, ptrs.data(), ws.data(), hs.data(), pixfmt, n, cfg.batch, cfg.thresh,
                                                                                    cfg.nms, det_flags, recs.data(), cap, counts.data())
                                                : yolo2_hip_run_images_pix_dets(ctx, ptrs.data(), ws.data(), hs.data(), pixfmt, n, cfg.batch, cfg.thresh, cfg.nms,
                                                                                det_flags, recs.data(), cap, counts.data(), &q);

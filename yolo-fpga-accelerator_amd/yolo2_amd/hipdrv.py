@@ -63,6 +63,7 @@ EXPORTS = [
     "yolo2_hip_draw_item_size",
     "yolo2_hip_calib_q8_from_stats", "yolo2_hip_calib_q8_tables", "yolo2_hip_quantize_weights_int8", "yolo2_hip_load_weights_int8",
     "yolo2_hip_run_batch_int8", "yolo2_hip_run_batch_int8_host", "yolo2_hip_debug_i8_tensor", "yolo2_execute_conv_layer_int8",
+    "yolo2_hip_run_images_pix_int8_host", "yolo2_hip_run_images_pix_dets_int8", "yolo2_hip_images_front_kernel_int8",
 ]
 
 # include/yolo2_hip.h YOLO2_PIX_*: the pixfmt argument of the _pix entries ("yuyv": packed YUYV 4:2:2, arrays uint8 [h][w][2])
@@ -286,6 +287,9 @@ def lib():
     sig("yolo2_hip_run_batch_int8_host", [vp, vp, i32, vp])
     sig("yolo2_hip_debug_i8_tensor", [vp, i32, i32, vp, C.c_size_t, pi32])
     sig("yolo2_execute_conv_layer_int8", [u64] * 4 + [vp] + [i32] * 10 + [u32])
+    sig("yolo2_hip_run_images_pix_int8_host", L.yolo2_hip_run_images_pix_host.argtypes[:-1])       # (no final_q)
+    sig("yolo2_hip_run_images_pix_dets_int8", L.yolo2_hip_run_images_pix_dets.argtypes[:-1])
+    sig("yolo2_hip_images_front_kernel_int8", [vp], C.c_char_p)
     _lib = L
     return L
 
@@ -811,6 +815,23 @@ class Yolo2Hip:
               "yolo2_hip_run_batch_int8_host")
         return region
 
+    def run_images_int8_host(self, images, batch: int, pixfmt=None) -> np.ndarray:
+        """images (uint8 [h][w][3], [h][w] grey or - pixfmt "yuyv" - [h][w][2], any sizes) -> float32 region tensors [n][425][13][13]
+        through the int8 pass; one kernel goes from the image bytes to layer 1 (yolo2_hip_run_images_pix_int8_host)."""
+        imgs = [np.ascontiguousarray(im, dtype=np.uint8) for im in images]
+        if pixfmt is None:
+            pixfmt = "grey8" if imgs and imgs[0].ndim == 2 else "rgb24"
+        n, ptrs, ws, hs, fmt, _keep = _image_args(imgs, pixfmt)
+        region = np.empty((n, 425, 13, 13), dtype=np.float32)
+        check(lib().yolo2_hip_run_images_pix_int8_host(self._h, ptrs, ws, hs, fmt, n, batch, region.ctypes.data_as(C.c_void_p)),
+              "yolo2_hip_run_images_pix_int8_host")
+        return region
+
+    def images_front_kernel_int8(self) -> str:
+        """What the last int8 images call ran up to layer 1: the fused kernel's name, or - option i8_no_front - the three launches
+        of the frames route joined by " + " ("" before the first call)."""
+        return lib().yolo2_hip_images_front_kernel_int8(self._h).decode()
+
     def debug_i8_tensor(self, layer_idx: int, frame: int = 0):
         """(int8 [C][H][W], Q) of layer `layer_idx`'s tensor in the last int8 run; -1 is the quantised input"""
         g = (C.c_int * 4)()
@@ -1010,7 +1031,7 @@ def _image_args(images, pixfmt=None):
     return n, ptrs, ws, hs, ch, imgs
 
 
-PRECISIONS = ("int16", "fp16", "fp32fast")
+PRECISIONS = ("int16", "fp16", "fp32fast", "int8")
 
 
 def run_images_dets(handle, images, batch: int, thresh: float, nms: float, cap: int = 845, best_class: bool = True, multi: bool = False,
@@ -1018,16 +1039,28 @@ def run_images_dets(handle, images, batch: int, thresh: float, nms: float, cap: 
     """yolo2_hip_run_images_u8_dets / yolo2_hip_multi_run_images_u8_dets: host images (uint8 [h][w][3]) -> per-frame detection
     records; letterbox, network and the tail run on the device(s), the region tensor never leaves HBM.  precision "fp16" /
     "fp32fast" (the split-fp16 pass) run the _dets_f16 entries instead (fp32 weights loaded); their final_q is None.
+    precision "int8": yolo2_hip_run_images_pix_dets_int8 (int8 weights loaded, single device; final_q None).
     pixfmt "grey8" / "rgb24" / "yuyv" (arrays [h][w][2]): the _pix_dets entries with that format; None infers grey / RGB.
     tail "app" sets YOLO2_DETS_APP_TAIL: the records are those of the reference's camera loop (yolo2_postprocess.c)."""
     if precision not in PRECISIONS:
         raise ValueError(f"precision must be one of {PRECISIONS}, not {precision!r}")
+    if precision == "int8":
+        if multi:
+            raise ValueError("the multi-GPU entries have no int8 form")
+        if pixfmt is None:                                         # (the int8 entries are _pix entries only)
+            first = np.asarray(images[0]) if len(images) else None
+            pixfmt = "grey8" if first is not None and first.ndim == 2 else "rgb24"
     app_tail = _check_tail(tail)
     n, ptrs, ws, hs, ch, _keep = _image_args(images, pixfmt)
     kind = "u8" if pixfmt is None else "pix"
     dets = np.zeros((n, cap), dtype=DET_DTYPE)
     counts = np.zeros(n, dtype=np.int32)
     flags = (DETS_BEST_CLASS if best_class else 0) | (DETS_APP_TAIL if app_tail else 0)
+    if precision == "int8":
+        name = "yolo2_hip_run_images_pix_dets_int8"
+        check(getattr(lib(), name)(handle, ptrs, ws, hs, ch, n, batch, thresh, nms, flags, dets.ctypes.data_as(C.c_void_p), cap,
+                                   counts.ctypes.data_as(C.c_void_p)), name)
+        return {"dets": [dets[f, :min(int(counts[f]), cap)] for f in range(n)], "counts": counts, "final_q": None}
     if precision != "int16":
         split = int(precision == "fp32fast")
         name = f"yolo2_hip_{'multi_' if multi else ''}run_images_{kind}_dets_f16"
