@@ -743,6 +743,67 @@ int yolo2_execute_conv_layer_int8(uint64_t input_addr, uint64_t output_addr, uin
                                   const int32_t *weight_q, int ifm_num, int ofm_num, int ksize, int input_w, int input_h, int batch,
                                   int q_in, int q_out, int is_nl, int out_float, uint32_t timeout_ms);
 
+/* ------------------------------------------------------- JPEG streams decoded on the GPU
+ *
+ * The reference's camera loop asks the camera for MJPEG first (linux_app/src/yolo2_v4l2.c:112-123) and its image path opens JPEG
+ * files; these entries take the compressed streams.  The host reads the headers only; Huffman decode, inverse DCT, up-sampling and
+ * colour conversion run on the device (k_jpegdec_entropy, one lane per restart interval; k_jpegdec_idct; k_jpegdec_rgb) and leave
+ * RGB24 in the chunk staging layout the images entries read, so the network's kernels run unchanged behind them.  The bytes are
+ * those of the host decoder (host/y2_codec.cpp, and so stb_image's) on every stream the decoder accepts.
+ *
+ * GPU-decodable: SOF0 / SOF1, 8-bit, Huffman; 1 component, or 3 components YCbCr (not the R,G,B component ids, not Adobe
+ * transform 0 without JFIF) with chroma sampling 1x1 and luma H, V each 1 or 2; exactly one scan holding all components; every
+ * Huffman table the scan names defined; any restart interval or none; EOI behind the scan; at most 16384 in a direction and 2^26
+ * pixels.  Everything else has a reason code and goes through the host decoder as before.
+ *
+ * Per-frame status (YOLO2_JPEG_ST_*): 0; a bad Huffman code; a coefficient index past 63; "restart out of step" - a restart interval
+ * that did not end at its marker, a count of RSTn markers that does not fit the geometry, or a last interval that does not end at
+ * the marker closing the scan: every case in which the host decoder's result depends on state carried across intervals.  Where
+ * several intervals of a frame fail, the first in stream order gives the status.  A flagged frame is not a guess: its pixels are
+ * zero-filled and the caller decodes it on the host.
+ *
+ * Out of scope here (they keep taking raw frames): the loop / annotate entries, the _multi_ entries, the calibration entry and
+ * bench.py; the colour stage is not fused into the letterbox or layer-0 kernels. */
+enum {
+    YOLO2_JPEG_OK = 0, YOLO2_JPEG_DAMAGED = 1, YOLO2_JPEG_PROGRESSIVE = 2, YOLO2_JPEG_UNSUPPORTED_SOF = 3, YOLO2_JPEG_COMPONENTS = 4,
+    YOLO2_JPEG_RGB_COLOUR = 5, YOLO2_JPEG_SAMPLING = 6, YOLO2_JPEG_SCANS = 7, YOLO2_JPEG_MISSING_TABLE = 8, YOLO2_JPEG_TOO_LARGE = 9
+};
+enum { YOLO2_JPEG_ST_OK = 0, YOLO2_JPEG_ST_BAD_CODE = 1, YOLO2_JPEG_ST_COEF_OVERRUN = 2, YOLO2_JPEG_ST_RESTART = 3 };
+typedef struct {
+    int width, height, components, hmax, vmax, restart_interval;
+    int gpu_decodable, reason;   /* reason: YOLO2_JPEG_* (0 iff gpu_decodable) */
+    size_t stream_bytes;         /* offset just past EOI, or size: cuts a concatenated MJPEG stream */
+} yolo2_hip_jpeg_info_t;
+/* Host only, no GPU call.  The segments are walked by their lengths; inside a scan the end is FF followed by anything but 00, FF or
+ * D0..D7.  Returns YOLO2_SUCCESS whatever the class (YOLO2_ERROR: null argument). */
+int yolo2_hip_jpeg_probe(const uint8_t *jpeg, size_t size, yolo2_hip_jpeg_info_t *info);
+const char *yolo2_hip_jpeg_reason_name(int reason);
+/* n streams -> RGB24 in host memory (rgb_out[i], caps[i] bytes of room), in chunks of `batch`; widths / heights / status [n] are
+ * filled.  Refused before any launch, naming the first frame and the probe's reason: a stream the probe does not accept, a caps[i]
+ * below w * h * 3.  A frame whose status is not 0 is zero-filled and the call returns YOLO2_ERROR naming the first such frame, every
+ * other frame complete.  No weights are needed. */
+int yolo2_hip_decode_jpeg_host(yolo2_hip_ctx *ctx, const uint8_t *const *streams, const size_t *sizes, int n, int batch,
+                               uint8_t *const *rgb_out, const size_t *caps, int *widths, int *heights, int *status);
+/* The same functions (csrc/jpeg_scan.hpp) run on the host, one frame, no GPU call: the doorway of the CPU tests and of
+ * tools/fuzz_jpegdec.cpp.  A stream the probe refuses: YOLO2_ERROR, *status = 100 + reason. */
+int yolo2_hip_decode_jpeg_ref(const uint8_t *stream, size_t size, uint8_t *rgb_out, size_t cap, int *width, int *height, int *status);
+/* Streams -> detection records: yolo2_hip_run_images_pix_dets (precision YOLO2_LOOP_INT16), _pix_dets_f16 (split 0: _FP16, split 1:
+ * _F32TOL) or _pix_dets_int8 (YOLO2_JPEG_INT8) fed the decoded RGB24 frames - the same kernels read the same bytes, so counts,
+ * records and final_q (int16 only; may be NULL) are identical.  sizes[i] == 0: frame i is raw RGB24 of widths[i] x heights[i] at
+ * streams[i], copied to its slot as in those entries (a caller mixes host-decoded frames into a chunk); for the others widths /
+ * heights are filled from the headers.  Refusals as above plus the joined entry's.  A frame whose status is not 0: zero-filled
+ * before the network reads it, counts[f] = 0, and the call returns YOLO2_ERROR naming the first such frame with every other frame
+ * complete (the loop entry's rule for unprintable records).  status [n] may not be NULL. */
+#define YOLO2_JPEG_INT8 3
+int yolo2_hip_run_images_jpeg_dets(yolo2_hip_ctx *ctx, int precision, const uint8_t *const *streams, const size_t *sizes,
+                                   int *widths, int *heights, int n, int batch, float thresh, float nms, int flags,
+                                   yolo2_hip_det *dets, int cap_per_frame, int *counts, int *final_q, int *status);
+/* Of the last of the two calls above on ctx, for reports: out8[0..3] device-event milliseconds per chunk (mean over the call's
+ * chunks) of the coefficient memset, k_jpegdec_entropy, k_jpegdec_idct and k_jpegdec_rgb (+ k_jpegdec_zero) - zero unless
+ * yolo2_hip_set_profiling was on -; [4] bytes uploaded as descriptors, tables and streams; [5] bytes uploaded as letterbox tables
+ * and raw frames; [6] chunks; [7] frames. */
+int yolo2_hip_jpeg_last_info(yolo2_hip_ctx *ctx, double *out8);
+
 /* ------------------------------------------------------- multi-GPU: frame sharding, one weight broadcast
  *
  * SURVEY.md 8(b) "init(device_list) ... load_weights (H2D on rank 0, RCCL broadcast to the rest)", 8(e): frames are

@@ -13,6 +13,7 @@
 //   yolo2_draw.hip    annotated frames: records + frames -> RGB24 with the reference's boxes and tags
 //   yolo2_jpeg.hip    RGB24 frames in device memory -> the reference's JPEG streams
 //   yolo2_loop.hip    the camera loop as one call: frames -> records and annotated frames from one upload (launches nothing itself)
+//   yolo2_jpegdec.hip JPEG streams -> RGB24 in the chunk staging layout (probe, host doorway, decoder kernels) and the entries behind it
 // Every non-template kernel is launched from exactly one of them (its kernels_*.hpp is included there only).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -223,6 +224,14 @@ struct PipeBufs {
     int regf_batch = 0;
     Y2DevBuf<float> dregf[2];
     Y2PinBuf<float> hregf[2];
+    // the JPEG entries (yolo2_jpegdec.hip): per buffer set the chunk's blob (descriptors, tables, status words, streams) pinned and on the
+    // device, and the pinned status mirror; the coefficient and plane buffers are touched by kernels of s_run only, so one of each
+    size_t jpg_blob = 0, jpg_samples = 0, jpg_status = 0;
+    Y2PinBuf<uint8_t> hjpg[2];
+    Y2DevBuf<uint8_t> djpg[2];
+    Y2PinBuf<int> hjstatus[2];
+    Y2DevBuf<int16_t> jcoef;
+    Y2DevBuf<uint8_t> jplanes;
 };
 
 // Staging of yolo2_hip_annotate_images_pix_host (yolo2_draw.hip): two buffer sets - pinned and device staging for a chunk's table,
@@ -266,6 +275,7 @@ struct yolo2_hip_ctx {
     Y2JpegBufs jpeg;
     Y2LoopBufs loop;
     yolo2_hip_loop_info_t loop_info = {};   // of the last loop call (yolo2_hip_loop_last_info)
+    double jpeg_dec_info[8] = {};           // of the last JPEG call (yolo2_hip_jpeg_last_info)
     int device = 0;
     Y2Options opt;                     // parsed once at creation (environment), changed only by yolo2_hip_set_option; lanes copy it
     std::shared_ptr<Y2PlanCache> plan_cache;   // weight-side cache bound by yolo2_hip_set_plan_cache (lanes share the parent's)

@@ -13,6 +13,7 @@
 //
 // Streaming frontend (the role of the reference's yolo2_linux --video/--camera loop, linux_app/src/main.c:878-1288):
 //   --input-list <file> | --input-dir <dir> | --video-raw <file|-> --video-width W --video-height H [--video-pix-fmt rgb24|yuyv422]
+//   | --video-mjpeg <file|-> (concatenated JPEG streams); --decode gpu sends baseline JPEG streams to the device compressed
 // Frames are taken in chunks of --batch per device, go to the GPU as BYTES (letterbox on the GPU), through the
 // int16 network on --devices a,b,... (contiguous frame shards, weights broadcast once by the library) and through the
 // region + boxes + NMS tail (--post gpu: yolo2_hip_postprocess_int16; --post host: the threaded host code).  Per frame it
@@ -61,6 +62,8 @@ struct AppConfig {
     // streaming frontend
     std::vector<int> devices;          // --devices a,b,...: frame shards over several GPUs
     std::string input_list, input_dir, video_raw, jsonl_path, save_dir;
+    std::string video_mjpeg;        // --video-mjpeg: concatenated JPEG streams (a camera's MJPEG), cut where each stream ends
+    std::string decode = "host";    // --decode: where JPEG streams are decoded - host (the decode pool) or gpu (yolo2_hip_run_images_jpeg_dets)
     bool annotate_gpu = false;   // --annotate-gpu: annotated frames come from yolo2_hip_annotate_images_pix_host, in the reference's look
     std::string annotated_format;   // --annotated-format jpg: they are encoded on the GPU too (yolo2_hip_annotate_images_pix_jpeg_host); "" / ppm: PPM
     int jpeg_quality = 80;          // --jpeg-quality, the reference streamer's default
@@ -75,7 +78,7 @@ struct AppConfig {
     int decode_threads = 0;            // image decode pool; 0 = all host cores
     bool strict = false;               // streaming: stop at the first undecodable input instead of skipping the frame
     bool plan_cache = true;            // int16: keep bounds / forms / timed conv plans of this weight set in <weights>/weights_reorg_int16.bin.y2plan
-    bool streaming() const { return !input_list.empty() || !input_dir.empty() || !video_raw.empty(); }
+    bool streaming() const { return !input_list.empty() || !input_dir.empty() || !video_raw.empty() || !video_mjpeg.empty(); }
 };
 
 void print_usage(const char *prog)
@@ -108,6 +111,12 @@ void print_usage(const char *prog)
         "  --video-pix-fmt <rgb24|yuyv422>   what --video-raw holds (default rgb24).  yuyv422 (also: yuyv): packed YUYV 4:2:2, a V4L2 camera's\n"
         "                        native frames (`ffmpeg -f v4l2 -pix_fmt yuyv422 ... -f rawvideo -`), 2 bytes per pixel, even width; they go to\n"
         "                        the GPU as they are and are converted where they are read (every --precision, --devices)\n"
+        "  --video-mjpeg <file|->  Concatenated JPEG streams, what a camera delivers as MJPEG; each frame ends where its stream does\n"
+        "  --decode <host|gpu>   Where JPEG streams are decoded (default host: the decode pool).  gpu, with --input-list, --input-dir or\n"
+        "                        --video-mjpeg and --post gpu: baseline 1- and 3-component streams go to the device compressed and are decoded\n"
+        "                        there (yolo2_hip_run_images_jpeg_dets); progressive / CMYK JPEG, PNG and PNM files are decoded on the pool and\n"
+        "                        ride in the same call; a stream the GPU decoder flags is decoded on the host and run again.  Same log and\n"
+        "                        JSONL.  Not with --save-annotated-dir or --loop-gpu (the frames' pixels stay on the device)\n"
         "  --max-frames <n>      Stop after n inference frames (default: all)\n"
         "  --infer-every <n>     Run inference on every n-th frame (default 1)\n"
         "  --jsonl <path>        One JSON record per frame (fields of the reference's --output-json)\n"
@@ -169,6 +178,11 @@ AppConfig parse_args(int argc, char **argv)
         else if (arg == "--input-list" && need("")) cfg.input_list = argv[++i];
         else if (arg == "--input-dir" && need("")) cfg.input_dir = argv[++i];
         else if (arg == "--video-raw" && need("")) cfg.video_raw = argv[++i];
+        else if (arg == "--video-mjpeg" && need("")) cfg.video_mjpeg = argv[++i];
+        else if (arg == "--decode" && need("")) {
+            cfg.decode = argv[++i];
+            if (cfg.decode != "host" && cfg.decode != "gpu") { std::fprintf(stderr, "Unsupported --decode %s (host | gpu)\n", cfg.decode.c_str()); std::exit(1); }
+        }
         else if (arg == "--video-width" && need("")) cfg.video_w = std::atoi(argv[++i]);
         else if (arg == "--video-height" && need("")) cfg.video_h = std::atoi(argv[++i]);
         else if (arg == "--video-pix-fmt" && need("")) {
@@ -234,6 +248,12 @@ AppConfig parse_args(int argc, char **argv)
         // (before a device is opened or a frame is read: the int16 set that --weights usually names is not what this pass loads)
         std::fprintf(stderr, "--precision int8 when streaming: %s/weights_int8.bin not found; --weights names a directory written by "
                              "yolov2_calibrate --format int8\n", cfg.weights_dir.c_str());
+        std::exit(1);
+    }
+    if (cfg.decode == "gpu" && (!(!cfg.input_list.empty() || !cfg.input_dir.empty() || !cfg.video_mjpeg.empty()) || cfg.post != "gpu" ||
+                                !cfg.save_dir.empty() || cfg.loop_gpu)) {
+        std::fprintf(stderr, "--decode gpu decodes the JPEG streams of --input-list, --input-dir or --video-mjpeg in front of --post gpu; "
+                             "not with --save-annotated-dir or --loop-gpu\n");
         std::exit(1);
     }
     if (cfg.video_pixfmt == YOLO2_PIX_YUYV && !cfg.video_raw.empty() && (cfg.video_w & 1)) {
@@ -333,6 +353,7 @@ struct SrcFrame {
     std::string source;
     int frame_index = 0;    // 1-based position in the stream
     y2h::ImageU8 img;       // (a --video-pix-fmt yuyv422 frame: img.rgb holds its 2 w h YUYV bytes, as they were read)
+    std::vector<uint8_t> jpeg;   // --video-mjpeg: the frame's stream; --decode gpu: the stream that goes to the device (img then has w, h only)
 };
 
 // Frame source: a list of image files, a directory, or a raw RGB24 stream.  next_ref() enumerates the frames selected for
@@ -358,13 +379,18 @@ class FrameSource {
             }
             std::sort(files_.begin(), files_.end());
             mode_ = "dir";
+        } else if (!cfg.video_mjpeg.empty()) {
+            raw_ = cfg.video_mjpeg == "-" ? stdin : std::fopen(cfg.video_mjpeg.c_str(), "rb");
+            if (!raw_) throw std::runtime_error("Cannot open " + cfg.video_mjpeg);
+            mode_ = "mjpeg";
         } else {
             if (cfg.video_w <= 0 || cfg.video_h <= 0) throw std::runtime_error("--video-width / --video-height must be positive");
             raw_ = cfg.video_raw == "-" ? stdin : std::fopen(cfg.video_raw.c_str(), "rb");
             if (!raw_) throw std::runtime_error("Cannot open " + cfg.video_raw);
             mode_ = "video";
         }
-        if (mode_ != "video" && files_.empty()) throw std::runtime_error("no input images");
+        if (mode_ != "video" && mode_ != "mjpeg" && files_.empty()) throw std::runtime_error("no input images");
+        gpu_decode = cfg.decode == "gpu";
     }
     ~FrameSource() { if (raw_ && raw_ != stdin) std::fclose(raw_); }
     const char *mode() const { return mode_.c_str(); }
@@ -381,6 +407,9 @@ class FrameSource {
                 const size_t rd = std::fread(f.img.rgb.data(), 1, f.img.rgb.size(), raw_);
                 if (rd != f.img.rgb.size()) return false;    // EOF (a trailing partial frame is dropped like the reference's reader)
                 f.source = cfg_.video_raw;
+            } else if (mode_ == "mjpeg") {
+                if (!next_mjpeg(f.jpeg)) return false;
+                f.source = cfg_.video_mjpeg;
             } else {
                 if (pos_ >= files_.size()) return false;
                 f.source = files_[pos_++];
@@ -393,9 +422,62 @@ class FrameSource {
             return true;
         }
     }
-    static void decode(SrcFrame &f) { f.img = y2h::load_image_u8(f.source); }
+    // One frame on the decode pool.  --decode host: the file (or the MJPEG frame's bytes) decoded as ever.  --decode gpu: a JPEG stream the
+    // GPU decoder takes (yolo2_hip_jpeg_probe) stays compressed - f.jpeg, with its size in f.img - everything else is decoded here.
+    static inline bool gpu_decode = false;
+    static void decode(SrcFrame &f)
+    {
+        if (gpu_decode && f.jpeg.empty()) {     // a file: its bytes, if they are a JPEG stream
+            std::ifstream in(f.source, std::ios::binary);
+            std::vector<uint8_t> d((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
+            if (d.size() >= 2 && d[0] == 0xff && d[1] == 0xd8) f.jpeg = std::move(d);
+        }
+        if (gpu_decode && !f.jpeg.empty()) {
+            yolo2_hip_jpeg_info_t info;
+            if (yolo2_hip_jpeg_probe(f.jpeg.data(), f.jpeg.size(), &info) == YOLO2_SUCCESS && info.gpu_decodable) {
+                f.img.w = info.width; f.img.h = info.height;
+                f.img.rgb.clear();
+                return;
+            }
+        }
+        if (!f.jpeg.empty()) {
+            f.img = y2h::decode_image(f.jpeg.data(), f.jpeg.size(), f.source);
+            f.jpeg.clear();
+        } else {
+            f.img = y2h::load_image_u8(f.source);
+        }
+    }
 
   private:
+    // the next stream of a --video-mjpeg input: from its SOI to where yolo2_hip_jpeg_probe says it ends; bytes between streams are skipped
+    bool next_mjpeg(std::vector<uint8_t> &out)
+    {
+        for (;;) {
+            size_t soi = mj_at_;
+            while (soi + 1 < mj_.size() && !(mj_[soi] == 0xff && mj_[soi + 1] == 0xd8)) ++soi;
+            if (soi + 1 < mj_.size()) {
+                yolo2_hip_jpeg_info_t info;
+                yolo2_hip_jpeg_probe(mj_.data() + soi, mj_.size() - soi, &info);
+                if (info.stream_bytes < mj_.size() - soi || mj_eof_) {     // the stream ends inside what has been read (or nothing more comes)
+                    out.assign(mj_.begin() + (long)soi, mj_.begin() + (long)(soi + info.stream_bytes));
+                    mj_at_ = soi + info.stream_bytes;
+                    return true;
+                }
+            } else if (mj_eof_) {
+                return false;
+            }
+            mj_.erase(mj_.begin(), mj_.begin() + (long)std::min(soi, mj_.size()));     // read on
+            mj_at_ = 0;
+            const size_t have = mj_.size(), more = std::max<size_t>((size_t)1 << 20, have);
+            mj_.resize(have + more);
+            const size_t rd = std::fread(mj_.data() + have, 1, more, raw_);
+            mj_.resize(have + rd);
+            if (rd == 0) mj_eof_ = true;
+        }
+    }
+    std::vector<uint8_t> mj_;
+    size_t mj_at_ = 0;
+    bool mj_eof_ = false;
     const AppConfig &cfg_;
     std::vector<std::string> files_;
     size_t pos_ = 0;
@@ -550,7 +632,8 @@ void run_stream(AppConfig cfg)
     // int8: the quantised pass from image bytes (yolo2_hip_run_images_pix_dets_int8), one device
     const bool i8 = cfg.precision == "int8";
     // what the frames' bytes are: decoded image files are RGB24, a raw video stream is what --video-pix-fmt says
-    const int pixfmt = cfg.input_list.empty() && cfg.input_dir.empty() ? cfg.video_pixfmt : YOLO2_PIX_RGB24;
+    const int pixfmt = !cfg.video_raw.empty() && cfg.input_list.empty() && cfg.input_dir.empty() ? cfg.video_pixfmt : YOLO2_PIX_RGB24;
+    const bool gpu_decode = cfg.decode == "gpu";
     if (cfg.precision != "int16" && !f16 && !i8) throw std::runtime_error("the streaming frontend runs the int16, fp16, fp32fast and int8 paths");
     if ((f16 || i8) && cfg.post == "host")
         throw std::runtime_error("--post host runs the int16 region tensor only; --precision " + cfg.precision + " needs --post gpu");
@@ -777,6 +860,54 @@ void run_stream(AppConfig cfg)
                                 ck->annotated[(size_t)f].resize(sizes[(size_t)f]);
                                 ck->annotated[(size_t)f].shrink_to_fit();
                             }
+                        } else if (gpu_decode) {
+                            // streams the GPU decoder takes go up compressed, the pool's frames ride along as raw frames (size 0)
+                            const int prec = i8 ? YOLO2_JPEG_INT8 : f16 ? (split ? YOLO2_LOOP_F32TOL : YOLO2_LOOP_FP16) : YOLO2_LOOP_INT16;
+                            std::vector<size_t> sizes((size_t)n);
+                            std::vector<int> status((size_t)n, 0);
+                            for (int i = 0; i < n; ++i) {
+                                SrcFrame &fr = ck->frames[(size_t)i];
+                                sizes[(size_t)i] = fr.jpeg.size();
+                                if (!fr.jpeg.empty()) ptrs[(size_t)i] = fr.jpeg.data();
+                            }
+                            int rc = yolo2_hip_run_images_jpeg_dets(ctx, prec, ptrs.data(), sizes.data(), ws.data(), hs.data(), n, cfg.batch, cfg.thresh, cfg.nms,
+                                                                    det_flags, recs.data(), cap, counts.data(), &q, status.data());
+                            std::vector<int> redo;
+                            for (int i = 0; i < n; ++i) if (status[(size_t)i]) redo.push_back(i);
+                            if (rc != YOLO2_SUCCESS && redo.empty()) throw std::runtime_error(yolo2_hip_last_error());
+                            // a stream the decoder flagged: decoded on the host like any file, and run again as a raw frame
+                            std::vector<int> again;
+                            for (int i : redo) {
+                                SrcFrame &fr = ck->frames[(size_t)i];
+                                try {
+                                    fr.img = y2h::decode_image(fr.jpeg.data(), fr.jpeg.size(), fr.source);
+                                    fr.jpeg.clear();
+                                    again.push_back(i);
+                                } catch (const std::exception &e) {
+                                    if (cfg.strict) throw std::runtime_error(fr.source + ": " + e.what());
+                                    ck->skipped.emplace_back(fr.frame_index, fr.source + ": " + e.what());
+                                    fr.frame_index = -1;      // dropped below
+                                }
+                            }
+                            if (!again.empty()) {
+                                const int m2 = (int)again.size();
+                                std::vector<const uint8_t *> p2((size_t)m2);
+                                std::vector<size_t> s2((size_t)m2, 0);
+                                std::vector<int> w2((size_t)m2), h2((size_t)m2), c2((size_t)m2), st2((size_t)m2);
+                                std::vector<yolo2_hip_det> r2((size_t)m2 * cap);
+                                for (int k = 0; k < m2; ++k) {
+                                    const SrcFrame &fr = ck->frames[(size_t)again[(size_t)k]];
+                                    p2[(size_t)k] = fr.img.rgb.data(); w2[(size_t)k] = fr.img.w; h2[(size_t)k] = fr.img.h;
+                                }
+                                if (yolo2_hip_run_images_jpeg_dets(ctx, prec, p2.data(), s2.data(), w2.data(), h2.data(), m2, cfg.batch, cfg.thresh, cfg.nms, det_flags,
+                                                                   r2.data(), cap, c2.data(), &q, st2.data()) != YOLO2_SUCCESS)
+                                    throw std::runtime_error(yolo2_hip_last_error());
+                                for (int k = 0; k < m2; ++k) {
+                                    const int i = again[(size_t)k];
+                                    counts[(size_t)i] = c2[(size_t)k];
+                                    std::copy(r2.begin() + (long)k * cap, r2.begin() + (long)k * cap + std::min(c2[(size_t)k], cap), recs.begin() + (long)i * cap);
+                                }
+                            }
                         } else {
                             const int rc = i8 ? yolo2_hip_run_images_pix_dets_int8(ctx, ptrs.data(), ws.data(), hs.data(), pixfmt, n, cfg.batch, cfg.thresh, cfg.nms,
                                                                                    det_flags, recs.data(), cap, counts.data())
@@ -841,6 +972,11 @@ void run_stream(AppConfig cfg)
                                                      : y2h::postprocess_batch(region.data(), n, q, ws.data(), hs.data(), cfg.thresh, cfg.nms, post_threads);
                         for (int f = 0; f < n; ++f) ck->dets[(size_t)f] = best_class_dets(all[(size_t)f], (int)all[(size_t)f].size(), last.classes, cfg.thresh);
                     }
+                    for (int f = n - 1; f >= 0; --f)     // (--decode gpu) frames that neither decoder could read: skipped, as the reader skips them
+                        if (ck->frames[(size_t)f].frame_index < 0) {
+                            ck->frames.erase(ck->frames.begin() + f);
+                            ck->dets.erase(ck->dets.begin() + f);
+                        }
                     ck->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() - t_annotate;
                     accel_s[(size_t)slot] += ck->seconds;
                 }

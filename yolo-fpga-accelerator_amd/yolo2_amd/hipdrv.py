@@ -64,6 +64,8 @@ EXPORTS = [
     "yolo2_hip_calib_q8_from_stats", "yolo2_hip_calib_q8_tables", "yolo2_hip_quantize_weights_int8", "yolo2_hip_load_weights_int8",
     "yolo2_hip_run_batch_int8", "yolo2_hip_run_batch_int8_host", "yolo2_hip_debug_i8_tensor", "yolo2_execute_conv_layer_int8",
     "yolo2_hip_run_images_pix_int8_host", "yolo2_hip_run_images_pix_dets_int8", "yolo2_hip_images_front_kernel_int8",
+    "yolo2_hip_jpeg_probe", "yolo2_hip_jpeg_reason_name", "yolo2_hip_decode_jpeg_host", "yolo2_hip_decode_jpeg_ref",
+    "yolo2_hip_run_images_jpeg_dets", "yolo2_hip_jpeg_last_info",
 ]
 
 # include/yolo2_hip.h YOLO2_PIX_*: the pixfmt argument of the _pix entries ("yuyv": packed YUYV 4:2:2, arrays uint8 [h][w][2])
@@ -290,6 +292,13 @@ def lib():
     sig("yolo2_hip_run_images_pix_int8_host", L.yolo2_hip_run_images_pix_host.argtypes[:-1])       # (no final_q)
     sig("yolo2_hip_run_images_pix_dets_int8", L.yolo2_hip_run_images_pix_dets.argtypes[:-1])
     sig("yolo2_hip_images_front_kernel_int8", [vp], C.c_char_p)
+    # JPEG streams decoded on the GPU (include/yolo2_hip.h)
+    sig("yolo2_hip_jpeg_probe", [vp, C.c_size_t, vp])
+    sig("yolo2_hip_jpeg_reason_name", [i32], C.c_char_p)
+    sig("yolo2_hip_decode_jpeg_host", [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp])
+    sig("yolo2_hip_decode_jpeg_ref", [vp, C.c_size_t, vp, C.c_size_t, pi32, pi32, pi32])
+    sig("yolo2_hip_jpeg_last_info", [vp, vp])
+    sig("yolo2_hip_run_images_jpeg_dets", [vp, i32, vp, vp, vp, vp, i32, i32, C.c_float, C.c_float, i32, vp, i32, vp, pi32, vp])
     _lib = L
     return L
 
@@ -518,6 +527,15 @@ class Yolo2Hip:
         """the camera loop as one call: records and annotated frames from one upload (module-level loop_images)"""
         return loop_images(self._h, images, pixfmt=pixfmt, precision=precision, tail=tail, thresh=thresh, nms=nms, labels=labels,
                            jpeg_quality=jpeg_quality, batch=batch, cap=cap)
+
+    def jpeg_decode(self, streams, batch: int = 64, strict: bool = True):
+        """see jpeg_decode"""
+        return jpeg_decode(self._h, streams, batch=batch, strict=strict)
+
+    def run_jpegs_dets(self, streams, precision: str = "int16", tail: str = "core", batch: int = 64, thresh: float = 0.24, nms: float = 0.45,
+                       cap: int = 845, best_class: bool = True, strict: bool = True):
+        """see run_jpegs_dets"""
+        return run_jpegs_dets(self._h, streams, batch, thresh, nms, cap=cap, best_class=best_class, precision=precision, tail=tail, strict=strict)
 
     def loop_last_info(self) -> dict:
         return loop_last_info(self._h)
@@ -1072,6 +1090,112 @@ def run_images_dets(handle, images, batch: int, thresh: float, nms: float, cap: 
     check(getattr(lib(), name)(handle, ptrs, ws, hs, ch, n, batch, thresh, nms, flags, dets.ctypes.data_as(C.c_void_p), cap,
                                counts.ctypes.data_as(C.c_void_p), C.byref(q)), name)
     return {"dets": [dets[f, :min(int(counts[f]), cap)] for f in range(n)], "counts": counts, "final_q": q.value}
+
+
+# ------------------------------------------------------------------ JPEG streams decoded on the GPU
+
+class JpegInfo(C.Structure):
+    """yolo2_hip_jpeg_info_t"""
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("components", C.c_int), ("hmax", C.c_int), ("vmax", C.c_int),
+                ("restart_interval", C.c_int), ("gpu_decodable", C.c_int), ("reason", C.c_int), ("stream_bytes", C.c_size_t)]
+
+
+JPEG_REASONS = ("accepted", "damaged", "progressive", "unsupported_sof", "components", "rgb_colour", "sampling", "scans", "missing_table",
+                "too_large")
+JPEG_PRECISIONS = {"int16": 0, "fp16": 1, "fp32fast": 2, "int8": 3}
+
+
+def jpeg_probe(data) -> dict:
+    """yolo2_hip_jpeg_probe (host only): the header's geometry, whether the GPU decoder takes the stream (reason: index into
+    JPEG_REASONS) and stream_bytes, the offset just past EOI, which cuts a concatenated MJPEG stream."""
+    buf = bytes(data)
+    info = JpegInfo()
+    check(lib().yolo2_hip_jpeg_probe(buf, len(buf), C.byref(info)), "yolo2_hip_jpeg_probe")
+    return {k: getattr(info, k) for k, _ in JpegInfo._fields_}
+
+
+def jpeg_decode_ref(data, cap: int = None):
+    """yolo2_hip_decode_jpeg_ref: the GPU decoder's stages run on the host -> (uint8 [h][w][3] or None, status).  A stream the probe
+    refuses gives (None, 100 + reason)."""
+    buf = bytes(data)
+    info = jpeg_probe(buf)
+    out = np.zeros(max(1, info["width"] * info["height"] * 3) if cap is None else cap, dtype=np.uint8)
+    w, h, st = C.c_int(0), C.c_int(0), C.c_int(0)
+    rc = lib().yolo2_hip_decode_jpeg_ref(buf, len(buf), out.ctypes.data_as(C.c_void_p), out.size, C.byref(w), C.byref(h), C.byref(st))
+    if rc != YOLO2_SUCCESS and st.value < 100:
+        check(rc, "yolo2_hip_decode_jpeg_ref")
+    if st.value:
+        return None, st.value
+    return out[:w.value * h.value * 3].reshape(h.value, w.value, 3), 0
+
+
+def jpeg_last_info(handle) -> dict:
+    """yolo2_hip_jpeg_last_info: per-chunk kernel milliseconds (under set_profiling) and uploaded bytes of the last JPEG call"""
+    v = (C.c_double * 8)()
+    check(lib().yolo2_hip_jpeg_last_info(handle, v), "yolo2_hip_jpeg_last_info")
+    return {"memset_ms": v[0], "entropy_ms": v[1], "idct_ms": v[2], "rgb_ms": v[3], "stream_bytes_h2d": int(v[4]), "frame_bytes_h2d": int(v[5]),
+            "chunks": int(v[6]), "frames": int(v[7])}
+
+
+def _stream_args(streams):
+    bufs = [bytes(s) for s in streams]
+    n = len(bufs)
+    ptrs = (C.c_char_p * n)(*bufs)
+    sizes = (C.c_size_t * n)(*[len(b) for b in bufs])
+    return n, ptrs, sizes, bufs
+
+
+def jpeg_decode(handle, streams, batch: int = 64, strict: bool = True):
+    """yolo2_hip_decode_jpeg_host: a list of JPEG streams -> (list of uint8 [h][w][3], status int32 [n]); the whole decoder runs on
+    the device.  A stream the probe refuses raises.  A frame the decoder flags (status != 0) comes back zero-filled: with strict
+    that raises too, otherwise the caller looks at status."""
+    n, ptrs, sizes, bufs = _stream_args(streams)
+    infos = [jpeg_probe(b) for b in bufs]
+    outs = [np.zeros((max(1, i["height"]), max(1, i["width"]), 3), dtype=np.uint8) for i in infos]
+    optrs = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
+    caps = (C.c_size_t * n)(*[o.size for o in outs])
+    ws, hs = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+    status = np.zeros(n, dtype=np.int32)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    rc = lib().yolo2_hip_decode_jpeg_host(handle, ptrs, sizes, n, batch, optrs, caps, vp(ws), vp(hs), vp(status))
+    if rc != YOLO2_SUCCESS and (strict or not status.any()):
+        check(rc, "yolo2_hip_decode_jpeg_host")
+    return [o[:hs[i], :ws[i]] for i, o in enumerate(outs)], status
+
+
+def run_jpegs_dets(handle, streams, batch: int, thresh: float, nms: float, cap: int = 845, best_class: bool = True, precision: str = "int16",
+                   tail: str = "core", strict: bool = True):
+    """yolo2_hip_run_images_jpeg_dets: JPEG streams (bytes) - or, mixed in, raw frames (uint8 [h][w][3] arrays, e.g. decoded on the
+    host) - -> detection records, the decoder and the network on the device.  Returns run_images_dets' dictionary plus "status"
+    (int32 [n], not 0: the decoder flagged the frame, its counts are 0) and "sizes" ([n] (w, h))."""
+    if precision not in JPEG_PRECISIONS:
+        raise ValueError(f"precision must be one of {tuple(JPEG_PRECISIONS)}, not {precision!r}")
+    app_tail = _check_tail(tail)
+    keep, n = [], len(streams)
+    ptrs, sizes = (C.c_void_p * n)(), (C.c_size_t * n)()
+    ws, hs = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+    for i, s in enumerate(streams):
+        if isinstance(s, np.ndarray):
+            a = np.ascontiguousarray(s, dtype=np.uint8)
+            if a.ndim != 3 or a.shape[2] != 3:
+                raise ValueError(f"frame {i}: a raw frame is uint8 [h][w][3], not {a.shape}")
+            keep.append(a)
+            ptrs[i], sizes[i], ws[i], hs[i] = a.ctypes.data, 0, a.shape[1], a.shape[0]
+        else:
+            b = C.create_string_buffer(bytes(s), len(s))
+            keep.append(b)
+            ptrs[i], sizes[i] = C.addressof(b), len(s)
+    dets = np.zeros((n, cap), dtype=DET_DTYPE)
+    counts, status = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+    flags = (DETS_BEST_CLASS if best_class else 0) | (DETS_APP_TAIL if app_tail else 0)
+    q = C.c_int(0)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    rc = lib().yolo2_hip_run_images_jpeg_dets(handle, JPEG_PRECISIONS[precision], ptrs, sizes, vp(ws), vp(hs), n, batch, thresh, nms, flags, vp(dets),
+                                              cap, vp(counts), C.byref(q), vp(status))
+    if rc != YOLO2_SUCCESS and (strict or not status.any()):
+        check(rc, "yolo2_hip_run_images_jpeg_dets")
+    return {"dets": [dets[f, :min(int(counts[f]), cap)] for f in range(n)], "counts": counts, "final_q": q.value if precision == "int16" else None,
+            "status": status, "sizes": [(int(ws[i]), int(hs[i])) for i in range(n)]}
 
 
 # ------------------------------------------------------------------ annotated frames
