@@ -423,7 +423,7 @@ int yolo2_hip_run_images_u8_host(yolo2_hip_ctx *ctx, const uint8_t *const *image
  *   rows / totals         optional: the reference's dets[] array after do_nms_sort, [batch][845][85] =
  *                         x, y, w, h, objectness, prob[80], and the number of slots in front that hold a candidate
  *   proc                  optional: l.output of forward_region_layer, [batch][425][13][13]
- * Synchronous (host buffers out); enqueues on `stream` (NULL = default). */
+ * Synchronous (host buffers out): enqueues on `stream` (NULL = default) and synchronises it before returning. */
 typedef struct {
     int frame, det, cls;
     float prob, x, y, w, h;
@@ -437,8 +437,8 @@ int yolo2_hip_postprocess_f32(yolo2_hip_ctx *ctx, uint64_t region_dev, int batch
 
 /* The camera loop's tail.  The reference's streaming app (linux_app/src/main.c:1013-1026, :1184-1197) and its single-image mode
  * (:827-858) do not run the src/core functions above but linux_app/src/yolo2_postprocess.c, and the two do not compute the same
- * numbers.  These two entries restate that file; arguments, checks, layouts and synchronisation are those of the entries above.
- * What differs from the src/core tail:
+ * numbers.  These two entries restate that file; arguments, checks and layouts are those of the entries above, and like them each
+ * enqueues on `stream` and synchronises it before returning.  What differs from the src/core tail:
  *   sigmoid      1.0f / (1.0f + expf(-x)) in float, x > 10 -> 1 and x < -10 -> 0 (:17-21), not 1. / (1. + exp(-x)) in double
  *   softmax      expf, the float sum in class order, then *= 1.0f / sum, 1 / n for a sum <= 0 (:30-57), not (float)exp(double) and / sum
  *   boxes        correct_region_boxes in float throughout, (netw - new_w) / 2.0f / netw (:77-101), not partly in double

@@ -83,14 +83,37 @@ def _pix_code(pixfmt, imgs) -> int:
     return PIXFMTS[pixfmt]
 
 
-def letterbox_pix(image: np.ndarray, pixfmt: str, net_w: int = 416, net_h: int = 416) -> np.ndarray:
+_hip = None      # the HIP runtime itself, for _stream_sync only
+
+
+def _stream_sync(stream: int):
+    """hipStreamSynchronize on a caller's stream (the wrappers below copy results back with blocking copies on the null stream, which
+    do not order behind a non-blocking stream)"""
+    global _hip
+    if _hip is None:
+        for name in ("libamdhip64.so", os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib", "libamdhip64.so")):
+            try:
+                _hip = C.CDLL(name)
+                break
+            except OSError:
+                continue
+        else:
+            raise Yolo2HipError("libamdhip64.so not found: cannot synchronise a caller's stream")
+        _hip.hipStreamSynchronize.argtypes = [C.c_void_p]
+    rc = _hip.hipStreamSynchronize(C.c_void_p(stream))
+    if rc:
+        raise Yolo2HipError(f"hipStreamSynchronize failed with HIP error {rc}")
+
+
+def letterbox_pix(image: np.ndarray, pixfmt: str, net_w: int = 416, net_h: int = 416, stream: int = 0) -> np.ndarray:
     """letterbox_u8 with a pixel format (yolo2_hip_letterbox_pix): "grey8" [h][w], "rgb24" [h][w][3] or "yuyv" [h][w][2] (packed
     YUYV 4:2:2, converted per fetched pixel on the GPU) -> float [3][net_h][net_w] frame."""
-    return letterbox_u8(image, net_w, net_h, pixfmt=pixfmt)
+    return letterbox_u8(image, net_w, net_h, pixfmt=pixfmt, stream=stream)
 
 
-def letterbox_u8(image_hwc: np.ndarray, net_w: int = 416, net_h: int = 416, pixfmt=None) -> np.ndarray:
-    """uint8 [h][w][3] (or [h][w]) host image -> float [3][net_h][net_w] frame, letterboxed on the GPU."""
+def letterbox_u8(image_hwc: np.ndarray, net_w: int = 416, net_h: int = 416, pixfmt=None, stream: int = 0) -> np.ndarray:
+    """uint8 [h][w][3] (or [h][w]) host image -> float [3][net_h][net_w] frame, letterboxed on the GPU; the kernel is enqueued on
+    `stream` (a hipStream_t as an integer, 0 = the null stream)."""
     im = np.ascontiguousarray(image_hwc, dtype=np.uint8)
     ch = 1 if im.ndim == 2 else im.shape[2]
     code = None if pixfmt is None else _pix_code(pixfmt, [im])
@@ -102,9 +125,11 @@ def letterbox_u8(image_hwc: np.ndarray, net_w: int = 416, net_h: int = 416, pixf
     try:
         check(L.yolo2_hip_memcpy_h2d(src, im.ctypes.data_as(C.c_void_p), im.nbytes), "h2d")
         if code is None:
-            check(L.yolo2_hip_letterbox_u8(src, im.shape[1], im.shape[0], ch, dst, net_w, net_h, None), "yolo2_hip_letterbox_u8")
+            check(L.yolo2_hip_letterbox_u8(src, im.shape[1], im.shape[0], ch, dst, net_w, net_h, C.c_void_p(stream)), "yolo2_hip_letterbox_u8")
         else:
-            check(L.yolo2_hip_letterbox_pix(src, im.shape[1], im.shape[0], code, dst, net_w, net_h, None), "yolo2_hip_letterbox_pix")
+            check(L.yolo2_hip_letterbox_pix(src, im.shape[1], im.shape[0], code, dst, net_w, net_h, C.c_void_p(stream)), "yolo2_hip_letterbox_pix")
+        if stream:
+            _stream_sync(stream)
         check(L.yolo2_hip_memcpy_d2h(out.ctypes.data_as(C.c_void_p), dst, out.nbytes), "d2h")
     finally:
         L.yolo2_hip_free(src)
@@ -714,11 +739,12 @@ class Yolo2Hip:
     def calib_reset(self):
         check(lib().yolo2_hip_calib_reset(self._h), "yolo2_hip_calib_reset")
 
-    def calib_frames(self, frames: np.ndarray):
-        """One exact fp32 pass over host frames [B][3][416][416] + the abs-max reductions, accumulated (yolo2_hip_calib_frames)."""
+    def calib_frames(self, frames: np.ndarray, stream: int = 0):
+        """One exact fp32 pass over host frames [B][3][416][416] + the abs-max reductions, accumulated (yolo2_hip_calib_frames), on
+        `stream` (0 = the null stream)."""
         buf = DevBuf(np.ascontiguousarray(frames, dtype=np.float32).reshape(-1, 3, 416, 416))
         try:
-            check(lib().yolo2_hip_calib_frames(self._h, buf.addr, buf.nbytes // (4 * 3 * 416 * 416), None), "yolo2_hip_calib_frames")
+            check(lib().yolo2_hip_calib_frames(self._h, buf.addr, buf.nbytes // (4 * 3 * 416 * 416), C.c_void_p(stream)), "yolo2_hip_calib_frames")
         finally:
             buf.free()
 
@@ -1209,7 +1235,7 @@ def _label_args(labels):
     return arr, len(enc), enc
 
 
-def annotate_pix(image: np.ndarray, dets, pixfmt=None, thresh: float = 0.24, labels=None):
+def annotate_pix(image: np.ndarray, dets, pixfmt=None, thresh: float = 0.24, labels=None, stream: int = 0):
     """yolo2_hip_annotate_pix: one image ("grey8" [h][w], "rgb24" [h][w][3], "yuyv" [h][w][2]; None infers grey / RGB) and its
     records (DET_DTYPE, one per detection) -> (uint8 [h][w][3] with the reference's boxes and tags painted in, records drawn)."""
     im = np.ascontiguousarray(image, dtype=np.uint8)
@@ -1225,7 +1251,7 @@ def annotate_pix(image: np.ndarray, dets, pixfmt=None, thresh: float = 0.24, lab
         check(L.yolo2_hip_alloc(max(out.nbytes, 16), C.byref(dst)), "alloc")
         check(L.yolo2_hip_memcpy_h2d(src, im.ctypes.data_as(C.c_void_p), im.nbytes), "h2d")
         check(L.yolo2_hip_annotate_pix(src, im.shape[1], im.shape[0], code, d.ctypes.data_as(C.c_void_p) if d.size else None, d.size,
-                                       thresh, lab, n_labels, dst, C.byref(drawn), None), "yolo2_hip_annotate_pix")
+                                       thresh, lab, n_labels, dst, C.byref(drawn), C.c_void_p(stream)), "yolo2_hip_annotate_pix")
         check(L.yolo2_hip_memcpy_d2h(out.ctypes.data_as(C.c_void_p), dst, out.nbytes), "d2h")
     finally:
         for buf in (src, dst):
@@ -1306,7 +1332,7 @@ def jpeg_bound(w: int, h: int) -> int:
     return int(lib().yolo2_hip_jpeg_bound(w, h))
 
 
-def jpeg_encode(rgb, quality: int = 80) -> bytes:
+def jpeg_encode(rgb, quality: int = 80, stream: int = 0) -> bytes:
     """yolo2_hip_jpeg_encode_rgb24: the same stream as write_jpg_host, encoded on the GPU"""
     im = _rgb24(rgb)
     L = lib()
@@ -1320,7 +1346,7 @@ def jpeg_encode(rgb, quality: int = 80) -> bytes:
         check(L.yolo2_hip_alloc(max(im.nbytes, 16), C.byref(src)), "alloc")
         check(L.yolo2_hip_alloc(cap, C.byref(dst)), "alloc")
         check(L.yolo2_hip_memcpy_h2d(src, im.ctypes.data_as(C.c_void_p), im.nbytes), "h2d")
-        check(L.yolo2_hip_jpeg_encode_rgb24(src, w, h, quality, dst, cap, C.byref(size), None), "yolo2_hip_jpeg_encode_rgb24")
+        check(L.yolo2_hip_jpeg_encode_rgb24(src, w, h, quality, dst, cap, C.byref(size), C.c_void_p(stream)), "yolo2_hip_jpeg_encode_rgb24")
         out = np.empty(size.value, dtype=np.uint8)
         check(L.yolo2_hip_memcpy_d2h(out.ctypes.data_as(C.c_void_p), dst, out.nbytes), "d2h")
     finally:
