@@ -914,6 +914,14 @@ int  yolo2_hip_multi_rccl_info(yolo2_hip_multi *m, yolo2_hip_rccl_info_t *out); 
  * Hosts that parse a .cfg compare it with this before using yolo2_hip_run_batch_*. */
 int yolo2_hip_num_layers(void);
 int yolo2_hip_layer_desc(int layer_idx, int desc[9]);
+/* ... and how the table is connected: the sources of a [route] layer as absolute layer indices, in the cfg's order.  Returns their
+ * number, 0 for a layer that is no route, YOLO2_ERROR for a bad argument.  A cfg whose routes differ describes another network. */
+int yolo2_hip_layer_routes(int layer_idx, int src[4]);
+/* Test hook: what the library derives from the table and the routes for one layer - {conv ordinal or -1, weight offset, bias offset
+ * (elements of the reference streams), layer whose output it reads (-1: the input; routes resolved, the concat tensor is its route
+ * layer), route layer of the concat tensor its output lives in or -1, first channel there, number of readers, first reader or -1,
+ * 1 if the region layer reads it, C, H, W of the tensor its output lives in}. */
+int yolo2_hip_debug_layer_wiring(int layer_idx, int out[12]);
 
 /* weights_reorg_int16.bin / bias_int16.bin carry one pad element after every odd-length
  * layer (yolo2_model.cpp:198-224).  Returns elements written, or -1 if the file is short. */

@@ -114,16 +114,16 @@ RULES = {
     # table and runs the separate kernels (line 888), so the launch a line with fuse=1 names there is never the one that runs.
     "fuse": (188, "if (p.K != 3 || (p.path != 3 && p.path != 4) || (gin.H & 1) || (gin.W & 1)) return false;"),
     "fuse_tile": (190, "if (lt > 12 * 256) return false;"),
-    "fuse_layer": (955, "if (kNet[i + 1].type != L_MAX) continue;"),
+    "fuse_layer": (925, "if (kNet[i + 1].type != L_MAX) continue;"),
 }
 # where the restated enumeration and the comparison live
 CITES = {
-    "candidates": (719, "for (int cfgx = 0; cfgx < 18 + 12 + 4; ++cfgx) {"),
-    "no_cap_on_wide_tiles": (728, "if (pad && P > 2) continue;"),
-    "splitk_offered": (738, "if (!sp->splitk_ok || !c->extra[i].empty() || fs == 0) continue;"),
-    "ks_cap": (866, "cand.ks_cap = s == 0 ? ks_potential_bytes(c, c->batch) : 0;"),
-    "exact": (870, "if (cand.P != pl.P || cand.lds_pad != pl.pad || cand.splitk != pl.splitk || cand.splitk_pp != pl.pp || cand.w16 != pl.w16 ||"),
-    "fuse_chosen": (888, "for (int i = 0; i < 32; ++i) c->fuse_pool[i] = c->fuse_pool[i] && fuse[i];"),
+    "candidates": (692, "for (int cfgx = 0; cfgx < 18 + 12 + 4; ++cfgx) {"),
+    "no_cap_on_wide_tiles": (701, "if (pad && P > 2) continue;"),
+    "splitk_offered": (711, "if (!sp->splitk_ok || !c->extra[i].empty() || fs == 0) continue;"),
+    "ks_cap": (838, "cand.ks_cap = s == 0 ? ks_potential_bytes(c, c->batch) : 0;"),
+    "exact": (842, "if (cand.P != pl.P || cand.lds_pad != pl.pad || cand.splitk != pl.splitk || cand.splitk_pp != pl.pp || cand.w16 != pl.w16 ||"),
+    "fuse_chosen": (860, "for (int i = 0; i < 32; ++i) c->fuse_pool[i] = c->fuse_pool[i] && fuse[i];"),
 }
 
 

@@ -77,6 +77,17 @@ __device__ __forceinline__ long shift64(long v, int right, int left, int mag, lo
     return v;
 }
 
+// Darknet's legacy reorg (stride 2) as the reference runs it (yolo2_model.cpp:112-129): out[i + 26*(j + 416*k)] = x[(2i + k%2) + 52*(2j + k/2)]
+// over the flat tensors.  From the flat output index o in [256][13][13]: the element (sc, sy, sx) of the logical [64][26][26] source.
+struct ReorgSrc { int sc, sy, sx; };
+__device__ __forceinline__ ReorgSrc reorg_src(int o)
+{
+    const int k = o / (26 * 416), rem = o - k * (26 * 416), j = rem / 26, i = rem - j * 26;
+    const int sidx = (2 * i + (k & 1)) + 52 * (2 * j + (k >> 1));
+    const int sc = sidx / 676, sr = sidx - sc * 676, sy = sr / 26;
+    return {sc, sy, sr - sy * 26};
+}
+
 // Pixel index q (raster over b, y, x of real pixels) -> flat item offset inside a channel group.
 __device__ __forceinline__ int flat_of(const ConvArgs &a, int q)
 {

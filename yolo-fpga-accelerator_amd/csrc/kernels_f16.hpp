@@ -2633,10 +2633,8 @@ __global__ void k_reorg_split(const _Float16 *__restrict__ in, _Float16 *__restr
 #pragma unroll
     for (int e = 0; e < 2; ++e) {
         const int o = (2 * cp + e) * 169 + pix;        // the reference's flat output index [256][13][13]
-        const int k = o / (26 * 416), rem = o - k * (26 * 416), j = rem / 26, i = rem - j * 26;
-        const int sidx = (2 * i + (k & 1)) + 52 * (2 * j + (k >> 1));
-        const int sc = sidx / 676, sr = sidx - sc * 676, sy = sr / 26, sx = sr - sy * 26;
-        v[e] = in[((size_t)kLead + (size_t)b * iPL + (size_t)(sy + 1) * iWp + sx) * iCp + p * iPS + sc];
+        const ReorgSrc s = reorg_src(o);
+        v[e] = in[((size_t)kLead + (size_t)b * iPL + (size_t)(s.sy + 1) * iWp + s.sx) * iCp + p * iPS + s.sc];
     }
     *reinterpret_cast<half2_t *>(out + ((size_t)kLead + (size_t)b * oPL + (size_t)(oy + 1) * oWp + ox) * oCp + p * oPS + 2 * cp) = v;
 }
@@ -2700,10 +2698,8 @@ __global__ void k_reorg_f16(const _Float16 *__restrict__ in, _Float16 *__restric
 #pragma unroll
     for (int e = 0; e < 2; ++e) {
         const int o = (2 * cp + e) * 169 + pix;        // the reference's flat output index [256][13][13]
-        const int k = o / (26 * 416), rem = o - k * (26 * 416), j = rem / 26, i = rem - j * 26;
-        const int sidx = (2 * i + (k & 1)) + 52 * (2 * j + (k >> 1));
-        const int sc = sidx / 676, sr = sidx - sc * 676, sy = sr / 26, sx = sr - sy * 26;
-        v[e] = in[((size_t)kLead + (size_t)b * iPL + (size_t)(sy + 1) * iWp + sx) * iCp + sc];
+        const ReorgSrc s = reorg_src(o);
+        v[e] = in[((size_t)kLead + (size_t)b * iPL + (size_t)(s.sy + 1) * iWp + s.sx) * iCp + s.sc];
     }
     *reinterpret_cast<half2_t *>(out + ((size_t)kLead + (size_t)b * oPL + (size_t)(oy + 1) * oWp + ox) * oCp + 2 * cp) = v;
 }

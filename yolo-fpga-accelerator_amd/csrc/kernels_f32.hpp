@@ -205,10 +205,8 @@ __global__ void k_reorg_f32(const float *__restrict__ in, float *__restrict__ ou
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= B * 256 * 169) return;
     const int b = t / (256 * 169), o = t - b * (256 * 169);
-    const int k = o / (26 * 416), rem = o - k * (26 * 416), j = rem / 26, i = rem - j * 26;
-    const int sidx = (2 * i + (k & 1)) + 52 * (2 * j + (k >> 1));
-    const int sc = sidx / 676, sr = sidx - sc * 676, sy = sr / 26, sx = sr - sy * 26;
-    const float v = in[(kLead + (long)(sc >> 2) * i_cg_stride + (long)b * iPL + (long)(sy + 1) * iWp + sx) * 4 + (sc & 3)];
+    const ReorgSrc s = reorg_src(o);
+    const float v = in[(kLead + (long)(s.sc >> 2) * i_cg_stride + (long)b * iPL + (long)(s.sy + 1) * iWp + s.sx) * 4 + (s.sc & 3)];
     const int oc = o / 169, orr = o - oc * 169, oy = orr / 13, ox = orr - oy * 13;
     out[(kLead + (long)(oc >> 2) * o_cg_stride + (long)b * oPL + (long)(oy + 1) * oWp + ox) * 4 + (oc & 3)] = v;
 }

@@ -234,11 +234,9 @@ __global__ __launch_bounds__(256) void k_i8_reorg(const signed char *__restrict_
     const int t = blockIdx.x * 256 + threadIdx.x;
     if (t >= B * 256 * 169) return;
     const int b = t / (256 * 169), o = t - b * (256 * 169);
-    const int k = o / (26 * 416), rem = o - k * (26 * 416), j = rem / 26, i = rem - j * 26;
-    const int sidx = (2 * i + (k & 1)) + 52 * (2 * j + (k >> 1));
-    const int sc = sidx / 676, sr = sidx - sc * 676;
+    const ReorgSrc s = reorg_src(o);
     const int oc = o / 169, orr = o - oc * 169;
-    out[((long)b * 169 + orr) * ocs + oc] = in[((long)b * 676 + sr) * ics + sc];
+    out[((long)b * 169 + orr) * ocs + oc] = in[((long)b * 676 + s.sy * 26 + s.sx) * ics + s.sc];
 }
 
 // dense int8 [B][C][HW] -> [B * HW][Cp], pad channels zero (the driver tier's input)

@@ -1310,13 +1310,8 @@ __global__ void k_reorg(const short *__restrict__ in, short *__restrict__ out, i
     if (t >= B * 256 * 169) return;
     const int b = t / (256 * 169);
     const int o = t - b * (256 * 169);  // flat [256][13][13] == flat i + 26*(j + 416*k)
-    const int k = o / (26 * 416);
-    const int rem = o - k * (26 * 416);
-    const int j = rem / 26, i = rem - j * 26;
-    const int sidx = (2 * i + (k & 1)) + 52 * (2 * j + (k >> 1));  // flat [64][26][26]
-    const int sc = sidx / 676, sr = sidx - sc * 676;
-    const int sy = sr / 26, sx = sr - sy * 26;
-    int v = in[(kLead + (long)(sc >> 2) * i_cg_stride + (long)b * iPL + (long)(sy + 1) * iWp + sx) * 4 + (sc & 3)];
+    const ReorgSrc s = reorg_src(o);
+    int v = in[(kLead + (long)(s.sc >> 2) * i_cg_stride + (long)b * iPL + (long)(s.sy + 1) * iWp + s.sx) * 4 + (s.sc & 3)];
     if (shift > 0) v >>= shift;                 // arithmetic, no rounding (yolo2_model.cpp:387-388)
     else if (shift < 0) v = (int)((unsigned)v << (-shift));
     v = clamp16(v);

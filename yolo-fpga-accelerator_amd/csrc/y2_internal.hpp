@@ -1,6 +1,6 @@
 // y2_internal.hpp -- what the translation units of libyolo2_hip.so share (nothing here is part of the C ABI).
 //
-//   yolo2_hip.hip     errors, model tables, context lifecycle, profiling, pre-processing, host-buffer streaming entries
+//   yolo2_hip.hip     errors, model tables (kNet: what the layers are; kWiring: how they are connected - "the wiring" below), context lifecycle, profiling, pre-processing, host-buffer streaming entries
 //   yolo2_driver.hip  tier 1: the reference's accelerator-driver interface (linux_app/include/yolo2_accel_linux.h,
 //                     dma_buffer_manager.h): device state, buffers, register file, per-layer calls
 //   yolo2_int16.hip   the int16 path: weight loading / arithmetic-form proofs, launch planning, autotune, run_batch_int16
@@ -143,6 +143,41 @@ struct LayerDesc {
 // config/yolov2.cfg as parsed by the reference; the C host re-derives the same
 // table from the .cfg file and checks it against this one before using the batched entry.
 extern const LayerDesc kNet[32];
+
+// ---------------------------------------------------------------------------- the wiring (yolo2_hip.hip)
+//
+// kNet says what every layer IS; this says how the layers are CONNECTED.  It is computed once, at compile time, from kNet, the stream
+// lengths and the two [route] lines of config/yolov2.cfg, and it checks itself (static_assert: every reader's c, h, w are its source
+// tensor's).  Every pass reads the graph from here: which tensor a layer reads, which outputs share the concat tensor and from
+// which channel, which tensor has a second reader, which conv writes the region buffer, conv ordinals and stream offsets.
+// A literal layer number may still name a MEASURED CHOICE about a layer (the fp16 kernel policy, the f16_skip masks, layer 0's fused
+// front kernels); it may not restate a fact of the graph.
+struct NetWire {
+    int ord;               // conv ordinal, -1 otherwise
+    long w_off, b_off;     // a conv's first element in the reference's weight / bias streams
+    int n_route, route[4]; // a route layer's sources as the cfg lists them, absolute
+    int src;               // the layer whose output tensor this layer reads (-1: the network input), routes resolved: a route of one
+                           // source stands for that source, a route of several is the concat tensor and stands for itself
+    int cat, ch_off;       // cat >= 0: the output lives in the concat tensor of route layer `cat`, from channel ch_off on (the cfg's order)
+    int readers, reader;   // how many layers read the output (through routes), and the first of them (-1: none)
+    bool to_region;        // the region layer reads it: the pass hands this output to the caller
+    int C, H, W;           // shape of the tensor the output lives in (a member of the concat: the concat's)
+};
+struct NetWiring {
+    NetWire layer[32];
+    int conv_layer[YOLO2_N_CONV];   // ord -> layer
+    int cat_conv, cat_feed;         // the concat's conv member, and the conv its reorg member reads: the two whose Qs the concat ties together
+};
+extern const NetWiring kWiring;
+static constexpr const NetWire (&kWire)[32] = kWiring.layer;
+static constexpr const int (&kConvLayer)[YOLO2_N_CONV] = kWiring.conv_layer;
+// slot of an activation-Q table (slot 0: the network input, slot k + 1: the output of conv k) for the Q layer's output tensor carries:
+// pools and the reorg keep their input's, the concat tensor carries its conv member's
+static inline int y2_act_q_slot(int layer)
+{
+    while (layer >= 0 && kWire[layer].ord < 0) layer = kNet[layer].type == L_ROUTE ? kWiring.cat_conv : kWire[layer].src;
+    return layer < 0 ? 0 : kWire[layer].ord + 1;
+}
 
 static inline unsigned blocks_for(long n, int bs) { return (unsigned)((n + bs - 1) / bs); }
 static inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
@@ -417,6 +452,43 @@ inline void y2_view_of(yolo2_hip_ctx::HalfTensor &v, const yolo2_hip_ctx::HalfTe
     v.own.reset();
     static_cast<yolo2_hip_ctx::HalfGeom &>(v) = of;
     v.d = of.d;
+}
+// the item tensor (Tensor, FTensor) of a [C][H][W] map for B frames, zero-filled: the zeros ARE the conv padding (fp32: +0.0f, also
+// the 4th lane of the input)
+template <typename TensorT>
+int y2_alloc_items(TensorT &t, int C, int H, int W, int B)
+{
+    t.g = y2::make_geom(C, H, W, B);
+    const int rc = y2_alloc_owned(t.own, t.d, (size_t)t.g.items);
+    if (rc) return rc;
+    HIP_TRY(hipMemset(t.d, 0, (size_t)t.g.items * sizeof(*t.d)), YOLO2_DMA_ERROR);
+    return YOLO2_SUCCESS;
+}
+// The tensors of one family as the wiring places them: every conv and pool layer owns a tensor, except that the members of a concat
+// (and its route layer's slot) are views of `cat`, so out[] is indexed by NetWire::src.  alloc(tensor, layer) allocates for that
+// layer's NetWire shape; a family may leave a layer without a tensor (d == nullptr).
+template <typename TensorT, typename Alloc>
+int y2_alloc_tensors(TensorT (&out)[32], TensorT &cat, Alloc alloc)
+{
+    for (int i = 0; i < 32; ++i) {
+        const NetWire &w = kWire[i];
+        int rc = YOLO2_SUCCESS;
+        if (w.cat >= 0) {
+            if (!cat.d && (rc = alloc(cat, w.cat))) return rc;
+            y2_view_of(out[i], cat);
+        } else if ((kNet[i].type == L_CONV || kNet[i].type == L_MAX) && (rc = alloc(out[i], i))) return rc;
+    }
+    return YOLO2_SUCCESS;
+}
+// what conv layer i of an item-layout family (int16, tiled fp32) reads and writes, and the first item of its output: a member of the
+// concat starts at its channel group there
+template <typename TensorT>
+struct Y2ConvIO { const TensorT *tin, *tout; long out_base; };
+template <typename TensorT>
+Y2ConvIO<TensorT> y2_conv_io(int i, const TensorT &in, const TensorT (&out)[32])
+{
+    const NetWire &w = kWire[i];
+    return {w.src < 0 ? &in : &out[w.src], &out[i], y2::kLead + (long)(w.ch_off / 4) * out[i].g.cg_stride};
 }
 // frames on the host -> device, `run(frames_dev, region_dev)` on the null stream, the region tensor (elements of R) back: the four
 // yolo2_hip_run_batch_*_host entries

@@ -83,12 +83,9 @@ int collect(yolo2_hip_ctx *c, unsigned (&host)[kSlots * 2])
     if (rc) return rc;
     unsigned *const s = c->calib_stats.get();
     HIP_TRY(hipMemsetAsync(s + 2 * kWeightSlot, 0, (size_t)2 * YOLO2_N_CONV * 2 * sizeof(unsigned), nullptr), YOLO2_DMA_ERROR);
-    long woff = 0, boff = 0;
     for (int o = 0; o < YOLO2_N_CONV; ++o) {
-        launch_absmax(c->wf32 + woff, yolo2_weight_len[o], s + 2 * (kWeightSlot + o), nullptr);
-        launch_absmax(c->bf32 + boff, yolo2_bias_len[o], s + 2 * (kBiasSlot + o), nullptr);
-        woff += yolo2_weight_len[o];
-        boff += yolo2_bias_len[o];
+        launch_absmax(c->wf32 + kWire[kConvLayer[o]].w_off, yolo2_weight_len[o], s + 2 * (kWeightSlot + o), nullptr);
+        launch_absmax(c->bf32 + kWire[kConvLayer[o]].b_off, yolo2_bias_len[o], s + 2 * (kBiasSlot + o), nullptr);
     }
     HIP_TRY(hipGetLastError(), YOLO2_ERROR);
     HIP_TRY(hipMemcpy(host, s, sizeof(host), hipMemcpyDeviceToHost), YOLO2_DMA_ERROR);
@@ -135,17 +132,15 @@ int y2_calib_frames(yolo2_hip_ctx *c, uint64_t frames_dev, int batch, int counte
         const ActGeom &g = c->f_in.g;
         launch_absmax((const float *)(c->f_in.d + kLead), (long)g.CG * g.cg_stride * 4, s + 2 * kActSlot, st);
     }
-    int ord = 0;
-    for (int i = 0; i < 32; ++i) {
+    for (int ord = 0; ord < YOLO2_N_CONV; ++ord) {
+        const int i = kConvLayer[ord];
         const LayerDesc &l = kNet[i];
-        if (l.type != L_CONV) continue;
         const auto &t = c->f_out[i];
-        // layer 24 is a view of the concat tensor: its channels start behind the 256 of the reorg half (64 channel groups)
-        const long base = kLead + (i == 24 ? (long)64 * t.g.cg_stride : 0);
+        // the concat's conv member is a view of the concat tensor: its channels start behind the reorg half's
+        const long base = y2_conv_io(i, c->f_in, c->f_out).out_base;
         const long items = (long)((l.n + 3) / 4) * t.g.cg_stride;
         if (base + items > t.g.items) return fail(YOLO2_ERROR, "calibration: layer %d's range leaves its tensor", i);
         launch_absmax((const float *)(t.d + base), items * 4, s + 2 * (kActSlot + 1 + ord), st);
-        ord++;
     }
     HIP_TRY(hipGetLastError(), YOLO2_ERROR);
     HIP_TRY(hipStreamSynchronize(st), YOLO2_ERROR);   // (also: `region` is freed on return)
@@ -214,18 +209,13 @@ extern "C" int yolo2_hip_calib_q_from_stats(const float *act_absmax, const float
             return fail(YOLO2_ERROR, "no Q in 0..15 holds the biases of conv %d (max |b| = %g)", o, (double)bias_absmax[o]);
     }
     if ((act_q[0] = q_of(act_absmax[0], 1.0)) < 0) return fail(YOLO2_ERROR, "no Q in 0..15 holds the network input (max = %g)", (double)act_absmax[0]);
-    int ord = 0, ord24 = -1, ord26 = -1;
-    for (int i = 0; i < 32; ++i) {
-        if (kNet[i].type != L_CONV) continue;
-        if (i == 24) ord24 = ord;
-        if (i == 26) ord26 = ord;
+    for (int ord = 0; ord < YOLO2_N_CONV; ++ord)
         if ((act_q[ord + 1] = q_of(act_absmax[ord + 1], headroom)) < 0)
-            return fail(YOLO2_ERROR, "no Q in 0..15 holds the output of conv %d (layer %d, max = %g, headroom %g)", ord, i,
+            return fail(YOLO2_ERROR, "no Q in 0..15 holds the output of conv %d (layer %d, max = %g, headroom %g)", ord, kConvLayer[ord],
                         (double)act_absmax[ord + 1], (double)headroom);
-        ord++;
-    }
-    // the concat fix-up (header comment): the reorg half is only ever shifted down to layer 24's Q
-    if (act_q[ord24 + 1] > act_q[ord26 + 1]) act_q[ord24 + 1] = act_q[ord26 + 1];
+    // the concat fix-up (header comment): the reorg half is only ever shifted down to the Q of the concat's conv member
+    const int q_conv = kWire[kWiring.cat_conv].ord + 1, q_feed = kWire[kWiring.cat_feed].ord + 1;
+    if (act_q[q_conv] > act_q[q_feed]) act_q[q_conv] = act_q[q_feed];
     return YOLO2_SUCCESS;
 }
 
@@ -277,8 +267,9 @@ extern "C" int yolo2_hip_calib_q8_from_stats(const float *act_absmax, float head
         if ((act_q[o + 1] = q8_of(act_absmax[o + 1], headroom)) == -100)
             return fail(YOLO2_ERROR, "no Q in -8..24 holds the output of conv %d (max = %g, headroom %g)", o, (double)act_absmax[o + 1],
                         (double)headroom);
-    // layer 24 is conv 19, layer 26 conv 20: both halves of the concat tensor take the smaller Q, nothing is shifted at run time
-    act_q[20] = act_q[21] = std::min(act_q[20], act_q[21]);
+    // both halves of the concat tensor (its conv member, and the conv its reorg member reads) take the smaller Q: nothing is shifted at run time
+    const int q_conv = kWire[kWiring.cat_conv].ord + 1, q_feed = kWire[kWiring.cat_feed].ord + 1;
+    act_q[q_conv] = act_q[q_feed] = std::min(act_q[q_conv], act_q[q_feed]);
     return YOLO2_SUCCESS;
 }
 
@@ -320,15 +311,12 @@ extern "C" int yolo2_hip_quantize_weights_int16(yolo2_hip_ctx *c, const int32_t 
     Y2DevBuf<short> wq, bq;
     if ((rc = wq.alloc(YOLO2_N_WEIGHTS)) || (rc = bq.alloc(YOLO2_N_BIAS))) return rc;
     HIP_TRY(hipMemsetAsync(slot, 0, 2 * sizeof(unsigned), nullptr), YOLO2_DMA_ERROR);
-    long woff = 0, boff = 0;
     for (int o = 0; o < YOLO2_N_CONV; ++o) {
-        const long nw = yolo2_weight_len[o], nb = yolo2_bias_len[o];
+        const long nw = yolo2_weight_len[o], nb = yolo2_bias_len[o], woff = kWire[kConvLayer[o]].w_off, boff = kWire[kConvLayer[o]].b_off;
         hipLaunchKernelGGL(k_quantize_i16, dim3(calib_grid(nw)), dim3(kCalibBlock), 0, nullptr, (const float *)(c->wf32 + woff), wq.get() + woff,
                            nw, (int)weight_q[o], slot);
         hipLaunchKernelGGL(k_quantize_i16, dim3(calib_grid(nb)), dim3(kCalibBlock), 0, nullptr, (const float *)(c->bf32 + boff), bq.get() + boff,
                            nb, (int)bias_q[o], slot);
-        woff += nw;
-        boff += nb;
     }
     HIP_TRY(hipGetLastError(), YOLO2_ERROR);
     unsigned n_clamped = 0;

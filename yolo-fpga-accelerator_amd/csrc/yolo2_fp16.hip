@@ -148,17 +148,15 @@ static inline int item_halves(int C, bool split) { return split ? round_up(3 * p
 static int pack_half_weights(yolo2_hip_ctx *c, const float *wd, const float *bd)
 {
     long wtot = 0, btot = 0;
-    int ord = 0;
-    for (int i = 0; i < 32; ++i)
-        if (kNet[i].type == L_CONV) {
-            const LayerDesc &l = kNet[i];
-            const int npad = round_up(l.n, l.n <= 64 ? 64 : kBN);
-            c->wh_off[ord] = wtot;
-            c->biasf_off[ord] = btot;
-            wtot += i == 0 ? (long)npad * 32 : (long)npad * l.size * l.size * item_halves(l.c, c->split);
-            btot += npad;
-            ord++;
-        }
+    for (int ord = 0; ord < YOLO2_N_CONV; ++ord) {
+        const int i = kConvLayer[ord];
+        const LayerDesc &l = kNet[i];
+        const int npad = round_up(l.n, l.n <= 64 ? 64 : kBN);
+        c->wh_off[ord] = wtot;
+        c->biasf_off[ord] = btot;
+        wtot += i == 0 ? (long)npad * 32 : (long)npad * l.size * l.size * item_halves(l.c, c->split);
+        btot += npad;
+    }
     for (yolo2_hip_ctx *l : c->f16_lanes) yolo2_hip_destroy(l);   // they alias the buffers that are about to be replaced
     c->f16_lanes.clear();
     y2_f16_plan_free(c);
@@ -172,11 +170,10 @@ static int pack_half_weights(yolo2_hip_ctx *c, const float *wd, const float *bd)
     c->wh = nullptr;
     c->biasf = nullptr;
     if ((rc = y2_alloc_owned(c->wh_own, c->wh, (size_t)wtot)) || (rc = y2_alloc_owned(c->biasf_own, c->biasf, (size_t)btot))) return rc;
-    long woff = 0, boff = 0;
-    ord = 0;
-    for (int i = 0; i < 32; ++i) {
+    for (int ord = 0; ord < YOLO2_N_CONV; ++ord) {
+        const int i = kConvLayer[ord];
         const LayerDesc &l = kNet[i];
-        if (l.type != L_CONV) continue;
+        const long woff = kWire[i].w_off, boff = kWire[i].b_off;
         const int npad = round_up(l.n, l.n <= 64 ? 64 : kBN), KK = l.size * l.size;
         if (c->split && i > 0) {
             const int Cp = item_halves(l.c, true);
@@ -189,9 +186,6 @@ static int pack_half_weights(yolo2_hip_ctx *c, const float *wd, const float *bd)
             hipLaunchKernelGGL(k_pack_weights_f16, dim3(blocks_for(std::max<long>(n, npad), 256)), dim3(256), 0, nullptr, wd + woff,
                                c->wh + c->wh_off[ord], c->biasf + c->biasf_off[ord], bd + boff, l.c, l.n, KK, Cp, npad, i == 0 ? 1 : 0);
         }
-        woff += yolo2_weight_len[ord];
-        boff += yolo2_bias_len[ord];
-        ord++;
     }
     HIP_TRY(hipGetLastError(), YOLO2_ERROR);
     return YOLO2_SUCCESS;
@@ -230,17 +224,15 @@ static int load_fp32_common(yolo2_hip_ctx *c, const void *weights_reorg, size_t 
 }
 
 // ---- tensor geometry: follows from kNet, the batch and the split mode; nothing here allocates.  The tensor that holds layer i's
-// output (a pool layer's: the pooled map; 24 and 27: the concat tensor they are placed in).  C == 0: the layer has none - layer 0's
-// 416x416x32 tensor never exists (conv0+pool are fused), a route concatenates by placement, layer 30 writes the region buffer.
+// output (NetWire's shape: a pool layer's is the pooled map, a member of the concat's the concat tensor it is placed in).  C == 0: the
+// layer has none - layer 0's 416x416x32 tensor never exists (conv0+pool are fused), a route of one source is an alias, the last conv
+// writes the region buffer.
 typedef yolo2_hip_ctx::HalfGeom HalfGeom;
 static HalfGeom f16_geom(int i, bool split, int B)
 {
     HalfGeom g;
-    const LayerDesc &l = kNet[std::max(i, 0)];
-    if (i == 24 || i == 27) { g.C = 1280; g.H = g.W = 13; }
-    else if (i >= 1 && i <= 29 && l.type == L_CONV) { g.C = l.n; g.H = l.h; g.W = l.w; }
-    else if (i >= 1 && i <= 29 && l.type == L_MAX) { g.C = l.c; g.H = l.h / 2; g.W = l.w / 2; }
-    else return g;
+    if (i < 1 || kWire[i].to_region || !(kNet[i].type == L_CONV || kNet[i].type == L_MAX || kWire[i].cat >= 0)) return g;
+    g.C = kWire[i].C; g.H = kWire[i].H; g.W = kWire[i].W;
     g.Cp = item_halves(g.C, split); g.Wp = g.W + 1; g.PL = (g.H + 1) * g.Wp; g.B = B;
     g.items = (size_t)kLead + (size_t)B * g.PL + kTail;
     return g;
@@ -261,11 +253,11 @@ static int ensure_f16_batch(yolo2_hip_ctx *c, int B)
     y2_free_tensors(c->h_in, c->h_out, c->h_cat, c->f16_batch);
     if (c->f16_plan) { c->f16_plan->batch = 0; c->f16_plan->steps.clear(); }   // the table points into the tensors just freed
     int rc;
-    if ((rc = alloc_half(c->h_cat, f16_geom(24, c->split, B)))) return rc;
-    for (int i = 1; i < 30; ++i)
-        if (i != 24 && i != 27 && f16_geom(i, c->split, B).C && (rc = alloc_half(c->h_out[i], f16_geom(i, c->split, B)))) return rc;
-    y2_view_of(c->h_out[24], c->h_cat);
-    y2_view_of(c->h_out[27], c->h_cat);
+    if ((rc = y2_alloc_tensors(c->h_out, c->h_cat, [&](yolo2_hip_ctx::HalfTensor &t, int i) {
+             const HalfGeom g = f16_geom(i, c->split, B);
+             return g.C ? alloc_half(t, g) : (int)YOLO2_SUCCESS;
+         })))
+        return rc;
     c->f16_batch = B;
     // the zero fills above run on the null stream; the pass may be enqueued on a non-blocking stream (the lanes'
     // are), which does not order itself behind it
@@ -386,7 +378,10 @@ static void fuse_pool_into_next(const F16Conv &q, F16Step &s)
     const HalfGeom tp = f16_geom(q.i + 1, q.split, q.B);
     s.a.pool = 1; s.a.oWp = tp.Wp; s.a.oPL = tp.PL; s.a.npool = q.B * tp.H * tp.W; s.a.Cp_out = tp.Cp; s.t_out = q.i + 1;
 }
-// the step runs the 1x1 layer i + 1 in its epilogue and stores THAT layer's tensor (the tensor between them is never written)
+// Layer i + 1 may run in layer i's epilogue: nothing else reads layer i (the tensor between them is never written), and layer
+// i + 1's output starts at channel 0 of the tensor it lives in (true for every conv -> 1x1 pair of this network).
+static bool next_is_only_reader(int i) { return kWire[i].readers == 1 && kWire[i + 1].src == i && kWire[i + 1].ch_off == 0; }
+// the step runs the 1x1 layer i + 1 in its epilogue and stores THAT layer's tensor
 static void fuse_1x1_next(const F16Conv &q, F16Step &s)
 {
     const LayerDesc &nx = kNet[q.i + 1];
@@ -403,7 +398,7 @@ static bool take_rw(const F16Conv &q, F16Step &s)
         ((size_t)kLead + (size_t)q.B * a.PL + kTail) * 128 >= (1ull << 31))   // (signed 32-bit byte offsets into the input)
         return false;
     const bool fuse1 = !q.pool_next && !q.o.f16_no_fuse1x1 && nx.type == L_CONV && nx.size == 1 && nx.c == 128 && nx.n == 64 && nx.leaky == l.leaky &&
-                       nx.h == l.h && nx.w == l.w && q.i + 1 != 16 && q.i + 1 != 24;   // (and nothing but layer i + 1 reads layer i: true for every conv of this network except 16)
+                       nx.h == l.h && nx.w == l.w && next_is_only_reader(q.i);
     s.T = q.B * (l.h / 2); s.grid = persistent_grid(s.T);
     const int n_stage = (2 * l.w + 2 * (l.w + 1) + 7) / 8;
     const bool rwb_ok = !q.o.f16_no_rwb && l.leaky && a.n_store == 128;   // k_conv_f16_rwb: leaky layers, every channel stored
@@ -526,7 +521,7 @@ static bool take_halo(const F16Conv &q, F16Step &s)
     s.grid = dim3(((a.npix + 255) / 256) * a.n_tiles); s.lds = (unsigned)(wide ? lds256 : lds128);   // (without `wide`: the three-buffer 128 form fits)
     // a 256-channel 3x3 whose only consumer is a 1x1 down to 128 channels (layer 8 -> 9): the 1x1 runs in the epilogue
     const bool fuse1 = wide && !q.split && !q.o.f16_no_fuse1x1 && !q.o.f16_m16 && !q.o.f16_w8 && l.n == 256 && a.n_tiles == 1 && nx.type == L_CONV &&
-                       nx.size == 1 && nx.c == 256 && nx.n == 128 && nx.leaky == l.leaky && nx.h == l.h && nx.w == l.w && q.i != 16 && q.i != 24;
+                       nx.size == 1 && nx.c == 256 && nx.n == 128 && nx.leaky == l.leaky && nx.h == l.h && nx.w == l.w && next_is_only_reader(q.i);
     if (fuse1) { fuse_1x1_next(q, s); use(s, FK_HALO_256_1X1); }
     else if (!wide) use(s, q.split ? FK_HALO_128_SP : FK_HALO_128);
     else if (q.split) use(s, FK_HALO_256_SP);
@@ -558,23 +553,25 @@ static int select_f16_table(const Y2Options &o, bool split, int B, F16Table &T)
             T.yuyv_kernel = yuyv.name; T.launch_yuyv = yuyv.launch_u8;
         }
     }
-    int ord = 1, skip_pool = -1, fused_conv = -1, cur = 1;   // (cur: the tensor the next layer reads)
+    // (a fused pool or 1x1 stores the tensor of the layer it swallowed, so every step reads the tensor the wiring names)
+    int skip_pool = -1, fused_conv = -1;
     for (int i = 2; i < 32; ++i) {
         const LayerDesc &l = kNet[i];
+        const NetWire &w = kWire[i];
         switch (l.type) {
         case L_CONV: {
-            if (i == fused_conv) { ord++; cur = i; break; }   // this 1x1 layer ran inside the launch of the 3x3 before it: its tensor exists already
+            if (i == fused_conv) break;   // this 1x1 layer ran inside the launch of the 3x3 before it: its tensor exists already
             F16Step s;
-            s.layer = i; s.B = B; s.w_ord = ord++;
-            s.t_in = i == 26 ? 16 : (i == 29 ? 27 : cur); s.t_out = i == 30 ? -1 : i;
+            s.layer = i; s.B = B; s.w_ord = w.ord;
+            s.t_in = w.src; s.t_out = w.to_region ? -1 : i;
             ConvF16Args &a = s.a;
             a.B = B; a.H = l.h; a.W = l.w; a.Wp = l.w + 1; a.PL = (l.h + 1) * (l.w + 1); a.npix = B * l.h * l.w;
-            a.Cp_in = f16_geom(s.t_in, split, B).Cp; a.Cp_out = i == 30 ? 0 : f16_geom(i, split, B).Cp;
+            a.Cp_in = f16_geom(s.t_in, split, B).Cp; a.Cp_out = f16_geom(i, split, B).Cp;   // (0 for the region buffer)
             a.N = l.n; a.leaky = l.leaky; a.KS = l.size; a.n_tiles = 1; a.stamp = o.stamp_layer == i;
-            a.out_ch_off = i == 24 ? 256 : 0; a.n_store = i == 30 ? l.n : round_up(l.n, 32);
-            a.split_n = split && i != 30 ? part_stride(i == 24 ? 1280 : l.n) : 0;
+            a.out_ch_off = w.ch_off; a.n_store = w.to_region ? l.n : round_up(l.n, 32);
+            a.split_n = split && !w.to_region ? part_stride(w.C) : 0;
             set_fast_div(a);
-            s.store = i == 30 ? FS_REGION : FS_FULL_OR_POOL;
+            s.store = w.to_region ? FS_REGION : FS_FULL_OR_POOL;
             // Conv layers whose only consumer is the 2x2 pool after them (2 and 6; 10 runs the halo kernel, 16 also
             // feeds the route) store the pooled tensor directly: MFMA rows ordered by pool window, max in the epilogue.
             // The persistent halo kernel takes the 104x104 layers EXCEPT layer 6: it stores the full-resolution tensor only
@@ -595,14 +592,13 @@ static int select_f16_table(const Y2Options &o, bool split, int B, F16Table &T)
                                            dst.H, dst.W, dst.Cp, s.store == FS_REGION ? 0 : a.split_n);
             if (rc) return rc;
             T.steps.push_back(s);
-            if (i != 30) cur = s.t_out;
             break;
         }
         case L_MAX: {
-            if (i == skip_pool) { cur = i; break; }   // already produced by the conv before it
-            const HalfGeom gi = f16_geom(cur, split, B), go = f16_geom(i, split, B);
+            if (i == skip_pool) break;   // already produced by the conv before it
+            const HalfGeom gi = f16_geom(w.src, split, B), go = f16_geom(i, split, B);
             F16Step s;
-            s.layer = i; s.B = B; s.t_in = cur; s.t_out = cur = i;
+            s.layer = i; s.B = B; s.t_in = w.src; s.t_out = i;
             s.oCp = go.Cp; s.OH = go.H; s.OW = go.W; s.iWp = gi.Wp; s.iPL = gi.PL; s.oWp = go.Wp; s.oPL = go.PL;
             if (split) s.oPS = part_stride(go.C);
             use(s, split ? FK_MAXPOOL_SP : FK_MAXPOOL);
@@ -611,9 +607,9 @@ static int select_f16_table(const Y2Options &o, bool split, int B, F16Table &T)
             break;
         }
         case L_REORG: {
-            const HalfGeom gi = f16_geom(cur, split, B), go = f16_geom(i, split, B);
+            const HalfGeom gi = f16_geom(w.src, split, B), go = f16_geom(i, split, B);
             F16Step s;
-            s.layer = i; s.B = B; s.t_in = cur; s.t_out = cur = i;
+            s.layer = i; s.B = B; s.t_in = w.src; s.t_out = i;
             s.iCp = gi.Cp; s.iWp = gi.Wp; s.iPL = gi.PL; s.oCp = go.Cp; s.oWp = go.Wp; s.oPL = go.PL;
             if (split) { s.iPS = part_stride(gi.C); s.oPS = part_stride(go.C); }
             use(s, split ? FK_REORG_SP : FK_REORG);
@@ -638,7 +634,7 @@ static int select_f16_table(const Y2Options &o, bool split, int B, F16Table &T)
 // ---- the table as text: one line per step with every field selection sets (yolo2_hip_f16_plan_describe, the `verbose` plan print)
 static std::string f16_table_text(const F16Table &T, const char *prefix)
 {
-    auto tensor = [](int t, const char *none) { return t < 0 ? std::string(none) : (t == 24 || t == 27 ? std::string("cat") : "t" + std::to_string(t)); };
+    auto tensor = [](int t, const char *none) { return t < 0 ? std::string(none) : (kWire[t].cat >= 0 ? std::string("cat") : "t" + std::to_string(t)); };
     std::string out;
     char buf[960], args[320];
     for (const F16Step &s : T.steps) {
@@ -903,20 +899,20 @@ extern "C" int yolo2_hip_debug_f16_tensor(yolo2_hip_ctx *c, int split, int layer
         return yolo2_hip_debug_f16_tensor(l, 0, layer_idx, frame % half, which, out, cap, geom);
     }
     if (layer_idx < 0 || layer_idx > 30) return fail(YOLO2_ERROR, "bad layer %d", layer_idx);
-    if (layer_idx == 30) return fail(YOLO2_ERROR, "layer 30's output is the region tensor the run returns");
+    if (kWire[layer_idx].to_region) return fail(YOLO2_ERROR, "layer %d's output is the region tensor the run returns", layer_idx);
     const LayerDesc &l = kNet[layer_idx];
     if (l.type == L_ROUTE) return fail(YOLO2_ERROR, "route layer %d has no tensor of its own", layer_idx);
     if (!c->f16_plan || c->f16_plan->batch != c->f16_last_batch) return fail(YOLO2_ERROR, "no launch table for the last run");
-    const bool cat = layer_idx == 24 || layer_idx == 27;
-    const yolo2_hip_ctx::HalfTensor &t = cat ? c->h_cat : c->h_out[layer_idx];
-    bool written = false;   // from the table itself: some step stores into this tensor (layer 24 / 27: the step of that layer)
+    const bool cat = kWire[layer_idx].cat >= 0;
+    const yolo2_hip_ctx::HalfTensor &t = c->h_out[layer_idx];
+    bool written = false;   // from the table itself: some step stores into this tensor (a member of the concat: the step of that layer)
     for (const F16Step &s : c->f16_plan->steps)
         if (t.d && s.out == t.d && (!cat || s.layer == layer_idx)) written = true;
     if (!written)
         return fail(YOLO2_ERROR, "layer %d's tensor is not written by the current fp16 plan (its launch is fused or it has none)", layer_idx);
     const int C = l.type == L_MAX ? l.c : (l.type == L_REORG ? 4 * l.c : l.n);
-    const int ps = c->split ? part_stride(cat ? 1280 : C) : t.Cp;
-    const int g[8] = {C, t.Cp, t.H, t.W, t.Wp, which == 0 ? t.PL : (which == 1 ? kLead : kTail), ps, layer_idx == 24 ? 256 : 0};
+    const int ps = c->split ? part_stride(kWire[layer_idx].C) : t.Cp;
+    const int g[8] = {C, t.Cp, t.H, t.W, t.Wp, which == 0 ? t.PL : (which == 1 ? kLead : kTail), ps, kWire[layer_idx].ch_off};
     memcpy(geom, g, sizeof(g));
     if (!out) return YOLO2_SUCCESS;
     const size_t n = (size_t)g[5] * t.Cp;

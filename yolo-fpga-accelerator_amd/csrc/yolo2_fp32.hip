@@ -34,7 +34,7 @@ extern "C" int yolo2_hip_run_frame_fp32_host(yolo2_hip_ctx *c, const float *fram
     if (!c->f16_loaded || !c->wf32) return fail(YOLO2_ERROR, "fp32 weights not loaded (yolo2_hip_load_weights_fp32)");
     HIP_TRY(hipSetDevice(c->device), YOLO2_INIT_ERROR);
     auto w8 = [](int w) { return (w + 7) & ~7; };
-    Y2DevBuf<float> own[32], in0_own, cat_own;   // own[i]: layer i's tensor where it has one of its own (24 and 27 live in cat)
+    Y2DevBuf<float> own[32], in0_own, cat_own;   // own[i]: layer i's tensor where it has one of its own (the concat's members live in cat)
     float *bufs[32] = {nullptr};
     int rc = YOLO2_SUCCESS;
     auto release = [&]() { (void)hipDeviceSynchronize(); };   // before the owners free the buffers the kernels use
@@ -45,57 +45,48 @@ extern "C" int yolo2_hip_run_frame_fp32_host(yolo2_hip_ctx *c, const float *fram
         }
         return o.get();
     };
-    float *const in0 = dalloc(in0_own, (size_t)3 * 416 * 416), *const cat = in0 ? dalloc(cat_own, (size_t)1280 * 13 * 16) : nullptr;
+    const NetWire &wc = kWire[kWire[kWiring.cat_conv].cat];
+    float *const in0 = dalloc(in0_own, (size_t)3 * 416 * 416), *const cat = in0 ? dalloc(cat_own, (size_t)wc.C * wc.H * w8(wc.W)) : nullptr;
     if (!in0 || !cat) { release(); return rc; }
     if (hipMemcpyAsync(in0, frame, (size_t)3 * 416 * 416 * sizeof(float), hipMemcpyHostToDevice, nullptr) != hipSuccess) {
         release();
         return fail(YOLO2_DMA_ERROR, "H2D of the frame failed");
     }
-    const float *cur = in0;
-    long woff = 0, boff = 0;
-    int ord = 0;
+    const float *last = nullptr;
     for (int i = 0; i < 32 && rc == YOLO2_SUCCESS; ++i) {
         const LayerDesc &l = kNet[i];
+        const NetWire &w = kWire[i];
         const int pad = l.type == L_CONV ? (l.size == 3 ? 1 : 0) : 0;
         const int ow = l.type == L_CONV ? (l.w - l.size + 2 * pad) + 1 : l.w / 2, oh = l.type == L_CONV ? (l.h - l.size + 2 * pad) + 1 : l.h / 2;
+        const float *const src = w.src < 0 ? in0 : bufs[w.src];
+        float *dst = nullptr;
+        if (w.cat >= 0) dst = cat + (size_t)w.ch_off * w.H * w8(w.W);   // the concat, by placement
+        else if ((l.type == L_CONV || l.type == L_MAX) && !(dst = dalloc(own[i], (size_t)w.C * oh * w8(ow)))) break;
+        bufs[i] = dst;
         switch (l.type) {
-        case L_CONV: {
-            const float *src = i == 26 ? bufs[16] : (i == 29 ? cat : cur);
-            float *dst = nullptr;
-            if (i == 24) dst = cat + (size_t)256 * 13 * 16;
-            else if (!(dst = dalloc(own[i], (size_t)l.n * oh * w8(ow)))) break;
+        case L_CONV:
             hipLaunchKernelGGL(k_conv_ref_f32, dim3(blocks_for((long)l.n * oh * ow, 256)), dim3(256), 0, nullptr, src, dst,
-                               (const float *)(c->wf32 + woff), (const float *)(c->bf32 + boff), l.c, l.n, l.size, 1, l.w, l.h, ow, oh,
+                               (const float *)(c->wf32 + w.w_off), (const float *)(c->bf32 + w.b_off), l.c, l.n, l.size, 1, l.w, l.h, ow, oh,
                                pad, l.leaky);
-            woff += yolo2_weight_len[ord];
-            boff += yolo2_bias_len[ord];
-            ord++;
-            bufs[i] = dst;
-            cur = dst;
             break;
-        }
-        case L_MAX: {
-            float *const dst = dalloc(own[i], (size_t)l.c * oh * w8(ow));
-            if (!dst) break;
-            hipLaunchKernelGGL((k_pool_ref<float>), dim3(blocks_for((long)l.c * oh * ow, 256)), dim3(256), 0, nullptr, cur, dst, l.c, 2, 2,
+        case L_MAX:
+            hipLaunchKernelGGL((k_pool_ref<float>), dim3(blocks_for((long)l.c * oh * ow, 256)), dim3(256), 0, nullptr, src, dst, l.c, 2, 2,
                                l.w, l.h, ow, oh, -1024.f * 1024.f);   // pad value of core_compute.cpp:291, core_io.cpp:101
-            bufs[i] = dst;
-            cur = dst;
             break;
-        }
         case L_REORG:
-            hipLaunchKernelGGL(k_reorg_ref_f32, dim3(blocks_for(256 * 13 * 13, 256)), dim3(256), 0, nullptr, cur, cat);
-            bufs[i] = cat;
-            cur = cat;
+            hipLaunchKernelGGL(k_reorg_ref_f32, dim3(blocks_for(256 * 13 * 13, 256)), dim3(256), 0, nullptr, src, dst);
+            break;
+        case L_REGION:
+            last = src;   // gathered below
             break;
         default:
-            break;   // route: concat by placement; region: gathered below
+            break;   // route: an alias, or the concat by placement
         }
     }
     if (rc == YOLO2_SUCCESS && hipGetLastError() != hipSuccess) rc = fail(YOLO2_ERROR, "fp32 pass: kernel launch failed");
     if (rc == YOLO2_SUCCESS) {   // yolo2_model.cpp:406-414: 13 of 16 columns
         std::vector<float> padded((size_t)425 * 13 * 16);
-        if (hipMemcpy(padded.data(), cur, padded.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
+        if (hipMemcpy(padded.data(), last, padded.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
             rc = fail(YOLO2_DMA_ERROR, "D2H of the region tensor failed");
         else
             for (int k = 0; k < 425 * 13; ++k) memcpy(region + (size_t)k * 13, padded.data() + (size_t)k * 16, 13 * sizeof(float));
@@ -105,15 +96,6 @@ extern "C" int yolo2_hip_run_frame_fp32_host(yolo2_hip_ctx *c, const float *fram
 }
 
 // ---------------------------------------------------------------------------- exact fp32, tiled (kernels_f32.hpp)
-
-static int alloc_ftensor(yolo2_hip_ctx::FTensor &t, int C, int H, int W, int B)
-{
-    t.g = make_geom(C, H, W, B);
-    const int rc = y2_alloc_owned(t.own, t.d, (size_t)t.g.items);
-    if (rc) return rc;
-    HIP_TRY(hipMemset(t.d, 0, (size_t)t.g.items * 16), YOLO2_DMA_ERROR);   // +0.0f: the conv padding and the 4th lane of the input
-    return YOLO2_SUCCESS;
-}
 
 template <int KS, int P>
 static void launch_conv_f32_n(const ConvPlan &p, const float4 *in, float4 *out, const float4 *w, const float *b, hipStream_t st)
@@ -177,31 +159,24 @@ static int ensure_f32_path(yolo2_hip_ctx *c, int B)
 {
     if (!c->wpkf) {   // pack the resident fp32 blobs: partial tiles zero-padded, like the int16 weights
         long wtot = 0, btot = 0;
-        int ord = 0;
-        for (int i = 0; i < 32; ++i)
-            if (kNet[i].type == L_CONV) {
-                c->wpkf_off[ord] = wtot;
-                c->biasf32_off[ord] = btot;
-                wtot += packed_weight_elems(kNet[i].c, kNet[i].n, kNet[i].size);
-                btot += (long)((kNet[i].n + 31) / 32) * 32;
-                ord++;
-            }
+        for (int ord = 0; ord < YOLO2_N_CONV; ++ord) {
+            const LayerDesc &l = kNet[kConvLayer[ord]];
+            c->wpkf_off[ord] = wtot;
+            c->biasf32_off[ord] = btot;
+            wtot += packed_weight_elems(l.c, l.n, l.size);
+            btot += (long)((l.n + 31) / 32) * 32;
+        }
         int arc;
         if ((arc = y2_alloc_owned(c->wpkf_own, c->wpkf, (size_t)wtot)) || (arc = y2_alloc_owned(c->biasf32_pk_own, c->biasf32_pk, (size_t)btot))) return arc;
         HIP_TRY(hipMemset(c->biasf32_pk, 0, (size_t)btot * 4), YOLO2_DMA_ERROR);
-        long woff = 0, boff = 0;
-        ord = 0;
-        for (int i = 0; i < 32; ++i) {
-            const LayerDesc &l = kNet[i];
-            if (l.type != L_CONV) continue;
+        for (int ord = 0; ord < YOLO2_N_CONV; ++ord) {
+            const LayerDesc &l = kNet[kConvLayer[ord]];
+            const NetWire &w = kWire[kConvLayer[ord]];
             const long n = packed_weight_elems(l.c, l.n, l.size);
-            hipLaunchKernelGGL((k_repack_weights<float>), dim3(blocks_for(n, 256)), dim3(256), 0, nullptr, (const float *)(c->wf32 + woff),
+            hipLaunchKernelGGL((k_repack_weights<float>), dim3(blocks_for(n, 256)), dim3(256), 0, nullptr, (const float *)(c->wf32 + w.w_off),
                                c->wpkf + c->wpkf_off[ord], l.c, l.n, l.size * l.size);
-            HIP_TRY(hipMemcpyAsync(c->biasf32_pk + c->biasf32_off[ord], c->bf32 + boff, (size_t)l.n * 4, hipMemcpyDeviceToDevice, nullptr),
+            HIP_TRY(hipMemcpyAsync(c->biasf32_pk + c->biasf32_off[ord], c->bf32 + w.b_off, (size_t)l.n * 4, hipMemcpyDeviceToDevice, nullptr),
                     YOLO2_DMA_ERROR);
-            woff += yolo2_weight_len[ord];
-            boff += yolo2_bias_len[ord];
-            ord++;
         }
         HIP_TRY(hipGetLastError(), YOLO2_ERROR);
         HIP_TRY(hipDeviceSynchronize(), YOLO2_ERROR);
@@ -209,31 +184,21 @@ static int ensure_f32_path(yolo2_hip_ctx *c, int B)
     if (c->f32_batch == B) return YOLO2_SUCCESS;
     y2_free_tensors(c->f_in, c->f_out, c->f_cat, c->f32_batch);
     int rc;
-    if ((rc = alloc_ftensor(c->f_in, 3, 416, 416, B))) return rc;
-    if ((rc = alloc_ftensor(c->f_cat, 1280, 13, 13, B))) return rc;
-    for (int i = 0; i < 31; ++i) {
-        const LayerDesc &l = kNet[i];
-        if (l.type == L_CONV && i != 24) {
-            if ((rc = alloc_ftensor(c->f_out[i], l.n, l.h, l.w, B))) return rc;
-        } else if (l.type == L_MAX) {
-            if ((rc = alloc_ftensor(c->f_out[i], l.c, l.h / 2, l.w / 2, B))) return rc;
-        }
-    }
-    y2_view_of(c->f_out[24], c->f_cat);
-    y2_view_of(c->f_out[27], c->f_cat);
+    typedef yolo2_hip_ctx::FTensor FTensor;
+    if ((rc = y2_alloc_items(c->f_in, kNet[0].c, kNet[0].h, kNet[0].w, B))) return rc;
+    if ((rc = y2_alloc_tensors(c->f_out, c->f_cat, [&](FTensor &t, int i) { return y2_alloc_items(t, kWire[i].C, kWire[i].H, kWire[i].W, B); }))) return rc;
     c->f32_batch = B;
     // pixels per lane: timed once per layer (the arithmetic does not depend on it)
     const int fp = c->opt.f32_p;   // test hook: 1 / 2 / 4 for every layer (0: timed)
     hipEvent_t e0, e1;
     HIP_TRY(hipEventCreate(&e0), YOLO2_ERROR);
     HIP_TRY(hipEventCreate(&e1), YOLO2_ERROR);
-    int ord = 0;
-    for (int i = 0; i < 32; ++i) {
+    for (int ord = 0; ord < YOLO2_N_CONV; ++ord) {
+        const int i = kConvLayer[ord];
         const LayerDesc &l = kNet[i];
-        if (l.type != L_CONV) continue;
-        const auto &tin = i == 0 ? c->f_in : (i == 26 ? c->f_out[16] : (i == 29 ? c->f_cat : c->f_out[i - 1]));
-        const auto &tout = c->f_out[i];
-        const long out_base = kLead + (i == 24 ? (long)64 * tout.g.cg_stride : 0);
+        const auto io = y2_conv_io(i, c->f_in, c->f_out);
+        const auto &tin = *io.tin, &tout = *io.tout;
+        const long out_base = io.out_base;
         float best = 1e30f;
         int bestP = 2;
         for (int P = 1; P <= 4; P <<= 1) {
@@ -250,7 +215,6 @@ static int ensure_f32_path(yolo2_hip_ctx *c, int B)
             if (t < best) { best = t; bestP = P; }
         }
         plan_conv_f32(c->fp32_plan[i], l, tin.g, tout.g.cg_stride, out_base, bestP);
-        ord++;
     }
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
@@ -274,39 +238,34 @@ extern "C" int yolo2_hip_run_batch_fp32(yolo2_hip_ctx *c, uint64_t frames_dev, i
         hipLaunchKernelGGL(k_pack_input_f32, dim3(blocks_for((long)B * g.H * g.W, 256)), dim3(256), 0, st, (const float *)(uintptr_t)frames_dev,
                            c->f_in.d, B, g.H, g.W, g.Wp, g.PL);
     }
-    int ord = 0;
-    const yolo2_hip_ctx::FTensor *cur = &c->f_in;
     for (int i = 0; i < 32; ++i) {
         const LayerDesc &l = kNet[i];
+        const int ord = kWire[i].ord;
+        const yolo2_hip_ctx::FTensor *const tin = kWire[i].src < 0 ? &c->f_in : &c->f_out[kWire[i].src];   // (a route: the tensor it stands for)
         switch (l.type) {
         case L_CONV: {
-            const auto *tin = i == 26 ? &c->f_out[16] : (i == 29 ? &c->f_cat : cur);
             launch_conv_f32(c->fp32_plan[i], tin->d, c->f_out[i].d, (const float4 *)(c->wpkf + c->wpkf_off[ord]),
                             c->biasf32_pk + c->biasf32_off[ord], st);
-            cur = &c->f_out[i];
-            ord++;
             break;
         }
         case L_MAX: {
-            const ActGeom &gi = cur->g, &go = c->f_out[i].g;
+            const ActGeom &gi = tin->g, &go = c->f_out[i].g;
             const long n = (long)go.CG * B * go.H * go.W;
-            hipLaunchKernelGGL(k_maxpool2_f32, dim3(blocks_for(n, 256)), dim3(256), 0, st, cur->d, c->f_out[i].d, go.CG, B, go.H, go.W, gi.Wp,
+            hipLaunchKernelGGL(k_maxpool2_f32, dim3(blocks_for(n, 256)), dim3(256), 0, st, tin->d, c->f_out[i].d, go.CG, B, go.H, go.W, gi.Wp,
                                gi.PL, go.Wp, go.PL);
-            cur = &c->f_out[i];
             break;
         }
         case L_REORG: {
-            const ActGeom &gi = cur->g, &go = c->f_cat.g;
-            hipLaunchKernelGGL(k_reorg_f32, dim3(blocks_for((long)B * 256 * 169, 256)), dim3(256), 0, st, (const float *)cur->d,
-                               (float *)c->f_cat.d, B, gi.Wp, gi.PL, gi.cg_stride, go.Wp, go.PL, go.cg_stride);
-            cur = &c->f_cat;
+            const ActGeom &gi = tin->g, &go = c->f_out[i].g;
+            hipLaunchKernelGGL(k_reorg_f32, dim3(blocks_for((long)B * 256 * 169, 256)), dim3(256), 0, st, (const float *)tin->d,
+                               (float *)c->f_out[i].d, B, gi.Wp, gi.PL, gi.cg_stride, go.Wp, go.PL, go.cg_stride);
             break;
         }
         case L_ROUTE:
             break;
         case L_REGION: {
-            const ActGeom &g = cur->g;
-            hipLaunchKernelGGL(k_unpack_dense_f32, dim3(blocks_for((long)B * 425 * 169, 256)), dim3(256), 0, st, (const float *)cur->d,
+            const ActGeom &g = tin->g;
+            hipLaunchKernelGGL(k_unpack_dense_f32, dim3(blocks_for((long)B * 425 * 169, 256)), dim3(256), 0, st, (const float *)tin->d,
                                (float *)(uintptr_t)region_dev, B, 425, 13, 13, g.Wp, g.PL, g.cg_stride);
             break;
         }

@@ -37,13 +37,20 @@ extern "C" const char *yolo2_hip_last_error(void) { return g_err; }
 extern "C" int yolo2_hip_set_error(int code, const char *msg) { return fail(code, "%s", msg ? msg : ""); }
 
 // ---------------------------------------------------------------------------- model tables
+// Host data.  The wiring is computed from them at compile time, so they are constexpr - in the host pass only: HIP puts a constexpr
+// global into the device code object as well, where no kernel wants them.
+#ifdef __HIP_DEVICE_COMPILE__
+#define Y2_HOST_TABLE const
+#else
+#define Y2_HOST_TABLE constexpr
+#endif
 
-extern "C" const int yolo2_weight_len[YOLO2_N_CONV] = {864, 18432, 73728, 8192, 73728, 294912, 32768, 294912,
-                                                       1179648, 131072, 1179648, 131072, 1179648, 4718592,
-                                                       524288, 4718592, 524288, 4718592, 9437184, 9437184,
-                                                       32768, 11796480, 435200};
-extern "C" const int yolo2_bias_len[YOLO2_N_CONV] = {32, 64, 128, 64, 128, 256, 128, 256, 512, 256, 512, 256,
-                                                     512, 1024, 512, 1024, 512, 1024, 1024, 1024, 64, 1024, 425};
+extern "C" Y2_HOST_TABLE int yolo2_weight_len[YOLO2_N_CONV] = {864, 18432, 73728, 8192, 73728, 294912, 32768, 294912,
+                                                               1179648, 131072, 1179648, 131072, 1179648, 4718592,
+                                                               524288, 4718592, 524288, 4718592, 9437184, 9437184,
+                                                               32768, 11796480, 435200};
+extern "C" Y2_HOST_TABLE int yolo2_bias_len[YOLO2_N_CONV] = {32, 64, 128, 64, 128, 256, 128, 256, 512, 256, 512, 256,
+                                                             512, 1024, 512, 1024, 512, 1024, 1024, 1024, 64, 1024, 425};
 
 extern "C" long yolo2_strip_int16_layer_pad(const int16_t *file, size_t file_elems, const int *layer_len,
                                             int n_layers, int16_t *dst)
@@ -61,7 +68,7 @@ extern "C" long yolo2_strip_int16_layer_pad(const int16_t *file, size_t file_ele
 
 // config/yolov2.cfg as parsed by the reference; the C host re-derives the same
 // table from the .cfg file and checks it against this one before using the batched entry.
-const LayerDesc kNet[32] = {
+Y2_HOST_TABLE LayerDesc kNet[32] = {
     {L_CONV, 3, 416, 416, 32, 3, 1},    {L_MAX, 32, 416, 416, 32, 2, 0},   {L_CONV, 32, 208, 208, 64, 3, 1},
     {L_MAX, 64, 208, 208, 64, 2, 0},    {L_CONV, 64, 104, 104, 128, 3, 1}, {L_CONV, 128, 104, 104, 64, 1, 1},
     {L_CONV, 64, 104, 104, 128, 3, 1},  {L_MAX, 128, 104, 104, 128, 2, 0}, {L_CONV, 128, 52, 52, 256, 3, 1},
@@ -74,6 +81,101 @@ const LayerDesc kNet[32] = {
     {L_REORG, 64, 26, 26, 256, 0, 0},   {L_ROUTE, 0, 0, 0, 0, 0, 0},       {L_CONV, 1280, 13, 13, 1024, 3, 1},
     {L_CONV, 1024, 13, 13, 425, 1, 0},  {L_REGION, 425, 13, 13, 0, 0, 0},
 };
+
+// The wiring (y2_internal.hpp): kNet plus the cfg's two [route] lines, layers=-9 at layer 25 and layers=-1,-4 at layer 28.
+#ifndef __HIP_DEVICE_COMPILE__
+struct RouteDef { int layer, n, src[4]; };
+constexpr RouteDef kRoutes[] = {{25, 1, {16}}, {28, 2, {27, 24}}};
+
+constexpr NetWiring make_wiring()
+{
+    NetWiring t = {};
+    int ord = 0, own_c[32] = {};
+    long w_off = 0, b_off = 0;
+    for (int i = 0; i < 32; ++i) {
+        const LayerDesc &l = kNet[i];
+        NetWire &w = t.layer[i];
+        w.ord = -1; w.cat = -1; w.reader = -1;
+        w.src = i == 0 ? -1 : (kNet[i - 1].type == L_ROUTE ? t.layer[i - 1].src : i - 1);
+        switch (l.type) {
+        case L_CONV:
+            w.ord = ord; w.w_off = w_off; w.b_off = b_off;
+            t.conv_layer[ord] = i;
+            w_off += yolo2_weight_len[ord]; b_off += yolo2_bias_len[ord]; ord++;
+            w.C = l.n; w.H = l.h; w.W = l.w;
+            break;
+        case L_MAX: w.C = l.c; w.H = l.h / 2; w.W = l.w / 2; break;
+        case L_REORG: w.C = l.n; w.H = l.h / 2; w.W = l.w / 2; break;
+        case L_REGION: w.C = l.c; w.H = l.h; w.W = l.w; break;
+        case L_ROUTE:
+            for (const RouteDef &r : kRoutes) {
+                if (r.layer != i) continue;
+                w.n_route = r.n;
+                for (int k = 0; k < r.n; ++k) w.route[k] = r.src[k];
+            }
+            if (w.n_route == 1) {            // an alias of its source
+                w.src = kNet[w.route[0]].type == L_ROUTE ? t.layer[w.route[0]].src : w.route[0];
+                w.C = t.layer[w.src].C; w.H = t.layer[w.src].H; w.W = t.layer[w.src].W;
+            } else {                         // the concat tensor: its members in the cfg's order
+                w.src = w.cat = i;
+                w.H = t.layer[w.route[0]].H; w.W = t.layer[w.route[0]].W;
+                for (int k = 0; k < w.n_route; ++k) {
+                    NetWire &m = t.layer[w.route[k]];
+                    m.cat = i; m.ch_off = w.C;
+                    w.C += own_c[w.route[k]];
+                    if (m.H != w.H || m.W != w.W) w.C = -1;   // (fails the check below)
+                    if (kNet[w.route[k]].type == L_CONV) t.cat_conv = w.route[k];
+                    if (kNet[w.route[k]].type == L_REORG) t.cat_feed = m.src;
+                }
+                for (int k = 0; k < w.n_route; ++k) t.layer[w.route[k]].C = w.C;
+            }
+            break;
+        }
+        own_c[i] = w.C;
+    }
+    for (int i = 0; i < 32; ++i) {           // who reads what: a reader of the concat tensor reads every member
+        const int s = t.layer[i].src;
+        if (kNet[i].type == L_ROUTE || s < 0) continue;
+        for (int j = 0; j <= s; ++j)
+            if (j == s || t.layer[j].cat == s) {
+                if (t.layer[j].readers++ == 0) t.layer[j].reader = i;
+                t.layer[j].to_region |= kNet[i].type == L_REGION;
+            }
+    }
+    return t;
+}
+// every layer's c, h, w are the shape of the tensor it reads (the concat's channel sum included), and the streams add up
+constexpr bool wiring_ok(const NetWiring &t)
+{
+    for (int i = 0; i < 32; ++i) {
+        const LayerDesc &l = kNet[i];
+        const int s = t.layer[i].src;
+        if (l.type == L_ROUTE) continue;
+        if (s < 0 ? (l.c != 3 || i != 0) : (t.layer[s].C != l.c || t.layer[s].H != l.h || t.layer[s].W != l.w)) return false;
+        if (l.type == L_CONV && (yolo2_weight_len[t.layer[i].ord] != l.c * l.n * l.size * l.size || yolo2_bias_len[t.layer[i].ord] != l.n)) return false;
+    }
+    const NetWire &last = t.layer[t.conv_layer[YOLO2_N_CONV - 1]];
+    return last.w_off + yolo2_weight_len[YOLO2_N_CONV - 1] == YOLO2_N_WEIGHTS && last.b_off + yolo2_bias_len[YOLO2_N_CONV - 1] == YOLO2_N_BIAS;
+}
+constexpr NetWiring kWiring = make_wiring();
+static_assert(wiring_ok(kWiring), "kNet, the route lists and the stream lengths do not describe one network");
+#endif
+
+extern "C" int yolo2_hip_layer_routes(int i, int src[4])
+{
+    if (i < 0 || i >= 32 || !src) return YOLO2_ERROR;
+    for (int k = 0; k < kWire[i].n_route; ++k) src[k] = kWire[i].route[k];
+    return kWire[i].n_route;
+}
+// Test hook: the wiring of layer i as {ord, w_off, b_off, src, cat, ch_off, readers, reader, to_region, C, H, W}
+extern "C" int yolo2_hip_debug_layer_wiring(int i, int out[12])
+{
+    if (i < 0 || i >= 32 || !out) return YOLO2_ERROR;
+    const NetWire &w = kWire[i];
+    const int v[12] = {w.ord, (int)w.w_off, (int)w.b_off, w.src, w.cat, w.ch_off, w.readers, w.reader, w.to_region ? 1 : 0, w.C, w.H, w.W};
+    for (int k = 0; k < 12; ++k) out[k] = v[k];
+    return YOLO2_SUCCESS;
+}
 
 extern "C" int yolo2_hip_num_layers(void) { return 32; }
 extern "C" int yolo2_hip_layer_desc(int i, int desc[9])

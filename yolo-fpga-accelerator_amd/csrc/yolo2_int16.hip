@@ -342,11 +342,12 @@ static int resolve_q(yolo2_hip_ctx *c)
 {
     std::vector<int> lists;   // concatenated block lists of split layers
     const int na = (int)c->act_q.size();
-    int current_Qa = na ? c->act_q[0] : 0, route24_q = 0, pending = -1, ord = 0;
+    int current_Qa = na ? c->act_q[0] : 0, route24_q = 0, pending = -1;
     c->reorg_shift = 0;
     for (int i = 0; i < 32; ++i) {
         const LayerDesc &l = kNet[i];
         if (l.type == L_CONV) {
+            const int ord = kWire[i].ord;
             ConvPlan &p = c->plan[i];
             p.C = l.c; p.N = l.n; p.K = l.size; p.H = l.h; p.W = l.w; p.leaky = l.leaky;
             p.Qa_in = ord < na ? c->act_q[ord] : current_Qa;
@@ -355,7 +356,7 @@ static int resolve_q(yolo2_hip_ctx *c)
             p.Qb = ord < (int)c->bias_q.size() ? c->bias_q[ord] : 0;
             if (pending >= 0) p.Qa_in = pending;
             current_Qa = p.Qa_out;
-            if (i == 24) route24_q = current_Qa;
+            if (i == kWiring.cat_conv) route24_q = current_Qa;
             pending = -1;
             // arithmetic form per block of 32 output channels; launches are grouped by form
             const int MB = (l.n + 31) / 32, so = p.Qa_in + p.Qw - p.Qa_out, sb = p.Qb - p.Qa_out;
@@ -416,7 +417,6 @@ static int resolve_q(yolo2_hip_ctx *c)
                     c->extra[i].push_back(e);
                 }
             }
-            ord++;
         } else if (l.type == L_REORG) {
             if (route24_q > 0) {
                 const int target = std::min(route24_q, current_Qa);
@@ -489,15 +489,15 @@ static int load_common(yolo2_hip_ctx *c, const short *w_dev, size_t n_weights, c
     c->act_q.assign(act_q, act_q + n_aq);
 
     long wtot = 0, btot = 0;
-    int ord = 0;
-    for (int i = 0; i < 32; ++i)
-        if (kNet[i].type == L_CONV) {
-            c->wpk_off[ord] = wtot;
-            c->bias_off[ord] = btot;
-            wtot += packed_weight_elems(kNet[i].c, kNet[i].n, kNet[i].size);
-            btot += (long)((kNet[i].n + 31) / 32) * 32;
-            ord++;
-        }
+    int mb_total = 0;
+    for (int ord = 0; ord < YOLO2_N_CONV; ++ord) {
+        const LayerDesc &l = kNet[kConvLayer[ord]];
+        c->wpk_off[ord] = wtot;
+        c->bias_off[ord] = btot;
+        wtot += packed_weight_elems(l.c, l.n, l.size);
+        btot += (long)((l.n + 31) / 32) * 32;
+        mb_total += (l.n + 31) / 32;
+    }
     int rc;
     c->wpk_own.reset();
     c->bias_pk_own.reset();
@@ -505,9 +505,6 @@ static int load_common(yolo2_hip_ctx *c, const short *w_dev, size_t n_weights, c
     if ((rc = y2_alloc_owned(c->wpk_own, c->wpk, (size_t)wtot)) || (rc = y2_alloc_owned(c->bias_pk_own, c->bias_pk, (size_t)btot))) return rc;
     HIP_TRY(hipMemset(c->bias_pk, 0, (size_t)btot * 2), YOLO2_DMA_ERROR);
     Y2DevBuf<int> bound_own, bound_mb_own, bound_abs_own;
-    int mb_total = 0;
-    for (int i = 0; i < 32; ++i)
-        if (kNet[i].type == L_CONV) mb_total += (kNet[i].n + 31) / 32;
     if ((rc = bound_own.alloc(YOLO2_N_CONV)) || (rc = bound_mb_own.alloc((size_t)mb_total)) || (rc = bound_abs_own.alloc((size_t)mb_total))) return rc;
     int *const bound = bound_own.get(), *const bound_mb = bound_mb_own.get(), *const bound_abs = bound_abs_own.get();
     HIP_TRY(hipMemset(bound, 0, sizeof(int) * YOLO2_N_CONV), YOLO2_DMA_ERROR);
@@ -531,13 +528,11 @@ static int load_common(yolo2_hip_ctx *c, const short *w_dev, size_t n_weights, c
         for (int o = 0; o < YOLO2_N_CONV && bounds_cached; ++o)    // (shape check: the file must describe THIS network)
             bounds_cached = (int)pc->bounds[o].sum_mb.size() == (yolo2_bias_len[o] + 31) / 32;
     }
-    long woff = 0, boff = 0;
-    ord = 0;
-    for (int i = 0; i < 32; ++i) {
-        const LayerDesc &l = kNet[i];
-        if (l.type != L_CONV) continue;
+    for (int ord = 0; ord < YOLO2_N_CONV; ++ord) {
+        const LayerDesc &l = kNet[kConvLayer[ord]];
+        const long boff = kWire[kConvLayer[ord]].b_off;
         const long n = packed_weight_elems(l.c, l.n, l.size);
-        hipLaunchKernelGGL((k_repack_weights<short>), dim3(blocks_for(n, 256)), dim3(256), 0, nullptr, w_dev + woff,
+        hipLaunchKernelGGL((k_repack_weights<short>), dim3(blocks_for(n, 256)), dim3(256), 0, nullptr, w_dev + kWire[kConvLayer[ord]].w_off,
                            c->wpk + c->wpk_off[ord], l.c, l.n, l.size * l.size);
         const int MB = (l.n + 31) / 32;
         if (!bounds_cached) {
@@ -559,9 +554,6 @@ static int load_common(yolo2_hip_ctx *c, const short *w_dev, size_t n_weights, c
             c->maxbias_mb[ord][k / 32] = std::max(c->maxbias_mb[ord][k / 32], v);
         }
         c->maxbias[ord] = mb;
-        woff += yolo2_weight_len[ord];
-        boff += yolo2_bias_len[ord];
-        ord++;
     }
     HIP_TRY(hipGetLastError(), YOLO2_ERROR);
     if (bounds_cached) {
@@ -580,14 +572,11 @@ static int load_common(yolo2_hip_ctx *c, const short *w_dev, size_t n_weights, c
         std::vector<int> hm(mb_total), ha(mb_total);
         HIP_TRY(hipMemcpy(hm.data(), bound_mb, sizeof(int) * mb_total, hipMemcpyDeviceToHost), YOLO2_DMA_ERROR);
         HIP_TRY(hipMemcpy(ha.data(), bound_abs, sizeof(int) * mb_total, hipMemcpyDeviceToHost), YOLO2_DMA_ERROR);
-        int o = 0;
-        for (int i = 0; i < 32; ++i)
-            if (kNet[i].type == L_CONV) {
-                const int MB = (kNet[i].n + 31) / 32;
-                c->maxsum_mb[o].assign(hm.begin() + mb_offs[o], hm.begin() + mb_offs[o] + MB);
-                c->maxabs_mb[o].assign(ha.begin() + mb_offs[o], ha.begin() + mb_offs[o] + MB);
-                o++;
-            }
+        for (int o = 0; o < YOLO2_N_CONV; ++o) {
+            const int MB = (kNet[kConvLayer[o]].n + 31) / 32;
+            c->maxsum_mb[o].assign(hm.begin() + mb_offs[o], hm.begin() + mb_offs[o] + MB);
+            c->maxabs_mb[o].assign(ha.begin() + mb_offs[o], ha.begin() + mb_offs[o] + MB);
+        }
     }
     }
     if ((rc = resolve_q(c))) return rc;
@@ -657,28 +646,13 @@ extern "C" int yolo2_hip_load_weights_int16(yolo2_hip_ctx *c, const int16_t *wei
 extern "C" int yolo2_hip_layer_path(yolo2_hip_ctx *c, int ord)
 {
     if (!c || !c->weights_loaded || ord < 0 || ord >= YOLO2_N_CONV) return -1;
-    int o = 0;
-    for (int i = 0; i < 32; ++i)
-        if (kNet[i].type == L_CONV) {
-            if (o == ord) return c->plan[i].path;
-            o++;
-        }
-    return -1;
+    return c->plan[kConvLayer[ord]].path;
 }
 
 extern "C" int yolo2_hip_layer_path_counts(yolo2_hip_ctx *c, int ord, int counts[5])
 {
     if (!c || !c->weights_loaded || ord < 0 || ord >= YOLO2_N_CONV || !counts) return YOLO2_ERROR;
     for (int k = 0; k < 5; ++k) counts[k] = c->path_counts[ord][k];
-    return YOLO2_SUCCESS;
-}
-
-static int alloc_tensor(Tensor &t, int C, int H, int W, int B)
-{
-    t.g = make_geom(C, H, W, B);
-    const int rc = y2_alloc_owned(t.own, t.d, (size_t)t.g.items);
-    if (rc) return rc;
-    HIP_TRY(hipMemset(t.d, 0, (size_t)t.g.items * 8), YOLO2_DMA_ERROR);  // the zeros ARE the conv padding
     return YOLO2_SUCCESS;
 }
 
@@ -700,12 +674,11 @@ static int autotune(yolo2_hip_ctx *c)
     const int frc = flush_own.alloc(flush_bytes);
     if (frc) return frc;
     void *const flush = flush_own.get();
-    int ord = 0;
-    for (int i = 0; i < 32; ++i) {
-        if (kNet[i].type != L_CONV) continue;
-        const Tensor &tin = i == 0 ? c->t_in : (i == 26 ? c->t_out[16] : (i == 29 ? c->t_cat : c->t_out[i - 1]));
-        const Tensor &tout = c->t_out[i];
-        const long out_base = kLead + (i == 24 ? (long)64 * tout.g.cg_stride : 0);
+    for (int ord = 0; ord < YOLO2_N_CONV; ++ord) {
+        const int i = kConvLayer[ord];
+        const auto io = y2_conv_io(i, c->t_in, c->t_out);
+        const Tensor &tin = *io.tin, &tout = *io.tout;
+        const long out_base = io.out_base;
         const int CGout = (kNet[i].n + 3) / 4;
         std::vector<ConvPlan *> subs{&c->plan[i]};
         for (auto &e : c->extra[i]) subs.push_back(&e);
@@ -778,7 +751,6 @@ static int autotune(yolo2_hip_ctx *c)
             sp->ks = bestKs;
             plan_conv(*sp, tin.g, tout.g.cg_stride, out_base, CGout, o, bestP);
         }
-        ord++;
     }
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
@@ -853,9 +825,9 @@ static int apply_plan_lines(yolo2_hip_ctx *c, Y2LineLookup look, const char *wha
     bool fuse[32] = {false};
     for (int i = 0; i < 32; ++i) {
         if (kNet[i].type != L_CONV) continue;
-        const Tensor &tin = i == 0 ? c->t_in : (i == 26 ? c->t_out[16] : (i == 29 ? c->t_cat : c->t_out[i - 1]));
-        const Tensor &tout = c->t_out[i];
-        const long out_base = kLead + (i == 24 ? (long)64 * tout.g.cg_stride : 0);
+        const auto io = y2_conv_io(i, c->t_in, c->t_out);
+        const Tensor &tin = *io.tin, &tout = *io.tout;
+        const long out_base = io.out_base;
         std::vector<ConvPlan *> subs{&c->plan[i]};
         for (auto &e : c->extra[i]) subs.push_back(&e);
         for (size_t s = 0; s < subs.size(); ++s) {
@@ -948,14 +920,13 @@ static int setup_pool_fusion(yolo2_hip_ctx *c, bool timed, bool default_on)
         if (frc) return frc;
     }
     void *const flush = flush_own.get();
-    int ord = 0;
     for (int i = 0; i < 31; ++i) {
         if (kNet[i].type != L_CONV) continue;
-        const int o = ord++;
         if (kNet[i + 1].type != L_MAX) continue;
-        const Tensor &tin = i == 0 ? c->t_in : c->t_out[i - 1];
+        const int o = kWire[i].ord;
+        const Tensor &tin = *y2_conv_io(i, c->t_in, c->t_out).tin;
         const Tensor &tout = c->t_out[i], &tpool = c->t_out[i + 1];
-        const int full = i == 16 ? 1 : 0;
+        const int full = kWire[i].readers > 1 ? 1 : 0;   // someone besides the pool reads the full-resolution tensor
         ConvPlan fp = c->plan[i];
         bool ok = plan_conv_pool(fp, tin.g, tpool.g, full);
         std::vector<ConvPlan> fx;
@@ -1090,39 +1061,24 @@ static int set_batch_single(yolo2_hip_ctx *c, int batch)
     if (c->batch != batch) {
         y2_free_activations(c);
         int rc;
-        if ((rc = alloc_tensor(c->t_in, 3, 416, 416, batch))) return rc;
-        if ((rc = alloc_tensor(c->t_cat, 1280, 13, 13, batch))) return rc;
-        for (int i = 0; i < 31; ++i) {
-            const LayerDesc &l = kNet[i];
-            if (l.type == L_CONV && i != 24) {
-                if ((rc = alloc_tensor(c->t_out[i], l.n, l.h, l.w, batch))) return rc;
-            } else if (l.type == L_MAX) {
-                if ((rc = alloc_tensor(c->t_out[i], l.c, l.h / 2, l.w / 2, batch))) return rc;
-            }
-        }
-        y2_view_of(c->t_out[24], c->t_cat);  // conv-24 output and the reorg output live in the concat tensor
-        y2_view_of(c->t_out[27], c->t_cat);  // (yolo2_model.cpp:97-104 does the same by arena placement)
+        if ((rc = y2_alloc_items(c->t_in, kNet[0].c, kNet[0].h, kNet[0].w, batch))) return rc;
+        // (the concat's conv and reorg members live in the concat tensor: yolo2_model.cpp:97-104 does the same by arena placement)
+        if ((rc = y2_alloc_tensors(c->t_out, c->t_cat, [&](Tensor &t, int i) { return y2_alloc_items(t, kWire[i].C, kWire[i].H, kWire[i].W, batch); })))
+            return rc;
         c->batch = batch;
     }
     const Y2Options &o = c->opt;
     // what a K-split plan may ask for (0 for batches > 4: no context of more frames ever carries a ks field); the scratch itself is
     // allocated from the plans that were accepted (ensure_ks_scratch), and launch_conv refuses a ks plan it cannot hold
     const size_t ks_pot = ks_potential_bytes(c, batch);
-    auto geom_of = [&](int i, const Tensor *&tin, const Tensor *&tout, long &out_base) {
-        tin = i == 0 ? &c->t_in : (i == 26 ? &c->t_out[16] : (i == 29 ? &c->t_cat : &c->t_out[i - 1]));
-        tout = &c->t_out[i];
-        out_base = kLead + (i == 24 ? (long)64 * tout->g.cg_stride : 0);
-    };
     for (int i = 0; i < 32; ++i) {
         if (kNet[i].type != L_CONV) continue;
-        const Tensor *tin, *tout;
-        long out_base;
-        geom_of(i, tin, tout, out_base);
+        const auto io = y2_conv_io(i, c->t_in, c->t_out);
         const int CGout = (kNet[i].n + 3) / 4;
         c->plan[i].ks_cap = ks_pot;
         c->plan[i].ks = 0;
-        plan_conv(c->plan[i], tin->g, tout->g.cg_stride, out_base, CGout, o);
-        for (auto &e : c->extra[i]) { e.ks_cap = 0; e.ks = 0; plan_conv(e, tin->g, tout->g.cg_stride, out_base, CGout, o); }
+        plan_conv(c->plan[i], io.tin->g, io.tout->g.cg_stride, io.out_base, CGout, o);
+        for (auto &e : c->extra[i]) { e.ks_cap = 0; e.ks = 0; plan_conv(e, io.tin->g, io.tout->g.cg_stride, io.out_base, CGout, o); }
     }
     if (o.force_p > 0) {   // test hooks: one pixels-per-lane value for every layer, optionally one kernel variant wherever it is legal
         for (int i = 0; i < 32; ++i) {
@@ -1131,11 +1087,9 @@ static int set_batch_single(yolo2_hip_ctx *c, int batch)
             c->plan[i].hiacc = o.force_hiacc;
             c->plan[i].ks = (o.force_ks > 0 && batch <= kKsMaxBatch) ? o.force_ks : 0;
             for (auto &e : c->extra[i]) { e.w16 = o.force_w16; e.hiacc = o.force_hiacc; }
-            const Tensor *tin, *tout;
-            long out_base;
-            geom_of(i, tin, tout, out_base);
-            plan_conv(c->plan[i], tin->g, tout->g.cg_stride, out_base, (kNet[i].n + 3) / 4, o, o.force_p);
-            for (auto &e : c->extra[i]) plan_conv(e, tin->g, tout->g.cg_stride, out_base, (kNet[i].n + 3) / 4, o, o.force_p);
+            const auto io = y2_conv_io(i, c->t_in, c->t_out);
+            plan_conv(c->plan[i], io.tin->g, io.tout->g.cg_stride, io.out_base, (kNet[i].n + 3) / 4, o, o.force_p);
+            for (auto &e : c->extra[i]) plan_conv(e, io.tin->g, io.tout->g.cg_stride, io.out_base, (kNet[i].n + 3) / 4, o, o.force_p);
         }
         c->plan_source = 4;
         const int rc = ensure_ks_scratch(c, ks_needed_bytes(c));
@@ -1208,21 +1162,15 @@ extern "C" int yolo2_hip_conv_launch_info(yolo2_hip_ctx *c, int ord, int *grid_x
 {
     if (!c || !c->batch) return fail(YOLO2_ERROR, "set_batch first");
     if (c->laned) return yolo2_hip_conv_launch_info(c->lanes[0], ord, grid_x, grid_y, block, lds_bytes, ppl);
-    int o = 0;
-    for (int i = 0; i < 32; ++i)
-        if (kNet[i].type == L_CONV) {
-            if (o == ord) {
-                const ConvPlan &pl = c->fuse_pool[i] ? c->fplan[i] : c->plan[i];
-                if (grid_x) *grid_x = pl.grid.x;
-                if (grid_y) *grid_y = pl.grid.y;
-                if (block) *block = pl.w16 ? 128 : 256;   // 128 = k_conv_i16_w16 (16 output channels per wavefront)
-                if (lds_bytes) *lds_bytes = pl.lds_bytes;
-                if (ppl) *ppl = pl.ks ? -pl.ks : (pl.splitk ? 0 : pl.P);   // 0: lane-split K kernel; -S: K split over S workgroups
-                return YOLO2_SUCCESS;
-            }
-            o++;
-        }
-    return fail(YOLO2_ERROR, "bad conv ordinal %d", ord);
+    if (ord < 0 || ord >= YOLO2_N_CONV) return fail(YOLO2_ERROR, "bad conv ordinal %d", ord);
+    const int i = kConvLayer[ord];
+    const ConvPlan &pl = c->fuse_pool[i] ? c->fplan[i] : c->plan[i];
+    if (grid_x) *grid_x = pl.grid.x;
+    if (grid_y) *grid_y = pl.grid.y;
+    if (block) *block = pl.w16 ? 128 : 256;   // 128 = k_conv_i16_w16 (16 output channels per wavefront)
+    if (lds_bytes) *lds_bytes = pl.lds_bytes;
+    if (ppl) *ppl = pl.ks ? -pl.ks : (pl.splitk ? 0 : pl.P);   // 0: lane-split K kernel; -S: K split over S workgroups
+    return YOLO2_SUCCESS;
 }
 
 // The launch plan of conv layer `ord` as text (lane 0's with lanes): "P=1 pad=0 w16=0 hiacc=1 ks=0 splitk=0 pp=1 grp=1 fused=0 form=4 extra=0 edge=0"
@@ -1234,18 +1182,12 @@ extern "C" int yolo2_hip_conv_plan_string(yolo2_hip_ctx *c, int ord, char *buf, 
     if (!c || !buf || cap <= 0) return fail(YOLO2_ERROR, "null argument");
     if (!c->batch) return fail(YOLO2_ERROR, "set_batch first");
     if (c->laned) return yolo2_hip_conv_plan_string(c->lanes[0], ord, buf, cap);
-    int o = 0;
-    for (int i = 0; i < 32; ++i)
-        if (kNet[i].type == L_CONV) {
-            if (o == ord) {
-                const ConvPlan &pl = c->fuse_pool[i] ? c->fplan[i] : c->plan[i];
-                snprintf(buf, (size_t)cap, "P=%d pad=%d w16=%d hiacc=%d ks=%d splitk=%d pp=%d grp=%d fused=%d form=%d extra=%zu edge=%d xcd=%d pack=%d", pl.P, pl.lds_pad, pl.w16,
-                         pl.hiacc, pl.ks, pl.splitk, pl.splitk_pp, pl.grp, pl.pool_fused, pl.path, c->extra[i].size(), pl.args.edge, pl.args.xcd_remap, pl.splitk_pack);
-                return YOLO2_SUCCESS;
-            }
-            o++;
-        }
-    return fail(YOLO2_ERROR, "bad conv ordinal %d", ord);
+    if (ord < 0 || ord >= YOLO2_N_CONV) return fail(YOLO2_ERROR, "bad conv ordinal %d", ord);
+    const int i = kConvLayer[ord];
+    const ConvPlan &pl = c->fuse_pool[i] ? c->fplan[i] : c->plan[i];
+    snprintf(buf, (size_t)cap, "P=%d pad=%d w16=%d hiacc=%d ks=%d splitk=%d pp=%d grp=%d fused=%d form=%d extra=%zu edge=%d xcd=%d pack=%d", pl.P, pl.lds_pad, pl.w16,
+             pl.hiacc, pl.ks, pl.splitk, pl.splitk_pp, pl.grp, pl.pool_fused, pl.path, c->extra[i].size(), pl.args.edge, pl.args.xcd_remap, pl.splitk_pack);
+    return YOLO2_SUCCESS;
 }
 
 extern "C" int yolo2_hip_run_batch_int16(yolo2_hip_ctx *c, uint64_t frames_dev, int batch, uint64_t region_dev,
@@ -1299,13 +1241,12 @@ extern "C" int yolo2_hip_run_batch_int16(yolo2_hip_ctx *c, uint64_t frames_dev, 
         hipLaunchKernelGGL(k_pack_input, dim3(blocks_for((long)B * g.H * g.W, 256)), dim3(256), 0, st, frames, c->t_in.d, B,
                            g.H, g.W, g.Wp, g.PL, scale);
     }
-    int ord = 0;
-    const Tensor *cur = &c->t_in;
     for (int i = 0; i < 32; ++i) {
         const LayerDesc &l = kNet[i];
+        const int ord = kWire[i].ord;
+        const Tensor *const tin = kWire[i].src < 0 ? &c->t_in : &c->t_out[kWire[i].src];   // (a route: the tensor it stands for)
         switch (l.type) {
         case L_CONV: {
-            const Tensor *tin = i == 26 ? &c->t_out[16] : (i == 29 ? &c->t_cat : cur);
             const int2 *wp = (const int2 *)(c->wpk + c->wpk_off[ord]);
             const short *bp = c->bias_pk + c->bias_off[ord];
             int lrc;
@@ -1318,28 +1259,24 @@ extern "C" int yolo2_hip_run_batch_int16(yolo2_hip_ctx *c, uint64_t frames_dev, 
                     if (!lrc) lrc = launch_conv(e, tin->d, c->t_out[i].d, wp, bp, st);
             }
             if (lrc) return lrc;
-            cur = &c->t_out[i];
-            ord++;
             break;
         }
         case L_MAX: {
-            if (!c->fuse_pool[i - 1]) launch_maxpool(*cur, c->t_out[i], B, st);
-            cur = &c->t_out[i];
+            if (!c->fuse_pool[i - 1]) launch_maxpool(*tin, c->t_out[i], B, st);
             break;
         }
         case L_REORG: {
-            const ActGeom &gi = cur->g, &go = c->t_cat.g;
-            hipLaunchKernelGGL(k_reorg, dim3(blocks_for((long)B * 256 * 169, 256)), dim3(256), 0, st, (const short *)cur->d,
-                               (short *)c->t_cat.d, B, gi.Wp, gi.PL, gi.cg_stride, go.Wp, go.PL, go.cg_stride, c->reorg_shift);
-            cur = &c->t_cat;
+            const ActGeom &gi = tin->g, &go = c->t_out[i].g;
+            hipLaunchKernelGGL(k_reorg, dim3(blocks_for((long)B * 256 * 169, 256)), dim3(256), 0, st, (const short *)tin->d,
+                               (short *)c->t_out[i].d, B, gi.Wp, gi.PL, gi.cg_stride, go.Wp, go.PL, go.cg_stride, c->reorg_shift);
             break;
         }
         case L_ROUTE:
             break;  // concat by placement (yolo2_model.cpp:404-405)
         case L_REGION: {
-            const ActGeom &g = cur->g;
+            const ActGeom &g = tin->g;
             hipLaunchKernelGGL(k_unpack_dense, dim3(blocks_for((long)B * 425 * 169, 256)), dim3(256), 0, st,
-                               (const short *)cur->d, region, B, 425, 13, 13, g.Wp, g.PL, g.cg_stride);
+                               (const short *)tin->d, region, B, 425, 13, 13, g.Wp, g.PL, g.cg_stride);
             break;
         }
         }
@@ -1367,7 +1304,7 @@ extern "C" int yolo2_hip_debug_layer_output(yolo2_hip_ctx *c, int layer_idx, int
         while (li > 0 && frame < c->lane_first[li]) --li;
         return yolo2_hip_debug_layer_output(c->lanes[li], layer_idx, frame - c->lane_first[li], out, cap, out_elems);
     }
-    if (layer_idx >= 0 && c->fuse_pool[layer_idx] && layer_idx != 16)
+    if (layer_idx >= 0 && c->fuse_pool[layer_idx] && kWire[layer_idx].readers == 1)
         return fail(YOLO2_ERROR, "layer %d's tensor is not materialised: conv + pool run fused (YOLO2_NO_POOLFUSE=1 keeps it)", layer_idx);
     // layer -1 = the quantised network input (yolo2_model.cpp:257-273), 3 x 416 x 416
     const LayerDesc &l = kNet[layer_idx < 0 ? 0 : layer_idx];
@@ -1375,7 +1312,7 @@ extern "C" int yolo2_hip_debug_layer_output(yolo2_hip_ctx *c, int layer_idx, int
     const Tensor &t = layer_idx < 0 ? c->t_in : c->t_out[layer_idx];
     int C = layer_idx < 0 ? 3 : (l.type == L_MAX ? l.c : l.n), H = t.g.H, W = t.g.W;
     const short *base = (const short *)t.d;
-    if (layer_idx == 24) base += (long)64 * t.g.cg_stride * 4;  // channels 256.. of the concat tensor
+    if (layer_idx >= 0) base += (long)(kWire[layer_idx].ch_off / 4) * t.g.cg_stride * 4;  // a member of the concat tensor: its channels there
     const int W8 = (W + 7) & ~7;
     const size_t n = (size_t)C * H * W8;
     if (out_elems) *out_elems = n;

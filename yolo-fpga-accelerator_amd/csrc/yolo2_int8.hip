@@ -48,7 +48,7 @@ constexpr int kQMin = -8, kQMax = 24, kSMin = -7, kSMax = 31;
 int tile_m(int N) { return N <= 32 ? 32 : (N <= 64 ? 64 : 128); }
 
 // Q of the tensor conv ordinal `ord` reads
-int qin_of(int ord, const int32_t *act_q) { return ord == 20 ? act_q[13] : (ord == 21 ? act_q[20] : act_q[ord]); }
+int qin_of(int ord, const int32_t *act_q) { return act_q[y2_act_q_slot(kWire[kConvLayer[ord]].src)]; }
 
 void launch_conv(const ConvI8Args &a, bool fout, hipStream_t st)
 {
@@ -133,46 +133,33 @@ int ensure_tensors(Y2I8 *s, int batch, bool front)
         t.own.reset();
         t.d = of.d + ch0; t.C = C; t.cs = of.cs; t.H = of.H; t.W = of.W; t.q = q;
     };
-    if ((rc = make(s->t_in, 3, 416, 416, s->act_q[0]))) return rc;
-    if ((rc = make(s->t[28], 1280, 13, 13, s->act_q[20]))) return rc;   // the concat tensor: reorg half, then layer 24
-    const Y2I8Tensor *cur = &s->t_in;
-    int ord = 0;
-    for (int i = 0; i < 30; ++i) {
+    if ((rc = make(s->t_in, kNet[0].c, kNet[0].h, kNet[0].w, s->act_q[0]))) return rc;
+    const int cat = kWire[kWiring.cat_conv].cat;   // the concat tensor: its route layer's slot, the members are views into it
+    if ((rc = make(s->t[cat], kWire[cat].C, kWire[cat].H, kWire[cat].W, s->act_q[y2_act_q_slot(cat)]))) return rc;
+    for (int i = 0; i < 32; ++i) {
         const LayerDesc &l = kNet[i];
+        const NetWire &w = kWire[i];
         Y2I8Tensor &t = s->t[i];
-        switch (l.type) {
-        case L_CONV:
-            if (i == 24) view(t, s->t[28], 256, l.n, s->act_q[ord + 1]);
-            else if ((rc = make(t, l.n, l.h, l.w, s->act_q[ord + 1]))) return rc;
-            ord++;
-            break;
-        case L_MAX:
-            if ((rc = make(t, l.c, l.h / 2, l.w / 2, cur->q))) return rc;
-            break;
-        case L_ROUTE:
-            if (i == 25) view(t, s->t[16], 0, s->t[16].C, s->t[16].q);
-            break;   // 28 is the concat tensor itself
-        case L_REORG:
-            view(t, s->t[28], 0, 256, cur->q);
-            break;
-        default:
-            break;
-        }
-        cur = &t;
+        const int q = s->act_q[y2_act_q_slot(l.type == L_CONV ? i : w.src)];   // a conv's own, otherwise its input's
+        if (w.to_region || l.type == L_REGION || i == cat) continue;
+        if (w.cat >= 0) view(t, s->t[cat], w.ch_off, l.n, q);
+        else if (l.type == L_ROUTE) view(t, s->t[w.src], 0, s->t[w.src].C, s->t[w.src].q);
+        else if ((rc = make(t, w.C, w.H, w.W, q))) return rc;
     }
     s->batch = batch;
     s->front_tensors = front;
     return YOLO2_SUCCESS;
 }
 
-// layers first..30 of the pass on `cur` (the tensor layer `first` reads; `ord` = its conv ordinal), shared by the frames route
-// (first = 0) and the images route (first = 2); ev[i + 1] is recorded behind layer i
-int run_layers(Y2I8 *s, int first, const Y2I8Tensor *cur, int ord, int batch, uint64_t region_dev, hipStream_t st, hipEvent_t *ev)
+// layers first..30 of the pass on `cur` (the tensor layer `first` reads), shared by the frames route (first = 0) and the images
+// route (first = 2); ev[i + 1] is recorded behind layer i
+int run_layers(Y2I8 *s, int first, const Y2I8Tensor *cur, int batch, uint64_t region_dev, hipStream_t st, hipEvent_t *ev)
 {
     for (int i = first; i < 32; ++i) {
         const LayerDesc &l = kNet[i];
         if (l.type == L_CONV) {
             if (cur->C != l.c || cur->H != l.h || cur->W != l.w) return fail(YOLO2_ERROR, "int8 pass: layer %d does not fit the tensor it reads", i);
+            const int ord = kWire[i].ord;
             ConvI8Args a;
             a.in = cur->d;
             a.w = s->wpk.get() + s->wpk_off[ord];
@@ -181,7 +168,7 @@ int run_layers(Y2I8 *s, int first, const Y2I8Tensor *cur, int ord, int batch, ui
             a.CC = cur->cs / 32;
             a.K = l.size; a.H = l.h; a.W = l.w; a.P = batch * l.h * l.w;
             a.N = l.n; a.Np = s->Np[ord]; a.leaky = l.leaky;
-            if (i == 30) {
+            if (kWire[i].to_region) {
                 a.out = (void *)(uintptr_t)region_dev;
                 a.ocs = 0;
             } else {
@@ -189,8 +176,7 @@ int run_layers(Y2I8 *s, int first, const Y2I8Tensor *cur, int ord, int batch, ui
                 a.ocs = s->t[i].cs;
                 cur = &s->t[i];
             }
-            launch_conv(a, i == 30, st);
-            ord++;
+            launch_conv(a, kWire[i].to_region, st);
         } else if (l.type == L_MAX) {
             const long n = (long)batch * (l.h / 2) * (l.w / 2) * (cur->cs / 16);
             hipLaunchKernelGGL(k_i8_pool, dim3(blocks_for(n, 256)), dim3(256), 0, st, (const signed char *)cur->d, s->t[i].d, l.h, l.w, cur->cs, n);
@@ -227,28 +213,20 @@ extern "C" int yolo2_hip_quantize_weights_int8(yolo2_hip_ctx *c, const int32_t *
     Y2DevBuf<int> b32, qw;
     int rc;
     if ((rc = w8.alloc(YOLO2_N_WEIGHTS)) || (rc = b32.alloc(YOLO2_N_BIAS)) || (rc = qw.alloc(YOLO2_N_BIAS))) return rc;
-    long woff = 0, boff = 0;
-    int ord = 0;
-    for (int i = 0; i < 32; ++i) {
-        const LayerDesc &l = kNet[i];
-        if (l.type != L_CONV) continue;
+    for (int ord = 0; ord < YOLO2_N_CONV; ++ord) {
+        const LayerDesc &l = kNet[kConvLayer[ord]];
+        const long woff = kWire[kConvLayer[ord]].w_off, boff = kWire[kConvLayer[ord]].b_off;
         hipLaunchKernelGGL(k_quantize_i8, dim3(l.n), dim3(256), 0, nullptr, (const float *)(c->wf32 + woff), (const float *)(c->bf32 + boff),
                            w8.get() + woff, b32.get() + boff, qw.get() + boff, l.n, l.c, l.size * l.size, qin_of(ord, act_q));
-        woff += yolo2_weight_len[ord];
-        boff += yolo2_bias_len[ord];
-        ord++;
     }
     HIP_TRY(hipGetLastError(), YOLO2_ERROR);
     HIP_TRY(hipMemcpy(w8_out, w8.get(), (size_t)YOLO2_N_WEIGHTS, hipMemcpyDeviceToHost), YOLO2_DMA_ERROR);
     HIP_TRY(hipMemcpy(bias32_out, b32.get(), (size_t)YOLO2_N_BIAS * sizeof(int32_t), hipMemcpyDeviceToHost), YOLO2_DMA_ERROR);
     HIP_TRY(hipMemcpy(weight_q_out, qw.get(), (size_t)YOLO2_N_BIAS * sizeof(int32_t), hipMemcpyDeviceToHost), YOLO2_DMA_ERROR);
-    boff = 0;
-    for (int o = 0; o < YOLO2_N_CONV; ++o) {
+    for (int o = 0; o < YOLO2_N_CONV; ++o)
         for (int m = 0; m < yolo2_bias_len[o]; ++m)
-            if (weight_q_out[boff + m] == kI8NoQ)
+            if (weight_q_out[kWire[kConvLayer[o]].b_off + m] == kI8NoQ)
                 return fail(YOLO2_ERROR, "no Q in %d..%d holds the weights of conv %d, channel %d (or one of them is not finite)", kQMin, kQMax, o, m);
-        boff += yolo2_bias_len[o];
-    }
     return YOLO2_SUCCESS;
 }
 
@@ -263,19 +241,19 @@ extern "C" int yolo2_hip_load_weights_int8(yolo2_hip_ctx *c, const int8_t *w8, s
         return fail(YOLO2_ERROR, "int8 weight set of %zu weights / %zu channels, the network has %d / %d", n_w, n_b, YOLO2_N_WEIGHTS, YOLO2_N_BIAS);
     for (int i = 0; i <= YOLO2_N_CONV; ++i)
         if (act_q[i] < kQMin || act_q[i] > kQMax) return fail(YOLO2_ERROR, "act_q[%d] = %d outside %d..%d", i, act_q[i], kQMin, kQMax);
-    if (act_q[20] != act_q[21])
-        return fail(YOLO2_ERROR, "act_q[20] = %d (layer 24) and act_q[21] = %d (layer 26) differ: the concat tensor of layer 29 needs one Q", act_q[20],
-                    act_q[21]);
+    const int q_conv = kWire[kWiring.cat_conv].ord + 1, q_feed = kWire[kWiring.cat_feed].ord + 1;
+    if (act_q[q_conv] != act_q[q_feed])
+        return fail(YOLO2_ERROR, "act_q[%d] = %d (layer %d) and act_q[%d] = %d (layer %d) differ: the concat tensor of layer %d needs one Q", q_conv,
+                    act_q[q_conv], kWiring.cat_conv, q_feed, act_q[q_feed], kWiring.cat_feed, kWire[kWire[kWiring.cat_conv].cat].reader);
     // every refusal on the host, before anything is allocated or launched
     std::vector<int> sh_host;
     long wpk_off[YOLO2_N_CONV], ch_off[YOLO2_N_CONV], wtot = 0, ctot = 0;
     int Np[YOLO2_N_CONV];
     {
-        long woff = 0, boff = 0;
-        int ord = 0;
-        for (int i = 0; i < 32; ++i) {
+        for (int ord = 0; ord < YOLO2_N_CONV; ++ord) {
+            const int i = kConvLayer[ord];
             const LayerDesc &l = kNet[i];
-            if (l.type != L_CONV) continue;
+            const long woff = kWire[i].w_off, boff = kWire[i].b_off;
             Np[ord] = round_up(l.n, tile_m(l.n));
             wpk_off[ord] = wtot;
             ch_off[ord] = ctot;
@@ -285,11 +263,8 @@ extern "C" int yolo2_hip_load_weights_int8(yolo2_hip_ctx *c, const int8_t *w8, s
             char what[48];
             snprintf(what, sizeof(what), "conv %d (layer %d)", ord, i);
             const int rc = check_layer(what, w8 + woff, bias32 + boff, weight_q + boff, l.n, (long)l.c * l.size * l.size, qin_of(ord, act_q),
-                                       act_q[ord + 1], i == 30, sh_host.data() + ch_off[ord]);
+                                       act_q[ord + 1], kWire[i].to_region, sh_host.data() + ch_off[ord]);
             if (rc) return rc;
-            woff += yolo2_weight_len[ord];
-            boff += yolo2_bias_len[ord];
-            ord++;
         }
     }
     HIP_TRY(hipSetDevice(c->device), YOLO2_INIT_ERROR);
@@ -311,18 +286,10 @@ extern "C" int yolo2_hip_load_weights_int8(yolo2_hip_ctx *c, const int8_t *w8, s
         HIP_TRY(hipMemcpy(s->w0front.get(), front, sizeof(front), hipMemcpyHostToDevice), YOLO2_DMA_ERROR);
     }
     std::vector<int> bias_host(ctot, 0);
-    {
-        long woff = 0, boff = 0;
-        int ord = 0;
-        for (int i = 0; i < 32; ++i) {
-            const LayerDesc &l = kNet[i];
-            if (l.type != L_CONV) continue;
-            memcpy(bias_host.data() + ch_off[ord], bias32 + boff, (size_t)l.n * sizeof(int));
-            launch_pack_weights(nat.get() + woff, s->wpk.get() + wpk_off[ord], l.n, l.c, l.size, Np[ord], nullptr);
-            woff += yolo2_weight_len[ord];
-            boff += yolo2_bias_len[ord];
-            ord++;
-        }
+    for (int ord = 0; ord < YOLO2_N_CONV; ++ord) {
+        const LayerDesc &l = kNet[kConvLayer[ord]];
+        memcpy(bias_host.data() + ch_off[ord], bias32 + kWire[kConvLayer[ord]].b_off, (size_t)l.n * sizeof(int));
+        launch_pack_weights(nat.get() + kWire[kConvLayer[ord]].w_off, s->wpk.get() + wpk_off[ord], l.n, l.c, l.size, Np[ord], nullptr);
     }
     HIP_TRY(hipGetLastError(), YOLO2_ERROR);
     HIP_TRY(hipMemcpy(s->bias.get(), bias_host.data(), (size_t)ctot * sizeof(int), hipMemcpyHostToDevice), YOLO2_DMA_ERROR);
@@ -358,7 +325,7 @@ extern "C" int yolo2_hip_run_batch_int8(yolo2_hip_ctx *c, uint64_t frames_dev, i
                            s->act_q[0], 416 * 416, n);
     }
     if (ev) HIP_TRY(hipEventRecord(ev[0], st), YOLO2_ERROR);
-    if ((rc = run_layers(s, 0, &s->t_in, 0, batch, region_dev, st, ev))) return rc;
+    if ((rc = run_layers(s, 0, &s->t_in, batch, region_dev, st, ev))) return rc;
     if (ev) c->prof_runs++;
     s->last_batch = batch;
     s->last_fused = false;
@@ -398,7 +365,7 @@ int y2_i8_run_images(yolo2_hip_ctx *c, const uint8_t *lb, bool yuyv, int batch, 
     if (yuyv) hipLaunchKernelGGL(k_i8_front_pix<LbYuyv>, grid, block, 0, st, a);
     else hipLaunchKernelGGL(k_i8_front_pix<LbInterleaved>, grid, block, 0, st, a);
     if (ev) (void)hipEventRecord(ev[2], st);
-    if ((rc = run_layers(s, 2, &s->t[1], 1, batch, (uint64_t)(uintptr_t)region_dev, st, ev))) return rc;
+    if ((rc = run_layers(s, 2, &s->t[1], batch, (uint64_t)(uintptr_t)region_dev, st, ev))) return rc;
     if (ev) c->prof_runs++;
     s->last_batch = batch;
     s->last_fused = true;

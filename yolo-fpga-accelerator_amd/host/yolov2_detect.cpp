@@ -290,6 +290,9 @@ void check_topology(const y2h::Network &net)
         if (l.type == y2h::CONV) ok = ok && d[1] == l.c && d[2] == l.h && d[3] == l.w && d[4] == l.n && d[5] == l.size && d[6] == l.stride && d[7] == l.pad && d[8] == (int)l.leaky;
         if (l.type == y2h::MAXPOOL) ok = ok && d[1] == l.c && d[2] == l.h && d[3] == l.w && d[5] == l.size && d[6] == l.stride;
         if (l.type == y2h::REORG) ok = ok && d[1] == l.c && d[2] == l.h && d[6] == l.stride;
+        int src[4];
+        const int n_src = yolo2_hip_layer_routes(i, src);   // (0 for a layer that is no route: the cfg's list is empty there too)
+        ok = ok && n_src == (int)l.route_layers.size() && std::equal(l.route_layers.begin(), l.route_layers.end(), src);
         if (!ok) throw std::runtime_error("cfg layer " + std::to_string(i) + " differs from the network the hip backend implements");
     }
 }
