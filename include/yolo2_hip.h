@@ -803,6 +803,20 @@ int yolo2_hip_run_images_jpeg_dets(yolo2_hip_ctx *ctx, int precision, const uint
  * yolo2_hip_set_profiling was on -; [4] bytes uploaded as descriptors, tables and streams; [5] bytes uploaded as letterbox tables
  * and raw frames; [6] chunks; [7] frames. */
 int yolo2_hip_jpeg_last_info(yolo2_hip_ctx *ctx, double *out8);
+/* Option "jpegdec_split" = S (yolo2_hip_set_option; a multiple of 16 in 16..4096, read per call, 0 / unset: the launches above
+ * exactly): the entropy stage gives a segment one lane per S raw bytes instead of one lane (k_jpegdec_split).  S is
+ * doubled for a segment until at most 2048 subsequences cover it; a segment shorter than two subsequences keeps its one lane.  The
+ * split lanes' result is accepted only where it is provably the one lane's; every other segment is decoded by the one-lane function
+ * in the same call (k_jpegdec_rest), so status words and bytes are those of the call without the option, always.
+ * yolo2_hip_jpeg_last_info's entropy figure is then the sum over the stage's launches.
+ * The doorway: yolo2_hip_decode_jpeg_ref with the entropy stage run that way on the host, lanes and rounds as loops, no GPU call;
+ * info8 as out8[0..5] below. */
+int yolo2_hip_decode_jpeg_split_ref(const uint8_t *stream, size_t size, int split_bytes, uint8_t *rgb_out, size_t cap, int *width,
+                                    int *height, int *status, double *info8);
+/* Of the last JPEG call on ctx (all zero when the option was unset): out8[0] subsequences, [1] segments split-decoded, [2] segments
+ * that fell back to the one-lane function, [3] segments too short to split, [4] most synchronisation rounds of any segment, [5] S,
+ * [6] / [7] device-event milliseconds per chunk of k_jpegdec_split and of k_jpegdec_rest (under yolo2_hip_set_profiling). */
+int yolo2_hip_jpeg_split_info(yolo2_hip_ctx *ctx, double *out8);
 
 /* ------------------------------------------------------- multi-GPU: frame sharding, one weight broadcast
  *

@@ -3,14 +3,17 @@
 the GPU, in one process (GPU box):
   (a) y2h_decode_image on 16 threads (the CPU share of a job on the GPU machines), then yolo2_hip_run_images_pix_dets_f16 (fp16) or
       yolo2_hip_run_images_pix_dets (int16) on the decoded RGB24 frames;
-  (b) yolo2_hip_run_images_jpeg_dets on the same streams.
+  (b) yolo2_hip_run_images_jpeg_dets on the same streams;
+  (c) route (b) under option jpegdec_split = S (many lanes per restart interval: k_jpegdec_split + k_jpegdec_rest), S in 64, 128, 256, 512.
 Streams: dog.jpg as it is (768x576, h1v2, DRI 96: 36 restart intervals, so 36 lanes of k_jpegdec_entropy per frame), and the same
 picture written by y2h_write_jpg_rgb24 at quality 80 (4:4:4, no DRI: one lane per frame).  Batches 64 and 256.  Every figure: one
 warm-up call of the shape, then `reps` windows that end in a device synchronise; the two routes alternate inside a repeat and every
 repeat is printed.  Also: device-event time of the decoder's kernels per chunk, staged / uploaded bytes per frame of both routes, and
 the decode-only rate of yolo2_hip_decode_jpeg_host against the host pool.  The bar (DRI stream, batch 256): the median of (b) is not
-below the median of (a) by more than the spread of (a)'s own repeats.  Writes profiles/r15_jpeg_decode_rates.txt.
-usage: python3 tools/jpeg_decode_report.py [chunks per call = 4] [reps = 3] [out = profiles/r15_jpeg_decode_rates.txt]"""
+below the median of (a) by more than the spread of (a)'s own repeats; the same bar for the best (c) on the stream without DRI at batch
+256, against the (a) and (b) of the same run.  Per S also the event time of the two launches per chunk and the rounds.  Writes
+profiles/r17_jpeg_split_rates.txt (profiles/r15_jpeg_decode_rates.txt is this tool's output before route (c) existed).
+usage: python3 tools/jpeg_decode_report.py [chunks per call = 4] [reps = 3] [out = profiles/r17_jpeg_split_rates.txt]"""
 import ctypes as C
 import os
 import statistics
@@ -26,14 +29,15 @@ from yolo2_amd import hipdrv, synth
 
 CHUNKS = int(sys.argv[1]) if len(sys.argv) > 1 else 4
 REPS = int(sys.argv[2]) if len(sys.argv) > 2 else 3
-out_path = sys.argv[3] if len(sys.argv) > 3 else os.path.join(ROOT, "profiles", "r15_jpeg_decode_rates.txt")
+out_path = sys.argv[3] if len(sys.argv) > 3 else os.path.join(ROOT, "profiles", "r17_jpeg_split_rates.txt")
 THREADS = 16
+SPLITS = (64, 128, 256, 512)
 
 H = hipdrv.host_lib()
 H.y2h_decode_image.restype = C.c_long
 H.y2h_decode_image.argtypes = [C.c_char_p, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long]
 L = hipdrv.lib()
-lines = [f"JPEG streams -> records: host decode pool ({THREADS} threads) + _pix_dets entry (a) beside yolo2_hip_run_images_jpeg_dets (b), one process; "
+lines = [f"JPEG streams -> records: host decode pool ({THREADS} threads) + _pix_dets entry (a) beside yolo2_hip_run_images_jpeg_dets (b) and the same under option jpegdec_split = S (c), one process; "
          f"{CHUNKS} chunks per call, {REPS} repeats after one warm-up call per shape, windows end in a device synchronise", ""]
 
 
@@ -70,6 +74,7 @@ pool = ThreadPoolExecutor(THREADS)
 vp = lambda a: a.ctypes.data_as(C.c_void_p)
 CAP = 100
 verdict = None
+split_verdict = None
 
 for B in (64, 256):
     n = CHUNKS * B
@@ -106,18 +111,42 @@ for B in (64, 256):
                 hipdrv.check(L.yolo2_hip_run_images_jpeg_dets(ctx._h, code, sptrs, sizes, vp(jw), vp(jh), n, B, 0.25, 0.45, 1, vp(dets), CAP, vp(counts),
                                                               C.byref(q), vp(status)), "route (b)")
 
+            def route_c(S):
+                ctx.set_option("jpegdec_split", S)
+                try:
+                    route_b()
+                finally:
+                    ctx.set_option("jpegdec_split", None)
+
             route_a()
             want = counts.copy()
             route_b()
             assert np.array_equal(counts, want) and not status.any()           # the two routes return the same records
+            for S in SPLITS:
+                route_c(S)
+                assert np.array_equal(counts, want) and not status.any()       # ... and so does every (c)
             t = {"a": [], "b": []}
+            t.update({S: [] for S in SPLITS})
             for _ in range(REPS):
                 t["a"].append(window(route_a))
                 t["b"].append(window(route_b))
+                for S in SPLITS:
+                    t[S].append(window(lambda: route_c(S)))
             ra, rb = [n / x for x in t["a"]], [n / x for x in t["b"]]
             ma, mb = statistics.median(ra), statistics.median(rb)
             say(f"  {prec}: (a) host pool + pix entry: median {ma:.0f} frames/s (repeats {', '.join(f'{r:.0f}' for r in ra)}); "
                 f"(b) GPU decoder: median {mb:.0f} frames/s (repeats {', '.join(f'{r:.0f}' for r in rb)}); (b) / (a) = {mb / ma:.2f}")
+            rc_ = {S: [n / x for x in t[S]] for S in SPLITS}
+            mc = {S: statistics.median(rc_[S]) for S in SPLITS}
+            for S in SPLITS:
+                say(f"    (c) S = {S}: median {mc[S]:.0f} frames/s (repeats {', '.join(f'{r:.0f}' for r in rc_[S])}); (c) / (b) = {mc[S] / mb:.2f}, "
+                    f"(c) / (a) = {mc[S] / ma:.2f}")
+            if B == 256 and "no DRI" in sname:
+                best = max(SPLITS, key=lambda S: mc[S])
+                spread = max(ra) - min(ra)
+                ok = mc[best] >= ma - spread
+                split_verdict = (split_verdict or []) + [f"{prec}: best (c) S = {best}: {mc[best]:.0f} against (a) {ma:.0f} - spread {spread:.0f} frames/s, "
+                                                         f"(b) {mb:.0f}: {'met' if ok else 'NOT met'}"]
             if B == 256 and "DRI 96" in sname:
                 spread = max(ra) - min(ra)
                 ok = mb >= ma - spread
@@ -134,6 +163,17 @@ for B in (64, 256):
             f"sum {dec_ms:.3f} ms = {B / (dec_ms * 1e-3):.0f} frames/s if nothing else ran")
         say(f"  bytes per frame: (a) staged and uploaded {W * Hh * 3} (raw RGB24); (b) staged and uploaded {i['stream_bytes_h2d'] / n:.0f} "
             f"(streams, descriptors, tables) + {i['frame_bytes_h2d'] / n:.0f} (letterbox table) = {(i['stream_bytes_h2d'] + i['frame_bytes_h2d']) / n / (W * Hh * 3):.3f} of (a)")
+        for S in SPLITS:
+            ctx.set_option("jpegdec_split", S)
+            ctx.set_profiling(True)
+            hipdrv.check(L.yolo2_hip_run_images_jpeg_dets(ctx._h, 1, sptrs, sizes, vp(jw), vp(jh), n, B, 0.25, 0.45, 1, vp(dets), CAP, vp(counts), C.byref(q),
+                                                          vp(status)), "profiled split call")
+            ctx.set_profiling(False)
+            ctx.set_option("jpegdec_split", None)
+            i, k = hipdrv.jpeg_last_info(ctx._h), hipdrv.jpeg_split_info(ctx._h)
+            say(f"  jpegdec_split = {S}, per chunk of {B}: k_jpegdec_split {k['split_ms']:.3f} ms + k_jpegdec_rest {k['fallback_ms']:.3f} ms (entropy stage "
+                f"{i['entropy_ms']:.3f} ms); per call {k['subsequences']} subsequences, {k['split_segments']} segments split, {k['fallback_segments']} fell back, "
+                f"{k['short_segments']} too short, most rounds of a segment {k['max_rounds']}")
         # decode only
         outs = (C.c_void_p * n)(*[frames[k].ctypes.data for k in range(n)])
         caps = (C.c_size_t * n)(*([W * Hh * 3] * n))
@@ -151,6 +191,9 @@ for B in (64, 256):
 
 say("bar (DRI stream at batch 256: median of (b) not below the median of (a) by more than the spread of (a)'s repeats):")
 for v in verdict or ["not measured"]:
+    say("  " + v)
+say("the same bar for route (c) on the stream without DRI at batch 256 (best S; (a) and (b) of the same repeats):")
+for v in split_verdict or ["not measured"]:
     say("  " + v)
 text = "\n".join(lines) + "\n"
 os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)

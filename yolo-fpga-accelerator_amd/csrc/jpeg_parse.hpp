@@ -1,7 +1,8 @@
 // jpeg_parse.hpp -- the host's side of the GPU JPEG decoder, plain C++ (no HIP): the probe (which streams the GPU decoder takes, with a
 // reason for the others, and where a stream ends), the per-frame descriptor the kernels read (geometry, tables, segment table), and
 // decode_ref: jpeg_scan.hpp's stages run one after the other on the host - the body of yolo2_hip_decode_jpeg_ref, which the CPU tests
-// and tools/fuzz_jpegdec.cpp compare with host/y2_codec.cpp.
+// and tools/fuzz_jpegdec.cpp compare with host/y2_codec.cpp.  With a subsequence size it runs the entropy stage as option jpegdec_split
+// does (split_plan, split_segment_host): the body of yolo2_hip_decode_jpeg_split_ref.
 //
 // The header checks restate Jpeg::segment / frame_header / scan_header of y2_codec.cpp and are never weaker: a stream that decoder
 // throws on is refused here (kDamaged), and so is what it tolerates but this walk does not (bytes between segments, a header that runs
@@ -318,10 +319,93 @@ inline int parse(const uint8_t *d, size_t n, Info &info, Parsed *out)
     return kAccepted;
 }
 
+// How option jpegdec_split = `split` bytes cuts one segment: data_end (the first FF of the marker that ends it), the subsequence in
+// raw bytes (`split`, doubled until at most kSplitMaxSub of them cover the data) and their number.  n_sub < 2: the segment takes
+// decode_segment's one lane (too short, or it does not end in a marker).
+struct SplitPlan {
+    uint32_t data_end;
+    int sub, n_sub;
+};
+inline SplitPlan split_plan(const uint8_t *base, const Segment &s, int split)
+{
+    SplitPlan p = {s.begin, split, 0};
+    if (split <= 0 || s.end < s.begin + 2 || base[s.end - 1] == 0 || base[s.end - 1] == 0xff || base[s.end - 2] != 0xff) return p;
+    uint32_t e = s.end - 2;
+    while (e > s.begin && base[e - 1] == 0xff) --e;
+    p.data_end = e;
+    const uint32_t len = e - s.begin;
+    while (((uint64_t)len + (uint32_t)p.sub - 1) / (uint32_t)p.sub > (uint64_t)kSplitMaxSub) p.sub *= 2;
+    p.n_sub = (int)((len + (uint32_t)p.sub - 1) / (uint32_t)p.sub);
+    return p;
+}
+
+// One segment by many lanes, the lanes and rounds as loops (what k_jpegdec_split does with a workgroup): speculate, synchronise, scan,
+// accept, write.  true: accepted, coefficients written (the segment's status is 0).  false: nothing written; decode_segment decides.
+inline bool split_segment_host(const Frame &f, const Tables &t, const uint8_t *base, const Segment &s, const SplitPlan &sp, int16_t *coef, int *rounds)
+{
+    int bpm = 0;
+    const uint32_t smap = split_slot_map(f, bpm), n_blocks = (uint32_t)s.n_mcu * (uint32_t)bpm;
+    const int ns = sp.n_sub, turns = 8 * sp.sub + 16;
+    auto sub_end = [&](int j) { const uint64_t e = (uint64_t)s.begin + (uint64_t)(j + 1) * (uint32_t)sp.sub; return e < sp.data_end ? (uint32_t)e : sp.data_end; };
+    std::vector<SplitRec> rec((size_t)ns), cur((size_t)ns);
+    std::vector<char> done((size_t)ns, 0);
+    SplitWrite none = {};
+    for (int i = 0; i < ns; ++i) {      // 1. speculate
+        split_run<false>(f, t, base, sp.data_end, sub_end(i), smap, bpm, turns, s.begin + (uint32_t)i * (uint32_t)sp.sub, 0u, rec[(size_t)i], none);
+        cur[(size_t)i] = rec[(size_t)i];
+        done[(size_t)i] = (rec[(size_t)i].meta & kSplitStopped) != 0;
+    }
+    *rounds = 0;
+    for (int r = 0; r < ns - 1; ++r) {  // 2. synchronise (lane i touches record i + r + 1 only: the order of the lanes does not matter)
+        bool any = false;
+        for (int i = 0; i + r + 1 < ns; ++i) {
+            if (done[(size_t)i]) continue;
+            const int j = i + r + 1;
+            SplitRec out;
+            split_run<false>(f, t, base, sp.data_end, sub_end(j), smap, bpm, turns, cur[(size_t)i].off, cur[(size_t)i].meta & kSplitStateMask, out, none);
+            *rounds = r + 1;
+            if (split_same(out, rec[(size_t)j])) { done[(size_t)i] = 1; continue; }
+            rec[(size_t)j] = cur[(size_t)i] = out;
+            if (out.meta & kSplitStopped) done[(size_t)i] = 1;
+            else any = true;
+        }
+        if (!any) break;
+    }
+    // 3. scan, 4. accept
+    std::vector<SplitRec> before((size_t)ns);
+    SplitRec run = {};
+    bool closes = false, overshoots = false;
+    for (int i = 0; i < ns; ++i) {
+        before[(size_t)i] = run;
+        const bool stopped_before = (run.meta & kSplitStopped) != 0;
+        closes |= split_closes(run.nblk, stopped_before, rec[(size_t)i], n_blocks);
+        overshoots |= split_overshoots(run.nblk, stopped_before, rec[(size_t)i], n_blocks);
+        run.nblk += rec[(size_t)i].nblk;
+        for (int k = 0; k < 3; ++k) run.dc[k] = (int32_t)((uint32_t)run.dc[k] + (uint32_t)rec[(size_t)i].dc[k]);
+        run.meta |= rec[(size_t)i].meta & kSplitStopped;
+    }
+    if (!closes || overshoots) return false;
+    for (int i = 0; i < ns; ++i) {      // 5. write
+        const SplitRec &b = before[(size_t)i];
+        if ((b.meta & kSplitStopped) || b.nblk >= n_blocks) break;
+        SplitWrite w = {(int)b.nblk, (int)n_blocks, s.first_mcu, {b.dc[0], b.dc[1], b.dc[2]}, coef};
+        SplitRec out;
+        split_run<true>(f, t, base, sp.data_end, sub_end(i), smap, bpm, turns, i ? rec[(size_t)i - 1].off : s.begin,
+                        i ? rec[(size_t)i - 1].meta & kSplitStateMask : 0u, out, w);
+    }
+    return true;
+}
+
 // The stages one after the other on the host, one frame: status as the kernels would leave it, RGB24 where it is 0.
 // Returns the probe's reason (0: accepted, rgb / status filled; the picture is w * h * 3 bytes, cap must hold it: -1 otherwise).
-inline int decode_ref(const uint8_t *d, size_t n, uint8_t *rgb, size_t cap, int *width, int *height, int *status)
+// split > 0: the entropy stage as option jpegdec_split runs it (yolo2_hip_decode_jpeg_split_ref); info8 = subsequences, segments
+// split-decoded, fallen back, too short, most rounds of a segment, split, 0, 0.
+inline int decode_ref(const uint8_t *d, size_t n, uint8_t *rgb, size_t cap, int *width, int *height, int *status, int split = 0, double *info8 = nullptr)
 {
+    if (info8) {
+        for (int i = 0; i < 8; ++i) info8[i] = 0;
+        info8[5] = split;
+    }
     Info info;
     std::vector<Parsed> ps(1);
     Parsed &P = ps[0];
@@ -333,7 +417,20 @@ inline int decode_ref(const uint8_t *d, size_t n, uint8_t *rgb, size_t cap, int 
     int st = P.status;
     std::vector<int16_t> coef(P.f.samples, 0);
     std::vector<uint8_t> planes(P.f.samples, 0);
-    for (size_t i = 0; i < P.segs.size() && st == kOk; ++i) st = decode_segment(P.f, P.t, d, P.segs[i], coef.data());
+    for (size_t i = 0; i < P.segs.size() && st == kOk; ++i) {
+        if (split > 0) {
+            const SplitPlan sp = split_plan(d, P.segs[i], split);
+            int rounds = 0;
+            const bool took = sp.n_sub >= 2 && split_segment_host(P.f, P.t, d, P.segs[i], sp, coef.data(), &rounds);
+            if (info8) {
+                if (sp.n_sub >= 2) info8[0] += sp.n_sub;
+                info8[sp.n_sub < 2 ? 3 : (took ? 1 : 2)] += 1;
+                if (rounds > info8[4]) info8[4] = rounds;
+            }
+            if (took) continue;
+        }
+        st = decode_segment(P.f, P.t, d, P.segs[i], coef.data());
+    }
     if (status) *status = st;
     if (st) return kAccepted;
     for (int k = 0; k < P.f.ncomp; ++k) {

@@ -3,6 +3,9 @@
 // DCT, and the up-sampling + colour formulas as a function of the output pixel.  They restate host/y2_codec.cpp (Bits, block_sequential,
 // interval_done, idct_block, row_*, ycc_to_rgb), which is the expected side of every test and stays as it is.  Users: the kernels
 // (kernels_jpegdec.hpp), the host doorway yolo2_hip_decode_jpeg_ref (jpeg_parse.hpp: y2jpg::decode_ref) and tools/fuzz_jpegdec.cpp.
+// Behind decode_segment: one segment decoded by many lanes (option jpegdec_split) - a reader whose positions are canonical (SBits), one
+// subsequence from a given state (split_run) and the acceptance rule; users k_jpegdec_split, yolo2_hip_decode_jpeg_split_ref
+// (jpeg_parse.hpp: split_segment_host) and tools/fuzz_jpegdec_split.cpp.
 // Plain C++ for a host compiler, __host__ __device__ under hipcc.  Integer arithmetic wraps as the host's does (-fwrapv on both sides).
 //
 // What differs from the host's walk, and why the bytes are the same:
@@ -224,6 +227,252 @@ Y2J_HD inline int decode_segment(const Frame &f, const Tables &t, const uint8_t 
     if (br.n < 24) br.fill();
     if (s.last ? br.marker < 0 : (br.marker < 0xd0 || br.marker > 0xd7)) return kRestartOutOfStep;
     return kOk;
+}
+
+// ---------------------------------------------------------------------------- one segment, many lanes
+// A segment's bytes [begin, data_end) - data_end: the first FF of the marker that ends it - are cut into subsequences of `sub` RAW
+// bytes; lane i decodes the symbols that START inside subsequence i.  Huffman streams re-synchronise, so a lane started at a boundary
+// soon walks the true symbol boundaries; rounds of "decode the next subsequence from my own exit state, stop when the record there is
+// what I computed" spread the true state of lane 0 over the segment (split_segment_host below is the whole algorithm as loops; the
+// kernel k_jpegdec_split is the same calls with a workgroup's lanes and barriers for the loops).
+//
+// POSITIONS.  A decoder's place is (off, bit): the raw offset of the first byte of the UNIT that holds the next unread bit, and the bit
+// inside it.  A unit is one data byte: a byte that is not FF, or FF.. 00 (a stuffed FF, fill bytes included).  Two decoders that
+// reach one bit by different routes report one place, whatever they prefetched: SBits keeps, beside `acc`, the raw length of each of
+// the (at most four) units it holds, and its place is `p` minus the lengths of the units not yet used up.  The stream is read in
+// place and stays intact.  Price: a register, and a handful of integer operations per symbol for where().
+constexpr int kSplitMin = 16, kSplitMax = 4096;   // option jpegdec_split: multiples of 16 in this range
+constexpr int kSplitMaxSub = 2048;                // subsequences of one segment (and of one workgroup): the subsequence is doubled until they fit
+
+struct SBits {
+    const uint8_t *base;
+    uint32_t p, lim;       // next raw byte to fetch; data_end
+    uint32_t acc, lens;    // lens: raw length of the last four units fetched, the newest in the low byte (0: a zero byte behind the data)
+    int n;
+    bool lost;             // a unit longer than 255 bytes, or an FF run that does not end in 00: the lane stops
+#if defined(__HIP_DEVICE_COMPILE__)
+    uint4 piece;
+    uint32_t piece_at;
+    __device__ void shift8()
+    {
+        piece.x = (piece.x >> 8) | (piece.y << 24); piece.y = (piece.y >> 8) | (piece.z << 24);
+        piece.z = (piece.z >> 8) | (piece.w << 24); piece.w >>= 8;
+    }
+#endif
+    Y2J_HD uint32_t next()   // as Bits::next
+    {
+#if defined(__HIP_DEVICE_COMPILE__)
+        const uint32_t at = p & ~15u;
+        if (at != piece_at) {
+            piece = *reinterpret_cast<const uint4 *>(base + at);
+            piece_at = at;
+            for (uint32_t k = p & 15u; k; --k) shift8();
+        }
+        const uint32_t b = piece.x & 255u;
+        shift8();
+        ++p;
+        return b;
+#else
+        return base[p++];
+#endif
+    }
+    Y2J_HD void fill()
+    {
+        while (n <= 24) {
+            uint32_t b = 0, len = 0;
+            if (p < lim) {
+                b = next();
+                len = 1;
+                if (b == 0xff) {
+                    uint32_t c = 0xff;
+                    while (c == 0xff && p < lim) { c = next(); ++len; }      // (bounded by lim)
+                    if (c != 0 || len > 255) { lost = true; len = 255; }
+                }
+            }
+            acc |= b << (24 - n);
+            n += 8;
+            lens = (lens << 8) | len;
+        }
+    }
+    Y2J_HD void drop(int k) { acc <<= k; n -= k; }
+    Y2J_HD void open(const uint8_t *b, uint32_t off, int bit, uint32_t data_end)
+    {
+        base = b; p = off; lim = data_end; acc = 0; lens = 0; n = 0; lost = false;
+#if defined(__HIP_DEVICE_COMPILE__)
+        piece_at = 0xffffffffu;
+        piece = make_uint4(0, 0, 0, 0);
+#endif
+        if (bit) { fill(); drop(bit); }
+    }
+    // the place of the next unread bit, and the raw length of the unit that holds it (bit != 0 only)
+    Y2J_HD void where(uint32_t &off, int &bit, uint32_t &ulen) const
+    {
+        const int u = (n + 7) >> 3;
+        uint32_t l = lens, sum = 0, last = 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+        for (int i = 0; i < 4; ++i) {
+            if (i < u) { last = l & 255u; sum += last; }
+            l >>= 8;
+        }
+        off = p - sum; bit = (8 - (n & 7)) & 7; ulen = last;
+    }
+    Y2J_HD int get(int k)
+    {
+        if (k == 0) return 0;
+        if (n < k) fill();
+        const int v = (int)(acc >> (32 - k));
+        drop(k);
+        return v;
+    }
+    Y2J_HD int symbol(const Huff &h)     // Bits::symbol
+    {
+        if (n < 16) fill();
+        const uint32_t e = h.look[acc >> 23];
+        if (e) { drop((int)(e >> 8)); return (int)(e & 255u); }
+        int code = (int)(acc >> 22), len = 10;
+        for (; len <= 16; ++len, code = (int)(acc >> (32 - len)))
+            if (h.maxcode[len] >= 0 && code <= h.maxcode[len] && code >= h.mincode[len]) break;
+        if (len > 16) return -1;
+        drop(len);
+        return h.vals[(h.valptr[len] + code - h.mincode[len]) & 255];
+    }
+    Y2J_HD int extend(int k)
+    {
+        if (k == 0) return 0;
+        const int v = get(k);
+        return v < (1 << (k - 1)) ? v - (1 << k) + 1 : v;
+    }
+};
+
+// What a lane leaves for one subsequence: its exit state - place, slot (the block's index within the MCU) and k (the zigzag index
+// expected next, 0: a DC symbol) - and what it decoded on the way: blocks completed, the sum of DC differences per component
+// (wrapping, as block_sequential's dc_pred += does), and whether the place behind the LAST block it completed is where a complete
+// segment ends.  The whole record is a function of the entry state, and the rounds compare whole records.
+struct SplitRec {
+    uint32_t off;
+    uint32_t meta;      // bit 0..2 | slot << 3 | k << 6 | kSplitStopped | kSplitCloseOk
+    uint32_t nblk;
+    int32_t dc[3];
+};
+constexpr uint32_t kSplitStopped = 1u << 12, kSplitCloseOk = 1u << 13, kSplitStateMask = 0xfffu | kSplitStopped;
+Y2J_HD inline bool split_same(const SplitRec &a, const SplitRec &b)
+{
+    return a.off == b.off && a.meta == b.meta && a.nblk == b.nblk && a.dc[0] == b.dc[0] && a.dc[1] == b.dc[1] && a.dc[2] == b.dc[2];
+}
+// slot -> component | x << 2 | y << 3, four bits a slot (at most 6 slots: luma 2x2 and two chroma blocks); the blocks of an MCU
+Y2J_HD inline uint32_t split_slot_map(const Frame &f, int &bpm)
+{
+    uint32_t m = 0;
+    int s = 0;
+    for (int k = 0; k < 3; ++k) {
+        if (k >= f.ncomp) break;
+        const int ci = f.order[k];
+        for (int y = 0; y < f.comp[ci].v; ++y)
+            for (int x = 0; x < f.comp[ci].h; ++x, ++s) m |= (uint32_t)(ci | (x << 2) | (y << 3)) << (4 * s);
+    }
+    bpm = s;
+    return m;
+}
+
+// What the writing pass knows on entry beside the state: the ordinal of the block it is in, the DC predictions, and where blocks go.
+struct SplitWrite {
+    int ordinal, n_blocks, first_mcu;
+    int pred[3];
+    int16_t *coef;      // the frame's
+};
+
+// The symbols that start in [state's place, sub_end) from the state in (in.off, in.meta); `turns` = 8 * subsequence bytes + 16 bounds
+// the loop.  A bad code, k > 63 or a lost reader STOPS the lane (kSplitStopped): on a speculative lane that is no error, the lane
+// below overwrites the record; on the true chain it sends the segment to decode_segment unless the geometry's blocks were complete.
+// kWrite: the same walk from a verified state, storing what block_sequential stores, for blocks below w.n_blocks only.
+template <bool kWrite>
+Y2J_HD inline void split_run(const Frame &f, const Tables &t, const uint8_t *base, uint32_t data_end, uint32_t sub_end, uint32_t smap, int bpm,
+                             int turns, uint32_t in_off, uint32_t in_meta, SplitRec &out, SplitWrite &w)
+{
+    SBits br;
+    br.open(base, in_off, (int)(in_meta & 7u), data_end);
+    int slot = (int)((in_meta >> 3) & 7u), k = (int)((in_meta >> 6) & 63u);
+    uint32_t nblk = 0, close_ok = 0, off = in_off, ulen = 0;
+    int bit = 0, d0 = 0, d1 = 0, d2 = 0, p0 = 0, p1 = 0, p2 = 0, mx = 0, my = 0;
+    int16_t *d = nullptr;
+    bool stopped = false;
+    auto block_at = [&]() {
+        const uint32_t e = smap >> (4 * slot);
+        const Comp &c = f.comp[e & 3u];
+        const int bx = mx * c.h + (int)((e >> 2) & 1u), by = my * c.v + (int)((e >> 3) & 1u);
+        d = w.coef + c.off + ((size_t)by * (size_t)(c.w2 >> 3) + (size_t)bx) * 64;
+    };
+    if (kWrite) {
+        p0 = w.pred[0]; p1 = w.pred[1]; p2 = w.pred[2];
+        const int mcu = w.first_mcu + w.ordinal / bpm;
+        mx = mcu % f.mcu_x; my = mcu / f.mcu_x;
+        block_at();
+    }
+    int turn = 0;
+    for (; turn < turns; ++turn) {
+        br.where(off, bit, ulen);
+        if (off >= sub_end) break;
+        if (kWrite && w.ordinal >= w.n_blocks) break;
+        if (br.lost) { stopped = true; break; }
+        const int ci = (int)((smap >> (4 * slot)) & 3u);
+        if (k == 0) {
+            const int s = br.symbol(t.dc[ci]);
+            if (s < 0 || s > 16) { stopped = true; break; }
+            const int diff = br.extend(s);
+            if (ci == 0) d0 += diff; else if (ci == 1) d1 += diff; else d2 += diff;
+            if (kWrite) {
+                int pred;
+                if (ci == 0) pred = (p0 += diff); else if (ci == 1) pred = (p1 += diff); else pred = (p2 += diff);
+                d[0] = (int16_t)(pred * t.q[ci][0]);
+            }
+            k = 1;
+        } else {
+            const int rs = br.symbol(t.ac[ci]);
+            if (rs < 0) { stopped = true; break; }
+            const int r = rs >> 4, s = rs & 15;
+            if (s == 0) {
+                k = rs == 0xf0 ? k + 16 : 64;
+            } else {
+                k += r;
+                if (k > 63) { stopped = true; break; }
+                const int z = zigzag(k++);
+                const int v = br.extend(s);
+                if (kWrite) d[z] = (int16_t)(v * t.q[ci][z]);
+            }
+        }
+        if (k >= 64) {
+            k = 0;
+            ++nblk;
+            if (++slot == bpm) {
+                slot = 0;
+                if (kWrite && ++mx == f.mcu_x) { mx = 0; ++my; }
+            }
+            br.where(off, bit, ulen);
+            close_ok = (bit ? off + ulen : off) == data_end ? kSplitCloseOk : 0u;
+            if (kWrite) { ++w.ordinal; block_at(); }
+        }
+    }
+    if (turn == turns || br.lost) stopped = true;
+    out.nblk = nblk; out.dc[0] = d0; out.dc[1] = d1; out.dc[2] = d2;
+    if (stopped) { out.off = 0xffffffffu; out.meta = kSplitStopped | close_ok; }
+    else { out.off = off; out.meta = (uint32_t)bit | ((uint32_t)slot << 3) | ((uint32_t)k << 6) | close_ok; }
+}
+
+// How one lane reads the scanned records: `before` = the exclusive prefix over the segment's subsequences in front of it (blocks, DC
+// sums, and whether any of them stopped), `own` = its record.  n_blocks = n_mcu x blocks of an MCU.  The segment is ACCEPTED when
+// some lane closes it and no lane overshoots; everything else is decode_segment's.
+//   closes:     on the true chain, the geometry's last block is completed here, and behind it less than one unit of data is left in
+//               front of the marker - where decode_segment's closing rule finds the marker whatever its reader had prefetched;
+//   overshoots: on the true chain and its blocks go past the geometry's (pad bits that decode into blocks, or damage).
+Y2J_HD inline bool split_closes(uint32_t before_nblk, bool before_stopped, const SplitRec &own, uint32_t n_blocks)
+{
+    return !before_stopped && before_nblk < n_blocks && before_nblk + own.nblk == n_blocks && (own.meta & kSplitCloseOk);
+}
+Y2J_HD inline bool split_overshoots(uint32_t before_nblk, bool before_stopped, const SplitRec &own, uint32_t n_blocks)
+{
+    return !before_stopped && before_nblk + own.nblk > n_blocks;
 }
 
 Y2J_HD constexpr int fx12(float x) { return (int)(x * 4096 + 0.5); }

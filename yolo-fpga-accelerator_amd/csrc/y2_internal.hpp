@@ -78,6 +78,8 @@ struct Y2Options {
          f16_no_fuse1x1 = false, f16_no_rw = false, f16_no_rwb = false, f16_no_rwc = false, f16_ring256 = false, f16_ring_sq = false;
     bool i8_no_front = false;     // the int8 images entries letterbox into float frames and run the frames route (the reference route of
                                   // k_i8_front_pix's tests and report, as f16_no_mfma0 is for the fp16 entries)
+    int jpegdec_split = 0;        // the GPU JPEG decoder's entropy stage with many lanes per segment: subsequence bytes, a multiple of 16 in
+                                  // 16..4096 (0: one lane per segment, today's launches); read per call
     int stamp_layer = -1;
     int f16_skip = 0;             // DIAGNOSTIC (results wrong by construction): bit mask of fp16 launches left out of the table, to measure
                                   // what a launch costs INSIDE the two-lane step: 1 = 1x1 layers 5 and 9, 2 = layer 0, 4 = layers 2/4/6,
@@ -311,6 +313,7 @@ struct yolo2_hip_ctx {
     Y2LoopBufs loop;
     yolo2_hip_loop_info_t loop_info = {};   // of the last loop call (yolo2_hip_loop_last_info)
     double jpeg_dec_info[8] = {};           // of the last JPEG call (yolo2_hip_jpeg_last_info)
+    double jpeg_split_info[8] = {};         // of the last JPEG call (yolo2_hip_jpeg_split_info): all zero without option jpegdec_split
     int device = 0;
     Y2Options opt;                     // parsed once at creation (environment), changed only by yolo2_hip_set_option; lanes copy it
     std::shared_ptr<Y2PlanCache> plan_cache;   // weight-side cache bound by yolo2_hip_set_plan_cache (lanes share the parent's)

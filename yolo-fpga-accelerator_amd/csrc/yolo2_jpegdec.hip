@@ -7,7 +7,8 @@
 //           sets once - and the streams, each on a 16-byte boundary); hin[b] = the LetterboxItem table and the caller's raw frames at
 //           their slots, exactly the staging layout of run_images_regf
 //   s_in    blob -> djpg[b] (the one upload of the compressed route); table and raw frames -> dbytes[b]
-//   s_run   memset of the coefficients, k_jpegdec_entropy, _idct, _rgb (into the frames' slots of dbytes[b]), _zero; then the
+//   s_run   memset of the coefficients, k_jpegdec_entropy (under option jpegdec_split: k_jpegdec_split, then k_jpegdec_rest - their
+//           tables SplitSeg[] / SplitWg[] lie in the blob in front of the streams, a word per segment behind the status words), _idct, _rgb (into the frames' slots of dbytes[b]), _zero; then the
 //           network of the precision by the code its _pix_dets entry runs it with, reading dbytes[b] as if the host had filled it
 //   s_out   tail + D2H of records, counts and status words (records entry), or D2H of the slots and status words (decode entry)
 // Buffer set b is refilled for chunk k + 2 after drain(k) has waited for e_out[b]; the coefficient and plane buffers exist once and
@@ -59,6 +60,25 @@ extern "C" int yolo2_hip_decode_jpeg_ref(const uint8_t *stream, size_t size, uin
     return YOLO2_SUCCESS;
 }
 
+extern "C" int yolo2_hip_decode_jpeg_split_ref(const uint8_t *stream, size_t size, int split_bytes, uint8_t *rgb_out, size_t cap, int *width, int *height,
+                                               int *status, double *info8)
+{
+    if (!stream || !rgb_out || !status || !info8) return fail(YOLO2_ERROR, "null argument");
+    if (split_bytes < kSplitMin || split_bytes > kSplitMax || split_bytes % 16)
+        return fail(YOLO2_ERROR, "split_bytes %d: a multiple of 16 in %d..%d", split_bytes, kSplitMin, kSplitMax);
+    int w = 0, h = 0;
+    *status = 0;
+    const int why = decode_ref(stream, size, rgb_out, cap, &w, &h, status, split_bytes, info8);
+    if (width) *width = w;
+    if (height) *height = h;
+    if (why > 0) {
+        *status = 100 + why;
+        return fail(YOLO2_ERROR, "not GPU-decodable: %s", yolo2_hip_jpeg_reason_name(why));
+    }
+    if (why < 0) return fail(YOLO2_ERROR, "output buffer too small (%zu < %zu bytes)", cap, (size_t)w * h * 3);
+    return YOLO2_SUCCESS;
+}
+
 namespace {
 
 int jpeg_ensure(PipeBufs &P, size_t blob, size_t samples, size_t status_words)
@@ -90,7 +110,8 @@ int jpeg_ensure(PipeBufs &P, size_t blob, size_t samples, size_t status_words)
 
 struct ChunkLayout {
     uint32_t segs_off, wg_off, status_off, tables_off, streams_off;
-    int n_seg, n_wg;
+    uint32_t sseg_off, swg_off;    // option jpegdec_split: SplitSeg[], SplitWg[]; the segments' words follow the status words
+    int n_seg, n_wg, n_swg;
 };
 
 // dets == nullptr: the decode entry (rgb_out / caps); otherwise the records entry
@@ -104,6 +125,7 @@ int run_jpeg(yolo2_hip_ctx *c, int precision, const uint8_t *const *streams, con
         return fail(YOLO2_ERROR, "bad image count %d / batch %d (1..1024) / capacity %d", n, batch, want_dets ? cap : 1);
     if (want_dets && thresh < 0.f) return fail(YOLO2_ERROR, "negative threshold");
     const bool i16 = precision == YOLO2_LOOP_INT16, i8 = precision == YOLO2_JPEG_INT8;
+    const int split = c->opt.jpegdec_split;      // read per call; 0: today's launches exactly
     if (want_dets && !i16 && !i8 && precision != YOLO2_LOOP_FP16 && precision != YOLO2_LOOP_F32TOL)
         return fail(YOLO2_ERROR, "unknown precision %d (YOLO2_LOOP_INT16, _FP16, _F32TOL or YOLO2_JPEG_INT8)", precision);
     // ---- headers: every refusal before anything is launched
@@ -161,11 +183,13 @@ int run_jpeg(yolo2_hip_ctx *c, int precision, const uint8_t *const *streams, con
             segs += parsed[(size_t)i].segs.size();
         }
         const size_t nf = (size_t)in_chunk(k), wgs = (segs + kEntropyLanes - 1) / kEntropyLanes;
-        const size_t blob = padded(nf * sizeof(Frame)) + padded(segs * sizeof(Segment)) + padded(wgs * sizeof(int)) + padded((nf + segs) * sizeof(int)) +
-                            padded(nf * sizeof(Tables)) + padded(str);
+        // (jpegdec_split: at most one SplitSeg and one SplitWg per segment, and a word per segment behind the status words)
+        const size_t words = nf + segs * (split ? 2 : 1);
+        const size_t blob = padded(nf * sizeof(Frame)) + padded(segs * sizeof(Segment)) + padded(wgs * sizeof(int)) + padded(words * sizeof(int)) +
+                            padded(nf * sizeof(Tables)) + padded(str) + (split ? padded(segs * sizeof(SplitSeg)) + padded(segs * sizeof(SplitWg)) : 0);
         if (blob > (size_t)1 << 31) return fail(YOLO2_ERROR, "chunk %d: more than 2 GiB of streams and tables (use a smaller batch)", k);
         cap_rgb = std::max(cap_rgb, rgb); cap_blob = std::max(cap_blob, blob); cap_samples = std::max(cap_samples, samples);
-        cap_status = std::max(cap_status, nf + segs);
+        cap_status = std::max(cap_status, words);
     }
     if (want_dets && i16 && batch != c->batch) {
         const int rc = yolo2_hip_set_batch(c, batch);
@@ -184,11 +208,22 @@ int run_jpeg(yolo2_hip_ctx *c, int precision, const uint8_t *const *streams, con
     std::vector<ChunkLayout> lay((size_t)2);
     std::vector<std::vector<size_t>> slot(2, std::vector<size_t>((size_t)batch));
     int first_bad = -1;
+    double split_info[8] = {0, 0, 0, 0, 0, (double)split, 0, 0};
     auto drain = [&](int k) {
         const int b = k & 1, nf = in_chunk(k), first = k * batch;
         (void)hipEventSynchronize(P.e_out[b]);
         const int *st = P.hjstatus[b].get();
         int seg = 0;
+        if (split) {
+            int n_seg = 0;
+            for (int f = 0; f < nf; ++f) n_seg += (int)parsed[(size_t)(first + f)].segs.size();
+            for (int j = 0; j < n_seg; ++j) {
+                const unsigned word = (unsigned)st[nf + n_seg + j];
+                if (!word) continue;
+                split_info[(word & 1u) ? 1 : 2] += 1;
+                split_info[4] = std::max(split_info[4], (double)(word >> 2));
+            }
+        }
         for (int f = 0; f < nf; ++f) {
             const Parsed &p = parsed[(size_t)(first + f)];
             int s = st[f];
@@ -217,7 +252,7 @@ int run_jpeg(yolo2_hip_ctx *c, int precision, const uint8_t *const *streams, con
         ~Events() { for (hipEvent_t x : e) (void)hipEventDestroy(x); }
     } prof;
     if (c->prof)
-        for (int i = 0; i < chunks * 5; ++i) {
+        for (int i = 0; i < chunks * (split ? 6 : 5); ++i) {     // (the sixth, behind the first chunks * 5: between k_jpegdec_split and k_jpegdec_rest)
             hipEvent_t e;
             Y2_TRY(hipEventCreate(&e), YOLO2_ERROR);
             prof.e.push_back(e);
@@ -236,12 +271,13 @@ int run_jpeg(yolo2_hip_ctx *c, int precision, const uint8_t *const *streams, con
         L.segs_off = (uint32_t)padded((size_t)nf * sizeof(Frame));
         L.wg_off = L.segs_off + (uint32_t)padded((size_t)n_seg * sizeof(Segment));
         L.status_off = L.wg_off + (uint32_t)padded((size_t)L.n_wg * sizeof(int));
-        L.tables_off = L.status_off + (uint32_t)padded((size_t)(nf + n_seg) * sizeof(int));
+        const size_t words = (size_t)nf + (size_t)n_seg * (split ? 2 : 1);
+        L.tables_off = L.status_off + (uint32_t)padded(words * sizeof(int));
         Frame *frames = reinterpret_cast<Frame *>(blob);
         Segment *segs = reinterpret_cast<Segment *>(blob + L.segs_off);
         int *wg = reinterpret_cast<int *>(blob + L.wg_off), *st = reinterpret_cast<int *>(blob + L.status_off);
         Tables *tables = reinterpret_cast<Tables *>(blob + L.tables_off);
-        memset(st, 0, (size_t)(nf + n_seg) * sizeof(int));
+        memset(st, 0, words * sizeof(int));
         // ---- table sets: identical ones once
         int n_sets = 0;
         std::vector<int> set_of((size_t)nf, 0);
@@ -253,7 +289,10 @@ int run_jpeg(yolo2_hip_ctx *c, int precision, const uint8_t *const *streams, con
             if (s == n_sets) memcpy(tables + n_sets++, &p.t, sizeof(Tables));
             set_of[(size_t)f] = s;
         }
-        L.streams_off = L.tables_off + (uint32_t)padded((size_t)n_sets * sizeof(Tables));
+        L.sseg_off = L.tables_off + (uint32_t)padded((size_t)n_sets * sizeof(Tables));
+        L.swg_off = L.sseg_off + (split ? (uint32_t)padded((size_t)n_seg * sizeof(SplitSeg)) : 0u);
+        L.streams_off = L.swg_off + (split ? (uint32_t)padded((size_t)n_seg * sizeof(SplitWg)) : 0u);
+        L.n_swg = 0;
         // ---- frames, segments, streams; the RGB24 slots
         size_t at = L.streams_off, rgb_off = table_bytes, coef_off = 0;
         int seg = 0, max_blocks = 0;
@@ -294,6 +333,28 @@ int run_jpeg(yolo2_hip_ctx *c, int precision, const uint8_t *const *streams, con
             for (int j = lo + 1; j < hi && same; ++j) same = frames[segs[j].frame].tables == s0;
             wg[w] = same ? s0 : -1;
         }
+        if (split) {
+            // the workgroups of k_jpegdec_split: consecutive segments of one frame, at least two subsequences each, filled up to
+            // kSplitMaxSub subsequences / kSplitWgSegs segments
+            SplitSeg *sseg = reinterpret_cast<SplitSeg *>(blob + L.sseg_off);
+            SplitWg *swg = reinterpret_cast<SplitWg *>(blob + L.swg_off);
+            int n_ss = 0;
+            for (int f = 0; f < nf; ++f) {
+                SplitWg cur = {n_ss, 0, 0, 0};
+                for (int j = frames[f].first_seg; j < frames[f].first_seg + (frames[f].raw ? 0 : frames[f].n_seg); ++j) {
+                    const SplitPlan sp = split_plan(blob, segs[j], split);
+                    if (sp.n_sub < 2) { split_info[3] += 1; continue; }
+                    if (cur.n == kSplitWgSegs || cur.n_tasks + sp.n_sub > kSplitMaxSub) {
+                        swg[L.n_swg++] = cur;
+                        cur = SplitWg{n_ss, 0, 0, 0};
+                    }
+                    sseg[n_ss++] = SplitSeg{sp.data_end, j, sp.sub, sp.n_sub, cur.n_tasks, {0, 0, 0}};
+                    ++cur.n; cur.n_tasks += sp.n_sub; cur.rounds = std::max(cur.rounds, sp.n_sub - 1);
+                    split_info[0] += sp.n_sub;
+                }
+                if (cur.n) swg[L.n_swg++] = cur;
+            }
+        }
         LetterboxItem *items = reinterpret_cast<LetterboxItem *>(hin);
         for (int f = 0; f < batch; ++f) {   // a partial last chunk repeats its last image
             const int i = std::min(f, nf - 1);
@@ -323,7 +384,15 @@ int run_jpeg(yolo2_hip_ctx *c, int precision, const uint8_t *const *streams, con
         stamp(k, 0);
         if (coef_off) Y2_TRY(hipMemsetAsync(P.jcoef.get(), 0, coef_off * sizeof(int16_t), P.s_run), YOLO2_ERROR);
         stamp(k, 1);
-        if (n_seg) hipLaunchKernelGGL(k_jpegdec_entropy, dim3((unsigned)L.n_wg), dim3(kEntropyLanes), 0, P.s_run, a);
+        if (split && n_seg) {
+            JpegSplitArgs sa;
+            sa.seg_off = L.sseg_off; sa.wg_off = L.swg_off; sa.word_off = L.status_off + (uint32_t)((size_t)(nf + n_seg) * sizeof(int));
+            if (L.n_swg) hipLaunchKernelGGL(k_jpegdec_split, dim3((unsigned)L.n_swg), dim3(kSplitThreads), 0, P.s_run, a, sa);
+            if (!prof.e.empty()) (void)hipEventRecord(prof.e[(size_t)(chunks * 5 + k)], P.s_run);
+            hipLaunchKernelGGL(k_jpegdec_rest, dim3((unsigned)L.n_wg), dim3(kEntropyLanes), 0, P.s_run, a, sa);
+        } else if (n_seg) {
+            hipLaunchKernelGGL(k_jpegdec_entropy, dim3((unsigned)L.n_wg), dim3(kEntropyLanes), 0, P.s_run, a);
+        }
         stamp(k, 2);
         if (max_blocks) hipLaunchKernelGGL(k_jpegdec_idct, dim3(blocks_for(max_blocks, kIdctThreads), (unsigned)nf), dim3(kIdctThreads), 0, P.s_run, a);
         stamp(k, 3);
@@ -365,7 +434,7 @@ int run_jpeg(yolo2_hip_ctx *c, int precision, const uint8_t *const *streams, con
             Y2_TRY(hipMemcpyAsync(P.hdets[b].get(), P.post[b].dets.get(), (size_t)batch * cap * sizeof(yolo2_hip_det), hipMemcpyDeviceToHost, P.s_out),
                    YOLO2_DMA_ERROR);
         }
-        Y2_TRY(hipMemcpyAsync(P.hjstatus[b].get(), P.djpg[b].get() + L.status_off, (size_t)(nf + n_seg) * sizeof(int), hipMemcpyDeviceToHost, P.s_out),
+        Y2_TRY(hipMemcpyAsync(P.hjstatus[b].get(), P.djpg[b].get() + L.status_off, words * sizeof(int), hipMemcpyDeviceToHost, P.s_out),
                YOLO2_DMA_ERROR);
         Y2_TRY(hipEventRecord(P.e_out[b], P.s_out), YOLO2_ERROR);
     }
@@ -381,6 +450,12 @@ int run_jpeg(yolo2_hip_ctx *c, int precision, const uint8_t *const *streams, con
                 if (hipEventElapsedTime(&ms, prof.e[(size_t)(k * 5 + i)], prof.e[(size_t)(k * 5 + i + 1)]) == hipSuccess) info[i] += ms / chunks;
             }
         info[4] = up_blob; info[5] = up_other; info[6] = chunks; info[7] = n;
+        for (int k = 0; k < chunks && split && !prof.e.empty(); ++k) {
+            float ms = 0.f;
+            if (hipEventElapsedTime(&ms, prof.e[(size_t)(k * 5 + 1)], prof.e[(size_t)(chunks * 5 + k)]) == hipSuccess) split_info[6] += ms / chunks;
+            if (hipEventElapsedTime(&ms, prof.e[(size_t)(chunks * 5 + k)], prof.e[(size_t)(k * 5 + 2)]) == hipSuccess) split_info[7] += ms / chunks;
+        }
+        memcpy(c->jpeg_split_info, split_info, sizeof(split_info));
     }
     if (want_dets && i16 && final_q) *final_q = q;
     if (first_bad >= 0)
@@ -394,6 +469,13 @@ extern "C" int yolo2_hip_jpeg_last_info(yolo2_hip_ctx *c, double *out8)
 {
     if (!c || !out8) return fail(YOLO2_ERROR, "null argument");
     memcpy(out8, c->jpeg_dec_info, sizeof(c->jpeg_dec_info));
+    return YOLO2_SUCCESS;
+}
+
+extern "C" int yolo2_hip_jpeg_split_info(yolo2_hip_ctx *c, double *out8)
+{
+    if (!c || !out8) return fail(YOLO2_ERROR, "null argument");
+    memcpy(out8, c->jpeg_split_info, sizeof(c->jpeg_split_info));
     return YOLO2_SUCCESS;
 }
 

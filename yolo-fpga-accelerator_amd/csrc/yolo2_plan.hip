@@ -27,6 +27,10 @@ struct StrOpt { const char *name; std::string Y2Options::*m; };
 const FlagOpt kI8Flags[] = {
     {"i8_no_front", &Y2Options::i8_no_front},
 };
+// The GPU JPEG decoder's subsequence size, a table of its own for the same reason as kI8Flags (and its values are multiples of 16)
+const IntOpt kJpegInts[] = {
+    {"jpegdec_split", &Y2Options::jpegdec_split, 16, 4096},
+};
 const FlagOpt kFlags[] = {
     {"no_lanes", &Y2Options::no_lanes}, {"verbose", &Y2Options::verbose}, {"no_plan_cache", &Y2Options::no_plan_cache},
     {"no_poolfuse", &Y2Options::no_poolfuse}, {"no_hiacc", &Y2Options::no_hiacc}, {"no_ks", &Y2Options::no_ks},
@@ -72,6 +76,15 @@ int Y2Options::set(const char *name, const char *value)
             this->*o.m = (int)v;
             return 0;
         }
+    for (const IntOpt &o : kJpegInts)
+        if (!strcmp(name, o.name)) {
+            if (clear) { this->*o.m = dflt.*o.m; return 0; }
+            char *end = nullptr;
+            const long v = strtol(value, &end, 10);
+            if (end == value || *end || (v != 0 && (v < o.lo || v > o.hi || v % 16))) return -1;
+            this->*o.m = (int)v;
+            return 0;
+        }
     for (const StrOpt &o : kStrs)
         if (!strcmp(name, o.name)) {
             this->*o.m = clear ? std::string() : std::string(value);
@@ -98,6 +111,7 @@ Y2Options Y2Options::from_env()
     for (const FlagOpt &f : kFlags) take(f.name);
     for (const FlagOpt &f : kI8Flags) take(f.name);
     for (const IntOpt &i : kInts) take(i.name);
+    for (const IntOpt &i : kJpegInts) take(i.name);
     for (const StrOpt &s : kStrs) take(s.name);
     return o;
 }
@@ -112,6 +126,8 @@ std::string Y2Options::describe() const
     for (const FlagOpt &f : kI8Flags)
         if (this->*f.m != d.*f.m) add(std::string(f.name) + "=" + (this->*f.m ? "1" : "0"));
     for (const IntOpt &i : kInts)
+        if (this->*i.m != d.*i.m) add(std::string(i.name) + "=" + std::to_string(this->*i.m));
+    for (const IntOpt &i : kJpegInts)
         if (this->*i.m != d.*i.m) add(std::string(i.name) + "=" + std::to_string(this->*i.m));
     for (const StrOpt &s : kStrs)
         if (this->*s.m != d.*s.m) add(std::string(s.name) + "=" + this->*s.m);

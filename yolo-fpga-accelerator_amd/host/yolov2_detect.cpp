@@ -75,6 +75,7 @@ struct AppConfig {
     std::string post = "gpu";          // region + boxes + NMS: gpu | host
     std::string tail = "core";         // whose arithmetic the tail restates: the reference's src/core, or its camera loop's (linux_app)
     int chunk_batches = 4;             // batches per device and accelerator call (streaming)
+    int decode_split = 0;              // --decode-split: option jpegdec_split of the GPU decoder (0: one lane per restart interval)
     int decode_threads = 0;            // image decode pool; 0 = all host cores
     bool strict = false;               // streaming: stop at the first undecodable input instead of skipping the frame
     bool plan_cache = true;            // int16: keep bounds / forms / timed conv plans of this weight set in <weights>/weights_reorg_int16.bin.y2plan
@@ -130,6 +131,8 @@ void print_usage(const char *prog)
         "  --loop-gpu            with --annotate-gpu --save-annotated-dir and --post gpu: one accelerator call per chunk makes the records AND\n"
         "                        the annotated frames from one upload (yolo2_hip_loop_images_pix); same log, JSONL and files\n"
         "  --chunk-batches <n>   Batches per device and accelerator call (default 4)\n"
+        "  --decode-split <bytes> With --decode gpu: many lanes per restart interval, one per <bytes> of entropy-coded data (option\n"
+        "                        jpegdec_split: a multiple of 16 in 16..4096; for streams without restart markers).  Same records.\n"
         "  --decode-threads <n>  Host threads decoding images ahead of the accelerators (default: all cores; one pool feeds every device)\n"
         "  --strict              Stop at the first input that cannot be read or decoded (default: log it, skip the frame, go on)\n"
         "  --no-plan-cache       int16: do not read / write <weights>/weights_reorg_int16.bin.y2plan (the weight set's bounds, forms and\n"
@@ -201,6 +204,13 @@ AppConfig parse_args(int argc, char **argv)
         else if (arg == "--jpeg-quality" && need("")) cfg.jpeg_quality = std::atoi(argv[++i]);
         else if (arg == "--chunk-batches" && need("")) cfg.chunk_batches = std::max(1, std::atoi(argv[++i]));
         else if (arg == "--decode-threads" && need("")) cfg.decode_threads = std::atoi(argv[++i]);
+        else if (arg == "--decode-split" && need("")) {
+            cfg.decode_split = std::atoi(argv[++i]);
+            if (cfg.decode_split < 16 || cfg.decode_split > 4096 || cfg.decode_split % 16) {
+                std::fprintf(stderr, "Unsupported --decode-split %s (a multiple of 16 in 16..4096)\n", argv[i]);
+                std::exit(1);
+            }
+        }
         else if (arg == "--strict") cfg.strict = true;
         else if (arg == "--no-plan-cache") cfg.plan_cache = false;
         else if (arg == "--post" && need("")) {
@@ -254,6 +264,10 @@ AppConfig parse_args(int argc, char **argv)
                                 !cfg.save_dir.empty() || cfg.loop_gpu)) {
         std::fprintf(stderr, "--decode gpu decodes the JPEG streams of --input-list, --input-dir or --video-mjpeg in front of --post gpu; "
                              "not with --save-annotated-dir or --loop-gpu\n");
+        std::exit(1);
+    }
+    if (cfg.decode_split && cfg.decode != "gpu") {
+        std::fprintf(stderr, "--decode-split is the GPU decoder's: it needs --decode gpu\n");
         std::exit(1);
     }
     if (cfg.video_pixfmt == YOLO2_PIX_YUYV && !cfg.video_raw.empty() && (cfg.video_w & 1)) {
@@ -810,6 +824,8 @@ void run_stream(AppConfig cfg)
     auto lane = [&](int slot) {
         try {
             yolo2_hip_ctx *ctx = yolo2_hip_multi_ctx(m, slot);
+            if (cfg.decode_split && yolo2_hip_set_option(ctx, "jpegdec_split", std::to_string(cfg.decode_split).c_str()) != YOLO2_SUCCESS)
+                throw std::runtime_error(yolo2_hip_last_error());
             // while the reader decodes its first chunk: plan the batch (activation tensors, lanes) on this device (int16; the fp16
             // passes build their launch table at the first chunk)
             if (!f16 && !i8) {

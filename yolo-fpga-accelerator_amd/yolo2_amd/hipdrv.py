@@ -65,7 +65,7 @@ EXPORTS = [
     "yolo2_hip_run_batch_int8", "yolo2_hip_run_batch_int8_host", "yolo2_hip_debug_i8_tensor", "yolo2_execute_conv_layer_int8",
     "yolo2_hip_run_images_pix_int8_host", "yolo2_hip_run_images_pix_dets_int8", "yolo2_hip_images_front_kernel_int8",
     "yolo2_hip_jpeg_probe", "yolo2_hip_jpeg_reason_name", "yolo2_hip_decode_jpeg_host", "yolo2_hip_decode_jpeg_ref",
-    "yolo2_hip_run_images_jpeg_dets", "yolo2_hip_jpeg_last_info",
+    "yolo2_hip_run_images_jpeg_dets", "yolo2_hip_jpeg_last_info", "yolo2_hip_decode_jpeg_split_ref", "yolo2_hip_jpeg_split_info",
 ]
 
 # include/yolo2_hip.h YOLO2_PIX_*: the pixfmt argument of the _pix entries ("yuyv": packed YUYV 4:2:2, arrays uint8 [h][w][2])
@@ -323,6 +323,8 @@ def lib():
     sig("yolo2_hip_decode_jpeg_host", [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp])
     sig("yolo2_hip_decode_jpeg_ref", [vp, C.c_size_t, vp, C.c_size_t, pi32, pi32, pi32])
     sig("yolo2_hip_jpeg_last_info", [vp, vp])
+    sig("yolo2_hip_decode_jpeg_split_ref", [vp, C.c_size_t, C.c_int, vp, C.c_size_t, pi32, pi32, pi32, vp])
+    sig("yolo2_hip_jpeg_split_info", [vp, vp])
     sig("yolo2_hip_run_images_jpeg_dets", [vp, i32, vp, vp, vp, vp, i32, i32, C.c_float, C.c_float, i32, vp, i32, vp, pi32, vp])
     _lib = L
     return L
@@ -1140,19 +1142,37 @@ def jpeg_probe(data) -> dict:
     return {k: getattr(info, k) for k, _ in JpegInfo._fields_}
 
 
-def jpeg_decode_ref(data, cap: int = None):
+_SPLIT_INFO = ("subsequences", "split_segments", "fallback_segments", "short_segments", "max_rounds", "split_bytes")
+
+
+def _split_info(v) -> dict:
+    d = {k: int(v[i]) for i, k in enumerate(_SPLIT_INFO)}
+    d.update(split_ms=v[6], fallback_ms=v[7])
+    return d
+
+
+def jpeg_decode_ref(data, cap: int = None, split: int = None):
     """yolo2_hip_decode_jpeg_ref: the GPU decoder's stages run on the host -> (uint8 [h][w][3] or None, status).  A stream the probe
-    refuses gives (None, 100 + reason)."""
+    refuses gives (None, 100 + reason).  split = S bytes: yolo2_hip_decode_jpeg_split_ref, the entropy stage as option jpegdec_split
+    runs it (many lanes per segment, here as loops) -> (picture or None, status, info as jpeg_split_info's)."""
     buf = bytes(data)
     info = jpeg_probe(buf)
     out = np.zeros(max(1, info["width"] * info["height"] * 3) if cap is None else cap, dtype=np.uint8)
     w, h, st = C.c_int(0), C.c_int(0), C.c_int(0)
-    rc = lib().yolo2_hip_decode_jpeg_ref(buf, len(buf), out.ctypes.data_as(C.c_void_p), out.size, C.byref(w), C.byref(h), C.byref(st))
+    if split is None:
+        name, extra = "yolo2_hip_decode_jpeg_ref", ()
+        rc = lib().yolo2_hip_decode_jpeg_ref(buf, len(buf), out.ctypes.data_as(C.c_void_p), out.size, C.byref(w), C.byref(h), C.byref(st))
+    else:
+        v = (C.c_double * 8)()
+        name = "yolo2_hip_decode_jpeg_split_ref"
+        rc = lib().yolo2_hip_decode_jpeg_split_ref(buf, len(buf), int(split), out.ctypes.data_as(C.c_void_p), out.size, C.byref(w), C.byref(h),
+                                                   C.byref(st), v)
+        extra = (_split_info(v),)
     if rc != YOLO2_SUCCESS and st.value < 100:
-        check(rc, "yolo2_hip_decode_jpeg_ref")
+        check(rc, name)
     if st.value:
-        return None, st.value
-    return out[:w.value * h.value * 3].reshape(h.value, w.value, 3), 0
+        return (None, st.value) + extra
+    return (out[:w.value * h.value * 3].reshape(h.value, w.value, 3), 0) + extra
 
 
 def jpeg_last_info(handle) -> dict:
@@ -1161,6 +1181,13 @@ def jpeg_last_info(handle) -> dict:
     check(lib().yolo2_hip_jpeg_last_info(handle, v), "yolo2_hip_jpeg_last_info")
     return {"memset_ms": v[0], "entropy_ms": v[1], "idct_ms": v[2], "rgb_ms": v[3], "stream_bytes_h2d": int(v[4]), "frame_bytes_h2d": int(v[5]),
             "chunks": int(v[6]), "frames": int(v[7])}
+
+
+def jpeg_split_info(handle) -> dict:
+    """yolo2_hip_jpeg_split_info: what option jpegdec_split did in the last JPEG call (all zero when it was unset)"""
+    v = (C.c_double * 8)()
+    check(lib().yolo2_hip_jpeg_split_info(handle, v), "yolo2_hip_jpeg_split_info")
+    return _split_info(v)
 
 
 def _stream_args(streams):
