@@ -762,8 +762,9 @@ int yolo2_execute_conv_layer_int8(uint64_t input_addr, uint64_t output_addr, uin
  * several intervals of a frame fail, the first in stream order gives the status.  A flagged frame is not a guess: its pixels are
  * zero-filled and the caller decodes it on the host.
  *
- * Out of scope here (they keep taking raw frames): the loop / annotate entries, the _multi_ entries, the calibration entry and
- * bench.py; the colour stage is not fused into the letterbox or layer-0 kernels. */
+ * Out of scope here (they keep taking raw frames): the annotate-only entries, the calibration entry and bench.py; the colour stage
+ * is not fused into the letterbox or layer-0 kernels.  The loop entry from streams is yolo2_hip_loop_images_jpeg below, the
+ * multi-GPU forms are in the multi-GPU section. */
 enum {
     YOLO2_JPEG_OK = 0, YOLO2_JPEG_DAMAGED = 1, YOLO2_JPEG_PROGRESSIVE = 2, YOLO2_JPEG_UNSUPPORTED_SOF = 3, YOLO2_JPEG_COMPONENTS = 4,
     YOLO2_JPEG_RGB_COLOUR = 5, YOLO2_JPEG_SAMPLING = 6, YOLO2_JPEG_SCANS = 7, YOLO2_JPEG_MISSING_TABLE = 8, YOLO2_JPEG_TOO_LARGE = 9
@@ -817,6 +818,26 @@ int yolo2_hip_decode_jpeg_split_ref(const uint8_t *stream, size_t size, int spli
  * that fell back to the one-lane function, [3] segments too short to split, [4] most synchronisation rounds of any segment, [5] S,
  * [6] / [7] device-event milliseconds per chunk of k_jpegdec_split and of k_jpegdec_rest (under yolo2_hip_set_profiling). */
 int yolo2_hip_jpeg_split_info(yolo2_hip_ctx *ctx, double *out8);
+/* The camera loop as one call FROM STREAMS: yolo2_hip_loop_images_pix (YOLO2_PIX_RGB24) with the decoder above in front of it, the
+ * decoded frame never leaving the device.  The decoder kernels write each frame into the slot of the chunk's staging buffer that the
+ * network's front kernel, k_draw_items' painter k_annotate_batch and the encoder then read, so dets, counts, final_q, drawn, out[f]
+ * and out_sizes[f] are, byte for byte, what yolo2_hip_decode_jpeg_host followed by yolo2_hip_loop_images_pix on its frames returns;
+ * only compressed bytes, tables and records cross PCIe in either direction (with YOLO2_LOOP_OUT_RGB24 the painted frames come back).
+ * Arguments as yolo2_hip_run_images_jpeg_dets (streams, sizes, widths, heights - sizes[i] == 0: frame i is raw RGB24 of widths[i] x
+ * heights[i] - and status [n], which may not be NULL) and as yolo2_hip_loop_images_pix (everything else; out_sizes is its `sizes`).
+ * precision: YOLO2_LOOP_INT16, _FP16 or _F32TOL; YOLO2_JPEG_INT8 is refused (the loop entries have no int8 form).  flags must
+ * contain YOLO2_DETS_BEST_CLASS; YOLO2_DETS_APP_TAIL is honoured.  Option jpegdec_split is read per call.
+ * Refused before any launch, every output (widths / heights included) untouched: what the probe refuses, with its reason; what
+ * yolo2_hip_loop_images_pix and yolo2_hip_run_images_jpeg_dets refuse; with YOLO2_LOOP_OUT_RGB24 a caps[f] below w * h * 3 of the
+ * header.  A frame whose scan the decoder flags: status[f] != 0, counts[f] = 0, drawn[f] = 0, out_sizes[f] = 0, nothing is written
+ * to out[f], and the call returns YOLO2_ERROR naming the first such frame with every other frame complete.
+ * Afterwards yolo2_hip_jpeg_last_info, _jpeg_split_info and _loop_last_info describe the call: image_bytes_staged is stream bytes plus
+ * raw-frame bytes, image_bytes_h2d everything uploaded (blobs, tables, raw frames); jpeg_last_info [5] counts the painter's and the
+ * encoder's tables with the letterbox tables. */
+int yolo2_hip_loop_images_jpeg(yolo2_hip_ctx *ctx, int precision, const uint8_t *const *streams, const size_t *sizes, int *widths,
+                               int *heights, int n, int batch, float thresh, float nms, int flags, yolo2_hip_det *dets,
+                               int cap_per_frame, int *counts, int *final_q, const char *const *labels, int n_labels, int out_format,
+                               int quality, uint8_t *const *out, const size_t *caps, size_t *out_sizes, int *drawn, int *status);
 
 /* ------------------------------------------------------- multi-GPU: frame sharding, one weight broadcast
  *
@@ -889,6 +910,18 @@ int  yolo2_hip_multi_loop_images_pix(yolo2_hip_multi *m, int precision, const ui
                                      int pixfmt, int n, int batch_per_device, float thresh, float nms, int flags, yolo2_hip_det *dets,
                                      int cap_per_frame, int *counts, int *final_q, const char *const *labels, int n_labels, int out_format,
                                      int quality, uint8_t *const *out, const size_t *caps, size_t *sizes, int *drawn);
+/* the same from JPEG streams (see yolo2_hip_loop_images_jpeg) and the records entry from streams (see yolo2_hip_run_images_jpeg_dets):
+ * shard i is decoded, run, painted and encoded by device i; the whole call is looked at before a shard starts; frame numbers in the
+ * records are global, status [n] is indexed globally, and a shard's error names the frame within the shard beside the shard's first
+ * frame; yolo2_hip_jpeg_last_info / _split_info / _loop_last_info of a member context describe its shard.  Option jpegdec_split is
+ * each member context's own. */
+int  yolo2_hip_multi_loop_images_jpeg(yolo2_hip_multi *m, int precision, const uint8_t *const *streams, const size_t *sizes, int *widths,
+                                      int *heights, int n, int batch_per_device, float thresh, float nms, int flags, yolo2_hip_det *dets,
+                                      int cap_per_frame, int *counts, int *final_q, const char *const *labels, int n_labels, int out_format,
+                                      int quality, uint8_t *const *out, const size_t *caps, size_t *out_sizes, int *drawn, int *status);
+int  yolo2_hip_multi_run_images_jpeg_dets(yolo2_hip_multi *m, int precision, const uint8_t *const *streams, const size_t *sizes, int *widths,
+                                          int *heights, int n, int batch_per_device, float thresh, float nms, int flags, yolo2_hip_det *dets,
+                                          int cap_per_frame, int *counts, int *final_q, int *status);
 
 /* (b) one process per device (torchrun / MPI style; what bench.py --gpus N runs): rank 0 makes the 128-byte id
  * (ncclGetUniqueId), the launcher hands it to every rank, each rank joins with its context (ncclCommInitRank), then

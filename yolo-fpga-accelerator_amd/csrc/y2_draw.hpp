@@ -13,6 +13,10 @@ int y2_annotate_check(const uint8_t *const *images, const int *widths, const int
 int y2_loop_check(int precision, const uint8_t *const *images, const int *widths, const int *heights, int pixfmt, int n, int batch, float thresh,
                   int flags, const yolo2_hip_det *dets, int cap_per_frame, const int *counts, int n_labels, int out_format, int quality,
                   uint8_t *const *out, const size_t *caps, const size_t *sizes);
+// ... and the loop entry from JPEG streams: the probe's refusals (headers only), then y2_loop_check on the sizes the headers give.
+int y2_loop_jpeg_check(int precision, const uint8_t *const *streams, const size_t *stream_sizes, const int *widths, const int *heights, int n, int batch,
+                       float thresh, int flags, const yolo2_hip_det *dets, int cap_per_frame, const int *counts, int n_labels, int out_format,
+                       int quality, uint8_t *const *out, const size_t *caps, const size_t *sizes, const int *status);
 // The same for the JPEG entries: the checks above (the streams' pointers in place of the frames') and what the encoder refuses.
 int y2_annotate_jpeg_check(const uint8_t *const *images, const int *widths, const int *heights, int pixfmt, int n, int batch,
                            const yolo2_hip_det *dets, int cap_per_frame, const int *counts, float thresh, int n_labels, uint8_t *const *jpeg,

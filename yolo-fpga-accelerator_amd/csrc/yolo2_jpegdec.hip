@@ -1,6 +1,7 @@
 // yolo2_jpegdec.hip -- JPEG streams -> RGB24 / detection records with the decoder on the GPU (include/yolo2_hip.h, "JPEG streams
 // decoded on the GPU").  The probe and the host doorway (jpeg_parse.hpp over jpeg_scan.hpp), the launches of
-// kernels_jpegdec.hpp, and the one chunk loop behind the two GPU entries.
+// kernels_jpegdec.hpp as a stage of a chunk loop (y2_jpegdec.hpp; the loop entry from streams, yolo2_loop.hip, calls it too), and
+// the one chunk loop behind the two GPU entries.
 //
 // A chunk, in buffer set b of PipeBufs:
 //   host    headers parsed; hjpg[b] = the blob (Frame[], Segment[], the workgroups' table sets, status words, Tables[] - identical
@@ -17,6 +18,7 @@
 #include "letterbox.hpp"
 #include "jpeg_parse.hpp"
 #include "kernels_jpegdec.hpp"
+#include "y2_jpegdec.hpp"
 
 using namespace y2;
 using namespace y2jpg;
@@ -112,7 +114,307 @@ struct ChunkLayout {
     uint32_t segs_off, wg_off, status_off, tables_off, streams_off;
     uint32_t sseg_off, swg_off;    // option jpegdec_split: SplitSeg[], SplitWg[]; the segments' words follow the status words
     int n_seg, n_wg, n_swg;
+    // what the launches of the chunk need beside the offsets
+    size_t words, coef_off;
+    int max_blocks;
+    unsigned max_pixels;
 };
+
+}  // namespace
+
+// ---------------------------------------------------------------------------- the decoder as a stage (y2_jpegdec.hpp)
+
+struct Y2JpegDec {
+    yolo2_hip_ctx *c = nullptr;
+    const uint8_t *const *streams = nullptr;
+    const size_t *sizes = nullptr;
+    const int *widths = nullptr, *heights = nullptr;
+    int n = 0, batch = 0, chunks = 0;
+    int split = 0;                       // option jpegdec_split as read when the call began; 0: today's launches exactly
+    std::vector<Parsed> parsed;
+    size_t cap_blob = 0, cap_samples = 0, cap_status = 0;
+    ChunkLayout lay[2] = {};
+    double split_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    double up_blob = 0, up_raw = 0;
+    // under yolo2_hip_set_profiling: five timing events per chunk around the memset and the three kernels (yolo2_hip_jpeg_last_info);
+    // with the option a sixth, behind the first chunks * 5: between k_jpegdec_split and k_jpegdec_rest
+    std::vector<hipEvent_t> prof;
+    int in_chunk(int k) const { return std::min(batch, n - k * batch); }
+    ~Y2JpegDec() { for (hipEvent_t x : prof) (void)hipEventDestroy(x); }
+};
+
+void Y2JpegDecDelete::operator()(Y2JpegDec *d) const { delete d; }
+
+int y2_jpegdec_open(yolo2_hip_ctx *c, const uint8_t *const *streams, const size_t *sizes, int *widths, int *heights, int n, bool raw_ok,
+                    const std::function<int(int)> &check, Y2JpegDecPtr *out)
+{
+    Y2JpegDecPtr d(new Y2JpegDec());
+    d->c = c; d->streams = streams; d->sizes = sizes; d->widths = widths; d->heights = heights; d->n = n;
+    d->split = c ? c->opt.jpegdec_split : 0;      // read per call (no context: the headers are all the caller wants)
+    d->split_info[5] = (double)d->split;
+    d->parsed.resize((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        if (!streams[i]) return fail(YOLO2_ERROR, "frame %d: null stream", i);
+        Parsed &p = d->parsed[(size_t)i];
+        if (sizes[i] == 0) {
+            if (!raw_ok) return fail(YOLO2_ERROR, "frame %d: empty stream", i);
+            memset(&p.f, 0, sizeof(p.f));
+            p.f.raw = 1; p.f.width = widths[i]; p.f.height = heights[i];
+        } else {
+            Info info;
+            if (parse(streams[i], sizes[i], info, &p))
+                return fail(YOLO2_ERROR, "frame %d: not GPU-decodable (reason %d: %s)", i, info.reason, yolo2_hip_jpeg_reason_name(info.reason));
+            widths[i] = info.width; heights[i] = info.height;
+        }
+        const int rc = check ? check(i) : YOLO2_SUCCESS;
+        if (rc) return rc;
+    }
+    *out = std::move(d);
+    return YOLO2_SUCCESS;
+}
+
+bool y2_jpegdec_raw(const Y2JpegDec *d, int frame) { return d->parsed[(size_t)frame].f.raw != 0; }
+
+int y2_jpegdec_plan(Y2JpegDec *d, int batch)
+{
+    d->batch = batch;
+    d->chunks = (d->n + batch - 1) / batch;
+    const int split = d->split;
+    for (int k = 0; k < d->chunks; ++k) {
+        size_t str = 0, samples = 0, segs = 0;
+        for (int i = k * batch; i < k * batch + d->in_chunk(k); ++i) {
+            str += (d->sizes[i] + 15) & ~(size_t)15;
+            samples += d->parsed[(size_t)i].f.samples;
+            segs += d->parsed[(size_t)i].segs.size();
+        }
+        const size_t nf = (size_t)d->in_chunk(k), wgs = (segs + kEntropyLanes - 1) / kEntropyLanes;
+        // (jpegdec_split: at most one SplitSeg and one SplitWg per segment, and a word per segment behind the status words)
+        const size_t words = nf + segs * (split ? 2 : 1);
+        const size_t blob = padded(nf * sizeof(Frame)) + padded(segs * sizeof(Segment)) + padded(wgs * sizeof(int)) + padded(words * sizeof(int)) +
+                            padded(nf * sizeof(Tables)) + padded(str) + (split ? padded(segs * sizeof(SplitSeg)) + padded(segs * sizeof(SplitWg)) : 0);
+        if (blob > (size_t)1 << 31) return fail(YOLO2_ERROR, "chunk %d: more than 2 GiB of streams and tables (use a smaller batch)", k);
+        d->cap_blob = std::max(d->cap_blob, blob); d->cap_samples = std::max(d->cap_samples, samples);
+        d->cap_status = std::max(d->cap_status, words);
+    }
+    return YOLO2_SUCCESS;
+}
+
+int y2_jpegdec_ensure(Y2JpegDec *d)
+{
+    int rc;
+    if ((rc = jpeg_ensure(d->c->pipe, d->cap_blob, std::max<size_t>(d->cap_samples, 64), d->cap_status))) return rc;
+    if (d->c->prof)
+        for (int i = 0; i < d->chunks * (d->split ? 6 : 5); ++i) {
+            hipEvent_t e;
+            HIP_TRY(hipEventCreate(&e), YOLO2_ERROR);
+            d->prof.push_back(e);
+        }
+    return YOLO2_SUCCESS;
+}
+
+int y2_jpegdec_stage(Y2JpegDec *d, int k, const size_t *slot, uint8_t *hin)
+{
+    PipeBufs &P = d->c->pipe;
+    const int b = k & 1, nf = d->in_chunk(k), first = k * d->batch, split = d->split;
+    const std::vector<Parsed> &parsed = d->parsed;
+    uint8_t *blob = P.hjpg[b].get();
+    // ---- blob layout
+    int n_seg = 0;
+    for (int f = 0; f < nf; ++f) n_seg += (int)parsed[(size_t)(first + f)].segs.size();
+    ChunkLayout &L = d->lay[b];
+    L.n_seg = n_seg; L.n_wg = (n_seg + kEntropyLanes - 1) / kEntropyLanes;
+    L.segs_off = (uint32_t)padded((size_t)nf * sizeof(Frame));
+    L.wg_off = L.segs_off + (uint32_t)padded((size_t)n_seg * sizeof(Segment));
+    L.status_off = L.wg_off + (uint32_t)padded((size_t)L.n_wg * sizeof(int));
+    const size_t words = (size_t)nf + (size_t)n_seg * (split ? 2 : 1);
+    L.words = words;
+    L.tables_off = L.status_off + (uint32_t)padded(words * sizeof(int));
+    Frame *frames = reinterpret_cast<Frame *>(blob);
+    Segment *segs = reinterpret_cast<Segment *>(blob + L.segs_off);
+    int *wg = reinterpret_cast<int *>(blob + L.wg_off), *st = reinterpret_cast<int *>(blob + L.status_off);
+    Tables *tables = reinterpret_cast<Tables *>(blob + L.tables_off);
+    memset(st, 0, words * sizeof(int));
+    // ---- table sets: identical ones once
+    int n_sets = 0;
+    std::vector<int> set_of((size_t)nf, 0);
+    for (int f = 0; f < nf; ++f) {
+        const Parsed &p = parsed[(size_t)(first + f)];
+        if (p.f.raw) continue;
+        int s = 0;
+        while (s < n_sets && memcmp(tables + s, &p.t, sizeof(Tables)) != 0) ++s;
+        if (s == n_sets) memcpy(tables + n_sets++, &p.t, sizeof(Tables));
+        set_of[(size_t)f] = s;
+    }
+    L.sseg_off = L.tables_off + (uint32_t)padded((size_t)n_sets * sizeof(Tables));
+    L.swg_off = L.sseg_off + (split ? (uint32_t)padded((size_t)n_seg * sizeof(SplitSeg)) : 0u);
+    L.streams_off = L.swg_off + (split ? (uint32_t)padded((size_t)n_seg * sizeof(SplitWg)) : 0u);
+    L.n_swg = 0;
+    // ---- frames, segments, streams; the RGB24 slots
+    size_t at = L.streams_off, coef_off = 0;
+    int seg = 0, max_blocks = 0;
+    unsigned max_pixels = 0;
+    for (int f = 0; f < nf; ++f) {
+        const Parsed &p = parsed[(size_t)(first + f)];
+        const int i = first + f;
+        Frame &F = frames[f];
+        F = p.f;
+        F.tables = set_of[(size_t)f];
+        F.first_seg = seg; F.n_seg = (int)p.segs.size();
+        F.coef_off = F.plane_off = coef_off;
+        F.rgb_off = slot[f];
+        const size_t bytes = (size_t)d->widths[i] * d->heights[i] * 3;
+        if (p.f.raw) {
+            memcpy(hin + slot[f], d->streams[i], bytes);
+        } else {
+            st[f] = p.status;
+            memcpy(blob + at, d->streams[i], d->sizes[i]);
+            for (const Segment &s : p.segs) {
+                Segment &ds = segs[seg++];
+                ds = s;
+                ds.begin += (uint32_t)at; ds.end += (uint32_t)at; ds.frame = f;
+            }
+            at += (d->sizes[i] + 15) & ~(size_t)15;
+            coef_off += p.f.samples;
+            max_blocks = std::max(max_blocks, p.f.blocks);
+            max_pixels = std::max(max_pixels, (unsigned)d->widths[i] * (unsigned)d->heights[i]);
+        }
+    }
+    L.coef_off = coef_off; L.max_blocks = max_blocks; L.max_pixels = max_pixels;
+    const size_t blob_bytes = padded(at);
+    memset(blob + at, 0, blob_bytes - at);
+    for (int w = 0; w < L.n_wg; ++w) {
+        const int lo = w * kEntropyLanes, hi = std::min(n_seg, lo + kEntropyLanes), s0 = frames[segs[lo].frame].tables;
+        bool same = true;
+        for (int j = lo + 1; j < hi && same; ++j) same = frames[segs[j].frame].tables == s0;
+        wg[w] = same ? s0 : -1;
+    }
+    if (split) {
+        // the workgroups of k_jpegdec_split: consecutive segments of one frame, at least two subsequences each, filled up to
+        // kSplitMaxSub subsequences / kSplitWgSegs segments
+        SplitSeg *sseg = reinterpret_cast<SplitSeg *>(blob + L.sseg_off);
+        SplitWg *swg = reinterpret_cast<SplitWg *>(blob + L.swg_off);
+        int n_ss = 0;
+        for (int f = 0; f < nf; ++f) {
+            SplitWg cur = {n_ss, 0, 0, 0};
+            for (int j = frames[f].first_seg; j < frames[f].first_seg + (frames[f].raw ? 0 : frames[f].n_seg); ++j) {
+                const SplitPlan sp = split_plan(blob, segs[j], split);
+                if (sp.n_sub < 2) { d->split_info[3] += 1; continue; }
+                if (cur.n == kSplitWgSegs || cur.n_tasks + sp.n_sub > kSplitMaxSub) {
+                    swg[L.n_swg++] = cur;
+                    cur = SplitWg{n_ss, 0, 0, 0};
+                }
+                sseg[n_ss++] = SplitSeg{sp.data_end, j, sp.sub, sp.n_sub, cur.n_tasks, {0, 0, 0}};
+                ++cur.n; cur.n_tasks += sp.n_sub; cur.rounds = std::max(cur.rounds, sp.n_sub - 1);
+                d->split_info[0] += sp.n_sub;
+            }
+            if (cur.n) swg[L.n_swg++] = cur;
+        }
+    }
+    HIP_TRY(hipMemcpyAsync(P.djpg[b].get(), blob, blob_bytes, hipMemcpyHostToDevice, P.s_in), YOLO2_DMA_ERROR);
+    d->up_blob += (double)blob_bytes;
+    return YOLO2_SUCCESS;
+}
+
+int y2_jpegdec_upload_raw(Y2JpegDec *d, int k, const size_t *slot, const uint8_t *hin)
+{
+    PipeBufs &P = d->c->pipe;
+    const int b = k & 1, nf = d->in_chunk(k), first = k * d->batch;
+    for (int f = 0; f < nf; ++f)
+        if (d->parsed[(size_t)(first + f)].f.raw) {
+            const size_t bytes = (size_t)d->widths[first + f] * d->heights[first + f] * 3;
+            HIP_TRY(hipMemcpyAsync(P.dbytes[b].get() + slot[f], hin + slot[f], bytes, hipMemcpyHostToDevice, P.s_in), YOLO2_DMA_ERROR);
+            d->up_raw += (double)bytes;
+        }
+    return YOLO2_SUCCESS;
+}
+
+int y2_jpegdec_launch(Y2JpegDec *d, int k)
+{
+    PipeBufs &P = d->c->pipe;
+    const int b = k & 1, nf = d->in_chunk(k), chunks = d->chunks;
+    const ChunkLayout &L = d->lay[b];
+    auto stamp = [&](int i) { if (!d->prof.empty()) (void)hipEventRecord(d->prof[(size_t)(k * 5 + i)], P.s_run); };
+    JpegDecArgs a;
+    a.blob = P.djpg[b].get();
+    a.frames_off = 0; a.segs_off = L.segs_off; a.wg_off = L.wg_off; a.status_off = L.status_off; a.tables_off = L.tables_off;
+    a.n_frames = nf; a.n_seg = L.n_seg;
+    a.coef = P.jcoef.get(); a.planes = P.jplanes.get(); a.rgb = P.dbytes[b].get();
+    stamp(0);
+    if (L.coef_off) HIP_TRY(hipMemsetAsync(P.jcoef.get(), 0, L.coef_off * sizeof(int16_t), P.s_run), YOLO2_ERROR);
+    stamp(1);
+    if (d->split && L.n_seg) {
+        JpegSplitArgs sa;
+        sa.seg_off = L.sseg_off; sa.wg_off = L.swg_off; sa.word_off = L.status_off + (uint32_t)((size_t)(nf + L.n_seg) * sizeof(int));
+        if (L.n_swg) hipLaunchKernelGGL(k_jpegdec_split, dim3((unsigned)L.n_swg), dim3(kSplitThreads), 0, P.s_run, a, sa);
+        if (!d->prof.empty()) (void)hipEventRecord(d->prof[(size_t)(chunks * 5 + k)], P.s_run);
+        hipLaunchKernelGGL(k_jpegdec_rest, dim3((unsigned)L.n_wg), dim3(kEntropyLanes), 0, P.s_run, a, sa);
+    } else if (L.n_seg) {
+        hipLaunchKernelGGL(k_jpegdec_entropy, dim3((unsigned)L.n_wg), dim3(kEntropyLanes), 0, P.s_run, a);
+    }
+    stamp(2);
+    if (L.max_blocks) hipLaunchKernelGGL(k_jpegdec_idct, dim3(blocks_for(L.max_blocks, kIdctThreads), (unsigned)nf), dim3(kIdctThreads), 0, P.s_run, a);
+    stamp(3);
+    if (L.max_blocks) hipLaunchKernelGGL(k_jpegdec_rgb, dim3(blocks_for((long)L.max_pixels, kRgbThreads), (unsigned)nf), dim3(kRgbThreads), 0, P.s_run, a);
+    if (L.max_pixels) hipLaunchKernelGGL(k_jpegdec_zero, dim3(64, (unsigned)nf), dim3(256), 0, P.s_run, a);
+    stamp(4);
+    HIP_TRY(hipGetLastError(), YOLO2_ERROR);
+    return YOLO2_SUCCESS;
+}
+
+int y2_jpegdec_status_d2h(Y2JpegDec *d, int k, hipStream_t st)
+{
+    PipeBufs &P = d->c->pipe;
+    const int b = k & 1;
+    HIP_TRY(hipMemcpyAsync(P.hjstatus[b].get(), P.djpg[b].get() + d->lay[b].status_off, d->lay[b].words * sizeof(int), hipMemcpyDeviceToHost, st),
+            YOLO2_DMA_ERROR);
+    return YOLO2_SUCCESS;
+}
+
+void y2_jpegdec_collect(Y2JpegDec *d, int k, int *status, int *first_bad)
+{
+    const int b = k & 1, nf = d->in_chunk(k), first = k * d->batch;
+    const int *st = d->c->pipe.hjstatus[b].get();
+    int n_seg = 0, seg = 0;
+    for (int f = 0; f < nf; ++f) n_seg += (int)d->parsed[(size_t)(first + f)].segs.size();
+    if (d->split)
+        for (int j = 0; j < n_seg; ++j) {
+            const unsigned word = (unsigned)st[nf + n_seg + j];
+            if (!word) continue;
+            d->split_info[(word & 1u) ? 1 : 2] += 1;
+            d->split_info[4] = std::max(d->split_info[4], (double)(word >> 2));
+        }
+    for (int f = 0; f < nf; ++f) {
+        const Parsed &p = d->parsed[(size_t)(first + f)];
+        int s = st[f];
+        for (size_t j = 0; j < p.segs.size() && !s; ++j) s = st[nf + seg + (int)j];      // the first failing interval in stream order
+        seg += (int)p.segs.size();
+        status[first + f] = s;
+        if (s && *first_bad < 0) *first_bad = first + f;
+    }
+}
+
+double y2_jpegdec_uploaded(const Y2JpegDec *d) { return d->up_blob + d->up_raw; }
+
+void y2_jpegdec_close(Y2JpegDec *d, double other_bytes)
+{
+    const int chunks = d->chunks;
+    double *info = d->c->jpeg_dec_info;
+    for (int i = 0; i < 8; ++i) info[i] = 0;
+    for (int k = 0; k < chunks && !d->prof.empty(); ++k)
+        for (int i = 0; i < 4; ++i) {
+            float ms = 0.f;
+            if (hipEventElapsedTime(&ms, d->prof[(size_t)(k * 5 + i)], d->prof[(size_t)(k * 5 + i + 1)]) == hipSuccess) info[i] += ms / chunks;
+        }
+    info[4] = d->up_blob; info[5] = other_bytes + d->up_raw; info[6] = chunks; info[7] = d->n;
+    for (int k = 0; k < chunks && d->split && !d->prof.empty(); ++k) {
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, d->prof[(size_t)(k * 5 + 1)], d->prof[(size_t)(chunks * 5 + k)]) == hipSuccess) d->split_info[6] += ms / chunks;
+        if (hipEventElapsedTime(&ms, d->prof[(size_t)(chunks * 5 + k)], d->prof[(size_t)(k * 5 + 2)]) == hipSuccess) d->split_info[7] += ms / chunks;
+    }
+    memcpy(d->c->jpeg_split_info, d->split_info, sizeof(d->split_info));
+}
+
+namespace {
 
 // dets == nullptr: the decode entry (rgb_out / caps); otherwise the records entry
 int run_jpeg(yolo2_hip_ctx *c, int precision, const uint8_t *const *streams, const size_t *sizes, int *widths, int *heights, int n, int batch,
@@ -125,33 +427,24 @@ int run_jpeg(yolo2_hip_ctx *c, int precision, const uint8_t *const *streams, con
         return fail(YOLO2_ERROR, "bad image count %d / batch %d (1..1024) / capacity %d", n, batch, want_dets ? cap : 1);
     if (want_dets && thresh < 0.f) return fail(YOLO2_ERROR, "negative threshold");
     const bool i16 = precision == YOLO2_LOOP_INT16, i8 = precision == YOLO2_JPEG_INT8;
-    const int split = c->opt.jpegdec_split;      // read per call; 0: today's launches exactly
     if (want_dets && !i16 && !i8 && precision != YOLO2_LOOP_FP16 && precision != YOLO2_LOOP_F32TOL)
         return fail(YOLO2_ERROR, "unknown precision %d (YOLO2_LOOP_INT16, _FP16, _F32TOL or YOLO2_JPEG_INT8)", precision);
     // ---- headers: every refusal before anything is launched
-    std::vector<Parsed> parsed((size_t)n);
-    for (int i = 0; i < n; ++i) {
-        if (!streams[i]) return fail(YOLO2_ERROR, "frame %d: null stream", i);
-        Parsed &p = parsed[(size_t)i];
-        if (sizes[i] == 0) {
-            if (!want_dets) return fail(YOLO2_ERROR, "frame %d: empty stream", i);
-            memset(&p.f, 0, sizeof(p.f));
-            p.f.raw = 1; p.f.width = widths[i]; p.f.height = heights[i];
-        } else {
-            Info info;
-            if (parse(streams[i], sizes[i], info, &p))
-                return fail(YOLO2_ERROR, "frame %d: not GPU-decodable (reason %d: %s)", i, info.reason, yolo2_hip_jpeg_reason_name(info.reason));
-            widths[i] = info.width; heights[i] = info.height;
-            if (!want_dets && caps[i] < (size_t)info.width * info.height * 3)
-                return fail(YOLO2_ERROR, "frame %d: output buffer too small (%zu < %zu bytes)", i, caps[i], (size_t)info.width * info.height * 3);
-            if (!want_dets && !rgb_out[i]) return fail(YOLO2_ERROR, "frame %d: null output", i);
-        }
-        if (want_dets) {
-            LetterboxArgs a;
-            const int rc = y2_letterbox_args(widths[i], heights[i], 3, 416, 416, a, true);
-            if (rc) return rc;
-        }
-    }
+    Y2JpegDecPtr dec;
+    int rc;
+    if ((rc = y2_jpegdec_open(c, streams, sizes, widths, heights, n, want_dets, [&](int i) -> int {
+            if (sizes[i] && !want_dets) {
+                if (caps[i] < (size_t)widths[i] * heights[i] * 3)
+                    return fail(YOLO2_ERROR, "frame %d: output buffer too small (%zu < %zu bytes)", i, caps[i], (size_t)widths[i] * heights[i] * 3);
+                if (!rgb_out[i]) return fail(YOLO2_ERROR, "frame %d: null output", i);
+            }
+            if (want_dets) {
+                LetterboxArgs a;
+                return y2_letterbox_args(widths[i], heights[i], 3, 416, 416, a, true);
+            }
+            return YOLO2_SUCCESS;
+        }, &dec)))
+        return rc;
     // ---- the network's own refusals
     yolo2_hip_ctx *run = nullptr;
     bool fused = false;
@@ -162,8 +455,7 @@ int run_jpeg(yolo2_hip_ctx *c, int precision, const uint8_t *const *streams, con
             if (!y2_i8_loaded(c)) return fail(YOLO2_ERROR, "int8 weights not loaded (yolo2_hip_load_weights_int8)");
             fused = y2_i8_images_fused(c);
         } else {
-            const int rc = y2_f16_images_ctx(c, precision == YOLO2_LOOP_F32TOL ? 1 : 0, &run);
-            if (rc) return rc;
+            if ((rc = y2_f16_images_ctx(c, precision == YOLO2_LOOP_F32TOL ? 1 : 0, &run))) return rc;
             fused = y2_f16_images_fused(run);
         }
     }
@@ -173,64 +465,31 @@ int run_jpeg(yolo2_hip_ctx *c, int precision, const uint8_t *const *streams, con
     auto in_chunk = [&](int k) { return std::min(batch, n - k * batch); };
     const size_t table_bytes = padded((size_t)batch * sizeof(LetterboxItem));
     // ---- sizes of the largest chunk
-    size_t cap_rgb = 0, cap_blob = 0, cap_samples = 0, cap_status = 0;
+    size_t cap_rgb = 0;
     for (int k = 0; k < chunks; ++k) {
-        size_t rgb = table_bytes, str = 0, samples = 0, segs = 0;
-        for (int i = k * batch; i < k * batch + in_chunk(k); ++i) {
-            rgb += padded((size_t)widths[i] * heights[i] * 3);
-            str += (sizes[i] + 15) & ~(size_t)15;
-            samples += parsed[(size_t)i].f.samples;
-            segs += parsed[(size_t)i].segs.size();
-        }
-        const size_t nf = (size_t)in_chunk(k), wgs = (segs + kEntropyLanes - 1) / kEntropyLanes;
-        // (jpegdec_split: at most one SplitSeg and one SplitWg per segment, and a word per segment behind the status words)
-        const size_t words = nf + segs * (split ? 2 : 1);
-        const size_t blob = padded(nf * sizeof(Frame)) + padded(segs * sizeof(Segment)) + padded(wgs * sizeof(int)) + padded(words * sizeof(int)) +
-                            padded(nf * sizeof(Tables)) + padded(str) + (split ? padded(segs * sizeof(SplitSeg)) + padded(segs * sizeof(SplitWg)) : 0);
-        if (blob > (size_t)1 << 31) return fail(YOLO2_ERROR, "chunk %d: more than 2 GiB of streams and tables (use a smaller batch)", k);
-        cap_rgb = std::max(cap_rgb, rgb); cap_blob = std::max(cap_blob, blob); cap_samples = std::max(cap_samples, samples);
-        cap_status = std::max(cap_status, words);
+        size_t rgb = table_bytes;
+        for (int i = k * batch; i < k * batch + in_chunk(k); ++i) rgb += padded((size_t)widths[i] * heights[i] * 3);
+        cap_rgb = std::max(cap_rgb, rgb);
     }
-    if (want_dets && i16 && batch != c->batch) {
-        const int rc = yolo2_hip_set_batch(c, batch);
-        if (rc) return rc;
-    }
-    int rc;
+    if ((rc = y2_jpegdec_plan(dec.get(), batch))) return rc;
+    if (want_dets && i16 && batch != c->batch && (rc = yolo2_hip_set_batch(c, batch))) return rc;
     if ((rc = y2_pipe_ensure(c->pipe, cap_rgb, cap_rgb, batch, false))) return rc;     // (first: growing it drops every other buffer of PipeBufs)
     if (want_dets && !i16 && (rc = y2_pipe_ensure_regf(c->pipe, batch, false))) return rc;
     if (want_dets && (rc = y2_pipe_ensure_post(c, batch, cap))) return rc;
-    if ((rc = jpeg_ensure(c->pipe, cap_blob, std::max<size_t>(cap_samples, 64), cap_status))) return rc;
     PipeBufs &P = c->pipe;
     const size_t gbytes = y2_post_geom_bytes();
     auto cleanup = [&]() { (void)hipDeviceSynchronize(); };
 #define Y2_TRY(expr, code) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { rc = fail(code, "%s failed: %s", #expr, hipGetErrorString(e_)); cleanup(); return rc; } } while (0)
+    if ((rc = y2_jpegdec_ensure(dec.get()))) { cleanup(); return rc; }
 
-    std::vector<ChunkLayout> lay((size_t)2);
     std::vector<std::vector<size_t>> slot(2, std::vector<size_t>((size_t)batch));
     int first_bad = -1;
-    double split_info[8] = {0, 0, 0, 0, 0, (double)split, 0, 0};
     auto drain = [&](int k) {
         const int b = k & 1, nf = in_chunk(k), first = k * batch;
         (void)hipEventSynchronize(P.e_out[b]);
-        const int *st = P.hjstatus[b].get();
-        int seg = 0;
-        if (split) {
-            int n_seg = 0;
-            for (int f = 0; f < nf; ++f) n_seg += (int)parsed[(size_t)(first + f)].segs.size();
-            for (int j = 0; j < n_seg; ++j) {
-                const unsigned word = (unsigned)st[nf + n_seg + j];
-                if (!word) continue;
-                split_info[(word & 1u) ? 1 : 2] += 1;
-                split_info[4] = std::max(split_info[4], (double)(word >> 2));
-            }
-        }
+        y2_jpegdec_collect(dec.get(), k, status, &first_bad);
         for (int f = 0; f < nf; ++f) {
-            const Parsed &p = parsed[(size_t)(first + f)];
-            int s = st[f];
-            for (size_t j = 0; j < p.segs.size() && !s; ++j) s = st[nf + seg + (int)j];      // the first failing interval in stream order
-            seg += (int)p.segs.size();
-            status[first + f] = s;
-            if (s && first_bad < 0) first_bad = first + f;
+            const int s = status[first + f];
             if (!want_dets) {
                 const size_t bytes = (size_t)widths[first + f] * heights[first + f] * 3;
                 memcpy(rgb_out[first + f], P.hin[b].get() + slot[(size_t)b][(size_t)f], bytes);
@@ -246,115 +505,18 @@ int run_jpeg(yolo2_hip_ctx *c, int precision, const uint8_t *const *streams, con
     int q = 0;
     std::vector<int> cw((size_t)batch), chh((size_t)batch);
     std::vector<hipEvent_t> net_done;
-    // under yolo2_hip_set_profiling: five timing events per chunk around the memset and the three kernels (yolo2_hip_jpeg_last_info)
-    struct Events {
-        std::vector<hipEvent_t> e;
-        ~Events() { for (hipEvent_t x : e) (void)hipEventDestroy(x); }
-    } prof;
-    if (c->prof)
-        for (int i = 0; i < chunks * (split ? 6 : 5); ++i) {     // (the sixth, behind the first chunks * 5: between k_jpegdec_split and k_jpegdec_rest)
-            hipEvent_t e;
-            Y2_TRY(hipEventCreate(&e), YOLO2_ERROR);
-            prof.e.push_back(e);
-        }
-    auto stamp = [&](int k, int i) { if (!prof.e.empty()) (void)hipEventRecord(prof.e[(size_t)(k * 5 + i)], P.s_run); };
-    double up_blob = 0, up_other = 0;
+    double up_tables = 0;
     for (int k = 0; k < chunks; ++k) {
         const int b = k & 1, nf = in_chunk(k), first = k * batch;
         if (k >= 2) drain(k - 2);
-        uint8_t *blob = P.hjpg[b].get(), *hin = P.hin[b].get();
-        // ---- blob layout
-        int n_seg = 0;
-        for (int f = 0; f < nf; ++f) n_seg += (int)parsed[(size_t)(first + f)].segs.size();
-        ChunkLayout &L = lay[(size_t)b];
-        L.n_seg = n_seg; L.n_wg = (n_seg + kEntropyLanes - 1) / kEntropyLanes;
-        L.segs_off = (uint32_t)padded((size_t)nf * sizeof(Frame));
-        L.wg_off = L.segs_off + (uint32_t)padded((size_t)n_seg * sizeof(Segment));
-        L.status_off = L.wg_off + (uint32_t)padded((size_t)L.n_wg * sizeof(int));
-        const size_t words = (size_t)nf + (size_t)n_seg * (split ? 2 : 1);
-        L.tables_off = L.status_off + (uint32_t)padded(words * sizeof(int));
-        Frame *frames = reinterpret_cast<Frame *>(blob);
-        Segment *segs = reinterpret_cast<Segment *>(blob + L.segs_off);
-        int *wg = reinterpret_cast<int *>(blob + L.wg_off), *st = reinterpret_cast<int *>(blob + L.status_off);
-        Tables *tables = reinterpret_cast<Tables *>(blob + L.tables_off);
-        memset(st, 0, words * sizeof(int));
-        // ---- table sets: identical ones once
-        int n_sets = 0;
-        std::vector<int> set_of((size_t)nf, 0);
+        uint8_t *hin = P.hin[b].get();
+        // ---- the RGB24 slots behind the letterbox table, then the blob (and its upload)
+        size_t rgb_off = table_bytes;
         for (int f = 0; f < nf; ++f) {
-            Parsed &p = parsed[(size_t)(first + f)];
-            if (p.f.raw) continue;
-            int s = 0;
-            while (s < n_sets && memcmp(tables + s, &p.t, sizeof(Tables)) != 0) ++s;
-            if (s == n_sets) memcpy(tables + n_sets++, &p.t, sizeof(Tables));
-            set_of[(size_t)f] = s;
-        }
-        L.sseg_off = L.tables_off + (uint32_t)padded((size_t)n_sets * sizeof(Tables));
-        L.swg_off = L.sseg_off + (split ? (uint32_t)padded((size_t)n_seg * sizeof(SplitSeg)) : 0u);
-        L.streams_off = L.swg_off + (split ? (uint32_t)padded((size_t)n_seg * sizeof(SplitWg)) : 0u);
-        L.n_swg = 0;
-        // ---- frames, segments, streams; the RGB24 slots
-        size_t at = L.streams_off, rgb_off = table_bytes, coef_off = 0;
-        int seg = 0, max_blocks = 0;
-        unsigned max_pixels = 0;
-        for (int f = 0; f < nf; ++f) {
-            Parsed &p = parsed[(size_t)(first + f)];
-            const int i = first + f;
-            Frame &F = frames[f];
-            F = p.f;
-            F.tables = set_of[(size_t)f];
-            F.first_seg = seg; F.n_seg = (int)p.segs.size();
-            F.coef_off = F.plane_off = coef_off;
-            F.rgb_off = rgb_off;
             slot[(size_t)b][(size_t)f] = rgb_off;
-            const size_t bytes = (size_t)widths[i] * heights[i] * 3;
-            if (p.f.raw) {
-                memcpy(hin + rgb_off, streams[i], bytes);
-            } else {
-                st[f] = p.status;
-                memcpy(blob + at, streams[i], sizes[i]);
-                for (const Segment &s : p.segs) {
-                    Segment &d = segs[seg++];
-                    d = s;
-                    d.begin += (uint32_t)at; d.end += (uint32_t)at; d.frame = f;
-                }
-                at += (sizes[i] + 15) & ~(size_t)15;
-                coef_off += p.f.samples;
-                max_blocks = std::max(max_blocks, p.f.blocks);
-                max_pixels = std::max(max_pixels, (unsigned)widths[i] * (unsigned)heights[i]);
-            }
-            rgb_off += padded(bytes);
+            rgb_off += padded((size_t)widths[first + f] * heights[first + f] * 3);
         }
-        const size_t blob_bytes = padded(at);
-        memset(blob + at, 0, blob_bytes - at);
-        for (int w = 0; w < L.n_wg; ++w) {
-            const int lo = w * kEntropyLanes, hi = std::min(n_seg, lo + kEntropyLanes), s0 = frames[segs[lo].frame].tables;
-            bool same = true;
-            for (int j = lo + 1; j < hi && same; ++j) same = frames[segs[j].frame].tables == s0;
-            wg[w] = same ? s0 : -1;
-        }
-        if (split) {
-            // the workgroups of k_jpegdec_split: consecutive segments of one frame, at least two subsequences each, filled up to
-            // kSplitMaxSub subsequences / kSplitWgSegs segments
-            SplitSeg *sseg = reinterpret_cast<SplitSeg *>(blob + L.sseg_off);
-            SplitWg *swg = reinterpret_cast<SplitWg *>(blob + L.swg_off);
-            int n_ss = 0;
-            for (int f = 0; f < nf; ++f) {
-                SplitWg cur = {n_ss, 0, 0, 0};
-                for (int j = frames[f].first_seg; j < frames[f].first_seg + (frames[f].raw ? 0 : frames[f].n_seg); ++j) {
-                    const SplitPlan sp = split_plan(blob, segs[j], split);
-                    if (sp.n_sub < 2) { split_info[3] += 1; continue; }
-                    if (cur.n == kSplitWgSegs || cur.n_tasks + sp.n_sub > kSplitMaxSub) {
-                        swg[L.n_swg++] = cur;
-                        cur = SplitWg{n_ss, 0, 0, 0};
-                    }
-                    sseg[n_ss++] = SplitSeg{sp.data_end, j, sp.sub, sp.n_sub, cur.n_tasks, {0, 0, 0}};
-                    ++cur.n; cur.n_tasks += sp.n_sub; cur.rounds = std::max(cur.rounds, sp.n_sub - 1);
-                    split_info[0] += sp.n_sub;
-                }
-                if (cur.n) swg[L.n_swg++] = cur;
-            }
-        }
+        if ((rc = y2_jpegdec_stage(dec.get(), k, slot[(size_t)b].data(), hin))) { cleanup(); return rc; }
         LetterboxItem *items = reinterpret_cast<LetterboxItem *>(hin);
         for (int f = 0; f < batch; ++f) {   // a partial last chunk repeats its last image
             const int i = std::min(f, nf - 1);
@@ -363,47 +525,15 @@ int run_jpeg(yolo2_hip_ctx *c, int precision, const uint8_t *const *streams, con
             if ((rc = y2_letterbox_args(widths[first + i], heights[first + i], 3, 416, 416, items[f].a, true))) { cleanup(); return rc; }
         }
         if (want_dets && (rc = y2_post_fill_geom(P.hgeom[b].get(), cw.data(), chh.data(), batch))) { cleanup(); return rc; }
-        // ---- uploads
-        Y2_TRY(hipMemcpyAsync(P.djpg[b].get(), blob, blob_bytes, hipMemcpyHostToDevice, P.s_in), YOLO2_DMA_ERROR);
+        // ---- the other uploads
         Y2_TRY(hipMemcpyAsync(P.dbytes[b].get(), hin, table_bytes, hipMemcpyHostToDevice, P.s_in), YOLO2_DMA_ERROR);
-        for (int f = 0; f < nf; ++f)
-            if (parsed[(size_t)(first + f)].f.raw) {
-                const size_t o = slot[(size_t)b][(size_t)f];
-                Y2_TRY(hipMemcpyAsync(P.dbytes[b].get() + o, hin + o, (size_t)widths[first + f] * heights[first + f] * 3, hipMemcpyHostToDevice, P.s_in),
-                       YOLO2_DMA_ERROR);
-            }
+        if ((rc = y2_jpegdec_upload_raw(dec.get(), k, slot[(size_t)b].data(), hin))) { cleanup(); return rc; }
         if (want_dets) Y2_TRY(hipMemcpyAsync(P.post[b].geom.get(), P.hgeom[b].get(), (size_t)batch * gbytes, hipMemcpyHostToDevice, P.s_in), YOLO2_DMA_ERROR);
         Y2_TRY(hipEventRecord(P.e_in[b], P.s_in), YOLO2_ERROR);
         Y2_TRY(hipStreamWaitEvent(P.s_run, P.e_in[b], 0), YOLO2_ERROR);
+        up_tables += (double)table_bytes;
         // ---- the decoder
-        JpegDecArgs a;
-        a.blob = P.djpg[b].get();
-        a.frames_off = 0; a.segs_off = L.segs_off; a.wg_off = L.wg_off; a.status_off = L.status_off; a.tables_off = L.tables_off;
-        a.n_frames = nf; a.n_seg = n_seg;
-        a.coef = P.jcoef.get(); a.planes = P.jplanes.get(); a.rgb = P.dbytes[b].get();
-        stamp(k, 0);
-        if (coef_off) Y2_TRY(hipMemsetAsync(P.jcoef.get(), 0, coef_off * sizeof(int16_t), P.s_run), YOLO2_ERROR);
-        stamp(k, 1);
-        if (split && n_seg) {
-            JpegSplitArgs sa;
-            sa.seg_off = L.sseg_off; sa.wg_off = L.swg_off; sa.word_off = L.status_off + (uint32_t)((size_t)(nf + n_seg) * sizeof(int));
-            if (L.n_swg) hipLaunchKernelGGL(k_jpegdec_split, dim3((unsigned)L.n_swg), dim3(kSplitThreads), 0, P.s_run, a, sa);
-            if (!prof.e.empty()) (void)hipEventRecord(prof.e[(size_t)(chunks * 5 + k)], P.s_run);
-            hipLaunchKernelGGL(k_jpegdec_rest, dim3((unsigned)L.n_wg), dim3(kEntropyLanes), 0, P.s_run, a, sa);
-        } else if (n_seg) {
-            hipLaunchKernelGGL(k_jpegdec_entropy, dim3((unsigned)L.n_wg), dim3(kEntropyLanes), 0, P.s_run, a);
-        }
-        stamp(k, 2);
-        if (max_blocks) hipLaunchKernelGGL(k_jpegdec_idct, dim3(blocks_for(max_blocks, kIdctThreads), (unsigned)nf), dim3(kIdctThreads), 0, P.s_run, a);
-        stamp(k, 3);
-        if (max_blocks) hipLaunchKernelGGL(k_jpegdec_rgb, dim3(blocks_for((long)max_pixels, kRgbThreads), (unsigned)nf), dim3(kRgbThreads), 0, P.s_run, a);
-        if (max_pixels) hipLaunchKernelGGL(k_jpegdec_zero, dim3(64, (unsigned)nf), dim3(256), 0, P.s_run, a);
-        stamp(k, 4);
-        up_blob += (double)blob_bytes;
-        up_other += (double)table_bytes;
-        for (int f = 0; f < nf; ++f)
-            if (parsed[(size_t)(first + f)].f.raw) up_other += (double)widths[first + f] * heights[first + f] * 3;
-        Y2_TRY(hipGetLastError(), YOLO2_ERROR);
+        if ((rc = y2_jpegdec_launch(dec.get(), k))) { cleanup(); return rc; }
         // ---- behind it
         if (!want_dets) {
             Y2_TRY(hipEventRecord(P.e_run[b], P.s_run), YOLO2_ERROR);
@@ -434,29 +564,13 @@ int run_jpeg(yolo2_hip_ctx *c, int precision, const uint8_t *const *streams, con
             Y2_TRY(hipMemcpyAsync(P.hdets[b].get(), P.post[b].dets.get(), (size_t)batch * cap * sizeof(yolo2_hip_det), hipMemcpyDeviceToHost, P.s_out),
                    YOLO2_DMA_ERROR);
         }
-        Y2_TRY(hipMemcpyAsync(P.hjstatus[b].get(), P.djpg[b].get() + L.status_off, words * sizeof(int), hipMemcpyDeviceToHost, P.s_out),
-               YOLO2_DMA_ERROR);
+        if ((rc = y2_jpegdec_status_d2h(dec.get(), k, P.s_out))) { cleanup(); return rc; }
         Y2_TRY(hipEventRecord(P.e_out[b], P.s_out), YOLO2_ERROR);
     }
     for (int k = std::max(0, chunks - 2); k < chunks; ++k) drain(k);
     cleanup();
 #undef Y2_TRY
-    {
-        double *info = c->jpeg_dec_info;
-        for (int i = 0; i < 8; ++i) info[i] = 0;
-        for (int k = 0; k < chunks && !prof.e.empty(); ++k)
-            for (int i = 0; i < 4; ++i) {
-                float ms = 0.f;
-                if (hipEventElapsedTime(&ms, prof.e[(size_t)(k * 5 + i)], prof.e[(size_t)(k * 5 + i + 1)]) == hipSuccess) info[i] += ms / chunks;
-            }
-        info[4] = up_blob; info[5] = up_other; info[6] = chunks; info[7] = n;
-        for (int k = 0; k < chunks && split && !prof.e.empty(); ++k) {
-            float ms = 0.f;
-            if (hipEventElapsedTime(&ms, prof.e[(size_t)(k * 5 + 1)], prof.e[(size_t)(chunks * 5 + k)]) == hipSuccess) split_info[6] += ms / chunks;
-            if (hipEventElapsedTime(&ms, prof.e[(size_t)(chunks * 5 + k)], prof.e[(size_t)(k * 5 + 2)]) == hipSuccess) split_info[7] += ms / chunks;
-        }
-        memcpy(c->jpeg_split_info, split_info, sizeof(split_info));
-    }
+    y2_jpegdec_close(dec.get(), up_tables);
     if (want_dets && i16 && final_q) *final_q = q;
     if (first_bad >= 0)
         return fail(YOLO2_ERROR, "frame %d: the GPU decoder flagged its scan (status %d); it is zero-filled, decode it on the host", first_bad, status[first_bad]);

@@ -20,10 +20,25 @@
 // s_out, which keeps chunks in order.  (3) With JPEG out the sizes come back first; the host reads them and queues ONE copy of the
 // bytes in use.  That copy for chunk k - 1 is queued on s_out BEFORE s_out is made to wait for chunk k's network, so it runs while the
 // network does, and the work area's sizes are copied out before chunk k's encoder (same stream) overwrites them.
+//
+// From JPEG streams (yolo2_hip_loop_images_jpeg): the same loop with the decoder stage of yolo2_jpegdec.hip (y2_jpegdec.hpp) in front of
+// the network.  The staging buffer keeps its layout, but a frame that arrives as a stream is not staged: its slot in dbytes[b] is
+// written by k_jpegdec_rgb (k_jpegdec_zero for a flagged scan), and the front kernel, the painter and the encoder read it there.
+//   s_in    the chunk's blob (descriptors, tables, streams) -> djpg[b]; tables in front of the slots, the caller's raw frames each
+//           into its slot, and with JPEG out the encoder's table behind the slots -> dbytes[b]
+//   s_run   coefficient memset, entropy stage (option jpegdec_split: two launches), k_jpegdec_idct, _rgb, _zero; then the network
+//   s_out   as above, with the decoder's status words copied out behind the records
+// (1) holds unchanged and now also covers the decoder: it WRITES the slots of dbytes[b] on s_run, and chunk k + 2 is staged and its
+// decoder enqueued only after deliver(k), so the painter of chunk k (s_out) has read them; djpg[b] and the pinned blob follow the same
+// rule (the status words of chunk k are copied out on s_out in front of e_out[b]).  (2) gains one line: the decoder's coefficient
+// and plane buffers exist once and are touched by kernels of s_run only, the stream that keeps the chunks' decoders and networks in
+// order (the int16 lanes' streams never see them).  (3) is unchanged.  A frame the decoder flags is painted and encoded like any
+// other (zero pixels), but nothing of it is handed out: status[f] != 0, counts[f] = drawn[f] = 0, sizes[f] = 0, out[f] untouched.
 #include "y2_internal.hpp"
 #include "letterbox.hpp"
 #include "y2_draw.hpp"
 #include "y2_jpeg.hpp"
+#include "y2_jpegdec.hpp"
 
 using namespace y2;
 
@@ -70,16 +85,14 @@ extern "C" int yolo2_hip_loop_last_info(yolo2_hip_ctx *c, yolo2_hip_loop_info_t 
     return YOLO2_SUCCESS;
 }
 
-extern "C" int yolo2_hip_loop_images_pix(yolo2_hip_ctx *c, int precision, const uint8_t *const *images, const int *widths, const int *heights,
-                                         int pixfmt, int n, int batch, float thresh, float nms, int flags, yolo2_hip_det *dets, int cap,
-                                         int *counts, int *final_q, const char *const *labels, int n_labels, int out_format, int quality,
-                                         uint8_t *const *out, const size_t *caps, size_t *sizes, int *drawn)
+// The chunk loop of both loop entries.  dec == nullptr: images are frames of pixfmt, staged and uploaded whole.  Otherwise: images are
+// the streams (and raw RGB24 frames) the decoder stage dec has the headers of, and status [n] receives its words.
+static int loop_run(yolo2_hip_ctx *c, int precision, const uint8_t *const *images, const int *widths, const int *heights, int pixfmt, int n, int batch,
+                    float thresh, float nms, int flags, yolo2_hip_det *dets, int cap, int *counts, int *final_q, const char *const *labels, int n_labels,
+                    int out_format, int quality, uint8_t *const *out, const size_t *caps, size_t *sizes, int *drawn, Y2JpegDec *dec, int *status,
+                    const size_t *stream_bytes)
 {
-    if (!c) return fail(YOLO2_ERROR, "loop: null argument");
     int rc;
-    if ((rc = y2_loop_check(precision, images, widths, heights, pixfmt, n, batch, thresh, flags, dets, cap, counts, n_labels, out_format, quality, out,
-                            caps, sizes)))
-        return rc;
     const bool i16 = precision == YOLO2_LOOP_INT16, jpeg = out_format == YOLO2_LOOP_OUT_JPEG;
     const int split = precision == YOLO2_LOOP_F32TOL ? 1 : 0, ch = y2_pix_channels(pixfmt), app_tail = (flags & YOLO2_DETS_APP_TAIL) ? 1 : 0;
     const bool yuyv = ch == 2;
@@ -115,8 +128,10 @@ extern "C" int yolo2_hip_loop_images_pix(yolo2_hip_ctx *c, int precision, const 
         cap_in = std::max(cap_in, in);
         cap_rgb = std::max(cap_rgb, rgb);
     }
+    if (dec && (rc = y2_jpegdec_plan(dec, batch))) return rc;
     if (i16 && batch != c->batch && (rc = yolo2_hip_set_batch(c, batch))) return rc;
     if ((rc = y2_pipe_ensure(c->pipe, cap_in, cap_in, batch, false)) || (rc = y2_pipe_ensure_post(c, batch, cap))) return rc;
+    if (dec && (rc = y2_jpegdec_ensure(dec))) return rc;     // (behind y2_pipe_ensure: growing that drops the decoder's buffers)
     if (!i16 && (rc = y2_pipe_ensure_regf(c->pipe, batch, false))) return rc;
     if ((rc = y2_loop_ensure(c, batch, cap, labels, n_labels))) return rc;
     // the product's buffers are the annotate entries': two sets of device + pinned RGB24 frames, or the painted frames and the
@@ -134,7 +149,7 @@ extern "C" int yolo2_hip_loop_images_pix(yolo2_hip_ctx *c, int precision, const 
     auto cleanup = [&]() { (void)hipDeviceSynchronize(); };
 #define Y2_TRY(expr, code) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { rc = fail(code, "%s failed: %s", #expr, hipGetErrorString(e_)); cleanup(); return rc; } } while (0)
 
-    int short_frame = -1, bad_frame = -1, q = 0;
+    int short_frame = -1, bad_frame = -1, flagged_frame = -1, q = 0;
     // fetch(k) (JPEG): wait for chunk k's sizes, queue one D2H of the stream bytes in use.  deliver(k): wait for chunk k's last copy and
     // hand everything out.
     auto fetch = [&](int k) -> int {
@@ -152,9 +167,17 @@ extern "C" int yolo2_hip_loop_images_pix(yolo2_hip_ctx *c, int precision, const 
         const int b = k & 1, nf = in_chunk(k), first = k * batch;
         Y2_TRY(hipEventSynchronize(P.e_out[b]), YOLO2_ERROR);
         memcpy(counts + first, P.hcounts[b].get(), (size_t)nf * sizeof(int));
+        if (dec) y2_jpegdec_collect(dec, k, status, &flagged_frame);
         size_t off = 0;
         for (int i = 0; i < nf; ++i) {
             const int f = first + i, cnt = std::min(std::max(P.hcounts[b].get()[i], 0), cap);
+            if (dec && status[f]) {   // a flagged scan: nothing of the frame is handed out; its bytes in the packed output are stepped over
+                counts[f] = 0;
+                if (drawn) drawn[f] = 0;
+                sizes[f] = 0;
+                off += jpeg ? std::min((size_t)J.hsizes[b].get()[i], caps[f]) : padded((size_t)widths[f] * heights[f] * 3);
+                continue;
+            }
             yolo2_hip_det *dst = dets + (size_t)f * cap;
             memcpy(dst, P.hdets[b].get() + (size_t)i * cap, (size_t)cnt * sizeof(yolo2_hip_det));
             for (int r = 0; r < cnt; ++r) dst[r].frame = f;   // frame numbers are global in the caller's records
@@ -181,6 +204,7 @@ extern "C" int yolo2_hip_loop_images_pix(yolo2_hip_ctx *c, int precision, const 
     std::vector<size_t> offs((size_t)batch), out_offs((size_t)batch), fbytes((size_t)batch);
     std::vector<int> cw((size_t)batch), chh((size_t)batch);
     std::vector<hipEvent_t> wait_for;   // what the tail of a chunk waits for
+    double up_tables = 0;               // (streams) bytes uploaded into dbytes[b] beside the raw frames
     for (int k = 0; k < chunks; ++k) {
         const int b = k & 1, nf = in_chunk(k), first = k * batch;
         // (buffer set b is free: chunk k - 2 was delivered in the round before - ordering (1) above)
@@ -194,9 +218,10 @@ extern "C" int yolo2_hip_loop_images_pix(yolo2_hip_ctx *c, int precision, const 
             jf[(size_t)i] = {widths[f], heights[f], out_off, caps[f]};
             off += padded(fbytes[(size_t)i]);
             out_off += padded((size_t)widths[f] * heights[f] * 3);
-            info.image_bytes_staged += fbytes[(size_t)i];
+            info.image_bytes_staged += dec && !y2_jpegdec_raw(dec, f) ? stream_bytes[f] : fbytes[(size_t)i];
         }
-        y2_stage_images(hin, images + first, offs.data(), fbytes.data(), nf);   // the frames, once
+        if (!dec) y2_stage_images(hin, images + first, offs.data(), fbytes.data(), nf);   // the frames, once
+        else if ((rc = y2_jpegdec_stage(dec, k, offs.data(), hin))) { cleanup(); return rc; }   // the blob (uploaded) and the raw frames
         LetterboxItem *items = reinterpret_cast<LetterboxItem *>(hin);
         for (int f = 0; f < batch; ++f) {   // a partial last chunk repeats its last image
             const int i = std::min(f, nf - 1);
@@ -211,12 +236,20 @@ extern "C" int yolo2_hip_loop_images_pix(yolo2_hip_ctx *c, int precision, const 
             off += plans[(size_t)k].table_bytes;
         }
         if ((rc = y2_post_fill_geom(P.hgeom[b].get(), cw.data(), chh.data(), batch))) { cleanup(); return rc; }
-        Y2_TRY(hipMemcpyAsync(P.dbytes[b].get(), hin, off, hipMemcpyHostToDevice, P.s_in), YOLO2_DMA_ERROR);   // the one upload
+        if (!dec) {
+            Y2_TRY(hipMemcpyAsync(P.dbytes[b].get(), hin, off, hipMemcpyHostToDevice, P.s_in), YOLO2_DMA_ERROR);   // the one upload
+            info.image_bytes_h2d += off;
+        } else {   // the tables around the slots and the raw frames; the slots of the streams are the decoder's to write
+            Y2_TRY(hipMemcpyAsync(P.dbytes[b].get(), hin, lead, hipMemcpyHostToDevice, P.s_in), YOLO2_DMA_ERROR);
+            if ((rc = y2_jpegdec_upload_raw(dec, k, offs.data(), hin))) { cleanup(); return rc; }
+            if (off > jtab) Y2_TRY(hipMemcpyAsync(P.dbytes[b].get() + jtab, hin + jtab, off - jtab, hipMemcpyHostToDevice, P.s_in), YOLO2_DMA_ERROR);
+            up_tables += (double)(lead + (off - jtab));
+        }
         Y2_TRY(hipMemcpyAsync(P.post[b].geom.get(), P.hgeom[b].get(), (size_t)batch * gbytes, hipMemcpyHostToDevice, P.s_in), YOLO2_DMA_ERROR);
         Y2_TRY(hipEventRecord(P.e_in[b], P.s_in), YOLO2_ERROR);
-        info.image_bytes_h2d += off;
         ++info.chunks;
         Y2_TRY(hipStreamWaitEvent(P.s_run, P.e_in[b], 0), YOLO2_ERROR);
+        if (dec && (rc = y2_jpegdec_launch(dec, k))) { cleanup(); return rc; }   // ---- the decoder, into the slots
         // ---- the network, by the code the _pix_dets entry of the precision runs it with
         if (i16) {
             rc = y2_pipe_enqueue_i16(c, b, yuyv, batch, &q, &wait_for);
@@ -234,6 +267,7 @@ extern "C" int yolo2_hip_loop_images_pix(yolo2_hip_ctx *c, int precision, const 
         if (rc) { cleanup(); return rc; }
         Y2_TRY(hipMemcpyAsync(P.hcounts[b].get(), P.post[b].counts.get(), (size_t)batch * sizeof(int), hipMemcpyDeviceToHost, P.s_out), YOLO2_DMA_ERROR);
         Y2_TRY(hipMemcpyAsync(P.hdets[b].get(), P.post[b].dets.get(), (size_t)batch * cap * sizeof(yolo2_hip_det), hipMemcpyDeviceToHost, P.s_out), YOLO2_DMA_ERROR);
+        if (dec && (rc = y2_jpegdec_status_d2h(dec, k, P.s_out))) { cleanup(); return rc; }
         if ((rc = y2_loop_enqueue_items(c, b, nf, cap, thresh, labels, n_labels, P.dbytes[b].get() + lb_bytes, P.post[b].dets.get(), P.post[b].counts.get(),
                                         P.s_out)) ||
             (rc = y2_loop_enqueue_paint(c, nf, max_strips, P.dbytes[b].get(), jpeg ? J.rgb.get() : A.dout[b].get(), P.s_out))) {
@@ -260,10 +294,83 @@ extern "C" int yolo2_hip_loop_images_pix(yolo2_hip_ctx *c, int precision, const 
     if (i16 && final_q) *final_q = q;
     if (!i16) c->images_l0[split] = fused ? std::string(y2_f16_images_kernel(run, yuyv))
                                           : std::string(yuyv ? "k_letterbox_yuyv_batch + " : "k_letterbox_u8_batch + ") + yolo2_hip_fp16_layer_kernel(run, 0);
+    if (dec) {
+        info.image_bytes_h2d = (uint64_t)(y2_jpegdec_uploaded(dec) + up_tables);
+        y2_jpegdec_close(dec, up_tables);
+    }
     c->loop_info = info;
+    if (flagged_frame >= 0)
+        return fail(YOLO2_ERROR, "loop: frame %d: the GPU decoder flagged its scan (status %d); nothing of it is returned, decode it on the host",
+                    flagged_frame, status[flagged_frame]);
     if (bad_frame >= 0)
         return fail(YOLO2_ERROR, "loop: frame %d has a record with a non-finite (or 2^23 and larger) prob among those to be drawn", bad_frame);
     if (short_frame >= 0)
         return fail(YOLO2_ERROR, "loop: output buffer too small for frame %d (%zu < %zu bytes)", short_frame, caps[short_frame], sizes[short_frame]);
     return YOLO2_SUCCESS;
+}
+
+extern "C" int yolo2_hip_loop_images_pix(yolo2_hip_ctx *c, int precision, const uint8_t *const *images, const int *widths, const int *heights,
+                                         int pixfmt, int n, int batch, float thresh, float nms, int flags, yolo2_hip_det *dets, int cap,
+                                         int *counts, int *final_q, const char *const *labels, int n_labels, int out_format, int quality,
+                                         uint8_t *const *out, const size_t *caps, size_t *sizes, int *drawn)
+{
+    if (!c) return fail(YOLO2_ERROR, "loop: null argument");
+    int rc;
+    if ((rc = y2_loop_check(precision, images, widths, heights, pixfmt, n, batch, thresh, flags, dets, cap, counts, n_labels, out_format, quality, out,
+                            caps, sizes)))
+        return rc;
+    return loop_run(c, precision, images, widths, heights, pixfmt, n, batch, thresh, nms, flags, dets, cap, counts, final_q, labels, n_labels, out_format,
+                    quality, out, caps, sizes, drawn, nullptr, nullptr, nullptr);
+}
+
+// Everything the loop entry from streams refuses that can be seen without a device: the probe's refusals, then - on the sizes the
+// headers give, left in wh (widths, then heights) - y2_loop_check's.  Touches none of the caller's arrays.  c == nullptr: the check
+// alone (the multi entry, before it starts a shard).
+static int loop_jpeg_open(yolo2_hip_ctx *c, int precision, const uint8_t *const *streams, const size_t *stream_sizes, const int *widths,
+                          const int *heights, int n, int batch, float thresh, int flags, const yolo2_hip_det *dets, int cap, const int *counts,
+                          int n_labels, int out_format, int quality, uint8_t *const *out, const size_t *caps, const size_t *sizes, const int *status,
+                          std::vector<int> &wh, Y2JpegDecPtr *dec)
+{
+    if (!streams || !stream_sizes || !widths || !heights || !status) return fail(YOLO2_ERROR, "loop: null argument");
+    if (precision == YOLO2_JPEG_INT8) return fail(YOLO2_ERROR, "loop: the loop entries have no int8 form (YOLO2_LOOP_INT16, _FP16 or _F32TOL)");
+    if (n <= 0 || batch <= 0 || batch > 1024 || cap <= 0 || cap > 65536)
+        return fail(YOLO2_ERROR, "loop: bad image count %d / batch %d (1..1024) / capacity %d (1..65536)", n, batch, cap);
+    wh.assign(widths, widths + n);
+    wh.insert(wh.end(), heights, heights + n);
+    int rc;
+    if ((rc = y2_jpegdec_open(c, streams, stream_sizes, wh.data(), wh.data() + n, n, true, nullptr, dec))) return rc;
+    return y2_loop_check(precision, streams, wh.data(), wh.data() + n, YOLO2_PIX_RGB24, n, batch, thresh, flags, dets, cap, counts, n_labels, out_format,
+                         quality, out, caps, sizes);
+}
+
+// (y2_draw.hpp)
+int y2_loop_jpeg_check(int precision, const uint8_t *const *streams, const size_t *stream_sizes, const int *widths, const int *heights, int n, int batch,
+                       float thresh, int flags, const yolo2_hip_det *dets, int cap, const int *counts, int n_labels, int out_format, int quality,
+                       uint8_t *const *out, const size_t *caps, const size_t *sizes, const int *status)
+{
+    std::vector<int> wh;
+    Y2JpegDecPtr dec;
+    return loop_jpeg_open(nullptr, precision, streams, stream_sizes, widths, heights, n, batch, thresh, flags, dets, cap, counts, n_labels, out_format,
+                          quality, out, caps, sizes, status, wh, &dec);
+}
+
+extern "C" int yolo2_hip_loop_images_jpeg(yolo2_hip_ctx *c, int precision, const uint8_t *const *streams, const size_t *stream_sizes, int *widths,
+                                          int *heights, int n, int batch, float thresh, float nms, int flags, yolo2_hip_det *dets, int cap,
+                                          int *counts, int *final_q, const char *const *labels, int n_labels, int out_format, int quality,
+                                          uint8_t *const *out, const size_t *caps, size_t *sizes, int *drawn, int *status)
+{
+    if (!c) return fail(YOLO2_ERROR, "loop: null argument");
+    std::vector<int> wh;
+    Y2JpegDecPtr dec;
+    int rc;
+    if ((rc = loop_jpeg_open(c, precision, streams, stream_sizes, widths, heights, n, batch, thresh, flags, dets, cap, counts, n_labels, out_format,
+                             quality, out, caps, sizes, status, wh, &dec)))
+        return rc;
+    // (the network's own refusals: loop_run's, here in front of the first write to the caller's arrays)
+    if (precision == YOLO2_LOOP_INT16 ? !c->weights_loaded : (!c->f16_loaded || !c->f16_plan || !c->wf32))
+        return fail(YOLO2_ERROR, precision == YOLO2_LOOP_INT16 ? "loop: int16 weights not loaded" : "loop: fp32 weights not loaded (yolo2_hip_load_weights_fp32)");
+    memcpy(widths, wh.data(), (size_t)n * sizeof(int));
+    memcpy(heights, wh.data() + n, (size_t)n * sizeof(int));
+    return loop_run(c, precision, streams, widths, heights, YOLO2_PIX_RGB24, n, batch, thresh, nms, flags, dets, cap, counts, final_q, labels, n_labels,
+                    out_format, quality, out, caps, sizes, drawn, dec.get(), status, stream_sizes);
 }

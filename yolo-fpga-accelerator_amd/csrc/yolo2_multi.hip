@@ -740,3 +740,67 @@ extern "C" int yolo2_hip_multi_annotate_images_pix_jpeg_host(yolo2_hip_multi *m,
                                                        quality, jpeg + lo, caps + lo, sizes + lo, drawn ? drawn + lo : nullptr);
     });
 }
+
+// the camera loop from JPEG streams (yolo2_hip_loop_images_jpeg), shard i decoded, run, painted and encoded by device i
+extern "C" int yolo2_hip_multi_loop_images_jpeg(yolo2_hip_multi *m, int precision, const uint8_t *const *streams, const size_t *stream_sizes,
+                                                int *widths, int *heights, int n, int batch_per_device, float thresh, float nms, int flags,
+                                                yolo2_hip_det *dets, int cap_per_frame, int *counts, int *final_q, const char *const *labels,
+                                                int n_labels, int out_format, int quality, uint8_t *const *out, const size_t *caps, size_t *sizes,
+                                                int *drawn, int *status)
+{
+    if (!m) return mfail(YOLO2_ERROR, "loop: null argument");
+    // the whole call is looked at before any shard starts (headers included)
+    const int rc = y2_loop_jpeg_check(precision, streams, stream_sizes, widths, heights, n, batch_per_device, thresh, flags, dets, cap_per_frame, counts,
+                                      n_labels, out_format, quality, out, caps, sizes, status);
+    if (rc) return rc;
+    std::vector<int> qs(m->ctx.size(), 0);
+    const int r = multi_run(m, n, [&](yolo2_hip_ctx *c, int lo, int hi) {
+        int qq = 0;
+        for (int f = lo; f < hi; ++f) counts[f] = 0;   // (a shard that is refused leaves no counts behind for the renumbering below)
+        const int r1 = yolo2_hip_loop_images_jpeg(c, precision, streams + lo, stream_sizes + lo, widths + lo, heights + lo, hi - lo,
+                                                  std::min(batch_per_device, hi - lo), thresh, nms, flags, dets + (size_t)lo * cap_per_frame,
+                                                  cap_per_frame, counts + lo, &qq, labels, n_labels, out_format, quality, out + lo, caps + lo,
+                                                  sizes + lo, drawn ? drawn + lo : nullptr, status + lo);
+        // records carry global frame indices (also where a shard returned an error with its frames complete)
+        for (int f = lo; f < hi; ++f)
+            for (int k = 0, cnt = std::min(std::max(counts[f], 0), cap_per_frame); k < cnt; ++k) dets[(size_t)f * cap_per_frame + k].frame = f;
+        for (size_t i = 0; i < m->ctx.size(); ++i)
+            if (m->ctx[i] == c) qs[i] = qq;
+        if (r1 && lo) return mfail(r1, "%s (frame numbers from %d, the shard's first)", yolo2_hip_last_error(), lo);
+        return r1;
+    });
+    if (final_q && precision == YOLO2_LOOP_INT16) *final_q = qs[0];   // (every device holds the same weights and Q tables; int16 only)
+    return r;
+}
+
+// streams -> records (yolo2_hip_run_images_jpeg_dets), shard i decoded and run by device i
+extern "C" int yolo2_hip_multi_run_images_jpeg_dets(yolo2_hip_multi *m, int precision, const uint8_t *const *streams, const size_t *stream_sizes,
+                                                    int *widths, int *heights, int n, int batch_per_device, float thresh, float nms, int flags,
+                                                    yolo2_hip_det *dets, int cap_per_frame, int *counts, int *final_q, int *status)
+{
+    if (!m || !streams || !stream_sizes || !widths || !heights || !dets || !counts || !status) return mfail(YOLO2_ERROR, "null argument");
+    if (n <= 0 || batch_per_device <= 0 || cap_per_frame <= 0) return mfail(YOLO2_ERROR, "bad image count / batch / capacity");
+    // the whole call is looked at before any shard starts: the probe's refusals
+    for (int i = 0; i < n; ++i) {
+        yolo2_hip_jpeg_info_t info;
+        if (!streams[i]) return mfail(YOLO2_ERROR, "frame %d: null stream", i);
+        if (stream_sizes[i] && yolo2_hip_jpeg_probe(streams[i], stream_sizes[i], &info) == YOLO2_SUCCESS && !info.gpu_decodable)
+            return mfail(YOLO2_ERROR, "frame %d: not GPU-decodable (reason %d: %s)", i, info.reason, yolo2_hip_jpeg_reason_name(info.reason));
+    }
+    std::vector<int> qs(m->ctx.size(), 0);
+    const int r = multi_run(m, n, [&](yolo2_hip_ctx *c, int lo, int hi) {
+        int qq = 0;
+        for (int f = lo; f < hi; ++f) counts[f] = 0;
+        const int r1 = yolo2_hip_run_images_jpeg_dets(c, precision, streams + lo, stream_sizes + lo, widths + lo, heights + lo, hi - lo,
+                                                      std::min(batch_per_device, hi - lo), thresh, nms, flags, dets + (size_t)lo * cap_per_frame,
+                                                      cap_per_frame, counts + lo, &qq, status + lo);
+        for (int f = lo; f < hi; ++f)   // records carry global frame indices
+            for (int k = 0, cnt = std::min(std::max(counts[f], 0), cap_per_frame); k < cnt; ++k) dets[(size_t)f * cap_per_frame + k].frame = f;
+        for (size_t i = 0; i < m->ctx.size(); ++i)
+            if (m->ctx[i] == c) qs[i] = qq;
+        if (r1 && lo) return mfail(r1, "%s (frame numbers from %d, the shard's first)", yolo2_hip_last_error(), lo);
+        return r1;
+    });
+    if (final_q && precision == YOLO2_LOOP_INT16) *final_q = qs[0];
+    return r;
+}

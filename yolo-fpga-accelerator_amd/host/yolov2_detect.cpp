@@ -117,7 +117,8 @@ void print_usage(const char *prog)
         "                        --video-mjpeg and --post gpu: baseline 1- and 3-component streams go to the device compressed and are decoded\n"
         "                        there (yolo2_hip_run_images_jpeg_dets); progressive / CMYK JPEG, PNG and PNM files are decoded on the pool and\n"
         "                        ride in the same call; a stream the GPU decoder flags is decoded on the host and run again.  Same log and\n"
-        "                        JSONL.  Not with --save-annotated-dir or --loop-gpu (the frames' pixels stay on the device)\n"
+        "                        JSONL.  With --save-annotated-dir only through --loop-gpu (yolo2_hip_loop_images_jpeg: the decoded frame is\n"
+        "                        painted and encoded where the decoder left it); same files\n"
         "  --max-frames <n>      Stop after n inference frames (default: all)\n"
         "  --infer-every <n>     Run inference on every n-th frame (default 1)\n"
         "  --jsonl <path>        One JSON record per frame (fields of the reference's --output-json)\n"
@@ -129,7 +130,8 @@ void print_usage(const char *prog)
         "                        encoded on the GPU (yolo2_hip_annotate_images_pix_jpeg_host); default ppm\n"
         "  --jpeg-quality <1..100>  quality of --annotated-format jpg (default 80)\n"
         "  --loop-gpu            with --annotate-gpu --save-annotated-dir and --post gpu: one accelerator call per chunk makes the records AND\n"
-        "                        the annotated frames from one upload (yolo2_hip_loop_images_pix); same log, JSONL and files\n"
+        "                        the annotated frames from one upload (yolo2_hip_loop_images_pix; with --decode gpu\n"
+        "                        yolo2_hip_loop_images_jpeg, from the compressed streams); same log, JSONL and files\n"
         "  --chunk-batches <n>   Batches per device and accelerator call (default 4)\n"
         "  --decode-split <bytes> With --decode gpu: many lanes per restart interval, one per <bytes> of entropy-coded data (option\n"
         "                        jpegdec_split: a multiple of 16 in 16..4096; for streams without restart markers).  Same records.\n"
@@ -261,9 +263,9 @@ AppConfig parse_args(int argc, char **argv)
         std::exit(1);
     }
     if (cfg.decode == "gpu" && (!(!cfg.input_list.empty() || !cfg.input_dir.empty() || !cfg.video_mjpeg.empty()) || cfg.post != "gpu" ||
-                                !cfg.save_dir.empty() || cfg.loop_gpu)) {
+                                (!cfg.save_dir.empty() && !cfg.loop_gpu))) {
         std::fprintf(stderr, "--decode gpu decodes the JPEG streams of --input-list, --input-dir or --video-mjpeg in front of --post gpu; "
-                             "not with --save-annotated-dir or --loop-gpu\n");
+                             "with --save-annotated-dir only through --loop-gpu (--annotate-gpu)\n");
         std::exit(1);
     }
     if (cfg.decode_split && cfg.decode != "gpu") {
@@ -853,32 +855,85 @@ void run_stream(AppConfig cfg)
                         const int cap = 845;
                         recs.resize((size_t)n * cap);
                         std::vector<int> counts((size_t)n);
+                        // (--decode gpu) streams the decoder flagged: decoded on the host like any file, to be run again as raw frames;
+                        // one that the host decoder cannot read either is skipped, as the reader skips such files
+                        auto host_decode_flagged = [&](const std::vector<int> &redo) {
+                            std::vector<int> again;
+                            for (int i : redo) {
+                                SrcFrame &fr = ck->frames[(size_t)i];
+                                try {
+                                    fr.img = y2h::decode_image(fr.jpeg.data(), fr.jpeg.size(), fr.source);
+                                    fr.jpeg.clear();
+                                    again.push_back(i);
+                                } catch (const std::exception &e) {
+                                    if (cfg.strict) throw std::runtime_error(fr.source + ": " + e.what());
+                                    ck->skipped.emplace_back(fr.frame_index, fr.source + ": " + e.what());
+                                    fr.frame_index = -1;      // dropped below
+                                }
+                            }
+                            return again;
+                        };
                         if (cfg.loop_gpu) {     // records and annotated frames from one call: the frames go up once
                             ck->annotated.resize((size_t)n);
-                            std::vector<uint8_t *> outs((size_t)n);
-                            std::vector<size_t> caps((size_t)n), sizes((size_t)n);
-                            for (int attempt = 0; attempt < 2; ++attempt) {     // (JPEG: room as below, a second call with the encoder's bound)
-                                for (int f = 0; f < n; ++f) {
-                                    const size_t raw = (size_t)ws[(size_t)f] * hs[(size_t)f] * 3, bound = yolo2_hip_jpeg_bound(ws[(size_t)f], hs[(size_t)f]);
-                                    caps[(size_t)f] = !annotate_jpg ? raw : attempt ? bound : std::min(bound, raw + 4096);
-                                    ck->annotated[(size_t)f].resize(caps[(size_t)f]);
-                                    outs[(size_t)f] = ck->annotated[(size_t)f].data();
-                                    sizes[(size_t)f] = 0;
+                            const int prec = f16 ? (split ? YOLO2_LOOP_F32TOL : YOLO2_LOOP_FP16) : YOLO2_LOOP_INT16;
+                            // one loop call over the frames `idx` of the chunk - with --decode gpu the streams go up compressed and the pool's
+                            // frames ride along as raw frames (size 0); returns the frames whose scan the GPU decoder flagged
+                            auto loop_call = [&](const std::vector<int> &idx) {
+                                const int m2 = (int)idx.size();
+                                std::vector<const uint8_t *> p2((size_t)m2);
+                                std::vector<size_t> s2((size_t)m2, 0), caps((size_t)m2), sizes((size_t)m2);
+                                std::vector<int> w2((size_t)m2), h2((size_t)m2), c2((size_t)m2), st2((size_t)m2, 0);
+                                std::vector<yolo2_hip_det> r2((size_t)m2 * cap);
+                                std::vector<uint8_t *> outs((size_t)m2);
+                                for (int k = 0; k < m2; ++k) {
+                                    const SrcFrame &fr = ck->frames[(size_t)idx[(size_t)k]];
+                                    p2[(size_t)k] = fr.jpeg.empty() ? fr.img.rgb.data() : fr.jpeg.data();
+                                    s2[(size_t)k] = fr.jpeg.size();
+                                    w2[(size_t)k] = fr.img.w; h2[(size_t)k] = fr.img.h;
                                 }
-                                const int rc = yolo2_hip_loop_images_pix(ctx, f16 ? (split ? YOLO2_LOOP_F32TOL : YOLO2_LOOP_FP16) : YOLO2_LOOP_INT16, ptrs.data(),
-                                                                         ws.data(), hs.data(), pixfmt, n, cfg.batch, cfg.thresh, cfg.nms, det_flags, recs.data(), cap,
-                                                                         counts.data(), &q, labels.data(), (int)labels.size(),
-                                                                         annotate_jpg ? YOLO2_LOOP_OUT_JPEG : YOLO2_LOOP_OUT_RGB24, cfg.jpeg_quality, outs.data(),
-                                                                         caps.data(), sizes.data(), nullptr);
-                                if (rc == YOLO2_SUCCESS) break;
-                                bool too_small = false;
-                                for (int f = 0; f < n; ++f) too_small = too_small || sizes[(size_t)f] > caps[(size_t)f];
-                                if (attempt || !annotate_jpg || !too_small) throw std::runtime_error(yolo2_hip_last_error());
-                            }
-                            for (int f = 0; f < n; ++f) {
-                                ck->annotated[(size_t)f].resize(sizes[(size_t)f]);
-                                ck->annotated[(size_t)f].shrink_to_fit();
-                            }
+                                for (int attempt = 0; attempt < 2; ++attempt) {     // (JPEG: room as below, a second call with the encoder's bound)
+                                    for (int k = 0; k < m2; ++k) {
+                                        std::vector<uint8_t> &a = ck->annotated[(size_t)idx[(size_t)k]];
+                                        const size_t raw = (size_t)w2[(size_t)k] * h2[(size_t)k] * 3, bound = yolo2_hip_jpeg_bound(w2[(size_t)k], h2[(size_t)k]);
+                                        caps[(size_t)k] = !annotate_jpg ? raw : attempt ? bound : std::min(bound, raw + 4096);
+                                        a.resize(caps[(size_t)k]);
+                                        outs[(size_t)k] = a.data();
+                                        sizes[(size_t)k] = 0;
+                                    }
+                                    const int fmt = annotate_jpg ? YOLO2_LOOP_OUT_JPEG : YOLO2_LOOP_OUT_RGB24;
+                                    const int rc = gpu_decode ? yolo2_hip_loop_images_jpeg(ctx, prec, p2.data(), s2.data(), w2.data(), h2.data(), m2, cfg.batch, cfg.thresh,
+                                                                                           cfg.nms, det_flags, r2.data(), cap, c2.data(), &q, labels.data(),
+                                                                                           (int)labels.size(), fmt, cfg.jpeg_quality, outs.data(), caps.data(),
+                                                                                           sizes.data(), nullptr, st2.data())
+                                                              : yolo2_hip_loop_images_pix(ctx, prec, p2.data(), w2.data(), h2.data(), pixfmt, m2, cfg.batch, cfg.thresh,
+                                                                                          cfg.nms, det_flags, r2.data(), cap, c2.data(), &q, labels.data(),
+                                                                                          (int)labels.size(), fmt, cfg.jpeg_quality, outs.data(), caps.data(),
+                                                                                          sizes.data(), nullptr);
+                                    if (rc == YOLO2_SUCCESS) break;
+                                    bool too_small = false, flagged = false;
+                                    for (int k = 0; k < m2; ++k) {
+                                        too_small = too_small || sizes[(size_t)k] > caps[(size_t)k];
+                                        flagged = flagged || st2[(size_t)k] != 0;
+                                    }
+                                    if (!attempt && annotate_jpg && too_small) continue;
+                                    if (too_small || !flagged) throw std::runtime_error(yolo2_hip_last_error());
+                                    break;     // (complete but for the flagged frames)
+                                }
+                                std::vector<int> redo;
+                                for (int k = 0; k < m2; ++k) {
+                                    const int i = idx[(size_t)k];
+                                    if (st2[(size_t)k]) { redo.push_back(i); continue; }
+                                    counts[(size_t)i] = c2[(size_t)k];
+                                    std::copy(r2.begin() + (long)k * cap, r2.begin() + (long)k * cap + std::min(c2[(size_t)k], cap), recs.begin() + (long)i * cap);
+                                    ck->annotated[(size_t)i].resize(sizes[(size_t)k]);
+                                    ck->annotated[(size_t)i].shrink_to_fit();
+                                }
+                                return redo;
+                            };
+                            std::vector<int> all((size_t)n);
+                            for (int i = 0; i < n; ++i) all[(size_t)i] = i;
+                            const std::vector<int> again = host_decode_flagged(loop_call(all));
+                            if (!again.empty() && !loop_call(again).empty()) throw std::runtime_error("a raw frame came back flagged by the JPEG decoder");
                         } else if (gpu_decode) {
                             // streams the GPU decoder takes go up compressed, the pool's frames ride along as raw frames (size 0)
                             const int prec = i8 ? YOLO2_JPEG_INT8 : f16 ? (split ? YOLO2_LOOP_F32TOL : YOLO2_LOOP_FP16) : YOLO2_LOOP_INT16;
@@ -895,19 +950,7 @@ void run_stream(AppConfig cfg)
                             for (int i = 0; i < n; ++i) if (status[(size_t)i]) redo.push_back(i);
                             if (rc != YOLO2_SUCCESS && redo.empty()) throw std::runtime_error(yolo2_hip_last_error());
                             // a stream the decoder flagged: decoded on the host like any file, and run again as a raw frame
-                            std::vector<int> again;
-                            for (int i : redo) {
-                                SrcFrame &fr = ck->frames[(size_t)i];
-                                try {
-                                    fr.img = y2h::decode_image(fr.jpeg.data(), fr.jpeg.size(), fr.source);
-                                    fr.jpeg.clear();
-                                    again.push_back(i);
-                                } catch (const std::exception &e) {
-                                    if (cfg.strict) throw std::runtime_error(fr.source + ": " + e.what());
-                                    ck->skipped.emplace_back(fr.frame_index, fr.source + ": " + e.what());
-                                    fr.frame_index = -1;      // dropped below
-                                }
-                            }
+                            const std::vector<int> again = host_decode_flagged(redo);
                             if (!again.empty()) {
                                 const int m2 = (int)again.size();
                                 std::vector<const uint8_t *> p2((size_t)m2);
@@ -995,6 +1038,7 @@ void run_stream(AppConfig cfg)
                         if (ck->frames[(size_t)f].frame_index < 0) {
                             ck->frames.erase(ck->frames.begin() + f);
                             ck->dets.erase(ck->dets.begin() + f);
+                            if (!ck->annotated.empty()) ck->annotated.erase(ck->annotated.begin() + f);
                         }
                     ck->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() - t_annotate;
                     accel_s[(size_t)slot] += ck->seconds;

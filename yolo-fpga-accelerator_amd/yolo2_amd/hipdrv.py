@@ -66,6 +66,7 @@ EXPORTS = [
     "yolo2_hip_run_images_pix_int8_host", "yolo2_hip_run_images_pix_dets_int8", "yolo2_hip_images_front_kernel_int8",
     "yolo2_hip_jpeg_probe", "yolo2_hip_jpeg_reason_name", "yolo2_hip_decode_jpeg_host", "yolo2_hip_decode_jpeg_ref",
     "yolo2_hip_run_images_jpeg_dets", "yolo2_hip_jpeg_last_info", "yolo2_hip_decode_jpeg_split_ref", "yolo2_hip_jpeg_split_info",
+    "yolo2_hip_loop_images_jpeg", "yolo2_hip_multi_loop_images_jpeg", "yolo2_hip_multi_run_images_jpeg_dets",
 ]
 
 # include/yolo2_hip.h YOLO2_PIX_*: the pixfmt argument of the _pix entries ("yuyv": packed YUYV 4:2:2, arrays uint8 [h][w][2])
@@ -325,7 +326,11 @@ def lib():
     sig("yolo2_hip_jpeg_last_info", [vp, vp])
     sig("yolo2_hip_decode_jpeg_split_ref", [vp, C.c_size_t, C.c_int, vp, C.c_size_t, pi32, pi32, pi32, vp])
     sig("yolo2_hip_jpeg_split_info", [vp, vp])
-    sig("yolo2_hip_run_images_jpeg_dets", [vp, i32, vp, vp, vp, vp, i32, i32, C.c_float, C.c_float, i32, vp, i32, vp, pi32, vp])
+    for name in ("run_images_jpeg_dets", "multi_run_images_jpeg_dets"):
+        sig("yolo2_hip_" + name, [vp, i32, vp, vp, vp, vp, i32, i32, C.c_float, C.c_float, i32, vp, i32, vp, pi32, vp])
+    # the camera loop from JPEG streams: the records entry's list up to final_q, then the loop's from labels on, then status
+    for name in ("loop_images_jpeg", "multi_loop_images_jpeg"):
+        sig("yolo2_hip_" + name, [vp, i32, vp, vp, vp, vp, i32, i32, C.c_float, C.c_float, i32, vp, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp])
     _lib = L
     return L
 
@@ -563,6 +568,12 @@ class Yolo2Hip:
                        cap: int = 845, best_class: bool = True, strict: bool = True):
         """see run_jpegs_dets"""
         return run_jpegs_dets(self._h, streams, batch, thresh, nms, cap=cap, best_class=best_class, precision=precision, tail=tail, strict=strict)
+
+    def loop_jpegs(self, streams, precision: str = "int16", tail: str = "core", thresh: float = 0.24, nms: float = 0.45, labels=None,
+                   jpeg_quality=None, batch: int = 64, cap: int = 845, strict: bool = True):
+        """the camera loop as one call from JPEG streams (module-level loop_jpegs)"""
+        return loop_jpegs(self._h, streams, precision=precision, tail=tail, thresh=thresh, nms=nms, labels=labels, jpeg_quality=jpeg_quality,
+                          batch=batch, cap=cap, strict=strict)
 
     def loop_last_info(self) -> dict:
         return loop_last_info(self._h)
@@ -1216,14 +1227,9 @@ def jpeg_decode(handle, streams, batch: int = 64, strict: bool = True):
     return [o[:hs[i], :ws[i]] for i, o in enumerate(outs)], status
 
 
-def run_jpegs_dets(handle, streams, batch: int, thresh: float, nms: float, cap: int = 845, best_class: bool = True, precision: str = "int16",
-                   tail: str = "core", strict: bool = True):
-    """yolo2_hip_run_images_jpeg_dets: JPEG streams (bytes) - or, mixed in, raw frames (uint8 [h][w][3] arrays, e.g. decoded on the
-    host) - -> detection records, the decoder and the network on the device.  Returns run_images_dets' dictionary plus "status"
-    (int32 [n], not 0: the decoder flagged the frame, its counts are 0) and "sizes" ([n] (w, h))."""
-    if precision not in JPEG_PRECISIONS:
-        raise ValueError(f"precision must be one of {tuple(JPEG_PRECISIONS)}, not {precision!r}")
-    app_tail = _check_tail(tail)
+def _mixed_stream_args(streams):
+    """streams (bytes) and raw frames (uint8 [h][w][3] arrays) -> (n, pointers, sizes - 0 for a raw frame -, widths, heights, what keeps
+    the buffers alive): the argument lists of the entries that take JPEG streams with raw frames mixed in"""
     keep, n = [], len(streams)
     ptrs, sizes = (C.c_void_p * n)(), (C.c_size_t * n)()
     ws, hs = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
@@ -1238,15 +1244,30 @@ def run_jpegs_dets(handle, streams, batch: int, thresh: float, nms: float, cap: 
             b = C.create_string_buffer(bytes(s), len(s))
             keep.append(b)
             ptrs[i], sizes[i] = C.addressof(b), len(s)
+    return n, ptrs, sizes, ws, hs, keep
+
+
+def run_jpegs_dets(handle, streams, batch: int, thresh: float, nms: float, cap: int = 845, best_class: bool = True, precision: str = "int16",
+                   tail: str = "core", strict: bool = True, multi: bool = False):
+    """yolo2_hip_run_images_jpeg_dets / its multi form: JPEG streams (bytes) - or, mixed in, raw frames (uint8 [h][w][3] arrays, e.g. decoded on the
+    host) - -> detection records, the decoder and the network on the device.  Returns run_images_dets' dictionary plus "status"
+    (int32 [n], not 0: the decoder flagged the frame, its counts are 0) and "sizes" ([n] (w, h))."""
+    if precision not in JPEG_PRECISIONS:
+        raise ValueError(f"precision must be one of {tuple(JPEG_PRECISIONS)}, not {precision!r}")
+    app_tail = _check_tail(tail)
+    if multi and precision == "int8":
+        raise ValueError("the multi-GPU entries have no int8 form")
+    n, ptrs, sizes, ws, hs, _keep = _mixed_stream_args(streams)
     dets = np.zeros((n, cap), dtype=DET_DTYPE)
     counts, status = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
     flags = (DETS_BEST_CLASS if best_class else 0) | (DETS_APP_TAIL if app_tail else 0)
     q = C.c_int(0)
     vp = lambda a: a.ctypes.data_as(C.c_void_p)
-    rc = lib().yolo2_hip_run_images_jpeg_dets(handle, JPEG_PRECISIONS[precision], ptrs, sizes, vp(ws), vp(hs), n, batch, thresh, nms, flags, vp(dets),
-                                              cap, vp(counts), C.byref(q), vp(status))
+    name = f"yolo2_hip_{'multi_' if multi else ''}run_images_jpeg_dets"
+    rc = getattr(lib(), name)(handle, JPEG_PRECISIONS[precision], ptrs, sizes, vp(ws), vp(hs), n, batch, thresh, nms, flags, vp(dets),
+                              cap, vp(counts), C.byref(q), vp(status))
     if rc != YOLO2_SUCCESS and (strict or not status.any()):
-        check(rc, "yolo2_hip_run_images_jpeg_dets")
+        check(rc, name)
     return {"dets": [dets[f, :min(int(counts[f]), cap)] for f in range(n)], "counts": counts, "final_q": q.value if precision == "int16" else None,
             "status": status, "sizes": [(int(ws[i]), int(hs[i])) for i in range(n)]}
 
@@ -1507,6 +1528,72 @@ def loop_images(handle, images, pixfmt=None, precision: str = "int16", tail: str
             "final_q": q if precision == "int16" else None, "frames": frames, "drawn": drawn}
 
 
+def loop_jpegs_raw(handle, streams, precision, flags, thresh, nms, batch, cap, labels, out_format, quality, caps, multi=False, guard=0):
+    """The loop entries from JPEG streams as they are: caps [n] bytes of room per frame -> (return code, dets [n][cap], counts,
+    final_q, list of uint8 [caps[f] + guard] buffers, sizes [n], records drawn [n], status [n], widths, heights).  With a guard every
+    output is a canary before the call: the buffers' and the records' bytes 0xA5, counts / drawn / status / widths / heights of the
+    streams -77, sizes 2^40 + 7."""
+    n, ptrs, ssizes, ws, hs, _keep = _mixed_stream_args(streams)
+    dets = np.zeros((n, cap), dtype=DET_DTYPE)
+    counts, drawn, status = (np.full(n, -77 if guard else 0, dtype=np.int32) for _ in range(3))
+    sizes = np.full(n, (1 << 40) + 7 if guard else 0, dtype=np.uint64)
+    if guard:
+        dets.view(np.uint8)[...] = 0xA5
+        for i in range(n):
+            if ssizes[i]:
+                ws[i] = hs[i] = -77
+    lab, n_labels, _keepl = _label_args(labels)
+    caps = np.ascontiguousarray(caps, dtype=np.uint64)
+    outs = [np.full(int(caps[f]) + guard, 0xA5, dtype=np.uint8) if guard else np.empty(int(caps[f]), dtype=np.uint8) for f in range(n)]
+    optrs = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
+    q = C.c_int(0)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    name = f"yolo2_hip_{'multi_' if multi else ''}loop_images_jpeg"
+    rc = getattr(lib(), name)(handle, precision, ptrs, ssizes, vp(ws), vp(hs), n, batch, thresh, nms, flags, vp(dets), cap, vp(counts), C.byref(q),
+                              lab, n_labels, out_format, quality, optrs, vp(caps), vp(sizes), vp(drawn), vp(status))
+    return rc, dets, counts, q.value, outs, sizes, drawn, status, ws, hs
+
+
+def loop_jpegs(handle, streams, precision: str = "int16", tail: str = "core", thresh: float = 0.24, nms: float = 0.45, labels=None,
+               jpeg_quality=None, batch: int = 64, cap: int = 845, multi: bool = False, strict: bool = True):
+    """yolo2_hip_loop_images_jpeg / its multi form: the camera loop as one call from JPEG streams (bytes) - or, mixed in, raw frames
+    (uint8 [h][w][3] arrays, e.g. decoded on the host) - with the decoder, the network, the painter and the encoder on the device.
+    Returns loop_images' dictionary plus "status" (int32 [n]; not 0: the decoder flagged the frame, its counts and drawn are 0 and
+    its frame is None) and "sizes" ([n] (w, h)).  A flagged frame raises under strict."""
+    if precision not in LOOP_PRECISIONS:
+        raise ValueError(f"precision must be one of {tuple(LOOP_PRECISIONS)}, not {precision!r} (the loop entries have no int8 form)")
+    flags = DETS_BEST_CLASS | (DETS_APP_TAIL if _check_tail(tail) else 0)
+    shapes = []
+    for i, s in enumerate(streams):
+        if isinstance(s, np.ndarray):
+            shapes.append((s.shape[0], s.shape[1]))
+        else:
+            info = jpeg_probe(s)
+            shapes.append((max(info["height"], 0), max(info["width"], 0)))
+    jpeg = jpeg_quality is not None
+    if jpeg:
+        caps = [min(jpeg_bound(s[1], s[0]), s[0] * s[1] * 3 + 4096) if s[0] and s[1] else 0 for s in shapes]
+    else:
+        caps = [s[0] * s[1] * 3 for s in shapes]
+    name = f"yolo2_hip_{'multi_' if multi else ''}loop_images_jpeg"
+    for attempt in range(2):
+        rc, dets, counts, q, outs, sizes, drawn, status, ws, hs = loop_jpegs_raw(handle, streams, LOOP_PRECISIONS[precision], flags, thresh, nms, batch,
+                                                                                 cap, labels, int(jpeg), int(jpeg_quality) if jpeg else 0, caps,
+                                                                                 multi=multi)
+        if rc == YOLO2_SUCCESS or attempt or not jpeg or not any(int(sizes[f]) > caps[f] for f in range(len(caps))):
+            break
+        caps = [jpeg_bound(s[1], s[0]) for s in shapes]   # (the rare frame that compresses to more than its raw size)
+    if rc != YOLO2_SUCCESS and (strict or not status.any()):
+        check(rc, name)
+    n = len(outs)
+    if jpeg:
+        frames = [None if status[f] else outs[f][:int(sizes[f])].tobytes() for f in range(n)]
+    else:
+        frames = [None if status[f] else outs[f].reshape(shapes[f][0], shapes[f][1], 3) for f in range(n)]
+    return {"dets": [dets[f, :min(int(counts[f]), cap)] for f in range(n)], "counts": counts, "final_q": q if precision == "int16" else None,
+            "frames": frames, "drawn": drawn, "status": status, "sizes": [(int(ws[i]), int(hs[i])) for i in range(n)]}
+
+
 def draw_items_dev(ctx_handle, dets, counts, widths, heights, thresh: float, labels=None):
     """yolo2_hip_draw_items_dev, the test doorway to k_draw_items: dets DET_DTYPE [n][cap] and counts [n] are uploaded, the kernel makes
     the draw items -> (return code, items uint8 [n][cap][item size], n_items [n], unprintable [n])."""
@@ -1674,3 +1761,11 @@ class Yolo2HipMulti:
     def loop_images(self, images, batch_per_device: int = 64, **kw):
         """the camera loop as one call, shard i on device i (module-level loop_images)"""
         return loop_images(self._m, images, batch=batch_per_device, multi=True, **kw)
+
+    def loop_jpegs(self, streams, batch_per_device: int = 64, **kw):
+        """the camera loop as one call from JPEG streams, shard i on device i (module-level loop_jpegs)"""
+        return loop_jpegs(self._m, streams, batch=batch_per_device, multi=True, **kw)
+
+    def run_jpegs_dets(self, streams, batch_per_device: int = 64, thresh: float = 0.24, nms: float = 0.45, **kw):
+        """JPEG streams -> records, shard i decoded and run by device i (module-level run_jpegs_dets)"""
+        return run_jpegs_dets(self._m, streams, batch_per_device, thresh, nms, multi=True, **kw)
