@@ -505,11 +505,30 @@ const char *yolo2_hip_images_layer0_kernel(yolo2_hip_ctx *ctx, int split);
  *                                        R = (298 c + 409 e + 128) >> 8
  *                                        G = (298 c - 100 d - 208 e + 128) >> 8
  *                                        B = (298 c + 516 d + 128) >> 8
- * A call is one format.  An odd YUYV width or an unknown pixfmt is YOLO2_ERROR (yolo2_hip_last_error names it) before anything is
- * launched; yolo2_hip_letterbox_pix also wants a YUYV image_dev on a 4-byte boundary.  After a YUYV call
- * yolo2_hip_images_layer0_kernel reports k_conv0_pool_mfma_yuyv[<split>], or under f16_no_mfma0 "k_letterbox_yuyv_batch + " and
- * the frame path's layer-0 kernel. */
-enum { YOLO2_PIX_GREY8 = 1, YOLO2_PIX_RGB24 = 3, YOLO2_PIX_YUYV = 0x56595559 /* V4L2 fourcc 'YUYV' */ };
+ *   YOLO2_PIX_NV12, YOLO2_PIX_I420     planar YUV 4:2:0, the frames of video decoders: w * h * 3 / 2 bytes, width AND height even.
+ *                                      A Y plane [h][w]; NV12 (V4L2 'NV12': hardware decoders, ISPs) follows it with one plane
+ *                                      [h/2][w/2][2] of interleaved U V pairs, I420 (V4L2 'YU12' = ffmpeg yuv420p) with a U plane
+ *                                      [h/2][w/2] and then a V plane [h/2][w/2].  Pixel (x, y) has Y(y, x), U(y >> 1, x >> 1) and
+ *                                      V(y >> 1, x >> 1) - chroma replicated, not interpolated - and its RGB bytes are the
+ *                                      formula above on those three.  Equivalently: the frame is the YUYV frame whose row y is
+ *                                      Y0 U Y1 V from luma row y and chroma row y >> 1, and every result of every entry is
+ *                                      bit-identical to the RGB24 entry on that frame's conversion.  This is this library's own
+ *                                      extension of the reference's formula: the reference has no 4:2:0 input (its --video path
+ *                                      lets ffmpeg convert), and identity with swscale's RGB is not claimed.
+ *                                      y2h_yuv420_to_rgb24 in libyolo2_host.so restates it on the host.  1.5 bytes per pixel
+ *                                      cross PCIe, half of RGB24's.
+ * A call is one format.  An odd YUYV / NV12 / I420 width, an odd NV12 / I420 height or an unknown pixfmt is YOLO2_ERROR
+ * (yolo2_hip_last_error names it) before anything is launched; yolo2_hip_letterbox_pix also wants a YUYV image_dev on a 4-byte
+ * boundary (NV12 and I420 frames may start at any address).  After a YUYV call yolo2_hip_images_layer0_kernel reports
+ * k_conv0_pool_mfma_yuyv[<split>], or under f16_no_mfma0 "k_letterbox_yuyv_batch + " and the frame path's layer-0 kernel; after an
+ * NV12 / I420 call the same names with _nv12 / _i420. */
+enum {
+    YOLO2_PIX_GREY8 = 1,
+    YOLO2_PIX_RGB24 = 3,
+    YOLO2_PIX_YUYV = 0x56595559, /* V4L2 fourcc 'YUYV' */
+    YOLO2_PIX_NV12 = 0x3231564E, /* V4L2 fourcc 'NV12' */
+    YOLO2_PIX_I420 = 0x32315559  /* V4L2 fourcc 'YU12' = ffmpeg yuv420p */
+};
 int yolo2_hip_letterbox_pix(uint64_t image_dev, int w, int h, int pixfmt, uint64_t frame_dev, int net_w, int net_h, void *stream);
 int yolo2_hip_run_images_pix_host(yolo2_hip_ctx *ctx, const uint8_t *const *images, const int *widths, const int *heights,
                                   int pixfmt, int n, int batch, int16_t *region_host, int *final_q);
@@ -526,8 +545,8 @@ int yolo2_hip_run_images_pix_dets_f16(yolo2_hip_ctx *ctx, int split, const uint8
  *
  * The reference's camera / video loop ends every frame with yolo2_draw_detections_rgb24 (linux_app/src/yolo2_draw.c:276-369, called at
  * linux_app/src/main.c:1079-1091) and hands the RGB24 frame to --save-annotated-dir or the MJPEG streamer.  These entries make that
- * frame on the GPU, bit-identical, from the frame in its camera format (YOLO2_PIX_*: RGB24 copied, GREY8 replicated, YUYV converted
- * as above) and records of the YOLO2_DETS_BEST_CLASS form (one per detection), whichever pass produced them; no weights are needed.
+ * frame on the GPU, bit-identical, from the frame in its camera format (YOLO2_PIX_*: RGB24 copied, GREY8 replicated, YUYV / NV12 /
+ * I420 converted as above) and records of the YOLO2_DETS_BEST_CLASS form (one per detection), whichever pass produced them; no weights are needed.
  *   which records   in array order, those with prob > thresh (and cls >= 0); later records paint over earlier ones
  *   box             corners (int)((x -+ w * 0.5f) * width) etc. in fp32, NaN / out-of-int-range products -> INT_MIN, each clamped to
  *                   the image; 2 pixels thick, every ring clamped again (yolo2_draw_rect_rgb24, :94-111); colour palette[cls % 8]
@@ -714,8 +733,8 @@ int yolo2_hip_run_batch_int8_host(yolo2_hip_ctx *ctx, const float *frames, int b
 /* Image bytes to region tensors / detection records on the int8 pass, single device: the contract of
  * yolo2_hip_run_images_pix_f16_host / _dets_f16 (chunks of `batch` images, 1..1024, a ragged last chunk repeats its last image;
  * staging, upload, kernels and download overlap on the context's three streams; region_host float [n][425][13][13]; the records
- * come from the float tail, flags YOLO2_DETS_BEST_CLASS / YOLO2_DETS_APP_TAIL).  pixfmt YOLO2_PIX_GREY8 / _RGB24 / _YUYV.
- * One kernel (k_i8_front_u8 / k_i8_front_yuyv) goes from the chunk's bytes to layer 1's tensor: letterbox, the input rule above,
+ * come from the float tail, flags YOLO2_DETS_BEST_CLASS / YOLO2_DETS_APP_TAIL).  pixfmt: any YOLO2_PIX_*.
+ * One kernel (k_i8_front_u8 / k_i8_front_yuyv / k_i8_front_nv12 / k_i8_front_i420) goes from the chunk's bytes to layer 1's tensor: letterbox, the input rule above,
  * layer 0 with its 27 inputs in one k step of v_mfma_i32_32x32x32_i8, and the 2x2 pool.  The result equals, bit for bit, the chunk
  * letterboxed (yolo2_hip_letterbox_pix) and run through yolo2_hip_run_batch_int8, which is what the entries do under option
  * i8_no_front.  The quantised input and layer 0's tensor (2 * batch * 416 * 416 * 32 bytes) are not allocated on this route.
@@ -726,7 +745,7 @@ int yolo2_hip_run_images_pix_int8_host(yolo2_hip_ctx *ctx, const uint8_t *const 
 int yolo2_hip_run_images_pix_dets_int8(yolo2_hip_ctx *ctx, const uint8_t *const *images, const int *widths, const int *heights,
                                        int pixfmt, int n, int batch, float thresh, float nms, int flags, yolo2_hip_det *dets,
                                        int cap_per_frame, int *counts);
-/* What the last int8 images call on ctx ran up to layer 1: "k_i8_front_u8" or "k_i8_front_yuyv"; under i8_no_front
+/* What the last int8 images call on ctx ran up to layer 1: "k_i8_front_u8", "k_i8_front_yuyv", "k_i8_front_nv12" or "k_i8_front_i420"; under i8_no_front
  * "k_letterbox_u8_batch + k_i8_quant_input + k_conv_i8" (or k_letterbox_yuyv_batch ...); "" before the first call. */
 const char *yolo2_hip_images_front_kernel_int8(yolo2_hip_ctx *ctx);
 /* Parity hook: the int8 tensor layer `layer_idx` (0..29; -1 = the quantised input) left behind in the last int8 run, frame `frame`,

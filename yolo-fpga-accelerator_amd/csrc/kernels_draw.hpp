@@ -34,7 +34,8 @@ struct AnnoHeader {
 };
 struct AnnoFrame {
     unsigned long long src_off, out_off;   // the frame's source bytes / its RGB24 output, in bytes from the two base addresses
-    int w, h, ch;                          // ch: source bytes per pixel - 1 grey, 3 RGB24, 2 packed YUYV 4:2:2 (w even, 4-byte aligned)
+    int w, h, ch;                          // ch: source bytes per pixel - 1 grey, 3 RGB24, 2 packed YUYV 4:2:2 (w even, 4-byte aligned);
+                                           // kLbChNv12 / kLbChI420: planar YUV 4:2:0 (w and h even, any address)
     int item0, n_items;                    // its items in the array, in record order
     int strips;                            // workgroups that have work on it: ceil(w * h / kAnnoStripPx)
 };
@@ -50,6 +51,16 @@ __device__ inline uint32_t anno_yuyv_px(uint32_t pair, int odd)
     const int c = 298 * ((int)((pair >> (odd * 16)) & 255u) - 16) + 128, d = (int)((pair >> 8) & 255u) - 128, e = (int)(pair >> 24) - 128;
     const int r = min(max((c + 409 * e) >> 8, 0), 255), g = min(max((c - 100 * d - 208 * e) >> 8, 0), 255), b = min(max((c + 516 * d) >> 8, 0), 255);
     return (uint32_t)r | ((uint32_t)g << 8) | ((uint32_t)b << 16);
+}
+
+// Pixel (x, y) of a planar 4:2:0 frame (letterbox.hpp, LbYuv420: Y plane, then NV12's interleaved U V plane or I420's U and V planes;
+// byte loads, the frame may start anywhere) as the YUYV pair it stands for
+__device__ inline uint32_t anno_yuv420_px(const uint8_t *__restrict__ src, int w, int h, bool semi, int x, int y)
+{
+    const uint8_t *c = src + (size_t)w * h;
+    const size_t at = semi ? (size_t)(y >> 1) * w + (x & ~1) : (size_t)(y >> 1) * (w >> 1) + (x >> 1);
+    const uint32_t u = c[at], v = semi ? c[at + 1] : c[at + (size_t)(w >> 1) * (h >> 1)];
+    return anno_yuyv_px((uint32_t)src[(size_t)y * w + x] | (u << 8) | (v << 24), 0);
 }
 
 // source pixel p of a frame -> R | G << 8 | B << 16
@@ -207,6 +218,14 @@ __global__ __launch_bounds__(kAnnoThreads) void k_annotate_batch(const uint8_t *
             col[4 * j + 1] = anno_yuyv_px(d0, 1);
             col[4 * j + 2] = anno_yuyv_px(d1, 0);
             col[4 * j + 3] = anno_yuyv_px(d1, 1);
+        } else if (fr.ch == kLbChNv12 || fr.ch == kLbChI420) {   // a run may cross a row's end: (x, y) per pixel
+            const int y0 = p / fr.w;
+            int x = p - y0 * fr.w, y = y0;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                col[4 * j + i] = p + i < p_hi ? anno_yuv420_px(src, fr.w, fr.h, fr.ch == kLbChNv12, x, y) : 0u;
+                if (++x == fr.w) { x = 0; ++y; }
+            }
         } else if (whole && src_al && fr.ch == 1) {
             const uint32_t d = *reinterpret_cast<const uint32_t *>(src + p);
 #pragma unroll

@@ -58,8 +58,9 @@ struct FrontI8Args {
     int q0, leaky;            // act_q[0]
 };
 
+// the kernel's body, so that a format's kernel can carry its own name (k_i8_front_pix below; kernels_i8_front_pix.hpp)
 template <class PIX>
-__global__ __launch_bounds__(256) void k_i8_front_pix(const FrontI8Args a)
+__device__ __forceinline__ void i8_front_tiles(const FrontI8Args &a)
 {
     __shared__ float lbt[256];
     __shared__ unsigned patch[kFrontPatch * kFrontPitch];
@@ -138,6 +139,12 @@ __global__ __launch_bounds__(256) void k_i8_front_pix(const FrontI8Args a)
             *reinterpret_cast<int4 *>(a.out + (((long)frame * 208 + oy) * 208 + ox) * 32 + 16 * h) = make_int4((int)o[0], (int)o[1], (int)o[2], (int)o[3]);
         }
     }
+}
+
+template <class PIX>
+__global__ __launch_bounds__(256) void k_i8_front_pix(const FrontI8Args a)
+{
+    i8_front_tiles<PIX>(a);
 }
 
 }  // namespace y2

@@ -8,6 +8,9 @@
 // lb_part's / lb_value's (letterbox.hpp restates them with the fetch as a parameter): the frame is bit-identical to
 // k_letterbox_u8's on the converted RGB24 image (tests/test_gpu_yuyv.py).
 //
+// NV12 and I420 frames (planar YUV 4:2:0, what video decoders emit) go the same way through LbYuv420: k_letterbox_nv12[_batch] and
+// k_letterbox_i420[_batch], 1.5 bytes per pixel (tests/test_gpu_yuv420.py).
+//
 // Include AFTER kernels_pre.hpp, in the one translation unit that includes it (yolo2_hip.hip): LetterboxArgs / LetterboxItem are
 // kernels_pre.hpp's definitions there, and letterbox.hpp's restatement of them is switched off.
 #pragma once
@@ -16,13 +19,15 @@
 
 namespace y2 {
 
-__device__ inline float lb_value_yuyv(const uint8_t *__restrict__ img, const LetterboxArgs &a, int t)
+template <class PIX>
+__device__ inline float lb_value_pix(const uint8_t *__restrict__ img, const LetterboxArgs &a, int t)
 {
     const int plane = a.net_w * a.net_h;
     const int k = t / plane, rem = t - k * plane;
     const int y = rem / a.net_w;
-    return lb_value_at<LbDiv255, LbYuyv>(img, a, k, y, rem - y * a.net_w);
+    return lb_value_at<LbDiv255, PIX>(img, a, k, y, rem - y * a.net_w);
 }
+__device__ inline float lb_value_yuyv(const uint8_t *__restrict__ img, const LetterboxArgs &a, int t) { return lb_value_pix<LbYuyv>(img, a, t); }
 
 // one image (a.ch == 2, a.w even, img on a 4-byte boundary)
 __global__ void k_letterbox_yuyv(const uint8_t *__restrict__ img, float *__restrict__ out, const LetterboxArgs a)
@@ -40,6 +45,34 @@ __global__ void k_letterbox_yuyv_batch(const uint8_t *__restrict__ base, float *
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= 3 * a.net_w * a.net_h) return;
     out[(size_t)blockIdx.y * frame_elems + t] = lb_value_yuyv(base + it->off, a, t);
+}
+
+// the two kernels above for a planar 4:2:0 fetch (a.w and a.h even, img at any address)
+template <class PIX>
+__device__ inline void letterbox_pix_one(const uint8_t *__restrict__ img, float *__restrict__ out, const LetterboxArgs &a)
+{
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= 3 * a.net_w * a.net_h) return;
+    out[t] = lb_value_pix<PIX>(img, a, t);
+}
+template <class PIX>
+__device__ inline void letterbox_pix_batch(const uint8_t *__restrict__ base, float *__restrict__ out, int frame_elems)
+{
+    const LetterboxItem *it = reinterpret_cast<const LetterboxItem *>(base) + blockIdx.y;
+    const LetterboxArgs a = it->a;
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= 3 * a.net_w * a.net_h) return;
+    out[(size_t)blockIdx.y * frame_elems + t] = lb_value_pix<PIX>(base + it->off, a, t);
+}
+__global__ void k_letterbox_nv12(const uint8_t *__restrict__ img, float *__restrict__ out, const LetterboxArgs a) { letterbox_pix_one<LbYuv420<true>>(img, out, a); }
+__global__ void k_letterbox_i420(const uint8_t *__restrict__ img, float *__restrict__ out, const LetterboxArgs a) { letterbox_pix_one<LbYuv420<false>>(img, out, a); }
+__global__ void k_letterbox_nv12_batch(const uint8_t *__restrict__ base, float *__restrict__ out, int frame_elems)
+{
+    letterbox_pix_batch<LbYuv420<true>>(base, out, frame_elems);
+}
+__global__ void k_letterbox_i420_batch(const uint8_t *__restrict__ base, float *__restrict__ out, int frame_elems)
+{
+    letterbox_pix_batch<LbYuv420<false>>(base, out, frame_elems);
 }
 
 }  // namespace y2

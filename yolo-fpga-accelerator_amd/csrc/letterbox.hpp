@@ -5,7 +5,8 @@
 // with the byte -> v / 255 step as a parameter, so that the fused kernel can take it from a table in LDS.  Every float operation
 // is lb_part / lb_value's, in their order: the values are bit-identical (tests/test_gpu_images_f16.py).
 // The pixel fetch is a parameter too: LbInterleaved reads kernels_pre.hpp's 1 or 3 interleaved byte channels, LbYuyv turns a packed
-// YUYV 4:2:2 pixel into the R, G or B byte first (kernels_pix.hpp, k_conv0_pool_mfma_yuyv).
+// YUYV 4:2:2 pixel into the R, G or B byte first (kernels_pix.hpp, k_conv0_pool_mfma_yuyv), LbYuv420 does the same for the planar
+// 4:2:0 frames of video decoders, NV12 and I420 (kernels_pix.hpp, kernels_f16_pix.hpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -57,12 +58,41 @@ struct LbYuyv {
     }
 };
 
+// Planar YUV 4:2:0: a full-resolution Y plane [a.h][a.w], then the chroma of every 2 x 2 block of pixels - SEMI (NV12): one plane
+// [a.h / 2][a.w / 2] of interleaved U V pairs; otherwise (I420 = yuv420p): a U plane [a.h / 2][a.w / 2], then a V plane of the same shape.
+// a.w and a.h are even.  Pixel (x, r) has Y(r, x) and the chroma of (r >> 1, x >> 1), replicated, not interpolated, and its byte is
+// LbYuyv's conversion of those three: the frame is the YUYV frame whose row r is Y0 U Y1 V from luma row r and chroma row r >> 1.
+// The plane addresses follow from a.w and a.h alone (a.ch is a format code here, not a byte count, and is not read).  All loads are
+// byte loads: an I420 chroma row is a.w / 2 bytes and starts anywhere, and the single-image entries take a frame at any address, so
+// an NV12 pair is not known to sit on an even address either.
+constexpr int kLbChNv12 = 12, kLbChI420 = 13;   // LetterboxArgs::ch / AnnoFrame::ch of the two formats
+template <bool SEMI>
+struct LbYuv420 {
+    const uint8_t *y, *u, *v;   // luma row r; chroma row r >> 1 (SEMI: v = u + 1, pairs two bytes apart)
+    int cu, cv;
+    __device__ LbYuv420(const uint8_t *__restrict__ img, const LetterboxArgs &a, int r, int k)
+        : y(img + (size_t)r * a.w), u(img + (size_t)a.w * a.h + (size_t)(r >> 1) * (SEMI ? a.w : a.w >> 1)),
+          v(u + (SEMI ? (size_t)1 : ((size_t)(a.w >> 1) * (a.h >> 1)))), cu(k == 0 ? 0 : (k == 1 ? -100 : 516)),
+          cv(k == 0 ? 409 : (k == 1 ? -208 : 0)) {}
+    __device__ uint8_t operator()(int x) const
+    {
+        const int xc = SEMI ? (x & ~1) : (x >> 1);
+        const int c = (int)y[x] - 16, d = (int)u[xc] - 128, e = (int)v[xc] - 128;
+        return (uint8_t)min(max((298 * c + cu * d + cv * e + 128) >> 8, 0), 255);
+    }
+};
+
+// a fetch that converts: lb_part_q runs its operations on the fetch's bytes instead of on interleaved channels
+template <class F> struct LbConverts : std::false_type {};
+template <> struct LbConverts<LbYuyv> : std::true_type {};
+template <bool SEMI> struct LbConverts<LbYuv420<SEMI>> : std::true_type {};
+
 // kernels_pre.hpp's lb_part: the horizontally interpolated value part(c, r, k) of resize_image's first pass
 template <class Q = LbDiv255, class F = LbInterleaved>
 __device__ inline float lb_part_q(const uint8_t *__restrict__ img, const LetterboxArgs &a, int c, int r, int k, Q q = Q())
 {
-    if constexpr (std::is_same<F, LbYuyv>::value) {   // the same operations on the converted bytes
-        const LbYuyv px(img, a, r, k);
+    if constexpr (LbConverts<F>::value) {   // the same operations on the converted bytes
+        const F px(img, a, r, k);
         if (c == a.new_w - 1 || a.w == 1) return q(px(a.w - 1));
         const float sx = __fmul_rn((float)c, a.w_scale);
         const int ix = (int)sx;

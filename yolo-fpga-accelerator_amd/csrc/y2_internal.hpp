@@ -519,11 +519,11 @@ void y2_f16_plan_free(yolo2_hip_ctx *c);
 // (split 1, made here) - or YOLO2_ERROR without fp32 weights.  y2_f16_images_fused: that pass has the layer-0 step from bytes (not under
 // f16_no_mfma0: the entries then letterbox into frames and run the frame path).  y2_f16_run_images: the pass on a chunk of `batch`
 // frames whose staging buffer (LetterboxItem table + images) is at lb, enqueued on st; y2_f16_images_kernel names its layer-0 kernel.
-// yuyv: the chunk's images are packed YUYV 4:2:2 frames (table items with ch == 2) instead of interleaved bytes.
+// kind: what the chunk's images are (Y2PixKind below) - interleaved bytes, packed YUYV 4:2:2 or planar 4:2:0 frames.
 int y2_f16_images_ctx(yolo2_hip_ctx *c, int split, yolo2_hip_ctx **run);
 bool y2_f16_images_fused(const yolo2_hip_ctx *run);
-int y2_f16_run_images(yolo2_hip_ctx *run, const uint8_t *lb, bool yuyv, int batch, float *region_dev, hipStream_t st);
-const char *y2_f16_images_kernel(const yolo2_hip_ctx *run, bool yuyv);
+int y2_f16_run_images(yolo2_hip_ctx *run, const uint8_t *lb, int kind, int batch, float *region_dev, hipStream_t st);
+const char *y2_f16_images_kernel(const yolo2_hip_ctx *run, int kind);
 
 // The per-layer driver calls' device work (yolo2_driver.hip validates, latches the register file, takes the lock, binds the
 // device, and synchronises with the reference's timeout semantics afterwards; these only enqueue on the null stream).
@@ -545,8 +545,8 @@ void y2_i8_free(yolo2_hip_ctx *c);
 // y2_i8_run_images runs k_i8_front_pix on the chunk's staging buffer at lb into layer 1's tensor and layers 2..30 behind it, on st.
 bool y2_i8_loaded(const yolo2_hip_ctx *c);
 bool y2_i8_images_fused(const yolo2_hip_ctx *c);
-int y2_i8_run_images(yolo2_hip_ctx *c, const uint8_t *lb, bool yuyv, int batch, float *region_dev, hipStream_t st);
-const char *y2_i8_front_kernel(bool yuyv);
+int y2_i8_run_images(yolo2_hip_ctx *c, const uint8_t *lb, int kind, int batch, float *region_dev, hipStream_t st);
+const char *y2_i8_front_kernel(int kind);
 
 // yolo2_draw.hip: the streams, events and buffers of c->anno (yolo2_hip_destroy)
 void y2_anno_free(yolo2_hip_ctx *c);
@@ -568,17 +568,49 @@ int y2_loop_enqueue_paint(yolo2_hip_ctx *c, int nf, int max_strips, const uint8_
 // yolo2_hip.hip: what the images entries and the loop entry share - the letterbox rule, the chunk letterbox launch, PipeBufs' growth
 // (need_hout: the pinned region mirrors; _post: the tail's buffers; _regf: the fp32 region tensors) and the threaded staging copy
 namespace y2 { struct LetterboxArgs; }
-int y2_letterbox_args(int w, int h, int channels, int net_w, int net_h, y2::LetterboxArgs &a, bool yuyv_ok);
-int y2_pix_channels(int pixfmt);
-void y2_launch_letterbox_batch(bool yuyv, const uint8_t *dbytes, float *din, int batch, hipStream_t st);
+// The pixel formats of the _pix entries, one descriptor each: everything the host code needs to know about a format.
+//   ch      what LetterboxArgs::ch / AnnoFrame::ch carry: bytes per pixel for interleaved bytes (1, 3) and YUYV (2); for the planar
+//           4:2:0 formats, which have no whole number of bytes per pixel, a code that only their own fetch looks at
+//   kind    which kernels read it (the letterbox, layer-0, int8-front and painter instantiations)
+//   frame_bytes(w, h)   size of a frame; sizes staging, offsets and geometry everywhere
+//   even_w / even_h     the parity rule; align: the address alignment the single-image entries ask for
+enum Y2PixKind { Y2_KIND_BYTES = 0, Y2_KIND_YUYV, Y2_KIND_NV12, Y2_KIND_I420, Y2_KIND_COUNT };
+struct Y2PixDesc {
+    int pixfmt;
+    const char *name;
+    int ch;
+    Y2PixKind kind;
+    int bits;   // per pixel
+    bool even_w, even_h;
+    unsigned align;
+    size_t frame_bytes(int w, int h) const { return (size_t)w * h * bits / 8; }
+};
+const Y2PixDesc *y2_pix_desc(int pixfmt, const char *who);   // by YOLO2_PIX_* fourcc; nullptr and "[who: ]unknown pixel format" otherwise
+const Y2PixDesc *y2_pix_desc_ch(int ch);                     // by its ch; nullptr for a ch no format has
+inline size_t y2_frame_bytes(int w, int h, int ch)
+{
+    const Y2PixDesc *d = y2_pix_desc_ch(ch);
+    return d ? d->frame_bytes(w, h) : (size_t)w * h * ch;
+}
+inline int y2_ch_kind(int ch)
+{
+    const Y2PixDesc *d = y2_pix_desc_ch(ch);
+    return d ? d->kind : Y2_KIND_BYTES;
+}
+// the parity rule of a frame: YOLO2_ERROR "who: NAME frames have an even width, not W" (... height ...)
+int y2_pix_check_parity(const Y2PixDesc &d, int w, int h, const char *who, int frame);
+// channels: a Y2PixDesc::ch.  pix: called from a _pix entry; the u8 entries, whose callers pass a channel count, take 1 and 3 only.
+int y2_letterbox_args(int w, int h, int channels, int net_w, int net_h, y2::LetterboxArgs &a, bool pix);
+const char *y2_letterbox_batch_kernel(int kind);
+void y2_launch_letterbox_batch(int kind, const uint8_t *dbytes, float *din, int batch, hipStream_t st);
 int y2_pipe_ensure(PipeBufs &p, size_t host_in, size_t dev_in, int batch, bool need_hout);
 int y2_pipe_ensure_post(yolo2_hip_ctx *c, int batch, int cap);
 int y2_pipe_ensure_regf(PipeBufs &p, int batch, bool need_host);
 void y2_stage_images(uint8_t *dst, const uint8_t *const *images, const size_t *offs, const size_t *bytes, int nf);
 // the network of the chunk in buffer set b (staged, its upload waited for on s_run), enqueued: int16 into dout[b], with the events whoever
 // needs the whole region tensor waits for (the lanes are not joined); fp16 / split into dregf[b], e_run[b] recorded behind it
-int y2_pipe_enqueue_i16(yolo2_hip_ctx *c, int b, bool yuyv, int batch, int *q, std::vector<hipEvent_t> *done);
-int y2_pipe_enqueue_f16(yolo2_hip_ctx *c, yolo2_hip_ctx *run, bool fused, int b, bool yuyv, int batch);
+int y2_pipe_enqueue_i16(yolo2_hip_ctx *c, int b, int kind, int batch, int *q, std::vector<hipEvent_t> *done);
+int y2_pipe_enqueue_f16(yolo2_hip_ctx *c, yolo2_hip_ctx *run, bool fused, int b, int kind, int batch);
 
 // yolo2_calib.hip: one exact fp32 pass over `batch` device frames + the abs-max reductions, accumulated into c->calib_stats; `counted`
 // of the frames are new ones (the images entry pads a short last chunk by repeating its last image).  Synchronises st.

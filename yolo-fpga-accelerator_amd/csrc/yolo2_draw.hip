@@ -21,22 +21,11 @@ namespace {
 
 size_t padded(size_t b) { return (b + 255) & ~(size_t)255; }
 
-// pixfmt -> source bytes per pixel (AnnoFrame::ch); 0 and the error for anything else
-int anno_channels(int pixfmt)
-{
-    if (pixfmt == YOLO2_PIX_GREY8) return 1;
-    if (pixfmt == YOLO2_PIX_RGB24) return 3;
-    if (pixfmt == YOLO2_PIX_YUYV) return 2;
-    (void)fail(YOLO2_ERROR, "annotate: unknown pixel format 0x%x (YOLO2_PIX_GREY8, YOLO2_PIX_RGB24 or YOLO2_PIX_YUYV)", (unsigned)pixfmt);
-    return 0;
-}
-
-int check_geometry(int w, int h, int ch, int frame)
+int check_geometry(int w, int h, const Y2PixDesc &pd, int frame)
 {
     if (w <= 0 || h <= 0) return fail(YOLO2_ERROR, "annotate: bad frame size %dx%d (frame %d)", w, h, frame);
     if ((long)w * h > (1L << 28)) return fail(YOLO2_ERROR, "annotate: frame %d too large (%dx%d)", frame, w, h);
-    if (ch == 2 && (w & 1)) return fail(YOLO2_ERROR, "annotate: YUYV frames have an even width, not %d (frame %d)", w, frame);
-    return YOLO2_SUCCESS;
+    return y2_pix_check_parity(pd, w, h, "annotate", frame);
 }
 
 int check_records(const yolo2_hip_det *dets, int n, int frame)
@@ -113,11 +102,12 @@ extern "C" int yolo2_hip_annotate_pix(uint64_t image_dev, int w, int h, int pixf
 {
     if (!image_dev || !rgb_out_dev) return fail(YOLO2_ERROR, "annotate: null buffer address");
     if (n_dets < 0 || (n_dets > 0 && !dets)) return fail(YOLO2_ERROR, "annotate: null records (n_dets %d)", n_dets);
-    const int ch = anno_channels(pixfmt);
-    if (!ch) return YOLO2_ERROR;
+    const Y2PixDesc *pd = y2_pix_desc(pixfmt, "annotate");
+    if (!pd) return YOLO2_ERROR;
+    const int ch = pd->ch;
     int rc;
-    if ((rc = check_geometry(w, h, ch, 0)) || (rc = check_common(thresh, n_labels)) || (rc = check_records(dets, n_dets, 0))) return rc;
-    if (ch == 2 && (image_dev & 3)) return fail(YOLO2_ERROR, "annotate: a YUYV frame starts on a 4-byte boundary");
+    if ((rc = check_geometry(w, h, *pd, 0)) || (rc = check_common(thresh, n_labels)) || (rc = check_records(dets, n_dets, 0))) return rc;
+    if (image_dev & (pd->align - 1)) return fail(YOLO2_ERROR, "annotate: a %s frame starts on a %u-byte boundary", pd->name, pd->align);
     const FrameIn fr = {w, h, ch, 0, 0, dets, n_dets};
     const size_t bytes = table_bytes(1, (size_t)count_drawn(dets, n_dets, thresh));
     std::vector<uint8_t> tbl(bytes);
@@ -181,8 +171,8 @@ int y2_annotate_check(const uint8_t *const *images, const int *widths, const int
                       int cap_per_frame, const int *counts, float thresh, int n_labels, uint8_t *const *annotated)
 {
     if (!images || !widths || !heights || !dets || !counts || !annotated) return fail(YOLO2_ERROR, "annotate: null argument");
-    const int ch = anno_channels(pixfmt);
-    if (!ch) return YOLO2_ERROR;
+    const Y2PixDesc *pd = y2_pix_desc(pixfmt, "annotate");
+    if (!pd) return YOLO2_ERROR;
     if (n <= 0 || batch <= 0 || batch > 1024 || cap_per_frame <= 0)
         return fail(YOLO2_ERROR, "annotate: bad image count %d / batch %d (1..1024) / capacity %d", n, batch, cap_per_frame);
     int rc;
@@ -190,7 +180,7 @@ int y2_annotate_check(const uint8_t *const *images, const int *widths, const int
     for (int f = 0; f < n; ++f) {
         if (!images[f] || !annotated[f]) return fail(YOLO2_ERROR, "annotate: null image or output %d", f);
         if (counts[f] < 0) return fail(YOLO2_ERROR, "annotate: negative record count %d of frame %d", counts[f], f);
-        if ((rc = check_geometry(widths[f], heights[f], ch, f)) ||
+        if ((rc = check_geometry(widths[f], heights[f], *pd, f)) ||
             (rc = check_records(dets + (size_t)f * cap_per_frame, std::min(counts[f], cap_per_frame), f)))
             return rc;
     }
@@ -207,7 +197,7 @@ extern "C" int yolo2_hip_annotate_images_pix_host(yolo2_hip_ctx *c, const uint8_
     if (!c) return fail(YOLO2_ERROR, "annotate: null argument");
     int rc;
     if ((rc = y2_annotate_check(images, widths, heights, pixfmt, n, batch, dets, cap_per_frame, counts, thresh, n_labels, annotated))) return rc;
-    const int ch = anno_channels(pixfmt);
+    const int ch = y2_pix_desc(pixfmt, "annotate")->ch;
     batch = std::min(batch, n);
     const int chunks = (n + batch - 1) / batch;
     auto in_chunk = [&](int k) { return std::min(batch, n - k * batch); };
@@ -217,7 +207,7 @@ extern "C" int yolo2_hip_annotate_images_pix_host(yolo2_hip_ctx *c, const uint8_
         size_t items = 0, in = 0, out = 0;
         for (int f = k * batch; f < k * batch + in_chunk(k); ++f) {
             items += (size_t)count_drawn(dets + (size_t)f * cap_per_frame, used(f), thresh);
-            in += padded((size_t)widths[f] * heights[f] * ch);
+            in += padded(y2_frame_bytes(widths[f], heights[f], ch));
             out += padded((size_t)widths[f] * heights[f] * 3);
         }
         cap_in = std::max(cap_in, table_bytes(in_chunk(k), items) + in);
@@ -249,7 +239,7 @@ extern "C" int yolo2_hip_annotate_images_pix_host(yolo2_hip_ctx *c, const uint8_
         size_t off = table_bytes(nf, items), out_off = 0;
         for (int i = 0; i < nf; ++i) {
             const int f = first + i;
-            const size_t bytes = (size_t)widths[f] * heights[f] * ch;
+            const size_t bytes = y2_frame_bytes(widths[f], heights[f], ch);
             memcpy(hin + off, images[f], bytes);
             fr[(size_t)i] = {widths[f], heights[f], ch, off, out_off, dets + (size_t)f * cap_per_frame, used(f)};
             off += padded(bytes);
@@ -370,7 +360,7 @@ extern "C" int yolo2_hip_draw_items_dev(yolo2_hip_ctx *c, uint64_t dets_dev, uin
     int rc;
     if ((rc = check_common(thresh, n_labels))) return rc;
     for (int f = 0; f < n_frames; ++f)
-        if ((rc = check_geometry(widths[f], heights[f], 3, f))) return rc;
+        if ((rc = check_geometry(widths[f], heights[f], *y2_pix_desc_ch(3), f))) return rc;
     HIP_TRY(hipSetDevice(c->device), YOLO2_INIT_ERROR);
     if ((rc = y2_loop_ensure(c, n_frames, cap_per_frame, labels, n_labels))) return rc;
     const size_t gbytes = y2_loop_geom_bytes(n_frames);
@@ -464,7 +454,7 @@ extern "C" int yolo2_hip_annotate_images_pix_jpeg_host(yolo2_hip_ctx *c, const u
     int rc;
     if ((rc = y2_annotate_jpeg_check(images, widths, heights, pixfmt, n, batch, dets, cap_per_frame, counts, thresh, n_labels, jpeg, caps, sizes)))
         return rc;
-    const int ch = anno_channels(pixfmt);
+    const int ch = y2_pix_desc(pixfmt, "annotate")->ch;
     batch = std::min(batch, n);
     const int chunks = (n + batch - 1) / batch;
     auto in_chunk = [&](int k) { return std::min(batch, n - k * batch); };
@@ -480,7 +470,7 @@ extern "C" int yolo2_hip_annotate_images_pix_jpeg_host(yolo2_hip_ctx *c, const u
         for (int i = 0; i < in_chunk(k); ++i) {
             const int f = k * batch + i;
             items[(size_t)k] += (size_t)count_drawn(dets + (size_t)f * cap_per_frame, used(f), thresh);
-            in += padded((size_t)widths[f] * heights[f] * ch);
+            in += padded(y2_frame_bytes(widths[f], heights[f], ch));
             jf[(size_t)i] = {widths[f], heights[f], out, caps[f]};
             out += padded((size_t)widths[f] * heights[f] * 3);
         }
@@ -534,7 +524,7 @@ extern "C" int yolo2_hip_annotate_images_pix_jpeg_host(yolo2_hip_ctx *c, const u
         size_t off = table_bytes(nf, items[(size_t)k]), out_off = 0;
         for (int i = 0; i < nf; ++i) {
             const int f = first + i;
-            const size_t bytes = (size_t)widths[f] * heights[f] * ch;
+            const size_t bytes = y2_frame_bytes(widths[f], heights[f], ch);
             memcpy(hin + off, images[f], bytes);
             fr[(size_t)i] = {widths[f], heights[f], ch, off, out_off, dets + (size_t)f * cap_per_frame, used(f)};
             jf[(size_t)i] = {widths[f], heights[f], out_off, caps[f]};

@@ -12,6 +12,7 @@
 
 #include "y2_internal.hpp"
 #include "kernels_f16.hpp"
+#include "kernels_f16_pix.hpp"
 
 using namespace y2;
 
@@ -61,10 +62,11 @@ struct F16Table {
     std::vector<F16Step> steps;
     // the images entries' layer-0 step "from bytes" (layers 0+1 from a chunk's staging buffer), used instead of steps[0]; every
     // other step is the table's.  Not set (launch_u8 == nullptr) under f16_no_mfma0: those entries letterbox into frames first.
-    // launch_yuyv / yuyv_kernel: the same step "from YUYV bytes" (a chunk of packed YUYV 4:2:2 frames: k_conv0_pool_mfma_yuyv).
+    // launch_pix / pix_kernel [Y2PixKind]: the same step from a chunk of frames of that kind (k_conv0_pool_mfma_yuyv / _nv12 / _i420;
+    // [Y2_KIND_BYTES] is launch_u8 / u8.kernel again).
     F16Step u8;
-    F16LaunchU8 launch_u8 = nullptr, launch_yuyv = nullptr;
-    const char *yuyv_kernel = "";
+    F16LaunchU8 launch_u8 = nullptr, launch_pix[Y2_KIND_COUNT] = {};
+    const char *pix_kernel[Y2_KIND_COUNT] = {"", "", "", ""};
 };
 struct F16Plan : F16Table {
     Y2Options opt;               // the context's option set as it was when the weights were loaded; a lane runs the parent's selection
@@ -300,6 +302,10 @@ template <auto K> static void L_conv0_bytes(const F16Step &s, const uint8_t *lb,
     XB(FK_C0_U8,         "k_conv0_pool_mfma_u8",               k_conv0_pool_mfma_u8<false>)                            \
     XB(FK_C0_YUYV_SP,    "k_conv0_pool_mfma_yuyv<split>",      k_conv0_pool_mfma_yuyv<true>)                           \
     XB(FK_C0_YUYV,       "k_conv0_pool_mfma_yuyv",             k_conv0_pool_mfma_yuyv<false>)                          \
+    XB(FK_C0_NV12_SP,    "k_conv0_pool_mfma_nv12<split>",      k_conv0_pool_mfma_nv12<true>)                           \
+    XB(FK_C0_NV12,       "k_conv0_pool_mfma_nv12",             k_conv0_pool_mfma_nv12<false>)                          \
+    XB(FK_C0_I420_SP,    "k_conv0_pool_mfma_i420<split>",      k_conv0_pool_mfma_i420<true>)                           \
+    XB(FK_C0_I420,       "k_conv0_pool_mfma_i420",             k_conv0_pool_mfma_i420<false>)                          \
     X(FK_RW,             "k_conv_f16_rw",                      L_rw, (k_conv_f16_rw<13, 0>), 256, 1)                   \
     X(FK_RW_POOL,        "k_conv_f16_rw<pool>",                L_rw, (k_conv_f16_rw<13, 1>), 256, 1)                   \
     X(FK_RW_1X1,         "k_conv_f16_rw<+1x1>",                L_rw, (k_conv_f16_rw<13, 2>), 256, 1)                   \
@@ -548,9 +554,13 @@ static int select_f16_table(const Y2Options &o, bool split, int B, F16Table &T)
         }
         T.steps.push_back(s);
         if (!o.f16_no_mfma0) {   // the same tiles, grid and output from image bytes (the images entries)
-            const F16Kernel &u8 = kF16Kernels[split ? FK_C0_U8_SP : FK_C0_U8], &yuyv = kF16Kernels[split ? FK_C0_YUYV_SP : FK_C0_YUYV];
+            const F16Kid kid[Y2_KIND_COUNT][2] = {{FK_C0_U8, FK_C0_U8_SP}, {FK_C0_YUYV, FK_C0_YUYV_SP}, {FK_C0_NV12, FK_C0_NV12_SP}, {FK_C0_I420, FK_C0_I420_SP}};
+            const F16Kernel &u8 = kF16Kernels[kid[Y2_KIND_BYTES][split ? 1 : 0]];
             T.u8 = s; T.u8.kernel = u8.name; T.launch_u8 = u8.launch_u8;
-            T.yuyv_kernel = yuyv.name; T.launch_yuyv = yuyv.launch_u8;
+            for (int kind = 0; kind < Y2_KIND_COUNT; ++kind) {
+                const F16Kernel &k = kF16Kernels[kid[kind][split ? 1 : 0]];
+                T.pix_kernel[kind] = k.name; T.launch_pix[kind] = k.launch_u8;
+            }
         }
     }
     // (a fused pool or 1x1 stores the tensor of the layer it swallowed, so every step reads the tensor the wiring names)
@@ -648,7 +658,7 @@ static std::string f16_table_text(const F16Table &T, const char *prefix)
                  tensor(s.t_out, s.store == FS_REGION ? "region" : "-").c_str(), s.w_ord, s.w2_ord, args, s.iCp, s.iWp, s.iPL, s.oCp, s.oWp, s.oPL, s.OH, s.OW, s.iPS, s.oPS);
         out += buf;
     }
-    if (T.launch_u8) out += std::string(prefix) + "u8 " + T.u8.kernel + "\n" + prefix + "yuyv " + T.yuyv_kernel + "\n";
+    if (T.launch_u8) out += std::string(prefix) + "u8 " + T.u8.kernel + "\n" + prefix + "yuyv " + T.pix_kernel[Y2_KIND_YUYV] + "\n";   // (the text of the recorded tables)
     return out;
 }
 
@@ -756,8 +766,8 @@ static int make_f16_lanes(yolo2_hip_ctx *c, int want_lanes)
 
 // The pass.  lb == nullptr: layer 0 reads the float frames at frames_dev (the table as it is).  lb != nullptr (the images entries):
 // layer 0 reads frames lb_first .. lb_first + batch - 1 of the chunk staging buffer lb through the table's step "from bytes", or,
-// for a chunk of YUYV frames (yuyv), "from YUYV bytes".
-static int run_f16(yolo2_hip_ctx *c, uint64_t frames_dev, const uint8_t *lb, int lb_first, bool yuyv, int batch, uint64_t region_dev,
+// for a chunk of YUYV / NV12 / I420 frames (kind: Y2PixKind), the step from those.
+static int run_f16(yolo2_hip_ctx *c, uint64_t frames_dev, const uint8_t *lb, int lb_first, int kind, int batch, uint64_t region_dev,
                    void *stream)
 {
     if (!c) return fail(YOLO2_ERROR, "null ctx");
@@ -782,7 +792,7 @@ static int run_f16(yolo2_hip_ctx *c, uint64_t frames_dev, const uint8_t *lb, int
             yolo2_hip_ctx *l = c->f16_lanes[i];
             hipStream_t ls = l->lane_stream ? l->lane_stream : st;
             if (l->lane_stream) HIP_TRY(hipStreamWaitEvent(ls, c->ev_fork, 0), YOLO2_ERROR);
-            const int rc = run_f16(l, lb ? 0 : frames_dev + (uint64_t)i * half * YOLO2_FRAME_ELEMS * sizeof(float), lb, lb_first + i * half, yuyv, half,
+            const int rc = run_f16(l, lb ? 0 : frames_dev + (uint64_t)i * half * YOLO2_FRAME_ELEMS * sizeof(float), lb, lb_first + i * half, kind, half,
                                    region_dev + (uint64_t)i * half * YOLO2_REGION_ELEMS * sizeof(float), ls);
             if (rc) return rc;
             if (l->lane_stream) HIP_TRY(hipEventRecord(l->ev_join, ls), YOLO2_ERROR);
@@ -804,7 +814,7 @@ static int run_f16(yolo2_hip_ctx *c, uint64_t frames_dev, const uint8_t *lb, int
     int next_ev = 0;
     const F16Plan &P = *c->f16_plan;
     if (lb && !P.launch_u8) return fail(YOLO2_ERROR, "fp16 plan has no layer-0 step from bytes");
-    const F16LaunchU8 from_bytes = yuyv ? P.launch_yuyv : P.launch_u8;
+    const F16LaunchU8 from_bytes = P.launch_pix[kind];
     for (const F16Step &s : P.steps) {
         if (ev) for (; next_ev <= s.layer; ++next_ev) (void)hipEventRecord(ev[next_ev], st);   // layers without a launch of their own
         if (lb && s.layer == 0)
@@ -821,7 +831,7 @@ static int run_f16(yolo2_hip_ctx *c, uint64_t frames_dev, const uint8_t *lb, int
 
 extern "C" int yolo2_hip_run_batch_fp16(yolo2_hip_ctx *c, uint64_t frames_dev, int batch, uint64_t region_dev, void *stream)
 {
-    return run_f16(c, frames_dev, nullptr, 0, false, batch, region_dev, stream);
+    return run_f16(c, frames_dev, nullptr, 0, Y2_KIND_BYTES, batch, region_dev, stream);
 }
 
 // ---------------------------------------------------------------------------- split-fp16: the MFMA path inside the fp32 tolerance
@@ -955,15 +965,15 @@ int y2_f16_images_ctx(yolo2_hip_ctx *c, int split, yolo2_hip_ctx **run)
 
 bool y2_f16_images_fused(const yolo2_hip_ctx *run) { return !run->f16_plan->opt.f16_no_mfma0; }
 
-int y2_f16_run_images(yolo2_hip_ctx *run, const uint8_t *lb, bool yuyv, int batch, float *region_dev, hipStream_t st)
+int y2_f16_run_images(yolo2_hip_ctx *run, const uint8_t *lb, int kind, int batch, float *region_dev, hipStream_t st)
 {
     if (!lb) return fail(YOLO2_ERROR, "null buffer address");
-    return run_f16(run, 0, lb, 0, yuyv, batch, (uint64_t)(uintptr_t)region_dev, st);
+    return run_f16(run, 0, lb, 0, kind, batch, (uint64_t)(uintptr_t)region_dev, st);
 }
 
-const char *y2_f16_images_kernel(const yolo2_hip_ctx *run, bool yuyv)
+const char *y2_f16_images_kernel(const yolo2_hip_ctx *run, int kind)
 {
     if (!run->f16_lanes.empty() && run->f16_last_laned) run = run->f16_lanes[0];
     if (!run->f16_plan || !run->f16_plan->launch_u8) return "";
-    return yuyv ? run->f16_plan->yuyv_kernel : run->f16_plan->u8.kernel;
+    return run->f16_plan->pix_kernel[kind];
 }

@@ -414,13 +414,45 @@ extern "C" int yolo2_hip_layer_times_ms(yolo2_hip_ctx *c, float *ms32)
 
 // ---------------------------------------------------------------------------- pre-processing
 
-// channels: bytes per pixel = LetterboxArgs::ch.  1 and 3 are interleaved byte channels; 2 marks a packed YUYV 4:2:2 frame and is
-// accepted from the _pix entries only (yuyv_ok): on the u8 entries, whose callers pass a channel count, it stays an error.
-int y2_letterbox_args(int w, int h, int channels, int net_w, int net_h, LetterboxArgs &a, bool yuyv_ok = false)
+// The pixel formats (y2_internal.hpp has the fields).  The first two are the u8 entries' channel counts.
+static const Y2PixDesc kPixDescs[] = {
+    {YOLO2_PIX_GREY8, "GREY8", 1, Y2_KIND_BYTES, 8, false, false, 1},
+    {YOLO2_PIX_RGB24, "RGB24", 3, Y2_KIND_BYTES, 24, false, false, 1},
+    {YOLO2_PIX_YUYV, "YUYV", 2, Y2_KIND_YUYV, 16, true, false, 4},            // (LbYuyv loads pixel pairs as dwords)
+    {YOLO2_PIX_NV12, "NV12", y2::kLbChNv12, Y2_KIND_NV12, 12, true, true, 1},   // (LbYuv420 loads bytes)
+    {YOLO2_PIX_I420, "I420", y2::kLbChI420, Y2_KIND_I420, 12, true, true, 1},
+};
+
+const Y2PixDesc *y2_pix_desc(int pixfmt, const char *who)
 {
-    if (w <= 0 || h <= 0 || net_w <= 1 || net_h <= 1 || (channels != 1 && channels != 3 && !(channels == 2 && yuyv_ok)))
+    for (const Y2PixDesc &d : kPixDescs)
+        if (d.pixfmt == pixfmt) return &d;
+    (void)fail(YOLO2_ERROR, "%s%sunknown pixel format 0x%x (YOLO2_PIX_GREY8, YOLO2_PIX_RGB24, YOLO2_PIX_YUYV, YOLO2_PIX_NV12 or YOLO2_PIX_I420)",
+               who ? who : "", who ? ": " : "", (unsigned)pixfmt);
+    return nullptr;
+}
+
+const Y2PixDesc *y2_pix_desc_ch(int ch)
+{
+    for (const Y2PixDesc &d : kPixDescs)
+        if (d.ch == ch) return &d;
+    return nullptr;
+}
+
+int y2_pix_check_parity(const Y2PixDesc &d, int w, int h, const char *who, int frame)
+{
+    const bool bad_w = d.even_w && (w & 1);
+    if (!bad_w && !(d.even_h && (h & 1))) return YOLO2_SUCCESS;
+    if (frame < 0) return fail(YOLO2_ERROR, "%s: %s frames have an even %s, not %d", who, d.name, bad_w ? "width" : "height", bad_w ? w : h);
+    return fail(YOLO2_ERROR, "%s: %s frames have an even %s, not %d (frame %d)", who, d.name, bad_w ? "width" : "height", bad_w ? w : h, frame);
+}
+
+int y2_letterbox_args(int w, int h, int channels, int net_w, int net_h, LetterboxArgs &a, bool pix = false)
+{
+    const Y2PixDesc *d = y2_pix_desc_ch(channels);
+    if (w <= 0 || h <= 0 || net_w <= 1 || net_h <= 1 || !d || (d->kind != Y2_KIND_BYTES && !pix))
         return fail(YOLO2_ERROR, "letterbox: bad image geometry %dx%dx%d -> %dx%d", w, h, channels, net_w, net_h);
-    if (channels == 2 && (w & 1)) return fail(YOLO2_ERROR, "letterbox: YUYV frames have an even width, not %d", w);
+    if (const int rc = y2_pix_check_parity(*d, w, h, "letterbox", -1)) return rc;
     if ((long)w * h > (1L << 28)) return fail(YOLO2_ERROR, "letterbox: image too large");
     a.w = w; a.h = h; a.ch = channels; a.net_w = net_w; a.net_h = net_h;
     // letterbox_image, src/core/yolo_image.cpp:148-165
@@ -449,38 +481,44 @@ extern "C" int yolo2_hip_letterbox_u8(uint64_t image_dev, int w, int h, int chan
     return YOLO2_SUCCESS;
 }
 
-// pixfmt -> bytes per pixel (LetterboxArgs::ch) for the _pix entries; 0 and an error for anything else
-int y2_pix_channels(int pixfmt)
+// pixfmt -> LetterboxArgs::ch for the _pix entries; 0 and an error for anything else
+static int pix_ch(int pixfmt)
 {
-    if (pixfmt == YOLO2_PIX_GREY8) return 1;
-    if (pixfmt == YOLO2_PIX_RGB24) return 3;
-    if (pixfmt == YOLO2_PIX_YUYV) return 2;
-    (void)fail(YOLO2_ERROR, "unknown pixel format 0x%x (YOLO2_PIX_GREY8, YOLO2_PIX_RGB24 or YOLO2_PIX_YUYV)", (unsigned)pixfmt);
-    return 0;
+    const Y2PixDesc *d = y2_pix_desc(pixfmt, nullptr);
+    return d ? d->ch : 0;
 }
 
 extern "C" int yolo2_hip_letterbox_pix(uint64_t image_dev, int w, int h, int pixfmt, uint64_t frame_dev, int net_w, int net_h,
                                        void *stream)
 {
-    const int ch = y2_pix_channels(pixfmt);
-    if (!ch) return YOLO2_ERROR;
-    if (ch != 2) return yolo2_hip_letterbox_u8(image_dev, w, h, ch, frame_dev, net_w, net_h, stream);
+    const Y2PixDesc *d = y2_pix_desc(pixfmt, nullptr);
+    if (!d) return YOLO2_ERROR;
+    if (d->kind == Y2_KIND_BYTES) return yolo2_hip_letterbox_u8(image_dev, w, h, d->ch, frame_dev, net_w, net_h, stream);
     if (!image_dev || !frame_dev) return fail(YOLO2_ERROR, "null buffer address");
-    if (image_dev & 3) return fail(YOLO2_ERROR, "letterbox: a YUYV frame starts on a 4-byte boundary");   // (LbYuyv loads pixel pairs)
+    if (image_dev & (d->align - 1)) return fail(YOLO2_ERROR, "letterbox: a %s frame starts on a %u-byte boundary", d->name, d->align);
     LetterboxArgs a;
-    int rc = y2_letterbox_args(w, h, ch, net_w, net_h, a, true);
+    int rc = y2_letterbox_args(w, h, d->ch, net_w, net_h, a, true);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_letterbox_yuyv, dim3(blocks_for((long)3 * net_w * net_h, 256)), dim3(256), 0, (hipStream_t)stream,
+    const auto kernel = d->kind == Y2_KIND_YUYV ? k_letterbox_yuyv : (d->kind == Y2_KIND_NV12 ? k_letterbox_nv12 : k_letterbox_i420);
+    hipLaunchKernelGGL(kernel, dim3(blocks_for((long)3 * net_w * net_h, 256)), dim3(256), 0, (hipStream_t)stream,
                        (const uint8_t *)(uintptr_t)image_dev, (float *)(uintptr_t)frame_dev, a);
     HIP_TRY(hipGetLastError(), YOLO2_ERROR);
     return YOLO2_SUCCESS;
 }
 
-// the chunk letterbox of either kind of staging buffer (pix: YUYV frames, table items with ch == 2)
-void y2_launch_letterbox_batch(bool yuyv, const uint8_t *dbytes, float *din, int batch, hipStream_t st)
+// the chunk letterbox of every kind of staging buffer (Y2PixKind: what the table items' frames are), and its name
+const char *y2_letterbox_batch_kernel(int kind)
+{
+    static const char *const names[Y2_KIND_COUNT] = {"k_letterbox_u8_batch", "k_letterbox_yuyv_batch", "k_letterbox_nv12_batch", "k_letterbox_i420_batch"};
+    return names[kind];
+}
+
+void y2_launch_letterbox_batch(int kind, const uint8_t *dbytes, float *din, int batch, hipStream_t st)
 {
     const dim3 grid(blocks_for((long)YOLO2_FRAME_ELEMS, 256), batch);
-    if (yuyv) hipLaunchKernelGGL(k_letterbox_yuyv_batch, grid, dim3(256), 0, st, dbytes, din, (int)YOLO2_FRAME_ELEMS);
+    if (kind == Y2_KIND_YUYV) hipLaunchKernelGGL(k_letterbox_yuyv_batch, grid, dim3(256), 0, st, dbytes, din, (int)YOLO2_FRAME_ELEMS);
+    else if (kind == Y2_KIND_NV12) hipLaunchKernelGGL(k_letterbox_nv12_batch, grid, dim3(256), 0, st, dbytes, din, (int)YOLO2_FRAME_ELEMS);
+    else if (kind == Y2_KIND_I420) hipLaunchKernelGGL(k_letterbox_i420_batch, grid, dim3(256), 0, st, dbytes, din, (int)YOLO2_FRAME_ELEMS);
     else hipLaunchKernelGGL(k_letterbox_u8_batch, grid, dim3(256), 0, st, dbytes, din, (int)YOLO2_FRAME_ELEMS);   // the whole chunk in one launch
 }
 
@@ -488,7 +526,7 @@ void y2_launch_letterbox_batch(bool yuyv, const uint8_t *dbytes, float *din, int
 // `batch` images.  The bytes (not the 4x larger float frames) cross PCIe; letterboxing runs on the
 // GPU into the chunk's frame buffer.  Same three-stream pipeline as yolo2_hip_run_frames_int16:
 // upload of chunk k+1 (CPU staging copy + DMA) overlaps the kernels of chunk k and the download of k-1.
-// (channels: bytes per pixel; pix: called from the _pix entry, where 2 = YUYV is a format)
+// (channels: a Y2PixDesc::ch; pix: called from the _pix entry, where the camera and video formats are accepted)
 static int run_images_i16_host(yolo2_hip_ctx *c, const uint8_t *const *images, const int *widths, const int *heights, int channels, bool pix,
                                int n, int batch, int16_t *region, int *final_q)
 {
@@ -509,7 +547,7 @@ static int run_images_i16_host(yolo2_hip_ctx *c, const uint8_t *const *images, c
             if (!images[i]) return fail(YOLO2_ERROR, "null image %d", i);
             const int rc = y2_letterbox_args(widths[i], heights[i], channels, 416, 416, a, pix);
             if (rc) return rc;
-            sum += padded((size_t)widths[i] * heights[i] * channels);
+            sum += padded(y2_frame_bytes(widths[i], heights[i], channels));
         }
         cap = std::max(cap, sum);
     }
@@ -541,7 +579,7 @@ static int run_images_i16_host(yolo2_hip_ctx *c, const uint8_t *const *images, c
         if (k >= 2) drain(k - 2);   // buffer set b is free again once chunk k-2 has left it
         size_t off = table_bytes;
         for (int i = 0; i < nf; ++i) {
-            const size_t bytes = (size_t)widths[first + i] * heights[first + i] * channels;
+            const size_t bytes = y2_frame_bytes(widths[first + i], heights[first + i], channels);
             memcpy(hin[b] + off, images[first + i], bytes);
             offs[(size_t)i] = off;
             off += padded(bytes);
@@ -556,7 +594,7 @@ static int run_images_i16_host(yolo2_hip_ctx *c, const uint8_t *const *images, c
         Y2_TRY(hipMemcpyAsync(dbytes[b], hin[b], off, hipMemcpyHostToDevice, s_in), YOLO2_DMA_ERROR);
         Y2_TRY(hipEventRecord(e_in[b], s_in), YOLO2_ERROR);
         Y2_TRY(hipStreamWaitEvent(s_run, e_in[b], 0), YOLO2_ERROR);
-        y2_launch_letterbox_batch(channels == 2, dbytes[b], din[b], batch, s_run);
+        y2_launch_letterbox_batch(y2_ch_kind(channels), dbytes[b], din[b], batch, s_run);
         Y2_TRY(hipGetLastError(), YOLO2_ERROR);
         rc = yolo2_hip_run_batch_int16(c, (uint64_t)(uintptr_t)din[b], batch, (uint64_t)(uintptr_t)dout[b], &q, s_run);
         if (rc) break;
@@ -584,7 +622,7 @@ extern "C" int yolo2_hip_run_images_u8_host(yolo2_hip_ctx *c, const uint8_t *con
 extern "C" int yolo2_hip_run_images_pix_host(yolo2_hip_ctx *c, const uint8_t *const *images, const int *widths, const int *heights,
                                              int pixfmt, int n, int batch, int16_t *region, int *final_q)
 {
-    const int ch = y2_pix_channels(pixfmt);
+    const int ch = pix_ch(pixfmt);
     return ch ? run_images_i16_host(c, images, widths, heights, ch, true, n, batch, region, final_q) : YOLO2_ERROR;
 }
 
@@ -595,7 +633,7 @@ extern "C" int yolo2_hip_calib_images_pix_host(yolo2_hip_ctx *c, const uint8_t *
                                                int pixfmt, int n, int batch)
 {
     if (!c || !images || !widths || !heights) return fail(YOLO2_ERROR, "null argument");
-    const int channels = y2_pix_channels(pixfmt);
+    const int channels = pix_ch(pixfmt);
     if (!channels) return YOLO2_ERROR;
     if (n <= 0 || batch <= 0 || batch > 1024) return fail(YOLO2_ERROR, "bad image count %d / batch %d", n, batch);
     if (!c->f16_loaded || !c->wf32) return fail(YOLO2_ERROR, "fp32 weights not loaded (yolo2_hip_load_weights_fp32)");
@@ -612,7 +650,7 @@ extern "C" int yolo2_hip_calib_images_pix_host(yolo2_hip_ctx *c, const uint8_t *
             if (!images[i]) return fail(YOLO2_ERROR, "null image %d", i);
             const int rc = y2_letterbox_args(widths[i], heights[i], channels, 416, 416, a, true);
             if (rc) return rc;
-            sum += padded((size_t)widths[i] * heights[i] * channels);
+            sum += padded(y2_frame_bytes(widths[i], heights[i], channels));
         }
         cap = std::max(cap, sum);
     }
@@ -626,7 +664,7 @@ extern "C" int yolo2_hip_calib_images_pix_host(yolo2_hip_ctx *c, const uint8_t *
         const int nf = in_chunk(k), first = k * batch;
         size_t off = table_bytes;
         for (int i = 0; i < nf; ++i) {
-            const size_t bytes = (size_t)widths[first + i] * heights[first + i] * channels;
+            const size_t bytes = y2_frame_bytes(widths[first + i], heights[first + i], channels);
             memcpy(hin + off, images[first + i], bytes);
             offs[(size_t)i] = off;
             off += padded(bytes);
@@ -638,7 +676,7 @@ extern "C" int yolo2_hip_calib_images_pix_host(yolo2_hip_ctx *c, const uint8_t *
             if ((rc = y2_letterbox_args(widths[first + i], heights[first + i], channels, 416, 416, items[f].a, true))) return rc;
         }
         HIP_TRY(hipMemcpyAsync(dbytes, hin, off, hipMemcpyHostToDevice, P.s_run), YOLO2_DMA_ERROR);
-        y2_launch_letterbox_batch(channels == 2, dbytes, P.din[0].get(), batch, P.s_run);
+        y2_launch_letterbox_batch(y2_ch_kind(channels), dbytes, P.din[0].get(), batch, P.s_run);
         HIP_TRY(hipGetLastError(), YOLO2_ERROR);
         if ((rc = y2_calib_frames(c, (uint64_t)(uintptr_t)P.din[0].get(), batch, nf, P.s_run))) return rc;   // (synchronises: hin is free again)
     }
@@ -679,11 +717,11 @@ int y2_pipe_ensure_post(yolo2_hip_ctx *c, int batch, int cap)
 // k + 1 the moment it has finished chunk k (and the chunk's letterbox is done) instead of waiting for the slowest lane - the fork / join
 // per 64 frames and the lanes' end spread (0.3 - 0.7 ms of a 20 ms step in the bench loop) do not exist in a stream of chunks.  Only what
 // needs the whole region tensor waits for all of them: `done` receives the events to wait for.
-int y2_pipe_enqueue_i16(yolo2_hip_ctx *c, int b, bool yuyv, int batch, int *q, std::vector<hipEvent_t> *done)
+int y2_pipe_enqueue_i16(yolo2_hip_ctx *c, int b, int kind, int batch, int *q, std::vector<hipEvent_t> *done)
 {
     PipeBufs &P = c->pipe;
     done->clear();
-    y2_launch_letterbox_batch(yuyv, P.dbytes[b].get(), P.din[b].get(), batch, P.s_run);
+    y2_launch_letterbox_batch(kind, P.dbytes[b].get(), P.din[b].get(), batch, P.s_run);
     HIP_TRY(hipGetLastError(), YOLO2_ERROR);
     bool own_streams = c->laned && (int)c->lanes.size() <= 8;
     if (own_streams) for (yolo2_hip_ctx *l : c->lanes) own_streams = own_streams && l->lane_stream;
@@ -732,7 +770,7 @@ static int run_images_i16_dets(yolo2_hip_ctx *c, const uint8_t *const *images, c
             if (!images[i]) return fail(YOLO2_ERROR, "null image %d", i);
             const int rc = y2_letterbox_args(widths[i], heights[i], channels, 416, 416, a, pix);
             if (rc) return rc;
-            sum += padded((size_t)widths[i] * heights[i] * channels);
+            sum += padded(y2_frame_bytes(widths[i], heights[i], channels));
         }
         cap_bytes = std::max(cap_bytes, sum);
     }
@@ -767,7 +805,7 @@ static int run_images_i16_dets(yolo2_hip_ctx *c, const uint8_t *const *images, c
         if (k >= 2) drain(k - 2);   // buffer set b is free again once chunk k-2 has left it
         size_t off = table_bytes;
         for (int i = 0; i < nf; ++i) {
-            const size_t bytes = (size_t)widths[first + i] * heights[first + i] * channels;
+            const size_t bytes = y2_frame_bytes(widths[first + i], heights[first + i], channels);
             memcpy(P.hin[b].get() + off, images[first + i], bytes);
             offs[(size_t)i] = off;
             off += padded(bytes);
@@ -785,7 +823,7 @@ static int run_images_i16_dets(yolo2_hip_ctx *c, const uint8_t *const *images, c
         Y2_TRY(hipMemcpyAsync(P.post[b].geom.get(), P.hgeom[b].get(), (size_t)batch * gbytes, hipMemcpyHostToDevice, P.s_in), YOLO2_DMA_ERROR);
         Y2_TRY(hipEventRecord(P.e_in[b], P.s_in), YOLO2_ERROR);
         Y2_TRY(hipStreamWaitEvent(P.s_run, P.e_in[b], 0), YOLO2_ERROR);
-        if ((rc = y2_pipe_enqueue_i16(c, b, channels == 2, batch, &q, &net_done))) break;     // letterbox + network; lanes are not joined
+        if ((rc = y2_pipe_enqueue_i16(c, b, y2_ch_kind(channels), batch, &q, &net_done))) break;     // letterbox + network; lanes are not joined
         for (hipEvent_t e : net_done) Y2_TRY(hipStreamWaitEvent(P.s_out, e, 0), YOLO2_ERROR);
         // the step after the path, on the device that produced the tensor, straight from HBM - on the download stream, so that the
         // next chunk's letterbox and network need not wait for it (the tail is 64 workgroups for 0.7 ms: latency, not work)
@@ -815,7 +853,7 @@ extern "C" int yolo2_hip_run_images_pix_dets(yolo2_hip_ctx *c, const uint8_t *co
                                              int pixfmt, int n, int batch, float thresh, float nms, int flags, yolo2_hip_det *dets,
                                              int cap_per_frame, int *counts, int *final_q)
 {
-    const int ch = y2_pix_channels(pixfmt);
+    const int ch = pix_ch(pixfmt);
     return ch ? run_images_i16_dets(c, images, widths, heights, ch, true, n, batch, thresh, nms, flags, dets, cap_per_frame, counts, final_q)
               : YOLO2_ERROR;
 }
@@ -870,14 +908,14 @@ void y2_stage_images(uint8_t *dst, const uint8_t *const *images, const size_t *o
 
 // (y2_internal.hpp) The fp16 / split pass of the chunk in buffer set b on s_run, into dregf[b]: layers 0 + 1 from the chunk's bytes where
 // the pass fuses them, else chunk letterbox + the frame path.  Records e_run[b] behind it.
-int y2_pipe_enqueue_f16(yolo2_hip_ctx *c, yolo2_hip_ctx *run, bool fused, int b, bool yuyv, int batch)
+int y2_pipe_enqueue_f16(yolo2_hip_ctx *c, yolo2_hip_ctx *run, bool fused, int b, int kind, int batch)
 {
     PipeBufs &P = c->pipe;
     int rc;
     if (fused) {
-        rc = y2_f16_run_images(run, P.dbytes[b].get(), yuyv, batch, P.dregf[b].get(), P.s_run);
+        rc = y2_f16_run_images(run, P.dbytes[b].get(), kind, batch, P.dregf[b].get(), P.s_run);
     } else {
-        y2_launch_letterbox_batch(yuyv, P.dbytes[b].get(), P.din[b].get(), batch, P.s_run);
+        y2_launch_letterbox_batch(kind, P.dbytes[b].get(), P.din[b].get(), batch, P.s_run);
         HIP_TRY(hipGetLastError(), YOLO2_ERROR);
         rc = yolo2_hip_run_batch_fp16(run, (uint64_t)(uintptr_t)P.din[b].get(), batch, (uint64_t)(uintptr_t)P.dregf[b].get(), P.s_run);
     }
@@ -889,13 +927,14 @@ int y2_pipe_enqueue_f16(yolo2_hip_ctx *c, yolo2_hip_ctx *run, bool fused, int b,
 // The chunk loop of the images entries whose pass leaves an fp32 region tensor (fp16, split-fp16, int8).
 // dets == nullptr: region tensors to region_host; otherwise the records (the int16 dets entry's contract).
 // resolve(): the pass's own refusals (weights not loaded ...), called after the argument checks and before anything is touched;
-// enqueue(b, yuyv, batch): the network of the chunk in buffer set b on s_run into dregf[b], e_run[b] recorded behind it.
+// enqueue(b, kind, batch): the network of the chunk in buffer set b on s_run into dregf[b], e_run[b] recorded behind it.
 template <class Resolve, class Enqueue>
 static int run_images_regf(yolo2_hip_ctx *c, const uint8_t *const *images, const int *widths, const int *heights, int channels, bool pix, int n,
                            int batch, float *region_host, float thresh, float nms, int flags, yolo2_hip_det *dets, int cap, int *counts,
                            Resolve resolve, Enqueue enqueue)
 {
-    const bool want_dets = dets != nullptr, yuyv = channels == 2;
+    const bool want_dets = dets != nullptr;
+    const int kind = y2_ch_kind(channels);
     if (n <= 0 || batch <= 0 || (want_dets && cap <= 0))
         return fail(YOLO2_ERROR, "bad image count %d / batch %d / capacity %d", n, batch, want_dets ? cap : 1);
     if (want_dets && thresh < 0.f) return fail(YOLO2_ERROR, "negative threshold");
@@ -915,7 +954,7 @@ static int run_images_regf(yolo2_hip_ctx *c, const uint8_t *const *images, const
             LetterboxArgs a;
             if (!images[i]) return fail(YOLO2_ERROR, "null image %d", i);
             if ((rc = y2_letterbox_args(widths[i], heights[i], channels, 416, 416, a, pix))) return rc;
-            sum += padded((size_t)widths[i] * heights[i] * channels);
+            sum += padded(y2_frame_bytes(widths[i], heights[i], channels));
         }
         cap_bytes = std::max(cap_bytes, sum);
     }
@@ -948,7 +987,7 @@ static int run_images_regf(yolo2_hip_ctx *c, const uint8_t *const *images, const
         if (k >= 2) drain(k - 2);   // buffer set b is free again once chunk k-2 has left it
         size_t off = table_bytes;
         for (int i = 0; i < nf; ++i) {
-            sizes[(size_t)i] = (size_t)widths[first + i] * heights[first + i] * channels;
+            sizes[(size_t)i] = y2_frame_bytes(widths[first + i], heights[first + i], channels);
             offs[(size_t)i] = off;
             off += padded(sizes[(size_t)i]);
         }
@@ -966,7 +1005,7 @@ static int run_images_regf(yolo2_hip_ctx *c, const uint8_t *const *images, const
         if (want_dets) Y2_TRY(hipMemcpyAsync(P.post[b].geom.get(), P.hgeom[b].get(), (size_t)batch * gbytes, hipMemcpyHostToDevice, P.s_in), YOLO2_DMA_ERROR);
         Y2_TRY(hipEventRecord(P.e_in[b], P.s_in), YOLO2_ERROR);
         Y2_TRY(hipStreamWaitEvent(P.s_run, P.e_in[b], 0), YOLO2_ERROR);
-        if ((rc = enqueue(b, yuyv, batch))) break;
+        if ((rc = enqueue(b, kind, batch))) break;
         Y2_TRY(hipStreamWaitEvent(P.s_out, P.e_run[b], 0), YOLO2_ERROR);
         if (want_dets) {   // the tail on the download stream, straight from HBM (see yolo2_hip_run_images_u8_dets)
             if ((rc = y2_post_enqueue_f32(P.dregf[b].get(), batch, thresh, nms, cap, best_only, app_tail, &P.post[b], P.s_out))) break;
@@ -998,10 +1037,10 @@ static int run_images_f16(yolo2_hip_ctx *c, int split, const uint8_t *const *ima
             if (r == YOLO2_SUCCESS) fused = y2_f16_images_fused(run);
             return r;
         },
-        [&](int b, bool yuyv, int bt) { return y2_pipe_enqueue_f16(c, run, fused, b, yuyv, bt); });
+        [&](int b, int kind, int bt) { return y2_pipe_enqueue_f16(c, run, fused, b, kind, bt); });
     if (rc == YOLO2_SUCCESS)
-        c->images_l0[split] = fused ? std::string(y2_f16_images_kernel(run, channels == 2))
-                                    : std::string(channels == 2 ? "k_letterbox_yuyv_batch + " : "k_letterbox_u8_batch + ") + yolo2_hip_fp16_layer_kernel(run, 0);
+        c->images_l0[split] = fused ? std::string(y2_f16_images_kernel(run, y2_ch_kind(channels)))
+                                    : std::string(y2_letterbox_batch_kernel(y2_ch_kind(channels))) + " + " + yolo2_hip_fp16_layer_kernel(run, 0);
     return rc;
 }
 
@@ -1019,13 +1058,13 @@ static int run_images_i8(yolo2_hip_ctx *c, const uint8_t *const *images, const i
             fused = y2_i8_images_fused(c);
             return (int)YOLO2_SUCCESS;
         },
-        [&](int b, bool yuyv, int bt) {
+        [&](int b, int kind, int bt) {
             PipeBufs &P = c->pipe;
             int r;
             if (fused) {
-                r = y2_i8_run_images(c, P.dbytes[b].get(), yuyv, bt, P.dregf[b].get(), P.s_run);
+                r = y2_i8_run_images(c, P.dbytes[b].get(), kind, bt, P.dregf[b].get(), P.s_run);
             } else {
-                y2_launch_letterbox_batch(yuyv, P.dbytes[b].get(), P.din[b].get(), bt, P.s_run);
+                y2_launch_letterbox_batch(kind, P.dbytes[b].get(), P.din[b].get(), bt, P.s_run);
                 HIP_TRY(hipGetLastError(), YOLO2_ERROR);
                 r = yolo2_hip_run_batch_int8(c, (uint64_t)(uintptr_t)P.din[b].get(), bt, (uint64_t)(uintptr_t)P.dregf[b].get(), P.s_run);
             }
@@ -1034,8 +1073,8 @@ static int run_images_i8(yolo2_hip_ctx *c, const uint8_t *const *images, const i
             return (int)YOLO2_SUCCESS;
         });
     if (rc == YOLO2_SUCCESS)
-        c->images_front_i8 = fused ? std::string(y2_i8_front_kernel(channels == 2))
-                                   : std::string(channels == 2 ? "k_letterbox_yuyv_batch" : "k_letterbox_u8_batch") + " + k_i8_quant_input + k_conv_i8";
+        c->images_front_i8 = fused ? std::string(y2_i8_front_kernel(y2_ch_kind(channels)))
+                                   : std::string(y2_letterbox_batch_kernel(y2_ch_kind(channels))) + " + k_i8_quant_input + k_conv_i8";
     return rc;
 }
 
@@ -1043,7 +1082,7 @@ extern "C" int yolo2_hip_run_images_pix_int8_host(yolo2_hip_ctx *c, const uint8_
                                                   int pixfmt, int n, int batch, float *region_host)
 {
     if (!c || !images || !widths || !heights || !region_host) return fail(YOLO2_ERROR, "null argument");
-    const int ch = y2_pix_channels(pixfmt);
+    const int ch = pix_ch(pixfmt);
     return ch ? run_images_i8(c, images, widths, heights, ch, n, batch, region_host, 0.f, 0.f, 0, nullptr, 0, nullptr) : YOLO2_ERROR;
 }
 
@@ -1052,7 +1091,7 @@ extern "C" int yolo2_hip_run_images_pix_dets_int8(yolo2_hip_ctx *c, const uint8_
                                                   int cap_per_frame, int *counts)
 {
     if (!c || !images || !widths || !heights || !dets || !counts) return fail(YOLO2_ERROR, "null argument");
-    const int ch = y2_pix_channels(pixfmt);
+    const int ch = pix_ch(pixfmt);
     return ch ? run_images_i8(c, images, widths, heights, ch, n, batch, nullptr, thresh, nms, flags, dets, cap_per_frame, counts) : YOLO2_ERROR;
 }
 
@@ -1069,7 +1108,7 @@ extern "C" int yolo2_hip_run_images_pix_f16_host(yolo2_hip_ctx *c, int split, co
                                                  const int *heights, int pixfmt, int n, int batch, float *region_host)
 {
     if (!c || !images || !widths || !heights || !region_host) return fail(YOLO2_ERROR, "null argument");
-    const int ch = y2_pix_channels(pixfmt);
+    const int ch = pix_ch(pixfmt);
     return ch ? run_images_f16(c, split, images, widths, heights, ch, true, n, batch, region_host, 0.f, 0.f, 0, nullptr, 0, nullptr) : YOLO2_ERROR;
 }
 
@@ -1086,7 +1125,7 @@ extern "C" int yolo2_hip_run_images_pix_dets_f16(yolo2_hip_ctx *c, int split, co
                                                  yolo2_hip_det *dets, int cap_per_frame, int *counts)
 {
     if (!c || !images || !widths || !heights || !dets || !counts) return fail(YOLO2_ERROR, "null argument");
-    const int ch = y2_pix_channels(pixfmt);
+    const int ch = pix_ch(pixfmt);
     return ch ? run_images_f16(c, split, images, widths, heights, ch, true, n, batch, nullptr, thresh, nms, flags, dets, cap_per_frame, counts)
               : YOLO2_ERROR;
 }

@@ -11,6 +11,7 @@
 #include "y2_internal.hpp"
 #include "kernels_i8.hpp"
 #include "kernels_i8_front.hpp"
+#include "kernels_i8_front_pix.hpp"
 
 using namespace y2;
 
@@ -336,9 +337,13 @@ extern "C" int yolo2_hip_run_batch_int8(yolo2_hip_ctx *c, uint64_t frames_dev, i
 // layers 2..30.  Profiling: the front's time is layer 1's slot (ev[1] .. ev[2]); layer 0's slot is empty.
 bool y2_i8_loaded(const yolo2_hip_ctx *c) { return c && c->i8 && c->i8->loaded; }
 bool y2_i8_images_fused(const yolo2_hip_ctx *c) { return !c->opt.i8_no_front; }
-const char *y2_i8_front_kernel(bool yuyv) { return yuyv ? "k_i8_front_yuyv" : "k_i8_front_u8"; }
+const char *y2_i8_front_kernel(int kind)
+{
+    static const char *const names[Y2_KIND_COUNT] = {"k_i8_front_u8", "k_i8_front_yuyv", "k_i8_front_nv12", "k_i8_front_i420"};
+    return names[kind];
+}
 
-int y2_i8_run_images(yolo2_hip_ctx *c, const uint8_t *lb, bool yuyv, int batch, float *region_dev, hipStream_t st)
+int y2_i8_run_images(yolo2_hip_ctx *c, const uint8_t *lb, int kind, int batch, float *region_dev, hipStream_t st)
 {
     int rc = need_i8(c);
     if (rc) return rc;
@@ -362,7 +367,9 @@ int y2_i8_run_images(yolo2_hip_ctx *c, const uint8_t *lb, bool yuyv, int batch, 
     a.q0 = s->act_q[0];
     a.leaky = kNet[0].leaky;
     const dim3 grid((unsigned)batch * kFrontTilesPerFrame), block(256);
-    if (yuyv) hipLaunchKernelGGL(k_i8_front_pix<LbYuyv>, grid, block, 0, st, a);
+    if (kind == Y2_KIND_YUYV) hipLaunchKernelGGL(k_i8_front_pix<LbYuyv>, grid, block, 0, st, a);
+    else if (kind == Y2_KIND_NV12) hipLaunchKernelGGL(k_i8_front_nv12, grid, block, 0, st, a);
+    else if (kind == Y2_KIND_I420) hipLaunchKernelGGL(k_i8_front_i420, grid, block, 0, st, a);
     else hipLaunchKernelGGL(k_i8_front_pix<LbInterleaved>, grid, block, 0, st, a);
     if (ev) (void)hipEventRecord(ev[2], st);
     if ((rc = run_layers(s, 2, &s->t[1], batch, (uint64_t)(uintptr_t)region_dev, st, ev))) return rc;

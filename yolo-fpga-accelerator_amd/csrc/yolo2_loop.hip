@@ -57,8 +57,9 @@ int y2_loop_check(int precision, const uint8_t *const *images, const int *widths
     if (out_format != YOLO2_LOOP_OUT_RGB24 && out_format != YOLO2_LOOP_OUT_JPEG)
         return fail(YOLO2_ERROR, "loop: unknown output format %d (YOLO2_LOOP_OUT_RGB24 or _JPEG)", out_format);
     if (!(flags & YOLO2_DETS_BEST_CLASS)) return fail(YOLO2_ERROR, "loop: flags must contain YOLO2_DETS_BEST_CLASS, the form the painter draws");
-    const int ch = y2_pix_channels(pixfmt);
-    if (!ch) return YOLO2_ERROR;
+    const Y2PixDesc *pd = y2_pix_desc(pixfmt, nullptr);
+    if (!pd) return YOLO2_ERROR;
+    const int ch = pd->ch;
     if (n <= 0 || batch <= 0 || batch > 1024 || cap_per_frame <= 0 || cap_per_frame > 65536)
         return fail(YOLO2_ERROR, "loop: bad image count %d / batch %d (1..1024) / capacity %d (1..65536)", n, batch, cap_per_frame);
     if (!(thresh >= 0.f)) return fail(YOLO2_ERROR, "loop: thresh %g is negative or not a number", (double)thresh);
@@ -94,8 +95,8 @@ static int loop_run(yolo2_hip_ctx *c, int precision, const uint8_t *const *image
 {
     int rc;
     const bool i16 = precision == YOLO2_LOOP_INT16, jpeg = out_format == YOLO2_LOOP_OUT_JPEG;
-    const int split = precision == YOLO2_LOOP_F32TOL ? 1 : 0, ch = y2_pix_channels(pixfmt), app_tail = (flags & YOLO2_DETS_APP_TAIL) ? 1 : 0;
-    const bool yuyv = ch == 2;
+    const int split = precision == YOLO2_LOOP_F32TOL ? 1 : 0, ch = y2_pix_desc(pixfmt, nullptr)->ch, app_tail = (flags & YOLO2_DETS_APP_TAIL) ? 1 : 0;
+    const int kind = y2_ch_kind(ch);
     if (i16 && !c->weights_loaded) return fail(YOLO2_ERROR, "loop: int16 weights not loaded");
     if (!i16 && (!c->f16_loaded || !c->f16_plan || !c->wf32)) return fail(YOLO2_ERROR, "loop: fp32 weights not loaded (yolo2_hip_load_weights_fp32)");
     HIP_TRY(hipSetDevice(c->device), YOLO2_INIT_ERROR);
@@ -115,7 +116,7 @@ static int loop_run(yolo2_hip_ctx *c, int precision, const uint8_t *const *image
         size_t in = lead, rgb = 0;
         for (int i = 0; i < in_chunk(k); ++i) {
             const int f = k * batch + i;
-            in += padded((size_t)widths[f] * heights[f] * ch);
+            in += padded(y2_frame_bytes(widths[f], heights[f], ch));
             jf[(size_t)i] = {widths[f], heights[f], rgb, caps[f]};
             rgb += padded((size_t)widths[f] * heights[f] * 3);
         }
@@ -212,7 +213,7 @@ static int loop_run(yolo2_hip_ctx *c, int precision, const uint8_t *const *image
         size_t off = lead, out_off = 0;
         for (int i = 0; i < nf; ++i) {
             const int f = first + i;
-            fbytes[(size_t)i] = (size_t)widths[f] * heights[f] * ch;
+            fbytes[(size_t)i] = y2_frame_bytes(widths[f], heights[f], ch);
             offs[(size_t)i] = off;
             out_offs[(size_t)i] = out_off;
             jf[(size_t)i] = {widths[f], heights[f], out_off, caps[f]};
@@ -252,9 +253,9 @@ static int loop_run(yolo2_hip_ctx *c, int precision, const uint8_t *const *image
         if (dec && (rc = y2_jpegdec_launch(dec, k))) { cleanup(); return rc; }   // ---- the decoder, into the slots
         // ---- the network, by the code the _pix_dets entry of the precision runs it with
         if (i16) {
-            rc = y2_pipe_enqueue_i16(c, b, yuyv, batch, &q, &wait_for);
+            rc = y2_pipe_enqueue_i16(c, b, kind, batch, &q, &wait_for);
         } else {
-            rc = y2_pipe_enqueue_f16(c, run, fused, b, yuyv, batch);
+            rc = y2_pipe_enqueue_f16(c, run, fused, b, kind, batch);
             wait_for.assign(1, P.e_run[b]);
         }
         if (rc) { cleanup(); return rc; }
@@ -292,8 +293,8 @@ static int loop_run(yolo2_hip_ctx *c, int precision, const uint8_t *const *image
 #undef Y2_TRY
     HIP_TRY(hipDeviceSynchronize(), YOLO2_ERROR);
     if (i16 && final_q) *final_q = q;
-    if (!i16) c->images_l0[split] = fused ? std::string(y2_f16_images_kernel(run, yuyv))
-                                          : std::string(yuyv ? "k_letterbox_yuyv_batch + " : "k_letterbox_u8_batch + ") + yolo2_hip_fp16_layer_kernel(run, 0);
+    if (!i16) c->images_l0[split] = fused ? std::string(y2_f16_images_kernel(run, kind))
+                                          : std::string(y2_letterbox_batch_kernel(kind)) + " + " + yolo2_hip_fp16_layer_kernel(run, 0);
     if (dec) {
         info.image_bytes_h2d = (uint64_t)(y2_jpegdec_uploaded(dec) + up_tables);
         y2_jpegdec_close(dec, up_tables);

@@ -292,6 +292,26 @@ bool yuyv_to_rgb24(const uint8_t *yuyv, uint8_t *rgb, int w, int h)
     return true;
 }
 
+// The same formula on a planar YUV 4:2:0 frame: pixel (x, y) takes Y(y, x) and the chroma of block (y >> 1, x >> 1)
+bool yuv420_to_rgb24(const uint8_t *frame, uint8_t *rgb, int w, int h, bool semi)
+{
+    if (!frame || !rgb || w <= 0 || h <= 0 || (w & 1) || (h & 1)) return false;
+    static const int kU[3] = {0, -100, 516}, kV[3] = {409, -208, 0};   // R, G, B
+    const size_t cw = (size_t)w / 2, ch = (size_t)h / 2;
+    const uint8_t *chroma = frame + (size_t)w * h;
+    for (int y = 0; y < h; ++y)
+        for (int x = 0; x < w; ++x) {
+            const size_t at = (size_t)(y >> 1) * cw + (size_t)(x >> 1);
+            const int d = (semi ? chroma[2 * at] : chroma[at]) - 128, e = (semi ? chroma[2 * at + 1] : chroma[cw * ch + at]) - 128;
+            const int luma = 298 * (frame[(size_t)y * w + x] - 16) + 128;
+            for (int k = 0; k < 3; ++k) {
+                const int v = (luma + kU[k] * d + kV[k] * e) >> 8;
+                rgb[((size_t)y * w + x) * 3 + k] = (uint8_t)std::min(std::max(v, 0), 255);
+            }
+        }
+    return true;
+}
+
 // letterbox_image, yolo_image.cpp:148-165
 Image letterbox_image(const Image &im, int w, int h)
 {
@@ -366,13 +386,14 @@ int draw_detections_rgb24(uint8_t *rgb, int w, int h, const DrawRecord *dets, in
     return drawn;
 }
 
-Image plain_box_frame(const uint8_t *bytes, int w, int h, bool yuyv, const DrawRecord *recs, int n, int classes)
+Image plain_box_frame(const uint8_t *bytes, int w, int h, int fmt, const DrawRecord *recs, int n, int classes)
 {
     Image im = make_image(w, h, 3);
-    std::vector<uint8_t> conv;   // the frame needs RGB pixels: a YUYV frame is converted here, on the host
-    if (yuyv) {
+    std::vector<uint8_t> conv;   // the frame needs RGB pixels: a YUYV / NV12 / I420 frame is converted here, on the host
+    if (fmt != kFrameRgb24) {
         conv.resize((size_t)im.w * im.h * 3);
-        if (!yuyv_to_rgb24(bytes, conv.data(), im.w, im.h)) throw std::runtime_error("bad YUYV frame");
+        if (fmt == kFrameYuyv ? !yuyv_to_rgb24(bytes, conv.data(), im.w, im.h) : !yuv420_to_rgb24(bytes, conv.data(), im.w, im.h, fmt == kFrameNv12))
+            throw std::runtime_error(fmt == kFrameYuyv ? "bad YUYV frame" : "bad YUV 4:2:0 frame");
     }
     const uint8_t *rgb = conv.empty() ? bytes : conv.data();
     for (int k = 0; k < 3; ++k)

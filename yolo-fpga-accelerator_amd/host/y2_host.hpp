@@ -59,6 +59,11 @@ Image letterbox_image(const Image &im, int w, int h);     // yolo_image.cpp:148-
 // shift, clamp to 0..255.  The GPU entries compute the same byte per fetched pixel (csrc/letterbox.hpp, LbYuyv).  False for an odd
 // or non-positive width / height (the reference converts pairs over the flat stream and leaves an odd frame's last pixel unwritten).
 bool yuyv_to_rgb24(const uint8_t *yuyv, uint8_t *rgb, int w, int h);
+// A planar YUV 4:2:0 frame (w h 3 / 2 bytes: the Y plane [h][w], then semi ? NV12's plane [h/2][w/2][2] of U V pairs : I420's U plane
+// [h/2][w/2] and V plane [h/2][w/2]) -> RGB24 by the same formula: pixel (x, y) from Y(y, x), U(y >> 1, x >> 1), V(y >> 1, x >> 1), chroma
+// replicated.  The library's own extension of the reference's conversion (the reference has no 4:2:0 input); the GPU entries compute
+// the same byte per fetched pixel (csrc/letterbox.hpp, LbYuv420).  False for a null pointer or an odd or non-positive width / height.
+bool yuv420_to_rgb24(const uint8_t *frame, uint8_t *rgb, int w, int h, bool semi);
 void draw_box(Image &im, int x1, int y1, int x2, int y2, int thick, float r, float g, float b);
 // The annotated frame of the reference's camera / video loop: yolo2_draw_detections_rgb24 (linux_app/src/yolo2_draw.c:276-369, called
 // at linux_app/src/main.c:1079-1091) on records of the library's yolo2_hip_det layout in the YOLO2_DETS_BEST_CLASS form (one per
@@ -70,10 +75,11 @@ struct DrawRecord {
     float prob, x, y, w, h;
 };
 int draw_detections_rgb24(uint8_t *rgb, int w, int h, const DrawRecord *dets, int n, float thresh, const char *const *labels, int n_labels);
-// The streaming CLI's own annotated frame (without --annotate-gpu): the frame's bytes (RGB24, or with yuyv a packed YUYV frame through
-// yuyv_to_rgb24) as a float image, one draw_box per record in a hue colour of its class, thickness max(1, h * .006).  No labels.
-// Throws std::runtime_error for a bad YUYV frame.
-Image plain_box_frame(const uint8_t *bytes, int w, int h, bool yuyv, const DrawRecord *recs, int n, int classes);
+// The streaming CLI's own annotated frame (without --annotate-gpu): the frame's bytes (fmt: RGB24, a packed YUYV frame through
+// yuyv_to_rgb24, or an NV12 / I420 frame through yuv420_to_rgb24) as a float image, one draw_box per record in a hue colour of its class, thickness max(1, h * .006).  No labels.
+// Throws std::runtime_error for a bad YUYV / 4:2:0 frame.
+enum { kFrameRgb24 = 0, kFrameYuyv = 1, kFrameNv12 = 2, kFrameI420 = 3 };
+Image plain_box_frame(const uint8_t *bytes, int w, int h, int fmt, const DrawRecord *recs, int n, int classes);
 int draw_font(char *chars, uint64_t *words);   // the packed font: 38 characters and their 35-bit glyph words (bit 5 * row + column)
 // The annotated frame as the JPEG stream the reference's MJPEG streamer sends (stb_image_write v1.09's stbi_write_jpg_to_func with 3
 // components, linux_app/src/yolo2_mjpeg_server.c:221-238), byte for byte (y2_jpeg.cpp; tests/golden/jpeg.npz): baseline, no

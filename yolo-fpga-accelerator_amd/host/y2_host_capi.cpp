@@ -134,12 +134,20 @@ int y2h_draw_detections_rgb24(uint8_t *rgb, int w, int h, const void *dets, int 
     return draw_detections_rgb24(rgb, w, h, static_cast<const DrawRecord *>(dets), n, thresh, labels, n_labels);
 }
 
+// yuv420_to_rgb24 (semi: NV12, otherwise I420): 0, or -1 (y2h_last_error) for a null pointer or an odd or non-positive width / height
+int y2h_yuv420_to_rgb24(const uint8_t *frame, uint8_t *rgb, int w, int h, int semi)
+{
+    if (yuv420_to_rgb24(frame, rgb, w, h, semi != 0)) return 0;
+    g_err = "yuv420_to_rgb24: bad frame " + std::to_string(w) + "x" + std::to_string(h) + " (NV12 / I420 frames have an even width and an even height)";
+    return -1;
+}
+
 // plain_box_frame, the CLI writer's own frame, for tools/annotate_report.py to time; returns the sum of the image, or -1
-// (y2h_last_error) for a bad YUYV frame
+// (y2h_last_error) for a bad frame; yuyv: 0 RGB24, 1 YUYV, 2 NV12, 3 I420
 double y2h_plain_box_frame(const uint8_t *bytes, int w, int h, int yuyv, const void *dets, int n, int classes)
 {
     try {
-        const Image im = plain_box_frame(bytes, w, h, yuyv != 0, static_cast<const DrawRecord *>(dets), n, classes);
+        const Image im = plain_box_frame(bytes, w, h, yuyv, static_cast<const DrawRecord *>(dets), n, classes);
         double sum = 0;
         for (float v : im.data) sum += v;
         return sum;

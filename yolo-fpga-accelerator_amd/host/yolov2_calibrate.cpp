@@ -4,7 +4,7 @@
 // The reference makes this set with a separate tool (weights/README.md step 2b); here it is the calibration tier of the HIP library
 // behind its C ABI (include/yolo2_hip.h, "calibration"): the exact fp32 pass runs the images, one abs-max per tensor gives the
 // ranges, the Q rule turns them into the three tables and the GPU quantises the resident fp32 streams.  Plain C++ host, like
-// yolov2_detect: it decodes the images (y2_codec.cpp), hands bytes over, and writes the five files in the reference's layout
+// yolov2_detect: it decodes the images (y2_codec.cpp) or reads raw video frames (--video-raw, any --video-pix-fmt), hands bytes over, and writes the five files in the reference's layout
 // (one pad element after every odd-length layer, yolo2_model.cpp:198-224).
 #include <algorithm>
 #include <cstdio>
@@ -22,7 +22,8 @@
 namespace {
 
 struct Config {
-    std::string weights_dir = "weights", out_dir, input_dir, input_list;
+    std::string weights_dir = "weights", out_dir, input_dir, input_list, video_raw;
+    int video_w = 640, video_h = 480, video_pixfmt = YOLO2_PIX_RGB24, max_frames = 0;   // --video-raw: as yolov2_detect's
     int batch = 8, device = 0;
     float headroom = 1.0f;
     std::string format = "int16";
@@ -31,10 +32,14 @@ struct Config {
 void print_usage(const char *prog)
 {
     std::printf(
-        "Usage: %s --weights <dir> (--input-dir <dir> | --input-list <file>) --out <dir> [options]\n"
+        "Usage: %s --weights <dir> (--input-dir <dir> | --input-list <file> | --video-raw <file>) --out <dir> [options]\n"
         "  --weights <dir>       Directory with weights_reorg.bin and bias.bin (fp32; default: weights)\n"
         "  --input-dir <dir>     Calibration images: every *.jpg / *.jpeg / *.png / *.ppm / *.pgm of a directory, sorted by name\n"
         "  --input-list <file>   Calibration images, one path per line\n"
+        "  --video-raw <file>    Calibration frames: raw video frames as yolov2_detect takes them, with --video-width <w> --video-height <h>\n"
+        "                        (default 640x480), --video-pix-fmt <rgb24|yuyv422|nv12|yuv420p> (default rgb24; also yuyv, i420: the GPU\n"
+        "                        reads the frames as they are; yuyv422 needs an even width, nv12 / yuv420p an even width and height) and\n"
+        "                        --max-frames <n> (default: all)\n"
         "  --out <dir>           Where weights_reorg_int16.bin, bias_int16.bin, weight_int16_Q.bin, bias_int16_Q.bin and iofm_Q.bin go\n"
         "  --batch <n>           Images per pass of the exact fp32 network (default 8)\n"
         "  --headroom <float>    Factor >= 1 kept free above every conv output's measured maximum (default 1)\n"
@@ -59,6 +64,18 @@ Config parse_args(int argc, char **argv)
         else if (arg == "--weights" && need()) cfg.weights_dir = argv[++i];
         else if (arg == "--input-dir" && need()) cfg.input_dir = argv[++i];
         else if (arg == "--input-list" && need()) cfg.input_list = argv[++i];
+        else if (arg == "--video-raw" && need()) cfg.video_raw = argv[++i];
+        else if (arg == "--video-width" && need()) cfg.video_w = std::atoi(argv[++i]);
+        else if (arg == "--video-height" && need()) cfg.video_h = std::atoi(argv[++i]);
+        else if (arg == "--max-frames" && need()) cfg.max_frames = std::atoi(argv[++i]);
+        else if (arg == "--video-pix-fmt" && need()) {
+            const std::string v = argv[++i];
+            if (v == "rgb24") cfg.video_pixfmt = YOLO2_PIX_RGB24;
+            else if (v == "yuyv422" || v == "yuyv") cfg.video_pixfmt = YOLO2_PIX_YUYV;
+            else if (v == "nv12") cfg.video_pixfmt = YOLO2_PIX_NV12;
+            else if (v == "yuv420p" || v == "i420") cfg.video_pixfmt = YOLO2_PIX_I420;
+            else { std::fprintf(stderr, "Unsupported --video-pix-fmt %s (rgb24 | yuyv422 | nv12 | yuv420p)\n", v.c_str()); std::exit(1); }
+        }
         else if (arg == "--out" && need()) cfg.out_dir = argv[++i];
         else if (arg == "--batch" && need()) cfg.batch = std::atoi(argv[++i]);
         else if (arg == "--headroom" && need()) cfg.headroom = (float)std::atof(argv[++i]);
@@ -66,10 +83,20 @@ Config parse_args(int argc, char **argv)
         else if (arg == "--format" && need()) cfg.format = argv[++i];
         else { std::fprintf(stderr, "Unknown argument: %s\n", arg.c_str()); print_usage(argv[0]); std::exit(1); }
     }
-    if (cfg.out_dir.empty() || (cfg.input_dir.empty() == cfg.input_list.empty())) {
-        std::fprintf(stderr, "--out and exactly one of --input-dir / --input-list are required\n");
+    if (cfg.out_dir.empty() || (int)!cfg.input_dir.empty() + (int)!cfg.input_list.empty() + (int)!cfg.video_raw.empty() != 1) {
+        std::fprintf(stderr, "--out and exactly one of --input-dir / --input-list / --video-raw are required\n");
         print_usage(argv[0]);
         std::exit(1);
+    }
+    if (!cfg.video_raw.empty()) {
+        const bool planar = cfg.video_pixfmt == YOLO2_PIX_NV12 || cfg.video_pixfmt == YOLO2_PIX_I420;
+        if (cfg.video_w < 1 || cfg.video_h < 1) { std::fprintf(stderr, "--video-width and --video-height must be positive\n"); std::exit(1); }
+        if ((cfg.video_pixfmt == YOLO2_PIX_YUYV && (cfg.video_w & 1)) || (planar && ((cfg.video_w | cfg.video_h) & 1))) {
+            std::fprintf(stderr, "--video-pix-fmt %s needs an even --video-width%s, not %dx%d\n",
+                         cfg.video_pixfmt == YOLO2_PIX_YUYV ? "yuyv422" : (cfg.video_pixfmt == YOLO2_PIX_NV12 ? "nv12" : "yuv420p"),
+                         planar ? " and --video-height" : "", cfg.video_w, cfg.video_h);
+            std::exit(1);
+        }
     }
     if (cfg.format != "int16" && cfg.format != "int8") { std::fprintf(stderr, "--format must be int16 or int8\n"); std::exit(1); }
     if (cfg.batch < 1 || cfg.batch > 1024) { std::fprintf(stderr, "--batch must be 1..1024\n"); std::exit(1); }
@@ -98,6 +125,25 @@ std::vector<std::string> list_inputs(const Config &cfg)
     }
     if (files.empty()) throw std::runtime_error("no calibration images");
     return files;
+}
+
+// the whole frames of a raw video file, as they are (a trailing partial frame is dropped)
+std::vector<std::vector<uint8_t>> read_video_frames(const Config &cfg)
+{
+    const size_t px = (size_t)cfg.video_w * cfg.video_h;
+    const size_t bytes = cfg.video_pixfmt == YOLO2_PIX_YUYV ? 2 * px
+                         : (cfg.video_pixfmt == YOLO2_PIX_NV12 || cfg.video_pixfmt == YOLO2_PIX_I420 ? px * 3 / 2 : 3 * px);
+    std::ifstream in(cfg.video_raw, std::ios::binary);
+    if (!in) throw std::runtime_error("Cannot open " + cfg.video_raw);
+    std::vector<std::vector<uint8_t>> frames;
+    while (cfg.max_frames <= 0 || (int)frames.size() < cfg.max_frames) {
+        std::vector<uint8_t> f(bytes);
+        in.read(reinterpret_cast<char *>(f.data()), (std::streamsize)bytes);
+        if ((size_t)in.gcount() != bytes) break;
+        frames.push_back(std::move(f));
+    }
+    if (frames.empty()) throw std::runtime_error("no whole frame in " + cfg.video_raw);
+    return frames;
 }
 
 std::vector<float> read_floats(const std::string &path, size_t want)
@@ -138,7 +184,8 @@ void check(int rc)
 
 int run(const Config &cfg)
 {
-    const std::vector<std::string> files = list_inputs(cfg);
+    const bool video = !cfg.video_raw.empty();
+    const std::vector<std::string> files = video ? std::vector<std::string>() : list_inputs(cfg);
     const std::vector<float> w = read_floats(cfg.weights_dir + "/weights_reorg.bin", (size_t)YOLO2_N_WEIGHTS);
     const std::vector<float> b = read_floats(cfg.weights_dir + "/bias.bin", (size_t)YOLO2_N_BIAS);
     std::vector<y2h::ImageU8> images;
@@ -146,12 +193,14 @@ int run(const Config &cfg)
     std::vector<const uint8_t *> ptrs;
     std::vector<int> ws, hs;
     for (const y2h::ImageU8 &im : images) { ptrs.push_back(im.rgb.data()); ws.push_back(im.w); hs.push_back(im.h); }
+    const std::vector<std::vector<uint8_t>> frames = video ? read_video_frames(cfg) : std::vector<std::vector<uint8_t>>();
+    for (const std::vector<uint8_t> &f : frames) { ptrs.push_back(f.data()); ws.push_back(cfg.video_w); hs.push_back(cfg.video_h); }
 
     yolo2_hip_ctx *ctx = nullptr;
     check(yolo2_hip_create(cfg.device, &ctx));
     struct Guard { yolo2_hip_ctx *c; ~Guard() { yolo2_hip_destroy(c); } } guard{ctx};
     check(yolo2_hip_load_weights_fp32(ctx, w.data(), w.size(), b.data(), b.size()));
-    check(yolo2_hip_calib_images_pix_host(ctx, ptrs.data(), ws.data(), hs.data(), YOLO2_PIX_RGB24, (int)images.size(), cfg.batch));
+    check(yolo2_hip_calib_images_pix_host(ctx, ptrs.data(), ws.data(), hs.data(), video ? cfg.video_pixfmt : YOLO2_PIX_RGB24, (int)ptrs.size(), cfg.batch));
     float act_max[YOLO2_N_CONV + 1], w_max[YOLO2_N_CONV], b_max[YOLO2_N_CONV];
     long seen = 0;
     check(yolo2_hip_calib_stats(ctx, act_max, w_max, b_max, &seen));

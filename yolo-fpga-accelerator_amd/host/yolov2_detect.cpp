@@ -12,7 +12,7 @@
 // `--batch N` runs the same frame N times through one batched call to show the batched entry.
 //
 // Streaming frontend (the role of the reference's yolo2_linux --video/--camera loop, linux_app/src/main.c:878-1288):
-//   --input-list <file> | --input-dir <dir> | --video-raw <file|-> --video-width W --video-height H [--video-pix-fmt rgb24|yuyv422]
+//   --input-list <file> | --input-dir <dir> | --video-raw <file|-> --video-width W --video-height H [--video-pix-fmt rgb24|yuyv422|nv12|yuv420p]
 //   | --video-mjpeg <file|-> (concatenated JPEG streams); --decode gpu sends baseline JPEG streams to the device compressed
 // Frames are taken in chunks of --batch per device, go to the GPU as BYTES (letterbox on the GPU), through the
 // int16 network on --devices a,b,... (contiguous frame shards, weights broadcast once by the library) and through the
@@ -69,7 +69,7 @@ struct AppConfig {
     int jpeg_quality = 80;          // --jpeg-quality, the reference streamer's default
     bool loop_gpu = false;          // --loop-gpu: records and annotated frames from ONE accelerator call per chunk (yolo2_hip_loop_images_pix)
     int video_w = 640, video_h = 480;
-    int video_pixfmt = YOLO2_PIX_RGB24; // --video-pix-fmt: what a --video-raw frame holds (RGB24, or packed YUYV 4:2:2 read by the GPU as it is)
+    int video_pixfmt = YOLO2_PIX_RGB24; // --video-pix-fmt: what a --video-raw frame holds (RGB24, or packed YUYV 4:2:2 / planar NV12 / I420 read by the GPU as they are)
     int max_frames = 0;                // 0 = all
     int infer_every = 1;
     std::string post = "gpu";          // region + boxes + NMS: gpu | host
@@ -112,6 +112,8 @@ void print_usage(const char *prog)
         "  --video-pix-fmt <rgb24|yuyv422>   what --video-raw holds (default rgb24).  yuyv422 (also: yuyv): packed YUYV 4:2:2, a V4L2 camera's\n"
         "                        native frames (`ffmpeg -f v4l2 -pix_fmt yuyv422 ... -f rawvideo -`), 2 bytes per pixel, even width; they go to\n"
         "                        the GPU as they are and are converted where they are read (every --precision, --devices)\n"
+        "                        nv12 | yuv420p (also: i420): planar YUV 4:2:0, what video decoders emit (`ffmpeg -i file -f rawvideo -pix_fmt\n"
+        "                        nv12 -`), w * h * 3 / 2 bytes per frame, even width and height; read and converted on the GPU the same way\n"
         "  --video-mjpeg <file|->  Concatenated JPEG streams, what a camera delivers as MJPEG; each frame ends where its stream does\n"
         "  --decode <host|gpu>   Where JPEG streams are decoded (default host: the decode pool).  gpu, with --input-list, --input-dir or\n"
         "                        --video-mjpeg and --post gpu: baseline 1- and 3-component streams go to the device compressed and are decoded\n"
@@ -144,7 +146,7 @@ void print_usage(const char *prog)
         "                        linux_app/src/yolo2_postprocess.c (float sigmoid / softmax / boxes, NMS at every --nms)\n"
         "  --precision int16 | fp16 | fp32fast   also when streaming: fp16 / fp32fast read weights_reorg.bin + bias.bin and run layers 0+1\n"
         "                        straight from the image bytes on the matrix cores (yolo2_hip_run_images_pix_dets_f16)\n"
-        "  --precision int8      also when streaming (--input-list, --input-dir, --video-raw with rgb24 or yuyv422), on one device with\n"
+        "  --precision int8      also when streaming (--input-list, --input-dir, --video-raw in any --video-pix-fmt), on one device with\n"
         "                        --post gpu: one kernel goes from the image bytes to layer 1 (yolo2_hip_run_images_pix_dets_int8); --jsonl,\n"
         "                        --tail app and --annotate-gpu --save-annotated-dir work as for fp16.  Refused: --loop-gpu and more than one\n"
         "                        device (the loop and multi-GPU entries have no int8 form)\n",
@@ -194,7 +196,9 @@ AppConfig parse_args(int argc, char **argv)
             const std::string v = argv[++i];
             if (v == "rgb24") cfg.video_pixfmt = YOLO2_PIX_RGB24;
             else if (v == "yuyv422" || v == "yuyv") cfg.video_pixfmt = YOLO2_PIX_YUYV;
-            else { std::fprintf(stderr, "Unsupported --video-pix-fmt %s (rgb24 | yuyv422)\n", v.c_str()); std::exit(1); }
+            else if (v == "nv12") cfg.video_pixfmt = YOLO2_PIX_NV12;
+            else if (v == "yuv420p" || v == "i420") cfg.video_pixfmt = YOLO2_PIX_I420;
+            else { std::fprintf(stderr, "Unsupported --video-pix-fmt %s (rgb24 | yuyv422 | nv12 | yuv420p)\n", v.c_str()); std::exit(1); }
         }
         else if (arg == "--max-frames" && need("")) cfg.max_frames = std::atoi(argv[++i]);
         else if (arg == "--infer-every" && need("")) cfg.infer_every = std::max(1, std::atoi(argv[++i]));
@@ -275,6 +279,22 @@ AppConfig parse_args(int argc, char **argv)
     if (cfg.video_pixfmt == YOLO2_PIX_YUYV && !cfg.video_raw.empty() && (cfg.video_w & 1)) {
         std::fprintf(stderr, "--video-pix-fmt yuyv422 needs an even --video-width, not %d\n", cfg.video_w);
         std::exit(1);
+    }
+    if ((cfg.video_pixfmt == YOLO2_PIX_NV12 || cfg.video_pixfmt == YOLO2_PIX_I420) && !cfg.video_raw.empty() && ((cfg.video_w | cfg.video_h) & 1)) {
+        std::fprintf(stderr, "--video-pix-fmt %s needs an even --video-width and --video-height, not %dx%d\n",
+                     cfg.video_pixfmt == YOLO2_PIX_NV12 ? "nv12" : "yuv420p", cfg.video_w, cfg.video_h);
+        std::exit(1);
+    }
+    // a raw file says nothing about what it holds, so a file that cannot be read is reported here with what would have been read from
+    // it, before anything is loaded (std::filesystem, not an open: the path may be a FIFO whose writer must not see a reader come and go)
+    if (!cfg.video_raw.empty() && cfg.video_raw != "-") {
+        std::error_code ec;
+        if (!std::filesystem::exists(cfg.video_raw, ec) || std::filesystem::is_directory(cfg.video_raw, ec)) {
+            const char *fmt = cfg.video_pixfmt == YOLO2_PIX_YUYV ? "yuyv422" : cfg.video_pixfmt == YOLO2_PIX_NV12 ? "nv12"
+                              : cfg.video_pixfmt == YOLO2_PIX_I420 ? "yuv420p" : "rgb24";
+            std::fprintf(stderr, "Cannot read --video-raw %s (%dx%d frames, --video-pix-fmt %s)\n", cfg.video_raw.c_str(), cfg.video_w, cfg.video_h, fmt);
+            std::exit(1);
+        }
     }
     return cfg;
 }
@@ -368,10 +388,22 @@ std::vector<OutDet> best_class_dets(const std::vector<y2h::Detection> &dets, int
     return out;
 }
 
+// bytes of one --video-raw frame
+static size_t video_frame_bytes(int w, int h, int pixfmt)
+{
+    const size_t px = (size_t)w * h;
+    return pixfmt == YOLO2_PIX_YUYV ? 2 * px : (pixfmt == YOLO2_PIX_NV12 || pixfmt == YOLO2_PIX_I420 ? px * 3 / 2 : 3 * px);
+}
+// y2h::plain_box_frame's name for it
+static int host_frame_fmt(int pixfmt)
+{
+    return pixfmt == YOLO2_PIX_YUYV ? y2h::kFrameYuyv : pixfmt == YOLO2_PIX_NV12 ? y2h::kFrameNv12 : pixfmt == YOLO2_PIX_I420 ? y2h::kFrameI420 : y2h::kFrameRgb24;
+}
+
 struct SrcFrame {
     std::string source;
     int frame_index = 0;    // 1-based position in the stream
-    y2h::ImageU8 img;       // (a --video-pix-fmt yuyv422 frame: img.rgb holds its 2 w h YUYV bytes, as they were read)
+    y2h::ImageU8 img;       // (a --video-pix-fmt yuyv422 / nv12 / yuv420p frame: img.rgb holds its 2 w h / 1.5 w h bytes, as they were read)
     std::vector<uint8_t> jpeg;   // --video-mjpeg: the frame's stream; --decode gpu: the stream that goes to the device (img then has w, h only)
 };
 
@@ -422,7 +454,7 @@ class FrameSource {
             SrcFrame f;
             if (mode_ == "video") {
                 f.img.w = cfg_.video_w; f.img.h = cfg_.video_h;
-                f.img.rgb.resize((size_t)cfg_.video_w * cfg_.video_h * (cfg_.video_pixfmt == YOLO2_PIX_YUYV ? 2 : 3));
+                f.img.rgb.resize(video_frame_bytes(cfg_.video_w, cfg_.video_h, cfg_.video_pixfmt));
                 const size_t rd = std::fread(f.img.rgb.data(), 1, f.img.rgb.size(), raw_);
                 if (rd != f.img.rgb.size()) return false;    // EOF (a trailing partial frame is dropped like the reference's reader)
                 f.source = cfg_.video_raw;
@@ -800,7 +832,7 @@ void run_stream(AppConfig cfg)
                     } else if (!cfg.save_dir.empty()) {
                         std::vector<y2h::DrawRecord> recs;
                         for (const OutDet &d : c.dets[(size_t)f]) recs.push_back({0, 0, d.class_id, d.prob, d.box.x, d.box.y, d.box.w, d.box.h});
-                        const y2h::Image im = y2h::plain_box_frame(fr.img.rgb.data(), fr.img.w, fr.img.h, pixfmt == YOLO2_PIX_YUYV, recs.data(),
+                        const y2h::Image im = y2h::plain_box_frame(fr.img.rgb.data(), fr.img.w, fr.img.h, host_frame_fmt(pixfmt), recs.data(),
                                                                    (int)recs.size(), last.classes);
                         char name[64];
                         std::snprintf(name, sizeof(name), "frame_%06d.ppm", infer_idx);

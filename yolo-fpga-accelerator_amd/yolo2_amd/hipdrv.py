@@ -71,17 +71,36 @@ EXPORTS = [
 
 # include/yolo2_hip.h YOLO2_PIX_*: the pixfmt argument of the _pix entries ("yuyv": packed YUYV 4:2:2, arrays uint8 [h][w][2])
 PIXFMTS = {"grey8": 1, "rgb24": 3, "yuyv": 0x56595559}
+# ... and the video formats, planar YUV 4:2:0: arrays uint8 [h * 3 / 2][w] - the Y plane's h rows, then h / 2 rows of chroma bytes.
+# A table of their own: PIXFMTS stays the camera formats' (tests pin it); every pixfmt= parameter takes a name of either.
+PIXFMTS_420 = {"nv12": 0x3231564E, "i420": 0x32315559}
+PLANAR_420 = tuple(PIXFMTS_420)
+
+
+def pix_code(pixfmt: str) -> int:
+    """the YOLO2_PIX_* value of a pixfmt name"""
+    if pixfmt in PIXFMTS:
+        return PIXFMTS[pixfmt]
+    if pixfmt in PIXFMTS_420:
+        return PIXFMTS_420[pixfmt]
+    raise ValueError(f"pixfmt must be None or one of {tuple(PIXFMTS) + PLANAR_420}, not {pixfmt!r}")
 
 
 def _pix_code(pixfmt, imgs) -> int:
     """the entries' pixfmt argument for a list of contiguous uint8 arrays, whose shapes must be that format's"""
-    if pixfmt not in PIXFMTS:
-        raise ValueError(f"pixfmt must be None or one of {tuple(PIXFMTS)}, not {pixfmt!r}")
-    last = {"grey8": None, "rgb24": 3, "yuyv": 2}[pixfmt]
+    code = pix_code(pixfmt)
+    last = {"grey8": None, "rgb24": 3, "yuyv": 2, "nv12": None, "i420": None}[pixfmt]
     for im in imgs:
+        if pixfmt in PLANAR_420 and (im.ndim != 2 or im.shape[0] % 3):
+            raise ValueError(f"a {pixfmt} image is uint8 [h * 3 / 2][w] with h even (rows a multiple of 3), not {im.shape}")
         if (im.ndim != 2 if last is None else im.ndim != 3 or im.shape[2] != last):
             raise ValueError(f"a {pixfmt} image is uint8 [h][w]{'' if last is None else f'[{last}]'}, not {im.shape}")
-    return PIXFMTS[pixfmt]
+    return code
+
+
+def _pix_hw(pixfmt, shape):
+    """(h, w) of the picture an array of that shape holds: a planar 4:2:0 array has h * 3 / 2 rows"""
+    return (shape[0] * 2 // 3 if pixfmt in PLANAR_420 else shape[0]), shape[1]
 
 
 _hip = None      # the HIP runtime itself, for _stream_sync only
@@ -107,8 +126,8 @@ def _stream_sync(stream: int):
 
 
 def letterbox_pix(image: np.ndarray, pixfmt: str, net_w: int = 416, net_h: int = 416, stream: int = 0) -> np.ndarray:
-    """letterbox_u8 with a pixel format (yolo2_hip_letterbox_pix): "grey8" [h][w], "rgb24" [h][w][3] or "yuyv" [h][w][2] (packed
-    YUYV 4:2:2, converted per fetched pixel on the GPU) -> float [3][net_h][net_w] frame."""
+    """letterbox_u8 with a pixel format (yolo2_hip_letterbox_pix): "grey8" [h][w], "rgb24" [h][w][3], "yuyv" [h][w][2] (packed
+    YUYV 4:2:2) or "nv12" / "i420" [h * 3 / 2][w] (planar YUV 4:2:0), converted per fetched pixel on the GPU -> float [3][net_h][net_w] frame."""
     return letterbox_u8(image, net_w, net_h, pixfmt=pixfmt, stream=stream)
 
 
@@ -128,7 +147,7 @@ def letterbox_u8(image_hwc: np.ndarray, net_w: int = 416, net_h: int = 416, pixf
         if code is None:
             check(L.yolo2_hip_letterbox_u8(src, im.shape[1], im.shape[0], ch, dst, net_w, net_h, C.c_void_p(stream)), "yolo2_hip_letterbox_u8")
         else:
-            check(L.yolo2_hip_letterbox_pix(src, im.shape[1], im.shape[0], code, dst, net_w, net_h, C.c_void_p(stream)), "yolo2_hip_letterbox_pix")
+            check(L.yolo2_hip_letterbox_pix(src, im.shape[1], _pix_hw(pixfmt, im.shape)[0], code, dst, net_w, net_h, C.c_void_p(stream)), "yolo2_hip_letterbox_pix")
         if stream:
             _stream_sync(stream)
         check(L.yolo2_hip_memcpy_d2h(out.ctypes.data_as(C.c_void_p), dst, out.nbytes), "d2h")
@@ -544,7 +563,7 @@ class Yolo2Hip:
     def run_images_host(self, images, batch: int = 64, pixfmt=None):
         """images: list of uint8 arrays [h][w][3] (or [h][w] grey) of arbitrary sizes -> region tensors.
         Bytes cross PCIe, letterboxing runs on the GPU (yolo2_hip_run_images_u8_host).  pixfmt "grey8" / "rgb24" / "yuyv" (arrays
-        [h][w][2]) names the format instead (yolo2_hip_run_images_pix_host); None infers grey / RGB from the shape."""
+        [h][w][2]) / "nv12" / "i420" (arrays [h * 3 / 2][w]) names the format instead (yolo2_hip_run_images_pix_host); None infers grey / RGB from the shape."""
         n, ptrs, ws, hs, fmt, _keep = _image_args(images, pixfmt)
         region = np.empty((n, 425, 13, 13), dtype=np.int16)
         q = C.c_int(0)
@@ -1084,7 +1103,7 @@ def _image_args(images, pixfmt=None):
     ch = (1 if imgs[0].ndim == 2 else imgs[0].shape[2]) if pixfmt is None else _pix_code(pixfmt, imgs)
     ptrs = (C.c_void_p * n)(*[im.ctypes.data for im in imgs])
     ws = (C.c_int * n)(*[im.shape[1] for im in imgs])
-    hs = (C.c_int * n)(*[im.shape[0] for im in imgs])
+    hs = (C.c_int * n)(*[_pix_hw(pixfmt, im.shape)[0] for im in imgs])
     return n, ptrs, ws, hs, ch, imgs
 
 
@@ -1097,7 +1116,7 @@ def run_images_dets(handle, images, batch: int, thresh: float, nms: float, cap: 
     records; letterbox, network and the tail run on the device(s), the region tensor never leaves HBM.  precision "fp16" /
     "fp32fast" (the split-fp16 pass) run the _dets_f16 entries instead (fp32 weights loaded); their final_q is None.
     precision "int8": yolo2_hip_run_images_pix_dets_int8 (int8 weights loaded, single device; final_q None).
-    pixfmt "grey8" / "rgb24" / "yuyv" (arrays [h][w][2]): the _pix_dets entries with that format; None infers grey / RGB.
+    pixfmt "grey8" / "rgb24" / "yuyv" (arrays [h][w][2]) / "nv12" / "i420" (arrays [h * 3 / 2][w]): the _pix_dets entries with that format; None infers grey / RGB.
     tail "app" sets YOLO2_DETS_APP_TAIL: the records are those of the reference's camera loop (yolo2_postprocess.c)."""
     if precision not in PRECISIONS:
         raise ValueError(f"precision must be one of {PRECISIONS}, not {precision!r}")
@@ -1284,21 +1303,23 @@ def _label_args(labels):
 
 
 def annotate_pix(image: np.ndarray, dets, pixfmt=None, thresh: float = 0.24, labels=None, stream: int = 0):
-    """yolo2_hip_annotate_pix: one image ("grey8" [h][w], "rgb24" [h][w][3], "yuyv" [h][w][2]; None infers grey / RGB) and its
+    """yolo2_hip_annotate_pix: one image ("grey8" [h][w], "rgb24" [h][w][3], "yuyv" [h][w][2], "nv12" / "i420" [h * 3 / 2][w]; None infers grey / RGB) and its
     records (DET_DTYPE, one per detection) -> (uint8 [h][w][3] with the reference's boxes and tags painted in, records drawn)."""
     im = np.ascontiguousarray(image, dtype=np.uint8)
-    code = _pix_code(pixfmt if pixfmt is not None else ("grey8" if im.ndim == 2 else "rgb24"), [im])
+    fmt = pixfmt if pixfmt is not None else ("grey8" if im.ndim == 2 else "rgb24")
+    code = _pix_code(fmt, [im])
+    h, w = _pix_hw(fmt, im.shape)
     d = np.ascontiguousarray(dets, dtype=DET_DTYPE).reshape(-1)
     lab, n_labels, _keep = _label_args(labels)
     L = lib()
     src, dst = C.c_uint64(0), C.c_uint64(0)
-    out = np.empty((im.shape[0], im.shape[1], 3), dtype=np.uint8)
+    out = np.empty((h, w, 3), dtype=np.uint8)
     drawn = C.c_int(0)
     try:
         check(L.yolo2_hip_alloc(max(im.nbytes, 16), C.byref(src)), "alloc")
         check(L.yolo2_hip_alloc(max(out.nbytes, 16), C.byref(dst)), "alloc")
         check(L.yolo2_hip_memcpy_h2d(src, im.ctypes.data_as(C.c_void_p), im.nbytes), "h2d")
-        check(L.yolo2_hip_annotate_pix(src, im.shape[1], im.shape[0], code, d.ctypes.data_as(C.c_void_p) if d.size else None, d.size,
+        check(L.yolo2_hip_annotate_pix(src, w, h, code, d.ctypes.data_as(C.c_void_p) if d.size else None, d.size,
                                        thresh, lab, n_labels, dst, C.byref(drawn), C.c_void_p(stream)), "yolo2_hip_annotate_pix")
         check(L.yolo2_hip_memcpy_d2h(out.ctypes.data_as(C.c_void_p), dst, out.nbytes), "d2h")
     finally:
@@ -1329,7 +1350,7 @@ def annotate_images(handle, images, dets, counts, batch: int, thresh: float, lab
         raise ValueError(f"dets is [n][cap] records for {n} images, not {d.shape}")
     cnt = np.ascontiguousarray(counts, dtype=np.int32)
     lab, n_labels, _keep = _label_args(labels)
-    outs = [np.empty((im.shape[0], im.shape[1], 3), dtype=np.uint8) for im in imgs]
+    outs = [np.empty(_pix_hw(fmt, im.shape) + (3,), dtype=np.uint8) for im in imgs]
     optrs = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
     drawn = np.zeros(n, dtype=np.int32)
     name = f"yolo2_hip_{'multi_' if multi else ''}annotate_images_pix_host"
@@ -1441,7 +1462,7 @@ def annotate_images_jpeg(handle, images, dets, counts, batch: int, thresh: float
     """yolo2_hip_annotate_images_pix_jpeg_host / its multi form: annotate_images, with the frames back as JPEG streams ->
     (list of bytes, records drawn per frame).  Room per frame: the raw frame's size, and - for the rare frame that compresses to
     more than that - a second call with the encoder's bound."""
-    shapes = [np.asarray(im).shape for im in images]
+    shapes = [_pix_hw(pixfmt, np.asarray(im).shape) for im in images]
     caps = [min(jpeg_bound(s[1], s[0]), s[0] * s[1] * 3 + 4096) for s in shapes]
     for attempt in range(2):
         rc, outs, sizes, drawn = annotate_images_jpeg_raw(handle, images, dets, counts, batch, thresh, quality, caps, labels=labels, pixfmt=pixfmt,
@@ -1506,7 +1527,7 @@ def loop_images(handle, images, pixfmt=None, precision: str = "int16", tail: str
     if precision not in LOOP_PRECISIONS:
         raise ValueError(f"precision must be one of {tuple(LOOP_PRECISIONS)}, not {precision!r}")
     flags = DETS_BEST_CLASS | (DETS_APP_TAIL if _check_tail(tail) else 0)
-    shapes = [np.asarray(im).shape for im in images]
+    shapes = [_pix_hw(pixfmt, np.asarray(im).shape) for im in images]
     jpeg = jpeg_quality is not None
     if jpeg:
         caps = [min(jpeg_bound(s[1], s[0]), s[0] * s[1] * 3 + 4096) for s in shapes]
