@@ -517,17 +517,28 @@ const char *yolo2_hip_images_layer0_kernel(yolo2_hip_ctx *ctx, int split);
  *                                      lets ffmpeg convert), and identity with swscale's RGB is not claimed.
  *                                      y2h_yuv420_to_rgb24 in libyolo2_host.so restates it on the host.  1.5 bytes per pixel
  *                                      cross PCIe, half of RGB24's.
+ *   YOLO2_PIX_BGR24                    packed B G R, 3 bytes per pixel (V4L2 'BGR3'): what OpenCV holds (cv2.VideoCapture, cv2.imread).
+ *                                      Rows of w * 3 bytes, any address, no constraint on w or h.
+ *   YOLO2_PIX_RGBA32, YOLO2_PIX_BGRA32 packed R G B X (V4L2 'AB24' = ffmpeg rgba / rgb0) and B G R X (V4L2 'AR24' = ffmpeg bgra / bgr0),
+ *                                      4 bytes per pixel: what GUI toolkits and screen capture hold.  Rows of w * 4 bytes, no
+ *                                      constraint on w or h.  X is never used: no result of any entry depends on the fourth byte.
+ *                                      For these three the GPU picks the R, G or B byte where it fetches the pixel (csrc/letterbox.hpp,
+ *                                      LbPacked), and every result of every entry is bit-identical to the RGB24 entry fed the same pixels
+ *                                      with the bytes reordered; y2h_packed_to_rgb24 in libyolo2_host.so restates the reorder.
  * A call is one format.  An odd YUYV / NV12 / I420 width, an odd NV12 / I420 height or an unknown pixfmt is YOLO2_ERROR
  * (yolo2_hip_last_error names it) before anything is launched; yolo2_hip_letterbox_pix also wants a YUYV image_dev on a 4-byte
- * boundary (NV12 and I420 frames may start at any address).  After a YUYV call yolo2_hip_images_layer0_kernel reports
+ * boundary, and an RGBA32 / BGRA32 one likewise (NV12, I420 and BGR24 frames may start at any address).  After a YUYV call yolo2_hip_images_layer0_kernel reports
  * k_conv0_pool_mfma_yuyv[<split>], or under f16_no_mfma0 "k_letterbox_yuyv_batch + " and the frame path's layer-0 kernel; after an
- * NV12 / I420 call the same names with _nv12 / _i420. */
+ * NV12 / I420 / BGR24 / RGBA32 / BGRA32 call the same names with _nv12 / _i420 / _bgr24 / _rgba32 / _bgra32. */
 enum {
     YOLO2_PIX_GREY8 = 1,
     YOLO2_PIX_RGB24 = 3,
     YOLO2_PIX_YUYV = 0x56595559, /* V4L2 fourcc 'YUYV' */
     YOLO2_PIX_NV12 = 0x3231564E, /* V4L2 fourcc 'NV12' */
-    YOLO2_PIX_I420 = 0x32315559  /* V4L2 fourcc 'YU12' = ffmpeg yuv420p */
+    YOLO2_PIX_I420 = 0x32315559, /* V4L2 fourcc 'YU12' = ffmpeg yuv420p */
+    YOLO2_PIX_BGR24 = 0x33524742,  /* V4L2 fourcc 'BGR3' = ffmpeg bgr24 */
+    YOLO2_PIX_RGBA32 = 0x34324241, /* V4L2 fourcc 'AB24' = ffmpeg rgba (rgb0) */
+    YOLO2_PIX_BGRA32 = 0x34325241  /* V4L2 fourcc 'AR24' = ffmpeg bgra (bgr0) */
 };
 int yolo2_hip_letterbox_pix(uint64_t image_dev, int w, int h, int pixfmt, uint64_t frame_dev, int net_w, int net_h, void *stream);
 int yolo2_hip_run_images_pix_host(yolo2_hip_ctx *ctx, const uint8_t *const *images, const int *widths, const int *heights,
@@ -546,7 +557,7 @@ int yolo2_hip_run_images_pix_dets_f16(yolo2_hip_ctx *ctx, int split, const uint8
  * The reference's camera / video loop ends every frame with yolo2_draw_detections_rgb24 (linux_app/src/yolo2_draw.c:276-369, called at
  * linux_app/src/main.c:1079-1091) and hands the RGB24 frame to --save-annotated-dir or the MJPEG streamer.  These entries make that
  * frame on the GPU, bit-identical, from the frame in its camera format (YOLO2_PIX_*: RGB24 copied, GREY8 replicated, YUYV / NV12 /
- * I420 converted as above) and records of the YOLO2_DETS_BEST_CLASS form (one per detection), whichever pass produced them; no weights are needed.
+ * I420 converted as above, BGR24 / RGBA32 / BGRA32 reordered) and records of the YOLO2_DETS_BEST_CLASS form (one per detection), whichever pass produced them; no weights are needed.
  *   which records   in array order, those with prob > thresh (and cls >= 0); later records paint over earlier ones
  *   box             corners (int)((x -+ w * 0.5f) * width) etc. in fp32, NaN / out-of-int-range products -> INT_MIN, each clamped to
  *                   the image; 2 pixels thick, every ring clamped again (yolo2_draw_rect_rgb24, :94-111); colour palette[cls % 8]
@@ -612,12 +623,14 @@ int yolo2_hip_annotate_images_pix_jpeg_host(yolo2_hip_ctx *ctx, const uint8_t *c
  * contain YOLO2_DETS_BEST_CLASS (the form the painter draws; YOLO2_DETS_APP_TAIL selects the camera loop's tail); one thresh serves the
  * records and the painter (main.c:1081).  out[f] (caps[f] bytes of room) and sizes[f]: with YOLO2_LOOP_OUT_RGB24 the bytes
  * yolo2_hip_annotate_images_pix_host writes for those records, sizes[f] = w * h * 3, and a caps[f] below that is refused up front;
- * with YOLO2_LOOP_OUT_JPEG (quality 1..100) the semantics of yolo2_hip_annotate_images_pix_jpeg_host.  drawn [n] may be NULL.
+ * with YOLO2_LOOP_OUT_JPEG (quality 1..100) the semantics of yolo2_hip_annotate_images_pix_jpeg_host; with YOLO2_LOOP_OUT_BGR24 the
+ * YOLO2_LOOP_OUT_RGB24 frame with bytes 0 and 2 of every pixel exchanged (what cv2.imshow / cv2.VideoWriter take; k_annotate_batch_bgr),
+ * same sizes and capacities, from any source format, quality ignored.  drawn [n] may be NULL.
  * A record that would be drawn but whose prob is not finite (or is 2^23 and more) is not drawn; the call then returns YOLO2_ERROR
  * naming the first such frame, everything else is complete.  Refused before any launch: what the entries it joins refuse.
  * Synchronous; batch <= 1024, cap_per_frame <= 65536. */
 enum { YOLO2_LOOP_INT16 = 0, YOLO2_LOOP_FP16 = 1, YOLO2_LOOP_F32TOL = 2 };
-enum { YOLO2_LOOP_OUT_RGB24 = 0, YOLO2_LOOP_OUT_JPEG = 1 };
+enum { YOLO2_LOOP_OUT_RGB24 = 0, YOLO2_LOOP_OUT_JPEG = 1, YOLO2_LOOP_OUT_BGR24 = 0x33524742 /* V4L2 fourcc 'BGR3' */ };
 int yolo2_hip_loop_images_pix(yolo2_hip_ctx *ctx, int precision, const uint8_t *const *images, const int *widths, const int *heights,
                               int pixfmt, int n, int batch, float thresh, float nms, int flags, yolo2_hip_det *dets, int cap_per_frame,
                               int *counts, int *final_q, const char *const *labels, int n_labels, int out_format, int quality,
@@ -734,7 +747,7 @@ int yolo2_hip_run_batch_int8_host(yolo2_hip_ctx *ctx, const float *frames, int b
  * yolo2_hip_run_images_pix_f16_host / _dets_f16 (chunks of `batch` images, 1..1024, a ragged last chunk repeats its last image;
  * staging, upload, kernels and download overlap on the context's three streams; region_host float [n][425][13][13]; the records
  * come from the float tail, flags YOLO2_DETS_BEST_CLASS / YOLO2_DETS_APP_TAIL).  pixfmt: any YOLO2_PIX_*.
- * One kernel (k_i8_front_u8 / k_i8_front_yuyv / k_i8_front_nv12 / k_i8_front_i420) goes from the chunk's bytes to layer 1's tensor: letterbox, the input rule above,
+ * One kernel (k_i8_front_u8 / k_i8_front_yuyv / k_i8_front_nv12 / k_i8_front_i420 / k_i8_front_bgr24 / k_i8_front_rgba32 / k_i8_front_bgra32) goes from the chunk's bytes to layer 1's tensor: letterbox, the input rule above,
  * layer 0 with its 27 inputs in one k step of v_mfma_i32_32x32x32_i8, and the 2x2 pool.  The result equals, bit for bit, the chunk
  * letterboxed (yolo2_hip_letterbox_pix) and run through yolo2_hip_run_batch_int8, which is what the entries do under option
  * i8_no_front.  The quantised input and layer 0's tensor (2 * batch * 416 * 416 * 32 bytes) are not allocated on this route.
@@ -745,7 +758,7 @@ int yolo2_hip_run_images_pix_int8_host(yolo2_hip_ctx *ctx, const uint8_t *const 
 int yolo2_hip_run_images_pix_dets_int8(yolo2_hip_ctx *ctx, const uint8_t *const *images, const int *widths, const int *heights,
                                        int pixfmt, int n, int batch, float thresh, float nms, int flags, yolo2_hip_det *dets,
                                        int cap_per_frame, int *counts);
-/* What the last int8 images call on ctx ran up to layer 1: "k_i8_front_u8", "k_i8_front_yuyv", "k_i8_front_nv12" or "k_i8_front_i420"; under i8_no_front
+/* What the last int8 images call on ctx ran up to layer 1: "k_i8_front_u8", "k_i8_front_yuyv", "k_i8_front_nv12", "k_i8_front_i420", "k_i8_front_bgr24", "k_i8_front_rgba32" or "k_i8_front_bgra32"; under i8_no_front
  * "k_letterbox_u8_batch + k_i8_quant_input + k_conv_i8" (or k_letterbox_yuyv_batch ...); "" before the first call. */
 const char *yolo2_hip_images_front_kernel_int8(yolo2_hip_ctx *ctx);
 /* Parity hook: the int8 tensor layer `layer_idx` (0..29; -1 = the quantised input) left behind in the last int8 run, frame `frame`,

@@ -35,7 +35,8 @@ struct AnnoHeader {
 struct AnnoFrame {
     unsigned long long src_off, out_off;   // the frame's source bytes / its RGB24 output, in bytes from the two base addresses
     int w, h, ch;                          // ch: source bytes per pixel - 1 grey, 3 RGB24, 2 packed YUYV 4:2:2 (w even, 4-byte aligned);
-                                           // kLbChNv12 / kLbChI420: planar YUV 4:2:0 (w and h even, any address)
+                                           // kLbChNv12 / kLbChI420: planar YUV 4:2:0 (w and h even, any address); kLbChBgr24: packed
+                                           // B G R (any address); kLbChRgba32 / kLbChBgra32: R G B X / B G R X dwords (4-byte aligned)
     int item0, n_items;                    // its items in the array, in record order
     int strips;                            // workgroups that have work on it: ceil(w * h / kAnnoStripPx)
 };
@@ -63,9 +64,15 @@ __device__ inline uint32_t anno_yuv420_px(const uint8_t *__restrict__ src, int w
     return anno_yuyv_px((uint32_t)src[(size_t)y * w + x] | (u << 8) | (v << 24), 0);
 }
 
+// c with bytes 0 and 2 exchanged and byte 3 cleared: B G R [X] <-> R | G << 8 | B << 16, one v_perm_b32
+__device__ inline uint32_t anno_swap_rb(uint32_t c) { return __byte_perm(c, 0u, 0x4012u); }
+
 // source pixel p of a frame -> R | G << 8 | B << 16
 __device__ inline uint32_t anno_load_px(const uint8_t *__restrict__ src, int ch, int p)
 {
+    if (ch == kLbChBgr24) return (uint32_t)src[(size_t)p * 3 + 2] | ((uint32_t)src[(size_t)p * 3 + 1] << 8) | ((uint32_t)src[(size_t)p * 3] << 16);
+    if (ch == kLbChRgba32) return reinterpret_cast<const uint32_t *>(src)[p] & 0xffffffu;   // (the fourth byte is dropped here)
+    if (ch == kLbChBgra32) return anno_swap_rb(reinterpret_cast<const uint32_t *>(src)[p]);
     if (ch == 3) return (uint32_t)src[(size_t)p * 3] | ((uint32_t)src[(size_t)p * 3 + 1] << 8) | ((uint32_t)src[(size_t)p * 3 + 2] << 16);
     if (ch == 1) return (uint32_t)src[p] * 0x010101u;
     return anno_yuyv_px(reinterpret_cast<const uint32_t *>(src)[p >> 1], p & 1);   // (the frame as one row of pairs)
@@ -172,9 +179,10 @@ __global__ __launch_bounds__(kItemsThreads) void k_draw_items(const y2d::DrawDet
     }
 }
 
-// grid (max strips of the chunk's frames, frames); table: AnnoHeader, AnnoFrame[frames], DrawItem[]
-__global__ __launch_bounds__(kAnnoThreads) void k_annotate_batch(const uint8_t *__restrict__ table, const uint8_t *__restrict__ src_base,
-                                                                 uint8_t *__restrict__ out_base)
+// The painter's body.  BGR: the output frame is packed B G R instead of R G B - one byte permute per pixel before the store.
+template <bool BGR>
+__device__ __forceinline__ void annotate_batch_tiles(const uint8_t *__restrict__ table, const uint8_t *__restrict__ src_base,
+                                                     uint8_t *__restrict__ out_base)
 {
     __shared__ uint64_t s_font[y2d::kDrawGlyphs];
     __shared__ DrawItem s_items[kAnnoPiece];
@@ -211,6 +219,17 @@ __global__ __launch_bounds__(kAnnoThreads) void k_annotate_batch(const uint8_t *
             col[4 * j + 1] = (d0 >> 24) | ((d1 & 0xffffu) << 8);
             col[4 * j + 2] = (d1 >> 16) | ((d2 & 0xffu) << 16);
             col[4 * j + 3] = d2 >> 8;
+        } else if (whole && src_al && fr.ch == kLbChBgr24) {   // RGB24's three dwords, every pixel's bytes 0 and 2 exchanged
+            const uint32_t *s = reinterpret_cast<const uint32_t *>(src + (size_t)p * 3);
+            const uint32_t d0 = s[0], d1 = s[1], d2 = s[2];
+            col[4 * j] = anno_swap_rb(d0);
+            col[4 * j + 1] = anno_swap_rb((d0 >> 24) | (d1 << 8));
+            col[4 * j + 2] = anno_swap_rb((d1 >> 16) | (d2 << 16));
+            col[4 * j + 3] = anno_swap_rb(d2 >> 8);
+        } else if (whole && (fr.ch == kLbChRgba32 || fr.ch == kLbChBgra32)) {   // one dword per pixel (4-byte aligned, as YUYV)
+            const uint32_t *s = reinterpret_cast<const uint32_t *>(src + (size_t)p * 4);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) col[4 * j + i] = fr.ch == kLbChBgra32 ? anno_swap_rb(s[i]) : (s[i] & 0xffffffu);
         } else if (whole && fr.ch == 2) {   // (a YUYV frame starts on a 4-byte boundary: the entries refuse any other)
             const uint32_t *s = reinterpret_cast<const uint32_t *>(src + (size_t)p * 2);
             const uint32_t d0 = s[0], d1 = s[1];
@@ -286,6 +305,10 @@ __global__ __launch_bounds__(kAnnoThreads) void k_annotate_batch(const uint8_t *
     }
 
     // ---- packed RGB24 out
+    if constexpr (BGR) {
+#pragma unroll
+        for (int k = 0; k < kAnnoGroups * 4; ++k) col[k] = anno_swap_rb(col[k]);
+    }
 #pragma unroll
     for (int j = 0; j < kAnnoGroups; ++j) {
         const int p = p_lo + (j * kAnnoThreads + tid) * 4;
@@ -307,6 +330,20 @@ __global__ __launch_bounds__(kAnnoThreads) void k_annotate_batch(const uint8_t *
             }
         }
     }
+}
+
+// grid (max strips of the chunk's frames, frames); table: AnnoHeader, AnnoFrame[frames], DrawItem[]
+__global__ __launch_bounds__(kAnnoThreads) void k_annotate_batch(const uint8_t *__restrict__ table, const uint8_t *__restrict__ src_base,
+                                                                 uint8_t *__restrict__ out_base)
+{
+    annotate_batch_tiles<false>(table, src_base, out_base);
+}
+
+// the same into packed BGR24 frames, what cv2.imshow / cv2.VideoWriter take (the loop's YOLO2_LOOP_OUT_BGR24)
+__global__ __launch_bounds__(kAnnoThreads) void k_annotate_batch_bgr(const uint8_t *__restrict__ table, const uint8_t *__restrict__ src_base,
+                                                                     uint8_t *__restrict__ out_base)
+{
+    annotate_batch_tiles<true>(table, src_base, out_base);
 }
 
 }  // namespace y2

@@ -26,4 +26,19 @@ __global__ __launch_bounds__(256) void k_conv0_pool_mfma_i420(const uint8_t *__r
     conv0_pool_mfma_tiles<SPLIT, true, LbYuv420<false>>(nullptr, lb, lb_first, w0, bias0, out, 416, 416, oWp, oPL, n_tile_total);
 }
 
+// Packed RGB in another byte order or with a fourth byte (LbPacked): BGR24, RGBA32, BGRA32.  The permutation is at the fetch, not in
+// layer 0's weights: the k order inside the MFMA, and with it every fp16 bit, is k_conv0_pool_mfma_u8's (tests/test_gpu_packed.py).
+#define Y2_CONV0_PACKED(NAME, BPP, SWAP)                                                                                                   \
+    template <bool SPLIT = false>                                                                                                          \
+    __global__ __launch_bounds__(256) void NAME(const uint8_t *__restrict__ lb, int lb_first, const float *__restrict__ w0,               \
+                                                const float *__restrict__ bias0, _Float16 *__restrict__ out, int oWp, int oPL,            \
+                                                int n_tile_total)                                                                          \
+    {                                                                                                                                      \
+        conv0_pool_mfma_tiles<SPLIT, true, LbPacked<BPP, SWAP>>(nullptr, lb, lb_first, w0, bias0, out, 416, 416, oWp, oPL, n_tile_total); \
+    }
+Y2_CONV0_PACKED(k_conv0_pool_mfma_bgr24, 3, true)
+Y2_CONV0_PACKED(k_conv0_pool_mfma_rgba32, 4, false)
+Y2_CONV0_PACKED(k_conv0_pool_mfma_bgra32, 4, true)
+#undef Y2_CONV0_PACKED
+
 }  // namespace y2

@@ -11,6 +11,9 @@
 // NV12 and I420 frames (planar YUV 4:2:0, what video decoders emit) go the same way through LbYuv420: k_letterbox_nv12[_batch] and
 // k_letterbox_i420[_batch], 1.5 bytes per pixel (tests/test_gpu_yuv420.py).
 //
+// Packed BGR24, RGBA32 and BGRA32 frames (what OpenCV, GUI toolkits and screen capture hold) go through LbPacked, which only picks
+// another byte: k_letterbox_bgr24[_batch], k_letterbox_rgba32[_batch], k_letterbox_bgra32[_batch] (tests/test_gpu_packed.py).
+//
 // Include AFTER kernels_pre.hpp, in the one translation unit that includes it (yolo2_hip.hip): LetterboxArgs / LetterboxItem are
 // kernels_pre.hpp's definitions there, and letterbox.hpp's restatement of them is switched off.
 #pragma once
@@ -74,5 +77,20 @@ __global__ void k_letterbox_i420_batch(const uint8_t *__restrict__ base, float *
 {
     letterbox_pix_batch<LbYuv420<false>>(base, out, frame_elems);
 }
+
+// ... and for packed BGR24 / RGBA32 / BGRA32 frames (LbPacked: BGR24 at any address, the 32-bit formats on a 4-byte boundary)
+#define Y2_LETTERBOX_PACKED(NAME, BPP, SWAP)                                                                                                  \
+    __global__ void NAME(const uint8_t *__restrict__ img, float *__restrict__ out, const LetterboxArgs a)                                    \
+    {                                                                                                                                         \
+        letterbox_pix_one<LbPacked<BPP, SWAP>>(img, out, a);                                                                                  \
+    }                                                                                                                                         \
+    __global__ void NAME##_batch(const uint8_t *__restrict__ base, float *__restrict__ out, int frame_elems)                                 \
+    {                                                                                                                                         \
+        letterbox_pix_batch<LbPacked<BPP, SWAP>>(base, out, frame_elems);                                                                     \
+    }
+Y2_LETTERBOX_PACKED(k_letterbox_bgr24, 3, true)
+Y2_LETTERBOX_PACKED(k_letterbox_rgba32, 4, false)
+Y2_LETTERBOX_PACKED(k_letterbox_bgra32, 4, true)
+#undef Y2_LETTERBOX_PACKED
 
 }  // namespace y2

@@ -6,7 +6,8 @@
 // is lb_part / lb_value's, in their order: the values are bit-identical (tests/test_gpu_images_f16.py).
 // The pixel fetch is a parameter too: LbInterleaved reads kernels_pre.hpp's 1 or 3 interleaved byte channels, LbYuyv turns a packed
 // YUYV 4:2:2 pixel into the R, G or B byte first (kernels_pix.hpp, k_conv0_pool_mfma_yuyv), LbYuv420 does the same for the planar
-// 4:2:0 frames of video decoders, NV12 and I420 (kernels_pix.hpp, kernels_f16_pix.hpp).
+// 4:2:0 frames of video decoders, NV12 and I420 (kernels_pix.hpp, kernels_f16_pix.hpp), LbPacked picks the R, G or B byte of a packed
+// BGR24 / RGBA32 / BGRA32 pixel, the frames OpenCV, GUI toolkits and screen capture hold.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -82,10 +83,31 @@ struct LbYuv420 {
     }
 };
 
+// Packed RGB in another byte order or with a fourth byte: BPP bytes per pixel, rows of a.w * BPP bytes; byte k (0 R, 1 G, 2 B) of pixel
+// x is row[x * BPP + (SWAP ? 2 - k : k)].  BPP 3, SWAP: BGR24 (V4L2 'BGR3', OpenCV's), byte loads, any address.  BPP 4: RGBA32 ('AB24':
+// R G B X) and, SWAP, BGRA32 ('AR24': B G R X); the pixel is one aligned dword (rows are 4 a.w bytes, the image starts on a 4-byte
+// boundary) and the fourth byte is shifted past, never into a result.  The byte is the source's own: everything after the fetch sees
+// what LbInterleaved would on the RGB24 frame with the bytes reordered.  (a.ch is a format code here, not a byte count, and is not read)
+constexpr int kLbChBgr24 = 24, kLbChRgba32 = 32, kLbChBgra32 = 33;   // LetterboxArgs::ch / AnnoFrame::ch of the three formats
+template <int BPP, bool SWAP>
+struct LbPacked {
+    static_assert(BPP == 3 || BPP == 4, "three packed bytes, or three and a fourth that is not used");
+    const uint8_t *row;   // row r, at channel k's byte (BPP 3) / at the pixel (BPP 4)
+    int shift;            // BPP 4: where channel k's byte sits in the pixel's dword
+    __device__ LbPacked(const uint8_t *__restrict__ img, const LetterboxArgs &a, int r, int k)
+        : row(img + ((size_t)r * a.w) * BPP + (BPP == 3 ? (SWAP ? 2 - k : k) : 0)), shift(8 * (SWAP ? 2 - k : k)) {}
+    __device__ uint8_t operator()(int x) const
+    {
+        if constexpr (BPP == 4) return (uint8_t)(reinterpret_cast<const uint32_t *>(row)[x] >> shift);
+        else return row[(size_t)x * 3];
+    }
+};
+
 // a fetch that converts: lb_part_q runs its operations on the fetch's bytes instead of on interleaved channels
 template <class F> struct LbConverts : std::false_type {};
 template <> struct LbConverts<LbYuyv> : std::true_type {};
 template <bool SEMI> struct LbConverts<LbYuv420<SEMI>> : std::true_type {};
+template <int BPP, bool SWAP> struct LbConverts<LbPacked<BPP, SWAP>> : std::true_type {};
 
 // kernels_pre.hpp's lb_part: the horizontally interpolated value part(c, r, k) of resize_image's first pass
 template <class Q = LbDiv255, class F = LbInterleaved>

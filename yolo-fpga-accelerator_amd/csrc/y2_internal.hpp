@@ -519,7 +519,7 @@ void y2_f16_plan_free(yolo2_hip_ctx *c);
 // (split 1, made here) - or YOLO2_ERROR without fp32 weights.  y2_f16_images_fused: that pass has the layer-0 step from bytes (not under
 // f16_no_mfma0: the entries then letterbox into frames and run the frame path).  y2_f16_run_images: the pass on a chunk of `batch`
 // frames whose staging buffer (LetterboxItem table + images) is at lb, enqueued on st; y2_f16_images_kernel names its layer-0 kernel.
-// kind: what the chunk's images are (Y2PixKind below) - interleaved bytes, packed YUYV 4:2:2 or planar 4:2:0 frames.
+// kind: what the chunk's images are (Y2PixKind below) - interleaved bytes, packed YUYV 4:2:2, planar 4:2:0 or packed BGR24 / RGBA32 / BGRA32 frames.
 int y2_f16_images_ctx(yolo2_hip_ctx *c, int split, yolo2_hip_ctx **run);
 bool y2_f16_images_fused(const yolo2_hip_ctx *run);
 int y2_f16_run_images(yolo2_hip_ctx *run, const uint8_t *lb, int kind, int batch, float *region_dev, hipStream_t st);
@@ -556,25 +556,26 @@ int y2_anno_jpeg_ensure(yolo2_hip_ctx *c, size_t cap_rgb, size_t cap_work, size_
 // ... and the device draw list of the loop entry (yolo2_loop.hip drives it; k_draw_items and the painter are launched here).
 // geom: the painter's table as the host knows it before the records exist (y2_loop_geom_bytes(nf) bytes; returns the most strips of a
 // frame).  _enqueue_items: k_draw_items on st from the records / counts of one tail, then the D2H of the per-frame
-// {items, unprintable} into c->loop.hinfo[b].  _enqueue_paint: k_annotate_batch over the table _enqueue_items left.
+// {items, unprintable} into c->loop.hinfo[b].  _enqueue_paint: k_annotate_batch (bgr: k_annotate_batch_bgr) over the table _enqueue_items left.
 void y2_loop_free(yolo2_hip_ctx *c);
 size_t y2_loop_geom_bytes(int nf);
 int y2_loop_fill_geom(uint8_t *geom, int nf, const int *widths, const int *heights, int ch, const size_t *src_off, const size_t *out_off);
 int y2_loop_ensure(yolo2_hip_ctx *c, int frames, int cap, const char *const *labels, int n_labels);
 int y2_loop_enqueue_items(yolo2_hip_ctx *c, int b, int nf, int cap, float thresh, const char *const *labels, int n_labels, const uint8_t *geom_dev,
                           const yolo2_hip_det *dets_dev, const int *counts_dev, hipStream_t st);
-int y2_loop_enqueue_paint(yolo2_hip_ctx *c, int nf, int max_strips, const uint8_t *src_base, uint8_t *out_base, hipStream_t st);
+int y2_loop_enqueue_paint(yolo2_hip_ctx *c, int nf, int max_strips, const uint8_t *src_base, uint8_t *out_base, bool bgr, hipStream_t st);
 
 // yolo2_hip.hip: what the images entries and the loop entry share - the letterbox rule, the chunk letterbox launch, PipeBufs' growth
 // (need_hout: the pinned region mirrors; _post: the tail's buffers; _regf: the fp32 region tensors) and the threaded staging copy
 namespace y2 { struct LetterboxArgs; }
 // The pixel formats of the _pix entries, one descriptor each: everything the host code needs to know about a format.
 //   ch      what LetterboxArgs::ch / AnnoFrame::ch carry: bytes per pixel for interleaved bytes (1, 3) and YUYV (2); for the planar
-//           4:2:0 formats, which have no whole number of bytes per pixel, a code that only their own fetch looks at
+//           4:2:0 formats, which have no whole number of bytes per pixel, and for packed BGR24 / RGBA32 / BGRA32, whose byte counts
+//           3 and 4 would not tell them from RGB24, a code that only their own fetch looks at
 //   kind    which kernels read it (the letterbox, layer-0, int8-front and painter instantiations)
 //   frame_bytes(w, h)   size of a frame; sizes staging, offsets and geometry everywhere
 //   even_w / even_h     the parity rule; align: the address alignment the single-image entries ask for
-enum Y2PixKind { Y2_KIND_BYTES = 0, Y2_KIND_YUYV, Y2_KIND_NV12, Y2_KIND_I420, Y2_KIND_COUNT };
+enum Y2PixKind { Y2_KIND_BYTES = 0, Y2_KIND_YUYV, Y2_KIND_NV12, Y2_KIND_I420, Y2_KIND_BGR24, Y2_KIND_RGBA32, Y2_KIND_BGRA32, Y2_KIND_COUNT };
 struct Y2PixDesc {
     int pixfmt;
     const char *name;

@@ -88,9 +88,9 @@ int fill_table(uint8_t *tbl, const FrameIn *fr, int nf, float thresh, const char
     return max_strips;
 }
 
-void launch_annotate(const uint8_t *table_dev, const uint8_t *src_base, uint8_t *out_base, int max_strips, int nf, hipStream_t st)
+void launch_annotate(const uint8_t *table_dev, const uint8_t *src_base, uint8_t *out_base, int max_strips, int nf, hipStream_t st, bool bgr = false)
 {
-    hipLaunchKernelGGL(k_annotate_batch, dim3((unsigned)max_strips, (unsigned)nf), dim3(kAnnoThreads), 0, st, table_dev, src_base, out_base);
+    hipLaunchKernelGGL(bgr ? k_annotate_batch_bgr : k_annotate_batch, dim3((unsigned)max_strips, (unsigned)nf), dim3(kAnnoThreads), 0, st, table_dev, src_base, out_base);
 }
 
 }  // namespace
@@ -341,9 +341,9 @@ int y2_loop_enqueue_items(yolo2_hip_ctx *c, int b, int nf, int cap, float thresh
     return YOLO2_SUCCESS;
 }
 
-int y2_loop_enqueue_paint(yolo2_hip_ctx *c, int nf, int max_strips, const uint8_t *src_base, uint8_t *out_base, hipStream_t st)
+int y2_loop_enqueue_paint(yolo2_hip_ctx *c, int nf, int max_strips, const uint8_t *src_base, uint8_t *out_base, bool bgr, hipStream_t st)
 {
-    launch_annotate(c->loop.table.get(), src_base, out_base, max_strips, nf, st);
+    launch_annotate(c->loop.table.get(), src_base, out_base, max_strips, nf, st, bgr);
     HIP_TRY(hipGetLastError(), YOLO2_ERROR);
     return YOLO2_SUCCESS;
 }

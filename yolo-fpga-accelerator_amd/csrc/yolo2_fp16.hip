@@ -62,11 +62,11 @@ struct F16Table {
     std::vector<F16Step> steps;
     // the images entries' layer-0 step "from bytes" (layers 0+1 from a chunk's staging buffer), used instead of steps[0]; every
     // other step is the table's.  Not set (launch_u8 == nullptr) under f16_no_mfma0: those entries letterbox into frames first.
-    // launch_pix / pix_kernel [Y2PixKind]: the same step from a chunk of frames of that kind (k_conv0_pool_mfma_yuyv / _nv12 / _i420;
+    // launch_pix / pix_kernel [Y2PixKind]: the same step from a chunk of frames of that kind (k_conv0_pool_mfma_yuyv / _nv12 / _i420 / _bgr24 / _rgba32 / _bgra32;
     // [Y2_KIND_BYTES] is launch_u8 / u8.kernel again).
     F16Step u8;
     F16LaunchU8 launch_u8 = nullptr, launch_pix[Y2_KIND_COUNT] = {};
-    const char *pix_kernel[Y2_KIND_COUNT] = {"", "", "", ""};
+    const char *pix_kernel[Y2_KIND_COUNT] = {"", "", "", "", "", "", ""};
 };
 struct F16Plan : F16Table {
     Y2Options opt;               // the context's option set as it was when the weights were loaded; a lane runs the parent's selection
@@ -341,7 +341,13 @@ template <auto K> static void L_conv0_bytes(const F16Step &s, const uint8_t *lb,
     X(FK_MAXPOOL_SP,     "k_maxpool2_split",                   L_maxpool_split, k_maxpool2_split, 256, 0)              \
     X(FK_MAXPOOL,        "k_maxpool2_f16",                     L_maxpool, k_maxpool2_f16, 256, 0)                      \
     X(FK_REORG_SP,       "k_reorg_split",                      L_reorg_split, k_reorg_split, 256, 0)                   \
-    X(FK_REORG,          "k_reorg_f16",                        L_reorg, k_reorg_f16, 256, 0)
+    X(FK_REORG,          "k_reorg_f16",                        L_reorg, k_reorg_f16, 256, 0)                           \
+    XB(FK_C0_BGR24_SP,   "k_conv0_pool_mfma_bgr24<split>",     k_conv0_pool_mfma_bgr24<true>)                          \
+    XB(FK_C0_BGR24,      "k_conv0_pool_mfma_bgr24",            k_conv0_pool_mfma_bgr24<false>)                         \
+    XB(FK_C0_RGBA32_SP,  "k_conv0_pool_mfma_rgba32<split>",    k_conv0_pool_mfma_rgba32<true>)                         \
+    XB(FK_C0_RGBA32,     "k_conv0_pool_mfma_rgba32",           k_conv0_pool_mfma_rgba32<false>)                        \
+    XB(FK_C0_BGRA32_SP,  "k_conv0_pool_mfma_bgra32<split>",    k_conv0_pool_mfma_bgra32<true>)                         \
+    XB(FK_C0_BGRA32,     "k_conv0_pool_mfma_bgra32",           k_conv0_pool_mfma_bgra32<false>)
 struct F16Kernel { const char *name; F16Launch launch; F16LaunchU8 launch_u8; unsigned block; const void *raise_lds; };
 #define ID(id, ...) id,
 enum F16Kid { F16_KERNELS(ID, ID) };
@@ -554,7 +560,8 @@ static int select_f16_table(const Y2Options &o, bool split, int B, F16Table &T)
         }
         T.steps.push_back(s);
         if (!o.f16_no_mfma0) {   // the same tiles, grid and output from image bytes (the images entries)
-            const F16Kid kid[Y2_KIND_COUNT][2] = {{FK_C0_U8, FK_C0_U8_SP}, {FK_C0_YUYV, FK_C0_YUYV_SP}, {FK_C0_NV12, FK_C0_NV12_SP}, {FK_C0_I420, FK_C0_I420_SP}};
+            const F16Kid kid[Y2_KIND_COUNT][2] = {{FK_C0_U8, FK_C0_U8_SP}, {FK_C0_YUYV, FK_C0_YUYV_SP}, {FK_C0_NV12, FK_C0_NV12_SP}, {FK_C0_I420, FK_C0_I420_SP},
+                                                  {FK_C0_BGR24, FK_C0_BGR24_SP}, {FK_C0_RGBA32, FK_C0_RGBA32_SP}, {FK_C0_BGRA32, FK_C0_BGRA32_SP}};
             const F16Kernel &u8 = kF16Kernels[kid[Y2_KIND_BYTES][split ? 1 : 0]];
             T.u8 = s; T.u8.kernel = u8.name; T.launch_u8 = u8.launch_u8;
             for (int kind = 0; kind < Y2_KIND_COUNT; ++kind) {

@@ -421,13 +421,17 @@ static const Y2PixDesc kPixDescs[] = {
     {YOLO2_PIX_YUYV, "YUYV", 2, Y2_KIND_YUYV, 16, true, false, 4},            // (LbYuyv loads pixel pairs as dwords)
     {YOLO2_PIX_NV12, "NV12", y2::kLbChNv12, Y2_KIND_NV12, 12, true, true, 1},   // (LbYuv420 loads bytes)
     {YOLO2_PIX_I420, "I420", y2::kLbChI420, Y2_KIND_I420, 12, true, true, 1},
+    {YOLO2_PIX_BGR24, "BGR24", y2::kLbChBgr24, Y2_KIND_BGR24, 24, false, false, 1},       // (LbPacked<3, .> loads bytes)
+    {YOLO2_PIX_RGBA32, "RGBA32", y2::kLbChRgba32, Y2_KIND_RGBA32, 32, false, false, 4},   // (LbPacked<4, .> loads a pixel as one dword)
+    {YOLO2_PIX_BGRA32, "BGRA32", y2::kLbChBgra32, Y2_KIND_BGRA32, 32, false, false, 4},
 };
 
 const Y2PixDesc *y2_pix_desc(int pixfmt, const char *who)
 {
     for (const Y2PixDesc &d : kPixDescs)
         if (d.pixfmt == pixfmt) return &d;
-    (void)fail(YOLO2_ERROR, "%s%sunknown pixel format 0x%x (YOLO2_PIX_GREY8, YOLO2_PIX_RGB24, YOLO2_PIX_YUYV, YOLO2_PIX_NV12 or YOLO2_PIX_I420)",
+    (void)fail(YOLO2_ERROR, "%s%sunknown pixel format 0x%x (YOLO2_PIX_GREY8, YOLO2_PIX_RGB24, YOLO2_PIX_YUYV, YOLO2_PIX_NV12, YOLO2_PIX_I420, "
+                            "YOLO2_PIX_BGR24, YOLO2_PIX_RGBA32 or YOLO2_PIX_BGRA32)",
                who ? who : "", who ? ": " : "", (unsigned)pixfmt);
     return nullptr;
 }
@@ -499,7 +503,9 @@ extern "C" int yolo2_hip_letterbox_pix(uint64_t image_dev, int w, int h, int pix
     LetterboxArgs a;
     int rc = y2_letterbox_args(w, h, d->ch, net_w, net_h, a, true);
     if (rc) return rc;
-    const auto kernel = d->kind == Y2_KIND_YUYV ? k_letterbox_yuyv : (d->kind == Y2_KIND_NV12 ? k_letterbox_nv12 : k_letterbox_i420);
+    static constexpr decltype(&k_letterbox_yuyv) kernels[Y2_KIND_COUNT] = {nullptr,           k_letterbox_yuyv,   k_letterbox_nv12,  k_letterbox_i420,
+                                                                           k_letterbox_bgr24, k_letterbox_rgba32, k_letterbox_bgra32};
+    const auto kernel = kernels[d->kind];
     hipLaunchKernelGGL(kernel, dim3(blocks_for((long)3 * net_w * net_h, 256)), dim3(256), 0, (hipStream_t)stream,
                        (const uint8_t *)(uintptr_t)image_dev, (float *)(uintptr_t)frame_dev, a);
     HIP_TRY(hipGetLastError(), YOLO2_ERROR);
@@ -509,17 +515,18 @@ extern "C" int yolo2_hip_letterbox_pix(uint64_t image_dev, int w, int h, int pix
 // the chunk letterbox of every kind of staging buffer (Y2PixKind: what the table items' frames are), and its name
 const char *y2_letterbox_batch_kernel(int kind)
 {
-    static const char *const names[Y2_KIND_COUNT] = {"k_letterbox_u8_batch", "k_letterbox_yuyv_batch", "k_letterbox_nv12_batch", "k_letterbox_i420_batch"};
+    static const char *const names[Y2_KIND_COUNT] = {"k_letterbox_u8_batch",    "k_letterbox_yuyv_batch",   "k_letterbox_nv12_batch",  "k_letterbox_i420_batch",
+                                                     "k_letterbox_bgr24_batch", "k_letterbox_rgba32_batch", "k_letterbox_bgra32_batch"};
     return names[kind];
 }
 
 void y2_launch_letterbox_batch(int kind, const uint8_t *dbytes, float *din, int batch, hipStream_t st)
 {
     const dim3 grid(blocks_for((long)YOLO2_FRAME_ELEMS, 256), batch);
-    if (kind == Y2_KIND_YUYV) hipLaunchKernelGGL(k_letterbox_yuyv_batch, grid, dim3(256), 0, st, dbytes, din, (int)YOLO2_FRAME_ELEMS);
-    else if (kind == Y2_KIND_NV12) hipLaunchKernelGGL(k_letterbox_nv12_batch, grid, dim3(256), 0, st, dbytes, din, (int)YOLO2_FRAME_ELEMS);
-    else if (kind == Y2_KIND_I420) hipLaunchKernelGGL(k_letterbox_i420_batch, grid, dim3(256), 0, st, dbytes, din, (int)YOLO2_FRAME_ELEMS);
-    else hipLaunchKernelGGL(k_letterbox_u8_batch, grid, dim3(256), 0, st, dbytes, din, (int)YOLO2_FRAME_ELEMS);   // the whole chunk in one launch
+    static constexpr decltype(&k_letterbox_u8_batch) kernels[Y2_KIND_COUNT] = {k_letterbox_u8_batch,    k_letterbox_yuyv_batch,   k_letterbox_nv12_batch,
+                                                                               k_letterbox_i420_batch,  k_letterbox_bgr24_batch,  k_letterbox_rgba32_batch,
+                                                                               k_letterbox_bgra32_batch};
+    hipLaunchKernelGGL(kernels[kind], grid, dim3(256), 0, st, dbytes, din, (int)YOLO2_FRAME_ELEMS);   // the whole chunk in one launch
 }
 
 // Camera-style entry: n images of arbitrary sizes as host bytes -> region tensors, in chunks of

@@ -339,7 +339,8 @@ bool y2_i8_loaded(const yolo2_hip_ctx *c) { return c && c->i8 && c->i8->loaded; 
 bool y2_i8_images_fused(const yolo2_hip_ctx *c) { return !c->opt.i8_no_front; }
 const char *y2_i8_front_kernel(int kind)
 {
-    static const char *const names[Y2_KIND_COUNT] = {"k_i8_front_u8", "k_i8_front_yuyv", "k_i8_front_nv12", "k_i8_front_i420"};
+    static const char *const names[Y2_KIND_COUNT] = {"k_i8_front_u8",    "k_i8_front_yuyv",   "k_i8_front_nv12",  "k_i8_front_i420",
+                                                     "k_i8_front_bgr24", "k_i8_front_rgba32", "k_i8_front_bgra32"};
     return names[kind];
 }
 
@@ -370,6 +371,9 @@ int y2_i8_run_images(yolo2_hip_ctx *c, const uint8_t *lb, int kind, int batch, f
     if (kind == Y2_KIND_YUYV) hipLaunchKernelGGL(k_i8_front_pix<LbYuyv>, grid, block, 0, st, a);
     else if (kind == Y2_KIND_NV12) hipLaunchKernelGGL(k_i8_front_nv12, grid, block, 0, st, a);
     else if (kind == Y2_KIND_I420) hipLaunchKernelGGL(k_i8_front_i420, grid, block, 0, st, a);
+    else if (kind == Y2_KIND_BGR24) hipLaunchKernelGGL(k_i8_front_bgr24, grid, block, 0, st, a);
+    else if (kind == Y2_KIND_RGBA32) hipLaunchKernelGGL(k_i8_front_rgba32, grid, block, 0, st, a);
+    else if (kind == Y2_KIND_BGRA32) hipLaunchKernelGGL(k_i8_front_bgra32, grid, block, 0, st, a);
     else hipLaunchKernelGGL(k_i8_front_pix<LbInterleaved>, grid, block, 0, st, a);
     if (ev) (void)hipEventRecord(ev[2], st);
     if ((rc = run_layers(s, 2, &s->t[1], batch, (uint64_t)(uintptr_t)region_dev, st, ev))) return rc;

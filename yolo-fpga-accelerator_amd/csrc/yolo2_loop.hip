@@ -54,8 +54,8 @@ int y2_loop_check(int precision, const uint8_t *const *images, const int *widths
     if (!images || !widths || !heights || !dets || !counts || !out || !caps || !sizes) return fail(YOLO2_ERROR, "loop: null argument");
     if (precision != YOLO2_LOOP_INT16 && precision != YOLO2_LOOP_FP16 && precision != YOLO2_LOOP_F32TOL)
         return fail(YOLO2_ERROR, "loop: unknown precision %d (YOLO2_LOOP_INT16, _FP16 or _F32TOL)", precision);
-    if (out_format != YOLO2_LOOP_OUT_RGB24 && out_format != YOLO2_LOOP_OUT_JPEG)
-        return fail(YOLO2_ERROR, "loop: unknown output format %d (YOLO2_LOOP_OUT_RGB24 or _JPEG)", out_format);
+    if (out_format != YOLO2_LOOP_OUT_RGB24 && out_format != YOLO2_LOOP_OUT_JPEG && out_format != YOLO2_LOOP_OUT_BGR24)
+        return fail(YOLO2_ERROR, "loop: unknown output format %d (YOLO2_LOOP_OUT_RGB24, _JPEG or _BGR24)", out_format);
     if (!(flags & YOLO2_DETS_BEST_CLASS)) return fail(YOLO2_ERROR, "loop: flags must contain YOLO2_DETS_BEST_CLASS, the form the painter draws");
     const Y2PixDesc *pd = y2_pix_desc(pixfmt, nullptr);
     if (!pd) return YOLO2_ERROR;
@@ -271,7 +271,7 @@ static int loop_run(yolo2_hip_ctx *c, int precision, const uint8_t *const *image
         if (dec && (rc = y2_jpegdec_status_d2h(dec, k, P.s_out))) { cleanup(); return rc; }
         if ((rc = y2_loop_enqueue_items(c, b, nf, cap, thresh, labels, n_labels, P.dbytes[b].get() + lb_bytes, P.post[b].dets.get(), P.post[b].counts.get(),
                                         P.s_out)) ||
-            (rc = y2_loop_enqueue_paint(c, nf, max_strips, P.dbytes[b].get(), jpeg ? J.rgb.get() : A.dout[b].get(), P.s_out))) {
+            (rc = y2_loop_enqueue_paint(c, nf, max_strips, P.dbytes[b].get(), jpeg ? J.rgb.get() : A.dout[b].get(), out_format == YOLO2_LOOP_OUT_BGR24, P.s_out))) {
             cleanup();
             return rc;
         }

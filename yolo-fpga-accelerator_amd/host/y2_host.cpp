@@ -312,6 +312,21 @@ bool yuv420_to_rgb24(const uint8_t *frame, uint8_t *rgb, int w, int h, bool semi
     return true;
 }
 
+// Packed BGR24 / RGBA32 / BGRA32 -> RGB24: byte k of pixel p is src[p * bpp + (swap ? 2 - k : k)]; a fourth byte is not read
+bool packed_to_rgb24(const uint8_t *src, uint8_t *rgb, int w, int h, int fmt)
+{
+    if (!src || !rgb || w <= 0 || h <= 0 || (fmt != kFrameBgr24 && fmt != kFrameRgba32 && fmt != kFrameBgra32)) return false;
+    const size_t bpp = fmt == kFrameBgr24 ? 3 : 4, n = (size_t)w * h;
+    const bool swap = fmt != kFrameRgba32;
+    for (size_t p = 0; p < n; ++p) {
+        const uint8_t *s = src + p * bpp;
+        rgb[p * 3] = s[swap ? 2 : 0];
+        rgb[p * 3 + 1] = s[1];
+        rgb[p * 3 + 2] = s[swap ? 0 : 2];
+    }
+    return true;
+}
+
 // letterbox_image, yolo_image.cpp:148-165
 Image letterbox_image(const Image &im, int w, int h)
 {
@@ -389,8 +404,11 @@ int draw_detections_rgb24(uint8_t *rgb, int w, int h, const DrawRecord *dets, in
 Image plain_box_frame(const uint8_t *bytes, int w, int h, int fmt, const DrawRecord *recs, int n, int classes)
 {
     Image im = make_image(w, h, 3);
-    std::vector<uint8_t> conv;   // the frame needs RGB pixels: a YUYV / NV12 / I420 frame is converted here, on the host
-    if (fmt != kFrameRgb24) {
+    std::vector<uint8_t> conv;   // the frame needs RGB pixels: a YUYV / NV12 / I420 frame is converted, a BGR24 / RGBA32 / BGRA32 one reordered here, on the host
+    if (fmt == kFrameBgr24 || fmt == kFrameRgba32 || fmt == kFrameBgra32) {
+        conv.resize((size_t)im.w * im.h * 3);
+        if (!packed_to_rgb24(bytes, conv.data(), im.w, im.h, fmt)) throw std::runtime_error("bad packed RGB frame");
+    } else if (fmt != kFrameRgb24) {
         conv.resize((size_t)im.w * im.h * 3);
         if (fmt == kFrameYuyv ? !yuyv_to_rgb24(bytes, conv.data(), im.w, im.h) : !yuv420_to_rgb24(bytes, conv.data(), im.w, im.h, fmt == kFrameNv12))
             throw std::runtime_error(fmt == kFrameYuyv ? "bad YUYV frame" : "bad YUV 4:2:0 frame");

@@ -64,6 +64,10 @@ bool yuyv_to_rgb24(const uint8_t *yuyv, uint8_t *rgb, int w, int h);
 // replicated.  The library's own extension of the reference's conversion (the reference has no 4:2:0 input); the GPU entries compute
 // the same byte per fetched pixel (csrc/letterbox.hpp, LbYuv420).  False for a null pointer or an odd or non-positive width / height.
 bool yuv420_to_rgb24(const uint8_t *frame, uint8_t *rgb, int w, int h, bool semi);
+// A packed BGR24 (B G R, w h 3 bytes), RGBA32 (R G B X, w h 4 bytes) or BGRA32 (B G R X) frame -> RGB24: the bytes reordered, the fourth
+// byte not read.  fmt: kFrameBgr24 / kFrameRgba32 / kFrameBgra32 below.  The GPU entries pick the same byte per fetched pixel
+// (csrc/letterbox.hpp, LbPacked).  False for a null pointer, a non-positive width / height or another fmt.
+bool packed_to_rgb24(const uint8_t *src, uint8_t *rgb, int w, int h, int fmt);
 void draw_box(Image &im, int x1, int y1, int x2, int y2, int thick, float r, float g, float b);
 // The annotated frame of the reference's camera / video loop: yolo2_draw_detections_rgb24 (linux_app/src/yolo2_draw.c:276-369, called
 // at linux_app/src/main.c:1079-1091) on records of the library's yolo2_hip_det layout in the YOLO2_DETS_BEST_CLASS form (one per
@@ -76,9 +80,9 @@ struct DrawRecord {
 };
 int draw_detections_rgb24(uint8_t *rgb, int w, int h, const DrawRecord *dets, int n, float thresh, const char *const *labels, int n_labels);
 // The streaming CLI's own annotated frame (without --annotate-gpu): the frame's bytes (fmt: RGB24, a packed YUYV frame through
-// yuyv_to_rgb24, or an NV12 / I420 frame through yuv420_to_rgb24) as a float image, one draw_box per record in a hue colour of its class, thickness max(1, h * .006).  No labels.
+// yuyv_to_rgb24, an NV12 / I420 frame through yuv420_to_rgb24, or a BGR24 / RGBA32 / BGRA32 frame through packed_to_rgb24) as a float image, one draw_box per record in a hue colour of its class, thickness max(1, h * .006).  No labels.
 // Throws std::runtime_error for a bad YUYV / 4:2:0 frame.
-enum { kFrameRgb24 = 0, kFrameYuyv = 1, kFrameNv12 = 2, kFrameI420 = 3 };
+enum { kFrameRgb24 = 0, kFrameYuyv = 1, kFrameNv12 = 2, kFrameI420 = 3, kFrameBgr24 = 4, kFrameRgba32 = 5, kFrameBgra32 = 6 };
 Image plain_box_frame(const uint8_t *bytes, int w, int h, int fmt, const DrawRecord *recs, int n, int classes);
 int draw_font(char *chars, uint64_t *words);   // the packed font: 38 characters and their 35-bit glyph words (bit 5 * row + column)
 // The annotated frame as the JPEG stream the reference's MJPEG streamer sends (stb_image_write v1.09's stbi_write_jpg_to_func with 3

@@ -1,6 +1,7 @@
 // y2_host_capi.cpp -- extern "C" doorway into the host logic for the Python tests
 // (libyolo2_host.so).  No GPU involved.
 #include <algorithm>
+#include <cstdio>
 #include <cstring>
 #include <exception>
 #include <string>
@@ -142,8 +143,24 @@ int y2h_yuv420_to_rgb24(const uint8_t *frame, uint8_t *rgb, int w, int h, int se
     return -1;
 }
 
+// packed_to_rgb24; pixfmt: the YOLO2_PIX_* fourcc of BGR24 ('BGR3'), RGBA32 ('AB24') or BGRA32 ('AR24').  0, or -1 (y2h_last_error) for a
+// null pointer, a non-positive width / height or another pixfmt
+int y2h_packed_to_rgb24(const uint8_t *src, int w, int h, int pixfmt, uint8_t *rgb)
+{
+    const int fmt = pixfmt == 0x33524742 ? kFrameBgr24 : pixfmt == 0x34324241 ? kFrameRgba32 : pixfmt == 0x34325241 ? kFrameBgra32 : -1;
+    if (fmt < 0) {
+        char hex[16];
+        std::snprintf(hex, sizeof(hex), "0x%x", (unsigned)pixfmt);
+        g_err = std::string("packed_to_rgb24: unknown pixel format ") + hex + " (BGR24, RGBA32 or BGRA32)";
+        return -1;
+    }
+    if (packed_to_rgb24(src, rgb, w, h, fmt)) return 0;
+    g_err = "packed_to_rgb24: null pointer or bad frame size " + std::to_string(w) + "x" + std::to_string(h);
+    return -1;
+}
+
 // plain_box_frame, the CLI writer's own frame, for tools/annotate_report.py to time; returns the sum of the image, or -1
-// (y2h_last_error) for a bad frame; yuyv: 0 RGB24, 1 YUYV, 2 NV12, 3 I420
+// (y2h_last_error) for a bad frame; yuyv: 0 RGB24, 1 YUYV, 2 NV12, 3 I420, 4 BGR24, 5 RGBA32, 6 BGRA32
 double y2h_plain_box_frame(const uint8_t *bytes, int w, int h, int yuyv, const void *dets, int n, int classes)
 {
     try {

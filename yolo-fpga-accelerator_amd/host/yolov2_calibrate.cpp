@@ -37,8 +37,9 @@ void print_usage(const char *prog)
         "  --input-dir <dir>     Calibration images: every *.jpg / *.jpeg / *.png / *.ppm / *.pgm of a directory, sorted by name\n"
         "  --input-list <file>   Calibration images, one path per line\n"
         "  --video-raw <file>    Calibration frames: raw video frames as yolov2_detect takes them, with --video-width <w> --video-height <h>\n"
-        "                        (default 640x480), --video-pix-fmt <rgb24|yuyv422|nv12|yuv420p> (default rgb24; also yuyv, i420: the GPU\n"
-        "                        reads the frames as they are; yuyv422 needs an even width, nv12 / yuv420p an even width and height) and\n"
+        "                        (default 640x480), --video-pix-fmt <rgb24|yuyv422|nv12|yuv420p|bgr24|rgba|bgra> (default rgb24; also\n"
+        "                        yuyv, i420, rgb0, bgr0: the GPU reads the frames as they are; yuyv422 needs an even width, nv12 / yuv420p an even\n"
+        "                        width and height; bgr24 is packed B G R, rgba / bgra are R G B X / B G R X with the fourth byte unused) and\n"
         "                        --max-frames <n> (default: all)\n"
         "  --out <dir>           Where weights_reorg_int16.bin, bias_int16.bin, weight_int16_Q.bin, bias_int16_Q.bin and iofm_Q.bin go\n"
         "  --batch <n>           Images per pass of the exact fp32 network (default 8)\n"
@@ -74,7 +75,10 @@ Config parse_args(int argc, char **argv)
             else if (v == "yuyv422" || v == "yuyv") cfg.video_pixfmt = YOLO2_PIX_YUYV;
             else if (v == "nv12") cfg.video_pixfmt = YOLO2_PIX_NV12;
             else if (v == "yuv420p" || v == "i420") cfg.video_pixfmt = YOLO2_PIX_I420;
-            else { std::fprintf(stderr, "Unsupported --video-pix-fmt %s (rgb24 | yuyv422 | nv12 | yuv420p)\n", v.c_str()); std::exit(1); }
+            else if (v == "bgr24") cfg.video_pixfmt = YOLO2_PIX_BGR24;
+            else if (v == "rgba" || v == "rgb0") cfg.video_pixfmt = YOLO2_PIX_RGBA32;
+            else if (v == "bgra" || v == "bgr0") cfg.video_pixfmt = YOLO2_PIX_BGRA32;
+            else { std::fprintf(stderr, "Unsupported --video-pix-fmt %s (rgb24 | yuyv422 | nv12 | yuv420p | bgr24 | rgba | bgra)\n", v.c_str()); std::exit(1); }
         }
         else if (arg == "--out" && need()) cfg.out_dir = argv[++i];
         else if (arg == "--batch" && need()) cfg.batch = std::atoi(argv[++i]);
@@ -131,7 +135,8 @@ std::vector<std::string> list_inputs(const Config &cfg)
 std::vector<std::vector<uint8_t>> read_video_frames(const Config &cfg)
 {
     const size_t px = (size_t)cfg.video_w * cfg.video_h;
-    const size_t bytes = cfg.video_pixfmt == YOLO2_PIX_YUYV ? 2 * px
+    const size_t bytes = cfg.video_pixfmt == YOLO2_PIX_RGBA32 || cfg.video_pixfmt == YOLO2_PIX_BGRA32 ? 4 * px
+                         : cfg.video_pixfmt == YOLO2_PIX_YUYV ? 2 * px
                          : (cfg.video_pixfmt == YOLO2_PIX_NV12 || cfg.video_pixfmt == YOLO2_PIX_I420 ? px * 3 / 2 : 3 * px);
     std::ifstream in(cfg.video_raw, std::ios::binary);
     if (!in) throw std::runtime_error("Cannot open " + cfg.video_raw);

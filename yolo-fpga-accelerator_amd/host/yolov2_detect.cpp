@@ -12,7 +12,7 @@
 // `--batch N` runs the same frame N times through one batched call to show the batched entry.
 //
 // Streaming frontend (the role of the reference's yolo2_linux --video/--camera loop, linux_app/src/main.c:878-1288):
-//   --input-list <file> | --input-dir <dir> | --video-raw <file|-> --video-width W --video-height H [--video-pix-fmt rgb24|yuyv422|nv12|yuv420p]
+//   --input-list <file> | --input-dir <dir> | --video-raw <file|-> --video-width W --video-height H [--video-pix-fmt rgb24|yuyv422|nv12|yuv420p|bgr24|rgba|bgra]
 //   | --video-mjpeg <file|-> (concatenated JPEG streams); --decode gpu sends baseline JPEG streams to the device compressed
 // Frames are taken in chunks of --batch per device, go to the GPU as BYTES (letterbox on the GPU), through the
 // int16 network on --devices a,b,... (contiguous frame shards, weights broadcast once by the library) and through the
@@ -69,7 +69,7 @@ struct AppConfig {
     int jpeg_quality = 80;          // --jpeg-quality, the reference streamer's default
     bool loop_gpu = false;          // --loop-gpu: records and annotated frames from ONE accelerator call per chunk (yolo2_hip_loop_images_pix)
     int video_w = 640, video_h = 480;
-    int video_pixfmt = YOLO2_PIX_RGB24; // --video-pix-fmt: what a --video-raw frame holds (RGB24, or packed YUYV 4:2:2 / planar NV12 / I420 read by the GPU as they are)
+    int video_pixfmt = YOLO2_PIX_RGB24; // --video-pix-fmt: what a --video-raw frame holds (RGB24, or packed YUYV 4:2:2 / planar NV12 / I420 / packed BGR24 / RGBA32 / BGRA32 read by the GPU as they are)
     int max_frames = 0;                // 0 = all
     int infer_every = 1;
     std::string post = "gpu";          // region + boxes + NMS: gpu | host
@@ -114,6 +114,9 @@ void print_usage(const char *prog)
         "                        the GPU as they are and are converted where they are read (every --precision, --devices)\n"
         "                        nv12 | yuv420p (also: i420): planar YUV 4:2:0, what video decoders emit (`ffmpeg -i file -f rawvideo -pix_fmt\n"
         "                        nv12 -`), w * h * 3 / 2 bytes per frame, even width and height; read and converted on the GPU the same way\n"
+        "                        bgr24 | rgba | bgra (also: rgb0, bgr0 - the same layouts): packed B G R (OpenCV's frames), R G B X and B G R X\n"
+        "                        (GUI toolkits, screen capture), 3 / 4 bytes per pixel, any size; the GPU picks the bytes where it reads the\n"
+        "                        frame, the fourth byte is never used (every --precision, --annotate-gpu, --loop-gpu, --devices)\n"
         "  --video-mjpeg <file|->  Concatenated JPEG streams, what a camera delivers as MJPEG; each frame ends where its stream does\n"
         "  --decode <host|gpu>   Where JPEG streams are decoded (default host: the decode pool).  gpu, with --input-list, --input-dir or\n"
         "                        --video-mjpeg and --post gpu: baseline 1- and 3-component streams go to the device compressed and are decoded\n"
@@ -198,7 +201,10 @@ AppConfig parse_args(int argc, char **argv)
             else if (v == "yuyv422" || v == "yuyv") cfg.video_pixfmt = YOLO2_PIX_YUYV;
             else if (v == "nv12") cfg.video_pixfmt = YOLO2_PIX_NV12;
             else if (v == "yuv420p" || v == "i420") cfg.video_pixfmt = YOLO2_PIX_I420;
-            else { std::fprintf(stderr, "Unsupported --video-pix-fmt %s (rgb24 | yuyv422 | nv12 | yuv420p)\n", v.c_str()); std::exit(1); }
+            else if (v == "bgr24") cfg.video_pixfmt = YOLO2_PIX_BGR24;
+            else if (v == "rgba" || v == "rgb0") cfg.video_pixfmt = YOLO2_PIX_RGBA32;
+            else if (v == "bgra" || v == "bgr0") cfg.video_pixfmt = YOLO2_PIX_BGRA32;
+            else { std::fprintf(stderr, "Unsupported --video-pix-fmt %s (rgb24 | yuyv422 | nv12 | yuv420p | bgr24 | rgba | bgra)\n", v.c_str()); std::exit(1); }
         }
         else if (arg == "--max-frames" && need("")) cfg.max_frames = std::atoi(argv[++i]);
         else if (arg == "--infer-every" && need("")) cfg.infer_every = std::max(1, std::atoi(argv[++i]));
@@ -291,7 +297,8 @@ AppConfig parse_args(int argc, char **argv)
         std::error_code ec;
         if (!std::filesystem::exists(cfg.video_raw, ec) || std::filesystem::is_directory(cfg.video_raw, ec)) {
             const char *fmt = cfg.video_pixfmt == YOLO2_PIX_YUYV ? "yuyv422" : cfg.video_pixfmt == YOLO2_PIX_NV12 ? "nv12"
-                              : cfg.video_pixfmt == YOLO2_PIX_I420 ? "yuv420p" : "rgb24";
+                              : cfg.video_pixfmt == YOLO2_PIX_I420 ? "yuv420p" : cfg.video_pixfmt == YOLO2_PIX_BGR24 ? "bgr24"
+                              : cfg.video_pixfmt == YOLO2_PIX_RGBA32 ? "rgba" : cfg.video_pixfmt == YOLO2_PIX_BGRA32 ? "bgra" : "rgb24";
             std::fprintf(stderr, "Cannot read --video-raw %s (%dx%d frames, --video-pix-fmt %s)\n", cfg.video_raw.c_str(), cfg.video_w, cfg.video_h, fmt);
             std::exit(1);
         }
@@ -392,18 +399,22 @@ std::vector<OutDet> best_class_dets(const std::vector<y2h::Detection> &dets, int
 static size_t video_frame_bytes(int w, int h, int pixfmt)
 {
     const size_t px = (size_t)w * h;
+    if (pixfmt == YOLO2_PIX_RGBA32 || pixfmt == YOLO2_PIX_BGRA32) return 4 * px;
     return pixfmt == YOLO2_PIX_YUYV ? 2 * px : (pixfmt == YOLO2_PIX_NV12 || pixfmt == YOLO2_PIX_I420 ? px * 3 / 2 : 3 * px);
 }
 // y2h::plain_box_frame's name for it
 static int host_frame_fmt(int pixfmt)
 {
+    if (pixfmt == YOLO2_PIX_BGR24) return y2h::kFrameBgr24;
+    if (pixfmt == YOLO2_PIX_RGBA32) return y2h::kFrameRgba32;
+    if (pixfmt == YOLO2_PIX_BGRA32) return y2h::kFrameBgra32;
     return pixfmt == YOLO2_PIX_YUYV ? y2h::kFrameYuyv : pixfmt == YOLO2_PIX_NV12 ? y2h::kFrameNv12 : pixfmt == YOLO2_PIX_I420 ? y2h::kFrameI420 : y2h::kFrameRgb24;
 }
 
 struct SrcFrame {
     std::string source;
     int frame_index = 0;    // 1-based position in the stream
-    y2h::ImageU8 img;       // (a --video-pix-fmt yuyv422 / nv12 / yuv420p frame: img.rgb holds its 2 w h / 1.5 w h bytes, as they were read)
+    y2h::ImageU8 img;       // (a --video-pix-fmt yuyv422 / nv12 / yuv420p frame: img.rgb holds its 2 w h / 1.5 w h bytes, as they were read; bgr24 / rgba / bgra likewise, 3 w h / 4 w h bytes)
     std::vector<uint8_t> jpeg;   // --video-mjpeg: the frame's stream; --decode gpu: the stream that goes to the device (img then has w, h only)
 };
 

@@ -75,6 +75,11 @@ PIXFMTS = {"grey8": 1, "rgb24": 3, "yuyv": 0x56595559}
 # A table of their own: PIXFMTS stays the camera formats' (tests pin it); every pixfmt= parameter takes a name of either.
 PIXFMTS_420 = {"nv12": 0x3231564E, "i420": 0x32315559}
 PLANAR_420 = tuple(PIXFMTS_420)
+# ... and packed RGB as most callers hold it: "bgr24" (OpenCV) arrays uint8 [h][w][3] of B G R; "rgba32" / "bgra32" (GUI toolkits, screen
+# capture) arrays uint8 [h][w][4] of R G B X / B G R X, the fourth byte never used.  A third table, for the same reason.
+PIXFMTS_PACKED = {"bgr24": 0x33524742, "rgba32": 0x34324241, "bgra32": 0x34325241}
+PACKED_RGB = tuple(PIXFMTS_PACKED)
+LOOP_OUT_RGB24, LOOP_OUT_JPEG, LOOP_OUT_BGR24 = 0, 1, 0x33524742   # include/yolo2_hip.h YOLO2_LOOP_OUT_*
 
 
 def pix_code(pixfmt: str) -> int:
@@ -83,13 +88,15 @@ def pix_code(pixfmt: str) -> int:
         return PIXFMTS[pixfmt]
     if pixfmt in PIXFMTS_420:
         return PIXFMTS_420[pixfmt]
-    raise ValueError(f"pixfmt must be None or one of {tuple(PIXFMTS) + PLANAR_420}, not {pixfmt!r}")
+    if pixfmt in PIXFMTS_PACKED:
+        return PIXFMTS_PACKED[pixfmt]
+    raise ValueError(f"pixfmt must be None or one of {tuple(PIXFMTS) + PLANAR_420 + PACKED_RGB}, not {pixfmt!r}")
 
 
 def _pix_code(pixfmt, imgs) -> int:
     """the entries' pixfmt argument for a list of contiguous uint8 arrays, whose shapes must be that format's"""
     code = pix_code(pixfmt)
-    last = {"grey8": None, "rgb24": 3, "yuyv": 2, "nv12": None, "i420": None}[pixfmt]
+    last = {"grey8": None, "rgb24": 3, "yuyv": 2, "nv12": None, "i420": None, "bgr24": 3, "rgba32": 4, "bgra32": 4}[pixfmt]
     for im in imgs:
         if pixfmt in PLANAR_420 and (im.ndim != 2 or im.shape[0] % 3):
             raise ValueError(f"a {pixfmt} image is uint8 [h * 3 / 2][w] with h even (rows a multiple of 3), not {im.shape}")
@@ -127,7 +134,7 @@ def _stream_sync(stream: int):
 
 def letterbox_pix(image: np.ndarray, pixfmt: str, net_w: int = 416, net_h: int = 416, stream: int = 0) -> np.ndarray:
     """letterbox_u8 with a pixel format (yolo2_hip_letterbox_pix): "grey8" [h][w], "rgb24" [h][w][3], "yuyv" [h][w][2] (packed
-    YUYV 4:2:2) or "nv12" / "i420" [h * 3 / 2][w] (planar YUV 4:2:0), converted per fetched pixel on the GPU -> float [3][net_h][net_w] frame."""
+    YUYV 4:2:2) "nv12" / "i420" [h * 3 / 2][w] (planar YUV 4:2:0) or "bgr24" [h][w][3] / "rgba32" / "bgra32" [h][w][4] (packed RGB), converted per fetched pixel on the GPU -> float [3][net_h][net_w] frame."""
     return letterbox_u8(image, net_w, net_h, pixfmt=pixfmt, stream=stream)
 
 
@@ -563,7 +570,7 @@ class Yolo2Hip:
     def run_images_host(self, images, batch: int = 64, pixfmt=None):
         """images: list of uint8 arrays [h][w][3] (or [h][w] grey) of arbitrary sizes -> region tensors.
         Bytes cross PCIe, letterboxing runs on the GPU (yolo2_hip_run_images_u8_host).  pixfmt "grey8" / "rgb24" / "yuyv" (arrays
-        [h][w][2]) / "nv12" / "i420" (arrays [h * 3 / 2][w]) names the format instead (yolo2_hip_run_images_pix_host); None infers grey / RGB from the shape."""
+        [h][w][2]) / "nv12" / "i420" (arrays [h * 3 / 2][w]) / "bgr24" ([h][w][3]) / "rgba32" / "bgra32" ([h][w][4]) names the format instead (yolo2_hip_run_images_pix_host); None infers grey / RGB from the shape."""
         n, ptrs, ws, hs, fmt, _keep = _image_args(images, pixfmt)
         region = np.empty((n, 425, 13, 13), dtype=np.int16)
         q = C.c_int(0)
@@ -574,10 +581,10 @@ class Yolo2Hip:
         return region, q.value
 
     def loop_images(self, images, pixfmt=None, precision: str = "int16", tail: str = "core", thresh: float = 0.24, nms: float = 0.45,
-                    labels=None, jpeg_quality=None, batch: int = 64, cap: int = 845):
+                    labels=None, jpeg_quality=None, batch: int = 64, cap: int = 845, out_order: str = "rgb"):
         """the camera loop as one call: records and annotated frames from one upload (module-level loop_images)"""
         return loop_images(self._h, images, pixfmt=pixfmt, precision=precision, tail=tail, thresh=thresh, nms=nms, labels=labels,
-                           jpeg_quality=jpeg_quality, batch=batch, cap=cap)
+                           jpeg_quality=jpeg_quality, batch=batch, cap=cap, out_order=out_order)
 
     def jpeg_decode(self, streams, batch: int = 64, strict: bool = True):
         """see jpeg_decode"""
@@ -589,10 +596,10 @@ class Yolo2Hip:
         return run_jpegs_dets(self._h, streams, batch, thresh, nms, cap=cap, best_class=best_class, precision=precision, tail=tail, strict=strict)
 
     def loop_jpegs(self, streams, precision: str = "int16", tail: str = "core", thresh: float = 0.24, nms: float = 0.45, labels=None,
-                   jpeg_quality=None, batch: int = 64, cap: int = 845, strict: bool = True):
+                   jpeg_quality=None, batch: int = 64, cap: int = 845, strict: bool = True, out_order: str = "rgb"):
         """the camera loop as one call from JPEG streams (module-level loop_jpegs)"""
         return loop_jpegs(self._h, streams, precision=precision, tail=tail, thresh=thresh, nms=nms, labels=labels, jpeg_quality=jpeg_quality,
-                          batch=batch, cap=cap, strict=strict)
+                          batch=batch, cap=cap, strict=strict, out_order=out_order)
 
     def loop_last_info(self) -> dict:
         return loop_last_info(self._h)
@@ -1116,7 +1123,7 @@ def run_images_dets(handle, images, batch: int, thresh: float, nms: float, cap: 
     records; letterbox, network and the tail run on the device(s), the region tensor never leaves HBM.  precision "fp16" /
     "fp32fast" (the split-fp16 pass) run the _dets_f16 entries instead (fp32 weights loaded); their final_q is None.
     precision "int8": yolo2_hip_run_images_pix_dets_int8 (int8 weights loaded, single device; final_q None).
-    pixfmt "grey8" / "rgb24" / "yuyv" (arrays [h][w][2]) / "nv12" / "i420" (arrays [h * 3 / 2][w]): the _pix_dets entries with that format; None infers grey / RGB.
+    pixfmt "grey8" / "rgb24" / "yuyv" (arrays [h][w][2]) / "nv12" / "i420" (arrays [h * 3 / 2][w]) / "bgr24" ([h][w][3]) / "rgba32" / "bgra32" ([h][w][4]): the _pix_dets entries with that format; None infers grey / RGB.
     tail "app" sets YOLO2_DETS_APP_TAIL: the records are those of the reference's camera loop (yolo2_postprocess.c)."""
     if precision not in PRECISIONS:
         raise ValueError(f"precision must be one of {PRECISIONS}, not {precision!r}")
@@ -1303,7 +1310,7 @@ def _label_args(labels):
 
 
 def annotate_pix(image: np.ndarray, dets, pixfmt=None, thresh: float = 0.24, labels=None, stream: int = 0):
-    """yolo2_hip_annotate_pix: one image ("grey8" [h][w], "rgb24" [h][w][3], "yuyv" [h][w][2], "nv12" / "i420" [h * 3 / 2][w]; None infers grey / RGB) and its
+    """yolo2_hip_annotate_pix: one image ("grey8" [h][w], "rgb24" [h][w][3], "yuyv" [h][w][2], "nv12" / "i420" [h * 3 / 2][w], "bgr24" [h][w][3], "rgba32" / "bgra32" [h][w][4]; None infers grey / RGB) and its
     records (DET_DTYPE, one per detection) -> (uint8 [h][w][3] with the reference's boxes and tags painted in, records drawn)."""
     im = np.ascontiguousarray(image, dtype=np.uint8)
     fmt = pixfmt if pixfmt is not None else ("grey8" if im.ndim == 2 else "rgb24")
@@ -1373,8 +1380,25 @@ def host_lib():
         H.y2h_write_jpg_rgb24.restype = C.c_long
         H.y2h_jpg_rgb24_bound.argtypes = [C.c_int, C.c_int]
         H.y2h_jpg_rgb24_bound.restype = C.c_size_t
+        H.y2h_packed_to_rgb24.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        H.y2h_packed_to_rgb24.restype = C.c_int
+        H.y2h_last_error.restype = C.c_char_p
         _host_lib = H
     return _host_lib
+
+
+def packed_to_rgb24_host(image, pixfmt: str) -> np.ndarray:
+    """y2h_packed_to_rgb24: a "bgr24" [h][w][3] / "rgba32" / "bgra32" [h][w][4] frame -> uint8 [h][w][3] RGB24, the bytes reordered on
+    the host (the fourth byte is not read) - what the GPU entries' fetch does per pixel"""
+    if pixfmt not in PIXFMTS_PACKED:
+        raise ValueError(f"pixfmt must be one of {PACKED_RGB}, not {pixfmt!r}")
+    im = np.ascontiguousarray(image, dtype=np.uint8)
+    _pix_code(pixfmt, [im])
+    H = host_lib()
+    out = np.empty((im.shape[0], im.shape[1], 3), dtype=np.uint8)
+    if H.y2h_packed_to_rgb24(im.ctypes.data, im.shape[1], im.shape[0], PIXFMTS_PACKED[pixfmt], out.ctypes.data) != 0:
+        raise ValueError(H.y2h_last_error().decode())
+    return out
 
 
 def _rgb24(rgb):
@@ -1519,13 +1543,15 @@ def loop_images_raw(handle, images, pixfmt, precision, flags, thresh, nms, batch
 
 
 def loop_images(handle, images, pixfmt=None, precision: str = "int16", tail: str = "core", thresh: float = 0.24, nms: float = 0.45,
-                labels=None, jpeg_quality=None, batch: int = 64, cap: int = 845, multi: bool = False):
+                labels=None, jpeg_quality=None, batch: int = 64, cap: int = 845, multi: bool = False, out_order: str = "rgb"):
     """yolo2_hip_loop_images_pix / its multi form: the camera loop as one call - host images -> {"dets": per-frame record arrays (one
     per detection, best class), "counts", "final_q" (int16 only, else None), "frames": the annotated frames as uint8 [h][w][3] (or,
     with jpeg_quality 1..100, as JPEG byte strings), "drawn": records drawn per frame}.  The frames go up once; records, draw items
-    and the painted frames are made on the device."""
+    and the painted frames are made on the device.  out_order "bgr": the raw frames come back as B G R (YOLO2_LOOP_OUT_BGR24, what
+    cv2.imshow / cv2.VideoWriter take); an error together with jpeg_quality."""
     if precision not in LOOP_PRECISIONS:
         raise ValueError(f"precision must be one of {tuple(LOOP_PRECISIONS)}, not {precision!r}")
+    out_format = _loop_out_format(out_order, jpeg_quality)
     flags = DETS_BEST_CLASS | (DETS_APP_TAIL if _check_tail(tail) else 0)
     shapes = [_pix_hw(pixfmt, np.asarray(im).shape) for im in images]
     jpeg = jpeg_quality is not None
@@ -1536,7 +1562,7 @@ def loop_images(handle, images, pixfmt=None, precision: str = "int16", tail: str
     name = f"yolo2_hip_{'multi_' if multi else ''}loop_images_pix"
     for attempt in range(2):
         rc, dets, counts, q, outs, sizes, drawn = loop_images_raw(handle, images, pixfmt, LOOP_PRECISIONS[precision], flags, thresh, nms, batch, cap,
-                                                                  labels, int(jpeg), int(jpeg_quality) if jpeg else 0, caps, multi=multi)
+                                                                  labels, out_format, int(jpeg_quality) if jpeg else 0, caps, multi=multi)
         if rc == YOLO2_SUCCESS or attempt or not jpeg or not any(int(sizes[f]) > caps[f] for f in range(len(caps))):
             break
         caps = [jpeg_bound(s[1], s[0]) for s in shapes]   # (the rare frame that compresses to more than its raw size)
@@ -1547,6 +1573,15 @@ def loop_images(handle, images, pixfmt=None, precision: str = "int16", tail: str
         frames = [outs[f].reshape(shapes[f][0], shapes[f][1], 3) for f in range(len(outs))]
     return {"dets": [dets[f, :min(int(counts[f]), cap)] for f in range(len(outs))], "counts": counts,
             "final_q": q if precision == "int16" else None, "frames": frames, "drawn": drawn}
+
+
+def _loop_out_format(out_order, jpeg_quality) -> int:
+    """the loop entries' out_format for out_order "rgb" / "bgr" and an optional JPEG quality"""
+    if out_order not in ("rgb", "bgr"):
+        raise ValueError(f"out_order must be 'rgb' or 'bgr', not {out_order!r}")
+    if out_order == "bgr" and jpeg_quality is not None:
+        raise ValueError("out_order 'bgr' is a raw frame's byte order: it cannot be combined with jpeg_quality")
+    return LOOP_OUT_JPEG if jpeg_quality is not None else (LOOP_OUT_BGR24 if out_order == "bgr" else LOOP_OUT_RGB24)
 
 
 def loop_jpegs_raw(handle, streams, precision, flags, thresh, nms, batch, cap, labels, out_format, quality, caps, multi=False, guard=0):
@@ -1576,13 +1611,14 @@ def loop_jpegs_raw(handle, streams, precision, flags, thresh, nms, batch, cap, l
 
 
 def loop_jpegs(handle, streams, precision: str = "int16", tail: str = "core", thresh: float = 0.24, nms: float = 0.45, labels=None,
-               jpeg_quality=None, batch: int = 64, cap: int = 845, multi: bool = False, strict: bool = True):
+               jpeg_quality=None, batch: int = 64, cap: int = 845, multi: bool = False, strict: bool = True, out_order: str = "rgb"):
     """yolo2_hip_loop_images_jpeg / its multi form: the camera loop as one call from JPEG streams (bytes) - or, mixed in, raw frames
     (uint8 [h][w][3] arrays, e.g. decoded on the host) - with the decoder, the network, the painter and the encoder on the device.
     Returns loop_images' dictionary plus "status" (int32 [n]; not 0: the decoder flagged the frame, its counts and drawn are 0 and
-    its frame is None) and "sizes" ([n] (w, h)).  A flagged frame raises under strict."""
+    its frame is None) and "sizes" ([n] (w, h)).  A flagged frame raises under strict.  out_order: as loop_images'."""
     if precision not in LOOP_PRECISIONS:
         raise ValueError(f"precision must be one of {tuple(LOOP_PRECISIONS)}, not {precision!r} (the loop entries have no int8 form)")
+    out_format = _loop_out_format(out_order, jpeg_quality)
     flags = DETS_BEST_CLASS | (DETS_APP_TAIL if _check_tail(tail) else 0)
     shapes = []
     for i, s in enumerate(streams):
@@ -1599,7 +1635,7 @@ def loop_jpegs(handle, streams, precision: str = "int16", tail: str = "core", th
     name = f"yolo2_hip_{'multi_' if multi else ''}loop_images_jpeg"
     for attempt in range(2):
         rc, dets, counts, q, outs, sizes, drawn, status, ws, hs = loop_jpegs_raw(handle, streams, LOOP_PRECISIONS[precision], flags, thresh, nms, batch,
-                                                                                 cap, labels, int(jpeg), int(jpeg_quality) if jpeg else 0, caps,
+                                                                                 cap, labels, out_format, int(jpeg_quality) if jpeg else 0, caps,
                                                                                  multi=multi)
         if rc == YOLO2_SUCCESS or attempt or not jpeg or not any(int(sizes[f]) > caps[f] for f in range(len(caps))):
             break
