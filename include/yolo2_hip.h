@@ -626,11 +626,23 @@ int yolo2_hip_annotate_images_pix_jpeg_host(yolo2_hip_ctx *ctx, const uint8_t *c
  * with YOLO2_LOOP_OUT_JPEG (quality 1..100) the semantics of yolo2_hip_annotate_images_pix_jpeg_host; with YOLO2_LOOP_OUT_BGR24 the
  * YOLO2_LOOP_OUT_RGB24 frame with bytes 0 and 2 of every pixel exchanged (what cv2.imshow / cv2.VideoWriter take; k_annotate_batch_bgr),
  * same sizes and capacities, from any source format, quality ignored.  drawn [n] may be NULL.
+ * With YOLO2_LOOP_OUT_NV12 / YOLO2_LOOP_OUT_I420 the YOLO2_LOOP_OUT_RGB24 frame comes back as planar YUV 4:2:0, what video encoders take
+ * (ffmpeg -f rawvideo -pix_fmt nv12 | yuv420p), in the layout of YOLO2_PIX_NV12 / YOLO2_PIX_I420: Y [h][w], then NV12's interleaved U V
+ * rows [h/2][w] or I420's U [h/2][w/2] and V [h/2][w/2]; sizes[f] = w * h * 3 / 2 (half of RGB24's bytes over PCIe), a caps[f] below that
+ * is refused up front, and so is an odd width or height (before any launch and any write to the caller's arrays), quality ignored.
+ * The conversion is the library's own definition, in integers (>> arithmetic, no clamp needed: Y 16..235, U and V 16..240):
+ *   per pixel        Y = ((66 R + 129 G + 25 B + 128) >> 8) + 16
+ *   per 2x2 block    U = ((-38 Rs - 74 Gs + 112 Bs + 512) >> 10) + 128,  V = ((112 Rs - 94 Gs - 18 Bs + 512) >> 10) + 128
+ * with Rs, Gs, Bs the sums of the block's four pixels (chroma of the block's mean colour).  It is the BT.601 studio-range forward
+ * transform whose constants pair with the inverse the 4:2:0 and YUYV inputs use (298 / 409 / 100 / 208 / 516); the reference has no
+ * YUV output, and identity with swscale's YUV is not claimed.  y2h_rgb24_to_yuv420 in libyolo2_host.so restates it on the host
+ * (k_annotate_batch_nv12 / _i420 compute it where the painter stores).  Everything else is what the call returns for RGB24 out.
  * A record that would be drawn but whose prob is not finite (or is 2^23 and more) is not drawn; the call then returns YOLO2_ERROR
  * naming the first such frame, everything else is complete.  Refused before any launch: what the entries it joins refuse.
  * Synchronous; batch <= 1024, cap_per_frame <= 65536. */
 enum { YOLO2_LOOP_INT16 = 0, YOLO2_LOOP_FP16 = 1, YOLO2_LOOP_F32TOL = 2 };
-enum { YOLO2_LOOP_OUT_RGB24 = 0, YOLO2_LOOP_OUT_JPEG = 1, YOLO2_LOOP_OUT_BGR24 = 0x33524742 /* V4L2 fourcc 'BGR3' */ };
+enum { YOLO2_LOOP_OUT_RGB24 = 0, YOLO2_LOOP_OUT_JPEG = 1, YOLO2_LOOP_OUT_BGR24 = 0x33524742 /* V4L2 fourcc 'BGR3' */,
+       YOLO2_LOOP_OUT_NV12 = 0x3231564E /* 'NV12' */, YOLO2_LOOP_OUT_I420 = 0x32315559 /* 'YU12' */ };
 int yolo2_hip_loop_images_pix(yolo2_hip_ctx *ctx, int precision, const uint8_t *const *images, const int *widths, const int *heights,
                               int pixfmt, int n, int batch, float thresh, float nms, int flags, yolo2_hip_det *dets, int cap_per_frame,
                               int *counts, int *final_q, const char *const *labels, int n_labels, int out_format, int quality,
@@ -861,7 +873,7 @@ int yolo2_hip_jpeg_split_info(yolo2_hip_ctx *ctx, double *out8);
  * contain YOLO2_DETS_BEST_CLASS; YOLO2_DETS_APP_TAIL is honoured.  Option jpegdec_split is read per call.
  * Refused before any launch, every output (widths / heights included) untouched: what the probe refuses, with its reason; what
  * yolo2_hip_loop_images_pix and yolo2_hip_run_images_jpeg_dets refuse; with YOLO2_LOOP_OUT_RGB24 a caps[f] below w * h * 3 of the
- * header.  A frame whose scan the decoder flags: status[f] != 0, counts[f] = 0, drawn[f] = 0, out_sizes[f] = 0, nothing is written
+ * header; with YOLO2_LOOP_OUT_NV12 / _I420 a header whose width or height is odd, or a caps[f] below w * h * 3 / 2.  A frame whose scan the decoder flags: status[f] != 0, counts[f] = 0, drawn[f] = 0, out_sizes[f] = 0, nothing is written
  * to out[f], and the call returns YOLO2_ERROR naming the first such frame with every other frame complete.
  * Afterwards yolo2_hip_jpeg_last_info, _jpeg_split_info and _loop_last_info describe the call: image_bytes_staged is stream bytes plus
  * raw-frame bytes, image_bytes_h2d everything uploaded (blobs, tables, raw frames); jpeg_last_info [5] counts the painter's and the

@@ -346,4 +346,226 @@ __global__ __launch_bounds__(kAnnoThreads) void k_annotate_batch_bgr(const uint8
     annotate_batch_tiles<true>(table, src_base, out_base);
 }
 
+// ---- The painter into planar YUV 4:2:0 frames (the loop's YOLO2_LOOP_OUT_NV12 / _I420, include/yolo2_hip.h): the RGB24 frame the
+// painter above leaves, converted where it would be stored -
+//   per pixel      Y = ((66 R + 129 G + 25 B + 128) >> 8) + 16
+//   per 2x2 block  U = ((-38 Rs - 74 Gs + 112 Bs + 512) >> 10) + 128,  V = ((112 Rs - 94 Gs - 18 Bs + 512) >> 10) + 128
+// (Rs, Gs, Bs: the sums over the block; arithmetic shifts; Y in 16..235 and U, V in 16..240 for every colour, so nothing is clamped).
+// A chroma byte needs a whole 2x2 block, so the flat mapping above does not serve: here a frame is a grid of PATCHES, 4 pixels wide
+// and 2 rows high (two blocks; the last patch of a row is 2 wide where w % 4 == 2), numbered row by row, ceil(w / 4) * (h / 2) of them.
+// A workgroup takes kAnnoYuvStrip consecutive patches, a lane kAnnoYuvPatches of them (patch j * 256 + tid of the strip) = 16 pixels,
+// the flat painter's count.  Per patch: two runs of 4 source pixels in, two dwords of Y, and one dword U V U V (NV12) or two bytes
+// each of U and V (I420) out.  Every wide store is taken only where its own byte offset allows it - a Y row starts on a dword only
+// where y * w does (w % 4 == 2: every other row), an I420 chroma row (w / 2 bytes) and the V plane ((w / 2) * (h / 2) bytes behind U)
+// may start on any byte - and falls back to byte stores; each output byte is still written once.  The source fetch, the staging of
+// the items that meet the workgroup's rows and the walk from the back of the list are the flat painter's.  AnnoFrame::strips
+// describes the flat mapping and is not read here: the workgroup count comes from anno_yuv_groups, on both sides of the launch.
+constexpr int kAnnoYuvPatches = 2, kAnnoYuvStrip = kAnnoThreads * kAnnoYuvPatches;
+static_assert(kAnnoYuvPatches * 8 == kAnnoGroups * 4, "a lane holds as many pixels as in the flat painter");
+
+// workgroups that have work on a w x h frame (w, h even)
+__host__ __device__ inline int anno_yuv_groups(int w, int h)
+{
+    return (int)((((long long)((w + 3) >> 2)) * (h >> 1) + kAnnoYuvStrip - 1) / kAnnoYuvStrip);
+}
+
+// pixels x .. x + n - 1 (n = 2 or 4, x % 4 == 0) of row y -> c[0 .. n - 1] as R | G << 8 | B << 16, the rest of c[0..3] zero
+__device__ __forceinline__ void anno_load_row4(const uint8_t *__restrict__ src, const AnnoFrame &fr, bool src_al, int x, int y, int n, uint32_t *c)
+{
+    const int p = y * fr.w + x;
+    const bool whole = n == 4, al = whole && src_al && (p & 3) == 0;   // al: the run's 12 (grey: 4) bytes start on a dword
+    if (al && fr.ch == 3) {
+        const uint32_t *s = reinterpret_cast<const uint32_t *>(src + (size_t)p * 3);
+        const uint32_t d0 = s[0], d1 = s[1], d2 = s[2];
+        c[0] = d0 & 0xffffffu;
+        c[1] = (d0 >> 24) | ((d1 & 0xffffu) << 8);
+        c[2] = (d1 >> 16) | ((d2 & 0xffu) << 16);
+        c[3] = d2 >> 8;
+    } else if (al && fr.ch == kLbChBgr24) {
+        const uint32_t *s = reinterpret_cast<const uint32_t *>(src + (size_t)p * 3);
+        const uint32_t d0 = s[0], d1 = s[1], d2 = s[2];
+        c[0] = anno_swap_rb(d0);
+        c[1] = anno_swap_rb((d0 >> 24) | (d1 << 8));
+        c[2] = anno_swap_rb((d1 >> 16) | (d2 << 16));
+        c[3] = anno_swap_rb(d2 >> 8);
+    } else if (whole && (fr.ch == kLbChRgba32 || fr.ch == kLbChBgra32)) {   // (4-byte aligned frames, one dword per pixel)
+        const uint32_t *s = reinterpret_cast<const uint32_t *>(src + (size_t)p * 4);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) c[i] = fr.ch == kLbChBgra32 ? anno_swap_rb(s[i]) : (s[i] & 0xffffffu);
+    } else if (whole && fr.ch == 2) {   // (a YUYV frame is 4-byte aligned and w is even, so p is even: whole pairs)
+        const uint32_t *s = reinterpret_cast<const uint32_t *>(src + (size_t)p * 2);
+        const uint32_t d0 = s[0], d1 = s[1];
+        c[0] = anno_yuyv_px(d0, 0);
+        c[1] = anno_yuyv_px(d0, 1);
+        c[2] = anno_yuyv_px(d1, 0);
+        c[3] = anno_yuyv_px(d1, 1);
+    } else if (fr.ch == kLbChNv12 || fr.ch == kLbChI420) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) c[i] = i < n ? anno_yuv420_px(src, fr.w, fr.h, fr.ch == kLbChNv12, x + i, y) : 0u;
+    } else if (al && fr.ch == 1) {
+        const uint32_t d = *reinterpret_cast<const uint32_t *>(src + p);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) c[i] = ((d >> (8 * i)) & 255u) * 0x010101u;
+    } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) c[i] = i < n ? anno_load_px(src, fr.ch, p + i) : 0u;
+    }
+}
+
+__device__ __forceinline__ uint32_t anno_luma(uint32_t c)
+{
+    return (uint32_t)(((66 * (int)(c & 255u) + 129 * (int)((c >> 8) & 255u) + 25 * (int)((c >> 16) & 255u) + 128) >> 8) + 16);
+}
+
+// U | V << 8 of the 2x2 block a b / c d
+__device__ __forceinline__ uint32_t anno_chroma(uint32_t a, uint32_t b, uint32_t c, uint32_t d)
+{
+    const int rs = (int)((a & 255u) + (b & 255u) + (c & 255u) + (d & 255u));
+    const int gs = (int)(((a >> 8) & 255u) + ((b >> 8) & 255u) + ((c >> 8) & 255u) + ((d >> 8) & 255u));
+    const int bs = (int)(((a >> 16) & 255u) + ((b >> 16) & 255u) + ((c >> 16) & 255u) + ((d >> 16) & 255u));
+    const int u = ((-38 * rs - 74 * gs + 112 * bs + 512) >> 10) + 128, v = ((112 * rs - 94 * gs - 18 * bs + 512) >> 10) + 128;
+    return (uint32_t)u | ((uint32_t)v << 8);
+}
+
+// n (2 or 4) bytes of dword v at out + off: one dword store where n == 4 and the address allows it, bytes otherwise
+__device__ __forceinline__ void anno_store_bytes(uint8_t *__restrict__ out, bool out_al, size_t off, uint32_t v, int n)
+{
+    if (n == 4 && out_al && (off & 3) == 0) {
+        *reinterpret_cast<uint32_t *>(out + off) = v;
+    } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            if (i < n) out[off + i] = (uint8_t)(v >> (8 * i));
+    }
+}
+
+// SEMI: NV12's interleaved U V plane; otherwise I420's U and V planes
+template <bool SEMI>
+__device__ __forceinline__ void annotate_batch_yuv420(const uint8_t *__restrict__ table, const uint8_t *__restrict__ src_base,
+                                                      uint8_t *__restrict__ out_base)
+{
+    __shared__ uint64_t s_font[y2d::kDrawGlyphs];
+    __shared__ DrawItem s_items[kAnnoPiece];
+    __shared__ int s_sel[kAnnoPiece];
+    __shared__ int s_wave[kAnnoThreads / 64];
+
+    const AnnoHeader *hd = reinterpret_cast<const AnnoHeader *>(table);
+    const AnnoFrame fr = reinterpret_cast<const AnnoFrame *>(table + sizeof(AnnoHeader))[blockIdx.y];
+    if ((int)blockIdx.x >= anno_yuv_groups(fr.w, fr.h)) return;   // (the whole workgroup)
+    const DrawItem *items = reinterpret_cast<const DrawItem *>(table + hd->items_off) + fr.item0;
+    const int tid = threadIdx.x;
+    if (tid < y2d::kDrawGlyphs) s_font[tid] = hd->font[tid];
+
+    const int pw = (fr.w + 3) >> 2, npatch = pw * (fr.h >> 1);   // patches per patch row, patches of the frame
+    const int q_lo = (int)blockIdx.x * kAnnoYuvStrip, q_hi = min(npatch, q_lo + kAnnoYuvStrip);
+    const int ya = 2 * (q_lo / pw), yb = 2 * ((q_hi - 1) / pw) + 1;   // the rows this strip touches
+    const uint8_t *src = src_base + fr.src_off;
+    uint8_t *out = out_base + fr.out_off;
+    const bool src_al = ((uintptr_t)src & 3) == 0, out_al = ((uintptr_t)out & 3) == 0;
+
+    // ---- this lane's pixels: patch j is patch q_lo + j * 256 + tid, its pixel (x0 + i, y0 + r) is col[8 * j + 4 * r + i]
+    uint32_t col[kAnnoYuvPatches * 8];
+    int x0[kAnnoYuvPatches], y0[kAnnoYuvPatches], pn[kAnnoYuvPatches];   // pn: the patch's width, 0 where the lane has none
+    unsigned todo = 0;   // bit k: pixel k exists and no item has painted it yet
+#pragma unroll
+    for (int j = 0; j < kAnnoYuvPatches; ++j) {
+        const int q = q_lo + j * kAnnoThreads + tid;
+        x0[j] = y0[j] = pn[j] = 0;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) col[8 * j + k] = 0u;
+        if (q >= q_hi) continue;
+        const int pr = q / pw;
+        x0[j] = (q - pr * pw) * 4;
+        y0[j] = pr * 2;
+        pn[j] = min(4, fr.w - x0[j]);
+        anno_load_row4(src, fr, src_al, x0[j], y0[j], pn[j], &col[8 * j]);
+        anno_load_row4(src, fr, src_al, x0[j], y0[j] + 1, pn[j], &col[8 * j + 4]);
+        todo |= (pn[j] == 4 ? 0xffu : 0x33u) << (8 * j);
+    }
+
+    // ---- the draw list from the back, kAnnoPiece items at a time (the flat painter's staging)
+    for (int hi = fr.n_items; hi > 0; hi -= kAnnoPiece) {
+        const int cnt = min(kAnnoPiece, hi);
+        __syncthreads();   // the piece before this one has been read by everybody (first time round: s_font is written)
+        bool meets = false;
+        if (tid < cnt) {
+            const DrawItem &g = items[hi - 1 - tid];
+            meets = g.ext[1] <= yb && g.ext[3] >= ya;
+        }
+        const unsigned long long m = __ballot(meets);
+        const int wave = tid >> 6, lane = tid & 63;
+        if (lane == 0) s_wave[wave] = __popcll(m);
+        __syncthreads();
+        int before = 0, nsel = 0;
+#pragma unroll
+        for (int v = 0; v < kAnnoThreads / 64; ++v) {
+            if (v < wave) before += s_wave[v];
+            nsel += s_wave[v];
+        }
+        if (meets) s_sel[before + __popcll(m & ((1ull << lane) - 1ull))] = hi - 1 - tid;
+        __syncthreads();
+        for (int e = tid; e < nsel * kAnnoItemDwords; e += kAnnoThreads) {
+            const int s = e / kAnnoItemDwords, d = e - s * kAnnoItemDwords;
+            reinterpret_cast<uint32_t *>(s_items)[e] = reinterpret_cast<const uint32_t *>(items + s_sel[s])[d];
+        }
+        __syncthreads();
+        for (int s = 0; s < nsel && todo; ++s) {
+            const DrawItem &it = s_items[s];
+#pragma unroll
+            for (int k = 0; k < kAnnoYuvPatches * 8; ++k) {
+                uint32_t c;
+                if (((todo >> k) & 1u) && anno_hit(it, s_font, x0[k >> 3] + (k & 3), y0[k >> 3] + ((k >> 2) & 1), c)) {
+                    col[k] = c;
+                    todo &= ~(1u << k);
+                }
+            }
+        }
+    }
+
+    // ---- planar 4:2:0 out
+    const size_t ysize = (size_t)fr.w * fr.h;
+#pragma unroll
+    for (int j = 0; j < kAnnoYuvPatches; ++j) {
+        const int n = pn[j];
+        if (!n) continue;
+        const uint32_t *c = &col[8 * j];
+#pragma unroll
+        for (int r = 0; r < 2; ++r)
+            anno_store_bytes(out, out_al, (size_t)(y0[j] + r) * fr.w + x0[j],
+                             anno_luma(c[4 * r]) | (anno_luma(c[4 * r + 1]) << 8) | (anno_luma(c[4 * r + 2]) << 16) | (anno_luma(c[4 * r + 3]) << 24), n);
+        const uint32_t uv0 = anno_chroma(c[0], c[1], c[4], c[5]), uv1 = anno_chroma(c[2], c[3], c[6], c[7]);   // (uv1 of a 2-wide patch is not stored)
+        if constexpr (SEMI) {
+            anno_store_bytes(out, out_al, ysize + (size_t)(y0[j] >> 1) * fr.w + x0[j], uv0 | (uv1 << 16), n);
+        } else {
+            const size_t cw = (size_t)(fr.w >> 1), at = ysize + (size_t)(y0[j] >> 1) * cw + (x0[j] >> 1), vplane = cw * (fr.h >> 1);
+            const uint32_t uu = (uv0 & 255u) | ((uv1 & 255u) << 8), vv = (uv0 >> 8) | (uv1 & 0xff00u);
+#pragma unroll
+            for (int pl = 0; pl < 2; ++pl) {   // U, then V
+                const size_t off = at + (pl ? vplane : 0);
+                const uint32_t b2 = pl ? vv : uu;
+                if (n == 4 && out_al && (off & 1) == 0) {
+                    *reinterpret_cast<uint16_t *>(out + off) = (uint16_t)b2;
+                } else {
+                    out[off] = (uint8_t)b2;
+                    if (n == 4) out[off + 1] = (uint8_t)(b2 >> 8);
+                }
+            }
+        }
+    }
+}
+
+// grid (max anno_yuv_groups of the chunk's frames, frames); the table of k_annotate_batch.  Frames: Y [h][w], then U V rows [h/2][w]
+__global__ __launch_bounds__(kAnnoThreads) void k_annotate_batch_nv12(const uint8_t *__restrict__ table, const uint8_t *__restrict__ src_base,
+                                                                      uint8_t *__restrict__ out_base)
+{
+    annotate_batch_yuv420<true>(table, src_base, out_base);
+}
+
+// ... Y [h][w], then U [h/2][w/2], then V [h/2][w/2]
+__global__ __launch_bounds__(kAnnoThreads) void k_annotate_batch_i420(const uint8_t *__restrict__ table, const uint8_t *__restrict__ src_base,
+                                                                      uint8_t *__restrict__ out_base)
+{
+    annotate_batch_yuv420<false>(table, src_base, out_base);
+}
+
 }  // namespace y2

@@ -556,14 +556,16 @@ int y2_anno_jpeg_ensure(yolo2_hip_ctx *c, size_t cap_rgb, size_t cap_work, size_
 // ... and the device draw list of the loop entry (yolo2_loop.hip drives it; k_draw_items and the painter are launched here).
 // geom: the painter's table as the host knows it before the records exist (y2_loop_geom_bytes(nf) bytes; returns the most strips of a
 // frame).  _enqueue_items: k_draw_items on st from the records / counts of one tail, then the D2H of the per-frame
-// {items, unprintable} into c->loop.hinfo[b].  _enqueue_paint: k_annotate_batch (bgr: k_annotate_batch_bgr) over the table _enqueue_items left.
+// {items, unprintable} into c->loop.hinfo[b].  _enqueue_paint: the painter of out_format (k_annotate_batch, _bgr, _nv12, _i420; the JPEG
+// route paints RGB24) over the table _enqueue_items left.  out_format (YOLO2_LOOP_OUT_*) also decides what _fill_geom returns: the
+// grid of the 4:2:0 painters counts patches, not flat strips (AnnoFrame::strips itself stays the flat count).
 void y2_loop_free(yolo2_hip_ctx *c);
 size_t y2_loop_geom_bytes(int nf);
-int y2_loop_fill_geom(uint8_t *geom, int nf, const int *widths, const int *heights, int ch, const size_t *src_off, const size_t *out_off);
+int y2_loop_fill_geom(uint8_t *geom, int nf, const int *widths, const int *heights, int ch, const size_t *src_off, const size_t *out_off, int out_format);
 int y2_loop_ensure(yolo2_hip_ctx *c, int frames, int cap, const char *const *labels, int n_labels);
 int y2_loop_enqueue_items(yolo2_hip_ctx *c, int b, int nf, int cap, float thresh, const char *const *labels, int n_labels, const uint8_t *geom_dev,
                           const yolo2_hip_det *dets_dev, const int *counts_dev, hipStream_t st);
-int y2_loop_enqueue_paint(yolo2_hip_ctx *c, int nf, int max_strips, const uint8_t *src_base, uint8_t *out_base, bool bgr, hipStream_t st);
+int y2_loop_enqueue_paint(yolo2_hip_ctx *c, int nf, int max_strips, const uint8_t *src_base, uint8_t *out_base, int out_format, hipStream_t st);
 
 // yolo2_hip.hip: what the images entries and the loop entry share - the letterbox rule, the chunk letterbox launch, PipeBufs' growth
 // (need_hout: the pinned region mirrors; _post: the tail's buffers; _regf: the fp32 region tensors) and the threaded staging copy

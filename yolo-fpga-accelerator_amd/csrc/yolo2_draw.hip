@@ -88,9 +88,14 @@ int fill_table(uint8_t *tbl, const FrameIn *fr, int nf, float thresh, const char
     return max_strips;
 }
 
-void launch_annotate(const uint8_t *table_dev, const uint8_t *src_base, uint8_t *out_base, int max_strips, int nf, hipStream_t st, bool bgr = false)
+// out_format: YOLO2_LOOP_OUT_RGB24 (the annotate entries' only form), _BGR24, or _NV12 / _I420, whose max_strips is the most
+// anno_yuv_groups of a frame (y2_loop_fill_geom)
+void launch_annotate(const uint8_t *table_dev, const uint8_t *src_base, uint8_t *out_base, int max_strips, int nf, hipStream_t st,
+                     int out_format = YOLO2_LOOP_OUT_RGB24)
 {
-    hipLaunchKernelGGL(bgr ? k_annotate_batch_bgr : k_annotate_batch, dim3((unsigned)max_strips, (unsigned)nf), dim3(kAnnoThreads), 0, st, table_dev, src_base, out_base);
+    auto *kernel = out_format == YOLO2_LOOP_OUT_BGR24 ? k_annotate_batch_bgr : out_format == YOLO2_LOOP_OUT_NV12 ? k_annotate_batch_nv12
+                   : out_format == YOLO2_LOOP_OUT_I420 ? k_annotate_batch_i420 : k_annotate_batch;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)max_strips, (unsigned)nf), dim3(kAnnoThreads), 0, st, table_dev, src_base, out_base);
 }
 
 }  // namespace
@@ -274,8 +279,9 @@ void y2_loop_free(yolo2_hip_ctx *c)
 
 size_t y2_loop_geom_bytes(int nf) { return padded(sizeof(AnnoHeader) + (size_t)nf * sizeof(AnnoFrame)); }
 
-int y2_loop_fill_geom(uint8_t *geom, int nf, const int *widths, const int *heights, int ch, const size_t *src_off, const size_t *out_off)
+int y2_loop_fill_geom(uint8_t *geom, int nf, const int *widths, const int *heights, int ch, const size_t *src_off, const size_t *out_off, int out_format)
 {
+    const bool yuv = out_format == YOLO2_LOOP_OUT_NV12 || out_format == YOLO2_LOOP_OUT_I420;
     AnnoHeader *hd = reinterpret_cast<AnnoHeader *>(geom);
     for (int i = 0; i < y2d::kDrawGlyphs; ++i) hd->font[i] = y2d::kDrawFont[i];
     hd->items_off = y2_loop_geom_bytes(nf);
@@ -287,7 +293,7 @@ int y2_loop_fill_geom(uint8_t *geom, int nf, const int *widths, const int *heigh
         af[f].w = widths[f]; af[f].h = heights[f]; af[f].ch = ch;
         af[f].item0 = af[f].n_items = 0;   // (k_draw_items fills them in the device's copy)
         af[f].strips = (int)(((long)widths[f] * heights[f] + kAnnoStripPx - 1) / kAnnoStripPx);
-        max_strips = std::max(max_strips, af[f].strips);
+        max_strips = std::max(max_strips, yuv ? anno_yuv_groups(widths[f], heights[f]) : af[f].strips);   // (strips stays the flat count)
     }
     return max_strips;
 }
@@ -341,9 +347,9 @@ int y2_loop_enqueue_items(yolo2_hip_ctx *c, int b, int nf, int cap, float thresh
     return YOLO2_SUCCESS;
 }
 
-int y2_loop_enqueue_paint(yolo2_hip_ctx *c, int nf, int max_strips, const uint8_t *src_base, uint8_t *out_base, bool bgr, hipStream_t st)
+int y2_loop_enqueue_paint(yolo2_hip_ctx *c, int nf, int max_strips, const uint8_t *src_base, uint8_t *out_base, int out_format, hipStream_t st)
 {
-    launch_annotate(c->loop.table.get(), src_base, out_base, max_strips, nf, st, bgr);
+    launch_annotate(c->loop.table.get(), src_base, out_base, max_strips, nf, st, out_format);
     HIP_TRY(hipGetLastError(), YOLO2_ERROR);
     return YOLO2_SUCCESS;
 }
@@ -366,7 +372,7 @@ extern "C" int yolo2_hip_draw_items_dev(yolo2_hip_ctx *c, uint64_t dets_dev, uin
     const size_t gbytes = y2_loop_geom_bytes(n_frames);
     std::vector<uint8_t> geom(gbytes);
     std::vector<size_t> zero((size_t)n_frames, 0);
-    (void)y2_loop_fill_geom(geom.data(), n_frames, widths, heights, 3, zero.data(), zero.data());
+    (void)y2_loop_fill_geom(geom.data(), n_frames, widths, heights, 3, zero.data(), zero.data(), YOLO2_LOOP_OUT_RGB24);
     Y2DevBuf<uint8_t> dgeom;
     if ((rc = dgeom.alloc(gbytes))) return rc;
     HIP_TRY(hipMemcpy(dgeom.get(), geom.data(), gbytes, hipMemcpyHostToDevice), YOLO2_DMA_ERROR);

@@ -1,5 +1,5 @@
 // yolo2_loop.hip -- the camera loop as one call (include/yolo2_hip.h, "the camera loop as one call"): frames -> detection records AND
-// the annotated frames (RGB24 or JPEG) from ONE upload per chunk.
+// the annotated frames (RGB24, BGR24, planar YUV 4:2:0 as NV12 / I420, or JPEG) from ONE upload per chunk.
 //
 // It joins what the images -> detections entries (yolo2_hip.hip) and the annotate entries (yolo2_draw.hip) do in two calls, on the
 // device: the chunk's frames stay in PipeBufs' device staging buffer from the letterbox to the painter, the records stay in HBM from
@@ -44,6 +44,9 @@ using namespace y2;
 
 namespace {
 size_t padded(size_t b) { return (b + 255) & ~(size_t)255; }
+bool out_yuv420(int out_format) { return out_format == YOLO2_LOOP_OUT_NV12 || out_format == YOLO2_LOOP_OUT_I420; }
+// bytes of a painted frame on the device: planar 4:2:0 (w, h even), or packed RGB24 / BGR24 (also what the JPEG route paints for its encoder)
+size_t out_frame_bytes(int out_format, int w, int h) { return out_yuv420(out_format) ? (size_t)w * h * 3 / 2 : (size_t)w * h * 3; }
 }  // namespace
 
 // (y2_draw.hpp) everything the loop entries refuse that can be seen without a context
@@ -54,8 +57,8 @@ int y2_loop_check(int precision, const uint8_t *const *images, const int *widths
     if (!images || !widths || !heights || !dets || !counts || !out || !caps || !sizes) return fail(YOLO2_ERROR, "loop: null argument");
     if (precision != YOLO2_LOOP_INT16 && precision != YOLO2_LOOP_FP16 && precision != YOLO2_LOOP_F32TOL)
         return fail(YOLO2_ERROR, "loop: unknown precision %d (YOLO2_LOOP_INT16, _FP16 or _F32TOL)", precision);
-    if (out_format != YOLO2_LOOP_OUT_RGB24 && out_format != YOLO2_LOOP_OUT_JPEG && out_format != YOLO2_LOOP_OUT_BGR24)
-        return fail(YOLO2_ERROR, "loop: unknown output format %d (YOLO2_LOOP_OUT_RGB24, _JPEG or _BGR24)", out_format);
+    if (out_format != YOLO2_LOOP_OUT_RGB24 && out_format != YOLO2_LOOP_OUT_JPEG && out_format != YOLO2_LOOP_OUT_BGR24 && !out_yuv420(out_format))
+        return fail(YOLO2_ERROR, "loop: unknown output format %d (YOLO2_LOOP_OUT_RGB24, _JPEG, _BGR24, _NV12 or _I420)", out_format);
     if (!(flags & YOLO2_DETS_BEST_CLASS)) return fail(YOLO2_ERROR, "loop: flags must contain YOLO2_DETS_BEST_CLASS, the form the painter draws");
     const Y2PixDesc *pd = y2_pix_desc(pixfmt, nullptr);
     if (!pd) return YOLO2_ERROR;
@@ -72,8 +75,12 @@ int y2_loop_check(int precision, const uint8_t *const *images, const int *widths
         if ((rc = y2_letterbox_args(widths[f], heights[f], ch, 416, 416, a, true))) return rc;
         if (out_format == YOLO2_LOOP_OUT_JPEG) {
             if ((rc = y2_jpeg_check_frame(widths[f], heights[f], f))) return rc;
-        } else if (caps[f] < (size_t)widths[f] * heights[f] * 3) {
-            return fail(YOLO2_ERROR, "loop: output buffer too small for frame %d (%zu < %zu bytes)", f, caps[f], (size_t)widths[f] * heights[f] * 3);
+        } else {
+            if (out_yuv420(out_format) && ((widths[f] | heights[f]) & 1))
+                return fail(YOLO2_ERROR, "loop: frame %d is %dx%d: YUV 4:2:0 output needs an even width and height (odd sizes are refused)", f, widths[f],
+                            heights[f]);
+            const size_t need = out_frame_bytes(out_format, widths[f], heights[f]);
+            if (caps[f] < need) return fail(YOLO2_ERROR, "loop: output buffer too small for frame %d (%zu < %zu bytes)", f, caps[f], need);
         }
     }
     return YOLO2_SUCCESS;
@@ -118,7 +125,7 @@ static int loop_run(yolo2_hip_ctx *c, int precision, const uint8_t *const *image
             const int f = k * batch + i;
             in += padded(y2_frame_bytes(widths[f], heights[f], ch));
             jf[(size_t)i] = {widths[f], heights[f], rgb, caps[f]};
-            rgb += padded((size_t)widths[f] * heights[f] * 3);
+            rgb += padded(out_frame_bytes(out_format, widths[f], heights[f]));
         }
         if (jpeg) {
             if ((rc = y2_jpeg_plan(jf.data(), in_chunk(k), &plans[(size_t)k]))) return rc;
@@ -176,7 +183,7 @@ static int loop_run(yolo2_hip_ctx *c, int precision, const uint8_t *const *image
                 counts[f] = 0;
                 if (drawn) drawn[f] = 0;
                 sizes[f] = 0;
-                off += jpeg ? std::min((size_t)J.hsizes[b].get()[i], caps[f]) : padded((size_t)widths[f] * heights[f] * 3);
+                off += jpeg ? std::min((size_t)J.hsizes[b].get()[i], caps[f]) : padded(out_frame_bytes(out_format, widths[f], heights[f]));
                 continue;
             }
             yolo2_hip_det *dst = dets + (size_t)f * cap;
@@ -193,7 +200,7 @@ static int loop_run(yolo2_hip_ctx *c, int precision, const uint8_t *const *image
                 sizes[f] = size;
                 if (size > caps[f] && short_frame < 0) short_frame = f;
             } else {
-                const size_t bytes = (size_t)widths[f] * heights[f] * 3;
+                const size_t bytes = out_frame_bytes(out_format, widths[f], heights[f]);
                 memcpy(out[f], A.hout[b].get() + off, bytes);
                 off += padded(bytes);
                 sizes[f] = bytes;
@@ -218,7 +225,7 @@ static int loop_run(yolo2_hip_ctx *c, int precision, const uint8_t *const *image
             out_offs[(size_t)i] = out_off;
             jf[(size_t)i] = {widths[f], heights[f], out_off, caps[f]};
             off += padded(fbytes[(size_t)i]);
-            out_off += padded((size_t)widths[f] * heights[f] * 3);
+            out_off += padded(out_frame_bytes(out_format, widths[f], heights[f]));
             info.image_bytes_staged += dec && !y2_jpegdec_raw(dec, f) ? stream_bytes[f] : fbytes[(size_t)i];
         }
         if (!dec) y2_stage_images(hin, images + first, offs.data(), fbytes.data(), nf);   // the frames, once
@@ -230,7 +237,7 @@ static int loop_run(yolo2_hip_ctx *c, int precision, const uint8_t *const *image
             items[f].off = offs[(size_t)i];
             if ((rc = y2_letterbox_args(widths[first + i], heights[first + i], ch, 416, 416, items[f].a, true))) { cleanup(); return rc; }
         }
-        const int max_strips = y2_loop_fill_geom(hin + lb_bytes, nf, cw.data(), chh.data(), ch, offs.data(), out_offs.data());
+        const int max_strips = y2_loop_fill_geom(hin + lb_bytes, nf, cw.data(), chh.data(), ch, offs.data(), out_offs.data(), out_format);
         const size_t jtab = off;
         if (jpeg) {
             y2_jpeg_write_table(jf.data(), nf, quality, hin + jtab);
@@ -271,7 +278,7 @@ static int loop_run(yolo2_hip_ctx *c, int precision, const uint8_t *const *image
         if (dec && (rc = y2_jpegdec_status_d2h(dec, k, P.s_out))) { cleanup(); return rc; }
         if ((rc = y2_loop_enqueue_items(c, b, nf, cap, thresh, labels, n_labels, P.dbytes[b].get() + lb_bytes, P.post[b].dets.get(), P.post[b].counts.get(),
                                         P.s_out)) ||
-            (rc = y2_loop_enqueue_paint(c, nf, max_strips, P.dbytes[b].get(), jpeg ? J.rgb.get() : A.dout[b].get(), out_format == YOLO2_LOOP_OUT_BGR24, P.s_out))) {
+            (rc = y2_loop_enqueue_paint(c, nf, max_strips, P.dbytes[b].get(), jpeg ? J.rgb.get() : A.dout[b].get(), jpeg ? YOLO2_LOOP_OUT_RGB24 : out_format, P.s_out))) {
             cleanup();
             return rc;
         }

@@ -312,6 +312,33 @@ bool yuv420_to_rgb24(const uint8_t *frame, uint8_t *rgb, int w, int h, bool semi
     return true;
 }
 
+// RGB24 -> planar YUV 4:2:0, the loop's YOLO2_LOOP_OUT_NV12 / _I420 (include/yolo2_hip.h): Y per pixel, U and V from the sums of each
+// 2x2 block; arithmetic shifts of possibly negative sums, nothing to clamp (Y 16..235, U and V 16..240 for every colour)
+bool rgb24_to_yuv420(const uint8_t *rgb, uint8_t *frame, int w, int h, bool semi)
+{
+    if (!rgb || !frame || w <= 0 || h <= 0 || (w & 1) || (h & 1)) return false;
+    const size_t cw = (size_t)w / 2, ch = (size_t)h / 2;
+    uint8_t *chroma = frame + (size_t)w * h;
+    for (int y = 0; y < h; ++y)
+        for (int x = 0; x < w; ++x) {
+            const uint8_t *p = rgb + ((size_t)y * w + x) * 3;
+            frame[(size_t)y * w + x] = (uint8_t)(((66 * p[0] + 129 * p[1] + 25 * p[2] + 128) >> 8) + 16);
+        }
+    for (size_t by = 0; by < ch; ++by)
+        for (size_t bx = 0; bx < cw; ++bx) {
+            int s[3] = {0, 0, 0};
+            for (int k = 0; k < 4; ++k) {
+                const uint8_t *p = rgb + ((2 * by + (size_t)(k >> 1)) * w + 2 * bx + (size_t)(k & 1)) * 3;
+                for (int c = 0; c < 3; ++c) s[c] += p[c];
+            }
+            const int u = ((-38 * s[0] - 74 * s[1] + 112 * s[2] + 512) >> 10) + 128, v = ((112 * s[0] - 94 * s[1] - 18 * s[2] + 512) >> 10) + 128;
+            const size_t at = by * cw + bx;
+            chroma[semi ? 2 * at : at] = (uint8_t)u;
+            chroma[semi ? 2 * at + 1 : cw * ch + at] = (uint8_t)v;
+        }
+    return true;
+}
+
 // Packed BGR24 / RGBA32 / BGRA32 -> RGB24: byte k of pixel p is src[p * bpp + (swap ? 2 - k : k)]; a fourth byte is not read
 bool packed_to_rgb24(const uint8_t *src, uint8_t *rgb, int w, int h, int fmt)
 {

@@ -64,6 +64,11 @@ bool yuyv_to_rgb24(const uint8_t *yuyv, uint8_t *rgb, int w, int h);
 // replicated.  The library's own extension of the reference's conversion (the reference has no 4:2:0 input); the GPU entries compute
 // the same byte per fetched pixel (csrc/letterbox.hpp, LbYuv420).  False for a null pointer or an odd or non-positive width / height.
 bool yuv420_to_rgb24(const uint8_t *frame, uint8_t *rgb, int w, int h, bool semi);
+// The way out: an RGB24 frame -> NV12 (semi) or I420, w * h * 3 / 2 bytes, the layout above.  Y = ((66 R + 129 G + 25 B + 128) >> 8) + 16
+// per pixel; U = ((-38 Rs - 74 Gs + 112 Bs + 512) >> 10) + 128 and V = ((112 Rs - 94 Gs - 18 Bs + 512) >> 10) + 128 per 2x2 block from the
+// sums of its four pixels.  The library's own definition (the reference has no YUV output; not swscale's); the loop's 4:2:0 painters
+// compute the same bytes (csrc/kernels_draw.hpp).  False for a null pointer or an odd or non-positive width / height, nothing written.
+bool rgb24_to_yuv420(const uint8_t *rgb, uint8_t *frame, int w, int h, bool semi);
 // A packed BGR24 (B G R, w h 3 bytes), RGBA32 (R G B X, w h 4 bytes) or BGRA32 (B G R X) frame -> RGB24: the bytes reordered, the fourth
 // byte not read.  fmt: kFrameBgr24 / kFrameRgba32 / kFrameBgra32 below.  The GPU entries pick the same byte per fetched pixel
 // (csrc/letterbox.hpp, LbPacked).  False for a null pointer, a non-positive width / height or another fmt.

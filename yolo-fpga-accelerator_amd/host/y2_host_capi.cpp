@@ -143,6 +143,15 @@ int y2h_yuv420_to_rgb24(const uint8_t *frame, uint8_t *rgb, int w, int h, int se
     return -1;
 }
 
+// rgb24_to_yuv420 (semi_planar: NV12, otherwise I420; out: w * h * 3 / 2 bytes): 0, or -1 (y2h_last_error) with out untouched for a null
+// pointer or an odd or non-positive width / height
+int y2h_rgb24_to_yuv420(const uint8_t *rgb, int w, int h, int semi_planar, uint8_t *out)
+{
+    if (rgb24_to_yuv420(rgb, out, w, h, semi_planar != 0)) return 0;
+    g_err = "rgb24_to_yuv420: null pointer or bad frame " + std::to_string(w) + "x" + std::to_string(h) + " (NV12 / I420 frames have an even width and an even height)";
+    return -1;
+}
+
 // packed_to_rgb24; pixfmt: the YOLO2_PIX_* fourcc of BGR24 ('BGR3'), RGBA32 ('AB24') or BGRA32 ('AR24').  0, or -1 (y2h_last_error) for a
 // null pointer, a non-positive width / height or another pixfmt
 int y2h_packed_to_rgb24(const uint8_t *src, int w, int h, int pixfmt, uint8_t *rgb)

@@ -65,7 +65,8 @@ struct AppConfig {
     std::string video_mjpeg;        // --video-mjpeg: concatenated JPEG streams (a camera's MJPEG), cut where each stream ends
     std::string decode = "host";    // --decode: where JPEG streams are decoded - host (the decode pool) or gpu (yolo2_hip_run_images_jpeg_dets)
     bool annotate_gpu = false;   // --annotate-gpu: annotated frames come from yolo2_hip_annotate_images_pix_host, in the reference's look
-    std::string annotated_format;   // --annotated-format jpg: they are encoded on the GPU too (yolo2_hip_annotate_images_pix_jpeg_host); "" / ppm: PPM
+    std::string annotated_format;   // --annotated-format jpg: they are encoded on the GPU too (yolo2_hip_annotate_images_pix_jpeg_host); "" / ppm: PPM;
+                                    // nv12 / yuv420p (--loop-gpu): raw planar YUV 4:2:0 frames, converted by the painter (YOLO2_LOOP_OUT_NV12 / _I420)
     int jpeg_quality = 80;          // --jpeg-quality, the reference streamer's default
     bool loop_gpu = false;          // --loop-gpu: records and annotated frames from ONE accelerator call per chunk (yolo2_hip_loop_images_pix)
     int video_w = 640, video_h = 480;
@@ -133,6 +134,9 @@ void print_usage(const char *prog)
         "                        needs --post gpu\n"
         "  --annotated-format <ppm|jpg>  with --annotate-gpu: jpg writes frame_NNNNNN.jpg, the reference's MJPEG stream of the frame,\n"
         "                        encoded on the GPU (yolo2_hip_annotate_images_pix_jpeg_host); default ppm\n"
+        "                        nv12 | yuv420p (also: i420), with --loop-gpu only: frame_NNNNNN.nv12 / frame_NNNNNN.yuv, the frame as raw planar\n"
+        "                        YUV 4:2:0 (w * h * 3 / 2 bytes, even sizes; the names of --video-pix-fmt), converted where the GPU paints it;\n"
+        "                        `cat` of the files is a rawvideo stream for a video encoder (ffmpeg -f rawvideo -pix_fmt nv12 | yuv420p)\n"
         "  --jpeg-quality <1..100>  quality of --annotated-format jpg (default 80)\n"
         "  --loop-gpu            with --annotate-gpu --save-annotated-dir and --post gpu: one accelerator call per chunk makes the records AND\n"
         "                        the annotated frames from one upload (yolo2_hip_loop_images_pix; with --decode gpu\n"
@@ -703,8 +707,13 @@ void run_stream(AppConfig cfg)
     if (cfg.batch <= 0) throw std::runtime_error("--batch must be positive");
     const bool annotate_gpu = cfg.annotate_gpu && !cfg.save_dir.empty();
     if (annotate_gpu && cfg.post != "gpu") throw std::runtime_error("--annotate-gpu paints the records of --post gpu");
-    if (!cfg.annotated_format.empty() && cfg.annotated_format != "ppm" && cfg.annotated_format != "jpg")
-        throw std::runtime_error("--annotated-format is ppm or jpg, not " + cfg.annotated_format);
+    if (cfg.annotated_format == "i420") cfg.annotated_format = "yuv420p";
+    const bool annotate_yuv = cfg.annotated_format == "nv12" || cfg.annotated_format == "yuv420p";
+    if (!cfg.annotated_format.empty() && cfg.annotated_format != "ppm" && cfg.annotated_format != "jpg" && !annotate_yuv)
+        throw std::runtime_error("--annotated-format is ppm, jpg, nv12 or yuv420p, not " + cfg.annotated_format);
+    if (annotate_yuv && !cfg.loop_gpu)
+        throw std::runtime_error("--annotated-format " + cfg.annotated_format + " needs --loop-gpu: the YUV 4:2:0 frames are made by the loop call's painter");
+    const char *annotated_ext = cfg.annotated_format == "jpg" ? "jpg" : cfg.annotated_format == "nv12" ? "nv12" : annotate_yuv ? "yuv" : "ppm";
     const bool annotate_jpg = cfg.annotated_format == "jpg";
     if (annotate_jpg && !annotate_gpu) throw std::runtime_error("--annotated-format jpg encodes the frames of --annotate-gpu --save-annotated-dir");
     const y2h::Network net = y2h::parse_cfg(cfg.cfg_path);
@@ -833,11 +842,11 @@ void run_stream(AppConfig cfg)
                     if (jf) write_jsonl(jf, src.mode(), fr.source, fr.frame_index, infer_idx, fr.img.w, fr.img.h, c.dets[(size_t)f], names);
                     if (annotate_gpu) {
                         char name[64];
-                        std::snprintf(name, sizeof(name), "frame_%06d.%s", infer_idx, annotate_jpg ? "jpg" : "ppm");
+                        std::snprintf(name, sizeof(name), "frame_%06d.%s", infer_idx, annotated_ext);
                         const std::string path = (fs::path(cfg.save_dir) / name).string();
                         FILE *pf = std::fopen(path.c_str(), "wb");
                         if (!pf) throw std::runtime_error("Cannot write " + path);
-                        if (!annotate_jpg) std::fprintf(pf, "P6\n%d %d\n255\n", fr.img.w, fr.img.h);
+                        if (!annotate_jpg && !annotate_yuv) std::fprintf(pf, "P6\n%d %d\n255\n", fr.img.w, fr.img.h);   // (jpg, nv12, yuv: the bytes as they came)
                         std::fwrite(c.annotated[(size_t)f].data(), 1, c.annotated[(size_t)f].size(), pf);
                         std::fclose(pf);
                     } else if (!cfg.save_dir.empty()) {
@@ -937,13 +946,14 @@ void run_stream(AppConfig cfg)
                                 for (int attempt = 0; attempt < 2; ++attempt) {     // (JPEG: room as below, a second call with the encoder's bound)
                                     for (int k = 0; k < m2; ++k) {
                                         std::vector<uint8_t> &a = ck->annotated[(size_t)idx[(size_t)k]];
-                                        const size_t raw = (size_t)w2[(size_t)k] * h2[(size_t)k] * 3, bound = yolo2_hip_jpeg_bound(w2[(size_t)k], h2[(size_t)k]);
+                                        const size_t raw = (size_t)w2[(size_t)k] * h2[(size_t)k] * 3 / (annotate_yuv ? 2 : 1), bound = yolo2_hip_jpeg_bound(w2[(size_t)k], h2[(size_t)k]);
                                         caps[(size_t)k] = !annotate_jpg ? raw : attempt ? bound : std::min(bound, raw + 4096);
                                         a.resize(caps[(size_t)k]);
                                         outs[(size_t)k] = a.data();
                                         sizes[(size_t)k] = 0;
                                     }
-                                    const int fmt = annotate_jpg ? YOLO2_LOOP_OUT_JPEG : YOLO2_LOOP_OUT_RGB24;
+                                    const int fmt = annotate_jpg ? YOLO2_LOOP_OUT_JPEG : cfg.annotated_format == "nv12" ? YOLO2_LOOP_OUT_NV12
+                                                    : annotate_yuv ? YOLO2_LOOP_OUT_I420 : YOLO2_LOOP_OUT_RGB24;
                                     const int rc = gpu_decode ? yolo2_hip_loop_images_jpeg(ctx, prec, p2.data(), s2.data(), w2.data(), h2.data(), m2, cfg.batch, cfg.thresh,
                                                                                            cfg.nms, det_flags, r2.data(), cap, c2.data(), &q, labels.data(),
                                                                                            (int)labels.size(), fmt, cfg.jpeg_quality, outs.data(), caps.data(),

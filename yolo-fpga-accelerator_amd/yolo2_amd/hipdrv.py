@@ -80,6 +80,7 @@ PLANAR_420 = tuple(PIXFMTS_420)
 PIXFMTS_PACKED = {"bgr24": 0x33524742, "rgba32": 0x34324241, "bgra32": 0x34325241}
 PACKED_RGB = tuple(PIXFMTS_PACKED)
 LOOP_OUT_RGB24, LOOP_OUT_JPEG, LOOP_OUT_BGR24 = 0, 1, 0x33524742   # include/yolo2_hip.h YOLO2_LOOP_OUT_*
+LOOP_OUT_NV12, LOOP_OUT_I420 = 0x3231564E, 0x32315559                # ... the annotated frame as planar YUV 4:2:0
 
 
 def pix_code(pixfmt: str) -> int:
@@ -1382,6 +1383,8 @@ def host_lib():
         H.y2h_jpg_rgb24_bound.restype = C.c_size_t
         H.y2h_packed_to_rgb24.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
         H.y2h_packed_to_rgb24.restype = C.c_int
+        H.y2h_rgb24_to_yuv420.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        H.y2h_rgb24_to_yuv420.restype = C.c_int
         H.y2h_last_error.restype = C.c_char_p
         _host_lib = H
     return _host_lib
@@ -1397,6 +1400,20 @@ def packed_to_rgb24_host(image, pixfmt: str) -> np.ndarray:
     H = host_lib()
     out = np.empty((im.shape[0], im.shape[1], 3), dtype=np.uint8)
     if H.y2h_packed_to_rgb24(im.ctypes.data, im.shape[1], im.shape[0], PIXFMTS_PACKED[pixfmt], out.ctypes.data) != 0:
+        raise ValueError(H.y2h_last_error().decode())
+    return out
+
+
+def rgb24_to_yuv420(im, fmt: str) -> np.ndarray:
+    """y2h_rgb24_to_yuv420: an RGB24 frame uint8 [h][w][3] (w, h even) -> uint8 [h * 3 / 2][w], the "nv12" or "i420" frame the loop
+    returns with out_order=fmt - the library's own integer BT.601 studio-range conversion, chroma from each 2x2 block's sums"""
+    if fmt not in ("nv12", "i420"):
+        raise ValueError(f"fmt must be 'nv12' or 'i420', not {fmt!r}")
+    rgb = _rgb24(im)
+    h, w = rgb.shape[:2]
+    H = host_lib()
+    out = np.empty((h * 3 // 2, w), dtype=np.uint8)
+    if H.y2h_rgb24_to_yuv420(rgb.ctypes.data, w, h, 1 if fmt == "nv12" else 0, out.ctypes.data) != 0:
         raise ValueError(H.y2h_last_error().decode())
     return out
 
@@ -1548,7 +1565,8 @@ def loop_images(handle, images, pixfmt=None, precision: str = "int16", tail: str
     per detection, best class), "counts", "final_q" (int16 only, else None), "frames": the annotated frames as uint8 [h][w][3] (or,
     with jpeg_quality 1..100, as JPEG byte strings), "drawn": records drawn per frame}.  The frames go up once; records, draw items
     and the painted frames are made on the device.  out_order "bgr": the raw frames come back as B G R (YOLO2_LOOP_OUT_BGR24, what
-    cv2.imshow / cv2.VideoWriter take); an error together with jpeg_quality."""
+    cv2.imshow / cv2.VideoWriter take); "nv12" / "i420": as planar YUV 4:2:0, uint8 [h * 3 / 2][w], what video encoders take
+    (YOLO2_LOOP_OUT_NV12 / _I420; even sizes only; rgb24_to_yuv420 of the "rgb" frame).  Each an error together with jpeg_quality."""
     if precision not in LOOP_PRECISIONS:
         raise ValueError(f"precision must be one of {tuple(LOOP_PRECISIONS)}, not {precision!r}")
     out_format = _loop_out_format(out_order, jpeg_quality)
@@ -1558,7 +1576,7 @@ def loop_images(handle, images, pixfmt=None, precision: str = "int16", tail: str
     if jpeg:
         caps = [min(jpeg_bound(s[1], s[0]), s[0] * s[1] * 3 + 4096) for s in shapes]
     else:
-        caps = [s[0] * s[1] * 3 for s in shapes]
+        caps = [_loop_raw_bytes(out_order, s) for s in shapes]
     name = f"yolo2_hip_{'multi_' if multi else ''}loop_images_pix"
     for attempt in range(2):
         rc, dets, counts, q, outs, sizes, drawn = loop_images_raw(handle, images, pixfmt, LOOP_PRECISIONS[precision], flags, thresh, nms, batch, cap,
@@ -1570,18 +1588,31 @@ def loop_images(handle, images, pixfmt=None, precision: str = "int16", tail: str
     if jpeg:
         frames = [outs[f][:int(sizes[f])].tobytes() for f in range(len(outs))]
     else:
-        frames = [outs[f].reshape(shapes[f][0], shapes[f][1], 3) for f in range(len(outs))]
+        frames = [outs[f].reshape(_loop_raw_shape(out_order, shapes[f])) for f in range(len(outs))]
     return {"dets": [dets[f, :min(int(counts[f]), cap)] for f in range(len(outs))], "counts": counts,
             "final_q": q if precision == "int16" else None, "frames": frames, "drawn": drawn}
 
 
 def _loop_out_format(out_order, jpeg_quality) -> int:
-    """the loop entries' out_format for out_order "rgb" / "bgr" and an optional JPEG quality"""
-    if out_order not in ("rgb", "bgr"):
-        raise ValueError(f"out_order must be 'rgb' or 'bgr', not {out_order!r}")
-    if out_order == "bgr" and jpeg_quality is not None:
-        raise ValueError("out_order 'bgr' is a raw frame's byte order: it cannot be combined with jpeg_quality")
-    return LOOP_OUT_JPEG if jpeg_quality is not None else (LOOP_OUT_BGR24 if out_order == "bgr" else LOOP_OUT_RGB24)
+    """the loop entries' out_format for out_order "rgb" / "bgr" / "nv12" / "i420" and an optional JPEG quality"""
+    if out_order not in _LOOP_OUT_ORDERS:
+        raise ValueError(f"out_order must be one of {tuple(_LOOP_OUT_ORDERS)}, not {out_order!r}")
+    if out_order != "rgb" and jpeg_quality is not None:
+        raise ValueError(f"out_order {out_order!r} is a raw frame's layout: it cannot be combined with jpeg_quality")
+    return LOOP_OUT_JPEG if jpeg_quality is not None else _LOOP_OUT_ORDERS[out_order]
+
+
+_LOOP_OUT_ORDERS = {"rgb": LOOP_OUT_RGB24, "bgr": LOOP_OUT_BGR24, "nv12": LOOP_OUT_NV12, "i420": LOOP_OUT_I420}
+
+
+def _loop_raw_bytes(out_order, hw) -> int:
+    """bytes of a raw annotated frame of hw = (h, w)"""
+    return hw[0] * hw[1] * 3 // 2 if out_order in ("nv12", "i420") else hw[0] * hw[1] * 3
+
+
+def _loop_raw_shape(out_order, hw):
+    """... and the shape it comes back in (an odd-sized 4:2:0 frame does not exist: the library refuses it)"""
+    return (hw[0] * 3 // 2, hw[1]) if out_order in ("nv12", "i420") else (hw[0], hw[1], 3)
 
 
 def loop_jpegs_raw(handle, streams, precision, flags, thresh, nms, batch, cap, labels, out_format, quality, caps, multi=False, guard=0):
@@ -1631,7 +1662,7 @@ def loop_jpegs(handle, streams, precision: str = "int16", tail: str = "core", th
     if jpeg:
         caps = [min(jpeg_bound(s[1], s[0]), s[0] * s[1] * 3 + 4096) if s[0] and s[1] else 0 for s in shapes]
     else:
-        caps = [s[0] * s[1] * 3 for s in shapes]
+        caps = [_loop_raw_bytes(out_order, s) for s in shapes]
     name = f"yolo2_hip_{'multi_' if multi else ''}loop_images_jpeg"
     for attempt in range(2):
         rc, dets, counts, q, outs, sizes, drawn, status, ws, hs = loop_jpegs_raw(handle, streams, LOOP_PRECISIONS[precision], flags, thresh, nms, batch,
@@ -1646,7 +1677,7 @@ def loop_jpegs(handle, streams, precision: str = "int16", tail: str = "core", th
     if jpeg:
         frames = [None if status[f] else outs[f][:int(sizes[f])].tobytes() for f in range(n)]
     else:
-        frames = [None if status[f] else outs[f].reshape(shapes[f][0], shapes[f][1], 3) for f in range(n)]
+        frames = [None if status[f] else outs[f].reshape(_loop_raw_shape(out_order, shapes[f])) for f in range(n)]
     return {"dets": [dets[f, :min(int(counts[f]), cap)] for f in range(n)], "counts": counts, "final_q": q if precision == "int16" else None,
             "frames": frames, "drawn": drawn, "status": status, "sizes": [(int(ws[i]), int(hs[i])) for i in range(n)]}
 
