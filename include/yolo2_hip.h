@@ -599,6 +599,30 @@ size_t yolo2_hip_jpeg_bound(int w, int h);
  * *size = the stream's length.  If it exceeds cap, nothing at or beyond cap is written and the call returns YOLO2_ERROR ("too
  * small"; *size is still set, jpeg_out_dev may be 0 if cap is 0).  Enqueues on `stream` and synchronises it. */
 int yolo2_hip_jpeg_encode_rgb24(uint64_t rgb_dev, int w, int h, int quality, uint64_t jpeg_out_dev, size_t cap, size_t *size, void *stream);
+/* ------------------------------------------------------- annotated frames as PNG: the library's own definition
+ *
+ * The reference's camera loop saves its annotated frames as frame_%06d.png with stb_image_write v1.09 (linux_app/src/main.c:1086).
+ * Its zlib is a serial hash-chain LZ77 over the whole frame with fixed Huffman codes, so its BYTES are not the definition.
+ * The library's PNG file is one that any decoder opens and whose pixels are exactly the frame's (csrc/png_huff.hpp states the
+ * format once, for the kernels and for y2h_write_png_rgb24 / y2h_zlib_huff in libyolo2_host.so):
+ *   signature, IHDR (8-bit RGB, no interlace), one IDAT, IEND;
+ *   rows filtered by stb_image_write's rule: the five filters with bpp = 3, each scored by the sum of abs((int8_t)byte), the first
+ *     filter in order 0..4 with the strictly smallest score; bytes outside the image are zero;
+ *   IDAT: zlib header 78 01, deflate blocks of 32 KiB of filtered bytes, each with dynamic Huffman codes and NO LZ matches (literals
+ *     and the end-of-block code; one distance code of zero bits; code lengths sent plainly), or stored where that is shorter than
+ *     8 * len + 35 bits; Adler-32.
+ * On the GPU the deflate stage is there (yolo2_hip_zlib_huff, six launches of csrc/kernels_png.hpp: histograms; codes; bit offsets;
+ * pack; copy; framing); the row filter and the file's framing run on the host (y2h_write_png_rgb24). */
+
+/* The most bytes the zlib stream of n bytes can take, exact arithmetic: 6 + n + ceil(42 * max(1, ceil(n / 32768)) / 8), every block
+ * stored at the worst bit alignment. */
+size_t yolo2_hip_zlib_huff_bound(size_t n);
+/* n arbitrary bytes at in_dev (n < 2^31; in_dev may be 0 if n is 0) -> a complete zlib stream at out_dev that zlib's inflate reads,
+ * the bytes y2h_zlib_huff writes; neither address needs any alignment.  *size = the stream's length; nothing at or behind
+ * out_dev + *size is written.  A cap below yolo2_hip_zlib_huff_bound(n) is refused before any launch.  Runs on the null stream of
+ * the calling thread's device and returns when the stream is complete. */
+int yolo2_hip_zlib_huff(uint64_t in_dev, size_t n, uint64_t out_dev, size_t cap, size_t *size);
+
 /* yolo2_hip_annotate_images_pix_host with JPEG streams out: the painter writes RGB24 into device memory, the encoder follows on the
  * same stream, and the frame never visits the host.  jpeg[f] has room for caps[f] bytes and receives min(sizes[f], caps[f]); the
  * download copies the sizes first and then only the bytes in use.  A frame whose stream exceeds its capacity gets its sizes[f]

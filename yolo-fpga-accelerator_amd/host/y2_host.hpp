@@ -96,6 +96,15 @@ int draw_font(char *chars, uint64_t *words);   // the packed font: 38 characters
 // 0); -1 for a null frame or a width / height outside 1..65535.  jpg_rgb24_bound: the most bytes a w x h frame can take (0: bad size).
 long write_jpg_rgb24(const uint8_t *rgb, int w, int h, int quality, uint8_t *out, size_t cap);
 size_t jpg_rgb24_bound(int w, int h);
+// The annotated frame as a PNG file, the library's own definition (csrc/png_huff.hpp; y2_png.cpp): 8-bit RGB, rows filtered by the rule
+// of stb_image_write v1.09 (the reference's writer, linux_app/src/main.c:1086), one IDAT of dynamic-Huffman deflate blocks without LZ
+// matches; not stb's bytes.  Returns the file's length and stores the bytes below `cap`; -1 for a null frame or a bad size.
+// png_rgb24_bound: exact arithmetic, the most bytes a w x h frame can take (0: bad size).  zlib_huff: the deflate stage alone, a
+// complete zlib stream of n arbitrary bytes (zlib_huff_bound(n) at most); yolo2_hip_zlib_huff produces the same bytes on the GPU.
+long write_png_rgb24(const uint8_t *rgb, int w, int h, uint8_t *out, size_t cap);
+size_t png_rgb24_bound(int w, int h);
+long zlib_huff(const uint8_t *in, size_t n, uint8_t *out, size_t cap);
+size_t zlib_huff_bound(size_t n);
 
 // ---------------------------------------------------------------- weights (yolo2_model.cpp:158-227)
 struct WeightsI16 {

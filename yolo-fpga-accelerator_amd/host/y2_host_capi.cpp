@@ -217,6 +217,22 @@ long y2h_write_jpg_rgb24(const uint8_t *rgb, int w, int h, int quality, uint8_t 
 }
 size_t y2h_jpg_rgb24_bound(int w, int h) { return jpg_rgb24_bound(w, h); }
 
+// write_png_rgb24 / zlib_huff (y2_png.cpp): return the length (bytes below cap are stored), or -1 (y2h_last_error)
+long y2h_write_png_rgb24(const uint8_t *rgb, int w, int h, uint8_t *out, size_t cap)
+{
+    const long n = write_png_rgb24(rgb, w, h, out, cap);
+    if (n < 0) g_err = "write_png_rgb24: null buffer or bad frame " + std::to_string(w) + "x" + std::to_string(h) + " (1..65535, below 2 GiB)";
+    return n;
+}
+size_t y2h_png_rgb24_bound(int w, int h) { return png_rgb24_bound(w, h); }
+long y2h_zlib_huff(const uint8_t *in, size_t n, uint8_t *out, size_t cap)
+{
+    const long r = zlib_huff(in, n, out, cap);
+    if (r < 0) g_err = "zlib_huff: null buffer";
+    return r;
+}
+size_t y2h_zlib_huff_bound(size_t n) { return zlib_huff_bound(n); }
+
 // decode_image (y2_codec.cpp): JPEG / PNG bytes -> RGB bytes [h][w][3]; returns w*h*3, or -1 (y2h_last_error) / -2 (capacity)
 long y2h_decode_image(const unsigned char *data, long n, int *w, int *h, unsigned char *rgb, long cap)
 {

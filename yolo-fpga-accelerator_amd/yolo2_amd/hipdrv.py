@@ -67,6 +67,7 @@ EXPORTS = [
     "yolo2_hip_jpeg_probe", "yolo2_hip_jpeg_reason_name", "yolo2_hip_decode_jpeg_host", "yolo2_hip_decode_jpeg_ref",
     "yolo2_hip_run_images_jpeg_dets", "yolo2_hip_jpeg_last_info", "yolo2_hip_decode_jpeg_split_ref", "yolo2_hip_jpeg_split_info",
     "yolo2_hip_loop_images_jpeg", "yolo2_hip_multi_loop_images_jpeg", "yolo2_hip_multi_run_images_jpeg_dets",
+    "yolo2_hip_zlib_huff_bound", "yolo2_hip_zlib_huff",
 ]
 
 # include/yolo2_hip.h YOLO2_PIX_*: the pixfmt argument of the _pix entries ("yuyv": packed YUYV 4:2:2, arrays uint8 [h][w][2])
@@ -325,6 +326,8 @@ def lib():
     # annotated frames as JPEG (include/yolo2_hip.h "annotated frames as JPEG")
     sig("yolo2_hip_jpeg_bound", [i32, i32], C.c_size_t)
     sig("yolo2_hip_jpeg_encode_rgb24", [u64, i32, i32, i32, u64, C.c_size_t, C.POINTER(C.c_size_t), vp])
+    sig("yolo2_hip_zlib_huff_bound", [C.c_size_t], C.c_size_t)
+    sig("yolo2_hip_zlib_huff", [u64, C.c_size_t, u64, C.c_size_t, C.POINTER(C.c_size_t)])
     for name in ("annotate_images_pix_jpeg_host", "multi_annotate_images_pix_jpeg_host"):
         sig("yolo2_hip_" + name, [vp, vp, vp, vp, i32, i32, i32, vp, i32, vp, C.c_float, vp, i32, i32, vp, vp, vp, vp])
     # the camera loop as one call (include/yolo2_hip.h "the camera loop as one call")
@@ -1385,6 +1388,14 @@ def host_lib():
         H.y2h_packed_to_rgb24.restype = C.c_int
         H.y2h_rgb24_to_yuv420.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
         H.y2h_rgb24_to_yuv420.restype = C.c_int
+        H.y2h_write_png_rgb24.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
+        H.y2h_write_png_rgb24.restype = C.c_long
+        H.y2h_png_rgb24_bound.argtypes = [C.c_int, C.c_int]
+        H.y2h_png_rgb24_bound.restype = C.c_size_t
+        H.y2h_zlib_huff.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
+        H.y2h_zlib_huff.restype = C.c_long
+        H.y2h_zlib_huff_bound.argtypes = [C.c_size_t]
+        H.y2h_zlib_huff_bound.restype = C.c_size_t
         H.y2h_last_error.restype = C.c_char_p
         _host_lib = H
     return _host_lib
@@ -1464,6 +1475,65 @@ def jpeg_encode(rgb, quality: int = 80, stream: int = 0) -> bytes:
             if buf.value:
                 L.yolo2_hip_free(buf)
     return out.tobytes()
+
+
+def write_png_host(rgb) -> bytes:
+    """y2h_write_png_rgb24: an RGB24 frame as a PNG file by the library's own definition (csrc/png_huff.hpp: stb_image_write's row
+    filter rule, dynamic-Huffman deflate without LZ matches), written on the host"""
+    im = _rgb24(rgb)
+    H = host_lib()
+    cap = H.y2h_png_rgb24_bound(im.shape[1], im.shape[0])
+    out = np.empty(max(cap, 1), dtype=np.uint8)
+    n = H.y2h_write_png_rgb24(im.ctypes.data, im.shape[1], im.shape[0], out.ctypes.data, cap)
+    if n < 0 or n > cap:
+        raise ValueError(f"y2h_write_png_rgb24 refused a {im.shape[1]}x{im.shape[0]} frame")
+    return out[:n].tobytes()
+
+
+def zlib_huff_host(data: bytes) -> bytes:
+    """y2h_zlib_huff: the deflate stage of write_png_host alone, a complete zlib stream of `data`"""
+    src = np.frombuffer(bytes(data) or b"\0", dtype=np.uint8)
+    H = host_lib()
+    cap = H.y2h_zlib_huff_bound(len(data))
+    out = np.empty(cap, dtype=np.uint8)
+    n = H.y2h_zlib_huff(src.ctypes.data, len(data), out.ctypes.data, cap)
+    if n < 0 or n > cap:
+        raise ValueError(H.y2h_last_error().decode())
+    return out[:n].tobytes()
+
+
+def _device_stream(entry: str, data: np.ndarray, cap: int, call, guard: int = 0):
+    """data up, call(src, dst, cap, size) on the device, the stream (and `guard` bytes behind it, preset to 0xA5) back"""
+    L = lib()
+    src, dst = C.c_uint64(0), C.c_uint64(0)
+    size = C.c_size_t(0)
+    room = np.full(cap + guard, 0xA5, dtype=np.uint8)
+    try:
+        check(L.yolo2_hip_alloc(max(data.nbytes, 16), C.byref(src)), "alloc")
+        check(L.yolo2_hip_alloc(room.nbytes, C.byref(dst)), "alloc")
+        if data.nbytes:
+            check(L.yolo2_hip_memcpy_h2d(src, data.ctypes.data_as(C.c_void_p), data.nbytes), "h2d")
+        check(L.yolo2_hip_memcpy_h2d(dst, room.ctypes.data_as(C.c_void_p), room.nbytes), "h2d")
+        check(call(src, dst, cap, C.byref(size)), entry)
+        check(L.yolo2_hip_memcpy_d2h(room.ctypes.data_as(C.c_void_p), dst, room.nbytes), "d2h")
+    finally:
+        for buf in (src, dst):
+            if buf.value:
+                L.yolo2_hip_free(buf)
+    if guard and not (room[size.value:] == 0xA5).all():
+        raise AssertionError(f"{entry} wrote behind the {size.value} bytes of its stream")
+    return room[:size.value].tobytes()
+
+
+def zlib_huff(data: bytes, guard: int = 0) -> bytes:
+    """yolo2_hip_zlib_huff: the deflate stage of write_png_host on the GPU, on arbitrary bytes: a complete zlib stream (zlib.decompress
+    reads it), the same bytes as zlib_huff_host.  guard > 0: the buffer is the bound + guard bytes, and everything behind the
+    stream must come back untouched (AssertionError)"""
+    src = np.frombuffer(bytes(data), dtype=np.uint8)
+    L = lib()
+    cap = int(L.yolo2_hip_zlib_huff_bound(len(data)))
+    return _device_stream("yolo2_hip_zlib_huff", src, cap,
+                          lambda s, dst, cap, size: L.yolo2_hip_zlib_huff(s, len(data), dst, cap, size), guard)
 
 
 def annotate_images_jpeg_raw(handle, images, dets, counts, batch: int, thresh: float, quality: int, caps, labels=None, pixfmt=None,
