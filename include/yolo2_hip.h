@@ -599,6 +599,15 @@ size_t yolo2_hip_jpeg_bound(int w, int h);
  * *size = the stream's length.  If it exceeds cap, nothing at or beyond cap is written and the call returns YOLO2_ERROR ("too
  * small"; *size is still set, jpeg_out_dev may be 0 if cap is 0).  Enqueues on `stream` and synchronises it. */
 int yolo2_hip_jpeg_encode_rgb24(uint64_t rgb_dev, int w, int h, int quality, uint64_t jpeg_out_dev, size_t cap, size_t *size, void *stream);
+/* Options "jpeg_subsample" = 0 | 420 and "jpeg_restart" = 0..65535 (yolo2_hip_set_option, read per call; unset: the stream and the
+ * launches above, exactly) select the library's own forms of the stream (csrc/jpeg_tables.hpp "the modes"), which
+ * the reference's writer does not have: 4:2:0 - MCUs of 16x16 pixels as Y00 Y01 Y10 Y11 Cb Cr, a chroma sample the fp32 mean of its
+ * 2x2 - and restart intervals of R MCUs - DRI in front of SOS, FF D0..D7 between the intervals, DC predictors zero again.  Every
+ * JPEG-writing entry honours them: the annotate entries and the loop entries those of their context, yolo2_hip_jpeg_encode_rgb24
+ * the process-wide set (ctx = NULL).  y2h_write_jpg_rgb24_ex is the same encoder on the host.
+ * yolo2_hip_jpeg_bound_ex: the most bytes a w x h stream of a mode can take (its header, twice the scan's bound of 1660 bits per
+ * block, 3 bytes per interval, 2); 0 for a size or a mode the entries refuse.  (0, 0) is yolo2_hip_jpeg_bound. */
+size_t yolo2_hip_jpeg_bound_ex(int w, int h, int subsample, int restart);
 /* ------------------------------------------------------- annotated frames as PNG: the library's own definition
  *
  * The reference's camera loop saves its annotated frames as frame_%06d.png with stb_image_write v1.09 (linux_app/src/main.c:1086).

@@ -4,11 +4,20 @@
 // never computes one.  The stream is the one the reference's MJPEG streamer sends (stb_image_write v1.09 through
 // linux_app/src/yolo2_mjpeg_server.c:221-238): baseline, three components without subsampling, the typical tables of ITU-T T.81
 // Annex K, no restart markers.
+//
+// Two modes of the library's own lead away from that stream (the reference's writer has neither; "the modes" below): subsample = 420
+// (MCUs of 16 x 16 pixels, chroma halved both ways) and restart = R (a marker after every R MCUs).  Mode (0, 0) is the stream above.
 #pragma once
 #include <cstddef>
 #include <cstdint>
 #include <cstring>
 #include <initializer_list>
+
+#if defined(__HIPCC__)
+#define Y2T_HD __host__ __device__
+#else
+#define Y2T_HD
+#endif
 
 namespace y2j {
 
@@ -62,6 +71,40 @@ enum { kDcLuma = 0, kAcLuma = 1, kDcChroma = 2, kAcChroma = 3 };
 
 // Where the frame's size sits in the header: SOF0's height and width, two big-endian bytes each.
 constexpr int kHeaderHeightAt = 159, kHeaderWidthAt = 161;
+
+// ---- the modes
+//   subsample = 420: an MCU is 16 x 16 pixels (edge pixels repeated) and six blocks in the order Y00 Y01 Y10 Y11 Cb Cr; SOF0 says 2x2,
+//     1x1, 1x1.  A Y block is the Y block of mode 0 at its place.  A chroma sample is the mean of the four fp32 Cb (Cr) values of its
+//     2 x 2 pixels, ((a + b) + (c + d)) * 0.25f with a and b from the upper row, each operation rounded on its own; then the same AAN
+//     passes and fdtbl[1].  Tables, zigzag and the other header segments are mode 0's.
+//   restart = R (MCUs per interval, 1..65535): DRI (FF DD 00 04 Rhi Rlo) in front of SOS; after every R MCUs except at the scan's end
+//     the last partial byte is filled with ones, FF D0+(k & 7) follows for interval k = 0, 1, ... and the DC predictors are zero
+//     again.  Stuffing applies to entropy bytes only, never to the marker.
+constexpr int kHeaderLumaSamplingAt = 165, kHeaderSosAt = kHeaderBytes - 14, kDriBytes = 6, kRestartMax = 65535;
+
+inline bool mode_ok(int subsample, int restart) { return (subsample == 0 || subsample == 420) && restart >= 0 && restart <= kRestartMax; }
+Y2T_HD inline int mcu_pixels(int subsample) { return subsample == 420 ? 16 : 8; }   // each way
+Y2T_HD inline int mcu_blocks(int subsample) { return subsample == 420 ? 6 : 3; }
+Y2T_HD inline bool block_is_luma(int subsample, int k) { return subsample == 420 ? k < 4 : k == 0; }   // k: the block's place in its MCU
+// The DC predictor of the block at place k of an MCU is the DC of the block this many places before it in stream order - the previous
+// block of its component - and zero where that block would lie before the interval's first.
+Y2T_HD inline int dc_pred_back(int subsample, int k) { return subsample != 420 ? 3 : k == 0 ? 3 : k < 4 ? 1 : 6; }
+Y2T_HD inline int header_bytes(int restart) { return kHeaderBytes + (restart ? kDriBytes : 0); }
+// byte i of the header of a w x h stream: `base` is Tables::header
+Y2T_HD inline uint8_t header_byte(const uint8_t *base, int i, int w, int h, int subsample, int restart)
+{
+    if (restart && i >= kHeaderSosAt) {
+        if (i >= kHeaderSosAt + kDriBytes) return base[i - kDriBytes];
+        const int dri[kDriBytes] = {0xFF, 0xDD, 0, 4, restart >> 8, restart & 255};
+        return (uint8_t)dri[i - kHeaderSosAt];
+    }
+    if (i == kHeaderHeightAt) return (uint8_t)(h >> 8);
+    if (i == kHeaderHeightAt + 1) return (uint8_t)h;
+    if (i == kHeaderWidthAt) return (uint8_t)(w >> 8);
+    if (i == kHeaderWidthAt + 1) return (uint8_t)w;
+    if (i == kHeaderLumaSamplingAt && subsample == 420) return 0x22;
+    return base[i];
+}
 
 struct Tables {
     float fdtbl[2][64];      // [0] luma, [1] chroma: what a transformed coefficient (natural index) is multiplied by before rounding
@@ -131,18 +174,20 @@ inline void make_tables(int quality, Tables *t)
     put({0xFF, 0xDA, 0, 12, 3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0});                           // SOS: whole spectrum, one scan
 }
 
-inline void header_for(const Tables &t, int w, int h, uint8_t *out)
-{
-    std::memcpy(out, t.header, kHeaderBytes);
-    out[kHeaderHeightAt] = (uint8_t)(h >> 8); out[kHeaderHeightAt + 1] = (uint8_t)h;
-    out[kHeaderWidthAt] = (uint8_t)(w >> 8);  out[kHeaderWidthAt + 1] = (uint8_t)w;
-}
-
 // the most bytes a w x h stream can take: header, every block at kBlockBitsMax with every byte stuffed, EOI
 inline size_t stream_bound(int w, int h)
 {
     const size_t blocks = 3 * (size_t)((w + 7) / 8) * (size_t)((h + 7) / 8);
     return (size_t)kHeaderBytes + 2 * ((blocks * kBlockBitsMax + 7) / 8) + 2;
+}
+
+// the same for a mode: blocks and header of the mode, and per interval at most one more stuffed byte than its blocks' share (an
+// interval of an odd number of worst-case blocks ends on half a byte) and the marker
+inline size_t stream_bound_ex(int w, int h, int subsample, int restart)
+{
+    const size_t m = (size_t)mcu_pixels(subsample), mcus = (((size_t)w + m - 1) / m) * (((size_t)h + m - 1) / m);
+    const size_t blocks = mcus * (size_t)mcu_blocks(subsample), intervals = restart ? (mcus + (size_t)restart - 1) / (size_t)restart : 0;
+    return (size_t)header_bytes(restart) + 2 * ((blocks * kBlockBitsMax + 7) / 8) + 3 * intervals + 2;
 }
 
 }  // namespace y2j

@@ -40,7 +40,9 @@ struct JpegFrame {
     unsigned long long us_off;    // its unstuffed stream in the work area, bytes (a multiple of 256), room for blocks * kBlockBitsMax bits
     unsigned long long cap;       // bytes the caller has room for: nothing at or beyond it is written
     int w, h, mcux;               // mcux: MCUs per row
-    int n_blk;                    // 3 * MCUs
+    int n_blk;                    // 3 * MCUs (6 * MCUs with subsample 420)
+    int subsample, restart;       // the mode (jpeg_tables.hpp); (0, 0): the reference's stream
+    unsigned n_int, rst0;         // its intervals (1 without restart) and where they start in rst_off
     unsigned blk0;                // its first block in coef / blk_off
     unsigned wg0, n_wg;           // its groups of kJpegBlocks blocks in wg_sum / wg_base
     unsigned seg0;                // its segments in seg_ff / seg_base (room for the bound)
@@ -460,4 +462,413 @@ __global__ __launch_bounds__(kJpegSegThreads) void k_jpeg_emit(const uint8_t *__
     }
 }
 
+// ================================================================================================ the modes (jpeg_tables.hpp)
+//
+// subsample = 420 and restart = R run kernels of their own; mode (0, 0) runs the eight launches above and nothing below.  A block is
+// still one lane of stages B and C, in stream order: block b = bpm * mcu + k, bpm = 3 or 6 blocks per MCU.
+//   k_jpeg_transform420  A   a workgroup owns kJpeg420Mcus whole MCUs: their RGB bytes go into LDS once (every pixel is fetched once
+//                            per workgroup, not once per component), then wavefront k takes block place k of every MCU - Y00 Y01 Y10
+//                            Y11 from 8 x 8 pixels, Cb and Cr from the 2 x 2 means of 16 x 16.  (subsample 0 keeps k_jpeg_transform.)
+//   k_jpeg_lengths_rst   B   the DC predictor is the previous block of the component (dc_pred_back), zero in an interval's first MCU.
+//                            The bit position is no prefix sum any more: an interval's end rounds it up to a byte.  ONE scan with an
+//                            associative operator does it: a run of blocks is the function p -> seen ? ceil8(p + pre) + post : p + pre
+//                            of the position p it starts at (pre: bits up to its first interval end, post: bits behind that end, whose
+//                            later roundings do not depend on p because they start from a multiple of 8), and two runs compose to a run
+//                            (JpegRun).  Exclusive scan within the workgroup -> blk_off (pre) / blk_post (post, seen in bit 31); the
+//                            group's run -> wg_sum / wg_post.  R = 1 (many ends per group) and an interval that spans groups and scan
+//                            rounds are the same operator.
+//   k_jpeg_scan_groups_rst B the same scan over the groups' runs in 64 bits -> wg_base, totals; zeroes the groups' end dwords
+//   k_jpeg_pack_rst      C   as k_jpeg_pack; the lane of a block that ends an interval (or the scan) fills its last byte with ones,
+//                            the lane of a block that starts one leaves rst_off[interval], the interval's byte offset in the
+//                            unstuffed stream.  Markers stay out of that stream, so k_jpeg_count_ff / _scan_segs run as they are.
+//   k_jpeg_sizes_rst     D   adds DRI and the markers' bytes to the sizes k_jpeg_scan_segs left
+//   k_jpeg_emit_rst      D   an entropy byte goes to header + its offset + stuffed zeros before it + 2 * intervals completed before
+//                            it; the lane of an interval's first byte writes FF Dn in front of it.  The interval of a byte: one
+//                            binary search per segment for the intervals its two ends lie in, one per lane inside that range, then
+//                            a step per interval start passed.
+
+constexpr int kJpeg420Mcus = 64;                    // MCUs per workgroup of k_jpeg_transform420: one per lane of a wavefront
+constexpr int kJpeg420Threads = 6 * kJpeg420Mcus;   // a wavefront per block place, so a wavefront runs one of the two code paths
+constexpr int kJpeg420RowDwords = 12;               // an MCU row: 16 pixels of 3 bytes
+// an MCU in LDS: 16 rows, and one dword so that the lanes of a wavefront (consecutive MCUs, same row and column) hit different banks
+constexpr int kJpeg420McuDwords = 16 * kJpeg420RowDwords + 1;
+// k_jpeg_pack_rst's LDS image: kJpegPackDwords' terms, with up to 7 fill bits behind every block (a block ends at most one interval)
+constexpr int kJpegPackDwordsRst = (31 + kJpegBlocks * (y2j::kBlockBitsMax + 7) + 31) / 32 + 1;
+
+__device__ inline uint32_t jpeg_byte(const uint32_t *w, int j) { return (w[j >> 2] >> (8 * (j & 3))) & 255u; }   // (j is a constant after unrolling)
+
+// grid (ceil(max MCUs / kJpeg420Mcus), frames)
+__global__ __launch_bounds__(kJpeg420Threads) void k_jpeg_transform420(const uint8_t *__restrict__ table, const uint8_t *__restrict__ src_base,
+                                                                       int16_t *__restrict__ coef)
+{
+    __shared__ float s_fd[2][64];
+    __shared__ uint32_t s_px[kJpeg420Mcus * kJpeg420McuDwords];
+    const JpegHeader *hd = reinterpret_cast<const JpegHeader *>(table);
+    const JpegFrame fr = jpeg_frame(table, blockIdx.y);
+    const int tid = threadIdx.x, n_mcu = fr.n_blk / 6, mcu0 = (int)blockIdx.x * kJpeg420Mcus;
+    if (mcu0 >= n_mcu) return;   // (the whole workgroup)
+    if (tid < 128) s_fd[tid >> 6][tid & 63] = hd->t.fdtbl[tid >> 6][tid & 63];
+    const int nm = min(kJpeg420Mcus, n_mcu - mcu0);
+    const uint8_t *src = src_base + fr.src_off;
+    // the MCUs' bytes, a dword of an MCU row per step (the source has any alignment and edge pixels repeat: byte loads)
+    for (int j = tid; j < nm * 16 * kJpeg420RowDwords; j += kJpeg420Threads) {
+        const int m = j / (16 * kJpeg420RowDwords), rem = j - m * (16 * kJpeg420RowDwords), r = rem / kJpeg420RowDwords, q = rem - r * kJpeg420RowDwords;
+        const int mcu = mcu0 + m, my = mcu / fr.mcux, mx = mcu - my * fr.mcux;
+        const uint8_t *row = src + (size_t)min(my * 16 + r, fr.h - 1) * fr.w * 3;
+        uint32_t v = 0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int at = 4 * q + i, px = at / 3, ch = at - 3 * px;
+            v |= (uint32_t)row[(size_t)min(mx * 16 + px, fr.w - 1) * 3 + ch] << (8 * i);
+        }
+        s_px[m * kJpeg420McuDwords + rem] = v;
+    }
+    __syncthreads();
+    const int k = tid >> 6, m = tid & 63;   // block place (the same for a wavefront), MCU
+    if (m >= nm) return;
+    const int base = m * kJpeg420McuDwords;
+    float d[64];
+    if (k < 4) {   // a Y block: k_jpeg_transform's Y, operation for operation
+        const int at = base + (k >> 1) * 8 * kJpeg420RowDwords + (k & 1) * 6;
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            uint32_t w[6];
+#pragma unroll
+            for (int i = 0; i < 6; ++i) w[i] = s_px[at + r * kJpeg420RowDwords + i];
+#pragma unroll
+            for (int c = 0; c < 8; ++c) {
+                const float R = (float)jpeg_byte(w, 3 * c), G = (float)jpeg_byte(w, 3 * c + 1), B = (float)jpeg_byte(w, 3 * c + 2);
+                d[r * 8 + c] = __fsub_rn(__fadd_rn(__fadd_rn(__fmul_rn(0.299f, R), __fmul_rn(0.587f, G)), __fmul_rn(0.114f, B)), 128.f);
+            }
+        }
+    } else {       // Cb or Cr: the four values of a 2 x 2 as k_jpeg_transform computes them, then ((a + b) + (c + d)) * 0.25f
+        const float c0 = k == 4 ? -0.16874f : 0.5f, c1 = k == 4 ? -0.33126f : -0.41869f, c2 = k == 4 ? 0.5f : -0.08131f;
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            uint32_t w[2][kJpeg420RowDwords];
+#pragma unroll
+            for (int i = 0; i < 2 * kJpeg420RowDwords; ++i) w[i / kJpeg420RowDwords][i % kJpeg420RowDwords] = s_px[base + 2 * r * kJpeg420RowDwords + i];
+#pragma unroll
+            for (int c = 0; c < 8; ++c) {
+                float v[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int at = 3 * (2 * c + (i & 1));
+                    const float R = (float)jpeg_byte(w[i >> 1], at), G = (float)jpeg_byte(w[i >> 1], at + 1), B = (float)jpeg_byte(w[i >> 1], at + 2);
+                    v[i] = __fadd_rn(__fadd_rn(__fmul_rn(c0, R), __fmul_rn(c1, G)), __fmul_rn(c2, B));
+                }
+                d[r * 8 + c] = __fmul_rn(__fadd_rn(__fadd_rn(v[0], v[1]), __fadd_rn(v[2], v[3])), 0.25f);
+            }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 8; ++r) jpeg_aan(d[8 * r], d[8 * r + 1], d[8 * r + 2], d[8 * r + 3], d[8 * r + 4], d[8 * r + 5], d[8 * r + 6], d[8 * r + 7]);
+#pragma unroll
+    for (int c = 0; c < 8; ++c) jpeg_aan(d[c], d[8 + c], d[16 + c], d[24 + c], d[32 + c], d[40 + c], d[48 + c], d[56 + c]);
+    uint32_t pk[32];
+#pragma unroll
+    for (int i = 0; i < 32; ++i) pk[i] = 0;
+#pragma unroll
+    for (int i = 0; i < 64; ++i) {
+        const float v = __fmul_rn(d[i], s_fd[k >= 4][i]);
+        const int q = (int)(v < 0.f ? __fsub_rn(v, 0.5f) : __fadd_rn(v, 0.5f));
+        const int z = y2j::kZigzag[i];
+        pk[z >> 1] |= ((uint32_t)q & 0xffffu) << (16 * (z & 1));
+    }
+    uint4 *o = reinterpret_cast<uint4 *>(coef + ((size_t)fr.blk0 + (size_t)(mcu0 + m) * 6 + k) * 64);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) o[i] = make_uint4(pk[4 * i], pk[4 * i + 1], pk[4 * i + 2], pk[4 * i + 3]);
+}
+
+// ---- the scan's operator
+
+// A run of blocks as a function of the bit position p it starts at: seen ? ceil8(p + pre) + post : p + pre
+template <typename T>
+struct JpegRun {
+    T pre, post;
+    uint32_t seen;
+    __device__ inline T at(T p) const { return seen ? ((p + pre + 7) & ~(T)7) + post : p + pre; }
+};
+// run a, then run b
+template <typename T>
+__device__ inline JpegRun<T> jpeg_run_then(const JpegRun<T> &a, const JpegRun<T> &b)
+{
+    if (!a.seen) return {a.pre + b.pre, b.post, b.seen};
+    if (!b.seen) return {a.pre, a.post + b.pre, 1u};
+    return {a.pre, ((a.post + b.pre + 7) & ~(T)7) + b.post, 1u};
+}
+// inclusive scan of one run per lane over a workgroup of N lanes (N a power of two), through the three arrays
+template <int N, typename T>
+__device__ inline JpegRun<T> jpeg_scan_runs(JpegRun<T> v, T *s_pre, T *s_post, uint32_t *s_seen, int tid)
+{
+    s_pre[tid] = v.pre; s_post[tid] = v.post; s_seen[tid] = v.seen;
+    __syncthreads();
+#pragma unroll
+    for (int d = 1; d < N; d <<= 1) {
+        JpegRun<T> t = {0, 0, 0u};
+        if (tid >= d) t = {s_pre[tid - d], s_post[tid - d], s_seen[tid - d]};
+        __syncthreads();
+        v = jpeg_run_then(t, v);
+        s_pre[tid] = v.pre; s_post[tid] = v.post; s_seen[tid] = v.seen;
+        __syncthreads();
+    }
+    return v;
+}
+__device__ inline JpegRun<uint32_t> jpeg_run_unpack(uint32_t pre, uint32_t post) { return {pre, post & 0x7fffffffu, post >> 31}; }
+
+// what the mode makes of block b of a frame
+struct JpegPlace {
+    int pred_back;   // the DC predictor is the DC of block b - pred_back; 0: the predictor is zero
+    bool luma, starts, ends;   // starts / ends an interval (the scan's end ends one)
+    unsigned interval;
+};
+__device__ inline JpegPlace jpeg_place_of(const JpegFrame &fr, int b)
+{
+    const int bpm = y2j::mcu_blocks(fr.subsample), mcu = b / bpm, k = b - mcu * bpm, R = fr.restart ? fr.restart : fr.n_blk;
+    const int in = mcu % R, back = y2j::dc_pred_back(fr.subsample, k);
+    JpegPlace p;
+    p.pred_back = in * bpm + k >= back ? back : 0;   // (zero where the component has no block in the interval yet)
+    p.luma = y2j::block_is_luma(fr.subsample, k);
+    p.starts = in == 0 && k == 0;
+    p.ends = k == bpm - 1 && (in == R - 1 || b == fr.n_blk - 1);
+    p.interval = (unsigned)(mcu / R);
+    return p;
+}
+
+// grid (ceil(max n_blk / kJpegBlocks), frames)
+__global__ __launch_bounds__(kJpegBlocks) void k_jpeg_lengths_rst(const uint8_t *__restrict__ table, const int16_t *__restrict__ coef,
+                                                                  uint32_t *__restrict__ blk_off, uint32_t *__restrict__ blk_post,
+                                                                  uint32_t *__restrict__ wg_sum, uint32_t *__restrict__ wg_post)
+{
+    __shared__ uint32_t s_code[4 * 256];
+    __shared__ uint32_t s_pre[kJpegBlocks], s_post[kJpegBlocks], s_seen[kJpegBlocks];
+    const JpegFrame fr = jpeg_frame(table, blockIdx.y);
+    if (blockIdx.x >= fr.n_wg) return;   // (the whole workgroup)
+    const int tid = threadIdx.x;
+    jpeg_stage_codes(s_code, table, tid, kJpegBlocks);
+    __syncthreads();
+    const int b = (int)blockIdx.x * kJpegBlocks + tid;
+    JpegRun<uint32_t> own = {0u, 0u, 0u};
+    if (b < fr.n_blk) {
+        const size_t blk = (size_t)fr.blk0 + b;
+        const JpegPlace pl = jpeg_place_of(fr, b);
+        const uint32_t *dc = s_code + (pl.luma ? 0 : 2) * 256, *ac = dc + 256;
+        JpegBlock c;
+        c.load(coef, blk);
+        const int pred = pl.pred_back ? (int)coef[(blk - pl.pred_back) * 64] : 0;
+        const int cat = jpeg_category(c.at(0) - pred);
+        uint32_t bits = (dc[cat] >> 16) + cat;
+        int run = 0;
+#pragma unroll
+        for (int i = 1; i < 64; ++i) {
+            const int v = c.at(i);
+            if (v == 0) {
+                ++run;
+            } else {
+                const int k = jpeg_category(v);
+                bits += (run >> 4) * (ac[0xF0] >> 16) + (ac[((run & 15) << 4) | k] >> 16) + k;
+                run = 0;
+            }
+        }
+        if (run) bits += ac[0] >> 16;
+        own = {bits, 0u, pl.ends ? 1u : 0u};
+    }
+    const JpegRun<uint32_t> incl = jpeg_scan_runs<kJpegBlocks>(own, s_pre, s_post, s_seen, tid);
+    if (b < fr.n_blk) {   // the run of the group's blocks before this one
+        blk_off[(size_t)fr.blk0 + b] = tid ? s_pre[tid - 1] : 0u;
+        blk_post[(size_t)fr.blk0 + b] = tid ? s_post[tid - 1] | s_seen[tid - 1] << 31 : 0u;
+    }
+    if (tid == kJpegBlocks - 1) {
+        wg_sum[fr.wg0 + blockIdx.x] = incl.pre;
+        wg_post[fr.wg0 + blockIdx.x] = incl.post | incl.seen << 31;
+    }
+}
+
+// grid (frames): the groups' runs -> wg_base (where each group starts), the frame's totals; the end dwords zeroed as k_jpeg_scan_groups does
+__global__ __launch_bounds__(kJpegScan) void k_jpeg_scan_groups_rst(const uint8_t *__restrict__ table, const uint32_t *__restrict__ wg_sum,
+                                                                    const uint32_t *__restrict__ wg_post, unsigned long long *__restrict__ wg_base,
+                                                                    uint8_t *__restrict__ us_base, JpegState *__restrict__ state)
+{
+    typedef unsigned long long u64;
+    __shared__ u64 s_pre[kJpegScan], s_post[kJpegScan];
+    __shared__ uint32_t s_seen[kJpegScan];
+    const JpegFrame fr = jpeg_frame(table, blockIdx.x);
+    const int tid = threadIdx.x;
+    uint32_t *us = reinterpret_cast<uint32_t *>(us_base + fr.us_off);
+    u64 running = 0;   // where the round's first group starts: the rounds before are a run applied to 0 already
+    for (unsigned base = 0; base < fr.n_wg; base += kJpegScan) {
+        const unsigned i = base + tid;
+        JpegRun<u64> own = {0, 0, 0u};
+        if (i < fr.n_wg) {
+            const JpegRun<uint32_t> g = jpeg_run_unpack(wg_sum[fr.wg0 + i], wg_post[fr.wg0 + i]);
+            own = {g.pre, g.post, g.seen};
+        }
+        const JpegRun<u64> incl = jpeg_scan_runs<kJpegScan>(own, s_pre, s_post, s_seen, tid);
+        if (i < fr.n_wg) {
+            JpegRun<u64> before = {0, 0, 0u};
+            if (tid) before = {s_pre[tid - 1], s_post[tid - 1], s_seen[tid - 1]};
+            const u64 lo = before.at(running), hi = incl.at(running);   // (hi > lo: a block has at least a DC code and an end-of-block)
+            wg_base[fr.wg0 + i] = lo;
+            us[lo >> 5] = 0u;
+            us[(hi - 1) >> 5] = 0u;
+        }
+        const JpegRun<u64> all = {s_pre[kJpegScan - 1], s_post[kJpegScan - 1], s_seen[kJpegScan - 1]};
+        running = all.at(running);
+        __syncthreads();
+    }
+    if (tid == 0) {   // (the last block ends an interval: a multiple of 8)
+        state[blockIdx.x].bits = running;
+        state[blockIdx.x].ubytes = running >> 3;
+    }
+}
+
+// grid (ceil(max n_blk / kJpegBlocks), frames)
+__global__ __launch_bounds__(kJpegBlocks) void k_jpeg_pack_rst(const uint8_t *__restrict__ table, const int16_t *__restrict__ coef,
+                                                               const uint32_t *__restrict__ blk_off, const uint32_t *__restrict__ blk_post,
+                                                               const uint32_t *__restrict__ wg_sum, const uint32_t *__restrict__ wg_post,
+                                                               const unsigned long long *__restrict__ wg_base, uint8_t *__restrict__ us_base,
+                                                               uint32_t *__restrict__ rst_off)
+{
+    __shared__ uint32_t s_code[4 * 256];
+    __shared__ uint32_t s_bits[kJpegPackDwordsRst];
+    const JpegFrame fr = jpeg_frame(table, blockIdx.y);
+    if (blockIdx.x >= fr.n_wg) return;   // (the whole workgroup)
+    const int tid = threadIdx.x;
+    jpeg_stage_codes(s_code, table, tid, kJpegBlocks);
+    const unsigned long long lo = wg_base[fr.wg0 + blockIdx.x], d0 = lo >> 5;
+    // in the image bit 0 is the top bit of dword d0 of the stream: a multiple of 32 away, so rounding up to a byte is the same there
+    const uint32_t first = (uint32_t)(lo - (d0 << 5));
+    const uint32_t end = jpeg_run_unpack(wg_sum[fr.wg0 + blockIdx.x], wg_post[fr.wg0 + blockIdx.x]).at(first);
+    const unsigned long long hi = (d0 << 5) + end;
+    const int nd = (int)((end - 1) >> 5) + 1;
+    for (int j = tid; j < nd + 1; j += kJpegBlocks) s_bits[j] = 0u;
+    __syncthreads();
+    const int b = (int)blockIdx.x * kJpegBlocks + tid;
+    if (b < fr.n_blk) {
+        const size_t blk = (size_t)fr.blk0 + b;
+        const JpegPlace pl = jpeg_place_of(fr, b);
+        const uint32_t *dc = s_code + (pl.luma ? 0 : 2) * 256, *ac = dc + 256;
+        JpegBlock c;
+        c.load(coef, blk);
+        uint32_t pos = jpeg_run_unpack(blk_off[blk], blk_post[blk]).at(first);
+        if (pl.starts) rst_off[fr.rst0 + pl.interval] = (uint32_t)(((d0 << 5) + pos) >> 3);   // (the entries refuse frames whose bound passes 2^31)
+        const int pred = pl.pred_back ? (int)coef[(blk - pl.pred_back) * 64] : 0;
+        const int diff = c.at(0) - pred, cat = jpeg_category(diff);
+        jpeg_put(s_bits, pos, ((dc[cat] & 0xffffu) << cat) | jpeg_extra(diff, cat), (int)(dc[cat] >> 16) + cat);
+        int run = 0;
+#pragma unroll
+        for (int i = 1; i < 64; ++i) {
+            const int v = c.at(i);
+            if (v == 0) {
+                ++run;
+            } else {
+                for (; run >= 16; run -= 16) jpeg_put(s_bits, pos, ac[0xF0] & 0xffffu, (int)(ac[0xF0] >> 16));
+                const int k = jpeg_category(v);
+                const uint32_t cw = ac[(run << 4) | k];
+                jpeg_put(s_bits, pos, ((cw & 0xffffu) << k) | jpeg_extra(v, k), (int)(cw >> 16) + k);
+                run = 0;
+            }
+        }
+        if (run) jpeg_put(s_bits, pos, ac[0] & 0xffffu, (int)(ac[0] >> 16));
+        const int fill = (int)((8 - (pos & 7)) & 7);
+        if (pl.ends && fill) jpeg_put(s_bits, pos, (1u << fill) - 1u, fill);
+    }
+    __syncthreads();
+    uint32_t *us = reinterpret_cast<uint32_t *>(us_base + fr.us_off);
+    for (int j = tid; j < nd; j += kJpegBlocks) {
+        const unsigned long long g = d0 + j;
+        const uint32_t v = __builtin_bswap32(s_bits[j]);
+        if ((g << 5) >= lo && ((g + 1) << 5) <= hi) us[g] = v;
+        else atomicOr(&us[g], v);   // shared with a neighbour, or the frame's last, partial dword: zeroed by k_jpeg_scan_groups_rst
+    }
+}
+
+// grid (ceil(frames / kJpegScan)): DRI and FF Dn between the intervals, which k_jpeg_scan_segs does not know of
+__global__ __launch_bounds__(kJpegScan) void k_jpeg_sizes_rst(const uint8_t *__restrict__ table, JpegState *__restrict__ state,
+                                                              unsigned long long *__restrict__ sizes, int nf)
+{
+    const int f = (int)(blockIdx.x * kJpegScan + threadIdx.x);
+    if (f >= nf) return;
+    const JpegFrame &fr = jpeg_frame(table, f);
+    const unsigned long long size = state[f].size + (unsigned)(y2j::header_bytes(fr.restart) - y2j::kHeaderBytes) + 2ull * (fr.n_int - 1);
+    state[f].size = size;
+    sizes[f] = size;
+}
+
+// the interval that unstuffed byte x lies in, among intervals lo..hi (it lies in one of them): the last whose offset is <= x
+__device__ inline unsigned jpeg_interval_of(const uint32_t *__restrict__ rst, unsigned lo, unsigned hi, unsigned long long x)
+{
+    while (lo < hi) {
+        const unsigned mid = (lo + hi + 1) >> 1;
+        if (rst[mid] <= x) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
+// grid (some, frames), as k_jpeg_count_ff
+__global__ __launch_bounds__(kJpegSegThreads) void k_jpeg_emit_rst(const uint8_t *__restrict__ table, const uint8_t *__restrict__ us_base,
+                                                                   const JpegState *__restrict__ state, const uint32_t *__restrict__ seg_base,
+                                                                   const uint32_t *__restrict__ rst_off, uint8_t *__restrict__ out_base)
+{
+    __shared__ uint32_t s_scan[kJpegSegThreads];
+    __shared__ unsigned s_iv[2];
+    const JpegHeader *hd = reinterpret_cast<const JpegHeader *>(table);
+    const JpegFrame fr = jpeg_frame(table, blockIdx.y);
+    const JpegState st = state[blockIdx.y];
+    uint8_t *out = out_base + st.out_off;
+    const uint32_t *rst = rst_off + fr.rst0;
+    const int tid = threadIdx.x, head = y2j::header_bytes(fr.restart);
+    if (blockIdx.x == 0) {
+        for (int i = tid; i < head; i += kJpegSegThreads)
+            if ((unsigned long long)i < fr.cap) out[i] = y2j::header_byte(hd->t.header, i, fr.w, fr.h, fr.subsample, fr.restart);
+        if (tid < 2 && st.size - 2 + tid < fr.cap) out[st.size - 2 + tid] = tid ? 0xD9 : 0xFF;   // EOI
+    }
+    const unsigned nseg = (unsigned)((st.ubytes + kJpegSegBytes - 1) / kJpegSegBytes);
+    for (unsigned seg = blockIdx.x; seg < nseg; seg += gridDim.x) {
+        const unsigned long long seg_at = (unsigned long long)seg * kJpegSegBytes;
+        // the segment's base: the intervals its first and its last byte lie in
+        if (tid < 2) {
+            const unsigned long long last = seg_at + kJpegSegBytes < st.ubytes ? seg_at + kJpegSegBytes - 1 : st.ubytes - 1;
+            s_iv[tid] = jpeg_interval_of(rst, 0u, fr.n_int - 1, tid ? last : seg_at);
+        }
+        uint32_t w[4];
+        const unsigned long long at = seg_at + tid * 16;
+        const int ff = jpeg_seg_load(us_base + fr.us_off, st.ubytes, at, w);
+        const uint32_t incl = jpeg_scan_incl<kJpegSegThreads>((uint32_t)ff, s_scan, tid);   // (its barriers publish s_iv)
+        if (at < st.ubytes) {
+            const unsigned iv_hi = s_iv[1];
+            unsigned iv = jpeg_interval_of(rst, s_iv[0], iv_hi, at);
+            unsigned long long next = iv < iv_hi ? rst[iv + 1] : ~0ull;   // where the next interval starts
+            unsigned long long o = (unsigned long long)head + at + seg_base[fr.seg0 + seg] + (incl - (uint32_t)ff) + 2ull * iv;
+            const bool at_start = iv && rst[iv] == at;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const uint8_t v = (uint8_t)(w[i >> 2] >> (8 * (i & 3)));
+                if (at + i < st.ubytes) {
+                    bool marker = i == 0 && at_start;
+                    if (at + i == next) {   // (an interval has at least one byte: one step)
+                        ++iv;
+                        o += 2;
+                        next = iv < iv_hi ? rst[iv + 1] : ~0ull;
+                        marker = true;
+                    }
+                    if (marker) {   // FF Dn of the interval before, in front of this interval's first byte; never stuffed
+                        if (o - 2 < fr.cap) out[o - 2] = 0xFF;
+                        if (o - 1 < fr.cap) out[o - 1] = (uint8_t)(0xD0 + ((iv - 1) & 7u));
+                    }
+                    if (o < fr.cap) out[o] = v;
+                    ++o;
+                    if (v == 255) {
+                        if (o < fr.cap) out[o] = 0;
+                        ++o;
+                    }
+                }
+            }
+        }
+        __syncthreads();
+    }
+}
+
 }  // namespace y2
+

@@ -442,7 +442,7 @@ int y2_annotate_jpeg_check(const uint8_t *const *images, const int *widths, cons
     int rc;
     if ((rc = y2_annotate_check(images, widths, heights, pixfmt, n, batch, dets, cap_per_frame, counts, thresh, n_labels, jpeg))) return rc;
     for (int f = 0; f < n; ++f)
-        if ((rc = y2_jpeg_check_frame(widths[f], heights[f], f))) return rc;
+        if ((rc = y2_jpeg_check_frame(widths[f], heights[f], f, Y2JpegMode()))) return rc;   // (the plan checks the mode's bound)
     return YOLO2_SUCCESS;
 }
 
@@ -469,6 +469,7 @@ extern "C" int yolo2_hip_annotate_images_pix_jpeg_host(yolo2_hip_ctx *c, const u
     // the encoder's table
     std::vector<Y2JpegFrameIn> jf((size_t)batch);
     std::vector<Y2JpegPlan> plans((size_t)chunks);
+    const Y2JpegMode jmode = y2_jpeg_mode(c);   // options jpeg_subsample / jpeg_restart, read per call
     std::vector<size_t> items((size_t)chunks, 0);
     size_t cap_in = 0, cap_rgb = 0, cap_work = 0, cap_out = 0;
     for (int k = 0; k < chunks; ++k) {
@@ -480,7 +481,7 @@ extern "C" int yolo2_hip_annotate_images_pix_jpeg_host(yolo2_hip_ctx *c, const u
             jf[(size_t)i] = {widths[f], heights[f], out, caps[f]};
             out += padded((size_t)widths[f] * heights[f] * 3);
         }
-        if ((rc = y2_jpeg_plan(jf.data(), in_chunk(k), &plans[(size_t)k]))) return rc;
+        if ((rc = y2_jpeg_plan(jf.data(), in_chunk(k), jmode, &plans[(size_t)k]))) return rc;
         cap_in = std::max(cap_in, table_bytes(in_chunk(k), items[(size_t)k]) + in + plans[(size_t)k].table_bytes);
         cap_rgb = std::max(cap_rgb, out);
         cap_work = std::max(cap_work, plans[(size_t)k].work_bytes);
@@ -539,7 +540,7 @@ extern "C" int yolo2_hip_annotate_images_pix_jpeg_host(yolo2_hip_ctx *c, const u
         }
         const int max_strips = fill_table(hin, fr.data(), nf, thresh, labels, n_labels, drawn ? drawn + first : nullptr);
         const size_t jtab = off;
-        y2_jpeg_write_table(jf.data(), nf, quality, hin + jtab);
+        y2_jpeg_write_table(jf.data(), nf, quality, jmode, hin + jtab);
         off += plan.table_bytes;
         Y2_TRY(hipMemcpyAsync(A.din[b].get(), hin, off, hipMemcpyHostToDevice, A.s_in), YOLO2_DMA_ERROR);
         Y2_TRY(hipEventRecord(A.e_in[b], A.s_in), YOLO2_ERROR);

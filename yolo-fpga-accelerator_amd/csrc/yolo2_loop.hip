@@ -74,7 +74,7 @@ int y2_loop_check(int precision, const uint8_t *const *images, const int *widths
         int rc;
         if ((rc = y2_letterbox_args(widths[f], heights[f], ch, 416, 416, a, true))) return rc;
         if (out_format == YOLO2_LOOP_OUT_JPEG) {
-            if ((rc = y2_jpeg_check_frame(widths[f], heights[f], f))) return rc;
+            if ((rc = y2_jpeg_check_frame(widths[f], heights[f], f, Y2JpegMode()))) return rc;   // (the plan checks the mode's bound)
         } else {
             if (out_yuv420(out_format) && ((widths[f] | heights[f]) & 1))
                 return fail(YOLO2_ERROR, "loop: frame %d is %dx%d: YUV 4:2:0 output needs an even width and height (odd sizes are refused)", f, widths[f],
@@ -118,6 +118,7 @@ static int loop_run(yolo2_hip_ctx *c, int precision, const uint8_t *const *image
     // per chunk: the staging bytes, the painted frames' bytes and (JPEG) the encoder's plan
     std::vector<Y2JpegFrameIn> jf((size_t)batch);
     std::vector<Y2JpegPlan> plans(jpeg ? (size_t)chunks : 0);
+    const Y2JpegMode jmode = y2_jpeg_mode(c);   // options jpeg_subsample / jpeg_restart, read per call
     size_t cap_in = 0, cap_rgb = 0, cap_work = 0, cap_out = 0;
     for (int k = 0; k < chunks; ++k) {
         size_t in = lead, rgb = 0;
@@ -128,7 +129,7 @@ static int loop_run(yolo2_hip_ctx *c, int precision, const uint8_t *const *image
             rgb += padded(out_frame_bytes(out_format, widths[f], heights[f]));
         }
         if (jpeg) {
-            if ((rc = y2_jpeg_plan(jf.data(), in_chunk(k), &plans[(size_t)k]))) return rc;
+            if ((rc = y2_jpeg_plan(jf.data(), in_chunk(k), jmode, &plans[(size_t)k]))) return rc;
             in += plans[(size_t)k].table_bytes;
             cap_work = std::max(cap_work, plans[(size_t)k].work_bytes);
             cap_out = std::max(cap_out, plans[(size_t)k].out_bytes);
@@ -240,7 +241,7 @@ static int loop_run(yolo2_hip_ctx *c, int precision, const uint8_t *const *image
         const int max_strips = y2_loop_fill_geom(hin + lb_bytes, nf, cw.data(), chh.data(), ch, offs.data(), out_offs.data(), out_format);
         const size_t jtab = off;
         if (jpeg) {
-            y2_jpeg_write_table(jf.data(), nf, quality, hin + jtab);
+            y2_jpeg_write_table(jf.data(), nf, quality, jmode, hin + jtab);
             off += plans[(size_t)k].table_bytes;
         }
         if ((rc = y2_post_fill_geom(P.hgeom[b].get(), cw.data(), chh.data(), batch))) { cleanup(); return rc; }

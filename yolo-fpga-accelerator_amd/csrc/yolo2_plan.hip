@@ -31,6 +31,11 @@ const FlagOpt kI8Flags[] = {
 const IntOpt kJpegInts[] = {
     {"jpegdec_split", &Y2Options::jpegdec_split, 16, 4096},
 };
+// The GPU JPEG encoder's mode: 0, or a value in lo..hi
+const IntOpt kJpegEncInts[] = {
+    {"jpeg_subsample", &Y2Options::jpeg_subsample, 420, 420},
+    {"jpeg_restart", &Y2Options::jpeg_restart, 1, 65535},
+};
 const FlagOpt kFlags[] = {
     {"no_lanes", &Y2Options::no_lanes}, {"verbose", &Y2Options::verbose}, {"no_plan_cache", &Y2Options::no_plan_cache},
     {"no_poolfuse", &Y2Options::no_poolfuse}, {"no_hiacc", &Y2Options::no_hiacc}, {"no_ks", &Y2Options::no_ks},
@@ -76,15 +81,19 @@ int Y2Options::set(const char *name, const char *value)
             this->*o.m = (int)v;
             return 0;
         }
+    auto zero_or = [&](const IntOpt &o, int step) {   // 0, or a multiple of step in lo..hi: 0 = set, -1 = bad value, 1 = another name
+        if (strcmp(name, o.name)) return 1;
+        if (clear) { this->*o.m = dflt.*o.m; return 0; }
+        char *end = nullptr;
+        const long v = strtol(value, &end, 10);
+        if (end == value || *end || (v != 0 && (v < o.lo || v > o.hi || v % step))) return -1;
+        this->*o.m = (int)v;
+        return 0;
+    };
     for (const IntOpt &o : kJpegInts)
-        if (!strcmp(name, o.name)) {
-            if (clear) { this->*o.m = dflt.*o.m; return 0; }
-            char *end = nullptr;
-            const long v = strtol(value, &end, 10);
-            if (end == value || *end || (v != 0 && (v < o.lo || v > o.hi || v % 16))) return -1;
-            this->*o.m = (int)v;
-            return 0;
-        }
+        if (const int r = zero_or(o, 16); r <= 0) return r;
+    for (const IntOpt &o : kJpegEncInts)
+        if (const int r = zero_or(o, 1); r <= 0) return r;
     for (const StrOpt &o : kStrs)
         if (!strcmp(name, o.name)) {
             this->*o.m = clear ? std::string() : std::string(value);
@@ -112,6 +121,7 @@ Y2Options Y2Options::from_env()
     for (const FlagOpt &f : kI8Flags) take(f.name);
     for (const IntOpt &i : kInts) take(i.name);
     for (const IntOpt &i : kJpegInts) take(i.name);
+    for (const IntOpt &i : kJpegEncInts) take(i.name);
     for (const StrOpt &s : kStrs) take(s.name);
     return o;
 }
@@ -128,6 +138,8 @@ std::string Y2Options::describe() const
     for (const IntOpt &i : kInts)
         if (this->*i.m != d.*i.m) add(std::string(i.name) + "=" + std::to_string(this->*i.m));
     for (const IntOpt &i : kJpegInts)
+        if (this->*i.m != d.*i.m) add(std::string(i.name) + "=" + std::to_string(this->*i.m));
+    for (const IntOpt &i : kJpegEncInts)
         if (this->*i.m != d.*i.m) add(std::string(i.name) + "=" + std::to_string(this->*i.m));
     for (const StrOpt &s : kStrs)
         if (this->*s.m != d.*s.m) add(std::string(s.name) + "=" + this->*s.m);

@@ -96,6 +96,10 @@ int draw_font(char *chars, uint64_t *words);   // the packed font: 38 characters
 // 0); -1 for a null frame or a width / height outside 1..65535.  jpg_rgb24_bound: the most bytes a w x h frame can take (0: bad size).
 long write_jpg_rgb24(const uint8_t *rgb, int w, int h, int quality, uint8_t *out, size_t cap);
 size_t jpg_rgb24_bound(int w, int h);
+// The same encoder in the library's own modes (csrc/jpeg_tables.hpp): subsample 0 | 420, restart 0..65535 MCUs per interval; (0, 0) is
+// write_jpg_rgb24.  A mode outside those is refused as a bad size is (-1 / 0).
+long write_jpg_rgb24_ex(const uint8_t *rgb, int w, int h, int quality, int subsample, int restart, uint8_t *out, size_t cap);
+size_t jpg_rgb24_bound_ex(int w, int h, int subsample, int restart);
 // The annotated frame as a PNG file, the library's own definition (csrc/png_huff.hpp; y2_png.cpp): 8-bit RGB, rows filtered by the rule
 // of stb_image_write v1.09 (the reference's writer, linux_app/src/main.c:1086), one IDAT of dynamic-Huffman deflate blocks without LZ
 // matches; not stb's bytes.  Returns the file's length and stores the bytes below `cap`; -1 for a null frame or a bad size.

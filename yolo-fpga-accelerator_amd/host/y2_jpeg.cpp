@@ -94,34 +94,56 @@ int put_block(Sink &s, float *blk, const float *fdtbl, int pred, const uint32_t 
 }  // namespace
 
 size_t jpg_rgb24_bound(int w, int h) { return w >= 1 && h >= 1 && w <= 65535 && h <= 65535 ? y2j::stream_bound(w, h) : 0; }
-
-long write_jpg_rgb24(const uint8_t *rgb, int w, int h, int quality, uint8_t *out, size_t cap)
+size_t jpg_rgb24_bound_ex(int w, int h, int subsample, int restart)
 {
-    if (!rgb || w < 1 || h < 1 || w > 65535 || h > 65535 || (cap && !out)) return -1;
+    return w >= 1 && h >= 1 && w <= 65535 && h <= 65535 && y2j::mode_ok(subsample, restart) ? y2j::stream_bound_ex(w, h, subsample, restart) : 0;
+}
+
+long write_jpg_rgb24(const uint8_t *rgb, int w, int h, int quality, uint8_t *out, size_t cap) { return write_jpg_rgb24_ex(rgb, w, h, quality, 0, 0, out, cap); }
+
+// The modes of csrc/jpeg_tables.hpp as one serial loop over MCUs; mode (0, 0) is the reference's stream.
+long write_jpg_rgb24_ex(const uint8_t *rgb, int w, int h, int quality, int subsample, int restart, uint8_t *out, size_t cap)
+{
+    if (!rgb || w < 1 || h < 1 || w > 65535 || h > 65535 || (cap && !out) || !y2j::mode_ok(subsample, restart)) return -1;
     y2j::Tables t;
     y2j::make_tables(quality, &t);
     Sink s{out, cap};
-    uint8_t head[y2j::kHeaderBytes];
-    y2j::header_for(t, w, h, head);
-    for (uint8_t b : head) s.byte(b);
+    for (int i = 0; i < y2j::header_bytes(restart); ++i) s.byte(y2j::header_byte(t.header, i, w, h, subsample, restart));
+    const int m = y2j::mcu_pixels(subsample), mcux = (w + m - 1) / m, mcus = mcux * ((h + m - 1) / m);
     int pred[3] = {0, 0, 0};
-    float Y[64], U[64], V[64];
-    for (int y0 = 0; y0 < h; y0 += 8)
-        for (int x0 = 0; x0 < w; x0 += 8) {
-            for (int r = 0; r < 8; ++r) {
-                const uint8_t *row = rgb + (size_t)(y0 + r < h ? y0 + r : h - 1) * w * 3;   // edge pixels are repeated
-                for (int c = 0; c < 8; ++c) {
-                    const uint8_t *px = row + (size_t)(x0 + c < w ? x0 + c : w - 1) * 3;
-                    const float R = px[0], G = px[1], B = px[2];
-                    Y[r * 8 + c] = 0.299f * R + 0.587f * G + 0.114f * B - 128;
-                    U[r * 8 + c] = -0.16874f * R - 0.33126f * G + 0.5f * B;
-                    V[r * 8 + c] = 0.5f * R - 0.41869f * G - 0.08131f * B;
-                }
-            }
-            pred[0] = put_block(s, Y, t.fdtbl[0], pred[0], t.code[y2j::kDcLuma], t.code[y2j::kAcLuma]);
-            pred[1] = put_block(s, U, t.fdtbl[1], pred[1], t.code[y2j::kDcChroma], t.code[y2j::kAcChroma]);
-            pred[2] = put_block(s, V, t.fdtbl[1], pred[2], t.code[y2j::kDcChroma], t.code[y2j::kAcChroma]);
+    float Y[16 * 16], U[16 * 16], V[16 * 16], blk[64];   // the MCU's pixels, row-major m x m
+    for (int mcu = 0; mcu < mcus; ++mcu) {
+        if (restart && mcu && mcu % restart == 0) {
+            if (s.have) s.bits(0x7fu, 8 - s.have);
+            s.byte(0xFF);   // (a marker: not stuffed)
+            s.byte((uint8_t)(0xD0 + ((mcu / restart - 1) & 7)));
+            pred[0] = pred[1] = pred[2] = 0;
         }
+        const int y0 = mcu / mcux * m, x0 = mcu % mcux * m;
+        for (int r = 0; r < m; ++r) {
+            const uint8_t *row = rgb + (size_t)(y0 + r < h ? y0 + r : h - 1) * w * 3;   // edge pixels are repeated
+            for (int c = 0; c < m; ++c) {
+                const uint8_t *px = row + (size_t)(x0 + c < w ? x0 + c : w - 1) * 3;
+                const float R = px[0], G = px[1], B = px[2];
+                Y[r * m + c] = 0.299f * R + 0.587f * G + 0.114f * B - 128;
+                U[r * m + c] = -0.16874f * R - 0.33126f * G + 0.5f * B;
+                V[r * m + c] = 0.5f * R - 0.41869f * G - 0.08131f * B;
+            }
+        }
+        for (int k = 0; k < m / 8 * (m / 8); ++k) {   // the Y blocks, row by row
+            for (int i = 0; i < 64; ++i) blk[i] = Y[((k / (m / 8)) * 8 + i / 8) * m + (k % (m / 8)) * 8 + i % 8];
+            pred[0] = put_block(s, blk, t.fdtbl[0], pred[0], t.code[y2j::kDcLuma], t.code[y2j::kAcLuma]);
+        }
+        int p = 1;
+        for (const float *C : {U, V}) {
+            for (int i = 0; i < 64; ++i) {
+                const float *q = C + (m / 8) * ((i / 8) * m + i % 8);   // the sample's pixel, or the upper left of its 2 x 2
+                blk[i] = m == 8 ? q[0] : ((q[0] + q[1]) + (q[m] + q[m + 1])) * 0.25f;
+            }
+            pred[p] = put_block(s, blk, t.fdtbl[1], pred[p], t.code[y2j::kDcChroma], t.code[y2j::kAcChroma]);
+            ++p;
+        }
+    }
     if (s.have) s.bits(0x7fu, 8 - s.have);   // the last byte's free bits are ones
     s.byte(0xFF);
     s.byte(0xD9);   // EOI

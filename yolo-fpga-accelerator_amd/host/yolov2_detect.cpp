@@ -68,6 +68,7 @@ struct AppConfig {
     std::string annotated_format;   // --annotated-format jpg: they are encoded on the GPU too (yolo2_hip_annotate_images_pix_jpeg_host); "" / ppm: PPM;
                                     // nv12 / yuv420p (--loop-gpu): raw planar YUV 4:2:0 frames, converted by the painter (YOLO2_LOOP_OUT_NV12 / _I420)
     int jpeg_quality = 80;          // --jpeg-quality, the reference streamer's default
+    int jpeg_subsample = 0, jpeg_restart = 0;   // --jpeg-subsample 420 / --jpeg-restart R: options jpeg_subsample / jpeg_restart
     bool loop_gpu = false;          // --loop-gpu: records and annotated frames from ONE accelerator call per chunk (yolo2_hip_loop_images_pix)
     int video_w = 640, video_h = 480;
     int video_pixfmt = YOLO2_PIX_RGB24; // --video-pix-fmt: what a --video-raw frame holds (RGB24, or packed YUYV 4:2:2 / planar NV12 / I420 / packed BGR24 / RGBA32 / BGRA32 read by the GPU as they are)
@@ -138,6 +139,8 @@ void print_usage(const char *prog)
         "                        YUV 4:2:0 (w * h * 3 / 2 bytes, even sizes; the names of --video-pix-fmt), converted where the GPU paints it;\n"
         "                        `cat` of the files is a rawvideo stream for a video encoder (ffmpeg -f rawvideo -pix_fmt nv12 | yuv420p)\n"
         "  --jpeg-quality <1..100>  quality of --annotated-format jpg (default 80)\n"
+        "  --jpeg-subsample 420   --annotated-format jpg as 4:2:0 (MCUs of 16x16 pixels; default: no subsampling, the reference's stream)\n"
+        "  --jpeg-restart <R>     ... with a restart marker after every R MCUs, 1..65535 (default: none)\n"
         "  --loop-gpu            with --annotate-gpu --save-annotated-dir and --post gpu: one accelerator call per chunk makes the records AND\n"
         "                        the annotated frames from one upload (yolo2_hip_loop_images_pix; with --decode gpu\n"
         "                        yolo2_hip_loop_images_jpeg, from the compressed streams); same log, JSONL and files\n"
@@ -218,6 +221,14 @@ AppConfig parse_args(int argc, char **argv)
         else if (arg == "--loop-gpu") cfg.loop_gpu = true;
         else if (arg == "--annotated-format" && need("")) cfg.annotated_format = argv[++i];
         else if (arg == "--jpeg-quality" && need("")) cfg.jpeg_quality = std::atoi(argv[++i]);
+        else if ((arg == "--jpeg-subsample" || arg == "--jpeg-restart") && need("")) {
+            int &v = arg == "--jpeg-subsample" ? cfg.jpeg_subsample : cfg.jpeg_restart;
+            v = std::atoi(argv[++i]);
+            if (yolo2_hip_jpeg_bound_ex(8, 8, cfg.jpeg_subsample, cfg.jpeg_restart) == 0) {   // (the library's own range check)
+                std::fprintf(stderr, "Unsupported %s %s (--jpeg-subsample 0 | 420, --jpeg-restart 0..65535)\n", arg.c_str(), argv[i]);
+                std::exit(1);
+            }
+        }
         else if (arg == "--chunk-batches" && need("")) cfg.chunk_batches = std::max(1, std::atoi(argv[++i]));
         else if (arg == "--decode-threads" && need("")) cfg.decode_threads = std::atoi(argv[++i]);
         else if (arg == "--decode-split" && need("")) {
@@ -880,6 +891,9 @@ void run_stream(AppConfig cfg)
             yolo2_hip_ctx *ctx = yolo2_hip_multi_ctx(m, slot);
             if (cfg.decode_split && yolo2_hip_set_option(ctx, "jpegdec_split", std::to_string(cfg.decode_split).c_str()) != YOLO2_SUCCESS)
                 throw std::runtime_error(yolo2_hip_last_error());
+            if ((cfg.jpeg_subsample && yolo2_hip_set_option(ctx, "jpeg_subsample", std::to_string(cfg.jpeg_subsample).c_str()) != YOLO2_SUCCESS) ||
+                (cfg.jpeg_restart && yolo2_hip_set_option(ctx, "jpeg_restart", std::to_string(cfg.jpeg_restart).c_str()) != YOLO2_SUCCESS))
+                throw std::runtime_error(yolo2_hip_last_error());
             // while the reader decodes its first chunk: plan the batch (activation tensors, lanes) on this device (int16; the fp16
             // passes build their launch table at the first chunk)
             if (!f16 && !i8) {
@@ -946,7 +960,7 @@ void run_stream(AppConfig cfg)
                                 for (int attempt = 0; attempt < 2; ++attempt) {     // (JPEG: room as below, a second call with the encoder's bound)
                                     for (int k = 0; k < m2; ++k) {
                                         std::vector<uint8_t> &a = ck->annotated[(size_t)idx[(size_t)k]];
-                                        const size_t raw = (size_t)w2[(size_t)k] * h2[(size_t)k] * 3 / (annotate_yuv ? 2 : 1), bound = yolo2_hip_jpeg_bound(w2[(size_t)k], h2[(size_t)k]);
+                                        const size_t raw = (size_t)w2[(size_t)k] * h2[(size_t)k] * 3 / (annotate_yuv ? 2 : 1), bound = yolo2_hip_jpeg_bound_ex(w2[(size_t)k], h2[(size_t)k], cfg.jpeg_subsample, cfg.jpeg_restart);
                                         caps[(size_t)k] = !annotate_jpg ? raw : attempt ? bound : std::min(bound, raw + 4096);
                                         a.resize(caps[(size_t)k]);
                                         outs[(size_t)k] = a.data();
@@ -1042,7 +1056,7 @@ void run_stream(AppConfig cfg)
                             // second call with the encoder's bound
                             for (int attempt = 0; attempt < 2; ++attempt) {
                                 for (int f = 0; f < n; ++f) {
-                                    const size_t bound = yolo2_hip_jpeg_bound(ws[(size_t)f], hs[(size_t)f]);
+                                    const size_t bound = yolo2_hip_jpeg_bound_ex(ws[(size_t)f], hs[(size_t)f], cfg.jpeg_subsample, cfg.jpeg_restart);
                                     caps[(size_t)f] = attempt ? bound : std::min(bound, (size_t)ws[(size_t)f] * hs[(size_t)f] * 3 + 4096);
                                     ck->annotated[(size_t)f].resize(caps[(size_t)f]);
                                     outs[(size_t)f] = ck->annotated[(size_t)f].data();

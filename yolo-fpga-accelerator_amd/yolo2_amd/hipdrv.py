@@ -4,7 +4,9 @@ This is host plumbing only: every compute call goes through the C ABI into the h
 HIP kernels.  There is no CPU fallback: if the library is missing or no GPU is present the
 calls raise.
 """
+import contextlib
 import ctypes as C
+import itertools
 import os
 import subprocess
 
@@ -57,7 +59,7 @@ EXPORTS = [
     "yolo2_hip_absmax_f32", "yolo2_hip_calib_reset", "yolo2_hip_calib_frames", "yolo2_hip_calib_images_pix_host", "yolo2_hip_calib_stats",
     "yolo2_hip_calib_q_tables", "yolo2_hip_calib_q_from_stats", "yolo2_hip_quantize_weights_int16",
     "yolo2_hip_annotate_pix", "yolo2_hip_annotate_images_pix_host", "yolo2_hip_multi_annotate_images_pix_host",
-    "yolo2_hip_jpeg_bound", "yolo2_hip_jpeg_encode_rgb24", "yolo2_hip_annotate_images_pix_jpeg_host",
+    "yolo2_hip_jpeg_bound", "yolo2_hip_jpeg_bound_ex", "yolo2_hip_jpeg_encode_rgb24", "yolo2_hip_annotate_images_pix_jpeg_host",
     "yolo2_hip_multi_annotate_images_pix_jpeg_host",
     "yolo2_hip_loop_images_pix", "yolo2_hip_multi_loop_images_pix", "yolo2_hip_loop_last_info", "yolo2_hip_draw_items_dev",
     "yolo2_hip_draw_item_size",
@@ -325,6 +327,7 @@ def lib():
         sig("yolo2_hip_" + name, [vp, vp, vp, vp, i32, i32, i32, vp, i32, vp, C.c_float, vp, i32, vp, vp])
     # annotated frames as JPEG (include/yolo2_hip.h "annotated frames as JPEG")
     sig("yolo2_hip_jpeg_bound", [i32, i32], C.c_size_t)
+    sig("yolo2_hip_jpeg_bound_ex", [i32, i32, i32, i32], C.c_size_t)
     sig("yolo2_hip_jpeg_encode_rgb24", [u64, i32, i32, i32, u64, C.c_size_t, C.POINTER(C.c_size_t), vp])
     sig("yolo2_hip_zlib_huff_bound", [C.c_size_t], C.c_size_t)
     sig("yolo2_hip_zlib_huff", [u64, C.c_size_t, u64, C.c_size_t, C.POINTER(C.c_size_t)])
@@ -585,10 +588,11 @@ class Yolo2Hip:
         return region, q.value
 
     def loop_images(self, images, pixfmt=None, precision: str = "int16", tail: str = "core", thresh: float = 0.24, nms: float = 0.45,
-                    labels=None, jpeg_quality=None, batch: int = 64, cap: int = 845, out_order: str = "rgb"):
+                    labels=None, jpeg_quality=None, batch: int = 64, cap: int = 845, out_order: str = "rgb", jpeg_subsample=None, jpeg_restart=None):
         """the camera loop as one call: records and annotated frames from one upload (module-level loop_images)"""
         return loop_images(self._h, images, pixfmt=pixfmt, precision=precision, tail=tail, thresh=thresh, nms=nms, labels=labels,
-                           jpeg_quality=jpeg_quality, batch=batch, cap=cap, out_order=out_order)
+                           jpeg_quality=jpeg_quality, batch=batch, cap=cap, out_order=out_order, jpeg_subsample=jpeg_subsample,
+                           jpeg_restart=jpeg_restart)
 
     def jpeg_decode(self, streams, batch: int = 64, strict: bool = True):
         """see jpeg_decode"""
@@ -600,18 +604,21 @@ class Yolo2Hip:
         return run_jpegs_dets(self._h, streams, batch, thresh, nms, cap=cap, best_class=best_class, precision=precision, tail=tail, strict=strict)
 
     def loop_jpegs(self, streams, precision: str = "int16", tail: str = "core", thresh: float = 0.24, nms: float = 0.45, labels=None,
-                   jpeg_quality=None, batch: int = 64, cap: int = 845, strict: bool = True, out_order: str = "rgb"):
+                   jpeg_quality=None, batch: int = 64, cap: int = 845, strict: bool = True, out_order: str = "rgb", jpeg_subsample=None,
+                   jpeg_restart=None):
         """the camera loop as one call from JPEG streams (module-level loop_jpegs)"""
         return loop_jpegs(self._h, streams, precision=precision, tail=tail, thresh=thresh, nms=nms, labels=labels, jpeg_quality=jpeg_quality,
-                          batch=batch, cap=cap, strict=strict, out_order=out_order)
+                          batch=batch, cap=cap, strict=strict, out_order=out_order, jpeg_subsample=jpeg_subsample, jpeg_restart=jpeg_restart)
 
     def loop_last_info(self) -> dict:
         return loop_last_info(self._h)
 
-    def annotate_images(self, images, dets, counts, batch: int, thresh: float, labels=None, pixfmt=None, jpeg_quality=None):
+    def annotate_images(self, images, dets, counts, batch: int, thresh: float, labels=None, pixfmt=None, jpeg_quality=None, jpeg_subsample=None,
+                        jpeg_restart=None):
         """the images with their detection records painted in, as the reference's camera loop does (module-level annotate_images);
         with jpeg_quality, as the JPEG streams its MJPEG streamer sends (a list of bytes)"""
-        return annotate_images(self._h, images, dets, counts, batch, thresh, labels=labels, pixfmt=pixfmt, jpeg_quality=jpeg_quality)
+        return annotate_images(self._h, images, dets, counts, batch, thresh, labels=labels, pixfmt=pixfmt, jpeg_quality=jpeg_quality,
+                               jpeg_subsample=jpeg_subsample, jpeg_restart=jpeg_restart)
 
     # ---- fp16 MFMA path
     def load_weights_fp32(self, weights_f32, bias_f32):
@@ -1340,13 +1347,16 @@ def annotate_pix(image: np.ndarray, dets, pixfmt=None, thresh: float = 0.24, lab
     return out, drawn.value
 
 
-def annotate_images(handle, images, dets, counts, batch: int, thresh: float, labels=None, pixfmt=None, multi: bool = False, jpeg_quality=None):
+def annotate_images(handle, images, dets, counts, batch: int, thresh: float, labels=None, pixfmt=None, multi: bool = False, jpeg_quality=None,
+                    jpeg_subsample=None, jpeg_restart=None):
     """yolo2_hip_annotate_images_pix_host / yolo2_hip_multi_annotate_images_pix_host: host images and the records a run_images_dets call
     returned for them -> (list of uint8 [h][w][3] annotated frames, records drawn per frame).  dets: DET_DTYPE [n][cap] with counts [n]
     (frame f uses min(counts[f], cap) records), or - counts None - a list of per-frame record arrays (run_images_dets()["dets"]).
-    jpeg_quality (1..100): the _jpeg_host entries instead - the frames come back as the reference's JPEG streams, a list of bytes."""
+    jpeg_quality (1..100): the _jpeg_host entries instead - the frames come back as the reference's JPEG streams, a list of bytes;
+    jpeg_subsample = 420 / jpeg_restart = R with it: the library's 4:2:0 / restart-interval forms of the stream."""
     if jpeg_quality is not None:
-        return annotate_images_jpeg(handle, images, dets, counts, batch, thresh, int(jpeg_quality), labels=labels, pixfmt=pixfmt, multi=multi)
+        return annotate_images_jpeg(handle, images, dets, counts, batch, thresh, int(jpeg_quality), labels=labels, pixfmt=pixfmt, multi=multi,
+                                    subsample=jpeg_subsample, restart=jpeg_restart)
     imgs0 = [np.ascontiguousarray(im, dtype=np.uint8) for im in images]
     fmt = pixfmt if pixfmt is not None else ("grey8" if imgs0[0].ndim == 2 else "rgb24")
     n, ptrs, ws, hs, code, imgs = _image_args(imgs0, fmt)
@@ -1384,6 +1394,10 @@ def host_lib():
         H.y2h_write_jpg_rgb24.restype = C.c_long
         H.y2h_jpg_rgb24_bound.argtypes = [C.c_int, C.c_int]
         H.y2h_jpg_rgb24_bound.restype = C.c_size_t
+        H.y2h_write_jpg_rgb24_ex.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
+        H.y2h_write_jpg_rgb24_ex.restype = C.c_long
+        H.y2h_jpg_rgb24_bound_ex.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
+        H.y2h_jpg_rgb24_bound_ex.restype = C.c_size_t
         H.y2h_packed_to_rgb24.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
         H.y2h_packed_to_rgb24.restype = C.c_int
         H.y2h_rgb24_to_yuv420.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
@@ -1436,38 +1450,60 @@ def _rgb24(rgb):
     return im
 
 
-def write_jpg_host(rgb, quality: int = 80) -> bytes:
-    """y2h_write_jpg_rgb24: an RGB24 frame as the JPEG stream of the reference's MJPEG streamer, encoded on the host"""
+def write_jpg_host(rgb, quality: int = 80, subsample: int = 0, restart: int = 0) -> bytes:
+    """y2h_write_jpg_rgb24_ex: an RGB24 frame as the JPEG stream of the reference's MJPEG streamer, encoded on the host; subsample =
+    420 / restart = R MCUs per interval: the library's own forms of it (mode (0, 0) is y2h_write_jpg_rgb24)"""
     im = _rgb24(rgb)
     H = host_lib()
-    cap = H.y2h_jpg_rgb24_bound(im.shape[1], im.shape[0])
+    cap = H.y2h_jpg_rgb24_bound_ex(im.shape[1], im.shape[0], subsample, restart)
     out = np.empty(max(cap, 1), dtype=np.uint8)
-    n = H.y2h_write_jpg_rgb24(im.ctypes.data, im.shape[1], im.shape[0], quality, out.ctypes.data, cap)
+    n = H.y2h_write_jpg_rgb24_ex(im.ctypes.data, im.shape[1], im.shape[0], quality, subsample, restart, out.ctypes.data, cap)
     if n < 0 or n > cap:
-        raise ValueError(f"y2h_write_jpg_rgb24 refused a {im.shape[1]}x{im.shape[0]} frame")
+        raise ValueError(f"y2h_write_jpg_rgb24_ex refused a {im.shape[1]}x{im.shape[0]} frame in mode ({subsample}, {restart})")
     return out[:n].tobytes()
 
 
-def jpeg_bound(w: int, h: int) -> int:
-    """yolo2_hip_jpeg_bound: the most bytes the stream of a w x h frame can take"""
-    return int(lib().yolo2_hip_jpeg_bound(w, h))
+def jpeg_bound(w: int, h: int, subsample: int = 0, restart: int = 0) -> int:
+    """yolo2_hip_jpeg_bound_ex: the most bytes the stream of a w x h frame can take in a mode ((0, 0): yolo2_hip_jpeg_bound)"""
+    return int(lib().yolo2_hip_jpeg_bound_ex(w, h, subsample, restart))
 
 
-def jpeg_encode(rgb, quality: int = 80, stream: int = 0) -> bytes:
-    """yolo2_hip_jpeg_encode_rgb24: the same stream as write_jpg_host, encoded on the GPU"""
+@contextlib.contextmanager
+def jpeg_mode(handle, subsample=None, restart=None, multi: bool = False):
+    """Options jpeg_subsample / jpeg_restart on a context (None: the process-wide set; multi: every member of a multi handle) for the
+    calls inside the block; they are unset again behind it.  An argument left None leaves its option as it stands."""
+    L = lib()
+    ctxs = [handle]
+    if multi:
+        ctxs = list(itertools.takewhile(bool, (L.yolo2_hip_multi_ctx(handle, i) for i in itertools.count())))
+    given = [(n, v) for n, v in ((b"jpeg_subsample", subsample), (b"jpeg_restart", restart)) if v is not None]
+    try:
+        for c in ctxs:
+            for name, v in given:
+                check(L.yolo2_hip_set_option(c, name, str(int(v)).encode()), f"yolo2_hip_set_option({name.decode()})")
+        yield
+    finally:
+        for c in ctxs:
+            for name, _ in given:
+                L.yolo2_hip_set_option(c, name, None)
+
+
+def jpeg_encode(rgb, quality: int = 80, stream: int = 0, subsample: int = 0, restart: int = 0) -> bytes:
+    """yolo2_hip_jpeg_encode_rgb24: the same stream as write_jpg_host, encoded on the GPU (the mode through the process-wide options)"""
     im = _rgb24(rgb)
     L = lib()
     h, w = im.shape[:2]
-    cap = jpeg_bound(w, h)
+    cap = jpeg_bound(w, h, subsample, restart)
     if not cap:
-        raise ValueError(f"width and height are 1..65535, not {w}x{h}")
+        raise ValueError(f"width and height are 1..65535, not {w}x{h}; subsample is 0 | 420 and restart 0..65535, not ({subsample}, {restart})")
     src, dst = C.c_uint64(0), C.c_uint64(0)
     size = C.c_size_t(0)
     try:
         check(L.yolo2_hip_alloc(max(im.nbytes, 16), C.byref(src)), "alloc")
         check(L.yolo2_hip_alloc(cap, C.byref(dst)), "alloc")
         check(L.yolo2_hip_memcpy_h2d(src, im.ctypes.data_as(C.c_void_p), im.nbytes), "h2d")
-        check(L.yolo2_hip_jpeg_encode_rgb24(src, w, h, quality, dst, cap, C.byref(size), C.c_void_p(stream)), "yolo2_hip_jpeg_encode_rgb24")
+        with jpeg_mode(None, subsample or None, restart or None):
+            check(L.yolo2_hip_jpeg_encode_rgb24(src, w, h, quality, dst, cap, C.byref(size), C.c_void_p(stream)), "yolo2_hip_jpeg_encode_rgb24")
         out = np.empty(size.value, dtype=np.uint8)
         check(L.yolo2_hip_memcpy_d2h(out.ctypes.data_as(C.c_void_p), dst, out.nbytes), "d2h")
     finally:
@@ -1569,18 +1605,28 @@ def annotate_images_jpeg_raw(handle, images, dets, counts, batch: int, thresh: f
     return rc, outs, sizes, drawn
 
 
-def annotate_images_jpeg(handle, images, dets, counts, batch: int, thresh: float, quality: int = 80, labels=None, pixfmt=None, multi: bool = False):
+def _jpeg_room(hw, subsample, restart) -> int:
+    """the bound of a frame of hw = (h, w) in the mode; an argument left None (the context's own option decides) counts as its worst"""
+    subs = (0, 420) if subsample is None else (subsample,)
+    return max(jpeg_bound(hw[1], hw[0], s, 1 if restart is None else restart) for s in subs) if hw[0] and hw[1] else 0
+
+
+def annotate_images_jpeg(handle, images, dets, counts, batch: int, thresh: float, quality: int = 80, labels=None, pixfmt=None, multi: bool = False,
+                         subsample=None, restart=None):
     """yolo2_hip_annotate_images_pix_jpeg_host / its multi form: annotate_images, with the frames back as JPEG streams ->
     (list of bytes, records drawn per frame).  Room per frame: the raw frame's size, and - for the rare frame that compresses to
-    more than that - a second call with the encoder's bound."""
+    more than that - a second call with the encoder's bound.  subsample / restart: options jpeg_subsample / jpeg_restart for this
+    call (jpeg_mode)."""
     shapes = [_pix_hw(pixfmt, np.asarray(im).shape) for im in images]
-    caps = [min(jpeg_bound(s[1], s[0]), s[0] * s[1] * 3 + 4096) for s in shapes]
-    for attempt in range(2):
-        rc, outs, sizes, drawn = annotate_images_jpeg_raw(handle, images, dets, counts, batch, thresh, quality, caps, labels=labels, pixfmt=pixfmt,
-                                                          multi=multi)
-        if rc == YOLO2_SUCCESS or attempt or not any(int(sizes[f]) > caps[f] for f in range(len(caps))):
-            break
-        caps = [jpeg_bound(s[1], s[0]) for s in shapes]
+    room = [_jpeg_room(s, subsample, restart) for s in shapes]
+    caps = [min(room[f], s[0] * s[1] * 3 + 4096) for f, s in enumerate(shapes)]
+    with jpeg_mode(handle, subsample, restart, multi):
+        for attempt in range(2):
+            rc, outs, sizes, drawn = annotate_images_jpeg_raw(handle, images, dets, counts, batch, thresh, quality, caps, labels=labels, pixfmt=pixfmt,
+                                                              multi=multi)
+            if rc == YOLO2_SUCCESS or attempt or not any(int(sizes[f]) > caps[f] for f in range(len(caps))):
+                break
+            caps = room
     check(rc, "yolo2_hip_annotate_images_pix_jpeg_host")
     return [outs[f][:int(sizes[f])].tobytes() for f in range(len(outs))], drawn
 
@@ -1630,13 +1676,15 @@ def loop_images_raw(handle, images, pixfmt, precision, flags, thresh, nms, batch
 
 
 def loop_images(handle, images, pixfmt=None, precision: str = "int16", tail: str = "core", thresh: float = 0.24, nms: float = 0.45,
-                labels=None, jpeg_quality=None, batch: int = 64, cap: int = 845, multi: bool = False, out_order: str = "rgb"):
+                labels=None, jpeg_quality=None, batch: int = 64, cap: int = 845, multi: bool = False, out_order: str = "rgb",
+                jpeg_subsample=None, jpeg_restart=None):
     """yolo2_hip_loop_images_pix / its multi form: the camera loop as one call - host images -> {"dets": per-frame record arrays (one
     per detection, best class), "counts", "final_q" (int16 only, else None), "frames": the annotated frames as uint8 [h][w][3] (or,
     with jpeg_quality 1..100, as JPEG byte strings), "drawn": records drawn per frame}.  The frames go up once; records, draw items
     and the painted frames are made on the device.  out_order "bgr": the raw frames come back as B G R (YOLO2_LOOP_OUT_BGR24, what
     cv2.imshow / cv2.VideoWriter take); "nv12" / "i420": as planar YUV 4:2:0, uint8 [h * 3 / 2][w], what video encoders take
-    (YOLO2_LOOP_OUT_NV12 / _I420; even sizes only; rgb24_to_yuv420 of the "rgb" frame).  Each an error together with jpeg_quality."""
+    (YOLO2_LOOP_OUT_NV12 / _I420; even sizes only; rgb24_to_yuv420 of the "rgb" frame).  Each an error together with jpeg_quality.
+    jpeg_subsample / jpeg_restart: the options of those names for this call (jpeg_mode)."""
     if precision not in LOOP_PRECISIONS:
         raise ValueError(f"precision must be one of {tuple(LOOP_PRECISIONS)}, not {precision!r}")
     out_format = _loop_out_format(out_order, jpeg_quality)
@@ -1644,16 +1692,18 @@ def loop_images(handle, images, pixfmt=None, precision: str = "int16", tail: str
     shapes = [_pix_hw(pixfmt, np.asarray(im).shape) for im in images]
     jpeg = jpeg_quality is not None
     if jpeg:
-        caps = [min(jpeg_bound(s[1], s[0]), s[0] * s[1] * 3 + 4096) for s in shapes]
+        room = [_jpeg_room(s, jpeg_subsample, jpeg_restart) for s in shapes]
+        caps = [min(room[f], s[0] * s[1] * 3 + 4096) for f, s in enumerate(shapes)]
     else:
         caps = [_loop_raw_bytes(out_order, s) for s in shapes]
     name = f"yolo2_hip_{'multi_' if multi else ''}loop_images_pix"
-    for attempt in range(2):
-        rc, dets, counts, q, outs, sizes, drawn = loop_images_raw(handle, images, pixfmt, LOOP_PRECISIONS[precision], flags, thresh, nms, batch, cap,
-                                                                  labels, out_format, int(jpeg_quality) if jpeg else 0, caps, multi=multi)
-        if rc == YOLO2_SUCCESS or attempt or not jpeg or not any(int(sizes[f]) > caps[f] for f in range(len(caps))):
-            break
-        caps = [jpeg_bound(s[1], s[0]) for s in shapes]   # (the rare frame that compresses to more than its raw size)
+    with jpeg_mode(handle, jpeg_subsample, jpeg_restart, multi):
+        for attempt in range(2):
+            rc, dets, counts, q, outs, sizes, drawn = loop_images_raw(handle, images, pixfmt, LOOP_PRECISIONS[precision], flags, thresh, nms, batch, cap,
+                                                                      labels, out_format, int(jpeg_quality) if jpeg else 0, caps, multi=multi)
+            if rc == YOLO2_SUCCESS or attempt or not jpeg or not any(int(sizes[f]) > caps[f] for f in range(len(caps))):
+                break
+            caps = room   # (the rare frame that compresses to more than its raw size)
     check(rc, name)
     if jpeg:
         frames = [outs[f][:int(sizes[f])].tobytes() for f in range(len(outs))]
@@ -1712,7 +1762,8 @@ def loop_jpegs_raw(handle, streams, precision, flags, thresh, nms, batch, cap, l
 
 
 def loop_jpegs(handle, streams, precision: str = "int16", tail: str = "core", thresh: float = 0.24, nms: float = 0.45, labels=None,
-               jpeg_quality=None, batch: int = 64, cap: int = 845, multi: bool = False, strict: bool = True, out_order: str = "rgb"):
+               jpeg_quality=None, batch: int = 64, cap: int = 845, multi: bool = False, strict: bool = True, out_order: str = "rgb",
+               jpeg_subsample=None, jpeg_restart=None):
     """yolo2_hip_loop_images_jpeg / its multi form: the camera loop as one call from JPEG streams (bytes) - or, mixed in, raw frames
     (uint8 [h][w][3] arrays, e.g. decoded on the host) - with the decoder, the network, the painter and the encoder on the device.
     Returns loop_images' dictionary plus "status" (int32 [n]; not 0: the decoder flagged the frame, its counts and drawn are 0 and
@@ -1730,17 +1781,19 @@ def loop_jpegs(handle, streams, precision: str = "int16", tail: str = "core", th
             shapes.append((max(info["height"], 0), max(info["width"], 0)))
     jpeg = jpeg_quality is not None
     if jpeg:
-        caps = [min(jpeg_bound(s[1], s[0]), s[0] * s[1] * 3 + 4096) if s[0] and s[1] else 0 for s in shapes]
+        room = [_jpeg_room(s, jpeg_subsample, jpeg_restart) for s in shapes]
+        caps = [min(room[f], s[0] * s[1] * 3 + 4096) for f, s in enumerate(shapes)]
     else:
         caps = [_loop_raw_bytes(out_order, s) for s in shapes]
     name = f"yolo2_hip_{'multi_' if multi else ''}loop_images_jpeg"
-    for attempt in range(2):
-        rc, dets, counts, q, outs, sizes, drawn, status, ws, hs = loop_jpegs_raw(handle, streams, LOOP_PRECISIONS[precision], flags, thresh, nms, batch,
-                                                                                 cap, labels, out_format, int(jpeg_quality) if jpeg else 0, caps,
-                                                                                 multi=multi)
-        if rc == YOLO2_SUCCESS or attempt or not jpeg or not any(int(sizes[f]) > caps[f] for f in range(len(caps))):
-            break
-        caps = [jpeg_bound(s[1], s[0]) for s in shapes]   # (the rare frame that compresses to more than its raw size)
+    with jpeg_mode(handle, jpeg_subsample, jpeg_restart, multi):
+        for attempt in range(2):
+            rc, dets, counts, q, outs, sizes, drawn, status, ws, hs = loop_jpegs_raw(handle, streams, LOOP_PRECISIONS[precision], flags, thresh, nms,
+                                                                                     batch, cap, labels, out_format, int(jpeg_quality) if jpeg else 0,
+                                                                                     caps, multi=multi)
+            if rc == YOLO2_SUCCESS or attempt or not jpeg or not any(int(sizes[f]) > caps[f] for f in range(len(caps))):
+                break
+            caps = room   # (the rare frame that compresses to more than its raw size)
     if rc != YOLO2_SUCCESS and (strict or not status.any()):
         check(rc, name)
     n = len(outs)
@@ -1911,10 +1964,11 @@ class Yolo2HipMulti:
               "yolo2_hip_multi_run_images_u8_host" if pixfmt is None else "yolo2_hip_multi_run_images_pix_host")
         return region, q.value
 
-    def annotate_images(self, images, dets, counts, batch_per_device: int, thresh: float, labels=None, pixfmt=None, jpeg_quality=None):
+    def annotate_images(self, images, dets, counts, batch_per_device: int, thresh: float, labels=None, pixfmt=None, jpeg_quality=None,
+                        jpeg_subsample=None, jpeg_restart=None):
         """annotated frames, shard i painted by device i (module-level annotate_images)"""
         return annotate_images(self._m, images, dets, counts, batch_per_device, thresh, labels=labels, pixfmt=pixfmt, multi=True,
-                               jpeg_quality=jpeg_quality)
+                               jpeg_quality=jpeg_quality, jpeg_subsample=jpeg_subsample, jpeg_restart=jpeg_restart)
 
     def loop_images(self, images, batch_per_device: int = 64, **kw):
         """the camera loop as one call, shard i on device i (module-level loop_images)"""
