@@ -6,16 +6,16 @@
 
 namespace y2 {
 
-__global__ __launch_bounds__(256) void k_i8_front_nv12(const FrontI8Args a) { i8_front_tiles<LbYuv420<true>>(a); }
-__global__ __launch_bounds__(256) void k_i8_front_i420(const FrontI8Args a) { i8_front_tiles<LbYuv420<false>>(a); }
-// packed BGR24 / RGBA32 / BGRA32 frames (LbPacked): bit-identical to k_i8_front_u8's on the reordered bytes (tests/test_gpu_packed.py)
-__global__ __launch_bounds__(256) void k_i8_front_bgr24(const FrontI8Args a) { i8_front_tiles<LbPacked<3, true>>(a); }
-__global__ __launch_bounds__(256) void k_i8_front_rgba32(const FrontI8Args a) { i8_front_tiles<LbPacked<4, false>>(a); }
-__global__ __launch_bounds__(256) void k_i8_front_bgra32(const FrontI8Args a) { i8_front_tiles<LbPacked<4, true>>(a); }
-// raw 8-bit Bayer frames (LbBayer<RX, RY>): bit-identical to k_i8_front_u8's on the demosaiced frame (tests/test_gpu_bayer.py)
-__global__ __launch_bounds__(256) void k_i8_front_bayer_rggb(const FrontI8Args a) { i8_front_tiles<LbBayer<0, 0>>(a); }
-__global__ __launch_bounds__(256) void k_i8_front_bayer_grbg(const FrontI8Args a) { i8_front_tiles<LbBayer<1, 0>>(a); }
-__global__ __launch_bounds__(256) void k_i8_front_bayer_gbrg(const FrontI8Args a) { i8_front_tiles<LbBayer<0, 1>>(a); }
-__global__ __launch_bounds__(256) void k_i8_front_bayer_bggr(const FrontI8Args a) { i8_front_tiles<LbBayer<1, 1>>(a); }
+// k_i8_front_<short> of every kind whose I8 column says GEN (pix_formats.hpp; the TPL kinds are k_i8_front_pix<fetch> itself).
+// Bit-identical to k_i8_front_u8's on the reordered bytes (packed: tests/test_gpu_packed.py) or on the demosaiced frame (raw Bayer:
+// tests/test_gpu_bayer.py).
+#define Y2_I8F_TPL(SHORT, ...)
+#define Y2_I8F_GEN(SHORT, ...) \
+    __global__ __launch_bounds__(256) void k_i8_front_##SHORT(const FrontI8Args a) { i8_front_tiles<__VA_ARGS__>(a); }
+#define Y2_I8F_ROW(KIND, SHORT, LB, I8, F16, ...) Y2_I8F_##I8(SHORT, __VA_ARGS__)
+Y2_PIX_KINDS(Y2_I8F_ROW)
+#undef Y2_I8F_ROW
+#undef Y2_I8F_GEN
+#undef Y2_I8F_TPL
 
 }  // namespace y2

@@ -33,27 +33,7 @@ __device__ inline float lb_value_pix(const uint8_t *__restrict__ img, const Lett
     const int y = rem / a.net_w;
     return lb_value_at<LbDiv255, PIX>(img, a, k, y, rem - y * a.net_w);
 }
-__device__ inline float lb_value_yuyv(const uint8_t *__restrict__ img, const LetterboxArgs &a, int t) { return lb_value_pix<LbYuyv>(img, a, t); }
-
-// one image (a.ch == 2, a.w even, img on a 4-byte boundary)
-__global__ void k_letterbox_yuyv(const uint8_t *__restrict__ img, float *__restrict__ out, const LetterboxArgs a)
-{
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= 3 * a.net_w * a.net_h) return;
-    out[t] = lb_value_yuyv(img, a, t);
-}
-
-// a whole chunk (k_letterbox_u8_batch's staging buffer: the LetterboxItem table, then the frames; blockIdx.y = frame)
-__global__ void k_letterbox_yuyv_batch(const uint8_t *__restrict__ base, float *__restrict__ out, int frame_elems)
-{
-    const LetterboxItem *it = reinterpret_cast<const LetterboxItem *>(base) + blockIdx.y;
-    const LetterboxArgs a = it->a;
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= 3 * a.net_w * a.net_h) return;
-    out[(size_t)blockIdx.y * frame_elems + t] = lb_value_yuyv(base + it->off, a, t);
-}
-
-// the two kernels above for a planar 4:2:0 fetch (a.w and a.h even, img at any address)
+// one image (the format's own rules: YUYV a.w even and img on a 4-byte boundary, 4:2:0 a.w and a.h even, ...: pix_formats.hpp)
 template <class PIX>
 __device__ inline void letterbox_pix_one(const uint8_t *__restrict__ img, float *__restrict__ out, const LetterboxArgs &a)
 {
@@ -61,6 +41,7 @@ __device__ inline void letterbox_pix_one(const uint8_t *__restrict__ img, float 
     if (t >= 3 * a.net_w * a.net_h) return;
     out[t] = lb_value_pix<PIX>(img, a, t);
 }
+// a whole chunk (k_letterbox_u8_batch's staging buffer: the LetterboxItem table, then the frames; blockIdx.y = frame)
 template <class PIX>
 __device__ inline void letterbox_pix_batch(const uint8_t *__restrict__ base, float *__restrict__ out, int frame_elems)
 {
@@ -70,46 +51,22 @@ __device__ inline void letterbox_pix_batch(const uint8_t *__restrict__ base, flo
     if (t >= 3 * a.net_w * a.net_h) return;
     out[(size_t)blockIdx.y * frame_elems + t] = lb_value_pix<PIX>(base + it->off, a, t);
 }
-__global__ void k_letterbox_nv12(const uint8_t *__restrict__ img, float *__restrict__ out, const LetterboxArgs a) { letterbox_pix_one<LbYuv420<true>>(img, out, a); }
-__global__ void k_letterbox_i420(const uint8_t *__restrict__ img, float *__restrict__ out, const LetterboxArgs a) { letterbox_pix_one<LbYuv420<false>>(img, out, a); }
-__global__ void k_letterbox_nv12_batch(const uint8_t *__restrict__ base, float *__restrict__ out, int frame_elems)
-{
-    letterbox_pix_batch<LbYuv420<true>>(base, out, frame_elems);
-}
-__global__ void k_letterbox_i420_batch(const uint8_t *__restrict__ base, float *__restrict__ out, int frame_elems)
-{
-    letterbox_pix_batch<LbYuv420<false>>(base, out, frame_elems);
-}
 
-// ... and for packed BGR24 / RGBA32 / BGRA32 frames (LbPacked: BGR24 at any address, the 32-bit formats on a 4-byte boundary)
-#define Y2_LETTERBOX_PACKED(NAME, BPP, SWAP)                                                                                                  \
-    __global__ void NAME(const uint8_t *__restrict__ img, float *__restrict__ out, const LetterboxArgs a)                                    \
+// k_letterbox_<short> and k_letterbox_<short>_batch of every kind whose LB column says GEN (pix_formats.hpp)
+#define Y2_LB_HAS(SHORT, ...)
+#define Y2_LB_GEN(SHORT, ...)                                                                                                                 \
+    __global__ void k_letterbox_##SHORT(const uint8_t *__restrict__ img, float *__restrict__ out, const LetterboxArgs a)                     \
     {                                                                                                                                         \
-        letterbox_pix_one<LbPacked<BPP, SWAP>>(img, out, a);                                                                                  \
+        letterbox_pix_one<__VA_ARGS__>(img, out, a);                                                                                          \
     }                                                                                                                                         \
-    __global__ void NAME##_batch(const uint8_t *__restrict__ base, float *__restrict__ out, int frame_elems)                                 \
+    __global__ void k_letterbox_##SHORT##_batch(const uint8_t *__restrict__ base, float *__restrict__ out, int frame_elems)                  \
     {                                                                                                                                         \
-        letterbox_pix_batch<LbPacked<BPP, SWAP>>(base, out, frame_elems);                                                                     \
+        letterbox_pix_batch<__VA_ARGS__>(base, out, frame_elems);                                                                             \
     }
-Y2_LETTERBOX_PACKED(k_letterbox_bgr24, 3, true)
-Y2_LETTERBOX_PACKED(k_letterbox_rgba32, 4, false)
-Y2_LETTERBOX_PACKED(k_letterbox_bgra32, 4, true)
-#undef Y2_LETTERBOX_PACKED
-
-// ... and for raw Bayer frames (LbBayer<RX, RY>: the red site's parities; any address)
-#define Y2_LETTERBOX_BAYER(NAME, RX, RY)                                                                                                      \
-    __global__ void NAME(const uint8_t *__restrict__ img, float *__restrict__ out, const LetterboxArgs a)                                    \
-    {                                                                                                                                         \
-        letterbox_pix_one<LbBayer<RX, RY>>(img, out, a);                                                                                      \
-    }                                                                                                                                         \
-    __global__ void NAME##_batch(const uint8_t *__restrict__ base, float *__restrict__ out, int frame_elems)                                 \
-    {                                                                                                                                         \
-        letterbox_pix_batch<LbBayer<RX, RY>>(base, out, frame_elems);                                                                         \
-    }
-Y2_LETTERBOX_BAYER(k_letterbox_bayer_rggb, 0, 0)
-Y2_LETTERBOX_BAYER(k_letterbox_bayer_grbg, 1, 0)
-Y2_LETTERBOX_BAYER(k_letterbox_bayer_gbrg, 0, 1)
-Y2_LETTERBOX_BAYER(k_letterbox_bayer_bggr, 1, 1)
-#undef Y2_LETTERBOX_BAYER
+#define Y2_LB_ROW(KIND, SHORT, LB, I8, F16, ...) Y2_LB_##LB(SHORT, __VA_ARGS__)
+Y2_PIX_KINDS(Y2_LB_ROW)
+#undef Y2_LB_ROW
+#undef Y2_LB_GEN
+#undef Y2_LB_HAS
 
 }  // namespace y2

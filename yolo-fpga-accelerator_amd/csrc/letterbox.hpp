@@ -16,6 +16,7 @@
 #include <type_traits>
 
 #include "bayer_def.hpp"
+#include "pix_formats.hpp"
 
 namespace y2 {
 
@@ -44,21 +45,28 @@ struct LbTable {
 // The pixel fetch, a type parameter of lb_part_q: which bytes of image row r are byte k of pixel x.
 // kernels_pre.hpp's: a.ch interleaved byte channels, a grey image gives its one channel three times (lb_part_q's own lines)
 struct LbInterleaved {};
-// Packed YUYV 4:2:2 (V4L2 'YUYV', a.ch == 2 bytes per pixel, a.w even): pixels 2p and 2p + 1 are the bytes Y0 U Y1 V at 4p, and
-// the byte is the reference camera loop's conversion (yolo2_yuyv_to_rgb24, linux_app/src/yolo2_v4l2.c:328-374): integer BT.601
-// with an arithmetic shift and a clamp to 0..255.  The pair is one aligned dword (rows are 2 a.w bytes, the image starts on a
-// 4-byte boundary), loaded once per pixel.
+// The YUV fetches' byte: the reference camera loop's conversion (yolo2_yuyv_to_rgb24, linux_app/src/yolo2_v4l2.c:328-374), integer
+// BT.601 with an arithmetic shift and a clamp to 0..255.  LbBt601(k): channel k's U and V coefficients.
+struct LbBt601 {
+    int cu, cv;
+    __device__ explicit LbBt601(int k) : cu(k == 0 ? 0 : (k == 1 ? -100 : 516)), cv(k == 0 ? 409 : (k == 1 ? -208 : 0)) {}
+};
+__device__ inline uint8_t lb_bt601_byte(const LbBt601 &m, int y, int u, int v)
+{
+    const int c = y - 16, d = u - 128, e = v - 128;
+    return (uint8_t)min(max((298 * c + m.cu * d + m.cv * e + 128) >> 8, 0), 255);
+}
+// Packed YUYV 4:2:2 (V4L2 'YUYV', a.ch == 2 bytes per pixel, a.w even): pixels 2p and 2p + 1 are the bytes Y0 U Y1 V at 4p.  The
+// pair is one aligned dword (rows are 2 a.w bytes, the image starts on a 4-byte boundary), loaded once per pixel.
 struct LbYuyv {
     const uint32_t *row;
-    int cu, cv;   // channel k's U and V coefficients
+    LbBt601 m;
     __device__ LbYuyv(const uint8_t *__restrict__ img, const LetterboxArgs &a, int r, int k)
-        : row(reinterpret_cast<const uint32_t *>(img + ((size_t)r * a.w) * 2)), cu(k == 0 ? 0 : (k == 1 ? -100 : 516)),
-          cv(k == 0 ? 409 : (k == 1 ? -208 : 0)) {}
+        : row(reinterpret_cast<const uint32_t *>(img + ((size_t)r * a.w) * 2)), m(k) {}
     __device__ uint8_t operator()(int x) const
     {
         const uint32_t p = row[x >> 1];
-        const int c = (int)((p >> ((x & 1) * 16)) & 255u) - 16, d = (int)((p >> 8) & 255u) - 128, e = (int)(p >> 24) - 128;
-        return (uint8_t)min(max((298 * c + cu * d + cv * e + 128) >> 8, 0), 255);
+        return lb_bt601_byte(m, (int)((p >> ((x & 1) * 16)) & 255u), (int)((p >> 8) & 255u), (int)(p >> 24));
     }
 };
 
@@ -69,20 +77,18 @@ struct LbYuyv {
 // The plane addresses follow from a.w and a.h alone (a.ch is a format code here, not a byte count, and is not read).  All loads are
 // byte loads: an I420 chroma row is a.w / 2 bytes and starts anywhere, and the single-image entries take a frame at any address, so
 // an NV12 pair is not known to sit on an even address either.
-constexpr int kLbChNv12 = 12, kLbChI420 = 13;   // LetterboxArgs::ch / AnnoFrame::ch of the two formats
+constexpr int kLbChNv12 = y2pix::ch_of(y2pix::NV12), kLbChI420 = y2pix::ch_of(y2pix::I420);   // LetterboxArgs::ch / AnnoFrame::ch of the two formats
 template <bool SEMI>
 struct LbYuv420 {
     const uint8_t *y, *u, *v;   // luma row r; chroma row r >> 1 (SEMI: v = u + 1, pairs two bytes apart)
-    int cu, cv;
+    LbBt601 m;
     __device__ LbYuv420(const uint8_t *__restrict__ img, const LetterboxArgs &a, int r, int k)
         : y(img + (size_t)r * a.w), u(img + (size_t)a.w * a.h + (size_t)(r >> 1) * (SEMI ? a.w : a.w >> 1)),
-          v(u + (SEMI ? (size_t)1 : ((size_t)(a.w >> 1) * (a.h >> 1)))), cu(k == 0 ? 0 : (k == 1 ? -100 : 516)),
-          cv(k == 0 ? 409 : (k == 1 ? -208 : 0)) {}
+          v(u + (SEMI ? (size_t)1 : ((size_t)(a.w >> 1) * (a.h >> 1)))), m(k) {}
     __device__ uint8_t operator()(int x) const
     {
         const int xc = SEMI ? (x & ~1) : (x >> 1);
-        const int c = (int)y[x] - 16, d = (int)u[xc] - 128, e = (int)v[xc] - 128;
-        return (uint8_t)min(max((298 * c + cu * d + cv * e + 128) >> 8, 0), 255);
+        return lb_bt601_byte(m, y[x], u[xc], v[xc]);
     }
 };
 
@@ -91,7 +97,7 @@ struct LbYuv420 {
 // R G B X) and, SWAP, BGRA32 ('AR24': B G R X); the pixel is one aligned dword (rows are 4 a.w bytes, the image starts on a 4-byte
 // boundary) and the fourth byte is shifted past, never into a result.  The byte is the source's own: everything after the fetch sees
 // what LbInterleaved would on the RGB24 frame with the bytes reordered.  (a.ch is a format code here, not a byte count, and is not read)
-constexpr int kLbChBgr24 = 24, kLbChRgba32 = 32, kLbChBgra32 = 33;   // LetterboxArgs::ch / AnnoFrame::ch of the three formats
+constexpr int kLbChBgr24 = y2pix::ch_of(y2pix::BGR24), kLbChRgba32 = y2pix::ch_of(y2pix::RGBA32), kLbChBgra32 = y2pix::ch_of(y2pix::BGRA32);   // LetterboxArgs::ch / AnnoFrame::ch of the three formats
 template <int BPP, bool SWAP>
 struct LbPacked {
     static_assert(BPP == 3 || BPP == 4, "three packed bytes, or three and a fourth that is not used");
@@ -111,7 +117,10 @@ struct LbPacked {
 // the 3 x 3 neighbourhood, mirrored at the frame's edges.  The constructor resolves what the row fixes - the three mirrored row
 // pointers and, from the row's parity and k, the site rule of the even and of the odd columns - so that operator() is a parity
 // select, two mirrored column indices and the rule's one to four byte loads.  The four patterns are four instantiations of this text.
-constexpr int kLbChBayer = 80;   // LetterboxArgs::ch / AnnoFrame::ch of the four patterns: kLbChBayer + RX + 2 * RY
+constexpr int kLbChBayer = y2pix::ch_of(y2pix::BAYER_RGGB8);   // LetterboxArgs::ch / AnnoFrame::ch of the four patterns: kLbChBayer + RX + 2 * RY
+static_assert(y2pix::ch_of(y2pix::BAYER_GRBG8) == kLbChBayer + 1 && y2pix::ch_of(y2pix::BAYER_GBRG8) == kLbChBayer + 2 &&
+                  y2pix::ch_of(y2pix::BAYER_BGGR8) == kLbChBayer + 3 && y2pix::by_fourcc(y2pix::BAYER_RGGB8)->min_side == y2b::kBayerMinSide,
+              "pix_formats.hpp: the Bayer rows");
 __host__ __device__ constexpr bool lb_ch_is_bayer(int ch) { return (ch & ~3) == kLbChBayer; }
 template <int RX, int RY>
 struct LbBayer {

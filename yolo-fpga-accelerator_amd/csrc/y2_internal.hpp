@@ -33,6 +33,7 @@
 #include "../../include/yolo2_hip.h"
 #include "conv_common.hpp"
 #include "layout.hpp"
+#include "pix_formats.hpp"   // after yolo2_hip.h: its rows are checked against YOLO2_PIX_*
 #include "y2_mem.hpp"
 
 // ---------------------------------------------------------------------------- errors (yolo2_hip.hip)
@@ -573,32 +574,10 @@ int y2_loop_enqueue_paint(yolo2_hip_ctx *c, int nf, int max_strips, const uint8_
 // yolo2_hip.hip: what the images entries and the loop entry share - the letterbox rule, the chunk letterbox launch, PipeBufs' growth
 // (need_hout: the pinned region mirrors; _post: the tail's buffers; _regf: the fp32 region tensors) and the threaded staging copy
 namespace y2 { struct LetterboxArgs; }
-// The pixel formats of the _pix entries, one descriptor each: everything the host code needs to know about a format.
-//   ch      what LetterboxArgs::ch / AnnoFrame::ch carry: bytes per pixel for interleaved bytes (1, 3) and YUYV (2); for the planar
-//           4:2:0 formats, which have no whole number of bytes per pixel, and for packed BGR24 / RGBA32 / BGRA32, whose byte counts
-//           3 and 4 would not tell them from RGB24, and for the four raw Bayer patterns (1 byte per pixel, as GREY8) a code that only
-//           their own fetch looks at
-//   kind    which kernels read it (the letterbox, layer-0, int8-front and painter instantiations)
-//   frame_bytes(w, h)   size of a frame; sizes staging, offsets and geometry everywhere
-//   even_w / even_h     the parity rule; align: the address alignment the single-image entries ask for
-//   min_side            the least width and height (a Bayer frame has a whole 2 x 2 block: the mirror needs a second row and column)
-enum Y2PixKind {
-    Y2_KIND_BYTES = 0, Y2_KIND_YUYV, Y2_KIND_NV12, Y2_KIND_I420, Y2_KIND_BGR24, Y2_KIND_RGBA32, Y2_KIND_BGRA32,
-    Y2_KIND_BAYER_RGGB, Y2_KIND_BAYER_GRBG, Y2_KIND_BAYER_GBRG, Y2_KIND_BAYER_BGGR,   // (in the order of kLbChBayer + rx + 2 * ry)
-    Y2_KIND_COUNT,
-    Y2_KIND_F16_COUNT = Y2_KIND_BAYER_RGGB   // the kinds [0, this) have a layer-0 step from bytes in the fp16 table; add a kind with one in front of the Bayer kinds
-};
-struct Y2PixDesc {
-    int pixfmt;
-    const char *name;
-    int ch;
-    Y2PixKind kind;
-    int bits;   // per pixel
-    bool even_w, even_h;
-    unsigned align;
-    int min_side;
-    size_t frame_bytes(int w, int h) const { return (size_t)w * h * bits / 8; }
-};
+// The pixel formats of the _pix entries, one descriptor each: everything the host code needs to know about a format.  The formats,
+// the descriptor's fields and Y2PixKind (which kernels read a frame) are pix_formats.hpp's; frame_bytes(w, h) sizes staging, offsets
+// and geometry everywhere.
+using Y2PixDesc = y2pix::Format;
 const Y2PixDesc *y2_pix_desc(int pixfmt, const char *who);   // by YOLO2_PIX_* fourcc; nullptr and "[who: ]unknown pixel format" otherwise
 const Y2PixDesc *y2_pix_desc_ch(int ch);                     // by its ch; nullptr for a ch no format has
 inline size_t y2_frame_bytes(int w, int h, int ch)

@@ -67,7 +67,9 @@ struct F16Table {
     // entries refuse them on these passes before anything is launched (y2_f16_images_check_kind).
     F16Step u8;
     F16LaunchU8 launch_u8 = nullptr, launch_pix[Y2_KIND_COUNT] = {};
-    const char *pix_kernel[Y2_KIND_COUNT] = {"", "", "", "", "", "", "", "", "", "", ""};
+#define Y2_PIX_ROW(...) "",
+    const char *pix_kernel[Y2_KIND_COUNT] = {Y2_PIX_KINDS(Y2_PIX_ROW)};
+#undef Y2_PIX_ROW
 };
 struct F16Plan : F16Table {
     Y2Options opt;               // the context's option set as it was when the weights were loaded; a lane runs the parent's selection
@@ -358,6 +360,15 @@ static const F16Kernel kF16Kernels[] = {F16_KERNELS(X, XB)};
 #undef ID
 #undef X
 #undef XB
+// the layer-0 step from bytes of every kind, by Y2PixKind: its {fp16, split} rows above, -1 where the kind has none (one row per row
+// of Y2_PIX_KINDS: a kind whose F16 column is not NONE needs its FK_C0_<KIND> and FK_C0_<KIND>_SP rows)
+enum { FK_C0_BYTES = FK_C0_U8, FK_C0_BYTES_SP = FK_C0_U8_SP };   // (the registry names the BYTES kind's kernel by its short name)
+#define Y2_C0_HAS(KIND) {FK_C0_##KIND, FK_C0_##KIND##_SP},
+#define Y2_C0_GEN(KIND) Y2_C0_HAS(KIND)
+#define Y2_C0_NONE(KIND) {-1, -1},
+#define Y2_PIX_ROW(KIND, SHORT, LB, I8, F16, ...) Y2_C0_##F16(KIND)
+static constexpr int kC0Bytes[Y2_KIND_COUNT][2] = {Y2_PIX_KINDS(Y2_PIX_ROW)};
+#undef Y2_PIX_ROW
 
 static int raise_f16_lds_limits()
 {
@@ -561,12 +572,11 @@ static int select_f16_table(const Y2Options &o, bool split, int B, F16Table &T)
         }
         T.steps.push_back(s);
         if (!o.f16_no_mfma0) {   // the same tiles, grid and output from image bytes (the images entries)
-            const F16Kid kid[Y2_KIND_F16_COUNT][2] = {{FK_C0_U8, FK_C0_U8_SP}, {FK_C0_YUYV, FK_C0_YUYV_SP}, {FK_C0_NV12, FK_C0_NV12_SP}, {FK_C0_I420, FK_C0_I420_SP},
-                                                  {FK_C0_BGR24, FK_C0_BGR24_SP}, {FK_C0_RGBA32, FK_C0_RGBA32_SP}, {FK_C0_BGRA32, FK_C0_BGRA32_SP}};
-            const F16Kernel &u8 = kF16Kernels[kid[Y2_KIND_BYTES][split ? 1 : 0]];
+            const F16Kernel &u8 = kF16Kernels[kC0Bytes[Y2_KIND_BYTES][split ? 1 : 0]];
             T.u8 = s; T.u8.kernel = u8.name; T.launch_u8 = u8.launch_u8;
-            for (int kind = 0; kind < Y2_KIND_F16_COUNT; ++kind) {
-                const F16Kernel &k = kF16Kernels[kid[kind][split ? 1 : 0]];
+            for (int kind = 0; kind < Y2_KIND_COUNT; ++kind) {
+                if (kC0Bytes[kind][0] < 0) continue;
+                const F16Kernel &k = kF16Kernels[kC0Bytes[kind][split ? 1 : 0]];
                 T.pix_kernel[kind] = k.name; T.launch_pix[kind] = k.launch_u8;
             }
         }
@@ -977,7 +987,7 @@ bool y2_f16_images_fused(const yolo2_hip_ctx *run) { return !run->f16_plan->opt.
 int y2_f16_images_check_kind(const yolo2_hip_ctx *run, int kind)
 {
     (void)run;
-    if (kind >= 0 && kind < Y2_KIND_F16_COUNT) return YOLO2_SUCCESS;   // (under f16_no_mfma0 too: one answer per format, whatever the route)
+    if (kind >= 0 && kind < Y2_KIND_COUNT && kC0Bytes[kind][0] >= 0) return YOLO2_SUCCESS;   // (under f16_no_mfma0 too: one answer per format, whatever the route)
     return fail(YOLO2_ERROR, "the fp16 and fp32-tolerance passes have no layer-0 kernel for raw Bayer frames (the int16 and int8 entries read them)");
 }
 

@@ -414,36 +414,19 @@ extern "C" int yolo2_hip_layer_times_ms(yolo2_hip_ctx *c, float *ms32)
 
 // ---------------------------------------------------------------------------- pre-processing
 
-// The pixel formats (y2_internal.hpp has the fields).  The first two are the u8 entries' channel counts.
-static const Y2PixDesc kPixDescs[] = {
-    {YOLO2_PIX_GREY8, "GREY8", 1, Y2_KIND_BYTES, 8, false, false, 1, 1},
-    {YOLO2_PIX_RGB24, "RGB24", 3, Y2_KIND_BYTES, 24, false, false, 1, 1},
-    {YOLO2_PIX_YUYV, "YUYV", 2, Y2_KIND_YUYV, 16, true, false, 4, 1},            // (LbYuyv loads pixel pairs as dwords)
-    {YOLO2_PIX_NV12, "NV12", y2::kLbChNv12, Y2_KIND_NV12, 12, true, true, 1, 1},   // (LbYuv420 loads bytes)
-    {YOLO2_PIX_I420, "I420", y2::kLbChI420, Y2_KIND_I420, 12, true, true, 1, 1},
-    {YOLO2_PIX_BGR24, "BGR24", y2::kLbChBgr24, Y2_KIND_BGR24, 24, false, false, 1, 1},       // (LbPacked<3, .> loads bytes)
-    {YOLO2_PIX_RGBA32, "RGBA32", y2::kLbChRgba32, Y2_KIND_RGBA32, 32, false, false, 4, 1},   // (LbPacked<4, .> loads a pixel as one dword)
-    {YOLO2_PIX_BGRA32, "BGRA32", y2::kLbChBgra32, Y2_KIND_BGRA32, 32, false, false, 4, 1},
-    // (LbBayer<rx, ry> loads bytes; ch = kLbChBayer + rx + 2 * ry)
-    {YOLO2_PIX_BAYER_RGGB8, "BAYER_RGGB8", y2::kLbChBayer + 0, Y2_KIND_BAYER_RGGB, 8, false, false, 1, y2b::kBayerMinSide},
-    {YOLO2_PIX_BAYER_GRBG8, "BAYER_GRBG8", y2::kLbChBayer + 1, Y2_KIND_BAYER_GRBG, 8, false, false, 1, y2b::kBayerMinSide},
-    {YOLO2_PIX_BAYER_GBRG8, "BAYER_GBRG8", y2::kLbChBayer + 2, Y2_KIND_BAYER_GBRG, 8, false, false, 1, y2b::kBayerMinSide},
-    {YOLO2_PIX_BAYER_BGGR8, "BAYER_BGGR8", y2::kLbChBayer + 3, Y2_KIND_BAYER_BGGR, 8, false, false, 1, y2b::kBayerMinSide},
-};
-
+// The pixel formats: y2pix::kFormats (pix_formats.hpp).  The first two are the u8 entries' channel counts.
 const Y2PixDesc *y2_pix_desc(int pixfmt, const char *who)
 {
-    for (const Y2PixDesc &d : kPixDescs)
-        if (d.pixfmt == pixfmt) return &d;
-    (void)fail(YOLO2_ERROR, "%s%sunknown pixel format 0x%x (YOLO2_PIX_GREY8, YOLO2_PIX_RGB24, YOLO2_PIX_YUYV, YOLO2_PIX_NV12, YOLO2_PIX_I420, "
-                            "YOLO2_PIX_BGR24, YOLO2_PIX_RGBA32 or YOLO2_PIX_BGRA32; YOLO2_PIX_BAYER_RGGB8, _BGGR8, _GRBG8 or _GBRG8)",
-               who ? who : "", who ? ": " : "", (unsigned)pixfmt);
+    if (const Y2PixDesc *d = y2pix::by_fourcc(pixfmt)) return d;
+#define Y2_PIX_ROW(ID, FOURCC, KIND, CH, BITS, EVEN_W, EVEN_H, ALIGN, MIN_SIDE, CLI, ALIAS, FRAME, MSG) MSG
+    (void)fail(YOLO2_ERROR, "%s%sunknown pixel format 0x%x (" Y2_PIX_FORMATS(Y2_PIX_ROW) ")", who ? who : "", who ? ": " : "", (unsigned)pixfmt);
+#undef Y2_PIX_ROW
     return nullptr;
 }
 
 const Y2PixDesc *y2_pix_desc_ch(int ch)
 {
-    for (const Y2PixDesc &d : kPixDescs)
+    for (const Y2PixDesc &d : y2pix::kFormats)
         if (d.ch == ch) return &d;
     return nullptr;
 }
@@ -494,6 +477,16 @@ extern "C" int yolo2_hip_letterbox_u8(uint64_t image_dev, int w, int h, int chan
     return YOLO2_SUCCESS;
 }
 
+// the letterbox kernels of every kind, by Y2PixKind (one row per row of Y2_PIX_KINDS)
+struct LetterboxKernels {
+    decltype(&k_letterbox_u8) one;
+    decltype(&k_letterbox_u8_batch) batch;
+    const char *batch_name;
+};
+#define Y2_PIX_ROW(KIND, SHORT, LB, I8, F16, ...) {k_letterbox_##SHORT, k_letterbox_##SHORT##_batch, "k_letterbox_" #SHORT "_batch"},
+static constexpr LetterboxKernels kLetterboxKernels[Y2_KIND_COUNT] = {Y2_PIX_KINDS(Y2_PIX_ROW)};
+#undef Y2_PIX_ROW
+
 // pixfmt -> LetterboxArgs::ch for the _pix entries; 0 and an error for anything else
 static int pix_ch(int pixfmt)
 {
@@ -512,10 +505,7 @@ extern "C" int yolo2_hip_letterbox_pix(uint64_t image_dev, int w, int h, int pix
     LetterboxArgs a;
     int rc = y2_letterbox_args(w, h, d->ch, net_w, net_h, a, true);
     if (rc) return rc;
-    static constexpr decltype(&k_letterbox_yuyv) kernels[Y2_KIND_COUNT] = {
-        nullptr,           k_letterbox_yuyv,   k_letterbox_nv12,   k_letterbox_i420,       k_letterbox_bgr24,      k_letterbox_rgba32,
-        k_letterbox_bgra32, k_letterbox_bayer_rggb, k_letterbox_bayer_grbg, k_letterbox_bayer_gbrg, k_letterbox_bayer_bggr};
-    const auto kernel = kernels[d->kind];
+    const auto kernel = kLetterboxKernels[d->kind].one;
     hipLaunchKernelGGL(kernel, dim3(blocks_for((long)3 * net_w * net_h, 256)), dim3(256), 0, (hipStream_t)stream,
                        (const uint8_t *)(uintptr_t)image_dev, (float *)(uintptr_t)frame_dev, a);
     HIP_TRY(hipGetLastError(), YOLO2_ERROR);
@@ -523,24 +513,12 @@ extern "C" int yolo2_hip_letterbox_pix(uint64_t image_dev, int w, int h, int pix
 }
 
 // the chunk letterbox of every kind of staging buffer (Y2PixKind: what the table items' frames are), and its name
-const char *y2_letterbox_batch_kernel(int kind)
-{
-    static const char *const names[Y2_KIND_COUNT] = {"k_letterbox_u8_batch",    "k_letterbox_yuyv_batch",   "k_letterbox_nv12_batch",  "k_letterbox_i420_batch",
-                                                     "k_letterbox_bgr24_batch", "k_letterbox_rgba32_batch", "k_letterbox_bgra32_batch",
-                                                     "k_letterbox_bayer_rggb_batch", "k_letterbox_bayer_grbg_batch",
-                                                     "k_letterbox_bayer_gbrg_batch", "k_letterbox_bayer_bggr_batch"};
-    return names[kind];
-}
+const char *y2_letterbox_batch_kernel(int kind) { return kLetterboxKernels[kind].batch_name; }
 
 void y2_launch_letterbox_batch(int kind, const uint8_t *dbytes, float *din, int batch, hipStream_t st)
 {
     const dim3 grid(blocks_for((long)YOLO2_FRAME_ELEMS, 256), batch);
-    static constexpr decltype(&k_letterbox_u8_batch) kernels[Y2_KIND_COUNT] = {k_letterbox_u8_batch,    k_letterbox_yuyv_batch,   k_letterbox_nv12_batch,
-                                                                               k_letterbox_i420_batch,  k_letterbox_bgr24_batch,  k_letterbox_rgba32_batch,
-                                                                               k_letterbox_bgra32_batch, k_letterbox_bayer_rggb_batch,
-                                                                               k_letterbox_bayer_grbg_batch, k_letterbox_bayer_gbrg_batch,
-                                                                               k_letterbox_bayer_bggr_batch};
-    hipLaunchKernelGGL(kernels[kind], grid, dim3(256), 0, st, dbytes, din, (int)YOLO2_FRAME_ELEMS);   // the whole chunk in one launch
+    hipLaunchKernelGGL(kLetterboxKernels[kind].batch, grid, dim3(256), 0, st, dbytes, din, (int)YOLO2_FRAME_ELEMS);   // the whole chunk in one launch
 }
 
 // Camera-style entry: n images of arbitrary sizes as host bytes -> region tensors, in chunks of

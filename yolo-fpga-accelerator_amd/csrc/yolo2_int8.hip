@@ -337,13 +337,17 @@ extern "C" int yolo2_hip_run_batch_int8(yolo2_hip_ctx *c, uint64_t frames_dev, i
 // layers 2..30.  Profiling: the front's time is layer 1's slot (ev[1] .. ev[2]); layer 0's slot is empty.
 bool y2_i8_loaded(const yolo2_hip_ctx *c) { return c && c->i8 && c->i8->loaded; }
 bool y2_i8_images_fused(const yolo2_hip_ctx *c) { return !c->opt.i8_no_front; }
-const char *y2_i8_front_kernel(int kind)
-{
-    static const char *const names[Y2_KIND_COUNT] = {"k_i8_front_u8",    "k_i8_front_yuyv",   "k_i8_front_nv12",  "k_i8_front_i420",
-                                                     "k_i8_front_bgr24", "k_i8_front_rgba32", "k_i8_front_bgra32",
-                                                     "k_i8_front_bayer_rggb", "k_i8_front_bayer_grbg", "k_i8_front_bayer_gbrg", "k_i8_front_bayer_bggr"};
-    return names[kind];
-}
+// the front kernel of every kind, by Y2PixKind (one row per row of Y2_PIX_KINDS; TPL: the template itself, GEN: kernels_i8_front_pix.hpp's)
+struct FrontKernel {
+    decltype(&k_i8_front_pix<LbInterleaved>) kernel;
+    const char *name;
+};
+#define Y2_I8K_TPL(SHORT, ...) k_i8_front_pix<__VA_ARGS__>
+#define Y2_I8K_GEN(SHORT, ...) k_i8_front_##SHORT
+#define Y2_PIX_ROW(KIND, SHORT, LB, I8, F16, ...) {Y2_I8K_##I8(SHORT, __VA_ARGS__), "k_i8_front_" #SHORT},
+static constexpr FrontKernel kFrontKernels[Y2_KIND_COUNT] = {Y2_PIX_KINDS(Y2_PIX_ROW)};
+#undef Y2_PIX_ROW
+const char *y2_i8_front_kernel(int kind) { return kFrontKernels[kind].name; }
 
 int y2_i8_run_images(yolo2_hip_ctx *c, const uint8_t *lb, int kind, int batch, float *region_dev, hipStream_t st)
 {
@@ -369,17 +373,7 @@ int y2_i8_run_images(yolo2_hip_ctx *c, const uint8_t *lb, int kind, int batch, f
     a.q0 = s->act_q[0];
     a.leaky = kNet[0].leaky;
     const dim3 grid((unsigned)batch * kFrontTilesPerFrame), block(256);
-    if (kind == Y2_KIND_YUYV) hipLaunchKernelGGL(k_i8_front_pix<LbYuyv>, grid, block, 0, st, a);
-    else if (kind == Y2_KIND_NV12) hipLaunchKernelGGL(k_i8_front_nv12, grid, block, 0, st, a);
-    else if (kind == Y2_KIND_I420) hipLaunchKernelGGL(k_i8_front_i420, grid, block, 0, st, a);
-    else if (kind == Y2_KIND_BGR24) hipLaunchKernelGGL(k_i8_front_bgr24, grid, block, 0, st, a);
-    else if (kind == Y2_KIND_RGBA32) hipLaunchKernelGGL(k_i8_front_rgba32, grid, block, 0, st, a);
-    else if (kind == Y2_KIND_BGRA32) hipLaunchKernelGGL(k_i8_front_bgra32, grid, block, 0, st, a);
-    else if (kind == Y2_KIND_BAYER_RGGB) hipLaunchKernelGGL(k_i8_front_bayer_rggb, grid, block, 0, st, a);
-    else if (kind == Y2_KIND_BAYER_GRBG) hipLaunchKernelGGL(k_i8_front_bayer_grbg, grid, block, 0, st, a);
-    else if (kind == Y2_KIND_BAYER_GBRG) hipLaunchKernelGGL(k_i8_front_bayer_gbrg, grid, block, 0, st, a);
-    else if (kind == Y2_KIND_BAYER_BGGR) hipLaunchKernelGGL(k_i8_front_bayer_bggr, grid, block, 0, st, a);
-    else hipLaunchKernelGGL(k_i8_front_pix<LbInterleaved>, grid, block, 0, st, a);
+    hipLaunchKernelGGL(kFrontKernels[kind].kernel, grid, block, 0, st, a);
     if (ev) (void)hipEventRecord(ev[2], st);
     if ((rc = run_layers(s, 2, &s->t[1], batch, (uint64_t)(uintptr_t)region_dev, st, ev))) return rc;
     if (ev) c->prof_runs++;

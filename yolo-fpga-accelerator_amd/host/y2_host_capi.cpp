@@ -8,6 +8,7 @@
 
 #include "../csrc/bayer_def.hpp"
 #include "../csrc/draw_list.hpp"
+#include "../csrc/pix_formats.hpp"
 #include "y2_host.hpp"
 
 using namespace y2h;
@@ -157,7 +158,7 @@ int y2h_rgb24_to_yuv420(const uint8_t *rgb, int w, int h, int semi_planar, uint8
 // null pointer, a non-positive width / height or another pixfmt
 int y2h_packed_to_rgb24(const uint8_t *src, int w, int h, int pixfmt, uint8_t *rgb)
 {
-    const int fmt = pixfmt == 0x33524742 ? kFrameBgr24 : pixfmt == 0x34324241 ? kFrameRgba32 : pixfmt == 0x34325241 ? kFrameBgra32 : -1;
+    const int fmt = pixfmt == y2pix::BGR24 ? kFrameBgr24 : pixfmt == y2pix::RGBA32 ? kFrameRgba32 : pixfmt == y2pix::BGRA32 ? kFrameBgra32 : -1;
     if (fmt < 0) {
         char hex[16];
         std::snprintf(hex, sizeof(hex), "0x%x", (unsigned)pixfmt);

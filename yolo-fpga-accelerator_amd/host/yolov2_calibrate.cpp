@@ -18,6 +18,7 @@
 
 #include "../../include/yolo2_hip.h"
 #include "y2_host.hpp"
+#include "y2_pix_cli.hpp"
 
 namespace {
 
@@ -72,18 +73,9 @@ Config parse_args(int argc, char **argv)
         else if (arg == "--max-frames" && need()) cfg.max_frames = std::atoi(argv[++i]);
         else if (arg == "--video-pix-fmt" && need()) {
             const std::string v = argv[++i];
-            if (v == "rgb24") cfg.video_pixfmt = YOLO2_PIX_RGB24;
-            else if (v == "yuyv422" || v == "yuyv") cfg.video_pixfmt = YOLO2_PIX_YUYV;
-            else if (v == "nv12") cfg.video_pixfmt = YOLO2_PIX_NV12;
-            else if (v == "yuv420p" || v == "i420") cfg.video_pixfmt = YOLO2_PIX_I420;
-            else if (v == "bgr24") cfg.video_pixfmt = YOLO2_PIX_BGR24;
-            else if (v == "rgba" || v == "rgb0") cfg.video_pixfmt = YOLO2_PIX_RGBA32;
-            else if (v == "bgra" || v == "bgr0") cfg.video_pixfmt = YOLO2_PIX_BGRA32;
-            else if (v == "bayer_rggb8") cfg.video_pixfmt = YOLO2_PIX_BAYER_RGGB8;
-            else if (v == "bayer_bggr8") cfg.video_pixfmt = YOLO2_PIX_BAYER_BGGR8;
-            else if (v == "bayer_grbg8") cfg.video_pixfmt = YOLO2_PIX_BAYER_GRBG8;
-            else if (v == "bayer_gbrg8") cfg.video_pixfmt = YOLO2_PIX_BAYER_GBRG8;
-            else { std::fprintf(stderr, "Unsupported --video-pix-fmt %s (rgb24 | yuyv422 | nv12 | yuv420p | bgr24 | rgba | bgra | bayer_rggb8 | bayer_bggr8 | bayer_grbg8 | bayer_gbrg8)\n", v.c_str()); std::exit(1); }
+            const y2pix::Format *f = y2cli::pix_by_spelling(v);
+            if (!f) { std::fprintf(stderr, "Unsupported --video-pix-fmt %s (%s)\n", v.c_str(), y2cli::pix_spellings().c_str()); std::exit(1); }
+            cfg.video_pixfmt = f->pixfmt;
         }
         else if (arg == "--out" && need()) cfg.out_dir = argv[++i];
         else if (arg == "--batch" && need()) cfg.batch = std::atoi(argv[++i]);
@@ -98,12 +90,11 @@ Config parse_args(int argc, char **argv)
         std::exit(1);
     }
     if (!cfg.video_raw.empty()) {
-        const bool planar = cfg.video_pixfmt == YOLO2_PIX_NV12 || cfg.video_pixfmt == YOLO2_PIX_I420;
+        const y2pix::Format &vf = y2cli::pix(cfg.video_pixfmt);
         if (cfg.video_w < 1 || cfg.video_h < 1) { std::fprintf(stderr, "--video-width and --video-height must be positive\n"); std::exit(1); }
-        if ((cfg.video_pixfmt == YOLO2_PIX_YUYV && (cfg.video_w & 1)) || (planar && ((cfg.video_w | cfg.video_h) & 1))) {
-            std::fprintf(stderr, "--video-pix-fmt %s needs an even --video-width%s, not %dx%d\n",
-                         cfg.video_pixfmt == YOLO2_PIX_YUYV ? "yuyv422" : (cfg.video_pixfmt == YOLO2_PIX_NV12 ? "nv12" : "yuv420p"),
-                         planar ? " and --video-height" : "", cfg.video_w, cfg.video_h);
+        if (!y2cli::pix_parity_ok(vf, cfg.video_w, cfg.video_h)) {
+            std::fprintf(stderr, "--video-pix-fmt %s needs an even --video-width%s, not %dx%d\n", vf.cli, vf.even_h ? " and --video-height" : "", cfg.video_w,
+                         cfg.video_h);
             std::exit(1);
         }
     }
@@ -139,13 +130,7 @@ std::vector<std::string> list_inputs(const Config &cfg)
 // the whole frames of a raw video file, as they are (a trailing partial frame is dropped)
 std::vector<std::vector<uint8_t>> read_video_frames(const Config &cfg)
 {
-    const size_t px = (size_t)cfg.video_w * cfg.video_h;
-    const bool bayer = cfg.video_pixfmt == YOLO2_PIX_BAYER_RGGB8 || cfg.video_pixfmt == YOLO2_PIX_BAYER_BGGR8 || cfg.video_pixfmt == YOLO2_PIX_BAYER_GRBG8 ||
-                       cfg.video_pixfmt == YOLO2_PIX_BAYER_GBRG8;
-    const size_t bytes = bayer ? px
-                         : cfg.video_pixfmt == YOLO2_PIX_RGBA32 || cfg.video_pixfmt == YOLO2_PIX_BGRA32 ? 4 * px
-                         : cfg.video_pixfmt == YOLO2_PIX_YUYV ? 2 * px
-                         : (cfg.video_pixfmt == YOLO2_PIX_NV12 || cfg.video_pixfmt == YOLO2_PIX_I420 ? px * 3 / 2 : 3 * px);
+    const size_t bytes = y2cli::pix(cfg.video_pixfmt).frame_bytes(cfg.video_w, cfg.video_h);
     std::ifstream in(cfg.video_raw, std::ios::binary);
     if (!in) throw std::runtime_error("Cannot open " + cfg.video_raw);
     std::vector<std::vector<uint8_t>> frames;

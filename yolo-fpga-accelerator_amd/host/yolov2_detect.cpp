@@ -42,14 +42,9 @@
 
 #include "../../include/yolo2_hip.h"
 #include "y2_host.hpp"
+#include "y2_pix_cli.hpp"
 
 namespace {
-
-// one of the four raw 8-bit Bayer patterns
-bool is_bayer(int pixfmt)
-{
-    return pixfmt == YOLO2_PIX_BAYER_RGGB8 || pixfmt == YOLO2_PIX_BAYER_BGGR8 || pixfmt == YOLO2_PIX_BAYER_GRBG8 || pixfmt == YOLO2_PIX_BAYER_GBRG8;
-}
 
 struct AppConfig {
     std::string cfg_path = "config/yolov2.cfg";
@@ -213,18 +208,9 @@ AppConfig parse_args(int argc, char **argv)
         else if (arg == "--video-height" && need("")) cfg.video_h = std::atoi(argv[++i]);
         else if (arg == "--video-pix-fmt" && need("")) {
             const std::string v = argv[++i];
-            if (v == "rgb24") cfg.video_pixfmt = YOLO2_PIX_RGB24;
-            else if (v == "yuyv422" || v == "yuyv") cfg.video_pixfmt = YOLO2_PIX_YUYV;
-            else if (v == "nv12") cfg.video_pixfmt = YOLO2_PIX_NV12;
-            else if (v == "yuv420p" || v == "i420") cfg.video_pixfmt = YOLO2_PIX_I420;
-            else if (v == "bgr24") cfg.video_pixfmt = YOLO2_PIX_BGR24;
-            else if (v == "rgba" || v == "rgb0") cfg.video_pixfmt = YOLO2_PIX_RGBA32;
-            else if (v == "bgra" || v == "bgr0") cfg.video_pixfmt = YOLO2_PIX_BGRA32;
-            else if (v == "bayer_rggb8") cfg.video_pixfmt = YOLO2_PIX_BAYER_RGGB8;
-            else if (v == "bayer_bggr8") cfg.video_pixfmt = YOLO2_PIX_BAYER_BGGR8;
-            else if (v == "bayer_grbg8") cfg.video_pixfmt = YOLO2_PIX_BAYER_GRBG8;
-            else if (v == "bayer_gbrg8") cfg.video_pixfmt = YOLO2_PIX_BAYER_GBRG8;
-            else { std::fprintf(stderr, "Unsupported --video-pix-fmt %s (rgb24 | yuyv422 | nv12 | yuv420p | bgr24 | rgba | bgra | bayer_rggb8 | bayer_bggr8 | bayer_grbg8 | bayer_gbrg8)\n", v.c_str()); std::exit(1); }
+            const y2pix::Format *f = y2cli::pix_by_spelling(v);
+            if (!f) { std::fprintf(stderr, "Unsupported --video-pix-fmt %s (%s)\n", v.c_str(), y2cli::pix_spellings().c_str()); std::exit(1); }
+            cfg.video_pixfmt = f->pixfmt;
         }
         else if (arg == "--max-frames" && need("")) cfg.max_frames = std::atoi(argv[++i]);
         else if (arg == "--infer-every" && need("")) cfg.infer_every = std::max(1, std::atoi(argv[++i]));
@@ -310,13 +296,10 @@ AppConfig parse_args(int argc, char **argv)
         std::fprintf(stderr, "--decode-split is the GPU decoder's: it needs --decode gpu\n");
         std::exit(1);
     }
-    if (cfg.video_pixfmt == YOLO2_PIX_YUYV && !cfg.video_raw.empty() && (cfg.video_w & 1)) {
-        std::fprintf(stderr, "--video-pix-fmt yuyv422 needs an even --video-width, not %d\n", cfg.video_w);
-        std::exit(1);
-    }
-    if ((cfg.video_pixfmt == YOLO2_PIX_NV12 || cfg.video_pixfmt == YOLO2_PIX_I420) && !cfg.video_raw.empty() && ((cfg.video_w | cfg.video_h) & 1)) {
-        std::fprintf(stderr, "--video-pix-fmt %s needs an even --video-width and --video-height, not %dx%d\n",
-                     cfg.video_pixfmt == YOLO2_PIX_NV12 ? "nv12" : "yuv420p", cfg.video_w, cfg.video_h);
+    const y2pix::Format &vf = y2cli::pix(cfg.video_pixfmt);
+    if (!cfg.video_raw.empty() && !y2cli::pix_parity_ok(vf, cfg.video_w, cfg.video_h)) {
+        if (vf.even_h) std::fprintf(stderr, "--video-pix-fmt %s needs an even --video-width and --video-height, not %dx%d\n", vf.cli, cfg.video_w, cfg.video_h);
+        else std::fprintf(stderr, "--video-pix-fmt %s needs an even --video-width, not %d\n", vf.cli, cfg.video_w);
         std::exit(1);
     }
     // a raw file says nothing about what it holds, so a file that cannot be read is reported here with what would have been read from
@@ -324,12 +307,7 @@ AppConfig parse_args(int argc, char **argv)
     if (!cfg.video_raw.empty() && cfg.video_raw != "-") {
         std::error_code ec;
         if (!std::filesystem::exists(cfg.video_raw, ec) || std::filesystem::is_directory(cfg.video_raw, ec)) {
-            const char *fmt = cfg.video_pixfmt == YOLO2_PIX_YUYV ? "yuyv422" : cfg.video_pixfmt == YOLO2_PIX_NV12 ? "nv12"
-                              : cfg.video_pixfmt == YOLO2_PIX_I420 ? "yuv420p" : cfg.video_pixfmt == YOLO2_PIX_BGR24 ? "bgr24"
-                              : cfg.video_pixfmt == YOLO2_PIX_RGBA32 ? "rgba" : cfg.video_pixfmt == YOLO2_PIX_BGRA32 ? "bgra"
-                              : cfg.video_pixfmt == YOLO2_PIX_BAYER_RGGB8 ? "bayer_rggb8" : cfg.video_pixfmt == YOLO2_PIX_BAYER_BGGR8 ? "bayer_bggr8"
-                              : cfg.video_pixfmt == YOLO2_PIX_BAYER_GRBG8 ? "bayer_grbg8" : cfg.video_pixfmt == YOLO2_PIX_BAYER_GBRG8 ? "bayer_gbrg8" : "rgb24";
-            std::fprintf(stderr, "Cannot read --video-raw %s (%dx%d frames, --video-pix-fmt %s)\n", cfg.video_raw.c_str(), cfg.video_w, cfg.video_h, fmt);
+            std::fprintf(stderr, "Cannot read --video-raw %s (%dx%d frames, --video-pix-fmt %s)\n", cfg.video_raw.c_str(), cfg.video_w, cfg.video_h, vf.cli);
             std::exit(1);
         }
     }
@@ -425,27 +403,6 @@ std::vector<OutDet> best_class_dets(const std::vector<y2h::Detection> &dets, int
     return out;
 }
 
-// bytes of one --video-raw frame
-static size_t video_frame_bytes(int w, int h, int pixfmt)
-{
-    const size_t px = (size_t)w * h;
-    if (is_bayer(pixfmt)) return px;
-    if (pixfmt == YOLO2_PIX_RGBA32 || pixfmt == YOLO2_PIX_BGRA32) return 4 * px;
-    return pixfmt == YOLO2_PIX_YUYV ? 2 * px : (pixfmt == YOLO2_PIX_NV12 || pixfmt == YOLO2_PIX_I420 ? px * 3 / 2 : 3 * px);
-}
-// y2h::plain_box_frame's name for it
-static int host_frame_fmt(int pixfmt)
-{
-    if (pixfmt == YOLO2_PIX_BGR24) return y2h::kFrameBgr24;
-    if (pixfmt == YOLO2_PIX_RGBA32) return y2h::kFrameRgba32;
-    if (pixfmt == YOLO2_PIX_BGRA32) return y2h::kFrameBgra32;
-    if (pixfmt == YOLO2_PIX_BAYER_RGGB8) return y2h::kFrameBayer;       // (kFrameBayer + rx + 2 * ry)
-    if (pixfmt == YOLO2_PIX_BAYER_GRBG8) return y2h::kFrameBayer + 1;
-    if (pixfmt == YOLO2_PIX_BAYER_GBRG8) return y2h::kFrameBayer + 2;
-    if (pixfmt == YOLO2_PIX_BAYER_BGGR8) return y2h::kFrameBayer + 3;
-    return pixfmt == YOLO2_PIX_YUYV ? y2h::kFrameYuyv : pixfmt == YOLO2_PIX_NV12 ? y2h::kFrameNv12 : pixfmt == YOLO2_PIX_I420 ? y2h::kFrameI420 : y2h::kFrameRgb24;
-}
-
 struct SrcFrame {
     std::string source;
     int frame_index = 0;    // 1-based position in the stream
@@ -500,7 +457,7 @@ class FrameSource {
             SrcFrame f;
             if (mode_ == "video") {
                 f.img.w = cfg_.video_w; f.img.h = cfg_.video_h;
-                f.img.rgb.resize(video_frame_bytes(cfg_.video_w, cfg_.video_h, cfg_.video_pixfmt));
+                f.img.rgb.resize(y2cli::pix(cfg_.video_pixfmt).frame_bytes(cfg_.video_w, cfg_.video_h));
                 const size_t rd = std::fread(f.img.rgb.data(), 1, f.img.rgb.size(), raw_);
                 if (rd != f.img.rgb.size()) return false;    // EOF (a trailing partial frame is dropped like the reference's reader)
                 f.source = cfg_.video_raw;
@@ -883,7 +840,7 @@ void run_stream(AppConfig cfg)
                     } else if (!cfg.save_dir.empty()) {
                         std::vector<y2h::DrawRecord> recs;
                         for (const OutDet &d : c.dets[(size_t)f]) recs.push_back({0, 0, d.class_id, d.prob, d.box.x, d.box.y, d.box.w, d.box.h});
-                        const y2h::Image im = y2h::plain_box_frame(fr.img.rgb.data(), fr.img.w, fr.img.h, host_frame_fmt(pixfmt), recs.data(),
+                        const y2h::Image im = y2h::plain_box_frame(fr.img.rgb.data(), fr.img.w, fr.img.h, y2cli::pix_host_frame(pixfmt), recs.data(),
                                                                    (int)recs.size(), last.classes);
                         char name[64];
                         std::snprintf(name, sizeof(name), "frame_%06d.ppm", infer_idx);

@@ -72,43 +72,39 @@ EXPORTS = [
     "yolo2_hip_zlib_huff_bound", "yolo2_hip_zlib_huff",
 ]
 
-# include/yolo2_hip.h YOLO2_PIX_*: the pixfmt argument of the _pix entries ("yuyv": packed YUYV 4:2:2, arrays uint8 [h][w][2])
-PIXFMTS = {"grey8": 1, "rgb24": 3, "yuyv": 0x56595559}
-# ... and the video formats, planar YUV 4:2:0: arrays uint8 [h * 3 / 2][w] - the Y plane's h rows, then h / 2 rows of chroma bytes.
-# A table of their own: PIXFMTS stays the camera formats' (tests pin it); every pixfmt= parameter takes a name of either.
-PIXFMTS_420 = {"nv12": 0x3231564E, "i420": 0x32315559}
-PLANAR_420 = tuple(PIXFMTS_420)
-# ... and packed RGB as most callers hold it: "bgr24" (OpenCV) arrays uint8 [h][w][3] of B G R; "rgba32" / "bgra32" (GUI toolkits, screen
-# capture) arrays uint8 [h][w][4] of R G B X / B G R X, the fourth byte never used.  A third table, for the same reason.
-PIXFMTS_PACKED = {"bgr24": 0x33524742, "rgba32": 0x34324241, "bgra32": 0x34325241}
-PACKED_RGB = tuple(PIXFMTS_PACKED)
-# ... and 8-bit raw Bayer, what a sensor without an ISP delivers: arrays uint8 [h][w], one byte per pixel, w and h at least 2; the name
-# is the top-left 2 x 2 block, row-major (V4L2 'RGGB' / 'BA81' / 'GRBG' / 'GBRG').  Demosaiced where the GPU fetches the pixel.
-PIXFMTS_BAYER = {"bayer_rggb8": 0x42474752, "bayer_bggr8": 0x31384142, "bayer_grbg8": 0x47425247, "bayer_gbrg8": 0x47524247}
-BAYER = tuple(PIXFMTS_BAYER)
+# include/yolo2_hip.h YOLO2_PIX_*: the pixfmt argument of the _pix entries, one row per format (csrc/pix_formats.hpp is the library's
+# list): (name, code, public table, trailing array dimension or None for [h][w] arrays, planar 4:2:0).  "yuyv": packed YUYV 4:2:2.
+# 420: planar YUV 4:2:0 video frames, arrays uint8 [h * 3 / 2][w] - the Y plane's h rows, then h / 2 rows of chroma bytes.  packed: "bgr24"
+# (OpenCV) B G R; "rgba32" / "bgra32" (GUI toolkits, screen capture) R G B X / B G R X, the fourth byte never used.  bayer: 8-bit raw
+# Bayer, one byte per pixel, w and h at least 2; the name is the top-left 2 x 2 block, row-major; demosaiced where the GPU fetches the pixel.
+_PIX_TABLE = (
+    ("grey8", 1, "camera", None, False), ("rgb24", 3, "camera", 3, False), ("yuyv", 0x56595559, "camera", 2, False),
+    ("nv12", 0x3231564E, "420", None, True), ("i420", 0x32315559, "420", None, True),
+    ("bgr24", 0x33524742, "packed", 3, False), ("rgba32", 0x34324241, "packed", 4, False), ("bgra32", 0x34325241, "packed", 4, False),
+    ("bayer_rggb8", 0x42474752, "bayer", None, False), ("bayer_bggr8", 0x31384142, "bayer", None, False),
+    ("bayer_grbg8", 0x47425247, "bayer", None, False), ("bayer_gbrg8", 0x47524247, "bayer", None, False),
+)
+_PIX = {r[0]: r for r in _PIX_TABLE}
+# The public tables (tests pin them; PIXFMTS stays the camera formats'): every pixfmt= parameter takes a name of any of them.
+PIXFMTS, PIXFMTS_420, PIXFMTS_PACKED, PIXFMTS_BAYER = ({r[0]: r[1] for r in _PIX_TABLE if r[2] == t} for t in ("camera", "420", "packed", "bayer"))
+PLANAR_420, PACKED_RGB, BAYER = tuple(PIXFMTS_420), tuple(PIXFMTS_PACKED), tuple(PIXFMTS_BAYER)
 LOOP_OUT_RGB24, LOOP_OUT_JPEG, LOOP_OUT_BGR24 = 0, 1, 0x33524742   # include/yolo2_hip.h YOLO2_LOOP_OUT_*
 LOOP_OUT_NV12, LOOP_OUT_I420 = 0x3231564E, 0x32315559                # ... the annotated frame as planar YUV 4:2:0
 
 
 def pix_code(pixfmt: str) -> int:
     """the YOLO2_PIX_* value of a pixfmt name"""
-    if pixfmt in PIXFMTS:
-        return PIXFMTS[pixfmt]
-    if pixfmt in PIXFMTS_420:
-        return PIXFMTS_420[pixfmt]
-    if pixfmt in PIXFMTS_PACKED:
-        return PIXFMTS_PACKED[pixfmt]
-    if pixfmt in PIXFMTS_BAYER:
-        return PIXFMTS_BAYER[pixfmt]
-    raise ValueError(f"pixfmt must be None or one of {tuple(PIXFMTS) + PLANAR_420 + PACKED_RGB + BAYER}, not {pixfmt!r}")
+    if pixfmt in _PIX:
+        return _PIX[pixfmt][1]
+    raise ValueError(f"pixfmt must be None or one of {tuple(_PIX)}, not {pixfmt!r}")
 
 
 def _pix_code(pixfmt, imgs) -> int:
     """the entries' pixfmt argument for a list of contiguous uint8 arrays, whose shapes must be that format's"""
     code = pix_code(pixfmt)
-    last = {"grey8": None, "rgb24": 3, "yuyv": 2, "nv12": None, "i420": None, "bgr24": 3, "rgba32": 4, "bgra32": 4}.get(pixfmt)   # (Bayer: [h][w])
+    last, planar = _PIX[pixfmt][3:]
     for im in imgs:
-        if pixfmt in PLANAR_420 and (im.ndim != 2 or im.shape[0] % 3):
+        if planar and (im.ndim != 2 or im.shape[0] % 3):
             raise ValueError(f"a {pixfmt} image is uint8 [h * 3 / 2][w] with h even (rows a multiple of 3), not {im.shape}")
         if (im.ndim != 2 if last is None else im.ndim != 3 or im.shape[2] != last):
             raise ValueError(f"a {pixfmt} image is uint8 [h][w]{'' if last is None else f'[{last}]'}, not {im.shape}")
