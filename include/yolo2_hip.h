@@ -624,6 +624,10 @@ int yolo2_hip_jpeg_encode_rgb24(uint64_t rgb_dev, int w, int h, int quality, uin
  * 2x2 - and restart intervals of R MCUs - DRI in front of SOS, FF D0..D7 between the intervals, DC predictors zero again.  Every
  * JPEG-writing entry honours them: the annotate entries and the loop entries those of their context, yolo2_hip_jpeg_encode_rgb24
  * the process-wide set (ctx = NULL).  y2h_write_jpg_rgb24_ex is the same encoder on the host.
+ * Option "jpeg_optimize" = 0 | 1 (read per call, with any (subsample, restart); unset: nothing above changes): the four Huffman
+ * tables and the DHT segment are made on the GPU from the frame's own symbol counts (csrc/jpeg_opt.hpp) - code
+ * lengths at most 16 bits (AC) / 11 (DC), so every bound above holds as it is - and a frame whose own tables would not make it
+ * smaller is the standard stream, byte for byte.  y2h_write_jpg_rgb24_opt is the same encoder on the host.
  * yolo2_hip_jpeg_bound_ex: the most bytes a w x h stream of a mode can take (its header, twice the scan's bound of 1660 bits per
  * block, 3 bytes per interval, 2); 0 for a size or a mode the entries refuse.  (0, 0) is yolo2_hip_jpeg_bound. */
 size_t yolo2_hip_jpeg_bound_ex(int w, int h, int subsample, int restart);

@@ -80,9 +80,11 @@ constexpr int kHeaderHeightAt = 159, kHeaderWidthAt = 161;
 //   restart = R (MCUs per interval, 1..65535): DRI (FF DD 00 04 Rhi Rlo) in front of SOS; after every R MCUs except at the scan's end
 //     the last partial byte is filled with ones, FF D0+(k & 7) follows for interval k = 0, 1, ... and the DC predictors are zero
 //     again.  Stuffing applies to entropy bytes only, never to the marker.
+//   optimize = 1 (with either of the above or neither): the Huffman tables and the DHT segment are the frame's own, or the standard
+//     ones where those cost no more - jpeg_opt.hpp, included at the end of this file, states it.
 constexpr int kHeaderLumaSamplingAt = 165, kHeaderSosAt = kHeaderBytes - 14, kDriBytes = 6, kRestartMax = 65535;
 
-inline bool mode_ok(int subsample, int restart) { return (subsample == 0 || subsample == 420) && restart >= 0 && restart <= kRestartMax; }
+inline bool mode_ok(int subsample, int restart, int optimize = 0) { return (optimize == 0 || optimize == 1) && (subsample == 0 || subsample == 420) && restart >= 0 && restart <= kRestartMax; }
 Y2T_HD inline int mcu_pixels(int subsample) { return subsample == 420 ? 16 : 8; }   // each way
 Y2T_HD inline int mcu_blocks(int subsample) { return subsample == 420 ? 6 : 3; }
 Y2T_HD inline bool block_is_luma(int subsample, int k) { return subsample == 420 ? k < 4 : k == 0; }   // k: the block's place in its MCU
@@ -191,3 +193,5 @@ inline size_t stream_bound_ex(int w, int h, int subsample, int restart)
 }
 
 }  // namespace y2j
+
+#include "jpeg_opt.hpp"

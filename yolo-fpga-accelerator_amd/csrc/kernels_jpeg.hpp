@@ -20,7 +20,9 @@
 //   k_jpeg_scan_segs   D   a workgroup per frame: exclusive scan of the segment counts, the stream's size
 //   k_jpeg_place       D   one workgroup: where each frame's stream starts in the packed output (sum of min(size, capacity))
 //   k_jpeg_emit        D   header, stuffed bytes (a zero after every 0xFF) and FF D9, nothing at or beyond the frame's capacity
-// The tables (fdtbl, code words, header) come from csrc/jpeg_tables.hpp on the host and lead the chunk's table.
+// The tables (fdtbl, code words, header) come from csrc/jpeg_tables.hpp on the host and lead the chunk's table.  Stages B, C and the
+// emit kernel are templates: <false> is the above; <true> ("optimize" at the end of this file) takes the code words and the header
+// from the frame's JpegOptFrame.
 //
 // Launched from yolo2_jpeg.hip only.
 #pragma once
@@ -54,6 +56,13 @@ struct JpegState {
     unsigned long long ff;        // 0xFF bytes in it
     unsigned long long size;      // kHeaderBytes + ubytes + ff + 2
     unsigned long long out_off;   // where the stream starts in the packed output
+};
+
+// optimize = 1 (jpeg_opt.hpp): what k_jpeg_opt_tables leaves per frame for the <true> forms of stages B, C and D
+struct JpegOptFrame {
+    uint32_t code[4][256];                  // the frame's code words, or Tables::code where it falls back
+    uint32_t head_len, used;                // the header's bytes; 1: the frame's own tables
+    uint8_t header[y2j::kOptHeaderSlot];    // the frame's header, size and sampling in place
 };
 
 constexpr int kJpegBlocks = 128;      // blocks (= lanes) per workgroup of stages A, B and C
@@ -181,22 +190,28 @@ struct JpegBlock {
     __device__ inline int at(int i) const { return (int)(int16_t)(pk[i >> 1] >> (16 * (i & 1))); }   // (i is a constant after unrolling)
 };
 
-__device__ inline void jpeg_stage_codes(uint32_t *s_code, const uint8_t *table, int tid, int threads)
+// the code words into LDS: the chunk's (kOpt false: opt is not read), or the frame's own
+template <bool kOpt>
+__device__ inline void jpeg_stage_codes(uint32_t *s_code, const uint8_t *table, const JpegOptFrame *opt, int frame, int tid, int threads)
 {
-    const uint32_t *code = &reinterpret_cast<const JpegHeader *>(table)->t.code[0][0];
+    const uint32_t *code = kOpt ? &opt[frame].code[0][0] : &reinterpret_cast<const JpegHeader *>(table)->t.code[0][0];
     for (int i = tid; i < 4 * 256; i += threads) s_code[i] = code[i];
 }
+// the DC predictor of block blk: the DC level `back` blocks before it, zero for back = 0 (stages B and C and k_jpeg_hist)
+__device__ inline int jpeg_dc_pred(const int16_t *coef, size_t blk, int back) { return back ? (int)coef[(blk - back) * 64] : 0; }
 
 // grid (ceil(max n_blk / kJpegBlocks), frames)
+template <bool kOpt>
 __global__ __launch_bounds__(kJpegBlocks) void k_jpeg_lengths(const uint8_t *__restrict__ table, const int16_t *__restrict__ coef,
-                                                              uint32_t *__restrict__ blk_off, uint32_t *__restrict__ wg_sum)
+                                                              uint32_t *__restrict__ blk_off, uint32_t *__restrict__ wg_sum,
+                                                              const JpegOptFrame *__restrict__ opt)
 {
     __shared__ uint32_t s_code[4 * 256];
     __shared__ uint32_t s_scan[kJpegBlocks];
     const JpegFrame fr = jpeg_frame(table, blockIdx.y);
     if (blockIdx.x >= fr.n_wg) return;   // (the whole workgroup)
     const int tid = threadIdx.x;
-    jpeg_stage_codes(s_code, table, tid, kJpegBlocks);
+    jpeg_stage_codes<kOpt>(s_code, table, opt, blockIdx.y, tid, kJpegBlocks);
     __syncthreads();
     const int b = (int)blockIdx.x * kJpegBlocks + tid;
     uint32_t bits = 0;
@@ -205,7 +220,7 @@ __global__ __launch_bounds__(kJpegBlocks) void k_jpeg_lengths(const uint8_t *__r
         const uint32_t *dc = s_code + (b % 3 ? 2 : 0) * 256, *ac = dc + 256;
         JpegBlock c;
         c.load(coef, blk);
-        const int pred = b >= 3 ? (int)coef[(blk - 3) * 64] : 0;
+        const int pred = jpeg_dc_pred(coef, blk, b >= 3 ? 3 : 0);
         const int cat = jpeg_category(c.at(0) - pred);
         bits = (dc[cat] >> 16) + cat;
         int run = 0;
@@ -270,16 +285,18 @@ __device__ inline void jpeg_put(uint32_t *s_bits, uint32_t &pos, uint32_t v, int
 __device__ inline uint32_t jpeg_extra(int v, int cat) { return (uint32_t)(v < 0 ? v - 1 : v) & ((1u << cat) - 1u); }
 
 // grid (ceil(max n_blk / kJpegBlocks), frames)
+template <bool kOpt>
 __global__ __launch_bounds__(kJpegBlocks) void k_jpeg_pack(const uint8_t *__restrict__ table, const int16_t *__restrict__ coef,
                                                            const uint32_t *__restrict__ blk_off, const uint32_t *__restrict__ wg_sum,
-                                                           const unsigned long long *__restrict__ wg_base, uint8_t *__restrict__ us_base)
+                                                           const unsigned long long *__restrict__ wg_base, uint8_t *__restrict__ us_base,
+                                                           const JpegOptFrame *__restrict__ opt)
 {
     __shared__ uint32_t s_code[4 * 256];
     __shared__ uint32_t s_bits[kJpegPackDwords];
     const JpegFrame fr = jpeg_frame(table, blockIdx.y);
     if (blockIdx.x >= fr.n_wg) return;   // (the whole workgroup)
     const int tid = threadIdx.x;
-    jpeg_stage_codes(s_code, table, tid, kJpegBlocks);
+    jpeg_stage_codes<kOpt>(s_code, table, opt, blockIdx.y, tid, kJpegBlocks);
     const unsigned long long lo = wg_base[fr.wg0 + blockIdx.x], hi = lo + wg_sum[fr.wg0 + blockIdx.x];
     // the frame's last group also owns the ones that fill the last byte
     const int fill = blockIdx.x + 1 == fr.n_wg ? (int)((8 - (hi & 7)) & 7) : 0;
@@ -295,7 +312,7 @@ __global__ __launch_bounds__(kJpegBlocks) void k_jpeg_pack(const uint8_t *__rest
         JpegBlock c;
         c.load(coef, blk);
         uint32_t pos = first + blk_off[blk];
-        const int pred = b >= 3 ? (int)coef[(blk - 3) * 64] : 0;
+        const int pred = jpeg_dc_pred(coef, blk, b >= 3 ? 3 : 0);
         const int diff = c.at(0) - pred, cat = jpeg_category(diff);
         jpeg_put(s_bits, pos, ((dc[cat] & 0xffffu) << cat) | jpeg_extra(diff, cat), (int)(dc[cat] >> 16) + cat);
         int run = 0;
@@ -418,9 +435,10 @@ __global__ __launch_bounds__(kJpegScan) void k_jpeg_place(const uint8_t *__restr
 }
 
 // grid (some, frames), as k_jpeg_count_ff
+template <bool kOpt>
 __global__ __launch_bounds__(kJpegSegThreads) void k_jpeg_emit(const uint8_t *__restrict__ table, const uint8_t *__restrict__ us_base,
                                                                const JpegState *__restrict__ state, const uint32_t *__restrict__ seg_base,
-                                                               uint8_t *__restrict__ out_base)
+                                                               uint8_t *__restrict__ out_base, const JpegOptFrame *__restrict__ opt)
 {
     __shared__ uint32_t s_scan[kJpegSegThreads];
     const JpegHeader *hd = reinterpret_cast<const JpegHeader *>(table);
@@ -428,13 +446,16 @@ __global__ __launch_bounds__(kJpegSegThreads) void k_jpeg_emit(const uint8_t *__
     const JpegState st = state[blockIdx.y];
     uint8_t *out = out_base + st.out_off;
     const int tid = threadIdx.x;
+    const int head = kOpt ? (int)opt[blockIdx.y].head_len : y2j::kHeaderBytes;
     if (blockIdx.x == 0) {
-        for (int i = tid; i < y2j::kHeaderBytes; i += kJpegSegThreads) {
-            uint8_t v = hd->t.header[i];
-            if (i == y2j::kHeaderHeightAt) v = (uint8_t)(fr.h >> 8);
-            if (i == y2j::kHeaderHeightAt + 1) v = (uint8_t)fr.h;
-            if (i == y2j::kHeaderWidthAt) v = (uint8_t)(fr.w >> 8);
-            if (i == y2j::kHeaderWidthAt + 1) v = (uint8_t)fr.w;
+        for (int i = tid; i < head; i += kJpegSegThreads) {
+            uint8_t v = kOpt ? opt[blockIdx.y].header[i] : hd->t.header[i];
+            if (!kOpt) {
+                if (i == y2j::kHeaderHeightAt) v = (uint8_t)(fr.h >> 8);
+                if (i == y2j::kHeaderHeightAt + 1) v = (uint8_t)fr.h;
+                if (i == y2j::kHeaderWidthAt) v = (uint8_t)(fr.w >> 8);
+                if (i == y2j::kHeaderWidthAt + 1) v = (uint8_t)fr.w;
+            }
             if ((unsigned long long)i < fr.cap) out[i] = v;
         }
         if (tid < 2 && st.size - 2 + tid < fr.cap) out[st.size - 2 + tid] = tid ? 0xD9 : 0xFF;   // EOI
@@ -445,7 +466,7 @@ __global__ __launch_bounds__(kJpegSegThreads) void k_jpeg_emit(const uint8_t *__
         const unsigned long long at = (unsigned long long)seg * kJpegSegBytes + tid * 16;
         const int ff = jpeg_seg_load(us_base + fr.us_off, st.ubytes, at, w);
         const uint32_t incl = jpeg_scan_incl<kJpegSegThreads>((uint32_t)ff, s_scan, tid);
-        unsigned long long o = (unsigned long long)y2j::kHeaderBytes + at + seg_base[fr.seg0 + seg] + (incl - (uint32_t)ff);
+        unsigned long long o = (unsigned long long)head + at + seg_base[fr.seg0 + seg] + (incl - (uint32_t)ff);
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
             const uint8_t v = (uint8_t)(w[i >> 2] >> (8 * (i & 3)));
@@ -636,16 +657,18 @@ __device__ inline JpegPlace jpeg_place_of(const JpegFrame &fr, int b)
 }
 
 // grid (ceil(max n_blk / kJpegBlocks), frames)
+template <bool kOpt>
 __global__ __launch_bounds__(kJpegBlocks) void k_jpeg_lengths_rst(const uint8_t *__restrict__ table, const int16_t *__restrict__ coef,
                                                                   uint32_t *__restrict__ blk_off, uint32_t *__restrict__ blk_post,
-                                                                  uint32_t *__restrict__ wg_sum, uint32_t *__restrict__ wg_post)
+                                                                  uint32_t *__restrict__ wg_sum, uint32_t *__restrict__ wg_post,
+                                                                  const JpegOptFrame *__restrict__ opt)
 {
     __shared__ uint32_t s_code[4 * 256];
     __shared__ uint32_t s_pre[kJpegBlocks], s_post[kJpegBlocks], s_seen[kJpegBlocks];
     const JpegFrame fr = jpeg_frame(table, blockIdx.y);
     if (blockIdx.x >= fr.n_wg) return;   // (the whole workgroup)
     const int tid = threadIdx.x;
-    jpeg_stage_codes(s_code, table, tid, kJpegBlocks);
+    jpeg_stage_codes<kOpt>(s_code, table, opt, blockIdx.y, tid, kJpegBlocks);
     __syncthreads();
     const int b = (int)blockIdx.x * kJpegBlocks + tid;
     JpegRun<uint32_t> own = {0u, 0u, 0u};
@@ -655,7 +678,7 @@ __global__ __launch_bounds__(kJpegBlocks) void k_jpeg_lengths_rst(const uint8_t 
         const uint32_t *dc = s_code + (pl.luma ? 0 : 2) * 256, *ac = dc + 256;
         JpegBlock c;
         c.load(coef, blk);
-        const int pred = pl.pred_back ? (int)coef[(blk - pl.pred_back) * 64] : 0;
+        const int pred = jpeg_dc_pred(coef, blk, pl.pred_back);
         const int cat = jpeg_category(c.at(0) - pred);
         uint32_t bits = (dc[cat] >> 16) + cat;
         int run = 0;
@@ -723,18 +746,19 @@ __global__ __launch_bounds__(kJpegScan) void k_jpeg_scan_groups_rst(const uint8_
 }
 
 // grid (ceil(max n_blk / kJpegBlocks), frames)
+template <bool kOpt>
 __global__ __launch_bounds__(kJpegBlocks) void k_jpeg_pack_rst(const uint8_t *__restrict__ table, const int16_t *__restrict__ coef,
                                                                const uint32_t *__restrict__ blk_off, const uint32_t *__restrict__ blk_post,
                                                                const uint32_t *__restrict__ wg_sum, const uint32_t *__restrict__ wg_post,
                                                                const unsigned long long *__restrict__ wg_base, uint8_t *__restrict__ us_base,
-                                                               uint32_t *__restrict__ rst_off)
+                                                               uint32_t *__restrict__ rst_off, const JpegOptFrame *__restrict__ opt)
 {
     __shared__ uint32_t s_code[4 * 256];
     __shared__ uint32_t s_bits[kJpegPackDwordsRst];
     const JpegFrame fr = jpeg_frame(table, blockIdx.y);
     if (blockIdx.x >= fr.n_wg) return;   // (the whole workgroup)
     const int tid = threadIdx.x;
-    jpeg_stage_codes(s_code, table, tid, kJpegBlocks);
+    jpeg_stage_codes<kOpt>(s_code, table, opt, blockIdx.y, tid, kJpegBlocks);
     const unsigned long long lo = wg_base[fr.wg0 + blockIdx.x], d0 = lo >> 5;
     // in the image bit 0 is the top bit of dword d0 of the stream: a multiple of 32 away, so rounding up to a byte is the same there
     const uint32_t first = (uint32_t)(lo - (d0 << 5));
@@ -752,7 +776,7 @@ __global__ __launch_bounds__(kJpegBlocks) void k_jpeg_pack_rst(const uint8_t *__
         c.load(coef, blk);
         uint32_t pos = jpeg_run_unpack(blk_off[blk], blk_post[blk]).at(first);
         if (pl.starts) rst_off[fr.rst0 + pl.interval] = (uint32_t)(((d0 << 5) + pos) >> 3);   // (the entries refuse frames whose bound passes 2^31)
-        const int pred = pl.pred_back ? (int)coef[(blk - pl.pred_back) * 64] : 0;
+        const int pred = jpeg_dc_pred(coef, blk, pl.pred_back);
         const int diff = c.at(0) - pred, cat = jpeg_category(diff);
         jpeg_put(s_bits, pos, ((dc[cat] & 0xffffu) << cat) | jpeg_extra(diff, cat), (int)(dc[cat] >> 16) + cat);
         int run = 0;
@@ -807,9 +831,11 @@ __device__ inline unsigned jpeg_interval_of(const uint32_t *__restrict__ rst, un
 }
 
 // grid (some, frames), as k_jpeg_count_ff
+template <bool kOpt>
 __global__ __launch_bounds__(kJpegSegThreads) void k_jpeg_emit_rst(const uint8_t *__restrict__ table, const uint8_t *__restrict__ us_base,
                                                                    const JpegState *__restrict__ state, const uint32_t *__restrict__ seg_base,
-                                                                   const uint32_t *__restrict__ rst_off, uint8_t *__restrict__ out_base)
+                                                                   const uint32_t *__restrict__ rst_off, uint8_t *__restrict__ out_base,
+                                                                   const JpegOptFrame *__restrict__ opt)
 {
     __shared__ uint32_t s_scan[kJpegSegThreads];
     __shared__ unsigned s_iv[2];
@@ -818,10 +844,11 @@ __global__ __launch_bounds__(kJpegSegThreads) void k_jpeg_emit_rst(const uint8_t
     const JpegState st = state[blockIdx.y];
     uint8_t *out = out_base + st.out_off;
     const uint32_t *rst = rst_off + fr.rst0;
-    const int tid = threadIdx.x, head = y2j::header_bytes(fr.restart);
+    const int tid = threadIdx.x, head = kOpt ? (int)opt[blockIdx.y].head_len : y2j::header_bytes(fr.restart);
     if (blockIdx.x == 0) {
         for (int i = tid; i < head; i += kJpegSegThreads)
-            if ((unsigned long long)i < fr.cap) out[i] = y2j::header_byte(hd->t.header, i, fr.w, fr.h, fr.subsample, fr.restart);
+            if ((unsigned long long)i < fr.cap)
+                out[i] = kOpt ? opt[blockIdx.y].header[i] : y2j::header_byte(hd->t.header, i, fr.w, fr.h, fr.subsample, fr.restart);
         if (tid < 2 && st.size - 2 + tid < fr.cap) out[st.size - 2 + tid] = tid ? 0xD9 : 0xFF;   // EOI
     }
     const unsigned nseg = (unsigned)((st.ubytes + kJpegSegBytes - 1) / kJpegSegBytes);
@@ -868,6 +895,179 @@ __global__ __launch_bounds__(kJpegSegThreads) void k_jpeg_emit_rst(const uint8_t
         }
         __syncthreads();
     }
+}
+
+// ================================================================================================ optimize (jpeg_opt.hpp)
+//
+// optimize = 1 puts three launches between stage A and stage B and runs the <true> forms of the kernels that read code words or the
+// header; the transforms, k_jpeg_count_ff, the scans and k_jpeg_place run as they are.
+//   k_jpeg_hist_clear      the chunk's counts to zero (a kernel, so that the sequence can be captured into a graph)
+//   k_jpeg_hist            a workgroup per kJpegBlocks blocks, a lane per block (stage B's split and its jpeg_place_of / jpeg_dc_pred):
+//                          the block's symbols counted into the lane's WAVEFRONT's copy of the 536 bins in LDS - end-of-block, sixteen
+//                          zeros and the small (run, size) symbols are hit by nearly every lane, and one copy would serialise all of
+//                          them - then the copies are added up and the non-zero sums go to hist[frame] with integer atomics
+//   k_jpeg_opt_tables      a workgroup per frame, a wavefront per table: all lanes rank-sort the (count, symbol) keys (distinct, so
+//                          the ranks are the host's order), lane 0 runs the tree, the limit and the per-length firsts of jpeg_opt.hpp
+//                          with every variably indexed array in LDS; after a barrier all four wavefronts add up both costs, and
+//                          after the next every lane knows the decision: the frame's code words (each lane its symbols' rank within
+//                          their length) or the standard ones go to JpegOptFrame, the DHT payload is put together in LDS and the
+//                          header's bytes are written by all lanes
+//   k_jpeg_sizes_opt       the sizes k_jpeg_scan_segs (and k_jpeg_sizes_rst) left, with the frame's header length in place of the
+//                          standard one
+// Resources (-Rpass-analysis=kernel-resource-usage, gfx950): DESIGN.md 4.10.3.
+
+constexpr int kJpegHistWaves = kJpegBlocks / 64;
+constexpr int kJpegOptThreads = 4 * 64;   // a wavefront per table
+
+// grid (ceil(n / kJpegScan)), n = frames * kOptHistBins
+__global__ __launch_bounds__(kJpegScan) void k_jpeg_hist_clear(uint32_t *__restrict__ hist, int n)
+{
+    const int i = (int)(blockIdx.x * kJpegScan + threadIdx.x);
+    if (i < n) hist[i] = 0u;
+}
+
+// grid (ceil(max n_blk / kJpegBlocks), frames)
+__global__ __launch_bounds__(kJpegBlocks) void k_jpeg_hist(const uint8_t *__restrict__ table, const int16_t *__restrict__ coef,
+                                                           uint32_t *__restrict__ hist)
+{
+    __shared__ uint32_t s_h[kJpegHistWaves][y2j::kOptHistBins];
+    const JpegFrame fr = jpeg_frame(table, blockIdx.y);
+    if (blockIdx.x >= fr.n_wg) return;   // (the whole workgroup)
+    const int tid = threadIdx.x;
+    for (int i = tid; i < kJpegHistWaves * y2j::kOptHistBins; i += kJpegBlocks) (&s_h[0][0])[i] = 0u;
+    __syncthreads();
+    const int b = (int)blockIdx.x * kJpegBlocks + tid;
+    if (b < fr.n_blk) {
+        const size_t blk = (size_t)fr.blk0 + b;
+        const JpegPlace pl = jpeg_place_of(fr, b);
+        uint32_t *dc = s_h[tid >> 6] + y2j::opt_hist_at(pl.luma ? y2j::kDcLuma : y2j::kDcChroma);
+        uint32_t *ac = s_h[tid >> 6] + y2j::opt_hist_at(pl.luma ? y2j::kAcLuma : y2j::kAcChroma);
+        JpegBlock c;
+        c.load(coef, blk);
+        atomicAdd(&dc[jpeg_category(c.at(0) - jpeg_dc_pred(coef, blk, pl.pred_back))], 1u);
+        int run = 0;
+#pragma unroll
+        for (int i = 1; i < 64; ++i) {
+            const int v = c.at(i);
+            if (v == 0) {
+                ++run;
+            } else {
+                if (run >= 16) atomicAdd(&ac[0xF0], (uint32_t)(run >> 4));
+                atomicAdd(&ac[((run & 15) << 4) | jpeg_category(v)], 1u);
+                run = 0;
+            }
+        }
+        if (run) atomicAdd(&ac[0], 1u);
+    }
+    __syncthreads();
+    for (int i = tid; i < y2j::kOptHistBins; i += kJpegBlocks) {
+        uint32_t sum = 0;
+#pragma unroll
+        for (int k = 0; k < kJpegHistWaves; ++k) sum += s_h[k][i];
+        if (sum) atomicAdd(&hist[(size_t)blockIdx.y * y2j::kOptHistBins + i], sum);
+    }
+}
+
+// grid (frames)
+__global__ __launch_bounds__(kJpegOptThreads) void k_jpeg_opt_tables(const uint8_t *__restrict__ table, const uint32_t *__restrict__ hist,
+                                                                     JpegOptFrame *__restrict__ opt)
+{
+    __shared__ y2j::OptScratch s_w[4];
+    __shared__ uint32_t s_hist[y2j::kOptHistBins];
+    __shared__ uint8_t s_dht[y2j::kDhtStdPayload];
+    __shared__ uint32_t s_n[4], s_used[4];
+    __shared__ unsigned long long s_total[4], s_cost[2];
+    const JpegHeader *hd = reinterpret_cast<const JpegHeader *>(table);
+    const JpegFrame fr = jpeg_frame(table, blockIdx.x);
+    const int tid = threadIdx.x, t = tid >> 6, lane = tid & 63;   // t: the wavefront's table, kDcLuma .. kAcChroma
+    y2j::OptScratch &w = s_w[t];
+    const int nsym = y2j::opt_syms(t);
+    for (int i = tid; i < y2j::kOptHistBins; i += kJpegOptThreads) s_hist[i] = hist[(size_t)blockIdx.x * y2j::kOptHistBins + i];
+    if (tid < 4) { s_n[tid] = 0u; s_used[tid] = 0u; s_total[tid] = 0ull; }
+    if (tid < 2) s_cost[tid] = 0ull;
+    for (int q = lane; q <= y2j::kOptReserved; q += 64) w.len[q] = 0;
+    __syncthreads();
+    const uint32_t *ht = s_hist + y2j::opt_hist_at(t);
+    {
+        unsigned long long total = 0;
+        uint32_t used = 0;
+        for (int q = lane; q < nsym; q += 64) { total += ht[q]; used += ht[q] != 0u; }
+        atomicAdd(&s_total[t], total);
+        atomicAdd(&s_n[t], used);
+    }
+    __syncthreads();
+    const bool built = s_total[t] < y2j::kOptCountLimit;   // (a count fits its key)
+    const int n = 1 + (int)s_n[t];                         // the keys: the symbols in use and the reserved one, the smallest
+    if (built) {
+        for (int q = lane; q < nsym; q += 64) {
+            if (!ht[q]) continue;
+            const uint32_t key = (ht[q] << 9) | (uint32_t)q;
+            int rank = 1;
+            for (int r = 0; r < nsym; ++r) rank += ht[r] != 0u && ((ht[r] << 9) | (uint32_t)r) < key;
+            w.h.key[rank] = key;
+        }
+        if (lane == 0) w.h.key[0] = (uint32_t)y2j::kOptReserved;
+    }
+    __syncthreads();
+    if (built && lane == 0) {
+        if (n >= 2) y2j::opt_lengths(w, n, y2j::opt_maxlen(t));
+        s_used[t] = (uint32_t)y2j::opt_canon_prepare(w, nsym);
+    }
+    __syncthreads();
+    {   // both costs: the code bits of the frame's symbols under either table set
+        unsigned long long own = 0, standard = 0;
+        for (int q = lane; q < nsym; q += 64) {
+            own += (unsigned long long)ht[q] * w.len[q];
+            standard += (unsigned long long)ht[q] * (hd->t.code[t][q] >> 16);
+        }
+        atomicAdd(&s_cost[0], own);
+        atomicAdd(&s_cost[1], standard);
+    }
+    __syncthreads();
+    bool use = true;
+    int payload = 0, off = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        use = use && s_total[k] < y2j::kOptCountLimit;
+        if (k < t) off += 17 + (int)s_used[k];
+        payload += 17 + (int)s_used[k];
+    }
+    use = use && payload <= y2j::kDhtStdPayload;   // (more symbols than T.81 has: not from 8-bit pixels)
+    use = use && s_cost[0] + 8ull * (unsigned)payload < s_cost[1] + 8ull * y2j::kDhtStdPayload;   // (the same for every lane)
+    JpegOptFrame &of = opt[blockIdx.x];
+    if (use) {
+        if (lane == 0) s_dht[off] = (uint8_t)y2j::opt_dht_id(t);
+        if (lane >= 1 && lane <= 16) s_dht[off + lane] = (uint8_t)w.h.count[lane];
+    }
+    for (int q = lane; q < 256; q += 64) {
+        uint32_t code = use ? 0u : hd->t.code[t][q];
+        if (use && q < nsym && w.len[q]) {
+            int place;
+            code = y2j::opt_canon_symbol(w, q, &place);
+            s_dht[off + 17 + place] = (uint8_t)q;
+        }
+        of.code[t][q] = code;
+    }
+    __syncthreads();
+    const int head = use ? y2j::opt_header_len(payload, fr.restart) : y2j::header_bytes(fr.restart);
+    for (int i = tid; i < head; i += kJpegOptThreads)
+        of.header[i] = use ? y2j::opt_header_byte(hd->t.header, i, fr.w, fr.h, fr.subsample, fr.restart, s_dht, payload)
+                           : y2j::header_byte(hd->t.header, i, fr.w, fr.h, fr.subsample, fr.restart);
+    if (tid == 0) {
+        of.head_len = (uint32_t)head;
+        of.used = use ? 1u : 0u;
+    }
+}
+
+// grid (ceil(frames / kJpegScan))
+__global__ __launch_bounds__(kJpegScan) void k_jpeg_sizes_opt(const uint8_t *__restrict__ table, const JpegOptFrame *__restrict__ opt,
+                                                              JpegState *__restrict__ state, unsigned long long *__restrict__ sizes, int nf)
+{
+    const int f = (int)(blockIdx.x * kJpegScan + threadIdx.x);
+    if (f >= nf) return;
+    const unsigned long long size = state[f].size - (unsigned)y2j::header_bytes(jpeg_frame(table, f).restart) + opt[f].head_len;
+    state[f].size = size;
+    sizes[f] = size;
 }
 
 }  // namespace y2

@@ -83,6 +83,7 @@ struct Y2Options {
                                   // 16..4096 (0: one lane per segment, today's launches); read per call
     int jpeg_subsample = 0;       // the GPU JPEG encoder's stream: 420 = MCUs of 16 x 16 with chroma halved both ways (0: none, the reference's
     int jpeg_restart = 0;         // stream); MCUs per restart interval, 1..65535 (0: no markers); both read per call
+    int jpeg_optimize = 0;        // 1: Huffman tables from the frame's own symbol counts, built on the GPU; read per call
     int stamp_layer = -1;
     int f16_skip = 0;             // DIAGNOSTIC (results wrong by construction): bit mask of fp16 launches left out of the table, to measure
                                   // what a launch costs INSIDE the two-lane step: 1 = 1x1 layers 5 and 9, 2 = layer 0, 4 = layers 2/4/6,

@@ -14,12 +14,13 @@ struct Y2JpegFrameIn {
     size_t cap;       // the caller's room for its stream
 };
 // The stream's mode (csrc/jpeg_tables.hpp): subsample 0 | 420, restart 0..65535 MCUs per interval.  (0, 0) is the reference's stream
-// and the eight launches that have always made it.
+// and the eight launches that have always made it.  optimize 0 | 1 (csrc/jpeg_opt.hpp), with any of them: Huffman tables per frame; 0
+// leaves the launches and the work area of (subsample, restart) as they are.
 struct Y2JpegMode {
-    int subsample = 0, restart = 0;
+    int subsample = 0, restart = 0, optimize = 0;
     bool plain() const { return !subsample && !restart; }
 };
-// Options jpeg_subsample / jpeg_restart as they stand now: of the context, or (c == nullptr) of the process-wide set.  Read per call.
+// Options jpeg_subsample / jpeg_restart / jpeg_optimize as they stand now: of the context, or (c == nullptr) of the process-wide set.  Read per call.
 Y2JpegMode y2_jpeg_mode(const yolo2_hip_ctx *c);
 struct Y2JpegPlan {
     int nf = 0;
@@ -28,6 +29,7 @@ struct Y2JpegPlan {
     size_t work_bytes = 0;    // the work area: everything below, at these offsets
     size_t coef = 0, blk_off = 0, wg_sum = 0, wg_base = 0, us = 0, seg_ff = 0, seg_base = 0, state = 0, sizes = 0;
     size_t blk_post = 0, wg_post = 0, rst_off = 0;   // the modes' arrays (empty in mode (0, 0))
+    size_t hist = 0, opt = 0;                        // optimize's: symbol counts and JpegOptFrame per frame (empty without it)
     size_t out_bytes = 0;     // sum of min(cap, bound): the most the packed output can hold
     unsigned grid_blk = 0, grid_seg = 0, grid_mcu = 0;   // grid_mcu: k_jpeg_transform420's
 };

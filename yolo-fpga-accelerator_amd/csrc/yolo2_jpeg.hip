@@ -1,6 +1,7 @@
 // yolo2_jpeg.hip -- RGB24 frames in device memory -> JPEG streams (include/yolo2_hip.h, "annotated frames as JPEG"): the stream the
 // reference's MJPEG streamer sends for a frame, byte for byte, made by the eight launches of kernels_jpeg.hpp - or, under options
-// jpeg_subsample / jpeg_restart, the library's own 4:2:0 and restart-interval forms of it by the kernels of "the modes" there.  The
+// jpeg_subsample / jpeg_restart, the library's own 4:2:0 and restart-interval forms of it by the kernels of "the modes" there, and
+// under jpeg_optimize any of them with Huffman tables made per frame on the GPU ("optimize" there, csrc/jpeg_opt.hpp).  The
 // host side here makes the tables (jpeg_tables.hpp), lays the work area out and enqueues; nothing is read back between the stages.
 // The batched entry that paints and encodes lives with the painter (yolo2_draw.hip) and comes through y2_jpeg.hpp.
 #include "y2_internal.hpp"
@@ -21,6 +22,7 @@ Y2JpegMode y2_jpeg_mode(const yolo2_hip_ctx *c)
     Y2JpegMode m;
     m.subsample = o.jpeg_subsample;
     m.restart = o.jpeg_restart;
+    m.optimize = o.jpeg_optimize;
     return m;
 }
 
@@ -110,6 +112,10 @@ int y2_jpeg_plan(const Y2JpegFrameIn *frames, int nf, Y2JpegMode mode, Y2JpegPla
         p.wg_post = take(groups * sizeof(uint32_t));
         p.rst_off = take(ints * sizeof(uint32_t));
     }
+    if (mode.optimize) {
+        p.hist = take((size_t)nf * y2j::kOptHistBins * sizeof(uint32_t));
+        p.opt = take((size_t)nf * sizeof(JpegOptFrame));
+    }
     p.work_bytes = at;
     p.grid_blk = max_groups;
     p.grid_seg = std::min(max_segs, 64u);   // (segments beyond a workgroup's first are taken in a loop; real streams are far below the bound)
@@ -150,15 +156,48 @@ int y2_jpeg_enqueue(const Y2JpegPlan &p, const uint8_t *table_dev, const uint8_t
     JpegState *state = reinterpret_cast<JpegState *>(work + p.state);
     unsigned long long *sizes = reinterpret_cast<unsigned long long *>(work + p.sizes);
     const dim3 per_blk(p.grid_blk, (unsigned)p.nf), per_seg(p.grid_seg, (unsigned)p.nf), per_frame((unsigned)p.nf);
-    if (p.mode.plain()) {
+    const dim3 frames_scan(((unsigned)p.nf + kJpegScan - 1) / kJpegScan);
+    const JpegOptFrame *no_opt = nullptr;
+    if (p.mode.optimize) {
+        // jpeg_opt.hpp: the counts and the frames' tables between stage A and stage B, then the <true> forms of the code-reading kernels
+        uint32_t *blk_post = reinterpret_cast<uint32_t *>(work + p.blk_post), *wg_post = reinterpret_cast<uint32_t *>(work + p.wg_post);
+        uint32_t *rst_off = reinterpret_cast<uint32_t *>(work + p.rst_off), *hist = reinterpret_cast<uint32_t *>(work + p.hist);
+        JpegOptFrame *opt = reinterpret_cast<JpegOptFrame *>(work + p.opt);
+        const int bins = p.nf * y2j::kOptHistBins;
+        if (p.mode.subsample)
+            hipLaunchKernelGGL(k_jpeg_transform420, dim3(p.grid_mcu, (unsigned)p.nf), dim3(kJpeg420Threads), 0, st, table_dev, src_base, coef);
+        else
+            hipLaunchKernelGGL(k_jpeg_transform, per_blk, dim3(kJpegBlocks), 0, st, table_dev, src_base, coef);
+        hipLaunchKernelGGL(k_jpeg_hist_clear, dim3(((unsigned)bins + kJpegScan - 1) / kJpegScan), dim3(kJpegScan), 0, st, hist, bins);
+        hipLaunchKernelGGL(k_jpeg_hist, per_blk, dim3(kJpegBlocks), 0, st, table_dev, coef, hist);
+        hipLaunchKernelGGL(k_jpeg_opt_tables, per_frame, dim3(kJpegOptThreads), 0, st, table_dev, hist, opt);
+        if (p.mode.plain()) {
+            hipLaunchKernelGGL(k_jpeg_lengths<true>, per_blk, dim3(kJpegBlocks), 0, st, table_dev, coef, blk_off, wg_sum, opt);
+            hipLaunchKernelGGL(k_jpeg_scan_groups, per_frame, dim3(kJpegScan), 0, st, table_dev, wg_sum, wg_base, us, state);
+            hipLaunchKernelGGL(k_jpeg_pack<true>, per_blk, dim3(kJpegBlocks), 0, st, table_dev, coef, blk_off, wg_sum, wg_base, us, opt);
+        } else {
+            hipLaunchKernelGGL(k_jpeg_lengths_rst<true>, per_blk, dim3(kJpegBlocks), 0, st, table_dev, coef, blk_off, blk_post, wg_sum, wg_post, opt);
+            hipLaunchKernelGGL(k_jpeg_scan_groups_rst, per_frame, dim3(kJpegScan), 0, st, table_dev, wg_sum, wg_post, wg_base, us, state);
+            hipLaunchKernelGGL(k_jpeg_pack_rst<true>, per_blk, dim3(kJpegBlocks), 0, st, table_dev, coef, blk_off, blk_post, wg_sum, wg_post, wg_base, us, rst_off, opt);
+        }
+        hipLaunchKernelGGL(k_jpeg_count_ff, per_seg, dim3(kJpegSegThreads), 0, st, table_dev, us, state, seg_ff);
+        hipLaunchKernelGGL(k_jpeg_scan_segs, per_frame, dim3(kJpegScan), 0, st, table_dev, seg_ff, seg_base, state, sizes);
+        if (!p.mode.plain()) hipLaunchKernelGGL(k_jpeg_sizes_rst, frames_scan, dim3(kJpegScan), 0, st, table_dev, state, sizes, p.nf);
+        hipLaunchKernelGGL(k_jpeg_sizes_opt, frames_scan, dim3(kJpegScan), 0, st, table_dev, opt, state, sizes, p.nf);
+        hipLaunchKernelGGL(k_jpeg_place, dim3(1), dim3(kJpegScan), 0, st, table_dev, state, p.nf);
+        if (p.mode.plain())
+            hipLaunchKernelGGL(k_jpeg_emit<true>, per_seg, dim3(kJpegSegThreads), 0, st, table_dev, us, state, seg_base, out_base, opt);
+        else
+            hipLaunchKernelGGL(k_jpeg_emit_rst<true>, per_seg, dim3(kJpegSegThreads), 0, st, table_dev, us, state, seg_base, rst_off, out_base, opt);
+    } else if (p.mode.plain()) {
         hipLaunchKernelGGL(k_jpeg_transform, per_blk, dim3(kJpegBlocks), 0, st, table_dev, src_base, coef);
-        hipLaunchKernelGGL(k_jpeg_lengths, per_blk, dim3(kJpegBlocks), 0, st, table_dev, coef, blk_off, wg_sum);
+        hipLaunchKernelGGL(k_jpeg_lengths<false>, per_blk, dim3(kJpegBlocks), 0, st, table_dev, coef, blk_off, wg_sum, no_opt);
         hipLaunchKernelGGL(k_jpeg_scan_groups, per_frame, dim3(kJpegScan), 0, st, table_dev, wg_sum, wg_base, us, state);
-        hipLaunchKernelGGL(k_jpeg_pack, per_blk, dim3(kJpegBlocks), 0, st, table_dev, coef, blk_off, wg_sum, wg_base, us);
+        hipLaunchKernelGGL(k_jpeg_pack<false>, per_blk, dim3(kJpegBlocks), 0, st, table_dev, coef, blk_off, wg_sum, wg_base, us, no_opt);
         hipLaunchKernelGGL(k_jpeg_count_ff, per_seg, dim3(kJpegSegThreads), 0, st, table_dev, us, state, seg_ff);
         hipLaunchKernelGGL(k_jpeg_scan_segs, per_frame, dim3(kJpegScan), 0, st, table_dev, seg_ff, seg_base, state, sizes);
         hipLaunchKernelGGL(k_jpeg_place, dim3(1), dim3(kJpegScan), 0, st, table_dev, state, p.nf);
-        hipLaunchKernelGGL(k_jpeg_emit, per_seg, dim3(kJpegSegThreads), 0, st, table_dev, us, state, seg_base, out_base);
+        hipLaunchKernelGGL(k_jpeg_emit<false>, per_seg, dim3(kJpegSegThreads), 0, st, table_dev, us, state, seg_base, out_base, no_opt);
     } else {
         uint32_t *blk_post = reinterpret_cast<uint32_t *>(work + p.blk_post), *wg_post = reinterpret_cast<uint32_t *>(work + p.wg_post);
         uint32_t *rst_off = reinterpret_cast<uint32_t *>(work + p.rst_off);
@@ -166,14 +205,14 @@ int y2_jpeg_enqueue(const Y2JpegPlan &p, const uint8_t *table_dev, const uint8_t
             hipLaunchKernelGGL(k_jpeg_transform420, dim3(p.grid_mcu, (unsigned)p.nf), dim3(kJpeg420Threads), 0, st, table_dev, src_base, coef);
         else
             hipLaunchKernelGGL(k_jpeg_transform, per_blk, dim3(kJpegBlocks), 0, st, table_dev, src_base, coef);
-        hipLaunchKernelGGL(k_jpeg_lengths_rst, per_blk, dim3(kJpegBlocks), 0, st, table_dev, coef, blk_off, blk_post, wg_sum, wg_post);
+        hipLaunchKernelGGL(k_jpeg_lengths_rst<false>, per_blk, dim3(kJpegBlocks), 0, st, table_dev, coef, blk_off, blk_post, wg_sum, wg_post, no_opt);
         hipLaunchKernelGGL(k_jpeg_scan_groups_rst, per_frame, dim3(kJpegScan), 0, st, table_dev, wg_sum, wg_post, wg_base, us, state);
-        hipLaunchKernelGGL(k_jpeg_pack_rst, per_blk, dim3(kJpegBlocks), 0, st, table_dev, coef, blk_off, blk_post, wg_sum, wg_post, wg_base, us, rst_off);
+        hipLaunchKernelGGL(k_jpeg_pack_rst<false>, per_blk, dim3(kJpegBlocks), 0, st, table_dev, coef, blk_off, blk_post, wg_sum, wg_post, wg_base, us, rst_off, no_opt);
         hipLaunchKernelGGL(k_jpeg_count_ff, per_seg, dim3(kJpegSegThreads), 0, st, table_dev, us, state, seg_ff);
         hipLaunchKernelGGL(k_jpeg_scan_segs, per_frame, dim3(kJpegScan), 0, st, table_dev, seg_ff, seg_base, state, sizes);
-        hipLaunchKernelGGL(k_jpeg_sizes_rst, dim3(((unsigned)p.nf + kJpegScan - 1) / kJpegScan), dim3(kJpegScan), 0, st, table_dev, state, sizes, p.nf);
+        hipLaunchKernelGGL(k_jpeg_sizes_rst, frames_scan, dim3(kJpegScan), 0, st, table_dev, state, sizes, p.nf);
         hipLaunchKernelGGL(k_jpeg_place, dim3(1), dim3(kJpegScan), 0, st, table_dev, state, p.nf);
-        hipLaunchKernelGGL(k_jpeg_emit_rst, per_seg, dim3(kJpegSegThreads), 0, st, table_dev, us, state, seg_base, rst_off, out_base);
+        hipLaunchKernelGGL(k_jpeg_emit_rst<false>, per_seg, dim3(kJpegSegThreads), 0, st, table_dev, us, state, seg_base, rst_off, out_base, no_opt);
     }
     HIP_TRY(hipGetLastError(), YOLO2_ERROR);
     return YOLO2_SUCCESS;

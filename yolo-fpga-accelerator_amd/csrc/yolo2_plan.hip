@@ -35,6 +35,7 @@ const IntOpt kJpegInts[] = {
 const IntOpt kJpegEncInts[] = {
     {"jpeg_subsample", &Y2Options::jpeg_subsample, 420, 420},
     {"jpeg_restart", &Y2Options::jpeg_restart, 1, 65535},
+    {"jpeg_optimize", &Y2Options::jpeg_optimize, 1, 1},
 };
 const FlagOpt kFlags[] = {
     {"no_lanes", &Y2Options::no_lanes}, {"verbose", &Y2Options::verbose}, {"no_plan_cache", &Y2Options::no_plan_cache},

@@ -105,6 +105,8 @@ size_t jpg_rgb24_bound(int w, int h);
 // The same encoder in the library's own modes (csrc/jpeg_tables.hpp): subsample 0 | 420, restart 0..65535 MCUs per interval; (0, 0) is
 // write_jpg_rgb24.  A mode outside those is refused as a bad size is (-1 / 0).
 long write_jpg_rgb24_ex(const uint8_t *rgb, int w, int h, int quality, int subsample, int restart, uint8_t *out, size_t cap);
+// ... and with optimize = 1 (csrc/jpeg_opt.hpp) the frame's own Huffman tables; optimize = 0 is write_jpg_rgb24_ex
+long write_jpg_rgb24_opt(const uint8_t *rgb, int w, int h, int quality, int subsample, int restart, int optimize, uint8_t *out, size_t cap);
 size_t jpg_rgb24_bound_ex(int w, int h, int subsample, int restart);
 // The annotated frame as a PNG file, the library's own definition (csrc/png_huff.hpp; y2_png.cpp): 8-bit RGB, rows filtered by the rule
 // of stb_image_write v1.09 (the reference's writer, linux_app/src/main.c:1086), one IDAT of dynamic-Huffman deflate blocks without LZ

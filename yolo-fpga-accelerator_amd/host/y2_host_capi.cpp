@@ -243,6 +243,15 @@ long y2h_write_jpg_rgb24_ex(const uint8_t *rgb, int w, int h, int quality, int s
     return n;
 }
 size_t y2h_jpg_rgb24_bound_ex(int w, int h, int subsample, int restart) { return jpg_rgb24_bound_ex(w, h, subsample, restart); }
+// optimize = 1: the frame's own Huffman tables (csrc/jpeg_opt.hpp), never past y2h_jpg_rgb24_bound_ex; 0: y2h_write_jpg_rgb24_ex
+long y2h_write_jpg_rgb24_opt(const uint8_t *rgb, int w, int h, int quality, int subsample, int restart, int optimize, uint8_t *out, size_t cap)
+{
+    const long n = write_jpg_rgb24_opt(rgb, w, h, quality, subsample, restart, optimize, out, cap);
+    if (n < 0)
+        g_err = "write_jpg_rgb24_opt: null buffer, bad frame " + std::to_string(w) + "x" + std::to_string(h) + " (1..65535) or bad mode (subsample " +
+                std::to_string(subsample) + ": 0 | 420, restart " + std::to_string(restart) + ": 0..65535, optimize " + std::to_string(optimize) + ": 0 | 1)";
+    return n;
+}
 
 // write_png_rgb24 / zlib_huff (y2_png.cpp): return the length (bytes below cap are stored), or -1 (y2h_last_error)
 long y2h_write_png_rgb24(const uint8_t *rgb, int w, int h, uint8_t *out, size_t cap)

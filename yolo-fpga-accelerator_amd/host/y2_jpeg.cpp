@@ -64,16 +64,20 @@ struct Sink {
     void code(uint32_t c) { bits(c & 0xffffu, (int)(c >> 16)); }
 };
 
-// transform, quantise and code one block; returns its DC level (the next block's predictor)
-int put_block(Sink &s, float *blk, const float *fdtbl, int pred, const uint32_t *dc, const uint32_t *ac)
+// transform and quantise one block: its levels in zigzag order
+void quantise_block(float *blk, const float *fdtbl, int *zz)
 {
     for (int r = 0; r < 8; ++r) aan_pass(blk + 8 * r, 1);
     for (int c = 0; c < 8; ++c) aan_pass(blk + c, 8);
-    int zz[64];
     for (int i = 0; i < 64; ++i) {
         const float v = blk[i] * fdtbl[i];
         zz[y2j::kZigzag[i]] = (int)(v < 0 ? v - 0.5f : v + 0.5f);
     }
+}
+
+// code one block
+void put_block(Sink &s, const int *zz, int pred, const uint32_t *dc, const uint32_t *ac)
+{
     uint32_t extra;
     int cat = category(zz[0] - pred, &extra);
     s.code(dc[cat]);
@@ -88,8 +92,90 @@ int put_block(Sink &s, float *blk, const float *fdtbl, int pred, const uint32_t 
         run = 0;
     }
     if (run) s.code(ac[0x00]);   // end of block, unless coefficient 63 closed it
-    return zz[0];
 }
+
+// count one block's symbols (csrc/jpeg_opt.hpp): exactly what put_block sends codes for
+void count_block(uint32_t *dc, uint32_t *ac, const int *zz, int pred)
+{
+    uint32_t extra;
+    ++dc[category(zz[0] - pred, &extra)];
+    int run = 0;
+    for (int i = 1; i < 64; ++i) {
+        if (zz[i] == 0) { ++run; continue; }
+        ac[0xF0] += (uint32_t)(run >> 4);
+        ++ac[((run & 15) << 4) | category(zz[i], &extra)];
+        run = 0;
+    }
+    if (run) ++ac[0x00];
+}
+
+// The modes of csrc/jpeg_tables.hpp as one serial loop over MCUs: v.restart(mcu) in front of every interval but the first, then
+// v.block(levels, luma, component) for the MCU's blocks in stream order.
+template <class V>
+void walk_blocks(const uint8_t *rgb, int w, int h, int subsample, int restart, const y2j::Tables &t, V &v)
+{
+    const int m = y2j::mcu_pixels(subsample), mcux = (w + m - 1) / m, mcus = mcux * ((h + m - 1) / m);
+    float Y[16 * 16], U[16 * 16], V_[16 * 16], blk[64];   // the MCU's pixels, row-major m x m
+    int zz[64];
+    for (int mcu = 0; mcu < mcus; ++mcu) {
+        if (restart && mcu && mcu % restart == 0) v.restart(mcu);
+        const int y0 = mcu / mcux * m, x0 = mcu % mcux * m;
+        for (int r = 0; r < m; ++r) {
+            const uint8_t *row = rgb + (size_t)(y0 + r < h ? y0 + r : h - 1) * w * 3;   // edge pixels are repeated
+            for (int c = 0; c < m; ++c) {
+                const uint8_t *px = row + (size_t)(x0 + c < w ? x0 + c : w - 1) * 3;
+                const float R = px[0], G = px[1], B = px[2];
+                Y[r * m + c] = 0.299f * R + 0.587f * G + 0.114f * B - 128;
+                U[r * m + c] = -0.16874f * R - 0.33126f * G + 0.5f * B;
+                V_[r * m + c] = 0.5f * R - 0.41869f * G - 0.08131f * B;
+            }
+        }
+        for (int k = 0; k < m / 8 * (m / 8); ++k) {   // the Y blocks, row by row
+            for (int i = 0; i < 64; ++i) blk[i] = Y[((k / (m / 8)) * 8 + i / 8) * m + (k % (m / 8)) * 8 + i % 8];
+            quantise_block(blk, t.fdtbl[0], zz);
+            v.block(zz, 0);
+        }
+        int p = 1;
+        for (const float *C : {U, V_}) {
+            for (int i = 0; i < 64; ++i) {
+                const float *q = C + (m / 8) * ((i / 8) * m + i % 8);   // the sample's pixel, or the upper left of its 2 x 2
+                blk[i] = m == 8 ? q[0] : ((q[0] + q[1]) + (q[m] + q[m + 1])) * 0.25f;
+            }
+            quantise_block(blk, t.fdtbl[1], zz);
+            v.block(zz, p++);
+        }
+    }
+}
+
+// the two passes over the blocks: counting (optimize = 1 only), then coding
+struct Counter {
+    uint32_t hist[y2j::kOptHistBins] = {};
+    int pred[3] = {0, 0, 0};
+    void restart(int) { pred[0] = pred[1] = pred[2] = 0; }
+    void block(const int *zz, int comp)
+    {
+        count_block(hist + y2j::opt_hist_at(comp ? y2j::kDcChroma : y2j::kDcLuma), hist + y2j::opt_hist_at(comp ? y2j::kAcChroma : y2j::kAcLuma), zz, pred[comp]);
+        pred[comp] = zz[0];
+    }
+};
+struct Coder {
+    Sink &s;
+    const uint32_t (*code)[256];
+    int every;
+    int pred[3] = {0, 0, 0};
+    void restart(int mcu)
+    {
+        if (s.have) s.bits(0x7fu, 8 - s.have);
+        s.byte(0xFF);   // (a marker: not stuffed)
+        s.byte((uint8_t)(0xD0 + ((mcu / every - 1) & 7)));
+        pred[0] = pred[1] = pred[2] = 0;
+    }
+    void block(const int *zz, int comp)
+    {
+        put_block(s, zz, pred[comp], code[comp ? y2j::kDcChroma : y2j::kDcLuma], code[comp ? y2j::kAcChroma : y2j::kAcLuma]);
+        pred[comp] = zz[0];
+    }
+};
 
 }  // namespace
 
@@ -101,49 +187,30 @@ size_t jpg_rgb24_bound_ex(int w, int h, int subsample, int restart)
 
 long write_jpg_rgb24(const uint8_t *rgb, int w, int h, int quality, uint8_t *out, size_t cap) { return write_jpg_rgb24_ex(rgb, w, h, quality, 0, 0, out, cap); }
 
-// The modes of csrc/jpeg_tables.hpp as one serial loop over MCUs; mode (0, 0) is the reference's stream.
 long write_jpg_rgb24_ex(const uint8_t *rgb, int w, int h, int quality, int subsample, int restart, uint8_t *out, size_t cap)
 {
-    if (!rgb || w < 1 || h < 1 || w > 65535 || h > 65535 || (cap && !out) || !y2j::mode_ok(subsample, restart)) return -1;
+    return write_jpg_rgb24_opt(rgb, w, h, quality, subsample, restart, 0, out, cap);
+}
+
+// Mode (0, 0) without optimize is the reference's stream.  optimize = 1 (csrc/jpeg_opt.hpp): the blocks are walked twice, first for the
+// symbol counts the frame's tables are made from.
+long write_jpg_rgb24_opt(const uint8_t *rgb, int w, int h, int quality, int subsample, int restart, int optimize, uint8_t *out, size_t cap)
+{
+    if (!rgb || w < 1 || h < 1 || w > 65535 || h > 65535 || (cap && !out) || !y2j::mode_ok(subsample, restart, optimize)) return -1;
     y2j::Tables t;
     y2j::make_tables(quality, &t);
     Sink s{out, cap};
-    for (int i = 0; i < y2j::header_bytes(restart); ++i) s.byte(y2j::header_byte(t.header, i, w, h, subsample, restart));
-    const int m = y2j::mcu_pixels(subsample), mcux = (w + m - 1) / m, mcus = mcux * ((h + m - 1) / m);
-    int pred[3] = {0, 0, 0};
-    float Y[16 * 16], U[16 * 16], V[16 * 16], blk[64];   // the MCU's pixels, row-major m x m
-    for (int mcu = 0; mcu < mcus; ++mcu) {
-        if (restart && mcu && mcu % restart == 0) {
-            if (s.have) s.bits(0x7fu, 8 - s.have);
-            s.byte(0xFF);   // (a marker: not stuffed)
-            s.byte((uint8_t)(0xD0 + ((mcu / restart - 1) & 7)));
-            pred[0] = pred[1] = pred[2] = 0;
-        }
-        const int y0 = mcu / mcux * m, x0 = mcu % mcux * m;
-        for (int r = 0; r < m; ++r) {
-            const uint8_t *row = rgb + (size_t)(y0 + r < h ? y0 + r : h - 1) * w * 3;   // edge pixels are repeated
-            for (int c = 0; c < m; ++c) {
-                const uint8_t *px = row + (size_t)(x0 + c < w ? x0 + c : w - 1) * 3;
-                const float R = px[0], G = px[1], B = px[2];
-                Y[r * m + c] = 0.299f * R + 0.587f * G + 0.114f * B - 128;
-                U[r * m + c] = -0.16874f * R - 0.33126f * G + 0.5f * B;
-                V[r * m + c] = 0.5f * R - 0.41869f * G - 0.08131f * B;
-            }
-        }
-        for (int k = 0; k < m / 8 * (m / 8); ++k) {   // the Y blocks, row by row
-            for (int i = 0; i < 64; ++i) blk[i] = Y[((k / (m / 8)) * 8 + i / 8) * m + (k % (m / 8)) * 8 + i % 8];
-            pred[0] = put_block(s, blk, t.fdtbl[0], pred[0], t.code[y2j::kDcLuma], t.code[y2j::kAcLuma]);
-        }
-        int p = 1;
-        for (const float *C : {U, V}) {
-            for (int i = 0; i < 64; ++i) {
-                const float *q = C + (m / 8) * ((i / 8) * m + i % 8);   // the sample's pixel, or the upper left of its 2 x 2
-                blk[i] = m == 8 ? q[0] : ((q[0] + q[1]) + (q[m] + q[m + 1])) * 0.25f;
-            }
-            pred[p] = put_block(s, blk, t.fdtbl[1], pred[p], t.code[y2j::kDcChroma], t.code[y2j::kAcChroma]);
-            ++p;
-        }
+    y2j::OptTables o;
+    if (optimize) {
+        Counter counts;
+        walk_blocks(rgb, w, h, subsample, restart, t, counts);
+        y2j::opt_build(counts.hist, t, w, h, subsample, restart, &o);
+        for (int i = 0; i < o.head_len; ++i) s.byte(o.header[i]);
+    } else {
+        for (int i = 0; i < y2j::header_bytes(restart); ++i) s.byte(y2j::header_byte(t.header, i, w, h, subsample, restart));
     }
+    Coder coder{s, optimize ? o.code : t.code, restart};
+    walk_blocks(rgb, w, h, subsample, restart, t, coder);
     if (s.have) s.bits(0x7fu, 8 - s.have);   // the last byte's free bits are ones
     s.byte(0xFF);
     s.byte(0xD9);   // EOI

@@ -70,6 +70,7 @@ struct AppConfig {
                                     // nv12 / yuv420p (--loop-gpu): raw planar YUV 4:2:0 frames, converted by the painter (YOLO2_LOOP_OUT_NV12 / _I420)
     int jpeg_quality = 80;          // --jpeg-quality, the reference streamer's default
     int jpeg_subsample = 0, jpeg_restart = 0;   // --jpeg-subsample 420 / --jpeg-restart R: options jpeg_subsample / jpeg_restart
+    bool jpeg_optimize = false;     // --jpeg-optimize: option jpeg_optimize (Huffman tables per frame)
     bool loop_gpu = false;          // --loop-gpu: records and annotated frames from ONE accelerator call per chunk (yolo2_hip_loop_images_pix)
     int video_w = 640, video_h = 480;
     int video_pixfmt = YOLO2_PIX_RGB24; // --video-pix-fmt: what a --video-raw frame holds (RGB24, or packed YUYV 4:2:2 / planar NV12 / I420 / packed BGR24 / RGBA32 / BGRA32 / raw 8-bit Bayer read by the GPU as they are)
@@ -145,6 +146,7 @@ void print_usage(const char *prog)
         "  --jpeg-quality <1..100>  quality of --annotated-format jpg (default 80)\n"
         "  --jpeg-subsample 420   --annotated-format jpg as 4:2:0 (MCUs of 16x16 pixels; default: no subsampling, the reference's stream)\n"
         "  --jpeg-restart <R>     ... with a restart marker after every R MCUs, 1..65535 (default: none)\n"
+        "  --jpeg-optimize        ... with Huffman tables made from each frame's own symbol counts on the GPU (default: the standard tables)\n"
         "  --loop-gpu            with --annotate-gpu --save-annotated-dir and --post gpu: one accelerator call per chunk makes the records AND\n"
         "                        the annotated frames from one upload (yolo2_hip_loop_images_pix; with --decode gpu\n"
         "                        yolo2_hip_loop_images_jpeg, from the compressed streams); same log, JSONL and files\n"
@@ -220,6 +222,7 @@ AppConfig parse_args(int argc, char **argv)
         else if (arg == "--loop-gpu") cfg.loop_gpu = true;
         else if (arg == "--annotated-format" && need("")) cfg.annotated_format = argv[++i];
         else if (arg == "--jpeg-quality" && need("")) cfg.jpeg_quality = std::atoi(argv[++i]);
+        else if (arg == "--jpeg-optimize") cfg.jpeg_optimize = true;
         else if ((arg == "--jpeg-subsample" || arg == "--jpeg-restart") && need("")) {
             int &v = arg == "--jpeg-subsample" ? cfg.jpeg_subsample : cfg.jpeg_restart;
             v = std::atoi(argv[++i]);
@@ -869,7 +872,8 @@ void run_stream(AppConfig cfg)
             if (cfg.decode_split && yolo2_hip_set_option(ctx, "jpegdec_split", std::to_string(cfg.decode_split).c_str()) != YOLO2_SUCCESS)
                 throw std::runtime_error(yolo2_hip_last_error());
             if ((cfg.jpeg_subsample && yolo2_hip_set_option(ctx, "jpeg_subsample", std::to_string(cfg.jpeg_subsample).c_str()) != YOLO2_SUCCESS) ||
-                (cfg.jpeg_restart && yolo2_hip_set_option(ctx, "jpeg_restart", std::to_string(cfg.jpeg_restart).c_str()) != YOLO2_SUCCESS))
+                (cfg.jpeg_restart && yolo2_hip_set_option(ctx, "jpeg_restart", std::to_string(cfg.jpeg_restart).c_str()) != YOLO2_SUCCESS) ||
+                (cfg.jpeg_optimize && yolo2_hip_set_option(ctx, "jpeg_optimize", "1") != YOLO2_SUCCESS))
                 throw std::runtime_error(yolo2_hip_last_error());
             // while the reader decodes its first chunk: plan the batch (activation tensors, lanes) on this device (int16; the fp16
             // passes build their launch table at the first chunk)

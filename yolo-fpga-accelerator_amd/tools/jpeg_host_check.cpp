@@ -1,4 +1,4 @@
-// CPU-only sanitizer harness for y2h::write_jpg_rgb24 (host/y2_jpeg.cpp + csrc/jpeg_tables.hpp): the encoder over ragged sizes - 1x1,
+// CPU-only sanitizer harness for y2h::write_jpg_rgb24 and write_jpg_rgb24_opt (host/y2_jpeg.cpp + csrc/jpeg_tables.hpp, jpeg_opt.hpp): the encoder over ragged sizes - 1x1,
 // one-row and one-column frames, widths and heights on both sides of multiples of 8 - with noise, flat and 0 / 255 checkerboard
 // content at the qualities' extremes, and over capacities from 0 to the stream's size.  Every frame and every output sits exactly
 // in its allocation, so a read outside the frame or a write at or beyond the capacity is a sanitizer report; the bytes below a
@@ -47,6 +47,36 @@ int main(int argc, char **argv)
             bytes += n;
         }
     }
+    // optimize = 1 (csrc/jpeg_opt.hpp) over the same sizes in every mode: never past the bound or the standard stream's length + 0,
+    // the same stream at every capacity, and optimize = 0 is write_jpg_rgb24_ex
+    const int modes[][2] = {{0, 0}, {420, 0}, {0, 1}, {420, 4}};
+    for (const auto &s : sizes) {
+        const int w = s[0], h = s[1];
+        std::vector<uint8_t> frame((size_t)w * h * 3);
+        for (int r = 0; r < 3; ++r) {
+            for (size_t i = 0; i < frame.size(); ++i) frame[i] = r == 0 ? (uint8_t)rng() : r == 1 ? (uint8_t)77 : (uint8_t)((i / 3 % (size_t)w & 1) ? 255 : 0);
+            for (const auto &m : modes) {
+                const int q = qualities[rng() % (sizeof(qualities) / sizeof(qualities[0]))];
+                const long n0 = y2h::write_jpg_rgb24_ex(frame.data(), w, h, q, m[0], m[1], nullptr, 0);
+                const long n = y2h::write_jpg_rgb24_opt(frame.data(), w, h, q, m[0], m[1], 1, nullptr, 0);
+                if (n < 4 || n > n0 || y2h::write_jpg_rgb24_opt(frame.data(), w, h, q, m[0], m[1], 0, nullptr, 0) != n0) {
+                    std::printf("%dx%d q%d (%d, %d): optimised size %ld against %ld\n", w, h, q, m[0], m[1], n, n0);
+                    return 1;
+                }
+                std::vector<uint8_t> full((size_t)n);
+                if (y2h::write_jpg_rgb24_opt(frame.data(), w, h, q, m[0], m[1], 1, full.data(), full.size()) != n) return 1;
+                const size_t caps[] = {1, 176, 200, (size_t)n - 1, (size_t)(rng() % (unsigned long)n)};
+                for (size_t cap : caps) {
+                    std::vector<uint8_t> part(cap);
+                    if (y2h::write_jpg_rgb24_opt(frame.data(), w, h, q, m[0], m[1], 1, part.data(), cap) != n || std::memcmp(part.data(), full.data(), cap) != 0) return 1;
+                    ++calls;
+                }
+                bytes += n;
+            }
+        }
+    }
+    const uint8_t pixel[3] = {1, 2, 3};
+    if (y2h::write_jpg_rgb24_opt(pixel, 1, 1, 80, 0, 0, 2, nullptr, 0) != -1) return 1;   // optimize is 0 | 1
     // refused before anything is read
     if (y2h::write_jpg_rgb24(nullptr, 4, 4, 80, nullptr, 0) != -1 || y2h::jpg_rgb24_bound(0, 4) != 0 || y2h::jpg_rgb24_bound(4, 65536) != 0) return 1;
     std::printf("%ld calls, %ld stream bytes\n", calls, bytes);

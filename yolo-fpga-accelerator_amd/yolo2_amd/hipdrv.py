@@ -590,11 +590,12 @@ class Yolo2Hip:
         return region, q.value
 
     def loop_images(self, images, pixfmt=None, precision: str = "int16", tail: str = "core", thresh: float = 0.24, nms: float = 0.45,
-                    labels=None, jpeg_quality=None, batch: int = 64, cap: int = 845, out_order: str = "rgb", jpeg_subsample=None, jpeg_restart=None):
+                    labels=None, jpeg_quality=None, batch: int = 64, cap: int = 845, out_order: str = "rgb", jpeg_subsample=None, jpeg_restart=None,
+                    jpeg_optimize=None):
         """the camera loop as one call: records and annotated frames from one upload (module-level loop_images)"""
         return loop_images(self._h, images, pixfmt=pixfmt, precision=precision, tail=tail, thresh=thresh, nms=nms, labels=labels,
                            jpeg_quality=jpeg_quality, batch=batch, cap=cap, out_order=out_order, jpeg_subsample=jpeg_subsample,
-                           jpeg_restart=jpeg_restart)
+                           jpeg_restart=jpeg_restart, jpeg_optimize=jpeg_optimize)
 
     def jpeg_decode(self, streams, batch: int = 64, strict: bool = True):
         """see jpeg_decode"""
@@ -607,20 +608,21 @@ class Yolo2Hip:
 
     def loop_jpegs(self, streams, precision: str = "int16", tail: str = "core", thresh: float = 0.24, nms: float = 0.45, labels=None,
                    jpeg_quality=None, batch: int = 64, cap: int = 845, strict: bool = True, out_order: str = "rgb", jpeg_subsample=None,
-                   jpeg_restart=None):
+                   jpeg_restart=None, jpeg_optimize=None):
         """the camera loop as one call from JPEG streams (module-level loop_jpegs)"""
         return loop_jpegs(self._h, streams, precision=precision, tail=tail, thresh=thresh, nms=nms, labels=labels, jpeg_quality=jpeg_quality,
-                          batch=batch, cap=cap, strict=strict, out_order=out_order, jpeg_subsample=jpeg_subsample, jpeg_restart=jpeg_restart)
+                          batch=batch, cap=cap, strict=strict, out_order=out_order, jpeg_subsample=jpeg_subsample, jpeg_restart=jpeg_restart,
+                          jpeg_optimize=jpeg_optimize)
 
     def loop_last_info(self) -> dict:
         return loop_last_info(self._h)
 
     def annotate_images(self, images, dets, counts, batch: int, thresh: float, labels=None, pixfmt=None, jpeg_quality=None, jpeg_subsample=None,
-                        jpeg_restart=None):
+                        jpeg_restart=None, jpeg_optimize=None):
         """the images with their detection records painted in, as the reference's camera loop does (module-level annotate_images);
         with jpeg_quality, as the JPEG streams its MJPEG streamer sends (a list of bytes)"""
         return annotate_images(self._h, images, dets, counts, batch, thresh, labels=labels, pixfmt=pixfmt, jpeg_quality=jpeg_quality,
-                               jpeg_subsample=jpeg_subsample, jpeg_restart=jpeg_restart)
+                               jpeg_subsample=jpeg_subsample, jpeg_restart=jpeg_restart, jpeg_optimize=jpeg_optimize)
 
     # ---- fp16 MFMA path
     def load_weights_fp32(self, weights_f32, bias_f32):
@@ -1350,15 +1352,16 @@ def annotate_pix(image: np.ndarray, dets, pixfmt=None, thresh: float = 0.24, lab
 
 
 def annotate_images(handle, images, dets, counts, batch: int, thresh: float, labels=None, pixfmt=None, multi: bool = False, jpeg_quality=None,
-                    jpeg_subsample=None, jpeg_restart=None):
+                    jpeg_subsample=None, jpeg_restart=None, jpeg_optimize=None):
     """yolo2_hip_annotate_images_pix_host / yolo2_hip_multi_annotate_images_pix_host: host images and the records a run_images_dets call
     returned for them -> (list of uint8 [h][w][3] annotated frames, records drawn per frame).  dets: DET_DTYPE [n][cap] with counts [n]
     (frame f uses min(counts[f], cap) records), or - counts None - a list of per-frame record arrays (run_images_dets()["dets"]).
     jpeg_quality (1..100): the _jpeg_host entries instead - the frames come back as the reference's JPEG streams, a list of bytes;
-    jpeg_subsample = 420 / jpeg_restart = R with it: the library's 4:2:0 / restart-interval forms of the stream."""
+    jpeg_subsample = 420 / jpeg_restart = R with it: the library's 4:2:0 / restart-interval forms of the stream; jpeg_optimize = 1:
+    Huffman tables per frame (option jpeg_optimize)."""
     if jpeg_quality is not None:
         return annotate_images_jpeg(handle, images, dets, counts, batch, thresh, int(jpeg_quality), labels=labels, pixfmt=pixfmt, multi=multi,
-                                    subsample=jpeg_subsample, restart=jpeg_restart)
+                                    subsample=jpeg_subsample, restart=jpeg_restart, optimize=jpeg_optimize)
     imgs0 = [np.ascontiguousarray(im, dtype=np.uint8) for im in images]
     fmt = pixfmt if pixfmt is not None else ("grey8" if imgs0[0].ndim == 2 else "rgb24")
     n, ptrs, ws, hs, code, imgs = _image_args(imgs0, fmt)
@@ -1398,6 +1401,8 @@ def host_lib():
         H.y2h_jpg_rgb24_bound.restype = C.c_size_t
         H.y2h_write_jpg_rgb24_ex.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
         H.y2h_write_jpg_rgb24_ex.restype = C.c_long
+        H.y2h_write_jpg_rgb24_opt.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
+        H.y2h_write_jpg_rgb24_opt.restype = C.c_long
         H.y2h_jpg_rgb24_bound_ex.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
         H.y2h_jpg_rgb24_bound_ex.restype = C.c_size_t
         H.y2h_packed_to_rgb24.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
@@ -1469,16 +1474,17 @@ def _rgb24(rgb):
     return im
 
 
-def write_jpg_host(rgb, quality: int = 80, subsample: int = 0, restart: int = 0) -> bytes:
-    """y2h_write_jpg_rgb24_ex: an RGB24 frame as the JPEG stream of the reference's MJPEG streamer, encoded on the host; subsample =
-    420 / restart = R MCUs per interval: the library's own forms of it (mode (0, 0) is y2h_write_jpg_rgb24)"""
+def write_jpg_host(rgb, quality: int = 80, subsample: int = 0, restart: int = 0, optimize: bool = False) -> bytes:
+    """y2h_write_jpg_rgb24_opt: an RGB24 frame as the JPEG stream of the reference's MJPEG streamer, encoded on the host; subsample =
+    420 / restart = R MCUs per interval: the library's own forms of it (mode (0, 0) is y2h_write_jpg_rgb24); optimize: Huffman tables
+    from the frame's own symbol counts (csrc/jpeg_opt.hpp; False: y2h_write_jpg_rgb24_ex)"""
     im = _rgb24(rgb)
     H = host_lib()
     cap = H.y2h_jpg_rgb24_bound_ex(im.shape[1], im.shape[0], subsample, restart)
     out = np.empty(max(cap, 1), dtype=np.uint8)
-    n = H.y2h_write_jpg_rgb24_ex(im.ctypes.data, im.shape[1], im.shape[0], quality, subsample, restart, out.ctypes.data, cap)
+    n = H.y2h_write_jpg_rgb24_opt(im.ctypes.data, im.shape[1], im.shape[0], quality, subsample, restart, int(bool(optimize)), out.ctypes.data, cap)
     if n < 0 or n > cap:
-        raise ValueError(f"y2h_write_jpg_rgb24_ex refused a {im.shape[1]}x{im.shape[0]} frame in mode ({subsample}, {restart})")
+        raise ValueError(f"y2h_write_jpg_rgb24_opt refused a {im.shape[1]}x{im.shape[0]} frame in mode ({subsample}, {restart})")
     return out[:n].tobytes()
 
 
@@ -1488,14 +1494,14 @@ def jpeg_bound(w: int, h: int, subsample: int = 0, restart: int = 0) -> int:
 
 
 @contextlib.contextmanager
-def jpeg_mode(handle, subsample=None, restart=None, multi: bool = False):
-    """Options jpeg_subsample / jpeg_restart on a context (None: the process-wide set; multi: every member of a multi handle) for the
+def jpeg_mode(handle, subsample=None, restart=None, multi: bool = False, optimize=None):
+    """Options jpeg_subsample / jpeg_restart / jpeg_optimize on a context (None: the process-wide set; multi: every member of a multi handle) for the
     calls inside the block; they are unset again behind it.  An argument left None leaves its option as it stands."""
     L = lib()
     ctxs = [handle]
     if multi:
         ctxs = list(itertools.takewhile(bool, (L.yolo2_hip_multi_ctx(handle, i) for i in itertools.count())))
-    given = [(n, v) for n, v in ((b"jpeg_subsample", subsample), (b"jpeg_restart", restart)) if v is not None]
+    given = [(n, v) for n, v in ((b"jpeg_subsample", subsample), (b"jpeg_restart", restart), (b"jpeg_optimize", optimize)) if v is not None]
     try:
         for c in ctxs:
             for name, v in given:
@@ -1507,7 +1513,7 @@ def jpeg_mode(handle, subsample=None, restart=None, multi: bool = False):
                 L.yolo2_hip_set_option(c, name, None)
 
 
-def jpeg_encode(rgb, quality: int = 80, stream: int = 0, subsample: int = 0, restart: int = 0) -> bytes:
+def jpeg_encode(rgb, quality: int = 80, stream: int = 0, subsample: int = 0, restart: int = 0, optimize: bool = False) -> bytes:
     """yolo2_hip_jpeg_encode_rgb24: the same stream as write_jpg_host, encoded on the GPU (the mode through the process-wide options)"""
     im = _rgb24(rgb)
     L = lib()
@@ -1521,7 +1527,7 @@ def jpeg_encode(rgb, quality: int = 80, stream: int = 0, subsample: int = 0, res
         check(L.yolo2_hip_alloc(max(im.nbytes, 16), C.byref(src)), "alloc")
         check(L.yolo2_hip_alloc(cap, C.byref(dst)), "alloc")
         check(L.yolo2_hip_memcpy_h2d(src, im.ctypes.data_as(C.c_void_p), im.nbytes), "h2d")
-        with jpeg_mode(None, subsample or None, restart or None):
+        with jpeg_mode(None, subsample or None, restart or None, optimize=1 if optimize else None):
             check(L.yolo2_hip_jpeg_encode_rgb24(src, w, h, quality, dst, cap, C.byref(size), C.c_void_p(stream)), "yolo2_hip_jpeg_encode_rgb24")
         out = np.empty(size.value, dtype=np.uint8)
         check(L.yolo2_hip_memcpy_d2h(out.ctypes.data_as(C.c_void_p), dst, out.nbytes), "d2h")
@@ -1631,15 +1637,15 @@ def _jpeg_room(hw, subsample, restart) -> int:
 
 
 def annotate_images_jpeg(handle, images, dets, counts, batch: int, thresh: float, quality: int = 80, labels=None, pixfmt=None, multi: bool = False,
-                         subsample=None, restart=None):
+                         subsample=None, restart=None, optimize=None):
     """yolo2_hip_annotate_images_pix_jpeg_host / its multi form: annotate_images, with the frames back as JPEG streams ->
     (list of bytes, records drawn per frame).  Room per frame: the raw frame's size, and - for the rare frame that compresses to
-    more than that - a second call with the encoder's bound.  subsample / restart: options jpeg_subsample / jpeg_restart for this
-    call (jpeg_mode)."""
+    more than that - a second call with the encoder's bound.  subsample / restart / optimize: options jpeg_subsample / jpeg_restart /
+    jpeg_optimize for this call (jpeg_mode)."""
     shapes = [_pix_hw(pixfmt, np.asarray(im).shape) for im in images]
     room = [_jpeg_room(s, subsample, restart) for s in shapes]
     caps = [min(room[f], s[0] * s[1] * 3 + 4096) for f, s in enumerate(shapes)]
-    with jpeg_mode(handle, subsample, restart, multi):
+    with jpeg_mode(handle, subsample, restart, multi, optimize):
         for attempt in range(2):
             rc, outs, sizes, drawn = annotate_images_jpeg_raw(handle, images, dets, counts, batch, thresh, quality, caps, labels=labels, pixfmt=pixfmt,
                                                               multi=multi)
@@ -1696,14 +1702,14 @@ def loop_images_raw(handle, images, pixfmt, precision, flags, thresh, nms, batch
 
 def loop_images(handle, images, pixfmt=None, precision: str = "int16", tail: str = "core", thresh: float = 0.24, nms: float = 0.45,
                 labels=None, jpeg_quality=None, batch: int = 64, cap: int = 845, multi: bool = False, out_order: str = "rgb",
-                jpeg_subsample=None, jpeg_restart=None):
+                jpeg_subsample=None, jpeg_restart=None, jpeg_optimize=None):
     """yolo2_hip_loop_images_pix / its multi form: the camera loop as one call - host images -> {"dets": per-frame record arrays (one
     per detection, best class), "counts", "final_q" (int16 only, else None), "frames": the annotated frames as uint8 [h][w][3] (or,
     with jpeg_quality 1..100, as JPEG byte strings), "drawn": records drawn per frame}.  The frames go up once; records, draw items
     and the painted frames are made on the device.  out_order "bgr": the raw frames come back as B G R (YOLO2_LOOP_OUT_BGR24, what
     cv2.imshow / cv2.VideoWriter take); "nv12" / "i420": as planar YUV 4:2:0, uint8 [h * 3 / 2][w], what video encoders take
     (YOLO2_LOOP_OUT_NV12 / _I420; even sizes only; rgb24_to_yuv420 of the "rgb" frame).  Each an error together with jpeg_quality.
-    jpeg_subsample / jpeg_restart: the options of those names for this call (jpeg_mode)."""
+    jpeg_subsample / jpeg_restart / jpeg_optimize: the options of those names for this call (jpeg_mode)."""
     if precision not in LOOP_PRECISIONS:
         raise ValueError(f"precision must be one of {tuple(LOOP_PRECISIONS)}, not {precision!r}")
     out_format = _loop_out_format(out_order, jpeg_quality)
@@ -1716,7 +1722,7 @@ def loop_images(handle, images, pixfmt=None, precision: str = "int16", tail: str
     else:
         caps = [_loop_raw_bytes(out_order, s) for s in shapes]
     name = f"yolo2_hip_{'multi_' if multi else ''}loop_images_pix"
-    with jpeg_mode(handle, jpeg_subsample, jpeg_restart, multi):
+    with jpeg_mode(handle, jpeg_subsample, jpeg_restart, multi, jpeg_optimize):
         for attempt in range(2):
             rc, dets, counts, q, outs, sizes, drawn = loop_images_raw(handle, images, pixfmt, LOOP_PRECISIONS[precision], flags, thresh, nms, batch, cap,
                                                                       labels, out_format, int(jpeg_quality) if jpeg else 0, caps, multi=multi)
@@ -1782,7 +1788,7 @@ def loop_jpegs_raw(handle, streams, precision, flags, thresh, nms, batch, cap, l
 
 def loop_jpegs(handle, streams, precision: str = "int16", tail: str = "core", thresh: float = 0.24, nms: float = 0.45, labels=None,
                jpeg_quality=None, batch: int = 64, cap: int = 845, multi: bool = False, strict: bool = True, out_order: str = "rgb",
-               jpeg_subsample=None, jpeg_restart=None):
+               jpeg_subsample=None, jpeg_restart=None, jpeg_optimize=None):
     """yolo2_hip_loop_images_jpeg / its multi form: the camera loop as one call from JPEG streams (bytes) - or, mixed in, raw frames
     (uint8 [h][w][3] arrays, e.g. decoded on the host) - with the decoder, the network, the painter and the encoder on the device.
     Returns loop_images' dictionary plus "status" (int32 [n]; not 0: the decoder flagged the frame, its counts and drawn are 0 and
@@ -1805,7 +1811,7 @@ def loop_jpegs(handle, streams, precision: str = "int16", tail: str = "core", th
     else:
         caps = [_loop_raw_bytes(out_order, s) for s in shapes]
     name = f"yolo2_hip_{'multi_' if multi else ''}loop_images_jpeg"
-    with jpeg_mode(handle, jpeg_subsample, jpeg_restart, multi):
+    with jpeg_mode(handle, jpeg_subsample, jpeg_restart, multi, jpeg_optimize):
         for attempt in range(2):
             rc, dets, counts, q, outs, sizes, drawn, status, ws, hs = loop_jpegs_raw(handle, streams, LOOP_PRECISIONS[precision], flags, thresh, nms,
                                                                                      batch, cap, labels, out_format, int(jpeg_quality) if jpeg else 0,
@@ -1984,10 +1990,11 @@ class Yolo2HipMulti:
         return region, q.value
 
     def annotate_images(self, images, dets, counts, batch_per_device: int, thresh: float, labels=None, pixfmt=None, jpeg_quality=None,
-                        jpeg_subsample=None, jpeg_restart=None):
+                        jpeg_subsample=None, jpeg_restart=None, jpeg_optimize=None):
         """annotated frames, shard i painted by device i (module-level annotate_images)"""
         return annotate_images(self._m, images, dets, counts, batch_per_device, thresh, labels=labels, pixfmt=pixfmt, multi=True,
-                               jpeg_quality=jpeg_quality, jpeg_subsample=jpeg_subsample, jpeg_restart=jpeg_restart)
+                               jpeg_quality=jpeg_quality, jpeg_subsample=jpeg_subsample, jpeg_restart=jpeg_restart,
+                               jpeg_optimize=jpeg_optimize)
 
     def loop_images(self, images, batch_per_device: int = 64, **kw):
         """the camera loop as one call, shard i on device i (module-level loop_images)"""
